@@ -15,6 +15,12 @@ rank's batch.
         shard ("replicas only"): one T1124 replica per rank is reported as `secondary`.
 Prints ONE JSON line on rank 0; its LAST key, `summary`, is a flat digest of every config and regime (survives a tail).
 
+A plain run sets up, warms up, times the K steps and prints the headline line (`metric`, `value`, `unit`, `higher_is_better`,
+`dtype`, `ms_per_step`).  Everything else the benchmark measures or checks -- the other BASELINE configs (`secondary`), the
+exact-fp32 library, the in-situ kernel rooflines, the CPU baseline, the parity figures against the reference's outputs -- runs
+only with `--full`.  `--dump-outputs DIR` writes what the timed path returned in its last step as DIR/<name>.npy (float32 /
+float64; the inputs are seeded fixtures, identical from run to run), so that two builds can be compared output for output.
+
 N > 1: the driver launches one rank per GPU with torch.distributed.run; run by hand without WORLD_SIZE, this script
 starts that launcher itself as a child process BEFORE anything touches the GPU and exits with its code.
 """
@@ -112,7 +118,7 @@ def reference_container_rates():
 
 
 def full_protocol_record():
-    """BASELINE.md section 3 by the letter, measured once on a GPU box (`python bench.py --cpu-protocol full`, ~2.5 minutes of host time)
+    """BASELINE.md section 3 by the letter, measured once on an MI355X host (`python bench.py --full --cpu-protocol full`, ~2.5 minutes of host time)
     and committed: profiles/<round>_cpu_baseline_full.json.  None if absent."""
     try:
         return json.load(open(os.path.join(ROOT, "profiles", "r05_cpu_baseline_full.json")))
@@ -178,7 +184,7 @@ def cpu_baseline(batch, init, weights, n_sample_steps, n_grad_steps):
                      f"of the same complex) under torch.no_grad after 2 warm-ups, graph recomputed per step as the reference does, "
                      f"{cores} threads = this box's CPU share for one GPU; {total_s:.1f} s measured, each sample scaled "
                      f"x{N_DIFFUSION_STEPS / per:g}.  Deviation from BASELINE.md section 3 (median of >= 5 FULL 100-step calls, ~110 s): "
-                     f"bounded to keep the default run within minutes"}
+                     f"bounded to keep the --full run within minutes"}
     if n_grad_steps > 0:
         wg = {k: v.clone().requires_grad_(True) for k, v in weights.items()}       # nn.Parameters, no torch.no_grad
         x = init
@@ -346,11 +352,16 @@ def main():
                     help="default: t1124 (BASELINE configs[1]) on one GPU, c5 (configs[4]: the 256 complexes sharded over the ranks) on several; "
                          "c5share = one GPU's share of configs[4] at 8 GPUs as one packed batch (the profiling workload of that regime)")
     ap.add_argument("--proximal", action="store_true", help="add the 50-step proximal optimisation (configs[2] / configs[3])")
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beyond the headline: secondary configs, "
+                    "exact-fp32 library, kernel rooflines, CPU baseline, parity against the reference's outputs (--cpu-*, "
+                    "--no-secondary and --no-roofline shape these and only act with --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy")
     ap.add_argument("--cpu-steps", type=int, default=50, help="diffusion steps of the CPU-baseline sample (0 = skip)")
     ap.add_argument("--cpu-grad-steps", type=int, default=4, help="steps of the autograd-on CPU sample (0 = skip)")
     ap.add_argument("--cpu-protocol", default="bounded", choices=["bounded", "full"],
                     help="full: BASELINE.md section 3 by the letter (5 full 100-step calls after 2 full warm-ups, ~2.5 minutes of host time) "
-                         "instead of the bounded sample; its committed record rides on every line as cpu_baseline.full_protocol")
+                         "instead of the bounded sample; its committed record rides on every --full line as cpu_baseline.full_protocol")
     ap.add_argument("--cpu-threads", type=int, default=0, help="threads of the CPU baseline (0 = this box's CPU share for one GPU: 16)")
     ap.add_argument("--no-secondary", action="store_true", help="skip the other BASELINE configs (`secondary` list)")
     ap.add_argument("--no-roofline", action="store_true", help="skip the in-situ kernel timing passes (child runs)")
@@ -365,6 +376,8 @@ def main():
 
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(spawn_ranks(args.gpus))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -376,7 +389,8 @@ def main():
         # the driver's command line carries no --workload: one GPU measures the configuration the metric is quoted on, several GPUs
         # measure the configuration BASELINE.json states for them (a single complex does not shard)
         args.workload = "t1124" if world == 1 else "c5"
-    want_secondary = not args.no_secondary and not args.proximal
+    want_secondary = args.full and not args.no_secondary and not args.proximal
+    want_roofline = args.full and not args.no_roofline
     # ---- host-side inputs that take a process pool: BEFORE anything touches the GPU (forked workers) -----------------------
     cores = min(16, os.cpu_count() or 1)
     if args.build_workers > 0:
@@ -428,7 +442,7 @@ def main():
     from packppi_amd import lib as _lib0
     lib_is_split_f16 = _lib0.load().pp_edge_variant() == 1      # 1 = split-f16 (default), 0 = exact fp32 (libpackppi_hip.f32.so)
     model.schedule = torch.linspace(1, 0, N_DIFFUSION_STEPS + 1)
-    counters = regime_counters()
+    counters = regime_counters() if want_roofline else {}
     ref_chi, complexes = None, None
 
     def fence():
@@ -507,7 +521,7 @@ def main():
                 "s1500": "synthetic 1500-residue 2-chain complex (default_rng(1500)), 1 per GPU"}[args.workload]
         residues = batch.true_residues()
         gb, init_d = batch.to(dev), init.to(dev)
-        ctx = model._context(gb)
+        ctx = model._context(gb) if want_roofline else None
 
         # One timed pass = what TDiffusionModule.sampling() costs on a batch it has not seen: the per-complex preparation
         # (kNN graph, frames, edge embedding, layer-0 static products: pp_complex_prepare, a fresh context) + 100 evaluations.
@@ -520,10 +534,26 @@ def main():
             return chi
 
     elapsed, chi = timed(one_pass, args.steps, args.warmup)
+    if args.dump_outputs:
+        if complexes is None:
+            outs = {"chi": chi}
+        else:
+            # configs[4]: what sample_sharded returns -- this rank's angles (complex by complex, in id order, along the
+            # residue axis) and the metric rows of all 256 complexes with their ids
+            outs = {"chi": torch.cat([chi[i][0] for i in sorted(chi)], 0), "metric_ids": c5_last["ids"], "metric_rows": c5_last["rows"]}
+        dump_outputs(args.dump_outputs, outs, "" if world == 1 else f"rank{rank}_")
     total_res = allsum(residues)
 
     # per-complex metric rows: the one real collective of the path (RCCL all-gather of fixed-width rows)
-    if complexes is None and batch is None:
+    if not args.full:
+        # the headline alone: no metric rows or parity figures beyond what the timed pass itself produced
+        atom_rmsd = None
+        rows_gathered = int(c5_last["ids"].numel()) if complexes is not None else 0
+        cnt = torch.tensor([1.0], device=dev)
+        if dist is not None:
+            dist.all_reduce(cnt)
+        ranks_seen = int(cnt.item())
+    elif complexes is None and batch is None:
         atom_rmsd, row = None, torch.zeros(13, device=dev)
         rows = [row]
         ranks_seen, rows_gathered = 1, 0
@@ -547,7 +577,7 @@ def main():
             dist.all_reduce(cnt)
         ranks_seen = int(cnt.item())
     max_dchi = None
-    if ref_chi is not None and not args.proximal:
+    if args.full and ref_chi is not None and not args.proximal:
         d = (chi.cpu().double() - ref_chi.double()).abs()
         d = torch.minimum(d, (2 * np.pi - d).abs())[batch.SC_D_mask.bool()]
         max_dchi = float(d.max())
@@ -596,7 +626,7 @@ def main():
                                  "end_state_vs_reference_fp64_rad": float((end - torch.from_numpy(z["chi64_step50"]).double()).abs().max()),
                                  "reference_fp32_vs_fp64_rad": float(z["div_32_64"][-1]),
                                  "held_to": PROX_HELD_TO}
-            if regime and not args.no_roofline:
+            if regime and want_roofline:
                 cx_ = Context(model._plan, gb_)
                 t_e, n_e = insitu_edge(cx_, init_d_, model.schedule)
                 regimes[regime] = regime_entry(regime, b_.true_residues(), cx_.K, t_e, n_e, counters)
@@ -606,7 +636,7 @@ def main():
             e2, gb2, last2 = single_entry("configs[2]", "data/T1124_lig.pdb, 100 steps + 50 proximal Adam steps (vtf 12, tol 0.5, lamda 1)",
                                           batch, init, ref_chi, True, "g6_prox_T1124")
             secondary.append(e2)
-            if not args.no_roofline:
+            if want_roofline:
                 prox_roof = {"T1124": proximal_roofline(gb2, last2["sampled"])}
             bs, inits_, refs = load_s1500()
             secondary.append(single_entry("S1500", "synthetic 1500-residue 2-chain complex, 100 steps, no proximal", bs, inits_, refs,
@@ -614,7 +644,7 @@ def main():
             e3, gb3, last3 = single_entry("configs[3]", "synthetic 1500-residue complex, 100 steps + 50 proximal Adam steps",
                                           bs, inits_, refs, True, "g6_prox_S1500")
             secondary.append(e3)
-            if not args.no_roofline:
+            if want_roofline:
                 prox_roof["S1500"] = proximal_roofline(gb3, last3["sampled"])
         if complexes is None:
             # one GPU's share of configs[4] when it runs on 8 GPUs: rank r takes shard (r mod 8) of parallel.shard_complexes(256
@@ -633,7 +663,7 @@ def main():
                               "steps": 3, "warmup": 1, "complexes": len(c5) * world,
                               "max_abs_dchi_vs_reference_rad": None,
                               "parity_is": "tests/test_hip_parity.py::test_c5_all_256_complexes_match_reference (all 256 vs the reference, worst 8.6e-6 rad)"})
-            if not args.no_roofline:
+            if want_roofline:
                 from packppi_amd.batch import pack
                 cx5 = Context(model._plan, pack(c5))
                 t_e, n_e = insitu_edge(cx5, c5_x0, model.schedule)
@@ -667,7 +697,7 @@ def main():
     # begin and end), the interval rocprofv3's kernel trace of this command reports (profiles/<PROFILE_TAG>_kernel_stats.csv).
     roof = None
     dtype = None
-    if complexes is None and not args.no_roofline:
+    if complexes is None and want_roofline:
         insitu = {}
         for which, kname in ((1, "k_edge_update"), (0, "k_node_message"), (2, "k_node_update")):
             ctx.profile_kernel(which)
@@ -766,20 +796,21 @@ def main():
             if args.workload == "t1124" else "synthetic (seeded random weights, random-backbone complexes, seeded initial noise)",
             "config": {"workload": name, "diffusion_steps": N_DIFFUSION_STEPS, "proximal": bool(args.proximal),
                        "residues_per_gpu": residues, "residues_rank0": residues, "residues_total": total_res, "mode": "ode"},
-            "parity": {"max_abs_dchi_vs_reference_rad": max_dchi, "atom_rmsd": atom_rmsd,
-                       "proximal_configs_held_to": PROX_HELD_TO},
             "ranks_seen": ranks_seen, "metrics_rows_gathered": rows_gathered, "dist_backend": backend,
         }
+        if args.full:
+            out["parity"] = {"max_abs_dchi_vs_reference_rad": max_dchi, "atom_rmsd": atom_rmsd, "proximal_configs_held_to": PROX_HELD_TO}
         if complexes is not None:
             out["config"]["complexes_total"] = 256
             out["config"]["complexes_this_rank"] = len(complexes)
+        if complexes is not None and args.full:
             out["parity"]["parity_is"] = "tests/test_hip_parity.py::test_c5_all_256_complexes_match_reference (all 256 vs the reference, <= 1e-4 rad)"
         if roof is not None:
             out["dtype"] = dtype
             out["roofline"] = roof
         if secondary is not None:
             out["secondary"] = secondary
-        if args.cpu_steps > 0 and args.gpus == 1 and complexes is None and batch is not None:
+        if args.full and args.cpu_steps > 0 and args.gpus == 1 and complexes is None and batch is not None:
             if args.cpu_protocol == "full":
                 out["cpu_baseline"] = cpu_baseline_full(batch, init, weights, args.cpu_threads or min(16, os.cpu_count() or 1))
             else:
@@ -799,7 +830,7 @@ def make_summary(out):
     short = {"configs[2]": "c2_t1124_prox", "S1500": "s1500", "configs[3]": "c3_s1500_prox", "configs[4] share": "c4_share_32cx",
              "configs[4] whole, one GPU": "c4_whole_1gpu", "configs[1], exact-fp32 library": "c1_f32lib", "configs[1] replicas": "c1_replicas"}
     head = "c4_sharded" if out["scaling"] == "strong" else ("c1_t1124" if "T1124" in out["config"]["workload"] else "headline")
-    cfg = {head: [r3(out["value"]), r3(out["ms_per_step"]), r3(out["parity"]["max_abs_dchi_vs_reference_rad"])]}
+    cfg = {head: [r3(out["value"]), r3(out["ms_per_step"]), r3((out.get("parity") or {}).get("max_abs_dchi_vs_reference_rad"))]}
     for e in out.get("secondary") or []:
         if "value" in e:
             cfg[short.get(e["config"], e["config"])] = [r3(e["value"]), r3(e["ms_per_step"]), r3(e.get("max_abs_dchi_vs_reference_rad"))]
@@ -830,7 +861,8 @@ def run_f32_child():
     if not os.path.exists(lib):
         entry["error"] = "libpackppi_hip.f32.so is not built (python __graft_entry__.py builds it)"
         return entry
-    cmd = [sys.executable, os.path.abspath(__file__), "--steps", "5", "--warmup", "2", "--cpu-steps", "0", "--no-secondary", "--no-roofline"]
+    cmd = [sys.executable, os.path.abspath(__file__), "--full", "--steps", "5", "--warmup", "2", "--cpu-steps", "0", "--no-secondary",
+           "--no-roofline"]
     try:
         env = {k: v for k, v in os.environ.items() if k not in RENDEZVOUS_ENV}
         r = subprocess.run(cmd, env=dict(env, PACKPPI_LIB=lib), capture_output=True, text=True, timeout=300)
@@ -842,6 +874,26 @@ def run_f32_child():
     except Exception as exc:          # the headline must not depend on this leg
         entry["error"] = f"{type(exc).__name__}: {exc}"[:300]
     return entry
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, prefix=""):
+    """Write {name: tensor} as out_dir/<prefix><name>.npy: float64 stays float64, everything else becomes float32.  An array
+    larger than its share of DUMP_LIMIT_BYTES is written as a fixed, seeded sample of its flattened elements (the sorted
+    indices go next to it as <name>_sample_index.npy)."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // max(len(arrays), 1)
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+        if a.nbytes > share:
+            n = share // (a.itemsize + 8)          # the sample and its float64 index stay within the share
+            idx = np.sort(np.random.default_rng(20251003).choice(a.size, size=n, replace=False))
+            np.save(os.path.join(out_dir, f"{prefix}{name}_sample_index.npy"), idx.astype(np.float64))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, f"{prefix}{name}.npy"), a)
 
 
 def sample_sharded_local(model, complexes, inits):

@@ -186,7 +186,7 @@ def test_bench_two_ranks_as_the_driver_launches_it(workload, rows):
     env = dict(os.environ, BENCH_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "PACKPPI_LIB"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0"]
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--full"]
                        + (["--workload", workload, "--no-secondary"] if workload else []),
                        env=env, cwd=root, capture_output=True, text=True, timeout=1100)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-2500:]
@@ -225,7 +225,7 @@ def test_bench_one_rank_through_rccl():
         port = sk.getsockname()[1]
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr", "127.0.0.1",
                         "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "0",
-                        "--cpu-steps", "0", "--no-secondary", "--workload", "c5"],
+                        "--full", "--cpu-steps", "0", "--no-secondary", "--workload", "c5"],
                        env=env, cwd=root, capture_output=True, text=True, timeout=900)
     if r.returncode != 0 and any(k in r.stderr for k in ("ncclSystemError", "ncclInternalError", "unhandled system error",
                                                           "ncclUnhandledCudaError", "NCCL WARN")) and "Traceback" in r.stderr \
@@ -237,3 +237,34 @@ def test_bench_one_rank_through_rccl():
     out = json.loads(lines[0])
     assert out["dist_backend"] == "nccl" and out["n_gpus"] == 1 and out["ranks_seen"] == 1
     assert out["metrics_rows_gathered"] == 256 and out["value"] > 0
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """`python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` as the driver runs it: a fresh child process, the
+    headline line only (none of the --full parts), K timed steps, and DIR/chi.npy = the angles the last timed step returned --
+    float32, the T1124 fixture's shape, within 1e-4 rad of the reference's 100-step output on the same noise."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "PACKPPI_LIB", "TORCHELASTIC_RUN_ID"):
+        env.pop(k, None)
+    out_dir = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                        "--dump-outputs", str(out_dir)], env=env, cwd=root, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-2500:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    out = json.loads(lines[0])
+    assert out["steps"] == 2 and out["warmup"] == 1 and out["ms_per_step"] > 0 and out["higher_is_better"] is True
+    assert out["metric"] == "sampled residues/sec at 100 diffusion steps" and out["unit"] == "residues/s" and out["dtype"].startswith("f32")
+    assert abs(out["value"] - 738 * 1e3 / out["ms_per_step"]) < 1e-6 * out["value"]
+    assert not {"secondary", "roofline", "cpu_baseline", "parity"} & set(out) and list(out)[-1] == "summary"
+    assert sorted(os.listdir(out_dir)) == ["chi.npy"]
+    chi = np.load(out_dir / "chi.npy")
+    z = np.load(os.path.join(root, "tests", "golden", "g4_T1124.npz"))
+    assert chi.dtype == np.float32 and chi.shape == z["chi_ode_100"].shape
+    d = torch.from_numpy(chi).double() - torch.from_numpy(z["chi_ode_100"]).double()
+    d = torch.minimum(d.abs(), (2 * np.pi - d.abs()).abs())[torch.from_numpy(z["batch.SC_D_mask"]).bool()]
+    assert float(d.max()) < 1e-4, float(d.max())

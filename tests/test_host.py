@@ -174,12 +174,11 @@ def test_hot_path_configs_are_read_and_checked(tmp_path, weights):
         config.load_hot_path_configs(tmp_path / "nowhere")
     with pytest.raises(RuntimeError, match="annealed_temp"):         # not a number at all; 0 and null are the reference's "no annealing"
         TDiffusionModule(weights, sample_cfg={"annealed_temp": float("nan")}, device="cuda")
-    ref = "/root/reference/configs"
-    if os.path.isdir(ref):                                           # the reference's own tree (absent on the GPU box)
-        r = config.load_hot_path_configs(ref)
-        config.check_compiled_dims(r.encoder_cfg, r.model_cfg)
-        assert r.sample_cfg["annealed_temp"] == 3 and r.sample_cfg["mode"] == "ode" and r.sample_cfg["num_steps"] == 50
-        assert r.ckpt_path is None
+    # the reference's own four hot-path files, unchanged (fixture tests/golden/configs/, laid out like its configs/)
+    r = config.load_hot_path_configs(os.path.join(GOLD, "configs"))
+    config.check_compiled_dims(r.encoder_cfg, r.model_cfg)
+    assert r.sample_cfg["annealed_temp"] == 3 and r.sample_cfg["mode"] == "ode" and r.sample_cfg["num_steps"] == 50
+    assert r.ckpt_path is None
 
 
 def test_rebalanced_relu_chains_are_the_same_network(weights):
@@ -306,14 +305,15 @@ def test_cli_flags_match_reference():
         eval_diffusion.main(["--outdir", "x"])
 
 
-def test_T1124_pdb_parses_to_the_golden_batch():
+def test_T1124_pdb_parses_to_the_golden_batch(tmp_path):
     """data/T1124_lig.pdb itself (11 208 ATOM records, 5 527 hydrogens, 1 313 alternate-location flags, 132 HETATM) through
     pdb_io + featurize == the batch the reference's prot_to_data produced from it (tests/golden/g4_T1124.npz, asserted
-    equal at generation time by tools/oracle/make_golden.py).  The file lives in the reference checkout: skipped where that
-    is absent (the GPU box)."""
-    path = "/root/reference/data/T1124_lig.pdb"
-    if not os.path.exists(path):
-        pytest.skip("reference checkout not present")
+    equal at generation time by tools/oracle/make_golden.py).  The file is stored gzipped as tests/golden/T1124_lig.pdb.gz."""
+    import gzip
+    import shutil
+    path = str(tmp_path / "T1124_lig.pdb")
+    with gzip.open(os.path.join(GOLD, "T1124_lig.pdb.gz"), "rb") as src, open(path, "wb") as dst:
+        shutil.copyfileobj(src, dst)
     from packppi_amd.batch import TENSOR_KEYS
     from packppi_amd.featurize import protein_to_batch
     from packppi_amd.pdb_io import from_pdb_file
@@ -473,3 +473,28 @@ def test_bench_summary_is_small_and_last():
     s = bench.make_summary(out)
     assert len(json.dumps(s)) < 1500, len(json.dumps(s))
     assert s["cfg"]["c1_t1124"][0] == 60970.0 and "c4_whole_1gpu" in s["cfg"] and set(s["roof"]) == {"t1124", "s1500", "c5"}
+
+
+def test_bench_dump_outputs_types_and_cap(tmp_path):
+    """bench.py --dump-outputs: every array as float32 (float64 kept), and an array beyond the 64 MB cap as the same seeded
+    sample of its elements on every call, with the sample's indices next to it."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    chi = torch.rand(1, 30, 4)
+    bench.dump_outputs(str(tmp_path / "a"), {"chi": chi, "ids": torch.arange(5), "d": torch.ones(3, dtype=torch.float64)})
+    a = np.load(tmp_path / "a" / "chi.npy")
+    assert a.dtype == np.float32 and np.array_equal(a, chi.numpy())
+    assert np.load(tmp_path / "a" / "ids.npy").dtype == np.float32 and np.load(tmp_path / "a" / "d.npy").dtype == np.float64
+    old = bench.DUMP_LIMIT_BYTES
+    try:
+        bench.DUMP_LIMIT_BYTES = 4000
+        big = torch.arange(10000, dtype=torch.float32)
+        for d in ("b", "c"):
+            bench.dump_outputs(str(tmp_path / d), {"big": big}, prefix="rank1_")
+        s1, i1 = np.load(tmp_path / "b" / "rank1_big.npy"), np.load(tmp_path / "b" / "rank1_big_sample_index.npy")
+        assert s1.nbytes + i1.nbytes <= 4000 and np.array_equal(s1, big.numpy()[i1.astype(np.int64)])
+        assert np.array_equal(s1, np.load(tmp_path / "c" / "rank1_big.npy"))
+    finally:
+        bench.DUMP_LIMIT_BYTES = old

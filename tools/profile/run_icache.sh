@@ -8,7 +8,7 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 export HIP_FORCE_DEV_KERNARG=${HIP_FORCE_DEV_KERNARG:-1}
 cd /tmp
-BENCH="python3 $ROOT/bench.py --steps 1 --warmup 1 --cpu-steps 0 --no-secondary --no-roofline $ICACHE_BENCH_ARGS"
+BENCH="python3 $ROOT/bench.py --full --steps 1 --warmup 1 --cpu-steps 0 --no-secondary --no-roofline $ICACHE_BENCH_ARGS"
 i=0
 for SET in "SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQC_ICACHE_MISSES_DUPLICATE" \
            "SQ_IFETCH SQ_IFETCH_LEVEL SQ_WAVE_CYCLES SQ_BUSY_CYCLES" \

@@ -9,7 +9,7 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 export HIP_FORCE_DEV_KERNARG=${HIP_FORCE_DEV_KERNARG:-1}      # before rocprofv3 starts: its preloaded library initialises the HIP runtime ahead of python (packppi_amd/__init__.py would set it too late)
 cd /tmp
-BENCH="python3 $ROOT/bench.py --steps 2 --warmup 1 --cpu-steps 0 --no-secondary"
+BENCH="python3 $ROOT/bench.py --full --steps 2 --warmup 1 --cpu-steps 0 --no-secondary"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o run -- $BENCH > $OUT/stats.json 2> $OUT/stats.err
 echo "stats pass done"
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/fetch -o run -- $BENCH > $OUT/fetch.json 2> $OUT/fetch.err

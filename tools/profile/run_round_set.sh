@@ -24,9 +24,10 @@ bash tools/profile/run_stats_workload.sh $V c5share "" c5 > gpurun_out/set_stats
 bash tools/profile/run_stats_workload.sh $V t1124 --proximal t1124_prox > gpurun_out/set_stats_prox.log 2>&1
 echo stats done
 cp profiles/${PROFILE_TAG}_* gpurun_out/ 2>/dev/null || true      # (before the bench lines: a committed older line in profiles/ must not overwrite a fresh one)
-python bench.py --steps 20 --warmup 5 > gpurun_out/${PROFILE_TAG}_bench_t1124.json 2> gpurun_out/set_bench.err
-python bench.py --proximal > gpurun_out/${PROFILE_TAG}_bench_t1124_prox.json 2>> gpurun_out/set_bench.err
-python bench.py --workload s1500 > gpurun_out/${PROFILE_TAG}_bench_s1500.json 2>> gpurun_out/set_bench.err
-python bench.py --workload s1500 --proximal > gpurun_out/${PROFILE_TAG}_bench_s1500_prox.json 2>> gpurun_out/set_bench.err
-python bench.py --workload c5 > gpurun_out/${PROFILE_TAG}_bench_c5.json 2>> gpurun_out/set_bench.err
+LINES=${BENCH_LINES_DIR:-bench_out}; mkdir -p $LINES      # the bench lines (bench.py --full: every config on the line)
+python bench.py --full --steps 20 --warmup 5 > $LINES/${PROFILE_TAG}_bench_t1124.json 2> $LINES/set_bench.err
+python bench.py --full --proximal > $LINES/${PROFILE_TAG}_bench_t1124_prox.json 2>> $LINES/set_bench.err
+python bench.py --full --workload s1500 > $LINES/${PROFILE_TAG}_bench_s1500.json 2>> $LINES/set_bench.err
+python bench.py --full --workload s1500 --proximal > $LINES/${PROFILE_TAG}_bench_s1500_prox.json 2>> $LINES/set_bench.err
+python bench.py --full --workload c5 > $LINES/${PROFILE_TAG}_bench_c5.json 2>> $LINES/set_bench.err
 echo bench done
