@@ -156,7 +156,7 @@ void pp_ctx_destroy(pp_ctx *ctx);
  * search, clash partners and E_idx numbering stay inside each complex; every other stage is per row or per
  * edge.  Results equal those of each complex prepared on its own (K = min(32, length): complexes shorter
  * than 32 residues cannot be mixed with longer ones -> PP_ERR_UNSUPPORTED).  pp_proximal needs one complex
- * per ctx.  CONTRACT: the device table must describe the batch (seg_offsets[0] = 0, seg_offsets[n_seg] = the number of rows,
+ * per ctx; pp_proximal_packed optimises every complex of a packed ctx at once.  CONTRACT: the device table must describe the batch (seg_offsets[0] = 0, seg_offsets[n_seg] = the number of rows,
  * every length within [min_len, max_len]): the library sizes its launches from min_len / max_len and cannot read the table
  * back without stalling the stream; a table that disagrees is clamped where that is cheap, but the behaviour is undefined. */
 pp_status pp_complex_prepare_packed(pp_plan *plan, const pp_batch *batch, const int32_t *seg_offsets, int n_seg,
@@ -198,6 +198,24 @@ pp_status pp_clash(pp_ctx *ctx, const float *chi, float *per_res, float *dchi, v
 pp_status pp_proximal(pp_ctx *ctx, const float *chi, float lamda, int num_steps, float *chi_traj,
                       float *chi_last, float *losses, void *stream);
 
+/* proximal_optimizer for EVERY complex of a packed batch at once (a ctx from pp_complex_prepare_packed; a B = 1
+ * ctx counts as one complex, a padded B > 1 ctx gives PP_ERR_INVALID).  Each complex keeps the reference's
+ * per-complex semantics (optimize.py:5-73): its own mean-clash mask, its own 1/n in the loss and the gradient,
+ * its own loss list and accept rule -- the bits pp_proximal gives that complex on its own ctx.  One launch per
+ * Adam step for all complexes, no host read-back.
+ * norm_rows (HOST int32 [n_seg], read before the call returns, or NULL): the row count each complex's means
+ * divide by; NULL = its length.  The reference (and pp_proximal on a padded B = 1 batch) divides by the padded
+ * max_size, while batch.pack drops the trailing padding rows: they add exact zeros to every sum (zero angles
+ * there), so with norm_rows = the padded lengths the results equal the per-complex runs on the padded batches.
+ * An entry below min_len gives PP_ERR_INVALID.  CONTRACT: every entry >= its complex's length (the lengths are on
+ * the device only; the kernels use max(entry, length)).
+ * chi [1,N,4]; chi_traj (or NULL) [num_steps,1,N,4]; chi_last [1,N,4] the last step; chi_accepted [1,N,4] per
+ * complex chi_last where losses[s][num_steps-1] < losses[s][0], else chi (TorsionalDiffusion.py:296-298, decided
+ * on the device); losses (DEVICE) [n_seg][num_steps] the pre-step loss values.  Memory: the ctx of a packed
+ * batch holds the static clash-partner lists of the loop, 1.5 KB per row. */
+pp_status pp_proximal_packed(pp_ctx *ctx, const float *chi, float lamda, int num_steps, const int32_t *norm_rows,
+                             float *chi_traj, float *chi_last, float *chi_accepted, float *losses, void *stream);
+
 /* Measurement aid, no reference counterpart: average duration (ms) of one launch of a hot kernel
  * (which: 0 = node-message kernel, 1 = edge-update kernel), timed with HIP events on `stream`
  * around `iters` launches.  Synchronises the stream. */
@@ -205,7 +223,7 @@ pp_status pp_time_kernel(pp_ctx *ctx, int which, int iters, float *avg_ms, void 
 
 /* Measurement aid, no reference counterpart: in-situ duration of a hot kernel.  After
  * pp_profile_kernel(ctx, which) (0 node message, 1 edge update, 2 node update; 3 the one launch per Adam step
- * inside pp_proximal: clash loss + gradient, the step, the reconstruction at the new angles) every launch of that
+ * inside pp_proximal / pp_proximal_packed: clash loss + gradient, the step, the reconstruction at the new angles) every launch of that
  * kernel made by pp_score / pp_sample / pp_proximal carries a start / stop HIP event pair on the launch stream
  * (hipExtLaunchKernelGGL: the dispatch's own begin and end, the interval rocprofv3's kernel trace reports);
  * pp_profile_read waits for the last one, returns the summed intervals (ms) and the number of

@@ -684,6 +684,7 @@ static pp_status prepare_impl(pp_plan *plan, const pp_batch *b, const int32_t *s
     c->N = b->B * b->L;
     const int shortest = packed ? min_len : b->L;
     c->K = shortest < PP_TOP_K ? shortest : PP_TOP_K;
+    c->shortest = shortest;
     const size_t N = c->N, K = c->K;
     pp_status st = PP_OK;
     // one arena for all workspaces (a context per batch is created and destroyed on the sampling path: ~35 hipMalloc /
@@ -702,11 +703,15 @@ static pp_status prepare_impl(pp_plan *plan, const pp_batch *b, const int32_t *s
     }
     ALLOC(xyz, N * 42); ALLOC(rec, N * 64); ALLOC(axes, N * 24); ALLOC(rec2, N * 64); ALLOC(axes2, N * 24); ALLOC(brad, N); ALLOC(per_res, N); ALLOC(dchi, N * 4);
     ALLOC(px, N * 4); ALLOC(pm, N * 4); ALLOC(pv, N * 4); ALLOC(pz, N * 4); ALLOC(pxeff, N * 4); ALLOC(pmask, N);
-    if (c->B == 1) { ALLOC(cand, (size_t)N * 4 * PP_CL_CAP); ALLOC(cand_cnt, N * 4); }      // the proximal loop is defined for one complex (optimize.py:27)
+    // the proximal loop is defined for one complex (optimize.py:27): a B = 1 context, or every complex of a packed one (pp_proximal_packed)
+    const bool prox = c->B == 1 || packed;
+    if (prox) { ALLOC(cand, (size_t)N * 4 * PP_CL_CAP); ALLOC(cand_cnt, N * 4); }
     ALLOC(scal, 64);
     ALLOC(sat, 4);
     ALLOC(seg, N);
     ALLOC(prox_part, (size_t)PP_PROX_CHUNK * N);
+    if (prox) { ALLOC(prox_nrows, c->B); ALLOC(prox_seg, c->B); ALLOC(prox_inv, N); }
+    if (packed) ALLOC(seg_off, (size_t)n_seg + 1);
     c->max_steps = 1 << 20;
 #undef ALLOC
     c->last_stream = static_cast<hipStream_t>(stream);
@@ -737,6 +742,12 @@ static pp_status prepare_impl(pp_plan *plan, const pp_batch *b, const int32_t *s
         if (packed) hipLaunchKernelGGL(k_fill_seg_packed, dim3((c->N + 255) / 256), dim3(256), 0, s_, c->seg, c->N, seg_offsets, n_seg, c->L);
         else hipLaunchKernelGGL(k_fill_seg, dim3((c->N + 255) / 256), dim3(256), 0, s_, c->seg, c->N, c->L);
         if (hipGetLastError() != hipSuccess) { pp_set_error("segment table launch failed"); st = PP_ERR_HIP; }
+        // the complexes' first rows, kept for pp_proximal_packed (the caller's table need not outlive this call's stream work)
+        if (st == PP_OK && packed &&
+            hipMemcpyAsync(c->seg_off, seg_offsets, ((size_t)n_seg + 1) * sizeof(int32_t), hipMemcpyDeviceToDevice, s_) != hipSuccess) {
+            pp_set_error("copying the segment offsets failed");
+            st = PP_ERR_HIP;
+        }
     }
     if (st == PP_OK && hipMemsetAsync(c->sat, 0, 4 * sizeof(unsigned), static_cast<hipStream_t>(stream)) != hipSuccess) {
         pp_set_error("clearing the saturation word failed");
@@ -944,6 +955,30 @@ extern "C" pp_status pp_proximal(pp_ctx *c, const float *chi, float lamda, int n
     return pp_launch_proximal(c, chi, lamda, num_steps, chi_traj, chi_last, losses, static_cast<hipStream_t>(stream));
 }
 
+extern "C" pp_status pp_proximal_packed(pp_ctx *c, const float *chi, float lamda, int num_steps, const int32_t *norm_rows,
+                                        float *chi_traj, float *chi_last, float *chi_accepted, float *losses, void *stream) {
+    if (c) c->last_stream = static_cast<hipStream_t>(stream);
+    if (!c || !chi || !chi_last || !chi_accepted || !losses) FAIL(PP_ERR_INVALID, "pp_proximal_packed: null argument");
+    if (!c->packed && c->B != 1)
+        FAIL(PP_ERR_INVALID, "pp_proximal_packed: needs a context from pp_complex_prepare_packed (or a B = 1 one), not a padded B > 1 batch");
+    if (num_steps < 1) FAIL(PP_ERR_INVALID, "pp_proximal_packed: num_steps must be >= 1");
+    if (!c->plan->clash_params_set) FAIL(PP_ERR_INVALID, "pp_proximal_packed: call pp_plan_set_clash_params first");
+    if (!c->b.atom_mask || !c->b.residue_index) FAIL(PP_ERR_INVALID, "pp_proximal_packed: batch lacks atom_mask / residue_index");
+    // every complex is at least min_len rows long (for a B = 1 context: N): an entry below that is shorter than its complex for sure
+    // (the exact lengths are on the device only; the kernels take max(entry, length))
+    const int shortest = c->packed ? c->shortest : c->N;
+    if (norm_rows)
+        for (int s = 0; s < c->B; s++)
+            if (norm_rows[s] < shortest)
+                FAIL(PP_ERR_INVALID, "pp_proximal_packed: norm_rows[" + std::to_string(s) + "] = " + std::to_string(norm_rows[s]) +
+                                         " is below the shortest complex (" + std::to_string(shortest) + " rows)");
+    PP_HIP_CHECK(hipSetDevice(c->plan->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    // the host table is caller-owned: from pageable memory, hipMemcpyAsync has taken the data when it returns
+    if (norm_rows) PP_HIP_CHECK(hipMemcpyAsync(c->prox_nrows, norm_rows, (size_t)c->B * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    return pp_launch_proximal_packed(c, chi, lamda, num_steps, norm_rows != nullptr, chi_traj, chi_last, chi_accepted, losses, s);
+}
+
 // Measurement aid (bench.py): average duration of one launch of a hot kernel, timed with HIP events on
 // `stream` around `iters` back-to-back launches.  which: 0 = node message, 1 = edge update (layer 1 weights).
 // The ctx must have been through pp_score / pp_sample so that its state buffers hold real activations.
@@ -1027,7 +1062,7 @@ extern "C" pp_status pp_debug_score_prefix(pp_ctx *c, const float *chi, float t,
 // pp_profile_read synchronises, sums the pair intervals, reports (total ms, launches) and switches profiling off.
 extern "C" pp_status pp_profile_kernel(pp_ctx *c, int which) {
     if (!c || which < 0 || which > 3)
-        FAIL(PP_ERR_INVALID, "pp_profile_kernel: which must be 0 (node message), 1 (edge update), 2 (node update) or 3 (the Adam-step launch of pp_proximal: clash + gradient + step + reconstruction)");
+        FAIL(PP_ERR_INVALID, "pp_profile_kernel: which must be 0 (node message), 1 (edge update), 2 (node update) or 3 (the Adam-step launch of pp_proximal / pp_proximal_packed: clash + gradient + step + reconstruction)");
     c->prof_which = which;
     c->prof_n = 0;
     return PP_OK;

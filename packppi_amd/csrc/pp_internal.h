@@ -131,6 +131,7 @@ struct pp_ctx {
     pp_batch b;               // caller-owned device pointers
     int B, L, K, N;           // N = B*L nodes (packed context: B = number of complexes, L = longest, N = sum of lengths)
     bool packed = false;      // rows of the complexes back to back, no padding rows (pp_complex_prepare_packed)
+    int shortest = 0;         // packed context: the caller's min_len (else L)
     int2 *seg;                // [N] (first row, length) of the complex each row belongs to
     // static per complex
     int32_t *eidx;            // [N][K] global node index of each neighbour
@@ -166,6 +167,11 @@ struct pp_ctx {
     int32_t *cand;            // [N][4][PP_CL_CAP] proximal: static clash-partner candidates of every (residue, wave of its workgroup)
     int32_t *cand_cnt;        // [N][4] their number, -1 = more than PP_CL_CAP (that wave scans all partners as before)
     float *prox_part;         // [PP_PROX_CHUNK][ceil(N / 16)] per-block loss terms of the proximal steps
+    // pp_proximal_packed (packed contexts and B = 1): one proximal loop per complex, all complexes in the same launches
+    int32_t *seg_off;         // [B + 1] packed context: the first row of every complex, then N (a copy of the caller's table)
+    int32_t *prox_nrows;      // [B] the caller's norm_rows (the row count each complex's means divide by)
+    float2 *prox_seg;         // [B] per complex: (mean divisor, 1 / divisor), written by k_prox_init_seg
+    float *prox_inv;          // [N] 1 / divisor of the row's complex: the gradient weight of k_clash_seg
     float *scal;              // small scalar scratch
     unsigned *sat;            // sticky word: bit 0 = an edge kernel, bit 1 = a node kernel clamped a hidden activation at 65504
     // in-situ kernel timing (pp_profile_kernel): every launch of one hot kernel carries a start / stop event pair
@@ -295,6 +301,8 @@ pp_status pp_launch_atom14(pp_ctx *c, const float *chi, float *xyz, hipStream_t 
 pp_status pp_launch_clash(pp_ctx *c, const float *xyz, float *per_res, float *dchi, hipStream_t s, bool use_candidates = false);
 pp_status pp_launch_proximal(pp_ctx *c, const float *chi, float lamda, int nsteps, float *traj,
                              float *chi_last, float *losses, hipStream_t s);
+pp_status pp_launch_proximal_packed(pp_ctx *c, const float *chi, float lamda, int nsteps, bool norm_given, float *traj,
+                                    float *chi_last, float *chi_accepted, float *losses, hipStream_t s);
 
 void pp_edge_occupancy(int *node_msg, int *edge_upd);
 

@@ -4,6 +4,7 @@
     compute_residue_clash(batch, SC_D, vtf=12., tol=0.5)       clash.py:335-365
     find_clash_mask(batch, SC_D, vtf, tol)                     optimize.py:5-18
     proximal_optimizer(batch, SC_D, vtf, tol, lamda, steps)    optimize.py:21-73
+    proximal_optimizer_packed(packed_batch, SC_D, ...)        the same for every complex of a batch.pack() batch at once
 
 All tensors must live on the MI355X; there is no CPU path here.
 """
@@ -63,3 +64,15 @@ def proximal_optimizer(batch, SC_D, violation_tolerance_factor, clash_overlap_to
                                                num_steps, want_traj=True)
     loss_list = [float(v) for v in losses.cpu()]          # the one host sync of the whole optimisation
     return [traj[i] for i in range(num_steps)], loss_list
+
+
+def proximal_optimizer_packed(packed_batch, SC_D, violation_tolerance_factor, clash_overlap_tolerance, lamda, num_steps=50,
+                              norm_rows=None, want_traj=False):
+    """``proximal_optimizer`` for every complex of a packed batch (``batch.pack``; a B = 1 batch counts as one complex) in the same
+    launches, each complex with the reference's per-complex semantics (optimize.py:5-73: its own clash mask, 1/n, loss list) and
+    the accept rule of TDiffusionModule.sampling (TorsionalDiffusion.py:296-298) decided on the device.  ``norm_rows``: the row
+    count each complex's means divide by (None: its packed length; its padded ``max_size`` reproduces the run on the padded
+    batch, whose padding rows pack() dropped).  Returns (trajectory [num_steps, 1, N, 4] or None, last [1, N, 4],
+    accepted [1, N, 4], losses [n_complexes, num_steps]), all left on the device."""
+    return _ctx_for(packed_batch).proximal_packed(SC_D, violation_tolerance_factor, clash_overlap_tolerance, lamda, num_steps,
+                                                  norm_rows=norm_rows, want_traj=want_traj)

@@ -17,7 +17,7 @@ _lib = None
 
 SYMBOLS = ("pp_version", "pp_last_error", "pp_build_id", "pp_plan_set_knn_ties", "pp_plan_set_annealed_temp", "pp_plan_rebalanced_chains", "pp_rebalance_weights_host", "pp_plan_ln_scaled_features", "pp_ln_operand_scales_host", "pp_topk_aten_host", "pp_plan_create", "pp_plan_destroy", "pp_plan_set_clash_params",
            "pp_complex_prepare", "pp_complex_prepare_packed", "pp_ctx_destroy", "pp_ctx_get_graph", "pp_ctx_set_graph", "pp_score", "pp_sample", "pp_atom14",
-           "pp_clash", "pp_proximal", "pp_time_kernel", "pp_profile_kernel", "pp_profile_read", "pp_edge_variant", "pp_has_range_check", "pp_range_check", "pp_range_check_parts", "pp_ctx_saturated")
+           "pp_clash", "pp_proximal", "pp_proximal_packed", "pp_time_kernel", "pp_profile_kernel", "pp_profile_read", "pp_edge_variant", "pp_has_range_check", "pp_range_check", "pp_range_check_parts", "pp_ctx_saturated")
 
 
 KNN_TIES = {"lower_index": 0, "aten_cpu": 1, "aten_member": 2}
@@ -91,6 +91,7 @@ def load():
     lib.pp_atom14.argtypes = [vp, vp, vp, vp]
     lib.pp_clash.argtypes = [vp, vp, vp, vp, vp]
     lib.pp_proximal.argtypes = [vp, vp, f, i, vp, vp, vp, vp]
+    lib.pp_proximal_packed.argtypes = [vp, vp, f, i, vp, vp, vp, vp, vp, vp]
     lib.pp_time_kernel.argtypes = [vp, i, i, C.POINTER(C.c_float), vp]
     lib.pp_profile_kernel.argtypes = [vp, i]
     lib.pp_profile_read.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_int)]
@@ -278,6 +279,7 @@ class Context:
         pb = PPBatch(self.B, self.L, *[(self._t[k].data_ptr() if self._t[k] is not None else None)
                                        for k, _ in _BATCH_SPEC])
         h = C.c_void_p()
+        self.seg_offsets_host = None          # packed batch: the complexes' first rows and the total (host list)
         seg = _get(batch, "seg_offsets")
         if seg is None:
             _check(lib.pp_complex_prepare(plan.handle, C.byref(pb), _stream(dev), C.byref(h)), "pp_complex_prepare")
@@ -296,6 +298,7 @@ class Context:
             if self.B != 1 or len(offs) < 2 or offs[-1] != self.L or offs[0] != 0 or min(lens) < 1:
                 raise RuntimeError("seg_offsets does not describe this batch")
             self._t["seg_offsets"] = seg.to(device=dev, dtype=torch.int32).contiguous()
+            self.seg_offsets_host = offs
             self.K = min(32, min(lens))
             _check(lib.pp_complex_prepare_packed(plan.handle, C.byref(pb), self._t["seg_offsets"].data_ptr(), len(lens),
                                                  min(lens), max(lens), _stream(dev), C.byref(h)),
@@ -365,6 +368,34 @@ class Context:
         _check(load().pp_proximal(self.handle, _ptr(chi), float(lamda), int(num_steps), _ptr(traj), _ptr(last),
                                   _ptr(losses), _stream(self.plan.device)), "pp_proximal")
         return traj, last, losses
+
+    def proximal_packed(self, chi, vtf, tol, lamda, num_steps, norm_rows=None, want_traj=False):
+        """proximal_optimizer for every complex of a packed batch at once (a B = 1 batch counts as one complex): each complex with its
+        own clash mask, 1/n, losses and accept rule -- the bits ``proximal`` gives it alone.  ``norm_rows`` (one int per complex, or
+        None = the complexes' lengths): the row count each complex's means divide by; pass the padded ``max_size`` to reproduce the
+        run on a padded batch.  Returns (traj [num_steps, 1, N, 4] or None, last [1, N, 4], accepted [1, N, 4],
+        losses [n_complexes, num_steps]), all on the device; no host synchronisation."""
+        self.plan.set_clash_params(vtf, tol)
+        offs = self.seg_offsets_host if self.seg_offsets_host is not None else [0, self.L]
+        n_seg = len(offs) - 1 if self.B == 1 else self.B
+        nr = None
+        if norm_rows is not None:
+            nr = np.ascontiguousarray([int(x) for x in norm_rows], dtype=np.int32)
+            if nr.size != n_seg:
+                raise ValueError(f"norm_rows has {nr.size} entries for {n_seg} complexes")
+            lens = [b - a for a, b in zip(offs[:-1], offs[1:])]
+            short = [(k, int(r), n) for k, (r, n) in enumerate(zip(nr, lens)) if r < n]
+            if self.B == 1 and short:
+                k, r, n = short[0]
+                raise ValueError(f"norm_rows[{k}] = {r} is shorter than complex {k} ({n} rows)")
+        chi = self._chi(chi)
+        traj = self._new(num_steps, self.B, self.L, 4) if want_traj else None
+        last, accepted = self._new(self.B, self.L, 4), self._new(self.B, self.L, 4)
+        losses = self._new(n_seg, max(int(num_steps), 1))
+        _check(load().pp_proximal_packed(self.handle, _ptr(chi), float(lamda), int(num_steps),
+                                         C.c_void_p(nr.ctypes.data) if nr is not None else C.c_void_p(0), _ptr(traj), _ptr(last),
+                                         _ptr(accepted), _ptr(losses), _stream(self.plan.device)), "pp_proximal_packed")
+        return traj, last, accepted, losses
 
     def saturated(self) -> int:
         """Sticky flag word of this context: 0 = clean; bit 0 / bit 1 = a hidden activation was clamped at 65504 in an edge-level /

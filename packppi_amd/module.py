@@ -14,7 +14,7 @@ from typing import Any, Dict, Optional
 import numpy as np
 import torch
 
-from .functional import proximal_optimizer
+from .functional import proximal_optimizer, proximal_optimizer_packed
 from .lib import BatchKey, Context, Plan
 
 SAMPLE_DEFAULTS = dict(eval_epochs=1, sample_during_training=True, annealed_temp=3, mode="ode", use_proximal=True,
@@ -186,6 +186,10 @@ class TDiffusionModule:
 
     def sampling(self, batch, use_proximal: bool = False, return_list: bool = False, sde_noise=None):
         cfg = self.hparams.sample_cfg
+        packed = batch.get("seg_offsets") is not None if hasattr(batch, "get") else False
+        if packed and use_proximal and return_list:
+            raise ValueError("return_list=True needs a B = 1 batch; for a packed batch use "
+                             "functional.proximal_optimizer_packed (per-complex losses [n_complexes, num_steps])")
         t = torch.tensor([1.]).repeat_interleave(batch.max_size * batch.num_proteins).to(self.device)
         SC_D_sample, _ = self.add_sc_noise(batch, t)
         n_steps = len(self.schedule) - 1
@@ -199,6 +203,9 @@ class TDiffusionModule:
         SC_D_sample = self._context(batch).sample(SC_D_sample, self.schedule, cfg.mode, sde_noise)
         if not use_proximal:
             return SC_D_sample
+        if packed:            # every complex optimised on its own terms, accept rule per complex on the device
+            return proximal_optimizer_packed(batch, SC_D_sample, cfg.violation_tolerance_factor, cfg.clash_overlap_tolerance,
+                                             cfg.lamda, cfg.num_steps)[2]
         SC_D_resample_list, loss_list = proximal_optimizer(batch, SC_D_sample, cfg.violation_tolerance_factor,
                                                            cfg.clash_overlap_tolerance, cfg.lamda, cfg.num_steps)
         if return_list:

@@ -96,7 +96,7 @@ def gather_metric_rows(ids: torch.Tensor, rows: torch.Tensor, group=None) -> Tup
 
 
 def sample_sharded(model, complexes, use_proximal=False, group=None, init_chi=None, max_rows=200_000, lengths=None,
-                   rank=None, world=None):
+                   rank=None, world=None, packed_proximal=True):
     """Run the sampling path on this rank's share of ``complexes`` (list of B = 1 batches already on the rank's device)
     and gather every complex's metric row on every rank.  With ``lengths`` (the residue counts of ALL complexes, known to
     every rank) ``complexes`` may be a dict {complex id: batch} that holds only this rank's share -- a rank need not build
@@ -104,12 +104,15 @@ def sample_sharded(model, complexes, use_proximal=False, group=None, init_chi=No
     an N-rank job one after the other; the gather then only orders the local rows).
 
     The shard is sampled as ragged PACKED batches (``batch.pack``: no padding rows are launched; complexes shorter than 32
-    residues go alone because K = min(32, L)), at most ``max_rows`` residues per batch; the proximal stage, which the
-    reference defines for one complex at a time (optimize.py:27), and the metrics then run per complex.
+    residues go alone because K = min(32, L)), at most ``max_rows`` residues per batch.  The proximal stage, which the
+    reference defines for one complex at a time (optimize.py:27), runs on the packed group as well (``packed_proximal``: one
+    ``proximal_optimizer_packed`` call per group, every complex with its own clash mask, normalisers -- its padded
+    ``max_size``, as the per-complex call divides --, losses and accept rule: the same bits); ``packed_proximal=False`` keeps
+    one ``proximal_optimizer`` call per complex.  The metrics of the proximal branch run per complex.
     ``init_chi`` (optional, {complex id: [1, L, 4]}) injects the initial noised angles instead of drawing them.
     Returns (chi per local complex id, ids_all, rows_all)."""
     from .batch import pack, unpack
-    from .functional import proximal_optimizer
+    from .functional import proximal_optimizer, proximal_optimizer_packed
     if rank is None:
         rank = dist.get_rank(group) if dist.is_initialized() else 0
     if world is None:
@@ -134,7 +137,7 @@ def sample_sharded(model, complexes, use_proximal=False, group=None, init_chi=No
         rows_in += n
     if cur:
         groups.append(cur)
-    chis, row_of = {}, {}
+    chis, row_of, proxed = {}, {}, set()
     for grp in groups:
         if len(grp) == 1:
             i = grp[0]
@@ -153,6 +156,10 @@ def sample_sharded(model, complexes, use_proximal=False, group=None, init_chi=No
         if not use_proximal:          # the metrics of the whole group in one go (the proximal stage changes the angles first)
             for i, row in zip(grp, packed_metric_rows(model, pb, out, [int(complexes[i]["max_size"]) for i in grp])):
                 row_of[i] = row
+        elif packed_proximal:         # the proximal stage of the whole group in one go, each complex divided by its padded size
+            out = proximal_optimizer_packed(pb, out, cfg.violation_tolerance_factor, cfg.clash_overlap_tolerance, cfg.lamda,
+                                            cfg.num_steps, norm_rows=[int(complexes[i]["max_size"]) for i in grp])[2]
+            proxed.update(grp)
         for i, chi in zip(grp, unpack(pb, out)):
             L = int(complexes[i]["max_size"])
             if chi.shape[1] == L:
@@ -163,7 +170,7 @@ def sample_sharded(model, complexes, use_proximal=False, group=None, init_chi=No
                 chis[i] = full
     rows = []
     for i in mine:
-        if use_proximal:
+        if use_proximal and i not in proxed:
             lst, losses = proximal_optimizer(complexes[i], chis[i], cfg.violation_tolerance_factor,
                                              cfg.clash_overlap_tolerance, cfg.lamda, cfg.num_steps)
             if losses[-1] < losses[0]:
