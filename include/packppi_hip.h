@@ -216,6 +216,42 @@ pp_status pp_proximal(pp_ctx *ctx, const float *chi, float lamda, int num_steps,
 pp_status pp_proximal_packed(pp_ctx *ctx, const float *chi, float lamda, int num_steps, const int32_t *norm_rows,
                              float *chi_traj, float *chi_last, float *chi_accepted, float *losses, void *stream);
 
+/* ---- PackPPI-AP: binding ddG prediction (src/models/AffinityPrediction.py) ----------------------------------------------
+ * The pretrained network at t = 0 is pp_score (get_pret_feature, :109-122: hV of a ctx of the wild-type batch and of one of
+ * the mutant batch).  The mutation encoder + MPNN (mode `network`, :50-71) run on a plan of their own: pp_plan_create with
+ * the score network's weight layout built from mutation_encoder.* / mutation_mpnn.*, node-embedding columns 35..50 and the
+ * decoder zero (packppi_amd/weights.py mutation_branch_state_dict), and on a ctx whose residue_mask is the local mask of
+ * get_local_subgraph (:124-145), which drives the neighbour search, mask_attend and mask_V as ProteinEncoder's `mask` does. */
+typedef struct pp_affinity pp_affinity; /* the tensors AffinityPrediction owns besides the two networks, on one GPU */
+
+#define PP_AFF_N_WEIGHTS 101889u        /* mode network: mut_bias, seq_embedding, mutation_fusion, ddg_predictor */
+#define PP_AFF_N_WEIGHTS_LINEAR 33153u  /* mode linear: ddg_predictor only */
+
+/* Replaces the construction of mut_bias, seq_embedding, mutation_fusion and ddg_predictor (AffinityPrediction.py:73-94) and
+ * their load_from_checkpoint.  `weights` is a HOST buffer of the tensors of packppi_amd/weights.py::affinity_head_spec(mode)
+ * concatenated in that order, nn.Linear / nn.Embedding layouts: n_weights = PP_AFF_N_WEIGHTS (network) or
+ * PP_AFF_N_WEIGHTS_LINEAR (linear; pp_affinity_encode then gives PP_ERR_INVALID).  mut_bias row 0 is used as given. */
+pp_status pp_affinity_create(const float *weights, size_t n_weights, int device, pp_affinity **aff);
+void pp_affinity_destroy(pp_affinity *aff);
+
+/* Replaces AffinityPrediction.encode (:148-169) after the pretrained features: the mutation encoder's node embedding
+ * Linear(35, 128) + LayerNorm from `residue_type` [N] and `sc_sincos` [N,4,2] AS GIVEN (the batch's SC_D_sincos or
+ * SC_D_sincos_mut, not recomputed from angles), the fusion Linear(384,128) ReLU Linear(128,128) of
+ * [hV_pret | that embedding | seq_embedding(residue_type)] plus mut_bias[mut_mask] (`mut_mask` int64 [N], 0 / 1), then the
+ * 3-layer MPNN on the ctx's graph.  `ctx` is a ctx of the mutation-branch plan whose batch carries the local mask as its
+ * residue_mask; one ctx serves the wild type and the mutant (the graph depends on neither).  hV [N,128] receives the MPNN
+ * output (exact zeros on rows outside the local mask). */
+pp_status pp_affinity_encode(const pp_affinity *aff, pp_ctx *ctx, const int64_t *residue_type, const float *sc_sincos,
+                             const int64_t *mut_mask, const float *hV_pret, float *hV, void *stream);
+
+/* Replaces the head of AffinityPrediction.forward (:186-187): per segment s (rows seg_offsets[s] .. seg_offsets[s+1]-1 of
+ * h_wt / h_mt [n_rows,128]) the max over rows of h_mt - h_wt and of h_wt - h_mt (a NaN anywhere in a feature's rows gives
+ * NaN, as torch.max), then ddg_predictor: ddg[s], ddg_inv[s].  Segments are the complexes of a packed batch or the B rows
+ * of a padded batch, padding rows INCLUDED (the reference's max sees them).  seg_offsets: DEVICE int32 [n_seg + 1], every
+ * entry within [0, n_rows] (entries are clamped to it); an empty segment gives the ddg_predictor of a -inf vector. */
+pp_status pp_affinity_predict(const pp_affinity *aff, const float *h_wt, const float *h_mt, const int32_t *seg_offsets,
+                              int n_seg, int n_rows, float *ddg, float *ddg_inv, void *stream);
+
 /* Measurement aid, no reference counterpart: average duration (ms) of one launch of a hot kernel
  * (which: 0 = node-message kernel, 1 = edge-update kernel), timed with HIP events on `stream`
  * around `iters` launches.  Synchronises the stream. */

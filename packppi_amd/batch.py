@@ -15,6 +15,19 @@ TENSOR_KEYS = (
     "BB_D", "BB_D_sincos", "BB_D_mask", "SC_D", "SC_D_sincos", "SC_D_mask",
     "chi_1pi_periodic_mask", "chi_2pi_periodic_mask",
 )
+# The extra per-residue keys of a PackPPI-AP batch (skempi_dataset.py:220-252): the mutation mask and the mutant's copies of
+# the wild-type keys that AffinityPrediction.forward swaps in (AffinityPrediction.py:178-181).
+MUT_KEYS = (
+    "mut_mask", "atom_mask_mut", "residue_type_mut", "SC_D_mut", "SC_D_sincos_mut", "SC_D_mask_mut",
+    "chi_1pi_periodic_mask_mut", "chi_2pi_periodic_mask_mut",
+)
+# every per-residue key skempi_datamodule.collate_fn stacks (skempi_datamodule.py:245-287), in its order
+AFFINITY_KEYS = (
+    "mut_mask", "X", "residue_mask", "residue_index", "chain_indices", "BB_D", "BB_D_sincos", "BB_D_mask",
+    "atom_mask", "residue_type", "SC_D", "SC_D_sincos", "SC_D_mask", "chi_1pi_periodic_mask", "chi_2pi_periodic_mask",
+    "atom_mask_mut", "residue_type_mut", "SC_D_mut", "SC_D_sincos_mut", "SC_D_mask_mut", "chi_1pi_periodic_mask_mut",
+    "chi_2pi_periodic_mask_mut",
+)
 
 
 class Batch(dict):
@@ -75,6 +88,22 @@ def collate(proteins: Iterable[Batch]) -> Batch:
     return out
 
 
+def collate_affinity(proteins: Iterable[Batch]) -> Batch:
+    """Padded batch of ``featurize.mutant_data`` outputs: ``ddg`` [B] plus every per-residue key padded with zeros to the
+    longest complex and stacked (skempi_datamodule.py:245-287)."""
+    proteins = list(proteins)
+    max_size = max(int(p["num_nodes"]) for p in proteins)
+
+    def pad(p, key):
+        t = p[key]
+        return F.pad(t, [0, 0] * (t.dim() - 1) + [0, max_size - int(p["num_nodes"])])
+
+    out = Batch(num_proteins=len(proteins), max_size=max_size, ddg=torch.stack([p["ddg"] for p in proteins]))
+    for key in AFFINITY_KEYS:
+        out[key] = torch.stack([pad(p, key) for p in proteins])
+    return out
+
+
 def split(batch: Batch) -> List[Batch]:
     """Inverse of ``collate`` up to padding: one B=1 batch per complex (padding kept)."""
     outs = []
@@ -86,7 +115,7 @@ def split(batch: Batch) -> List[Batch]:
     return outs
 
 
-def pack(complexes: Iterable[Batch]) -> Batch:
+def pack(complexes: Iterable[Batch], trim: bool = True) -> Batch:
     """Ragged batch WITHOUT padding rows: the complexes' rows back to back in one [1, sum of lengths, ...] batch, plus
     ``seg_offsets`` (int32 [n + 1]: first row of every complex, then the total; ``seg_offsets_host`` is the same as a list,
     so that nothing has to be read back from the device).
@@ -96,9 +125,14 @@ def pack(complexes: Iterable[Batch]) -> Batch:
     running it alone (``lib.Context`` / ``pp_complex_prepare_packed``).  Accepts per-complex data (``protein_to_data``,
     tensors [L, ...]) or B = 1 batches ([1, L, ...]).  Only TRAILING padding is dropped: a complex keeps its rows up to the
     last true residue, so a residue masked out in the middle of a chain (a missing backbone atom: featurize.py) stays in
-    place with its ``residue_mask`` 0, exactly as the reference carries it."""
+    place with its ``residue_mask`` 0, exactly as the reference carries it.
+
+    ``trim=False`` keeps every row, trailing padding included (PackPPI-AP: the max over residues of AffinityPrediction.py:186
+    sees those rows).  Complexes that all carry the PackPPI-AP keys (``mut_mask``, the ``*_mut`` keys, ``ddg``) keep them:
+    the per-row keys are packed like the others, ``ddg`` becomes [n]."""
     complexes = list(complexes)
-    rows = {k: [] for k in TENSOR_KEYS}
+    keys = TENSOR_KEYS + tuple(k for k in MUT_KEYS if all(k in c for c in complexes))
+    rows = {k: [] for k in keys}
     offs = [0]
     ends = []
     for c in complexes:
@@ -107,19 +141,22 @@ def pack(complexes: Iterable[Batch]) -> Batch:
             raise ValueError("pack() takes single complexes (use split() on a padded batch first)")
         keep = (c["residue_mask"][0] if lead else c["residue_mask"]) > 0
         # index of the last true residue + 1 (0 for an empty complex), computed where the mask lives
-        ends.append((keep * torch.arange(1, keep.numel() + 1, device=keep.device)).max())
+        ends.append((keep * torch.arange(1, keep.numel() + 1, device=keep.device)).max() if trim else
+                    torch.tensor(keep.numel(), device=keep.device))
     ends = [int(x) for x in torch.stack(ends).tolist()]            # ONE read-back for the whole batch
     for c, n in zip(complexes, ends):
         if n == 0:
             raise ValueError("empty complex")
         lead = c["residue_type"].dim() == 2
-        for k in TENSOR_KEYS:
+        for k in keys:
             t = c[k][0] if lead else c[k]
             rows[k].append(t[:n])
         offs.append(offs[-1] + n)
     out = Batch(num_proteins=1, max_size=offs[-1])
-    for k in TENSOR_KEYS:
+    for k in keys:
         out[k] = torch.cat(rows[k], 0).unsqueeze(0)
+    if all("ddg" in c for c in complexes):
+        out["ddg"] = torch.cat([c["ddg"].reshape(-1) for c in complexes])
     out["seg_offsets"] = torch.tensor(offs, dtype=torch.int32).to(out["X"].device, non_blocking=True)
     out["seg_offsets_host"] = offs
     return out

@@ -892,6 +892,24 @@ extern "C" pp_status pp_score(pp_ctx *c, const float *chi, float t, float *score
     return PP_OK;
 }
 
+extern "C" pp_status pp_affinity_encode(const pp_affinity *a, pp_ctx *c, const int64_t *residue_type, const float *sc_sincos,
+                                        const int64_t *mut_mask, const float *hV_pret, float *hV, void *stream) {
+    if (c) c->last_stream = static_cast<hipStream_t>(stream);
+    if (!a || !c || !residue_type || !sc_sincos || !mut_mask || !hV_pret || !hV) FAIL(PP_ERR_INVALID, "pp_affinity_encode: null argument");
+    if (!a->network) FAIL(PP_ERR_INVALID, "pp_affinity_encode: the affinity head was created for mode linear (no mutation branch)");
+    if (!c->plan->has_network) FAIL(PP_ERR_INVALID, "pp_affinity_encode: plan was created without network weights");
+    if (a->device != c->plan->device) FAIL(PP_ERR_INVALID, "pp_affinity_encode: affinity head and ctx are on different devices");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    PP_HIP_CHECK(hipSetDevice(c->plan->device));
+    StepParams sp;
+    fill_step(&sp, 0.f, 0.f, c->plan->annealed_temp);     // not read by the network: its time-embedding columns are zero
+    pp_status st;
+    if ((st = pp_launch_affinity_embed(c, a, residue_type, sc_sincos, mut_mask, hV_pret, s)) != PP_OK) return st;
+    if ((st = run_network(c, s, 0, PP_NU_SCORE, nullptr, PP_MODE_ODE, nullptr, &sp, nullptr)) != PP_OK) return st;
+    PP_HIP_CHECK(hipMemcpyAsync(hV, c->hV, (size_t)c->N * 128 * sizeof(float), hipMemcpyDeviceToDevice, s));
+    return PP_OK;
+}
+
 extern "C" pp_status pp_sample(pp_ctx *c, float *chi, const float *schedule, int n_schedule, int mode,
                                const float *sde_noise, void *stream) {
     if (c) c->last_stream = static_cast<hipStream_t>(stream);

@@ -284,7 +284,21 @@ __device__ __forceinline__ float pp_pair_dihedral_t(const float *p0, const float
 }
 #endif
 
+// PackPPI-AP head tensors (pp_affinity.hip): one device allocation; matrices read by k_affinity_embed in the k-quad
+// interleaved layout of dense_slice ([in / 4][128][4]), those of k_affinity_head transposed ([in][out])
+struct pp_affinity {
+    int device;
+    bool network;                                              // has mut_bias / seq_embedding / mutation_fusion (mode network)
+    float *buf;
+    const float *mut_bias, *seq_emb;                           // [2][128], [21][128]
+    const float *f0T, *f0_b, *f2T, *f2_b;                      // mutation_fusion.0 [96][128][4], .2 [32][128][4]
+    const float *d0T, *d0_b, *d2T, *d2_b, *d4_w, *d4_b;        // ddg_predictor.0 / .2 [128][128], .4 [128], [1]
+};
+
 // ---- launchers implemented in the kernel translation units ----------------------------------
+// k_affinity_embed (pp_node.hip): the mutation branch's node embedding + fusion -> ctx h_V and layer 0's node-message inputs
+pp_status pp_launch_affinity_embed(pp_ctx *c, const pp_affinity *a, const int64_t *rtype, const float *sc_sincos,
+                                   const int64_t *mut_mask, const float *hV_pret, hipStream_t s);
 pp_status pp_launch_prepare(pp_ctx *c, hipStream_t s, const int64_t *E_idx = nullptr);   // E_idx: given neighbour lists instead of the kNN search
 pp_status pp_launch_node_embed(pp_ctx *c, const float *chi, const StepParams &sp, hipStream_t s);
 // cur: this step's scalars (layer 2 inside sampling); next: the next step, if its node embedding is to follow (else null)

@@ -1331,3 +1331,96 @@ pp_status pp_launch_node_update(pp_ctx *c, int layer, int last_mode, float *chi,
     PP_HIP_CHECK(hipGetLastError());
     return PP_OK;
 }
+
+// ==================================================================================================================
+// k_affinity_embed: PackPPI-AP mutation branch, everything between the two networks (AffinityPrediction.py:148-168)
+//   h_V_mutation = LN(Linear(35,128)(one-hot(S) | BB_D_sincos | SC_D_sincos))   mutation_encoder, time_embedding_dim = 0
+//   h = Linear(128,128)(ReLU(Linear(384,128)(h_V_pret | h_V_mutation | seq_embedding(S)))) + mut_bias[mut_mask]
+// then h -> ctx h_V and the inputs of layer 0's node message (the tail of k_node_embed), so that the MPNN of the
+// mutation-branch plan runs unchanged.  SC_D_sincos is read as the caller gives it: on a mutated row the mutant's is 0
+// while its SC_D_mask may be 1, so it is not sin / cos of the angles times the mask as in k_node_embed.
+// Same block layout as k_node_embed (NB residues, thread = output feature x quarter of the reduction), fp32 VALU:
+// once per branch, not per step.
+// ==================================================================================================================
+struct AffArgs {
+    const int64_t *rtype;        // [N] wild-type or mutant residue types
+    const float *sc_sincos;      // [N][4][2]
+    const int64_t *mut_mask;     // [N]
+    const float *hV_pret;        // [N][128]
+    const float *mut_bias, *seq_emb, *f0T, *f0_b, *f2T, *f2_b;
+};
+
+__global__ void __launch_bounds__(NT)
+k_affinity_embed(NodeArgs A, PreW pre0, AffArgs F) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    Smem &sm = *reinterpret_cast<Smem *>(smem_raw);
+    int flip = 0, rflip = 0;
+    const int t = threadIdx.x, f = t & 127, ks = t >> 7, n0 = blockIdx.x * NB;
+    if (t < 6) sm.p[t] = load_rows(A.bb_sincos, 6, n0, A.N, t);
+    else if (t < 14) sm.p[t] = load_rows(F.sc_sincos, 8, n0, A.N, t - 6);
+    int ty[NB];
+#pragma unroll
+    for (int i = 0; i < NB; i++) {
+        const int n = n0 + i;
+        const int64_t r = n < A.N ? F.rtype[n] : 0;
+        ty[i] = (r >= 0 && r < 21) ? (int)r : 20;
+    }
+    __syncthreads();
+    VN acc = vn(A.emb_b[f]);
+    VN_FOR {
+        acc.g[gi].x += A.embT[ty[4 * gi + 0] * 128 + f]; acc.g[gi].y += A.embT[ty[4 * gi + 1] * 128 + f];
+        acc.g[gi].z += A.embT[ty[4 * gi + 2] * 128 + f]; acc.g[gi].w += A.embT[ty[4 * gi + 3] * 128 + f];
+    }
+#pragma unroll
+    for (int k = 0; k < 14; k++) acc = vfma(A.embT[(21 + k) * 128 + f], sm.p[k], acc);
+    const VN hm = layernorm(sm, rflip, acc, A.emb_g[f], A.emb_beta[f]);
+    // fusion input [h_V_pret | h_V_mutation | seq_embedding(S)] -> sm.a[0..383]
+    if (ks == 0) sm.a[f] = load_rows(F.hV_pret, 128, n0, A.N, f);
+    else if (ks == 1) sm.a[128 + f] = hm;
+    else if (ks == 2) {
+        VN e;
+        VN_FOR e.g[gi] = f4v{F.seq_emb[ty[4 * gi + 0] * 128 + f], F.seq_emb[ty[4 * gi + 1] * 128 + f],
+                             F.seq_emb[ty[4 * gi + 2] * 128 + f], F.seq_emb[ty[4 * gi + 3] * 128 + f]};
+        sm.a[256 + f] = e;
+    }
+    __syncthreads();
+    VN x = meet(sm, flip, dense_slice<384>(F.f0T, 128, f, sm.a, ks), 128, f, ks);
+    x = vrelu(vadd(x, vn(F.f0_b[f])));
+    if (ks == 0) sm.a[384 + f] = x;
+    __syncthreads();
+    VN y = meet(sm, flip, dense_slice<128>(F.f2T, 128, f, sm.a + 384, ks), 128, f, ks);
+    VN bias;
+    VN_FOR {
+        const int b = n0 + 4 * gi;
+        float v[4];
+#pragma unroll
+        for (int i = 0; i < 4; i++) v[i] = F.mut_bias[((b + i < A.N && F.mut_mask[b + i] != 0) ? 128 : 0) + f];
+        bias.g[gi] = f4v{v[0], v[1], v[2], v[3]};
+    }
+    y = vadd(vadd(y, vn(F.f2_b[f])), bias);
+    if (ks == 0) {
+        store_rows(A.hV, 128, n0, A.N, f, y);
+        sm.h[f] = y;
+    }
+    __syncthreads();
+    message_inputs(sm, flip, pre0, A.frames, n0, A.N, A.ptsN, A.PAn, A.PCn);
+}
+
+pp_status pp_launch_affinity_embed(pp_ctx *c, const pp_affinity *a, const int64_t *rtype, const float *sc_sincos,
+                                   const int64_t *mut_mask, const float *hV_pret, hipStream_t s) {
+    static bool attr = false;
+    if (!attr) {
+        PP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_affinity_embed),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(Smem)));
+        attr = true;
+    }
+    NodeArgs A = make_args(c);
+    PreW pre0 = make_pre(c->plan, 0, false);
+    AffArgs F;
+    F.rtype = rtype; F.sc_sincos = sc_sincos; F.mut_mask = mut_mask; F.hV_pret = hV_pret;
+    F.mut_bias = a->mut_bias; F.seq_emb = a->seq_emb;
+    F.f0T = a->f0T; F.f0_b = a->f0_b; F.f2T = a->f2T; F.f2_b = a->f2_b;
+    hipLaunchKernelGGL(k_affinity_embed, dim3((c->N + NB - 1) / NB), dim3(NT), sizeof(Smem), s, A, pre0, F);
+    PP_HIP_CHECK(hipGetLastError());
+    return PP_OK;
+}

@@ -113,3 +113,103 @@ def protein_to_data(protein: Dict) -> Batch:
 def protein_to_batch(protein: Dict) -> Batch:
     """B=1 batch, the form ``ProteinAnalysis.get_prot`` hands to ``sampling`` (protein_analysis.py:103-122)."""
     return as_single(protein_to_data(protein))
+
+
+# ---- PackPPI-AP: wild type + mutant featurisation ------------------------------------------------------------------------
+
+def parse_mutstr(mutstr: str):
+    """"RA47A,EA48A" -> [{'wt': 'R', 'chain': 'A', 'resseq': 47, 'mt': 'A'}, ...] (eval_affinity.py:45-56)."""
+    muts = []
+    for name in mutstr.split(","):
+        muts.append({"wt": name[0], "mt": name[-1], "chain": name[1], "resseq": int(name[2:-1])})
+    return muts
+
+
+def mutant_data(protein: Dict, mutations=None, ddg=None, log=print) -> Batch:
+    """Per-complex wild-type and mutant tensors, as ``SkempiDataset.prot_to_data`` lays them out without ESM
+    (skempi_dataset.py:73-262): the keys of ``protein_to_data`` plus ``ddg``, ``mut_mask`` and the ``*_mut`` keys.
+
+    ``mutations`` (default ``protein['mutations']``) are dicts as ``parse_mutstr`` returns them.  A mutation is looked up
+    by chain and the RAW PDB residue number (before the chain offset); one whose chain is absent or whose target residue
+    is not one of the 20 types is skipped with the reference's message; a wild-type letter that disagrees with the
+    structure raises ValueError.  Differences from ``protein_to_data`` that the reference makes here: the backbone dihedral
+    mask is computed from the raw residue numbers, and ``SC_D_mask_mut`` from the wild-type atoms at the mutant's chi atom
+    slots (it can be 1 on a mutated row while ``SC_D_mut`` and ``SC_D_sincos_mut`` are 0 there)."""
+    if mutations is None:
+        mutations = protein.get("mutations", [])
+    X = torch.from_numpy(np.asarray(protein["atom_positions"])).float()
+    L = X.shape[0]
+    rtype = torch.from_numpy(np.asarray(protein["aaindex"])).long()
+    amask = torch.from_numpy(np.asarray(protein["atom_mask"])).float()
+    raw_index = torch.from_numpy(np.asarray(protein["residue_index"])).long()
+    chain_id = np.asarray(protein["chain_id"])
+    if ddg is None:
+        ddg = protein.get("ddG", 0.0)
+    ddg = torch.tensor(ddg, dtype=torch.float32)
+    chain, rindex = chain_numbers_and_offset_index(protein)
+
+    rmask = torch.isfinite(X[:, :4].sum(dim=(-1, -2))).float()
+    bb, bb_mask = backbone_dihedrals(X, raw_index)
+    sc, sc_mask = sidechain_dihedrals(X, rtype)
+    bb_sc = torch.stack((bb.sin(), bb.cos()), -1) * bb_mask[..., None]
+    sc_sc = torch.stack((sc.sin(), sc.cos()), -1) * sc_mask[..., None]
+    pi1 = torch.from_numpy(rc.chi_pi_periodic)[rtype].bool()
+
+    rtype_mut, amask_mut, sc_mut, sc_sc_mut = rtype.clone(), amask.clone(), sc.clone(), sc_sc.clone()
+    path = protein.get("pdb_path")
+    for m in mutations:
+        tag = f"{m['wt']}{m['chain']}{m['resseq']}{m['mt']}"
+        if m["chain"] not in chain_id or m["mt"] not in rc.restypes:
+            log(f"Ignore the mutation: {tag}")
+            continue
+        index = torch.from_numpy((chain_id == m["chain"]) & (raw_index.numpy() == int(m["resseq"])))
+        hits = int(index.sum())
+        if hits != 1:
+            raise ValueError(f"The mutation: {tag} matches {hits} residues of chain {m['chain']} in {path} file")
+        ref_wt = rc.restypes[int(rtype[index])]
+        if ref_wt != m["wt"]:
+            raise ValueError(f"The mutation: {tag} is inconsistent with wild-type {ref_wt} in {path} file")
+        mt = rc.restype_order[m["mt"]]
+        rtype_mut[index] = mt
+        amask_mut[index] = torch.tensor([1.0 if a else 0.0 for a in rc.atom14_names[mt]], dtype=torch.float32)
+        sc_mut[index] = 0.0
+        sc_sc_mut[index] = 0.0
+    _, sc_mask_mut = sidechain_dihedrals(X, rtype_mut)
+    pi1_mut = torch.from_numpy(rc.chi_pi_periodic)[rtype_mut].bool()
+    mut_mask = (rtype != rtype_mut).long()
+
+    m1, m2, m3 = rmask, rmask[:, None], rmask[:, None, None]
+    sc_mask, sc_mask_mut = sc_mask * m2, sc_mask_mut * m2
+    data = Batch(
+        num_nodes=L,
+        ddg=ddg,
+        mut_mask=(mut_mask * m1).long(),
+        X=X * m3,
+        residue_mask=rmask,
+        residue_index=(rindex * m1).long(),
+        chain_indices=(chain * m1).long(),
+        BB_D=bb * m2,
+        BB_D_sincos=bb_sc * m3,
+        BB_D_mask=bb_mask * m2,
+        atom_mask=amask * m2,
+        residue_type=(rtype * m1).long(),
+        SC_D=sc * m2,
+        SC_D_sincos=sc_sc * m3,
+        SC_D_mask=sc_mask,
+        chi_1pi_periodic_mask=torch.logical_and(sc_mask, pi1 * m2),
+        chi_2pi_periodic_mask=torch.logical_and(sc_mask, ~pi1 * m2),
+        atom_mask_mut=amask_mut * m2,
+        residue_type_mut=(rtype_mut * m1).long(),
+        SC_D_mut=sc_mut * m2,
+        SC_D_sincos_mut=sc_sc_mut * m3,
+        SC_D_mask_mut=sc_mask_mut,
+        chi_1pi_periodic_mask_mut=torch.logical_and(sc_mask_mut, pi1_mut * m2),
+        chi_2pi_periodic_mask_mut=torch.logical_and(sc_mask_mut, ~pi1_mut * m2),
+    )
+    data.apply(lambda v: torch.nan_to_num(v) if isinstance(v, torch.Tensor) and v.is_floating_point() else v)
+    return data
+
+
+def mutant_batch(protein: Dict, mutstr: str, log=print) -> Batch:
+    """B = 1 batch of one mutation string, as eval_affinity.py:45-73 builds it (``ddg`` of shape [1])."""
+    return as_single(mutant_data(protein, parse_mutstr(mutstr), log=log))

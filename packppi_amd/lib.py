@@ -17,7 +17,8 @@ _lib = None
 
 SYMBOLS = ("pp_version", "pp_last_error", "pp_build_id", "pp_plan_set_knn_ties", "pp_plan_set_annealed_temp", "pp_plan_rebalanced_chains", "pp_rebalance_weights_host", "pp_plan_ln_scaled_features", "pp_ln_operand_scales_host", "pp_topk_aten_host", "pp_plan_create", "pp_plan_destroy", "pp_plan_set_clash_params",
            "pp_complex_prepare", "pp_complex_prepare_packed", "pp_ctx_destroy", "pp_ctx_get_graph", "pp_ctx_set_graph", "pp_score", "pp_sample", "pp_atom14",
-           "pp_clash", "pp_proximal", "pp_proximal_packed", "pp_time_kernel", "pp_profile_kernel", "pp_profile_read", "pp_edge_variant", "pp_has_range_check", "pp_range_check", "pp_range_check_parts", "pp_ctx_saturated")
+           "pp_clash", "pp_proximal", "pp_proximal_packed", "pp_time_kernel", "pp_profile_kernel", "pp_profile_read", "pp_edge_variant", "pp_has_range_check", "pp_range_check", "pp_range_check_parts", "pp_ctx_saturated",
+           "pp_affinity_create", "pp_affinity_destroy", "pp_affinity_encode", "pp_affinity_predict")
 
 
 KNN_TIES = {"lower_index": 0, "aten_cpu": 1, "aten_member": 2}
@@ -102,6 +103,11 @@ def load():
     lib.pp_range_check_parts.argtypes = [C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), i]
     lib.pp_ctx_saturated.argtypes = [vp, C.POINTER(C.c_int), vp]
     lib.pp_edge_variant.restype = C.c_int
+    lib.pp_affinity_create.argtypes = [vp, C.c_size_t, i, C.POINTER(vp)]
+    lib.pp_affinity_destroy.argtypes = [vp]
+    lib.pp_affinity_destroy.restype = None
+    lib.pp_affinity_encode.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.pp_affinity_predict.argtypes = [vp, vp, vp, vp, i, i, vp, vp, vp]
     _lib = lib
     return lib
 
@@ -427,4 +433,66 @@ class Context:
         h = getattr(self, "handle", None)
         if h and _lib is not None:
             _lib.pp_ctx_destroy(h)
+            self.handle = None
+
+
+class AffinityHead:
+    """The tensors PackPPI-AP owns besides the two networks (mut_bias, seq_embedding, mutation_fusion, ddg_predictor) on one
+    GPU: ``pp_affinity_create``.  ``state_dict`` holds at least weights.affinity_head_spec(mode)."""
+
+    def __init__(self, state_dict, device, mode="network"):
+        from .weights import affinity_head_spec
+        lib = load()
+        self.device = torch.device(device)
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.mode = mode
+        flat = np.ascontiguousarray(torch.cat([torch.as_tensor(state_dict[n]).detach().float().cpu().reshape(-1)
+                                               for n, _ in affinity_head_spec(mode)]).numpy(), dtype=np.float32)
+        h = C.c_void_p()
+        _check(lib.pp_affinity_create(flat.ctypes.data, flat.size, self.device.index, C.byref(h)), "pp_affinity_create")
+        self.handle = h
+
+    def encode(self, ctx: "Context", residue_type, sc_sincos, mut_mask, hV_pret):
+        """AffinityPrediction.encode after the pretrained features, on ``ctx`` (a Context of the mutation-branch plan whose
+        batch carries the local mask as residue_mask): [B, L, 128] MPNN output."""
+        dev = self.device
+        rt = residue_type.to(device=dev, dtype=torch.int64).contiguous()
+        sc = sc_sincos.to(device=dev, dtype=torch.float32).contiguous()
+        mm = mut_mask.to(device=dev, dtype=torch.int64).contiguous()
+        hp = hV_pret.to(device=dev, dtype=torch.float32).contiguous()
+        n = ctx.B * ctx.L if ctx.seg_offsets_host is None else ctx.L
+        if rt.numel() != n or sc.numel() != 8 * n or mm.numel() != n or hp.numel() != 128 * n:
+            raise RuntimeError("pp_affinity_encode: tensors do not match the context's rows")
+        hV = torch.empty(hp.shape, dtype=torch.float32, device=dev)
+        _check(load().pp_affinity_encode(self.handle, ctx.handle, _ptr(rt), _ptr(sc), _ptr(mm), _ptr(hp), _ptr(hV),
+                                         _stream(dev)), "pp_affinity_encode")
+        return hV
+
+    def predict(self, h_wt, h_mt, seg_offsets):
+        """(ddg [n_seg], ddg_inv [n_seg]): ddg_predictor of the max over each segment's rows of h_mt - h_wt / h_wt - h_mt.
+        ``seg_offsets``: int list or tensor [n_seg + 1] of row offsets into the flattened [rows, 128] tensors."""
+        dev = self.device
+        hw = h_wt.to(device=dev, dtype=torch.float32).contiguous()
+        hm = h_mt.to(device=dev, dtype=torch.float32).contiguous()
+        if hw.shape != hm.shape or hw.shape[-1] != 128:
+            raise RuntimeError("pp_affinity_predict: h_wt and h_mt must have the same shape [..., 128]")
+        rows = hw.numel() // 128
+        offs = torch.as_tensor(seg_offsets).to(dtype=torch.int32)
+        if offs.device.type == "cpu":
+            o = offs.tolist()
+            if o[0] < 0 or o[-1] > rows or any(b < a for a, b in zip(o[:-1], o[1:])):
+                raise RuntimeError(f"seg_offsets {o} do not describe {rows} rows")
+        offs = offs.to(dev).contiguous()
+        n_seg = offs.numel() - 1
+        ddg = torch.empty(n_seg, dtype=torch.float32, device=dev)
+        inv = torch.empty(n_seg, dtype=torch.float32, device=dev)
+        _check(load().pp_affinity_predict(self.handle, _ptr(hw), _ptr(hm), _ptr(offs), int(n_seg), int(rows), _ptr(ddg), _ptr(inv),
+                                          _stream(dev)), "pp_affinity_predict")
+        return ddg, inv
+
+    def __del__(self):
+        h = getattr(self, "handle", None)
+        if h and _lib is not None:
+            _lib.pp_affinity_destroy(h)
             self.handle = None
