@@ -175,6 +175,13 @@ pp_status pp_ctx_set_graph(pp_ctx *ctx, const int64_t *E_idx, void *stream);
  * timestep shared by all residues.  score [B,L,4]; hV [B,L,128] may be NULL. */
 pp_status pp_score(pp_ctx *ctx, const float *chi, float t, float *score, float *hV, void *stream);
 
+/* The same with a timestep PER ROW: t_rows is a DEVICE array [B*L] (packed ctx: [N]).  This is what the denoising
+ * score-matching loss calls (TorsionalDiffusion.py:126-137 draws one t per complex).  Only the node embedding sees the time; its
+ * 16 sinusoidal features of t_rows[n] * 10000 (layers.py:257-264) are computed on the device the way pp_score computes them on
+ * the host, so a constant t_rows gives the bits pp_score gives.  t_rows is not modified (the reference's in-place `*= 10000` is
+ * a side effect its own forward never observes).  A non-finite t_rows on an unmasked row sets bit 2 of pp_ctx_saturated. */
+pp_status pp_score_rows(pp_ctx *ctx, const float *chi, const float *t_rows, float *score, float *hV, void *stream);
+
 /* Replaces the loop of TDiffusionModule.sampling (TorsionalDiffusion.py:259-280):
  * chi [B,L,4] holds the initial noised angles on entry and the sample on exit.
  * `schedule` is a HOST array of n_schedule times (n_schedule-1 network evaluations); it is read before the
@@ -251,6 +258,33 @@ pp_status pp_affinity_encode(const pp_affinity *aff, pp_ctx *ctx, const int64_t 
  * entry within [0, n_rows] (entries are clamped to it); an empty segment gives the ddg_predictor of a -inf vector. */
 pp_status pp_affinity_predict(const pp_affinity *aff, const float *h_wt, const float *h_mt, const int32_t *seg_offsets,
                               int n_seg, int n_rows, float *ddg, float *ddg_inv, void *stream);
+
+/* ---- Denoising score-matching loss (TorsionalDiffusion.py:126-154; schedule.py:30-94) ------------------------------------------
+ * Replaces SO2Schedule.score(x, sigma) (schedule.py:66-75) for PI = pi / 2 (pi_periodic = 1) and PI = pi (0) WITHOUT the
+ * reference's 5001 x 5001 fp64 tables: a table entry is a pure function of its two indices, so it is computed.  x, sigma, score:
+ * DEVICE [n] (sigma already expanded to x's shape); idx: DEVICE int32 [n][2] = (sigma index, x index), may be NULL.
+ *   - quantisation as schedule.py:67-74: wrap into [-PI, PI), sign, log(|x| / PI + 1e-10), scale, clip to [0, 5000], round half
+ *     to even; sigma likewise with SIGMA_MIN = 3e-3, SIGMA_MAX = 2.  NumPy promotion: the first log runs on a float32 array; under
+ *     the reference's pinned NumPy 1.22 the scaling that follows stays in float32, under NumPy 2 (which made this project's
+ *     fixtures) the float32 log is promoted and the scaling runs in float64.  The kernel follows NumPy 2: fp32 logf, then fp64.
+ *   - x_j, sigma_i from the grids of schedule.py:40-43, which the caller computes with NumPy as the reference does and hands
+ *     over once per device: pp_so2_set_grids(x_grid, sigma_grid HOST fp64 [2][5001]: schedule 1pi, then 2pi).  Synchronous.
+ *     pp_so2_score before it gives PP_ERR_INVALID.
+ *   - entry in fp64, terms i = -100 .. 100 in that order: p = sum exp(-(x + 2 PI i)^2 / 2 / sigma^2),
+ *     g = sum (x + 2 PI i) / sigma^2 exp(...), entry = g / (p == 0 ? 1e-10 : p); score = (float)(-sign * entry). */
+pp_status pp_so2_set_grids(const double *x_grid, const double *sigma_grid, int device);
+pp_status pp_so2_score(const float *x, const float *sigma, size_t n, int pi_periodic, float *score, int32_t *idx, int device,
+                       void *stream);
+
+/* Replaces the tail of TDiffusionModule.forward (TorsionalDiffusion.py:139-153), per segment: the complexes of a packed ctx, the
+ * B rows of a padded ctx (padding rows included), one segment for B = 1.  All DEVICE: pred_score (the network's, unscaled),
+ * target_score [N][4]; t_rows [N]; score_norm fp64 [2][5001] (score_norm_ of the 1pi schedule, then of the 2pi one); num, den
+ * fp64 [n_seg].  sigma = exp(ln(0.01 pi) + (ln pi - ln(0.01 pi)) t) in fp32, its score_norm index per schedule as
+ * schedule.py:88-94, sn chosen by chi_1pi_periodic_mask; in fp64
+ *     num[s] = sum (target - pred * sqrt(sn) * SC_D_mask)^2 / (sn + 1e-6),     den[s] = sum SC_D_mask
+ * in a fixed order (no float atomics).  The reference's loss is sum_s num / max(sum_s den, 1). */
+pp_status pp_dsm_loss(pp_ctx *ctx, const float *pred_score, const float *target_score, const float *t_rows,
+                      const double *score_norm, double *num, double *den, void *stream);
 
 /* Measurement aid, no reference counterpart: average duration (ms) of one launch of a hot kernel
  * (which: 0 = node-message kernel, 1 = edge-update kernel), timed with HIP events on `stream`

@@ -892,6 +892,26 @@ extern "C" pp_status pp_score(pp_ctx *c, const float *chi, float t, float *score
     return PP_OK;
 }
 
+// pp_score with a time per row: only the node embedding sees the time (columns 35..50 of encoder.node_embedding), so the
+// sibling embedding kernel is the one difference; the MPNN, the decoder and every edge kernel are pp_score's.
+extern "C" pp_status pp_score_rows(pp_ctx *c, const float *chi, const float *t_rows, float *score, float *hV, void *stream) {
+    if (c) c->last_stream = static_cast<hipStream_t>(stream);
+    if (!c || !chi || !t_rows || !score) FAIL(PP_ERR_INVALID, "pp_score_rows: null argument");
+    if (!c->plan->has_network) FAIL(PP_ERR_INVALID, "pp_score_rows: plan was created without network weights");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    PP_HIP_CHECK(hipSetDevice(c->plan->device));
+    StepParams sp;
+    fill_step(&sp, 0.f, 0.f, c->plan->annealed_temp);     // PP_NU_SCORE reads no per-step scalar and no time embedding
+    pp_status st;
+    flag_nonfinite(c, chi, 4, 4, s);
+    flag_nonfinite(c, t_rows, 1, 1, s);
+    if ((st = pp_launch_node_embed_rows(c, chi, t_rows, s)) != PP_OK) return st;
+    if ((st = run_network(c, s, 0, PP_NU_SCORE, nullptr, PP_MODE_ODE, nullptr, &sp, nullptr)) != PP_OK) return st;
+    PP_HIP_CHECK(hipMemcpyAsync(score, c->score, (size_t)c->N * 4 * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (hV) PP_HIP_CHECK(hipMemcpyAsync(hV, c->hV, (size_t)c->N * 128 * sizeof(float), hipMemcpyDeviceToDevice, s));
+    return PP_OK;
+}
+
 extern "C" pp_status pp_affinity_encode(const pp_affinity *a, pp_ctx *c, const int64_t *residue_type, const float *sc_sincos,
                                         const int64_t *mut_mask, const float *hV_pret, float *hV, void *stream) {
     if (c) c->last_stream = static_cast<hipStream_t>(stream);

@@ -301,6 +301,7 @@ pp_status pp_launch_affinity_embed(pp_ctx *c, const pp_affinity *a, const int64_
                                    const int64_t *mut_mask, const float *hV_pret, hipStream_t s);
 pp_status pp_launch_prepare(pp_ctx *c, hipStream_t s, const int64_t *E_idx = nullptr);   // E_idx: given neighbour lists instead of the kNN search
 pp_status pp_launch_node_embed(pp_ctx *c, const float *chi, const StepParams &sp, hipStream_t s);
+pp_status pp_launch_node_embed_rows(pp_ctx *c, const float *chi, const float *t_rows, hipStream_t s);   // a time per row (DEVICE [N])
 // cur: this step's scalars (layer 2 inside sampling); next: the next step, if its node embedding is to follow (else null)
 pp_status pp_launch_node_update(pp_ctx *c, int layer, int last_mode, float *chi, int step, int mode,
                                 const float *noise, const StepParams *cur, const StepParams *next, hipStream_t s);

@@ -265,6 +265,77 @@ k_node_embed(NodeArgs A, PreW pre0, const float *chi, StepParams sp) {
     message_inputs(sm, flip, pre0, A.frames, n0, A.N, A.ptsN, A.PAn, A.PCn);
 }
 
+// embed_pre without its 16 time columns: bias + the 35 inputs that do not depend on the time, the same arithmetic in the same
+// order (a copy, not a shared helper: k_node_embed must keep compiling to the instructions it had).  Ends behind a barrier that
+// follows the writes to sm.p[0..13], so the caller may fill other slots of sm.p before the call and read them after it.
+__device__ __forceinline__ VN embed_pre35(Smem &sm, const NodeArgs &A, const float *chi, int n0) {
+    const int t = threadIdx.x, f = t & 127;
+    if (t < 6) sm.p[t] = load_rows(A.bb_sincos, 6, n0, A.N, t);
+    else if (t < 14) {
+        int k = (t - 6) >> 1, sc = (t - 6) & 1;
+        VN x = load_rows(chi, 4, n0, A.N, k), m = load_rows(A.sc_mask, 4, n0, A.N, k), v;
+        VN_FOR v.g[gi] = sc ? f4v{cosf(x.g[gi].x), cosf(x.g[gi].y), cosf(x.g[gi].z), cosf(x.g[gi].w)}
+                            : f4v{sinf(x.g[gi].x), sinf(x.g[gi].y), sinf(x.g[gi].z), sinf(x.g[gi].w)};
+        sm.p[t] = vmul(v, m);
+    }
+    __syncthreads();
+    VN acc = vn(A.emb_b[f]);
+    VN_FOR {
+        const int b = n0 + 4 * gi;
+        const int t0 = b + 0 < A.N ? (int)A.rtype[b + 0] : 0, t1 = b + 1 < A.N ? (int)A.rtype[b + 1] : 0;
+        const int t2 = b + 2 < A.N ? (int)A.rtype[b + 2] : 0, t3 = b + 3 < A.N ? (int)A.rtype[b + 3] : 0;
+        acc.g[gi].x += A.embT[t0 * 128 + f]; acc.g[gi].y += A.embT[t1 * 128 + f];
+        acc.g[gi].z += A.embT[t2 * 128 + f]; acc.g[gi].w += A.embT[t3 * 128 + f];
+    }
+#pragma unroll
+    for (int k = 0; k < 14; k++) acc = vfma(A.embT[(21 + k) * 128 + f], sm.p[k], acc);
+    return acc;
+}
+
+// Sibling of k_node_embed for a time PER ROW (pp_score_rows: the loss draws one t per complex).  The 16 sinusoidal features of
+// t_rows[n] * 10000 are computed here as fill_step computes them on the host: fp32 product with the fp32 frequencies (handed
+// over as arguments, so that no device expf is involved), sin / cos in double on that fp32 argument, one rounding.  The sum
+// over the 16 columns runs in fill_step's order per row, so a constant t_rows gives the bits of k_node_embed.
+struct TimeFreq {
+    float v[8];
+};
+
+__global__ void __launch_bounds__(NT)
+k_node_embed_rows(NodeArgs A, PreW pre0, const float *chi, const float *__restrict__ t_rows, TimeFreq fq) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    Smem &sm = *reinterpret_cast<Smem *>(smem_raw);
+    int flip = 0, rflip = 0;
+    const int f = threadIdx.x & 127, ks = threadIdx.x >> 7, n0 = blockIdx.x * NB;
+    if (threadIdx.x >= 64 && threadIdx.x < 80) {       // wave 1: feature k of the block's rows -> sm.p[16 + k]
+        const int k = threadIdx.x - 64;
+        float fr = 0.f;
+#pragma unroll
+        for (int i = 0; i < 8; i++) fr = (k & 7) == i ? fq.v[i] : fr;
+        VN ts = load_rows(t_rows, 1, n0, A.N, 0), v;
+        VN_FOR {
+            float e[4];
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const float arg = (comp(ts.g[gi], j) * 10000.0f) * fr;
+                e[j] = (float)(k < 8 ? sin((double)arg) : cos((double)arg));
+            }
+            v.g[gi] = f4v{e[0], e[1], e[2], e[3]};
+        }
+        sm.p[16 + k] = v;
+    }
+    VN acc = embed_pre35(sm, A, chi, n0);
+    VN tacc = vn(0.f);
+#pragma unroll
+    for (int k = 0; k < 16; k++) tacc = vfma(A.embT[(35 + k) * 128 + f], sm.p[16 + k], tacc);
+    VN h = layernorm(sm, rflip, vadd(acc, tacc), A.emb_g[f], A.emb_beta[f]);
+    if (ks == 0) {
+        store_rows(A.hV, 128, n0, A.N, f, h);
+        sm.h[f] = h;
+    }
+    __syncthreads();
+    message_inputs(sm, flip, pre0, A.frames, n0, A.N, A.ptsN, A.PAn, A.PCn);
+}
+
 // (x + pi) % (2 pi) - pi with torch.remainder semantics in fp32
 __device__ __forceinline__ float wrap_pi(float x) {
     const float PIf = 3.14159274101257324f, TWO_PIf = 6.28318548202514648f;
@@ -1214,6 +1285,8 @@ static pp_status node_attrs() {
     if (!done) {
         PP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_node_embed),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(Smem)));
+        PP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_node_embed_rows),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(Smem)));
         for (int multi = 0; multi < 2; multi++)
             for (int mode = 0; mode < 3; mode++)
                 PP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(nu_kernel(mode, multi != 0)),
@@ -1241,6 +1314,19 @@ pp_status pp_launch_node_embed(pp_ctx *c, const float *chi, const StepParams &sp
     NodeArgs A = make_args(c);
     PreW pre0 = make_pre(c->plan, 0, false);
     hipLaunchKernelGGL(k_node_embed, dim3((c->N + NB - 1) / NB), dim3(NT), sizeof(Smem), s, A, pre0, chi, sp);
+    PP_HIP_CHECK(hipGetLastError());
+    return PP_OK;
+}
+
+pp_status pp_launch_node_embed_rows(pp_ctx *c, const float *chi, const float *t_rows, hipStream_t s) {
+    pp_status st = node_attrs();
+    if (st != PP_OK) return st;
+    NodeArgs A = make_args(c);
+    PreW pre0 = make_pre(c->plan, 0, false);
+    TimeFreq fq;
+    const float nemb = (float)(-(log(10000.0) / 7.0));       // as fill_step
+    for (int i = 0; i < 8; i++) fq.v[i] = expf((float)i * nemb);
+    hipLaunchKernelGGL(k_node_embed_rows, dim3((c->N + NB - 1) / NB), dim3(NT), sizeof(Smem), s, A, pre0, chi, t_rows, fq);
     PP_HIP_CHECK(hipGetLastError());
     return PP_OK;
 }

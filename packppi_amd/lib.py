@@ -18,7 +18,8 @@ _lib = None
 SYMBOLS = ("pp_version", "pp_last_error", "pp_build_id", "pp_plan_set_knn_ties", "pp_plan_set_annealed_temp", "pp_plan_rebalanced_chains", "pp_rebalance_weights_host", "pp_plan_ln_scaled_features", "pp_ln_operand_scales_host", "pp_topk_aten_host", "pp_plan_create", "pp_plan_destroy", "pp_plan_set_clash_params",
            "pp_complex_prepare", "pp_complex_prepare_packed", "pp_ctx_destroy", "pp_ctx_get_graph", "pp_ctx_set_graph", "pp_score", "pp_sample", "pp_atom14",
            "pp_clash", "pp_proximal", "pp_proximal_packed", "pp_time_kernel", "pp_profile_kernel", "pp_profile_read", "pp_edge_variant", "pp_has_range_check", "pp_range_check", "pp_range_check_parts", "pp_ctx_saturated",
-           "pp_affinity_create", "pp_affinity_destroy", "pp_affinity_encode", "pp_affinity_predict")
+           "pp_affinity_create", "pp_affinity_destroy", "pp_affinity_encode", "pp_affinity_predict",
+           "pp_score_rows", "pp_so2_set_grids", "pp_so2_score", "pp_dsm_loss")
 
 
 KNN_TIES = {"lower_index": 0, "aten_cpu": 1, "aten_member": 2}
@@ -108,6 +109,10 @@ def load():
     lib.pp_affinity_destroy.restype = None
     lib.pp_affinity_encode.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
     lib.pp_affinity_predict.argtypes = [vp, vp, vp, vp, i, i, vp, vp, vp]
+    lib.pp_score_rows.argtypes = [vp, vp, vp, vp, vp, vp]
+    lib.pp_so2_set_grids.argtypes = [vp, vp, i]
+    lib.pp_so2_score.argtypes = [vp, vp, C.c_size_t, i, vp, vp, i, vp]
+    lib.pp_dsm_loss.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
     _lib = lib
     return lib
 
@@ -329,12 +334,51 @@ class Context:
         E = E_idx.to(device=self.plan.device, dtype=torch.int64).reshape(self.B, self.L, self.K).contiguous()
         _check(load().pp_ctx_set_graph(self.handle, _ptr(E), _stream(self.plan.device)), "pp_ctx_set_graph")
 
-    def score(self, chi, t: float):
+    def score(self, chi, t):
+        """``t``: a number, or a tensor; one with mixed values ([B*L], packed: [N]) goes to ``score_rows``."""
+        if isinstance(t, torch.Tensor) and t.numel() > 1:
+            if not bool((t == t.reshape(-1)[0]).all()):
+                return self.score_rows(chi, t)
+            t = t.reshape(-1)[0]
         chi = self._chi(chi)
         score, hV = self._new(self.B, self.L, 4), self._new(self.B, self.L, 128)
         _check(load().pp_score(self.handle, _ptr(chi), float(t), _ptr(score), _ptr(hV), _stream(self.plan.device)),
                "pp_score")
         return score, hV
+
+    @property
+    def n_rows(self) -> int:
+        return self.B * self.L
+
+    @property
+    def n_segments(self) -> int:
+        """Complexes of a packed context, else the B rows of the padded batch."""
+        return len(self.seg_offsets_host) - 1 if self.seg_offsets_host is not None else self.B
+
+    def _rows(self, t, what, width=1):
+        t = t.to(device=self.plan.device, dtype=torch.float32).contiguous()
+        if t.numel() != self.n_rows * width:
+            raise ValueError(f"{what} has {t.numel()} elements, this context has {self.n_rows} rows x {width}")
+        return t
+
+    def score_rows(self, chi, t_rows):
+        """``score`` with a time per row ([B*L], packed: [N]): pp_score_rows.  ``t_rows`` is not modified."""
+        chi, t_rows = self._chi(chi), self._rows(t_rows, "t")
+        score, hV = self._new(self.B, self.L, 4), self._new(self.B, self.L, 128)
+        _check(load().pp_score_rows(self.handle, _ptr(chi), _ptr(t_rows), _ptr(score), _ptr(hV), _stream(self.plan.device)),
+               "pp_score_rows")
+        return score, hV
+
+    def dsm_loss(self, pred_score, target_score, t_rows, score_norm):
+        """(num [n_segments], den [n_segments]) fp64 on the device: the masked, normalised squared error of
+        TorsionalDiffusion.py:139-153 per segment.  ``score_norm``: fp64 [2, 5001] on the device (1pi, 2pi)."""
+        pred, tgt, t_rows = self._rows(pred_score, "pred_score", 4), self._rows(target_score, "target_score", 4), self._rows(t_rows, "t")
+        if score_norm.dtype != torch.float64 or tuple(score_norm.shape) != (2, SO2_GRID) or score_norm.device != self.plan.device:
+            raise ValueError(f"score_norm must be a float64 [2, {SO2_GRID}] tensor on {self.plan.device}")
+        num, den = self._new(self.n_segments, dtype=torch.float64), self._new(self.n_segments, dtype=torch.float64)
+        _check(load().pp_dsm_loss(self.handle, _ptr(pred), _ptr(tgt), _ptr(t_rows), _ptr(score_norm.contiguous()), _ptr(num), _ptr(den),
+                                  _stream(self.plan.device)), "pp_dsm_loss")
+        return num, den
 
     def sample(self, chi, schedule, mode="ode", sde_noise=None):
         chi = self._chi(chi).clone()
@@ -434,6 +478,42 @@ class Context:
         if h and _lib is not None:
             _lib.pp_ctx_destroy(h)
             self.handle = None
+
+
+SO2_GRID = 5001
+_so2_grids_on = set()
+
+
+def so2_grids():
+    """(x [2, 5001], sigma [2, 5001]) fp64: the grids of SO2Schedule.__init__ (schedule.py:40-43) for PI = pi / 2, then PI = pi,
+    computed with NumPy by the reference's own expressions."""
+    X_MIN, X_N, SIGMA_MIN, SIGMA_MAX, SIGMA_N = 1e-5, 5000, 3e-3, 2, 5000
+    xs, ss = [], []
+    for PI in (1 / 2 * np.pi, np.pi):
+        xs.append(10 ** np.linspace(np.log10(X_MIN), 0, X_N + 1) * PI)
+        ss.append(10 ** np.linspace(np.log10(SIGMA_MIN), np.log10(SIGMA_MAX), SIGMA_N + 1) * PI)
+    return np.ascontiguousarray(np.stack(xs)), np.ascontiguousarray(np.stack(ss))
+
+
+def so2_score(x, sigma, pi_periodic: bool, want_idx: bool = False):
+    """SO2Schedule.score(x, sigma) of the schedule with PI = pi / 2 (``pi_periodic``) or pi, computed on the device without the
+    reference's tables (pp_so2_score).  ``sigma`` broadcasts to ``x``.  -> fp32 score shaped like ``x`` (and the int32
+    [..., 2] (sigma index, x index) pairs)."""
+    if x.device.type != "cuda":
+        raise RuntimeError(f"so2_score needs tensors on the HIP device, got {x.device}")
+    lib, dev = load(), x.device
+    idx_dev = dev.index if dev.index is not None else torch.cuda.current_device()
+    if idx_dev not in _so2_grids_on:
+        xg, sg = so2_grids()
+        _check(lib.pp_so2_set_grids(xg.ctypes.data, sg.ctypes.data, idx_dev), "pp_so2_set_grids")
+        _so2_grids_on.add(idx_dev)
+    xf = x.to(torch.float32).contiguous()
+    sf = sigma.to(device=dev, dtype=torch.float32).expand_as(xf).contiguous()
+    score = torch.empty_like(xf)
+    idx = torch.empty(*xf.shape, 2, dtype=torch.int32, device=dev) if want_idx else None
+    _check(lib.pp_so2_score(_ptr(xf), _ptr(sf), xf.numel(), 1 if pi_periodic else 0, _ptr(score), _ptr(idx), idx_dev, _stream(dev)),
+           "pp_so2_score")
+    return (score, idx) if want_idx else score
 
 
 class AffinityHead:

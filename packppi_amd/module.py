@@ -3,7 +3,8 @@
 Mirrors ``src/models/TorsionalDiffusion.py``: ``network`` (:90-109), ``add_sc_noise`` (:111-124),
 ``sampling`` (:254-298), ``compute_rmsd`` (:300-309), ``analyze_samples`` (:311-341), the plain
 ``schedule`` attribute (:77) and ``load_from_checkpoint(..., strict=False)`` as the CLIs use it
-(eval_diffusion.py:29-41).  Training hooks are out of scope.
+(eval_diffusion.py:29-41); and the denoising score-matching loss ``forward`` / ``step`` / ``validation_step`` /
+``test_step`` (:126-229), forward pass only.  Gradients, optimisers and the other Lightning hooks are out of scope.
 """
 import math
 import pickle
@@ -105,6 +106,7 @@ class TDiffusionModule:
         self.device = torch.device("cpu")
         self._plan: Optional[Plan] = None
         self._ctx_key, self._ctx = None, None
+        self._score_norm = None           # [2, 5001] fp64 on the device: set_score_norm, or made at the first forward
         self._knn_ties = knn_ties         # None: the library default (the reference CPU path's torch.topk choice)
         self.to(device)
 
@@ -162,12 +164,11 @@ class TDiffusionModule:
 
     # ---- reference surface -------------------------------------------------------------------
     def network(self, batch, SC_D_noised, t):
-        """-> (pred_score [B,L,4], h_V [B,L,128]).  ``t`` [B*L] must hold one shared value."""
+        """-> (pred_score [B,L,4], h_V [B,L,128]).  ``t``: one value, or [B*L] (packed batch: [N]); mixed values run the per-row
+        embedding kernel (pp_score_rows), one shared value pp_score.  ``t`` is NOT modified: the reference multiplies it by
+        10000 in place (layers.py:258), a side effect its own ``forward`` never observes."""
         t = torch.as_tensor(t, dtype=torch.float32).reshape(-1)
-        t0 = float(t[0])
-        if t.numel() > 1 and not bool((t == t[0]).all()):
-            raise NotImplementedError("per-residue timesteps only occur in training (out of scope)")
-        return self._context(batch).score(SC_D_noised, t0)
+        return self._context(batch).score(SC_D_noised, t if t.numel() > 1 else float(t[0]))
 
     @torch.no_grad()
     def add_sc_noise(self, batch, t):
@@ -183,6 +184,100 @@ class TDiffusionModule:
         x = (x + np.pi) % (2 * np.pi) - np.pi
         shape = (batch.num_proteins, -1, 4)
         return x.reshape(shape), torch.zeros_like(x).reshape(shape)
+
+    @torch.no_grad()
+    def add_sc_noise_with_score(self, batch, t, noise=None):
+        """``add_sc_noise`` with its second return: (noised angles, target score), TorsionalDiffusion.py:111-124.  The same two
+        draws in the same order (or ``noise`` [2, N, 4], the two N(0,1) draws, injected); the target score of each schedule is
+        SO2Schedule.score(noise, sigma) (schedule.py:185-193) computed on the device without the tables, masked like the
+        noise, and joined as ``where(1pi mask, score_1pi, score_2pi)``."""
+        from .lib import so2_score
+        x = batch.SC_D.reshape(-1, 4)
+        sig = self._t_to_sigma(t.to(x.device)).unsqueeze(-1)
+        m1, m2 = batch.chi_1pi_periodic_mask.reshape(-1, 4), batch.chi_2pi_periodic_mask.reshape(-1, 4)
+        if noise is not None:
+            noise = torch.as_tensor(noise).to(device=x.device, dtype=x.dtype)
+            if tuple(noise.shape) != (2, *x.shape):
+                raise ValueError(f"noise must have shape {(2, *x.shape)} (the 1pi draw, then the 2pi draw), got {tuple(noise.shape)}")
+        n1 = (torch.randn_like(x) if noise is None else noise[0]) * sig
+        s1 = so2_score(n1, sig, True) * m1
+        x = x + n1 * m1
+        n2 = (torch.randn_like(x) if noise is None else noise[1]) * sig
+        s2 = so2_score(n2, sig, False) * m2
+        x = x + n2 * m2
+        x = (x + np.pi) % (2 * np.pi) - np.pi
+        shape = (batch.num_proteins, -1, 4)
+        return x.reshape(shape), torch.where(m1.bool(), s1, s2).reshape(shape)
+
+    # ---- denoising score-matching loss (TorsionalDiffusion.py:126-229) -----------------------------------------------------------
+    def set_score_norm(self, tables=None, seed=None):
+        """The two ``score_norm_`` tables the loss divides by.  ``tables``: an ``.npy`` path or a [2, 5001] array (1pi, 2pi), e.g.
+        from a reference run; None: ``schedule.score_norm_tables(seed)`` (seed None: unseeded np.random, as the reference)."""
+        from .schedule import load_score_norm, score_norm_tables
+        arr = load_score_norm(tables) if tables is not None else score_norm_tables(seed, self.device)
+        self._score_norm = torch.from_numpy(np.ascontiguousarray(arr)).to(self.device)
+        return self
+
+    def _segments(self, batch):
+        offs = batch.get("seg_offsets_host") if hasattr(batch, "get") else None
+        if offs is None and hasattr(batch, "get") and batch.get("seg_offsets") is not None:
+            offs = [int(v) for v in batch["seg_offsets"].tolist()]
+        if offs is not None:
+            return [b - a for a, b in zip(offs[:-1], offs[1:])]
+        return [int(batch.max_size)] * int(batch.num_proteins)
+
+    @torch.no_grad()
+    def forward(self, batch, t=None, noise=None, per_complex=False):
+        """The loss ``trainer.test`` / every validation epoch report: fp64 scalar ``sum num / max(sum den, 1)`` over the batch
+        (TorsionalDiffusion.py:126-154); ``per_complex=True``: [n_complexes] ``num / max(den, 1)``.  ``t``: one time per complex
+        ([num_proteins]; packed batch: one per packed complex), None draws ``torch.rand`` on the CPU like ``sample_train_t``.
+        ``noise``: the two N(0,1) draws [2, N, 4], None draws them on the batch's device."""
+        lens = self._segments(batch)
+        if t is None:
+            t = torch.rand((len(lens),))
+        t = torch.as_tensor(t, dtype=torch.float32).reshape(-1)
+        if t.numel() != len(lens):
+            raise ValueError(f"t has {t.numel()} entries for {len(lens)} complexes (one time per complex)")
+        if self._score_norm is None:
+            self.set_score_norm()
+        self._score_norm = self._score_norm.to(self.device)
+        t_rows = torch.repeat_interleave(t, torch.tensor(lens)).to(self.device)
+        SC_D_noised, target = self.add_sc_noise_with_score(batch, t_rows, noise)
+        ctx = self._context(batch)
+        pred, _ = ctx.score_rows(SC_D_noised, t_rows)
+        num, den = ctx.dsm_loss(pred, target, t_rows, self._score_norm)
+        if per_complex:
+            return num / den.clamp(min=1)
+        return num.sum() / den.sum().clamp(min=1)
+
+    def step(self, batch):
+        return self.forward(batch)
+
+    def _metric_step(self, name, batch):
+        loss = self.step(batch)
+        tot, n = getattr(self, "_" + name, (0.0, 0))
+        setattr(self, "_" + name, (tot + float(loss), n + 1))
+        return {"loss": loss}
+
+    def validation_step(self, batch, batch_idx=0):
+        return self._metric_step("val_loss", batch)
+
+    def test_step(self, batch, batch_idx=0):
+        return self._metric_step("test_loss", batch)
+
+    @property
+    def val_loss(self) -> float:
+        """Running mean of the ``validation_step`` losses (``reset_metrics`` clears it); NaN before the first step."""
+        tot, n = getattr(self, "_val_loss", (0.0, 0))
+        return tot / n if n else float("nan")
+
+    @property
+    def test_loss(self) -> float:
+        tot, n = getattr(self, "_test_loss", (0.0, 0))
+        return tot / n if n else float("nan")
+
+    def reset_metrics(self):
+        self._val_loss, self._test_loss = (0.0, 0), (0.0, 0)
 
     def sampling(self, batch, use_proximal: bool = False, return_list: bool = False, sde_noise=None):
         cfg = self.hparams.sample_cfg
