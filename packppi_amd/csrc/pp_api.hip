@@ -862,7 +862,7 @@ static pp_status run_network(pp_ctx *c, hipStream_t s, int step, int last_mode, 
             prof_disarm(c);
             if (st != PP_OK) return st;
             prof_arm(c, 1);
-            st = pp_launch_edge_update(c, l, s);
+            st = pp_launch_edge_update(c, l, l == 0 || !pp_edge_fused(), s);   // layer 1's h_E has no reader here
             prof_disarm(c);
             if (st != PP_OK) return st;
         } else {
@@ -1018,7 +1018,8 @@ extern "C" pp_status pp_proximal_packed(pp_ctx *c, const float *chi, float lamda
 }
 
 // Measurement aid (bench.py): average duration of one launch of a hot kernel, timed with HIP events on
-// `stream` around `iters` back-to-back launches.  which: 0 = node message, 1 = edge update (layer 1 weights).
+// `stream` around `iters` back-to-back launches.  which: 0 = node message, 1 = edge update (layer 1 weights; the instance
+// that sampling runs, which does not write h_E back in the fused build).
 // The ctx must have been through pp_score / pp_sample so that its state buffers hold real activations.
 extern "C" pp_status pp_time_kernel(pp_ctx *c, int which, int iters, float *avg_ms, void *stream) {
     if (!c || !avg_ms || iters < 1) FAIL(PP_ERR_INVALID, "pp_time_kernel: bad argument");
@@ -1034,9 +1035,9 @@ extern "C" pp_status pp_time_kernel(pp_ctx *c, int which, int iters, float *avg_
     PP_HIP_CHECK(hipEventCreate(&e0));
     PP_HIP_CHECK(hipEventCreate(&e1));
     pp_status st = PP_OK;
-    for (int w = 0; w < 2 && st == PP_OK; w++) st = which == 0 ? pp_launch_node_message(c, 0, s) : pp_launch_edge_update(c, 1, s);
+    for (int w = 0; w < 2 && st == PP_OK; w++) st = which == 0 ? pp_launch_node_message(c, 0, s) : pp_launch_edge_update(c, 1, !pp_edge_fused(), s);
     PP_HIP_CHECK(hipEventRecord(e0, s));
-    for (int i = 0; i < iters && st == PP_OK; i++) st = which == 0 ? pp_launch_node_message(c, 0, s) : pp_launch_edge_update(c, 1, s);
+    for (int i = 0; i < iters && st == PP_OK; i++) st = which == 0 ? pp_launch_node_message(c, 0, s) : pp_launch_edge_update(c, 1, !pp_edge_fused(), s);
     PP_HIP_CHECK(hipEventRecord(e1, s));
     PP_HIP_CHECK(hipEventSynchronize(e1));
     float ms = 0.f;
@@ -1052,7 +1053,7 @@ extern "C" pp_status pp_time_kernel(pp_ctx *c, int which, int iters, float *avg_
 #ifdef PP_DIAG
 extern "C" pp_status pp_debug_edge(pp_ctx *c, int layer, void *stream) {
     if (!c || !c->plan->has_network) FAIL(PP_ERR_INVALID, "pp_debug_edge: bad ctx");
-    return pp_launch_edge_update(c, layer, static_cast<hipStream_t>(stream));
+    return pp_launch_edge_update(c, layer, true, static_cast<hipStream_t>(stream));
 }
 extern "C" pp_status pp_debug_nm(pp_ctx *c, int layer, void *stream) {
     if (!c || !c->plan->has_network) FAIL(PP_ERR_INVALID, "pp_debug_nm: bad ctx");
@@ -1063,10 +1064,11 @@ extern "C" pp_status pp_debug_set_hE(pp_ctx *c, const float *src, size_t n) {
     PP_HIP_CHECK(hipMemcpy(c->hE, src, n * sizeof(float), hipMemcpyDeviceToDevice));
     return PP_OK;
 }
-// which: 0 h_E, 1 S, 2 msum, 3 h_E0, 4 Z_em, 5 h_V
+// which: 0 h_E, 1 S, 2 msum, 3 h_E0, 4 Z_em, 5 h_V, 6 score
 extern "C" pp_status pp_debug_buffer(pp_ctx *c, int which, float *dst, size_t n) {
     if (!c || !dst) FAIL(PP_ERR_INVALID, "pp_debug_buffer: null");
-    const float *src = which == 0 ? c->hE : which == 1 ? c->S : which == 2 ? c->msum : which == 3 ? c->hE0 : which == 4 ? c->Zem : c->hV;
+    const float *src = which == 0 ? c->hE : which == 1 ? c->S : which == 2 ? c->msum : which == 3 ? c->hE0 : which == 4 ? c->Zem :
+                       which == 6 ? c->score : c->hV;
     PP_HIP_CHECK(hipDeviceSynchronize());
     PP_HIP_CHECK(hipMemcpy(dst, src, n * sizeof(float), hipMemcpyDeviceToDevice));
     return PP_OK;
@@ -1088,7 +1090,7 @@ extern "C" pp_status pp_debug_score_prefix(pp_ctx *c, const float *chi, float t,
     if (more()) st = pp_launch_node_message(c, 0, s);
     for (int l = 0; l < 3; l++) {
         if (more()) st = pp_launch_node_update(c, l, l < 2 ? PP_NU_MID : PP_NU_SCORE, nullptr, 0, PP_MODE_ODE, nullptr, l < 2 ? nullptr : &sp, nullptr, s);
-        if (l < 2 && more()) st = pp_launch_edge_update(c, l, s);
+        if (l < 2 && more()) st = pp_launch_edge_update(c, l, true, s);     // every h_E stays readable
     }
     return st;
 }

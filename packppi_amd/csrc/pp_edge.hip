@@ -392,7 +392,9 @@ k_node_message(EdgeArgs A) {
 // FUSE: the workgroup goes straight on to the NEXT layer's node message of its residue (same 32 edges, whose new
 // h_E it holds; the node-level inputs PA2 / PC2 / pts2 were written by the node update that ran before this kernel):
 // one launch, one prologue and one read of h_E less per layer.
-template <int S, bool ST0, bool FUSE>
+// WB: the new h_E is written back to A.hE_out (masked rows as zeros).  Without it (the layer-1 launch of a fused evaluation,
+// whose only consumer of h_E is the fused message below, fed from registers through xbuf) neither store is issued.
+template <int S, bool ST0, bool FUSE, bool WB = true>
 __global__ void __launch_bounds__(ET, PP_EU_WGS)
 k_edge_update(EdgeArgs A) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -404,7 +406,7 @@ k_edge_update(EdgeArgs A) {
     const int K = A.K;
     const int jj = j < K ? j : K - 1;
     if (A.rmask[n] == 0.f) {              // masked / padded residue: its edges are zero, whole workgroup leaves
-        if (j < K) {
+        if (WB && j < K) {
             f32x4v z = {0.f, 0.f, 0.f, 0.f};
             float *orow = A.hE_out + ((size_t)n * K + j) * 128 + 32 * wave;
 #pragma unroll
@@ -520,7 +522,7 @@ k_edge_update(EdgeArgs A) {
 #pragma unroll
     for (int r = 0; r < 16; r++) out[r] *= me;
     // lanes j >= K mirror edge K - 1 (same inputs, same value): they store it again rather than being masked off
-    store_tile(A.hE_out + ((size_t)n * K + jj) * 128 + 32 * wave, h, out);
+    if constexpr (WB) store_tile(A.hE_out + ((size_t)n * K + jj) * 128 + 32 * wave, h, out);
     if constexpr (FUSE) {
         // ---- next layer's node message on the fresh edges ------------------------------------------------
         // its inputs are fetched here and not earlier: offsets made opaque behind `out` (scalar ones stay scalar)
@@ -654,7 +656,8 @@ static bool edge_attrs() {
         ok = set(reinterpret_cast<const void *>(k_node_message<PP_NM_SLOTS, false>), NM_SMEM) &&
              set(reinterpret_cast<const void *>(k_node_message<PP_NM_SLOTS, true>), NM_SMEM) &&
              set(reinterpret_cast<const void *>(k_edge_update<PP_EU_SLOTS, false, true>), EU_SMEM) &&
-             set(reinterpret_cast<const void *>(k_edge_update<PP_EU_SLOTS, true, true>), EU_SMEM);
+             set(reinterpret_cast<const void *>(k_edge_update<PP_EU_SLOTS, true, true>), EU_SMEM) &&
+             set(reinterpret_cast<const void *>(k_edge_update<PP_EU_SLOTS, false, true, false>), EU_SMEM);
     }
     return ok;
 }
@@ -693,13 +696,15 @@ pp_status pp_launch_node_message(pp_ctx *c, int layer, hipStream_t s) {
     return PP_OK;
 }
 
-// layers 0 and 1 only (the reference's layer-2 edge update is dead code); also produces S / msum of layer + 1
-pp_status pp_launch_edge_update(pp_ctx *c, int layer, hipStream_t s) {
+// layers 0 and 1 only (the reference's layer-2 edge update is dead code); also produces S / msum of layer + 1.
+// keep_hE = false skips the h_E write-back of a layer-1 launch (layer 0 always stores: layer 1 reads it)
+pp_status pp_launch_edge_update(pp_ctx *c, int layer, bool keep_hE, hipStream_t s) {
     EDGE_ATTR_CHECK()
     if (layer < 0 || layer > 1) { pp_set_error("pp_launch_edge_update: layer must be 0 or 1"); return PP_ERR_INVALID; }
     EdgeArgs A = edge_args(c, layer, true);
     if (layer == 0) PP_LAUNCH(c, (k_edge_update<PP_EU_SLOTS, true, true>), dim3(c->N), dim3(ET), EU_SMEM, s, A);
-    else PP_LAUNCH(c, (k_edge_update<PP_EU_SLOTS, false, true>), dim3(c->N), dim3(ET), EU_SMEM, s, A);
+    else if (keep_hE) PP_LAUNCH(c, (k_edge_update<PP_EU_SLOTS, false, true>), dim3(c->N), dim3(ET), EU_SMEM, s, A);
+    else PP_LAUNCH(c, (k_edge_update<PP_EU_SLOTS, false, true, false>), dim3(c->N), dim3(ET), EU_SMEM, s, A);
     PP_HIP_CHECK(hipGetLastError());
     return PP_OK;
 }

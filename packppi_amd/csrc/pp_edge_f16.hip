@@ -736,7 +736,9 @@ k_node_message(EdgeArgs A) {
 // launch, one prologue and one read of h_E less per layer.
 // LNS: the plan carries operand scales behind small LayerNorm gains (A.ls_*): the three LayerNorm outputs that become f16 operands
 // are multiplied by their power-of-two scale vector before the split (the default instances contain none of it).
-template <int R, bool ST0, bool FUSE, bool LNS = false>
+// WB: the new h_E is written back to A.hE_out (masked rows as zeros).  Without it (the layer-1 launch of a fused evaluation,
+// whose only consumer of h_E is the fused message below, fed from registers through xbuf) neither store is issued.
+template <int R, bool ST0, bool FUSE, bool LNS = false, bool WB = true>
 __device__ __forceinline__ void edge_update_body(const EdgeArgs &A, const int res0, float *smem) {
     float *const xbuf = smem, *const x1buf = smem + R * XBUF_FLOATS, *const stat = x1buf + R * XBUF_FLOATS,
                  *const prm = stat + R * STAT_FLOATS;
@@ -750,7 +752,7 @@ __device__ __forceinline__ void edge_update_body(const EdgeArgs &A, const int re
 #pragma unroll
     for (int r = 0; r < R; r++)
         if (inr[r] && !live[r]) {         // masked / padded residue: its edges are zero
-            if (j < K) {
+            if (WB && j < K) {
                 f32x4v z = {0.f, 0.f, 0.f, 0.f};
                 float *orow = A.hE_out + ((size_t)n[r] * K + j) * 128 + 32 * wave;
 #pragma unroll
@@ -889,7 +891,7 @@ __device__ __forceinline__ void edge_update_body(const EdgeArgs &A, const int re
 #pragma unroll
         for (int q = 0; q < 16; q++) out[r][q] *= me[r];
         // lanes j >= K mirror edge K - 1 (same inputs, same value): they store it again rather than being masked off
-        if (live[r]) store_tile(A.hE_out + ((size_t)n[r] * K + jj) * 128 + 32 * wave, h, out[r]);
+        if (WB && live[r]) store_tile(A.hE_out + ((size_t)n[r] * K + jj) * 128 + 32 * wave, h, out[r]);
     }
     TS(12)
     if constexpr (FUSE) {
@@ -973,11 +975,11 @@ __device__ __forceinline__ void edge_update_body(const EdgeArgs &A, const int re
 #endif
 }
 
-template <int R, bool ST0, bool FUSE, bool LNS = false>
+template <int R, bool ST0, bool FUSE, bool LNS = false, bool WB = true>
 __global__ void __launch_bounds__(ET, R == 1 ? PP_WGS : PP_WGS2)
 k_edge_update(EdgeArgs A) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    edge_update_body<R, ST0, FUSE, LNS>(A, blockIdx.x * R, smem);
+    edge_update_body<R, ST0, FUSE, LNS, WB>(A, blockIdx.x * R, smem);
 }
 
 // MIXED launch for one complex that fills the chip once (2 < residues per CU <= 3).  Every workgroup streams the layer's
@@ -987,7 +989,7 @@ k_edge_update(EdgeArgs A) {
 // for two passes of the stream instead of three.  Workgroups 0 .. n_pairs - 1 take residues (2 b, 2 b + 1), the others one
 // residue each; in dispatch order the first half lands on distinct CUs, so a CU mostly gets one of each kind (placement is
 // the hardware's choice: it only affects speed).  A residue's kind is a function of (index, N): results are reproducible.
-template <bool ST0, bool FUSE, bool LNS = false>
+template <bool ST0, bool FUSE, bool LNS = false, bool WB = true>
 __global__ void __launch_bounds__(ET, 2)
 k_edge_update_mix(EdgeArgs A) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -1003,8 +1005,8 @@ k_edge_update_mix(EdgeArgs A) {
     } else {
         if (b < A.n_pairs) pair = b; else single = b - A.n_pairs;
     }
-    if (pair >= 0) edge_update_body<2, ST0, FUSE, LNS>(A, 2 * pair, smem);
-    else edge_update_body<1, ST0, FUSE, LNS>(A, 2 * A.n_pairs + single, smem);
+    if (pair >= 0) edge_update_body<2, ST0, FUSE, LNS, WB>(A, 2 * pair, smem);
+    else edge_update_body<1, ST0, FUSE, LNS, WB>(A, 2 * A.n_pairs + single, smem);
 }
 
 // the stand-alone node message (layer 0) with the same split of a CU's three residues: two weight passes instead of three
@@ -1284,11 +1286,15 @@ typedef void (*edge_kernel_t)(EdgeArgs);
 template <int R> static edge_kernel_t nm_kernel(bool st0) {
     return st0 ? k_node_message<R, true> : k_node_message<R, false>;
 }
-template <int R> static edge_kernel_t eu_kernel(bool st0, bool lns) {
+// wb = false selects the instances without the h_E write-back.  They exist for layer 1 only (ST0 = false): layer 0's h_E is
+// the next layer's input, so its launch always stores.
+template <int R> static edge_kernel_t eu_kernel(bool st0, bool lns, bool wb) {
+    if (!wb && !st0) return lns ? k_edge_update<R, false, PP_FUSED, true, false> : k_edge_update<R, false, PP_FUSED, false, false>;
     if (lns) return st0 ? k_edge_update<R, true, PP_FUSED, true> : k_edge_update<R, false, PP_FUSED, true>;
     return st0 ? k_edge_update<R, true, PP_FUSED> : k_edge_update<R, false, PP_FUSED>;
 }
-static edge_kernel_t mix_kernel(bool st0, bool lns) {
+static edge_kernel_t mix_kernel(bool st0, bool lns, bool wb) {
+    if (!wb && !st0) return lns ? k_edge_update_mix<false, PP_FUSED, true, false> : k_edge_update_mix<false, PP_FUSED, false, false>;
     if (lns) return st0 ? k_edge_update_mix<true, PP_FUSED, true> : k_edge_update_mix<false, PP_FUSED, true>;
     return st0 ? k_edge_update_mix<true, PP_FUSED> : k_edge_update_mix<false, PP_FUSED>;
 }
@@ -1296,8 +1302,8 @@ static edge_kernel_t mix_kernel(bool st0, bool lns) {
 static edge_kernel_t nm_kernel_r(int R, bool st0) {
     return R == 1 ? nm_kernel<1>(st0) : nm_kernel<2>(st0);
 }
-static edge_kernel_t eu_kernel_r(int R, bool st0, bool lns = false) {
-    return R == 1 ? eu_kernel<1>(st0, lns) : eu_kernel<2>(st0, lns);
+static edge_kernel_t eu_kernel_r(int R, bool st0, bool lns = false, bool wb = true) {
+    return R == 1 ? eu_kernel<1>(st0, lns, wb) : eu_kernel<2>(st0, lns, wb);
 }
 
 
@@ -1313,11 +1319,14 @@ static bool edge_attrs() {
         for (int R = 1; R <= PP_RMAX && ok; R++)
             for (int st0 = 0; st0 < 2 && ok; st0++)
                 ok = set(reinterpret_cast<const void *>(nm_kernel_r(R, st0)), MAX_SMEM) &&
-                     set(reinterpret_cast<const void *>(eu_kernel_r(R, st0, false)), MAX_SMEM) &&
-                     set(reinterpret_cast<const void *>(eu_kernel_r(R, st0, true)), MAX_SMEM);
+                     set(reinterpret_cast<const void *>(eu_kernel_r(R, st0, false, true)), MAX_SMEM) &&
+                     set(reinterpret_cast<const void *>(eu_kernel_r(R, st0, true, true)), MAX_SMEM) &&
+                     set(reinterpret_cast<const void *>(eu_kernel_r(R, st0, false, false)), MAX_SMEM) &&
+                     set(reinterpret_cast<const void *>(eu_kernel_r(R, st0, true, false)), MAX_SMEM);
         for (int st0 = 0; st0 < 2 && ok; st0++)
             for (int lns = 0; lns < 2 && ok; lns++)
-                ok = set(reinterpret_cast<const void *>(mix_kernel(st0, lns)), MAX_SMEM);
+                ok = set(reinterpret_cast<const void *>(mix_kernel(st0, lns, true)), MAX_SMEM) &&
+                     set(reinterpret_cast<const void *>(mix_kernel(st0, lns, false)), MAX_SMEM);
         ok = ok && set(reinterpret_cast<const void *>(k_node_message_mix<true>), MAX_SMEM) &&
              set(reinterpret_cast<const void *>(k_node_message_mix<false>), MAX_SMEM);
         int dev = 0;
@@ -1406,8 +1415,9 @@ pp_status pp_launch_node_message(pp_ctx *c, int layer, hipStream_t s) {
 extern "C" int pp_edge_variant(void) { return 1; }
 bool pp_edge_fused() { return PP_FUSED; }
 
-// layers 0 and 1 only (the reference's layer-2 edge update is dead code)
-pp_status pp_launch_edge_update(pp_ctx *c, int layer, hipStream_t s) {
+// layers 0 and 1 only (the reference's layer-2 edge update is dead code); keep_hE = false skips the h_E write-back of a
+// layer-1 launch (layer 0 always stores: layer 1 reads it)
+pp_status pp_launch_edge_update(pp_ctx *c, int layer, bool keep_hE, hipStream_t s) {
     EDGE_ATTR_CHECK()
     if (layer < 0 || layer > 1) { pp_set_error("pp_launch_edge_update: layer must be 0 or 1"); return PP_ERR_INVALID; }
     EdgeArgs A = edge_args(c, layer, true);
@@ -1419,11 +1429,11 @@ pp_status pp_launch_edge_update(pp_ctx *c, int layer, hipStream_t s) {
         A.n_pairs = (c->N + 2) / 3;
         A.mix_mode = g_mix;
         const int singles = c->N - 2 * A.n_pairs > 0 ? c->N - 2 * A.n_pairs : 0;
-        PP_LAUNCH(c, mix_kernel(layer == 0, lns), dim3(A.n_pairs + singles), dim3(ET), eu_smem(2) > eu_smem(1) ? eu_smem(2) : eu_smem(1), s, A);
+        PP_LAUNCH(c, mix_kernel(layer == 0, lns, keep_hE), dim3(A.n_pairs + singles), dim3(ET), eu_smem(2) > eu_smem(1) ? eu_smem(2) : eu_smem(1), s, A);
         PP_HIP_CHECK(hipGetLastError());
         return PP_OK;
     }
-    PP_LAUNCH(c, eu_kernel_r(R, layer == 0, lns), dim3((c->N + R - 1) / R), dim3(ET), eu_smem(R), s, A);
+    PP_LAUNCH(c, eu_kernel_r(R, layer == 0, lns, keep_hE), dim3((c->N + R - 1) / R), dim3(ET), eu_smem(R), s, A);
     PP_HIP_CHECK(hipGetLastError());
     return PP_OK;
 }

@@ -311,7 +311,10 @@ pp_status pp_launch_edge_embed_f16(pp_ctx *c, hipStream_t s);   // pp_edge_f16.h
 #endif
 pp_status pp_launch_node_message(pp_ctx *c, int layer, hipStream_t s);
 bool pp_edge_fused();            // does pp_launch_edge_update also compute the next layer's node message?
-pp_status pp_launch_edge_update(pp_ctx *c, int layer, hipStream_t s);   // + node message of layer + 1
+// + node message of layer + 1.  keep_hE: write the new h_E back to c->hE.  A fused evaluation passes false for layer 1, where
+// the fused message takes h_E from registers and the next evaluation's layer 0 overwrites c->hE before anything reads it;
+// the unfused build (whose layer-2 node message reads c->hE) and the diagnostics pass true.  Layer 0 always stores.
+pp_status pp_launch_edge_update(pp_ctx *c, int layer, bool keep_hE, hipStream_t s);
 pp_status pp_launch_atom14(pp_ctx *c, const float *chi, float *xyz, hipStream_t s);
 pp_status pp_launch_clash(pp_ctx *c, const float *xyz, float *per_res, float *dchi, hipStream_t s, bool use_candidates = false);
 pp_status pp_launch_proximal(pp_ctx *c, const float *chi, float lamda, int nsteps, float *traj,
