@@ -535,7 +535,12 @@ class AffinityHead:
 
     def encode(self, ctx: "Context", residue_type, sc_sincos, mut_mask, hV_pret):
         """AffinityPrediction.encode after the pretrained features, on ``ctx`` (a Context of the mutation-branch plan whose
-        batch carries the local mask as residue_mask): [B, L, 128] MPNN output."""
+        batch carries the local mask as residue_mask): [B, L, 128] MPNN output.
+
+        A NaN or infinity in ``hV_pret`` or ``sc_sincos`` is NOT flagged: pp_affinity_encode does not set bit 2 of
+        ``ctx.saturated()`` for them (only the context's own batch tensors are scanned when it is built).  ``hV_pret`` is this
+        path's own pp_score output, whose inputs are scanned by the pretrained network's context; a caller that passes features
+        from elsewhere checks them itself."""
         dev = self.device
         rt = residue_type.to(device=dev, dtype=torch.int64).contiguous()
         sc = sc_sincos.to(device=dev, dtype=torch.float32).contiguous()

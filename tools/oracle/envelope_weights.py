@@ -98,3 +98,38 @@ def small_ln_gain_variants(sd0):
             apply(f"mpnn.mpnn_layers.{l}.norm.2", [(f"mpnn.mpnn_layers.{l}.edge_dense.W_in.weight", 0)])
         out["small LN gains, " + name] = v
     return out
+
+
+_AP_PREFIXES = (("mutation_encoder.", "encoder."), ("mutation_mpnn.", "mpnn."))
+
+
+def affinity_envelope_variants(ap_sd):
+    """{name: state_dict}: every family above on the tensors PackPPI-AP owns (packppi_amd/weights.py affinity_weight_spec without
+    ``pret.``).  The mutation encoder + MPNN are the score network's encoder + MPNN under other names, so the families' key
+    matching applies to them after renaming; ``mutation_fusion.*``, ``ddg_predictor.*`` and the two embedding tables are 2-d
+    ``weight`` tensors and follow the rule for linear layers (their biases the rule for biases).  Two more variants make the plan
+    of the mutation branch rewrite the checkpoint (csrc/pp_rebalance.h): an edge FFN input layer x 3e5 (its ReLU chain is
+    rebalanced) and an edge-level LayerNorm gain x 4e4 (its operand features get a power-of-two scale)."""
+    def to_score(k):
+        for a, b in _AP_PREFIXES:
+            if k.startswith(a):
+                return b + k[len(a):]
+        return k
+
+    def to_ap(k):
+        for a, b in _AP_PREFIXES:
+            if k.startswith(b):
+                return a + k[len(b):]
+        return k
+
+    sd0 = {to_score(k): v for k, v in ap_sd.items()}
+    out = {}
+    for family in (envelope_variants, tiny_operand_variants, small_ln_gain_variants):
+        for name, v in family(sd0).items():
+            out[name] = {to_ap(k): t for k, t in v.items()}
+    for name, key, f in (("edge FFN W_in x3e5", "mutation_mpnn.mpnn_layers.1.edge_dense.W_in.weight", 3e5),
+                         ("edge LayerNorm gain x4e4", "mutation_mpnn.mpnn_layers.0.norm.3.weight", 4e4)):
+        v = dict(ap_sd)
+        v[key] = ap_sd[key] * f
+        out[name] = v
+    return out
