@@ -1,19 +1,22 @@
 // C ABI of libpackppi_hip.so: plan / ctx lifetime and the per-call kernel schedules.
-#include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
-#include <string.h>
 
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <cstring>
+#include <memory>
 #include <new>
 #include <string>
 #include <vector>
 
 #include "pp_internal.h"
+#include "pp_pack.h"           // the packed weight layouts and pack_network() (host-only header)
+#ifdef PP_EDGE_F16
+#include "pp_rebalance.h"      // rebalance_relu_chains(): power-of-two rebalancing of the ReLU chains (host-only header)
+#endif
 #include "pp_topk_aten.h"
-#include <algorithm>
-#include <cstring>
-#include <cmath>
-#include <chrono>
 
 static thread_local std::string g_err;
 void pp_set_error(const std::string &msg) { g_err = msg; }
@@ -34,270 +37,6 @@ extern "C" const char *pp_build_id(void) { return g_build_id + 12; }
         return code;         \
     } while (0)
 
-// ---------------------------------------------------------------------------------------------
-// host-side transpose of W[rows][ld] columns [c0, c0+cols) into dst[cols][rows]
-static size_t put_T(std::vector<float> &arena, const float *W, int rows, int ld, int c0, int cols) {
-    size_t at = arena.size();
-    at = (at + 3) & ~size_t(3);
-    arena.resize(at + (size_t)rows * cols);
-    float *d = arena.data() + at;
-    for (int r = 0; r < rows; r++)
-        for (int c = 0; c < cols; c++) d[(size_t)c * rows + r] = W[(size_t)r * ld + c0 + c];
-    return at;
-}
-
-// k-quad interleaved transpose for the node kernels (pp_node.hip): dst[in / 4][out][in % 4], so that a thread owning
-// output column `out` reads four consecutive reduction inputs with one 16-byte load (cols % 4 == 0)
-static size_t put_T4(std::vector<float> &arena, const float *W, int rows, int ld, int c0, int cols) {
-    size_t at = arena.size();
-    at = (at + 3) & ~size_t(3);
-    arena.resize(at + (size_t)rows * cols);
-    float *d = arena.data() + at;
-    for (int r = 0; r < rows; r++)
-        for (int c = 0; c < cols; c++) d[((size_t)(c >> 2) * rows + r) * 4 + (c & 3)] = W[(size_t)r * ld + c0 + c];
-    return at;
-}
-
-// fp32 -> IEEE binary16 bits, round to nearest even (subnormals kept: the MFMA honours them)
-static uint16_t f2h(float f) {
-    uint32_t x;
-    memcpy(&x, &f, 4);
-    const uint32_t sign = (x >> 16) & 0x8000u;
-    x &= 0x7fffffffu;
-    if (x >= 0x7f800000u) return (uint16_t)(sign | 0x7c00u | ((x > 0x7f800000u) ? 0x200u : 0));
-    if (x >= 0x477ff000u) return (uint16_t)(sign | 0x7c00u);                   // rounds to >= 65520: overflow
-    if (x < 0x33000001u) return (uint16_t)sign;                                 // < 2^-25: rounds to zero
-    int e = (int)(x >> 23) - 127;
-    uint32_t m = (x & 0x7fffffu) | 0x800000u;
-    int shift = e < -14 ? 13 + (-14 - e) : 13;                                  // subnormal: shift further
-    uint32_t r = m >> shift, rem = m & ((1u << shift) - 1u), half = 1u << (shift - 1);
-    if (rem > half || (rem == half && (r & 1u))) r++;
-    uint32_t out = e < -14 ? r : (((uint32_t)(e + 15) << 10) + (r - 0x400u));   // a carry out of the mantissa bumps e
-    return (uint16_t)(sign | out);
-}
-static float h2f(uint16_t h) {
-    const uint32_t sign = (uint32_t)(h & 0x8000u) << 16, e = (h >> 10) & 31u, m = h & 0x3ffu;
-    float v;
-    if (e == 0) v = ldexpf((float)m, -24);
-    else if (e == 31) v = m ? NAN : INFINITY;
-    else v = ldexpf((float)(m | 0x400u), (int)e - 25);
-    uint32_t b;
-    memcpy(&b, &v, 4);
-    b |= sign;
-    memcpy(&v, &b, 4);
-    return v;
-}
-
-#ifdef PP_EDGE_F16      // experimental split-f16 edge kernels (pp_edge_f16.hip): PACKPPI_EDGE=f16 python -m packppi_amd.build
-// Append one weight chunk (a K = 32 slice of a 128-row layer) packed for the edge kernels' wave-private LDS-DMA pipeline
-// and split-f16 arithmetic (pp_edge.hip): [wave 4][k-step s 2][part hi|lo 2][lane 64][i 8] halves = 16 KB, where lane =
-// (row & 31, half h) of wave row >> 5 holds the A-operand of v_mfma_f32_32x32x16_f16 for k-step s: input column
-//   col(s, h, i)   (`colmap`; < 0 = zero padding)  --  32-wide slices: col0 + 8 (2 s + (i >> 2)) + 4 h + (i & 3), the order
-//   in which the accumulator registers of the producing layer become B operands.
-template <typename ColMap>
-static void put_chunk_f16(std::vector<float> &arena, const float *W, int ld, int row0, ColMap colmap) {
-    size_t at = arena.size();
-    arena.resize(at + (size_t)128 * 32, 0.f);
-    uint16_t *d = reinterpret_cast<uint16_t *>(arena.data() + at);
-    for (int wave = 0; wave < 4; wave++)
-        for (int s = 0; s < 2; s++)
-            for (int lane = 0; lane < 64; lane++)
-                for (int i = 0; i < 8; i++) {
-                    const int row = row0 + 32 * wave + (lane & 31), h = lane >> 5;
-                    const int col = colmap(wave, s, h, i);
-                    const float w = col >= 0 ? W[(size_t)row * ld + col] : 0.f;
-                    const uint16_t hi = f2h(w);
-                    const uint16_t lo = f2h(w - h2f(hi));
-                    uint16_t *base = d + (size_t)wave * 2048;      // 4 KB per wave = 2048 halves
-                    base[((2 * s + 0) * 64 + lane) * 8 + i] = hi;
-                    base[((2 * s + 1) * 64 + lane) * 8 + i] = lo;
-                }
-}
-static void put_chunk(std::vector<float> &arena, const float *W, int ld, int row0, int col0, int ncols) {
-    (void)ncols;
-    put_chunk_f16(arena, W, ld, row0, [col0](int, int s, int h, int i) { return col0 + 8 * (2 * s + (i >> 2)) + 4 * h + (i & 3); });
-}
-// chunk at position p of a ROTATED layer (pp_edge_f16.hip, "ROTATED TILE ORDER"): wave w's quarter holds the columns of input
-// tile (w + p) & 3 of the 128-wide block at col_base -- every wave starts a layer with the tile it produced itself
-static void put_chunk_rot(std::vector<float> &arena, const float *W, int ld, int row0, int col_base, int p) {
-    put_chunk_f16(arena, W, ld, row0, [col_base, p](int wave, int s, int h, int i) {
-        return col_base + 32 * ((wave + p) & 3) + 8 * (2 * s + (i >> 2)) + 4 * h + (i & 3);
-    });
-}
-// geometry chunk C of a message MLP's first layer: features f = 16 (2 C + s) + 8 h + i of the 72 (columns 384 + f)
-// Lane half h of the geometry operand carries the features of points 4h .. 4h+3 only (so the four waves of a workgroup
-// compute one point each), point-major: k-step q = 0..3 holds point 4h + q as
-// p_loc xyz | |p_loc| | local neighbour xyz | its norm; k-step 4 holds the four distances | 0 x4.  k-step S = 2 C + s.
-static void put_geo_chunk(std::vector<float> &arena, const float *W, int C) {
-    put_chunk_f16(arena, W, 456, 0, [C](int, int s, int h, int i) {
-        const int S5 = 2 * C + s;
-        int f;
-        if (S5 < 4) {
-            const int pt = 4 * h + S5;
-            if (i < 3) f = 3 * pt + i;
-            else if (i == 3) f = 24 + pt;
-            else if (i < 7) f = 32 + 3 * pt + (i - 4);
-            else f = 56 + pt;
-        } else if (S5 == 4 && i < 4) {
-            f = 64 + 4 * h + i;
-        } else {
-            return -1;
-        }
-        return 384 + f;
-    });
-}
-#else
-// Append one weight chunk = the [128 rows][ncols] block of W (row stride ld) at (row0, col0), packed for the edge
-// kernels' wave-private LDS-DMA pipeline (pp_edge.hip): [wave 4][quad 4][lane 64][4 floats], where lane = (row & 31,
-// half h) of wave row >> 5 holds the A-operand registers of MFMA steps 4q..4q+3:
-//   ncols == 32:  W[row][col0 + 8 q + 4 h + p]                 (k-order F of the accumulator layout)
-//   ncols == 24:  W[row][col0 + 12 h + 4 q + p], quad 3 = 0    (geometry chunks: half h feeds inputs 12 h .. 12 h + 11)
-static void put_chunk(std::vector<float> &arena, const float *W, int ld, int row0, int col0, int ncols) {
-    size_t at = arena.size();
-    arena.resize(at + (size_t)128 * 32, 0.f);
-    float *d = arena.data() + at;
-    for (int wave = 0; wave < 4; wave++)
-        for (int q = 0; q < (ncols == 32 ? 4 : 3); q++)
-            for (int lane = 0; lane < 64; lane++)
-                for (int pp = 0; pp < 4; pp++) {
-                    int row = 32 * wave + (lane & 31), h = lane >> 5;
-                    int col = ncols == 32 ? 8 * q + 4 * h + pp : 12 * h + 4 * q + pp;
-                    d[((wave * 4 + q) * 64 + lane) * 4 + pp] = W[(size_t)(row0 + row) * ld + col0 + col];
-                }
-}
-static void put_geo_chunk(std::vector<float> &arena, const float *W, int C) { put_chunk(arena, W, 456, 0, 384 + 24 * C, 24); }
-// (the exact-fp32 edge kernels of pp_edge.hip read their input tiles in natural order)
-static void put_chunk_rot(std::vector<float> &arena, const float *W, int ld, int row0, int col_base, int p) {
-    put_chunk(arena, W, ld, row0, col_base + 32 * p, 32);
-}
-#endif
-// chunk stream of one message MLP: [W_in[:,128:256] x4 unless `skip_wb`,] W_in[:,384:456] x3 (24 cols), W_mid x4
-// [, W_out x4, FFN blocks].  Layer 0 skips the W_B chunks: its W_B h_E0 is precomputed once per complex (k_edge_static).
-static size_t put_stream(std::vector<float> &arena, const float *w, const LayerOff &L, bool edge, bool skip_wb) {
-    size_t at = (arena.size() + 3) & ~size_t(3);
-    arena.resize(at);
-    const float *win = w + (edge ? L.em_in_w : L.nm_in_w), *wmid = w + (edge ? L.em_mid_w : L.nm_mid_w);
-    // the four chunks of a 128-wide input are consumed in rotated tile order by the split-f16 kernels (put_chunk_rot)
-    if (!skip_wb)
-        for (int p = 0; p < 4; p++) put_chunk_rot(arena, win, 456, 0, 128, p);
-    for (int g = 0; g < 3; g++) put_geo_chunk(arena, win, g);
-    for (int p = 0; p < 4; p++) put_chunk_rot(arena, wmid, 128, 0, 0, p);
-    if (edge) {
-        for (int p = 0; p < 4; p++) put_chunk_rot(arena, w + L.em_out_w, 128, 0, 0, p);
-        for (int c = 0; c < 4; c++) {
-            for (int p = 0; p < 4; p++) put_chunk_rot(arena, w + L.ed_in_w, 128, 128 * c, 0, p);
-            for (int p = 0; p < 4; p++) put_chunk_rot(arena, w + L.ed_out_w, 512, 0, 128 * c, p);
-        }
-    }
-    return at;
-}
-// ---- k_node_update (pp_node.hip) ------------------------------------------------------------------------------
-// One slot: rows row0 .. row0+15 (those < nrows are real) of W (row stride ld), columns col0 .. col0+31 (those < col0 + ncols
-// real), as the A operand of v_mfma_f32_16x16x32_f16: lane l holds W[row0 + (l & 15)][col0 + 8 (l >> 4) + j], j = 0..7;
-// hi = f16(w), lo = f16((w - hi) * 2^11) (the scaling keeps lo out of the f16 subnormal range; the kernel accumulates the
-// lo products separately and folds them in with 2^-11).
-static void put_node_slot(uint16_t *d, const float *W, int ld, int row0, int nrows, int col0, int ncols) {
-    for (int lane = 0; lane < 64; lane++)
-        for (int j = 0; j < 8; j++) {
-            const int r = lane & 15, k = 8 * (lane >> 4) + j;
-            const float w = (W && r < nrows && k < ncols) ? W[(size_t)(row0 + r) * ld + col0 + k] : 0.f;
-            const uint16_t hi = f2h(w);
-            d[lane * 8 + j] = hi;
-            d[512 + lane * 8 + j] = f2h((w - h2f(hi)) * PP_NU_LO_SCALE);
-        }
-}
-// the slot list of layer l (see pp_internal.h): [wave][slot]
-static size_t put_node_stream(std::vector<float> &arena, const float *w, const WeightOff &off, int l) {
-    const LayerOff &L = off.layer[l];
-    const bool last = l == 2;
-    const int nslots = last ? PP_NU_SLOTS_LAST : PP_NU_SLOTS_MID;
-    size_t at = (arena.size() + 3) & ~size_t(3);
-    arena.resize(at + (size_t)PP_NU_WAVES * nslots * PP_NU_SLOT_FLOATS, 0.f);
-    for (int wv = 0; wv < PP_NU_WAVES; wv++) {
-        uint16_t *base = reinterpret_cast<uint16_t *>(arena.data() + at + (size_t)wv * nslots * PP_NU_SLOT_FLOATS);
-        int s = 0;
-        auto put = [&](const float *W, int ld, int row0, int nrows, int col0, int ncols) {
-            put_node_slot(base + (size_t)s * 1024, W, ld, row0, nrows, col0, ncols);
-            s++;
-        };
-        for (int ks = 0; ks < 4; ks++) put(w + L.nm_out_w, 128, 16 * wv, 16, 32 * ks, 32);
-        for (int c = 0; c < 4; c++)
-            for (int ks = 0; ks < 4; ks++) put(w + L.nd_in_w, 128, 16 * (4 * wv + c), 16, 32 * ks, 32);
-        for (int ks = 0; ks < 16; ks++) put(w + L.nd_out_w, 512, 16 * wv, 16, 32 * ks, 32);
-        if (!last) {
-            const LayerOff &Nx = off.layer[l + 1];
-            for (int ks = 0; ks < 4; ks++) put(w + L.em_in_w, 456, 16 * wv, 16, 32 * ks, 32);
-            for (int ks = 0; ks < 4; ks++) put(w + L.em_in_w, 456, 16 * wv, 16, 256 + 32 * ks, 32);
-            for (int ks = 0; ks < 4; ks++) put(w + Nx.nm_in_w, 456, 16 * wv, 16, 32 * ks, 32);
-            for (int ks = 0; ks < 4; ks++) put(w + Nx.nm_in_w, 456, 16 * wv, 16, 256 + 32 * ks, 32);
-            // the 48 point features: rows 0..23 = this layer's points_fn_edge, 24..47 = the next layer's points_fn_node
-            std::vector<float> pw(48 * 128);
-            memcpy(pw.data(), w + L.pts_edge_w, 24 * 128 * sizeof(float));
-            memcpy(pw.data() + 24 * 128, w + Nx.pts_node_w, 24 * 128 * sizeof(float));
-            for (int ks = 0; ks < 4; ks++) put(wv < 3 ? pw.data() : nullptr, 128, 16 * wv, 16, 32 * ks, 32);
-        } else {
-            const LayerOff &L0 = off.layer[0];
-            for (int ks = 0; ks < 4; ks++) put(wv < 4 ? w + off.d0_in_w : nullptr, 128, 16 * wv, 16, 32 * ks, 32);
-            for (int t = 0; t < 2; t++)
-                for (int ks = 0; ks < 2; ks++) put(wv == 0 ? w + off.d0_out_w : nullptr, 64, 16 * t, 16, 32 * ks, 32);
-            put(wv == 0 ? w + off.d2_in_w : nullptr, 32, 0, 16, 0, 32);
-            put(wv == 0 ? w + off.d2_out_w : nullptr, 16, 0, 4, 0, 16);
-            // node_embedding.weight [128][51], input columns 21..50 (6 backbone sin/cos, 8 chi sin/cos, 16 time) as one k-step
-            put(w + off.node_emb_w, 51, 16 * wv, 16, 21, 30);
-            for (int ks = 0; ks < 4; ks++) put(w + L0.nm_in_w, 456, 16 * wv, 16, 32 * ks, 32);
-            for (int ks = 0; ks < 4; ks++) put(w + L0.nm_in_w, 456, 16 * wv, 16, 256 + 32 * ks, 32);
-            for (int ks = 0; ks < 4; ks++) put(wv < 2 ? w + L0.pts_node_w : nullptr, 128, 16 * wv, wv == 0 ? 16 : 8, 32 * ks, 32);
-        }
-        if (s != nslots) abort();
-    }
-    return at;
-}
-static size_t put_node_params(std::vector<float> &arena, const float *w, const WeightOff &off, int l) {
-    const LayerOff &L = off.layer[l];
-    const bool last = l == 2;
-    size_t at = (arena.size() + 3) & ~size_t(3);
-    arena.resize(at + (last ? NU_P_LAST_TOTAL : NU_P_MID_TOTAL), 0.f);
-    float *d = arena.data() + at;
-    auto cp = [&](int dst, size_t src, int n) { memcpy(d + dst, w + src, n * sizeof(float)); };
-    cp(NU_P_OUTB, L.nm_out_b, 128); cp(NU_P_G0, L.norm_g[0], 128); cp(NU_P_B0, L.norm_b[0], 128);
-    cp(NU_P_FIB, L.nd_in_b, 512); cp(NU_P_FOB, L.nd_out_b, 128); cp(NU_P_G1, L.norm_g[1], 128); cp(NU_P_B1, L.norm_b[1], 128);
-    if (!last) {
-        const LayerOff &Nx = off.layer[l + 1];
-        cp(NU_P_PAE_B, L.em_in_b, 128); cp(NU_P_PAN_B, Nx.nm_in_b, 128);
-        cp(NU_P_PTS_B, L.pts_edge_b, 24); cp(NU_P_PTS_B + 24, Nx.pts_node_b, 24);
-    } else {
-        const LayerOff &L0 = off.layer[0];
-        cp(NU_P_DB0, off.d0_in_b, 64); cp(NU_P_DB1, off.d0_out_b, 32); cp(NU_P_DB2, off.d2_in_b, 16); cp(NU_P_DB3, off.d2_out_b, 4);
-        cp(NU_P_PAN0_B, L0.nm_in_b, 128); cp(NU_P_PTS0_B, L0.pts_node_b, 24);
-        cp(NU_P_EMB_B, off.node_emb_b, 128); cp(NU_P_EMB_G, off.norm_nodes_g, 128); cp(NU_P_EMB_BETA, off.norm_nodes_b, 128);
-    }
-    return at;
-}
-
-// k_edge_static's stream: the W_B chunks of layer 0's node message, then of its edge message
-static size_t put_static_stream(std::vector<float> &arena, const float *w, const LayerOff &L) {
-    size_t at = (arena.size() + 3) & ~size_t(3);
-    arena.resize(at);
-    for (int s = 0; s < 4; s++) put_chunk(arena, w + L.nm_in_w, 456, 0, 128 + 32 * s, 32);
-    for (int s = 0; s < 4; s++) put_chunk(arena, w + L.em_in_w, 456, 0, 128 + 32 * s, 32);
-    return at;
-}
-// the edge kernel's small per-layer vectors in one block (staged to LDS once per workgroup):
-// b_mid | b_out | ffn_out_b | g2 | be2 | ffn_in_b[512]   (1152 floats)
-static size_t put_edge_params(std::vector<float> &arena, const float *w, const LayerOff &L) {
-    size_t at = (arena.size() + 3) & ~size_t(3);
-    arena.resize(at);
-    auto app = [&](size_t off, int n) { arena.insert(arena.end(), w + off, w + off + n); };
-    app(L.em_mid_b, 128); app(L.em_out_b, 128); app(L.ed_out_b, 128);
-    app(L.norm_g[2], 128); app(L.norm_b[2], 128);
-    app(L.ed_in_b, 512);
-    return at;
-}
-
-#ifdef PP_EDGE_F16
-#include "pp_rebalance.h"      // rebalance_relu_chains(): power-of-two rebalancing of the ReLU chains (host-only header)
-#endif
-
 template <typename T>
 static pp_status upload(T **dst, const T *src, size_t n) {
     PP_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(dst), n * sizeof(T)));
@@ -313,18 +52,31 @@ extern "C" int pp_has_range_check(void) {
     return 0;
 #endif
 }
-extern "C" pp_status pp_range_check_parts(unsigned long long *edge_events, unsigned long long *node_events, int reset) {
-    if (!edge_events || !node_events) FAIL(PP_ERR_INVALID, "pp_range_check_parts: null argument");
+// `who`: the export the message names
+static pp_status range_check(const char *who, unsigned long long *edge_events, unsigned long long *node_events, int reset) {
 #ifdef PP_CHECK_RANGE
+    (void)who;
     PP_HIP_CHECK(hipDeviceSynchronize());
     *edge_events = (unsigned long long)pp_edge_range_hits(reset);
     *node_events = (unsigned long long)pp_node_range_hits(reset);
     return PP_OK;
 #else
+    (void)reset;
     *edge_events = *node_events = 0;
-    FAIL(PP_ERR_UNSUPPORTED, "pp_range_check_parts: this library was built without -DPP_CHECK_RANGE (use libpackppi_hip.chk.so: "
-                             "python -m packppi_amd.rangecheck)");
+    FAIL(PP_ERR_UNSUPPORTED, std::string(who) + ": this library was built without -DPP_CHECK_RANGE (use libpackppi_hip.chk.so: "
+                                                "python -m packppi_amd.rangecheck)");
 #endif
+}
+extern "C" pp_status pp_range_check_parts(unsigned long long *edge_events, unsigned long long *node_events, int reset) {
+    if (!edge_events || !node_events) FAIL(PP_ERR_INVALID, "pp_range_check_parts: null argument");
+    return range_check("pp_range_check_parts", edge_events, node_events, reset);
+}
+extern "C" pp_status pp_range_check(unsigned long long *events, int reset) {
+    if (!events) FAIL(PP_ERR_INVALID, "pp_range_check: null argument");
+    unsigned long long edge = 0, node = 0;
+    const pp_status st = range_check("pp_range_check", &edge, &node, reset);
+    *events = edge + node;
+    return st;
 }
 // Non-finite INPUTS.  The kernels clamp hidden activations with v_med3 / v_max, which turn a NaN into a finite number: a NaN that
 // enters with the caller's tensors would come out as finite angles that mean nothing, where the reference returns NaN
@@ -355,18 +107,31 @@ extern "C" pp_status pp_ctx_saturated(pp_ctx *c, int *flags, void *stream) {
     *flags = (int)v;
     return PP_OK;
 }
-extern "C" pp_status pp_range_check(unsigned long long *events, int reset) {
-    if (!events) FAIL(PP_ERR_INVALID, "pp_range_check: null argument");
-#ifdef PP_CHECK_RANGE
-    PP_HIP_CHECK(hipDeviceSynchronize());
-    *events = (unsigned long long)pp_edge_range_hits(reset) + (unsigned long long)pp_node_range_hits(reset);
-    return PP_OK;
-#else
-    *events = 0;
-    FAIL(PP_ERR_UNSUPPORTED, "pp_range_check: this library was built without -DPP_CHECK_RANGE (use libpackppi_hip.chk.so: "
-                             "python -m packppi_amd.rangecheck)");
-#endif
+
+// How far a side-chain atom can get from its CA whatever the chi angles are, per residue type: the atom sits at chain(lit) in the
+// backbone frame (origin CA), the chain composes default frames and rotations about x, a rotation keeps the norm and a frame adds at
+// most the length of its translation: |atom - CA| <= |lit| + sum of |t_k| over the frames of its chain (features.py:95-194).
+// Rigorous, about 15 % above the true maximum; the proximal loop's static partner lists are built from it (pp_clash.hip).
+static void side_chain_extents(const pp_tables *tables, float (&ext)[21]) {
+    for (int S = 0; S < 21; S++) {
+        float m = 0.f;
+        for (int a = 4; a < 14; a++) {
+            if (tables->atom14_mask[S * 14 + a] == 0.f) continue;
+            const float *lp = tables->lit_positions + (S * 14 + a) * 3;
+            float b = std::sqrt(lp[0] * lp[0] + lp[1] * lp[1] + lp[2] * lp[2]);
+            const int g = tables->atom14_to_group[S * 14 + a];
+            auto tlen = [&](int k) { const float *f = tables->default_frames + ((size_t)S * 8 + k) * 16; return std::sqrt(f[3] * f[3] + f[7] * f[7] + f[11] * f[11]); };
+            if (g >= 4) for (int k = 4; k <= g; k++) b += tlen(k);
+            else b += tlen(g);
+            m = std::max(m, b);
+        }
+        ext[S] = m * 1.0001f + 1e-3f;
+    }
 }
+
+// owners for objects under construction: an early return releases what was allocated so far through the public destroy call
+struct PlanDeleter { void operator()(pp_plan *p) const { pp_plan_destroy(p); } };
+struct CtxDeleter { void operator()(pp_ctx *c) const { pp_ctx_destroy(c); } };
 
 extern "C" pp_status pp_plan_create(const float *weights, size_t n_weights, const pp_tables *tables, int device,
                                     pp_plan **out) {
@@ -390,7 +155,9 @@ extern "C" pp_status pp_plan_create(const float *weights, size_t n_weights, cons
     if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
         FAIL(PP_ERR_NO_DEVICE, std::string("pp_plan_create: kernels are built for gfx950 only, device is ") + prop.gcnArchName);
 
-    pp_plan *p = new (std::nothrow) pp_plan();
+    // value-initialised: every device pointer is null until its upload, and pp_plan_destroy skips nulls -- every return below
+    // frees the plan and what it holds so far
+    std::unique_ptr<pp_plan, PlanDeleter> p(new (std::nothrow) pp_plan());
     if (!p) FAIL(PP_ERR_INVALID, "out of host memory");
     p->device = device;
     p->off = off;
@@ -402,89 +169,45 @@ extern "C" pp_status pp_plan_create(const float *weights, size_t n_weights, cons
     const float *wpack = weights;          // what the edge-level MFMA streams are packed from
 #ifdef PP_EDGE_F16
     std::vector<float> rebalanced, ln_packed;
-    p->ln_scale = nullptr;
-    p->ln_scaled_features = 0;
     if (has_net) {
         LnScales sc;
         p->rebalanced_chains = rewrite_checkpoint(weights, off, rebalanced, ln_packed, sc);
         p->ln_scaled_features = sc.n_scaled;
         for (size_t i = 0; i < off.total; i++)
-            if (!(std::fabs(rebalanced[i]) < 65504.f) || !(std::fabs(ln_packed[i]) < 65504.f)) {
-                delete p;
+            if (!(std::fabs(rebalanced[i]) < 65504.f) || !(std::fabs(ln_packed[i]) < 65504.f))
                 FAIL(PP_ERR_INVALID, "pp_plan_create: weight " + std::to_string(i) + " leaves the f16 range when its ReLU chain is "
                                      "rebalanced (run this checkpoint on libpackppi_hip.f32.so)");
-            }
         weights = rebalanced.data();       // everything below -- device copy, node-level streams, transposed copies -- is made from it
         wpack = ln_packed.data();          // ... and the edge-level streams from the copy with the operand scales in its columns
         if (sc.n_scaled > 0 && (st = upload(&p->ln_scale, &sc.v[0][0], (size_t)5 * 128)) != PP_OK) return st;
     }
 #endif
     if (has_net) {
-    if ((st = upload(&p->w, weights, off.total)) != PP_OK) return st;
-
-    std::vector<float> arena;
-    arena.reserve(3u << 20);
-    size_t o_node_emb = put_T(arena, weights + off.node_emb_w, 128, 51, 0, 51);
-    size_t o_edge_emb = put_T(arena, weights + off.edge_emb_w, 128, 468, 0, 468);
-    size_t o_l[3][14];
-    for (int l = 0; l < 3; l++) {
-        const LayerOff &L = off.layer[l];
-        o_l[l][0] = put_T4(arena, weights + L.pts_node_w, 24, 128, 0, 128);
-        o_l[l][1] = put_T4(arena, weights + L.pts_edge_w, 24, 128, 0, 128);
-        o_l[l][2] = put_T4(arena, weights + L.nm_in_w, 128, 456, 0, 128);
-        o_l[l][3] = put_T4(arena, weights + L.nm_in_w, 128, 456, 256, 128);
-        o_l[l][4] = put_T4(arena, weights + L.em_in_w, 128, 456, 0, 128);
-        o_l[l][5] = put_T4(arena, weights + L.em_in_w, 128, 456, 256, 128);
-        o_l[l][6] = put_T4(arena, weights + L.nm_out_w, 128, 128, 0, 128);
-        o_l[l][7] = put_T4(arena, weights + L.nd_in_w, 512, 128, 0, 128);
-        o_l[l][8] = put_T4(arena, weights + L.nd_out_w, 128, 512, 0, 512);
-        o_l[l][9] = put_stream(arena, wpack, L, false, l == 0);
-        o_l[l][10] = put_stream(arena, wpack, L, true, l == 0);
-        if (l < 2) put_stream(arena, wpack, off.layer[l + 1], false, false);   // fused kernel: next layer's node message follows
-        o_l[l][11] = put_edge_params(arena, weights, L);
-        o_l[l][12] = put_node_stream(arena, weights, off, l);
-        o_l[l][13] = put_node_params(arena, weights, off, l);
-    }
-    size_t o_static = put_static_stream(arena, wpack, off.layer[0]);
-
-
+        if ((st = upload(&p->w, weights, off.total)) != PP_OK) return st;
+        std::vector<float> arena;
+        const PackOff o = pack_network(arena, weights, wpack, off);
+        if ((st = upload(&p->wT, arena.data(), arena.size())) != PP_OK) return st;
+        const float *wT = p->wT;
+        p->node_emb_T = wT + o.node_emb_T;
+        p->edge_emb_T = wT + o.edge_emb_T;
+        for (int l = 0; l < 3; l++) {
+            const LayerPackOff &ol = o.lt[l];
+            LayerT &t = p->lt[l];
+            t.pts_node_wT = wT + ol.pts_node_wT; t.pts_edge_wT = wT + ol.pts_edge_wT;
+            t.nm_A_T = wT + ol.nm_A_T; t.nm_C_T = wT + ol.nm_C_T;
+            t.em_A_T = wT + ol.em_A_T; t.em_C_T = wT + ol.em_C_T;
+            t.nm_out_T = wT + ol.nm_out_T;
+            t.nd_in_T = wT + ol.nd_in_T; t.nd_out_T = wT + ol.nd_out_T;
+            t.nm_stream = wT + ol.nm_stream; t.em_stream = wT + ol.em_stream;
+            t.em_params = wT + ol.em_params;
+            t.nu_stream = wT + ol.nu_stream; t.nu_params = wT + ol.nu_params;
+        }
+        p->static_stream = wT + o.static_stream;
 #ifdef PP_EDGE_F16
-    // edge embedding, RBF block (input columns 65..464 of encoder.edge_embedding.weight): 13 chunks of two 16-deep k-steps,
-    // k-step S = atom pair S, lane half h = RBFs 8h .. 8h+7 of that pair
-    size_t o_embed = (arena.size() + 3) & ~size_t(3);
-    arena.resize(o_embed);
-    for (int cch = 0; cch < 13; cch++)
-        put_chunk_f16(arena, weights + off.edge_emb_w, 468, 0, [cch](int, int s2, int h, int i) {
-            const int k = 32 * cch + 16 * s2 + 8 * h + i;
-            return k < 400 ? 65 + k : -1;
-        });
+        p->embed_stream = wT + o.embed_stream;
 #endif
-    size_t o_d0i = put_T4(arena, weights + off.d0_in_w, 64, 128, 0, 128);
-    size_t o_d0o = put_T4(arena, weights + off.d0_out_w, 32, 64, 0, 64);
-    size_t o_d2i = put_T4(arena, weights + off.d2_in_w, 16, 32, 0, 32);
-    size_t o_d2o = put_T4(arena, weights + off.d2_out_w, 4, 16, 0, 16);
-    if ((st = upload(&p->wT, arena.data(), arena.size())) != PP_OK) return st;
-    p->node_emb_T = p->wT + o_node_emb;
-    p->edge_emb_T = p->wT + o_edge_emb;
-    for (int l = 0; l < 3; l++) {
-        LayerT &t = p->lt[l];
-        t.pts_node_wT = p->wT + o_l[l][0]; t.pts_edge_wT = p->wT + o_l[l][1];
-        t.nm_A_T = p->wT + o_l[l][2]; t.nm_C_T = p->wT + o_l[l][3];
-        t.em_A_T = p->wT + o_l[l][4]; t.em_C_T = p->wT + o_l[l][5];
-        t.nm_out_T = p->wT + o_l[l][6];
-        t.nd_in_T = p->wT + o_l[l][7]; t.nd_out_T = p->wT + o_l[l][8];
-        t.nm_stream = p->wT + o_l[l][9]; t.em_stream = p->wT + o_l[l][10];
-        t.em_params = p->wT + o_l[l][11];
-        t.nu_stream = p->wT + o_l[l][12]; t.nu_params = p->wT + o_l[l][13];
-    }
-    p->static_stream = p->wT + o_static;
-
-
-#ifdef PP_EDGE_F16
-    p->embed_stream = p->wT + o_embed;
-#endif
-    p->d0_in_T = p->wT + o_d0i; p->d0_out_T = p->wT + o_d0o;
-    p->d2_in_T = p->wT + o_d2i; p->d2_out_T = p->wT + o_d2o;
+        p->d0_in_T = wT + o.d0_in_T; p->d0_out_T = wT + o.d0_out_T;
+        p->d2_in_T = wT + o.d2_in_T; p->d2_out_T = wT + o.d2_out_T;
     }
 
     if ((st = upload(&p->default_frames, tables->default_frames, 21 * 8 * 16)) != PP_OK) return st;
@@ -492,32 +215,13 @@ extern "C" pp_status pp_plan_create(const float *weights, size_t n_weights, cons
     if ((st = upload(&p->atom14_mask, tables->atom14_mask, 21 * 14)) != PP_OK) return st;
     if ((st = upload(&p->lit_positions, tables->lit_positions, 21 * 14 * 3)) != PP_OK) return st;
     if ((st = upload(&p->between_radius, tables->between_radius, 21 * 14)) != PP_OK) return st;
-    {
-        // How far a side-chain atom can get from its CA whatever the chi angles are: the atom sits at chain(lit) in the backbone
-        // frame (origin CA), the chain composes default frames and rotations about x, a rotation keeps the norm and a frame adds at
-        // most the length of its translation: |atom - CA| <= |lit| + sum of |t_k| over the frames of its chain (features.py:95-194).
-        // Rigorous, about 15 % above the true maximum; the proximal loop's static partner lists are built from it (pp_clash.hip).
-        float ext[21];
-        for (int S = 0; S < 21; S++) {
-            float m = 0.f;
-            for (int a = 4; a < 14; a++) {
-                if (tables->atom14_mask[S * 14 + a] == 0.f) continue;
-                const float *lp = tables->lit_positions + (S * 14 + a) * 3;
-                float b = std::sqrt(lp[0] * lp[0] + lp[1] * lp[1] + lp[2] * lp[2]);
-                const int g = tables->atom14_to_group[S * 14 + a];
-                auto tlen = [&](int k) { const float *f = tables->default_frames + ((size_t)S * 8 + k) * 16; return std::sqrt(f[3] * f[3] + f[7] * f[7] + f[11] * f[11]); };
-                if (g >= 4) for (int k = 4; k <= g; k++) b += tlen(k);
-                else b += tlen(g);
-                m = std::max(m, b);
-            }
-            ext[S] = m * 1.0001f + 1e-3f;
-        }
-        if ((st = upload(&p->side_extent, ext, 21)) != PP_OK) return st;
-    }
+    float ext[21];
+    side_chain_extents(tables, ext);
+    if ((st = upload(&p->side_extent, ext, 21)) != PP_OK) return st;
     PP_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&p->bounds_lower), 21 * 14 * 14 * sizeof(float)));
     PP_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&p->bounds_upper), 21 * 14 * 14 * sizeof(float)));
     p->clash_params_set = false;
-    *out = p;
+    *out = p.release();
     return PP_OK;
 }
 
@@ -674,8 +378,10 @@ static pp_status prepare_impl(pp_plan *plan, const pp_batch *b, const int32_t *s
                 !b->SC_D_mask || !b->chi_1pi_periodic_mask || !b->chi_2pi_periodic_mask))
         FAIL(PP_ERR_INVALID, "pp_complex_prepare: batch has a null tensor pointer");
     PP_HIP_CHECK(hipSetDevice(plan->device));
-    pp_ctx *c = new (std::nothrow) pp_ctx();
-    if (!c) FAIL(PP_ERR_INVALID, "out of host memory");      // value-initialised: every pointer null, prof_which = -1
+    // value-initialised: every pointer null, prof_which = -1.  Every return below goes through pp_ctx_destroy.
+    std::unique_ptr<pp_ctx, CtxDeleter> owner(new (std::nothrow) pp_ctx());
+    if (!owner) FAIL(PP_ERR_INVALID, "out of host memory");
+    pp_ctx *c = owner.get();
     c->plan = plan;
     c->b = *b;
     c->packed = packed;
@@ -686,7 +392,6 @@ static pp_status prepare_impl(pp_plan *plan, const pp_batch *b, const int32_t *s
     c->K = shortest < PP_TOP_K ? shortest : PP_TOP_K;
     c->shortest = shortest;
     const size_t N = c->N, K = c->K;
-    pp_status st = PP_OK;
     // one arena for all workspaces (a context per batch is created and destroyed on the sampling path: ~35 hipMalloc /
     // hipFree pairs cost 1.5 ms per context, one pair 0.1 ms): sizes first, then one hipMalloc, then the pointers
     struct Slot { void **p; size_t bytes; };
@@ -695,11 +400,11 @@ static pp_status prepare_impl(pp_plan *plan, const pp_batch *b, const int32_t *s
 #define ALLOC(field, n) { const size_t bytes_ = (((n) ? (n) : 1) * sizeof(*c->field) + 255) & ~size_t(255);          \
                           slots.push_back({reinterpret_cast<void **>(&c->field), bytes_}); total += bytes_; }
     if (net) {
-    ALLOC(eidx, N * K); ALLOC(mask_att, N * 32); ALLOC(frames, N * 12); ALLOC(bbpos, N * 15);
-    ALLOC(hE0, N * K * 128); ALLOC(hE, N * K * 128); ALLOC(Znm, N * K * 128); ALLOC(Zem, N * K * 128); ALLOC(hV, N * 128); ALLOC(hV_alt, N * 128); ALLOC(S, N * 128); ALLOC(msum, N);
-    ALLOC(ptsN, N * 48); ALLOC(PAn, N * 128); ALLOC(PCn, N * 128);
-    ALLOC(ptsE, N * 48); ALLOC(PAe, N * 128); ALLOC(PCe, N * 128);
-    ALLOC(score, N * 4); ALLOC(chi_tmp, N * 4);
+        ALLOC(eidx, N * K); ALLOC(mask_att, N * 32); ALLOC(frames, N * 12); ALLOC(bbpos, N * 15);
+        ALLOC(hE0, N * K * 128); ALLOC(hE, N * K * 128); ALLOC(Znm, N * K * 128); ALLOC(Zem, N * K * 128); ALLOC(hV, N * 128); ALLOC(hV_alt, N * 128); ALLOC(S, N * 128); ALLOC(msum, N);
+        ALLOC(ptsN, N * 48); ALLOC(PAn, N * 128); ALLOC(PCn, N * 128);
+        ALLOC(ptsE, N * 48); ALLOC(PAe, N * 128); ALLOC(PCe, N * 128);
+        ALLOC(score, N * 4); ALLOC(chi_tmp, N * 4);
     }
     ALLOC(xyz, N * 42); ALLOC(rec, N * 64); ALLOC(axes, N * 24); ALLOC(rec2, N * 64); ALLOC(axes2, N * 24); ALLOC(brad, N); ALLOC(per_res, N); ALLOC(dchi, N * 4);
     ALLOC(px, N * 4); ALLOC(pm, N * 4); ALLOC(pv, N * 4); ALLOC(pz, N * 4); ALLOC(pxeff, N * 4); ALLOC(pmask, N);
@@ -729,35 +434,27 @@ static pp_status prepare_impl(pp_plan *plan, const pp_batch *b, const int32_t *s
         }
     }
     if (!c->arena && hipMalloc(&c->arena, total) != hipSuccess) {
-        pp_set_error("hipMalloc of the context workspace failed");
         c->arena = nullptr;
-        st = PP_ERR_HIP;
-    } else {
-        if (!c->arena_bytes) c->arena_bytes = total;
-        char *base = static_cast<char *>(c->arena);
-        for (const Slot &sl : slots) { *sl.p = base; base += sl.bytes; }
+        FAIL(PP_ERR_HIP, "hipMalloc of the context workspace failed");
     }
-    if (st == PP_OK) {
-        hipStream_t s_ = static_cast<hipStream_t>(stream);
-        if (packed) hipLaunchKernelGGL(k_fill_seg_packed, dim3((c->N + 255) / 256), dim3(256), 0, s_, c->seg, c->N, seg_offsets, n_seg, c->L);
-        else hipLaunchKernelGGL(k_fill_seg, dim3((c->N + 255) / 256), dim3(256), 0, s_, c->seg, c->N, c->L);
-        if (hipGetLastError() != hipSuccess) { pp_set_error("segment table launch failed"); st = PP_ERR_HIP; }
-        // the complexes' first rows, kept for pp_proximal_packed (the caller's table need not outlive this call's stream work)
-        if (st == PP_OK && packed &&
-            hipMemcpyAsync(c->seg_off, seg_offsets, ((size_t)n_seg + 1) * sizeof(int32_t), hipMemcpyDeviceToDevice, s_) != hipSuccess) {
-            pp_set_error("copying the segment offsets failed");
-            st = PP_ERR_HIP;
-        }
+    if (!c->arena_bytes) c->arena_bytes = total;
+    char *base = static_cast<char *>(c->arena);
+    for (const Slot &sl : slots) { *sl.p = base; base += sl.bytes; }
+    hipStream_t s_ = static_cast<hipStream_t>(stream);
+    if (packed) hipLaunchKernelGGL(k_fill_seg_packed, dim3((c->N + 255) / 256), dim3(256), 0, s_, c->seg, c->N, seg_offsets, n_seg, c->L);
+    else hipLaunchKernelGGL(k_fill_seg, dim3((c->N + 255) / 256), dim3(256), 0, s_, c->seg, c->N, c->L);
+    if (hipGetLastError() != hipSuccess) FAIL(PP_ERR_HIP, "segment table launch failed");
+    // the complexes' first rows, kept for pp_proximal_packed (the caller's table need not outlive this call's stream work)
+    if (packed && hipMemcpyAsync(c->seg_off, seg_offsets, ((size_t)n_seg + 1) * sizeof(int32_t), hipMemcpyDeviceToDevice, s_) != hipSuccess)
+        FAIL(PP_ERR_HIP, "copying the segment offsets failed");
+    if (hipMemsetAsync(c->sat, 0, 4 * sizeof(unsigned), s_) != hipSuccess) FAIL(PP_ERR_HIP, "clearing the saturation word failed");
+    if (net) {
+        pp_status st;
+        flag_nonfinite(c, c->b.X, 42, 12, s_);      // N, CA, C, O of the unmasked rows
+        if ((st = pp_launch_prepare(c, s_)) != PP_OK) return st;
+        if ((st = pp_launch_edge_static(c, s_)) != PP_OK) return st;
     }
-    if (st == PP_OK && hipMemsetAsync(c->sat, 0, 4 * sizeof(unsigned), static_cast<hipStream_t>(stream)) != hipSuccess) {
-        pp_set_error("clearing the saturation word failed");
-        st = PP_ERR_HIP;
-    }
-    if (net && st == PP_OK) flag_nonfinite(c, c->b.X, 42, 12, static_cast<hipStream_t>(stream));      // N, CA, C, O of the unmasked rows
-    if (net && st == PP_OK) st = pp_launch_prepare(c, static_cast<hipStream_t>(stream));
-    if (net && st == PP_OK) st = pp_launch_edge_static(c, static_cast<hipStream_t>(stream));
-    if (st != PP_OK) { pp_ctx_destroy(c); return st; }
-    *out = c;
+    *out = owner.release();
     return PP_OK;
 }
 
@@ -875,6 +572,16 @@ static pp_status run_network(pp_ctx *c, hipStream_t s, int step, int last_mode, 
     return PP_OK;
 }
 
+// the tail the single evaluations share: the three layers with the decoder (PP_NU_SCORE) on the embedded h_V, then the results out
+// (`score` or `hV` may be null).  `sp`: PP_NU_SCORE reads no per-step scalar and no time embedding from it
+static pp_status evaluate_and_copy(pp_ctx *c, const StepParams &sp, float *score, float *hV, hipStream_t s) {
+    pp_status st;
+    if ((st = run_network(c, s, 0, PP_NU_SCORE, nullptr, PP_MODE_ODE, nullptr, &sp, nullptr)) != PP_OK) return st;
+    if (score) PP_HIP_CHECK(hipMemcpyAsync(score, c->score, (size_t)c->N * 4 * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (hV) PP_HIP_CHECK(hipMemcpyAsync(hV, c->hV, (size_t)c->N * 128 * sizeof(float), hipMemcpyDeviceToDevice, s));
+    return PP_OK;
+}
+
 extern "C" pp_status pp_score(pp_ctx *c, const float *chi, float t, float *score, float *hV, void *stream) {
     if (c) c->last_stream = static_cast<hipStream_t>(stream);
     if (!c || !chi || !score) FAIL(PP_ERR_INVALID, "pp_score: null argument");
@@ -886,10 +593,7 @@ extern "C" pp_status pp_score(pp_ctx *c, const float *chi, float t, float *score
     pp_status st;
     flag_nonfinite(c, chi, 4, 4, s);
     if ((st = pp_launch_node_embed(c, chi, sp, s)) != PP_OK) return st;
-    if ((st = run_network(c, s, 0, PP_NU_SCORE, nullptr, PP_MODE_ODE, nullptr, &sp, nullptr)) != PP_OK) return st;
-    PP_HIP_CHECK(hipMemcpyAsync(score, c->score, (size_t)c->N * 4 * sizeof(float), hipMemcpyDeviceToDevice, s));
-    if (hV) PP_HIP_CHECK(hipMemcpyAsync(hV, c->hV, (size_t)c->N * 128 * sizeof(float), hipMemcpyDeviceToDevice, s));
-    return PP_OK;
+    return evaluate_and_copy(c, sp, score, hV, s);
 }
 
 // pp_score with a time per row: only the node embedding sees the time (columns 35..50 of encoder.node_embedding), so the
@@ -906,10 +610,7 @@ extern "C" pp_status pp_score_rows(pp_ctx *c, const float *chi, const float *t_r
     flag_nonfinite(c, chi, 4, 4, s);
     flag_nonfinite(c, t_rows, 1, 1, s);
     if ((st = pp_launch_node_embed_rows(c, chi, t_rows, s)) != PP_OK) return st;
-    if ((st = run_network(c, s, 0, PP_NU_SCORE, nullptr, PP_MODE_ODE, nullptr, &sp, nullptr)) != PP_OK) return st;
-    PP_HIP_CHECK(hipMemcpyAsync(score, c->score, (size_t)c->N * 4 * sizeof(float), hipMemcpyDeviceToDevice, s));
-    if (hV) PP_HIP_CHECK(hipMemcpyAsync(hV, c->hV, (size_t)c->N * 128 * sizeof(float), hipMemcpyDeviceToDevice, s));
-    return PP_OK;
+    return evaluate_and_copy(c, sp, score, hV, s);
 }
 
 extern "C" pp_status pp_affinity_encode(const pp_affinity *a, pp_ctx *c, const int64_t *residue_type, const float *sc_sincos,
@@ -925,9 +626,7 @@ extern "C" pp_status pp_affinity_encode(const pp_affinity *a, pp_ctx *c, const i
     fill_step(&sp, 0.f, 0.f, c->plan->annealed_temp);     // not read by the network: its time-embedding columns are zero
     pp_status st;
     if ((st = pp_launch_affinity_embed(c, a, residue_type, sc_sincos, mut_mask, hV_pret, s)) != PP_OK) return st;
-    if ((st = run_network(c, s, 0, PP_NU_SCORE, nullptr, PP_MODE_ODE, nullptr, &sp, nullptr)) != PP_OK) return st;
-    PP_HIP_CHECK(hipMemcpyAsync(hV, c->hV, (size_t)c->N * 128 * sizeof(float), hipMemcpyDeviceToDevice, s));
-    return PP_OK;
+    return evaluate_and_copy(c, sp, nullptr, hV, s);
 }
 
 extern "C" pp_status pp_sample(pp_ctx *c, float *chi, const float *schedule, int n_schedule, int mode,
@@ -1125,4 +824,3 @@ extern "C" pp_status pp_profile_read(pp_ctx *c, float *total_ms, int *launches) 
     c->prof_n = 0;
     return PP_OK;
 }
-

@@ -20,8 +20,7 @@
 PP_RANGE_COUNTER
 PP_RANGE_READER(pp_edge_range_hits)
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4v __attribute__((ext_vector_type(4)));
+#include "pp_edge_tile.h"      // f32x16 / f32x4v and the tile helpers shared by the two edge translation units
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 
 // ---- split-f16 arithmetic -------------------------------------------------------------------------------------
@@ -102,7 +101,7 @@ __device__ __forceinline__ void join_tile(const HT &t, f32x16 &v) {
 #define ET 256
 #define CH32 (128 * 32)                 // floats per packed weight chunk (16 KB); a wave's quarter is 1024 floats
 #define XBUF_FLOATS (4 * 4 * 64 * 4)    // exchange buffer: [tile][quad][lane] float4
-#define PARAM_FLOATS 1152               // edge kernel: small per-layer vectors, packed by pp_api.hip put_edge_params
+#define PARAM_FLOATS 1152               // edge kernel: small per-layer vectors, packed by pp_pack.h put_edge_params
 #define PARAM_LDS 640                   // ... of which b_mid | b_out | ffn_out_b | g2 | be2 are staged to LDS (ffn_in_b is read in place), then g3 | be3 (256)
 
 #define MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
@@ -119,7 +118,7 @@ struct EdgeArgs {
     const float *hE_in;        // [N][K][128]
     float *hE_out;             // [N][K][128]   (edge kernel)
     float *S, *msum;           // node kernel outputs
-    const float *wstream;      // this kernel's weight chunks, packed in consumption order (pp_api.hip put_chunk)
+    const float *wstream;      // this kernel's weight chunks, packed in consumption order (pp_pack.h put_chunk)
     const float *params;       // edge kernel: b_mid | b_out | ffn_out_b | g2 | be2 | ffn_in_b[512]
     const float *g3, *be3;     // edge kernel: last LayerNorm (read in the epilogue)
     const float *b_mid;        // node kernel (per-lane read)
@@ -255,21 +254,6 @@ __device__ __forceinline__ void mfma_geo(const AOp &a, const float *gbuf, int la
         }
     }
 }
-// one tile (16 registers) <-> 32 consecutive features of a row-major vector
-__device__ __forceinline__ void load_tile(const float *__restrict__ row32, int h, f32x16 &d) {
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        f32x4v a = *reinterpret_cast<const f32x4v *>(row32 + 8 * q + 4 * h);
-        d[4 * q] = a[0]; d[4 * q + 1] = a[1]; d[4 * q + 2] = a[2]; d[4 * q + 3] = a[3];
-    }
-}
-__device__ __forceinline__ void add_tile(const float *__restrict__ row32, int h, f32x16 &d) {
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        f32x4v a = *reinterpret_cast<const f32x4v *>(row32 + 8 * q + 4 * h);
-        d[4 * q] += a[0]; d[4 * q + 1] += a[1]; d[4 * q + 2] += a[2]; d[4 * q + 3] += a[3];
-    }
-}
 // a tile that is only ever ADDED to another one travels as four independent 16-byte pieces: a 16-register tuple for it would
 // fragment the register file where many tiles are in flight at once (the batched prologue loads)
 struct TileQ {
@@ -283,13 +267,6 @@ __device__ __forceinline__ void add_tile_q(const TileQ &t, f32x16 &d) {
 #pragma unroll
     for (int q = 0; q < 4; q++) {
         d[4 * q] += t.q[q][0]; d[4 * q + 1] += t.q[q][1]; d[4 * q + 2] += t.q[q][2]; d[4 * q + 3] += t.q[q][3];
-    }
-}
-__device__ __forceinline__ void store_tile(float *__restrict__ row32, int h, const f32x16 &d) {
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        f32x4v a = {d[4 * q], d[4 * q + 1], d[4 * q + 2], d[4 * q + 3]};
-        *reinterpret_cast<f32x4v *>(row32 + 8 * q + 4 * h) = a;
     }
 }
 // LNS instances: dst = src * s, s a per-feature power of two (exact) -- the operand copy that gets split when a LayerNorm gain is
@@ -310,28 +287,8 @@ __device__ __forceinline__ void scale_tile(const float *__restrict__ s32, int h,
     } else {                                                                              \
         PUBLISH_OWN(false, SRC, BUF)                                                      \
     }
-__device__ __forceinline__ void relu_tile(f32x16 &d) {
-#pragma unroll
-    for (int r = 0; r < 16; r++) d[r] = fmaxf(d[r], 0.f);
-}
-
-// exchange buffer: tile t, quad q, lane l -> float4
-__device__ __forceinline__ void xbuf_put(float *xbuf, int t, int lane, const f32x16 &d) {
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        f32x4v a = {d[4 * q], d[4 * q + 1], d[4 * q + 2], d[4 * q + 3]};
-        *reinterpret_cast<f32x4v *>(xbuf + ((t * 4 + q) * 64 + lane) * 4) = a;
-    }
-}
-__device__ __forceinline__ void xbuf_get(const float *xbuf, int t, int lane, f32x16 &d) {
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        f32x4v a = *reinterpret_cast<const f32x4v *>(xbuf + ((t * 4 + q) * 64 + lane) * 4);
-        d[4 * q] = a[0]; d[4 * q + 1] = a[1]; d[4 * q + 2] = a[2]; d[4 * q + 3] = a[3];
-    }
-}
-
-// split tiles through the same 4 KB per tile: [hi s0 | hi s1 | lo s0 | lo s1][lane] h8
+// split tiles through the exchange buffer (xbuf_put / xbuf_get of pp_edge_tile.h), the same 4 KB per tile:
+// [hi s0 | hi s1 | lo s0 | lo s1][lane] h8
 __device__ __forceinline__ void xbuf_put_h(float *xbuf, int t, int lane, const HT &d) {
     h8 *xb = reinterpret_cast<h8 *>(xbuf) + (t * 4) * 64 + lane;
     xb[0] = d.hi[0]; xb[64] = d.hi[1]; xb[128] = d.lo[0]; xb[192] = d.lo[1];
@@ -341,43 +298,8 @@ __device__ __forceinline__ void xbuf_get_h(const float *xbuf, int t, int lane, H
     d.hi[0] = xb[0]; d.hi[1] = xb[64]; d.lo[0] = xb[128]; d.lo[1] = xb[192];
 }
 
-// LayerNorm statistics over the 128 features of this lane's edge (64 here, 64 in lane ^ 32); v is centred in
-// place; returns 1/std, writes the mean
-__device__ __forceinline__ float ln_center(f32x16 (&v)[4], float &mean_out) {
-    float s = 0.f;
-#pragma unroll
-    for (int t = 0; t < 4; t++)
-#pragma unroll
-        for (int r = 0; r < 16; r++) s += v[t][r];
-    s += __shfl_xor(s, 32);
-    const float mean = s * (1.f / 128.f);
-    mean_out = mean;
-    float q = 0.f;
-#pragma unroll
-    for (int t = 0; t < 4; t++)
-#pragma unroll
-        for (int r = 0; r < 16; r++) {
-            float d = v[t][r] - mean;
-            v[t][r] = d;
-            q = fmaf(d, d, q);
-        }
-    q += __shfl_xor(q, 32);
-    return 1.f / sqrtf(q * (1.f / 128.f) + 1e-5f);
-}
-// centred tile -> tile * rstd * gamma + beta
-__device__ __forceinline__ void ln_affine_tile(f32x16 &v, float rstd, const float *__restrict__ gamma32,
-                                               const float *__restrict__ beta32, int h) {
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        f32x4v g = *reinterpret_cast<const f32x4v *>(gamma32 + 8 * q + 4 * h);
-        f32x4v b = *reinterpret_cast<const f32x4v *>(beta32 + 8 * q + 4 * h);
-#pragma unroll
-        for (int p = 0; p < 4; p++) v[4 * q + p] = fmaf(v[4 * q + p] * rstd, g[p], b[p]);
-    }
-}
-
 // 72 invariant point features of edge (i, j) as split-f16 MFMA operands in LDS.  Lane half h carries the features of
-// points 4h .. 4h+3 (pp_api.hip put_geo_chunk permutes W_G's columns to match), point-major: k-step q = 0..3 holds point
+// points 4h .. 4h+3 (pp_pack.h put_geo_chunk permutes W_G's columns to match), point-major: k-step q = 0..3 holds point
 // 4h + q as  p_loc xyz | |p_loc| | R_i^T (p_glob_j - t_i) xyz | its norm;  k-step 4 holds |p_glob_i - p_glob_j| of the four
 // points | 0 x4.  All four waves need all of it as B operand, so they SHARE the work: wave w computes point 4h + w of its
 // lanes, splits its eight values into ONE operand vector (hi, lo: two lane-linear 16-byte LDS writes) and drops its
@@ -473,7 +395,7 @@ __device__ __forceinline__ void geometry_put(const GeoI &g, const float (&pj)[3]
 //             stage whose operands have arrived -- position 3 of the layer, or of the W1 block in front of the publication.
 // A hand-over used to be: barrier, ReLU + split, LDS write, barrier, LDS read latency, all exposed (~1 300 cycles of a lone
 // workgroup, x10 per launch: profiles/r03_edge_stage_stamps.txt); what stays exposed is the split itself.  The weight stream
-// is private to each wave, so the rotation costs nothing: pp_api.hip put_chunk_rot packs wave w's quarter of the chunk at
+// is private to each wave, so the rotation costs nothing: pp_pack.h put_chunk_rot packs wave w's quarter of the chunk at
 // position p from input tile (w + p) & 3.  (Accumulation order per output feature changes with the wave: results differ
 // from round 3 by fp32 rounding, deterministically.)
 #define ROT(p) ((wave + (p)) & 3)        // input tile at position p of a rotated layer (wave-uniform)

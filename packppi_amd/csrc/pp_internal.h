@@ -55,9 +55,9 @@ struct LayerT {
     const float *nm_out_T;                           // [128][128]
     const float *nd_in_T;                            // [128][512]
     const float *nd_out_T;                           // [512][128]
-    const float *nm_stream, *em_stream;              // MFMA weight chunks packed in consumption order (pp_edge.hip)
+    const float *nm_stream, *em_stream;              // MFMA weight chunks packed in consumption order (pp_pack.h put_stream)
     const float *em_params;                          // edge kernel small vectors, one block
-    const float *nu_stream;                          // k_node_update: split-f16 weight slots, [wave][slot] (pp_api.hip put_node_stream)
+    const float *nu_stream;                          // k_node_update: split-f16 weight slots, [wave][slot] (pp_pack.h put_node_stream)
     const float *nu_params;                          // k_node_update: small per-layer vectors, one block (NU_P_* offsets)
 };
 
@@ -92,7 +92,7 @@ struct pp_plan {
     bool has_network;         // false: geometry-only plan (atom14 / clash / proximal)
     int knn_ties;             // PP_KNN_TIES_*: what the neighbour search does on exactly equal distances
     float annealed_temp;      // sample_cfg.annealed_temp (the T of schedule.py:205-208), default 3
-    int rebalanced_chains;    // split-f16 build: ReLU chains whose layers were rescaled by a power of two (pp_api.hip rebalance_relu_chains)
+    int rebalanced_chains;    // split-f16 build: ReLU chains whose layers were rescaled by a power of two (pp_rebalance.h rebalance_relu_chains)
     float *ln_scale = nullptr;       // split-f16 build: [5][128] power-of-two operand scales behind small LayerNorm gains (pp_rebalance.h), or null
     int ln_scaled_features = 0;      // ... how many of them differ from 1
     float *w;                 // device copy of all weights, original layouts
@@ -110,7 +110,7 @@ struct pp_plan {
     float *atom14_mask;       // [21][14]
     float *lit_positions;     // [21][14][3]
     float *between_radius;    // [21][14]
-    float *side_extent;       // [21] upper bound of |side-chain atom - CA| over all chi, per residue type (pp_api.hip clash_extents)
+    float *side_extent;       // [21] upper bound of |side-chain atom - CA| over all chi, per residue type (pp_api.hip side_chain_extents)
     float *bounds_lower, *bounds_upper;   // [21][14][14]
     float clash_tol;
     bool clash_params_set;
@@ -166,7 +166,7 @@ struct pp_ctx {
     uint8_t *pmask;           // [N]
     int32_t *cand;            // [N][4][PP_CL_CAP] proximal: static clash-partner candidates of every (residue, wave of its workgroup)
     int32_t *cand_cnt;        // [N][4] their number, -1 = more than PP_CL_CAP (that wave scans all partners as before)
-    float *prox_part;         // [PP_PROX_CHUNK][ceil(N / 16)] per-block loss terms of the proximal steps
+    float *prox_part;         // [PP_PROX_CHUNK][N] per-residue loss terms of the proximal steps parked before one reduction (k_prox_losses)
     // pp_proximal_packed (packed contexts and B = 1): one proximal loop per complex, all complexes in the same launches
     int32_t *seg_off;         // [B + 1] packed context: the first row of every complex, then N (a copy of the caller's table)
     int32_t *prox_nrows;      // [B] the caller's norm_rows (the row count each complex's means divide by)
