@@ -73,11 +73,12 @@ __device__ __forceinline__ float sel8(const float (&v)[8], int g) {
 // One Adam step of the proximal optimiser (UPD argument of k_clash<CAND, true>): since round 5 it runs in the TAIL of the clash
 // kernel, on the residue whose gradient that workgroup has just reduced, and goes straight on to the reconstruction at the new
 // angles (one launch per Adam step instead of two).  loss_t is parked per residue in `loss_part` and summed in the fixed order of
-// k_prox_losses, so the loss curve does not depend on arrival order.
+// k_prox_losses, so the loss curve does not depend on arrival order.  inv_row[i] = 1 / n of the complex residue i belongs to (written by
+// k_prox_init): the weight of its gradient and of its anchor term.
 struct ProxUpd {
     int t, nblocks;
-    float lamda, step_size, bc2s, inv_n;
-    const float *chi0, *z;
+    float lamda, step_size, bc2s;
+    const float *chi0, *z, *inv_row;
     const uint8_t *mask;
     float *x, *m, *v, *xeff, *traj, *last, *loss_part;
 };
@@ -264,6 +265,10 @@ k_atom14(int N, const float *__restrict__ X, const int64_t *__restrict__ rtype,
 // registers) and to the reconstruction at the new angles, which it writes into the OTHER record / axes buffer (F.rec_out, F.axes_out:
 // the other workgroups of this launch still read this step's) -- one launch per Adam step instead of two.  The four partner stripes of
 // wave 0 run the tail redundantly (same addresses, same values; stripe 0 stores): no divergence inside the 16-lane shuffles.
+//
+// The 1 / n of the mean over residues (gradient weights; with FUSE also the Adam anchor term): without FUSE (pp_clash) the argument
+// inv_ntot, 1 / N of the whole context, over a padded B > 1 batch too; with FUSE the residue's own complex, F.U.inv_row[i] (inv_ntot
+// is not read), so every complex of a packed batch gets the weights it gets alone.  Partners are rows of the same complex: same 1 / n.
 struct ClashFuse {
     const float *X, *BB_D, *default_frames, *amask14, *lit, *atom_exists, *between_radius;
     const int64_t *rindex;
@@ -281,30 +286,233 @@ k_clash(int N, const int2 *__restrict__ seg, const float *__restrict__ xyz, cons
         const float *__restrict__ axes, float tol, float inv_ntot,
         float *__restrict__ per_res, float *__restrict__ dchi, const int32_t *__restrict__ cand, const int32_t *__restrict__ cand_cnt,
         ClashFuse F) {
-#define PP_CLASH_INV_N inv_ntot
-#define PP_CLASH_STEP_INV_N U.inv_n
-#include "pp_clash_body.inc"
-#undef PP_CLASH_INV_N
-#undef PP_CLASH_STEP_INV_N
-}
+    __shared__ int s_list[CL_WAVES][CL_MAXC];
+    __shared__ float s_red[CL_WAVES][16][4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int i = blockIdx.x;              // one workgroup per residue; its waves take interleaved 64-partner windows
+    if (i >= N) return;
+    const int row0 = seg[i].x, L = seg[i].y;      // partner residues: the rows of this residue's own complex
+    const int a = lane & 15, slot = lane >> 4;
+    const bool own = a < 14;
+    float inv_n = inv_ntot;
+    if constexpr (FUSE) inv_n = F.U.inv_row[i];
+    // rec[n] (written by k_atom14): 14 x (x, y, z, exists * radius) | (CA, bounding radius) | (n side-chain atoms,
+    // residue_index, residue type): every partner needs 15 coalesced 16-byte reads instead of ~85 scattered ones
+    const float4 me = rec[(size_t)i * 16 + 15];
+    const int S = __float_as_int(me.z);
+    const int ri = __float_as_int(me.y);
+    float pa[3] = {0.f, 0.f, 0.f}, ea = 0.f, ra = 0.f;
+    if (own) {
+        const float4 q = rec[(size_t)i * 16 + a];
+        pa[0] = q.x; pa[1] = q.y; pa[2] = q.z;
+        ra = q.w;
+        ea = q.w != 0.f ? 1.f : 0.f;
+    }
+    const float nsc = me.x;                          // number of side-chain atoms -> this residue's weight in the mean
+    const float wi = inv_n / (nsc + 1e-10f);
+    const float4 cme = rec[(size_t)i * 16 + 14];          // bounding sphere (centroid, radius)
+    const float cai[3] = {cme.x, cme.y, cme.z};
+    const float radi = cme.w;
+    const float reach = 3.6f - tol;                 // largest r_a + r_b - tol (S-S)
 
-// The Adam-step launch of pp_proximal_packed: k_clash<CAND, true> with the 1 / n of the residue's own complex, inv_row[i] (written by
-// k_prox_init_seg), in place of the whole context's inv_ntot / U.inv_n: every complex of a packed batch gets the gradient and loss
-// weights it gets on its own.  (The partners are rows of the same complex: their 1 / n is the same.)
-template <bool CAND>
-__global__ void __launch_bounds__(64 * CL_WAVES)
-k_clash_seg(int N, const int2 *__restrict__ seg, const float *__restrict__ xyz, const float4 *__restrict__ rec, const float *__restrict__ exists,
-            const float *__restrict__ lower, const float *__restrict__ upper, const int32_t *__restrict__ a2g,
-            const float *__restrict__ axes, float tol, float *__restrict__ per_res, float *__restrict__ dchi,
-            const int32_t *__restrict__ cand, const int32_t *__restrict__ cand_cnt, ClashFuse F, const float *__restrict__ inv_row) {
-    constexpr bool FUSE = true;
-#define PP_CLASH_INV_N inv_row[i]
-#define PP_CLASH_STEP_INV_N inv_row[i]
-#include "pp_clash_body.inc"
-#undef PP_CLASH_INV_N
-#undef PP_CLASH_STEP_INV_N
+    float loss_a = 0.f, ga[3] = {0.f, 0.f, 0.f};
+    int *list = s_list[wave];
+    int n_static = -1;
+    if constexpr (CAND) n_static = cand_cnt[(size_t)i * CL_WAVES + wave];
+    const int32_t *my_cand = CAND ? cand + ((size_t)i * CL_WAVES + wave) * PP_CL_CAP : nullptr;
+    // partner residues of the same complex: from the static candidates (one pass), or in windows that fit the candidate list
+    const bool use_static = CAND && n_static >= 0;
+    bool more = true;
+    for (int base = 64 * wave; use_static ? more : base < L; ) {
+        int cnt = 0;
+        int jscan = base;
+        if (use_static) {
+            // the static candidates of this wave (ascending, at most PP_CL_CAP <= CL_MAXC): the exact sphere test on each, compacted in order
+            for (int c0 = 0; c0 < n_static; c0 += 64) {
+                const int ci = c0 + lane;
+                bool keep = false;
+                int jg = 0;
+                if (ci < n_static) {
+                    jg = my_cand[ci];
+                    const float4 cj = rec[(size_t)jg * 16 + 14];
+                    float dx = cj.x - cai[0], dy = cj.y - cai[1], dz = cj.z - cai[2];
+                    float lim = radi + cj.w + reach;
+                    keep = (lim > 0.f) && (dx * dx + dy * dy + dz * dz < lim * lim);
+                }
+                unsigned long long bal = __ballot(keep);
+                if (keep) list[cnt + __popcll(bal & ((1ull << lane) - 1ull))] = jg;
+                cnt += __popcll(bal);
+            }
+            more = false;
+        } else {
+            for (; jscan < L && cnt + 64 <= CL_MAXC; jscan += 64 * CL_WAVES) {
+                int jl = jscan + lane;
+                bool keep = false;
+                if (jl < L) {
+                    int jg = row0 + jl;
+                    if (jg != i) {
+                        const float4 cj = rec[(size_t)jg * 16 + 14];
+                        const float4 mj = rec[(size_t)jg * 16 + 15];
+                        float dx = cj.x - cai[0], dy = cj.y - cai[1], dz = cj.z - cai[2];
+                        float lim = radi + cj.w + reach;
+                        keep = (lim > 0.f) && (dx * dx + dy * dy + dz * dz < lim * lim) && (__float_as_int(mj.y) != ri);
+                    }
+                }
+                unsigned long long bal = __ballot(keep);
+                if (keep) list[cnt + __popcll(bal & ((1ull << lane) - 1ull))] = row0 + jl;
+                cnt += __popcll(bal);
+            }
+        }
+        base = jscan;
+        __builtin_amdgcn_wave_barrier();
+        for (int c = slot; c < cnt; c += 4) {
+            const int jg = list[c];
+            // all of the partner's records first, unconditionally: inside the branches below the compiler may not hoist them,
+            // and fourteen dependent round trips per candidate were 13 of this kernel's 20 us at T1124 (fetching the next
+            // candidate's records one iteration ahead on top of this gains nothing)
+            float4 pbr[14];
+#pragma unroll
+            for (int bb = 0; bb < 14; bb++) pbr[bb] = rec[(size_t)jg * 16 + bb];
+            const float4 mj = rec[(size_t)jg * 16 + 15];
+            const int rj = __float_as_int(mj.y);
+            const bool i_low = ri < rj;
+            const bool adjacent = i_low ? (ri + 1 == rj) : (rj + 1 == ri);
+            const float wj = inv_n / (mj.x + 1e-10f);
+            if (own && ea != 0.f) {
+#pragma unroll
+                for (int bb = 0; bb < 14; bb++) {
+                    const float4 pb = pbr[bb];
+                    bool ok = pb.w != 0.f && !(a < 4 && bb < 4) && !(a == 5 && bb == 5);
+                    if (adjacent) {
+                        // peptide bond C(lower) - N(higher)
+                        if (i_low ? (a == 2 && bb == 0) : (a == 0 && bb == 2)) ok = false;
+                    }
+                    if (ok) {
+                        float dx = pa[0] - pb.x, dy = pa[1] - pb.y, dz = pa[2] - pb.z;
+                        // squared test first: the IEEE sqrt and the division below are ~50 instructions, and only a few
+                        // per cent of the surviving atom pairs overlap (most trips skip the branch for the whole wave)
+                        const float d2 = 1e-10f + dx * dx + dy * dy + dz * dz;
+                        const float thr = (ra + pb.w) - tol;
+                        if (!(thr > 0.f && d2 < thr * thr)) continue;
+                        float d = sqrtf(d2);
+                        float err = thr - d;
+                        if (err > 0.f) {
+                            loss_a += err;
+                            float cw = (a >= 4 ? wi : 0.f) + (bb >= 4 ? wj : 0.f);
+                            float sc = -cw / d;
+                            ga[0] = fmaf(sc, dx, ga[0]); ga[1] = fmaf(sc, dy, ga[1]); ga[2] = fmaf(sc, dz, ga[2]);
+                        }
+                    }
+                }
+            }
+        }
+        __builtin_amdgcn_wave_barrier();
+    }
+    // fold the 4 partner stripes, then the 4 waves (fixed order: reproducible)
+    for (int o = 16; o <= 32; o <<= 1) {
+        loss_a += __shfl_xor(loss_a, o);
+        ga[0] += __shfl_xor(ga[0], o); ga[1] += __shfl_xor(ga[1], o); ga[2] += __shfl_xor(ga[2], o);
+    }
+    if (lane < 16) {
+        s_red[wave][lane][0] = loss_a; s_red[wave][lane][1] = ga[0]; s_red[wave][lane][2] = ga[1]; s_red[wave][lane][3] = ga[2];
+    }
+    __syncthreads();
+    if (wave != 0) return;
+    if (slot == 0) {
+#pragma unroll
+        for (int w = 1; w < CL_WAVES; w++) {
+            loss_a += s_red[w][a][0]; ga[0] += s_red[w][a][1]; ga[1] += s_red[w][a][2]; ga[2] += s_red[w][a][3];
+        }
+    } else {
+        loss_a = 0.f; ga[0] = ga[1] = ga[2] = 0.f;
+    }
+    // within-residue bounds: stripes of partner atoms b = slot, slot+4, ...
+    if (own && ea != 0.f) {
+        for (int bb = slot; bb < 14; bb += 4) {
+            if (bb == a || (a < 4 && bb < 4)) continue;
+            const float4 pb = rec[(size_t)i * 16 + bb];
+            if (pb.w == 0.f) continue;
+            float dx = pa[0] - pb.x, dy = pa[1] - pb.y, dz = pa[2] - pb.z;
+            float d = sqrtf(1e-10f + dx * dx + dy * dy + dz * dz);
+            float lo = lower[(S * 14 + a) * 14 + bb], up = upper[(S * 14 + a) * 14 + bb];
+            float e_lo = lo - d, e_up = d - up;
+            float l = fmaxf(e_lo, 0.f) + fmaxf(e_up, 0.f);
+            loss_a += 2.f * l;                                  // row sum + column sum of a symmetric table
+            float dl = (e_up > 0.f ? 1.f : 0.f) - (e_lo > 0.f ? 1.f : 0.f);
+            float cw = 2.f * ((a >= 4 ? wi : 0.f) + (bb >= 4 ? wi : 0.f));
+            float sc = cw * dl / d;
+            ga[0] = fmaf(sc, dx, ga[0]); ga[1] = fmaf(sc, dy, ga[1]); ga[2] = fmaf(sc, dz, ga[2]);
+        }
+    }
+    // fold the 4 partner stripes
+    for (int o = 16; o <= 32; o <<= 1) {
+        loss_a += __shfl_xor(loss_a, o);
+        ga[0] += __shfl_xor(ga[0], o); ga[1] += __shfl_xor(ga[1], o); ga[2] += __shfl_xor(ga[2], o);
+    }
+    float lres = (own && a >= 4) ? loss_a : 0.f;
+    for (int o = 8; o > 0; o >>= 1) lres += __shfl_xor(lres, o);
+    const float pres = lres / (nsc + 1e-10f);
+    if (lane == 0) per_res[i] = pres;
+    float dk[4] = {0.f, 0.f, 0.f, 0.f};
+    if (dchi || FUSE) {
+        if (own && a >= 5) {
+            const int g = a2g[S * 14 + a];
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                if (g >= 4 + k) {
+                    const float *ax = axes + ((size_t)i * 4 + k) * 6;
+                    float rx = pa[0] - ax[3], ry = pa[1] - ax[4], rz = pa[2] - ax[5];
+                    float cx = ax[1] * rz - ax[2] * ry, cy = ax[2] * rx - ax[0] * rz, cz = ax[0] * ry - ax[1] * rx;
+                    dk[k] = ga[0] * cx + ga[1] * cy + ga[2] * cz;
+                }
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            for (int o = 8; o > 0; o >>= 1) dk[k] += __shfl_xor(dk[k], o);
+        }
+        if (dchi && lane < 4) dchi[(size_t)i * 4 + lane] = lane == 0 ? dk[0] : (lane == 1 ? dk[1] : (lane == 2 ? dk[2] : dk[3]));
+    }
+    if constexpr (FUSE) {
+        const ProxUpd &U = F.U;
+        const bool st = slot == 0;                  // the stripe that stores
+        // everything the tail reads, in one batch: the reconstruction's inputs and the Adam operands of chi_k, k = a < 4
+        const A14In I = a14_load(i, a, S, F.X, F.BB_D, F.default_frames, a2g, F.amask14, F.lit, F.atom_exists, F.between_radius);
+        const int k = a < 4 ? a : 0;
+        const size_t e = (size_t)i * 4 + k;
+        const float xe = U.xeff[e], ze = U.z[e], xo = U.x[e], mo = U.m[e], vo = U.v[e], c0v = U.chi0[e];
+        const bool mk = U.mask[i] != 0;
+        // loss_t = mean_n [sum_k (xeff - z)^2 + lamda per_res] at the incoming iterate; then torch.optim.Adam defaults (lr 1e-2,
+        // betas (0.9, 0.999), eps 1e-8, bias-corrected; step_size = lr / (1 - beta1^t) and bc2s = sqrt(1 - beta2^t) come from the
+        // host in double); outputs as optimize.py:66-71
+        const float dch = k == 0 ? dk[0] : (k == 1 ? dk[1] : (k == 2 ? dk[2] : dk[3]));
+        float q = 0.f, outv = 0.f;
+        if (a < 4) {
+            const float d = xe - ze;
+            q = fabsf(d) * fabsf(d);
+            const float b1 = 0.9f, b2 = 0.999f, eps = 1e-8f;
+            float g = 0.f;
+            if (mk) g = 2.f * (xo - ze) * inv_n + U.lamda * dch;
+            const float mm = mo + (g - mo) * (1.f - b1);             // exp_avg.lerp_(grad, 1 - beta1)
+            const float vv = vo * b2 + (1.f - b2) * (g * g);
+            const float denom = sqrtf(vv) / U.bc2s + eps;
+            const float xn = xo - U.step_size * (mm / denom);
+            outv = mk ? xn : c0v;
+            if (st) {
+                U.m[e] = mm; U.v[e] = vv; U.x[e] = xn;
+                U.xeff[e] = outv;
+                if (U.traj) U.traj[(size_t)U.t * N * 4 + e] = outv;
+                if (U.last) U.last[e] = outv;
+            }
+        }
+        q += __shfl_xor(q, 1, 16);
+        q += __shfl_xor(q, 2, 16);
+        if (lane == 0) U.loss_part[(size_t)U.t * N + i] = q + U.lamda * pres;
+        // the reconstruction at the new angles: lane a in 3..6 evaluates chi_(a-3), which lane a - 3 has just stepped
+        const float chi_new = __shfl(outv, (a - 3) & 15, 16);
+        a14_finish(I, i, a, st, a < 3 ? I.bbd_t : chi_new, F.rindex, F.xyz, F.axes_out, F.brad, F.rec_out);
+    }
 }
-
 
 // ---------------------------------------------------------------------------------------------
 // static clash-partner candidates of the proximal loop: once per pp_proximal
@@ -365,71 +573,7 @@ k_clash_cand(int N, const int2 *__restrict__ seg, const float *__restrict__ X, c
 }
 
 // ---------------------------------------------------------------------------------------------
-// proximal optimiser pieces (B = 1)
-// ---------------------------------------------------------------------------------------------
-// mean of per_res -> scal[0]; mask[n] = per_res[n] > mean; z = chi*mask; x = z; m = v = 0; xeff = chi
-__global__ void __launch_bounds__(1024)
-k_prox_init(int N, const float *__restrict__ per_res, const float *__restrict__ chi, uint8_t *__restrict__ mask,
-            float *__restrict__ z, float *__restrict__ x, float *__restrict__ m, float *__restrict__ v,
-            float *__restrict__ xeff) {
-    __shared__ float s_part[16];
-    __shared__ float s_mean;
-    float s = 0.f;
-    for (int n = threadIdx.x; n < N; n += 1024) s += per_res[n];
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float t = 0.f;
-        for (int w = 0; w < 16; w++) t += s_part[w];
-        s_mean = t / (float)N;
-    }
-    __syncthreads();
-    const float mean = s_mean;
-    for (int n = threadIdx.x; n < N; n += 1024) {
-        const bool mk = per_res[n] > mean;
-        mask[n] = mk ? 1 : 0;
-        for (int k = 0; k < 4; k++) {
-            const float c = chi[(size_t)n * 4 + k];
-            const float zz = mk ? c : 0.f;
-            z[(size_t)n * 4 + k] = zz;
-            x[(size_t)n * 4 + k] = zz;
-            m[(size_t)n * 4 + k] = 0.f;
-            v[(size_t)n * 4 + k] = 0.f;
-            xeff[(size_t)n * 4 + k] = c;
-        }
-    }
-}
-
-// losses[t0 + t] = (1 / N) sum of the per-residue terms the fused clash kernel left, in a fixed order: groups of 16 residues first,
-// then the groups in order (the order of rounds 2-4, when a 16-residue block of k_atom14<true> summed its own terms).  One workgroup per
-// step: a lane adds up one group (16 sequential adds), the group sums meet in LDS and lane 0 adds them in order -- the chain of N dependent
-// loads a single lane per step would walk is 185 us at T1124.
-__global__ void __launch_bounds__(256)
-k_prox_losses(int N, float inv_n, const float *__restrict__ part, float *__restrict__ losses) {
-    __shared__ float s_tt[256];
-    const int t = blockIdx.x;
-    const int ngroups = (N + 15) / 16;
-    float s = 0.f;
-    for (int g0 = 0; g0 < ngroups; g0 += 256) {          // 256 groups (4096 residues) at a time, in order
-        const int g = g0 + threadIdx.x;
-        float tt = 0.f;
-        if (g < ngroups)
-            for (int i = 16 * g; i < 16 * g + 16 && i < N; i++) tt += part[(size_t)t * N + i];
-        s_tt[threadIdx.x] = tt;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            const int n = ngroups - g0 < 256 ? ngroups - g0 : 256;
-            for (int q = 0; q < n; q++) s += s_tt[q];
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) losses[t] = s * inv_n;
-}
-
-// ---------------------------------------------------------------------------------------------
-// the same per complex of a packed batch (pp_proximal_packed).  Written out next to the B = 1 kernels rather than folded into them:
-// k_prox_init / k_prox_losses compile to the instructions they always did.
+// proximal optimiser pieces: per complex (segment) of the context.  pp_proximal is the one-segment case of pp_proximal_packed.
 // ---------------------------------------------------------------------------------------------
 // Rows [row0, row1) of complex s: off[s], off[s + 1] of the packed table (off == nullptr: one complex, rows 0 .. N - 1, a B = 1
 // context); a table that breaks the contract of pp_complex_prepare_packed is clamped to stay inside the batch.
@@ -440,16 +584,19 @@ __device__ __forceinline__ void seg_rows(const int32_t *__restrict__ off, int s,
     row1 = row1 < row0 ? row0 : (row1 > N ? N : row1);
 }
 
-// k_prox_init for complex s = blockIdx.x, in its own row coordinates: the same strided sums, butterfly and in-order LDS combine, so the
-// mean has the bits it has when the complex is alone.  The divisor of the complex's means is n = max(nrows[s], its length) (nrows ==
-// nullptr: the length), converted to fp32 as the B = 1 path converts N; 1 / n is IEEE-rounded (HIP's fp32 division is correctly
-// rounded unless fast-math flags say otherwise), the bits of the host's 1.0f / (float)N of pp_launch_proximal.  Also writes (n, 1 / n)
-// to seg_norm[s] (k_prox_losses_seg) and 1 / n to inv_row of every row of the complex (k_clash_seg).
+// For complex s = blockIdx.x, in its own row coordinates: mean of per_res; mask[g] = per_res[g] > mean; z = chi * mask; x = z;
+// m = v = 0; xeff = chi.  The divisor of the complex's means is n = max(nrows[s], its length) (nrows == nullptr: the length).  Also
+// writes (n, 1 / n) to seg_norm[s] (k_prox_losses) and 1 / n to inv_row of every row of the complex (k_clash<CAND, true>).
+//
+// A complex has the same bits alone in a B = 1 context and as one segment of a packed batch: the divisor is (float)n either way (a
+// B = 1 context: (float)N); 1 / n is one IEEE-rounded fp32 division on the device, the bits of 1.0f / (float)n on the host (HIP's
+// fp32 division is correctly rounded unless fast-math flags say otherwise); the strided sums, the butterfly and the in-order LDS
+// combine run over the complex's own rows counted from its first; and k_prox_losses counts its groups of 16 from that row too.
 __global__ void __launch_bounds__(1024)
-k_prox_init_seg(int N, const int32_t *__restrict__ off, const int32_t *__restrict__ nrows, const float *__restrict__ per_res,
-                const float *__restrict__ chi, uint8_t *__restrict__ mask, float *__restrict__ z, float *__restrict__ x,
-                float *__restrict__ m, float *__restrict__ v, float *__restrict__ xeff, float2 *__restrict__ seg_norm,
-                float *__restrict__ inv_row) {
+k_prox_init(int N, const int32_t *__restrict__ off, const int32_t *__restrict__ nrows, const float *__restrict__ per_res,
+            const float *__restrict__ chi, uint8_t *__restrict__ mask, float *__restrict__ z, float *__restrict__ x,
+            float *__restrict__ m, float *__restrict__ v, float *__restrict__ xeff, float2 *__restrict__ seg_norm,
+            float *__restrict__ inv_row) {
     __shared__ float s_part[16];
     __shared__ float s_mean;
     int row0, row1;
@@ -489,11 +636,14 @@ k_prox_init_seg(int N, const int32_t *__restrict__ off, const int32_t *__restric
     }
 }
 
-// k_prox_losses for step t0 + blockIdx.x of complex s = blockIdx.y: its groups of 16 counted from its own first row, in the order of
-// k_prox_losses (the complex's bits when it is alone), times its own 1 / n -> losses[s][t0 + t] (row stride nsteps).
+// losses[s][t0 + t] (row stride nsteps) for step t = blockIdx.x of the chunk and complex s = blockIdx.y: (1 / n) sum of the
+// per-residue terms the fused clash kernel left, in a fixed order: groups of 16 residues counted from the complex's first row, then the
+// groups in order (the order of rounds 2-4, when a 16-residue block of k_atom14<true> summed its own terms).  One workgroup per (step,
+// complex): a lane adds up one group (16 sequential adds), the group sums meet in LDS and lane 0 adds them in order -- the chain of N
+// dependent loads a single lane per step would walk is 185 us at T1124.
 __global__ void __launch_bounds__(256)
-k_prox_losses_seg(int N, const int32_t *__restrict__ off, const float2 *__restrict__ seg_norm, const float *__restrict__ part,
-                  int nsteps, int t0, float *__restrict__ losses) {
+k_prox_losses(int N, const int32_t *__restrict__ off, const float2 *__restrict__ seg_norm, const float *__restrict__ part,
+              int nsteps, int t0, float *__restrict__ losses) {
     __shared__ float s_tt[256];
     const int t = blockIdx.x, sg = blockIdx.y;
     int row0, row1;
@@ -502,7 +652,7 @@ k_prox_losses_seg(int N, const int32_t *__restrict__ off, const float2 *__restri
     const float *p = part + (size_t)t * N + row0;
     const int ngroups = (len + 15) / 16;
     float s = 0.f;
-    for (int g0 = 0; g0 < ngroups; g0 += 256) {
+    for (int g0 = 0; g0 < ngroups; g0 += 256) {          // 256 groups (4096 residues) at a time, in order
         const int g = g0 + threadIdx.x;
         float tt = 0.f;
         if (g < ngroups)
@@ -561,10 +711,10 @@ pp_status pp_launch_clash(pp_ctx *c, const float *xyz, float *per_res, float *dc
     return PP_OK;
 }
 
-// The proximal loop of pp_proximal (seg = false: one complex, the whole context's 1 / N) and of pp_proximal_packed (seg = true:
-// every complex of the context with its own mean, 1 / n and loss reduction; k_prox_init_seg, k_clash_seg, k_prox_losses_seg).
-static pp_status prox_loop(pp_ctx *c, const float *chi, float lamda, int nsteps, const int32_t *nrows, float *traj, float *chi_last,
-                           float *losses, hipStream_t s, bool seg) {
+// The proximal loop, per complex of the context: each has its own clash mask mean, 1 / n and loss row (losses [B][nsteps]).  off:
+// the device table of first rows, or nullptr = the context is one complex, rows 0 .. N - 1 (its losses are row 0).
+static pp_status prox_loop(pp_ctx *c, const float *chi, float lamda, int nsteps, const int32_t *off, const int32_t *nrows,
+                           float *traj, float *chi_last, float *losses, hipStream_t s) {
     pp_status st;
     const pp_plan *p = c->plan;
     // static partner candidates of the whole loop (the backbone does not move): k_clash<true> reads them instead of scanning
@@ -576,19 +726,15 @@ static pp_status prox_loop(pp_ctx *c, const float *chi, float lamda, int nsteps,
     // clash mask at the incoming angles (optimize.py:5-18); per_res does not depend on the normaliser
     if ((st = pp_launch_atom14(c, chi, c->xyz, s)) != PP_OK) return st;
     if ((st = pp_launch_clash(c, c->xyz, c->per_res, nullptr, s, cands)) != PP_OK) return st;
-    const int32_t *off = c->packed ? c->seg_off : nullptr;
-    if (seg)
-        hipLaunchKernelGGL(k_prox_init_seg, dim3(c->B), dim3(1024), 0, s, c->N, off, nrows, c->per_res, chi, c->pmask, c->pz, c->px,
-                           c->pm, c->pv, c->pxeff, c->prox_seg, c->prox_inv);
-    else
-        hipLaunchKernelGGL(k_prox_init, dim3(1), dim3(1024), 0, s, c->N, c->per_res, chi, c->pmask, c->pz, c->px, c->pm,
-                           c->pv, c->pxeff);
+    hipLaunchKernelGGL(k_prox_init, dim3(c->B), dim3(1024), 0, s, c->N, off, nrows, c->per_res, chi, c->pmask, c->pz, c->px, c->pm,
+                       c->pv, c->pxeff, c->prox_seg, c->prox_inv);
     // ONE launch per Adam step: [clash + gradient at the current angles -> step t on the workgroup's own residue -> its
     // reconstruction at the new angles, into the other record / axes buffer].  Loss terms are parked per residue and reduced in a
     // fixed order, PP_PROX_CHUNK steps at a time.
     // (records and axes at the start angles are in c->rec / c->axes already: the atom14 launch above ran at `chi`, which is what
     // k_prox_init has just copied into xeff, and the clash launch between them writes neither)
     float *rec_in = c->rec, *rec_out = c->rec2, *axes_in = c->axes, *axes_out = c->axes2;
+    const float inv_ntot_unused = 0.f;          // k_clash's scalar 1 / N is pp_clash's: the fused instances read U.inv_row
     for (int t = 0; t < nsteps; t++) {
         const double bc1 = 1.0 - pow(0.9, (double)(t + 1)), bc2 = 1.0 - pow(0.999, (double)(t + 1));
         ClashFuse F;
@@ -597,39 +743,28 @@ static pp_status prox_loop(pp_ctx *c, const float *chi, float lamda, int nsteps,
         F.xyz = c->xyz; F.axes_out = axes_out; F.brad = c->brad; F.rec_out = reinterpret_cast<float4 *>(rec_out);
         ProxUpd &U = F.U;
         U.nblocks = 0;
-        U.lamda = lamda; U.step_size = (float)(1e-2 / bc1); U.bc2s = (float)sqrt(bc2); U.inv_n = 1.0f / (float)c->N;
-        U.chi0 = chi; U.z = c->pz; U.mask = c->pmask;
+        U.lamda = lamda; U.step_size = (float)(1e-2 / bc1); U.bc2s = (float)sqrt(bc2);
+        U.chi0 = chi; U.z = c->pz; U.inv_row = c->prox_inv; U.mask = c->pmask;
         U.x = c->px; U.m = c->pm; U.v = c->pv; U.xeff = c->pxeff; U.last = chi_last;
         U.loss_part = c->prox_part;
         U.t = t % PP_PROX_CHUNK;
         U.traj = traj ? traj + (size_t)(t - U.t) * c->N * 4 : nullptr;     // U.t indexes within the chunk
         c->prof_armed = c->prof_which == 3;          // pp_profile_kernel(3): the fused clash + Adam step + reconstruction
         const float4 *rin = reinterpret_cast<const float4 *>(rec_in);
-        if (seg && cands)
-            PP_LAUNCH(c, (k_clash_seg<true>), dim3(c->N), dim3(64 * CL_WAVES), 0, s, c->N, c->seg, c->xyz, rin, c->b.atom_mask,
-                      p->bounds_lower, p->bounds_upper, p->atom14_to_group, axes_in, p->clash_tol, c->per_res, c->dchi, c->cand,
-                      c->cand_cnt, F, c->prox_inv);
-        else if (seg)
-            PP_LAUNCH(c, (k_clash_seg<false>), dim3(c->N), dim3(64 * CL_WAVES), 0, s, c->N, c->seg, c->xyz, rin, c->b.atom_mask,
-                      p->bounds_lower, p->bounds_upper, p->atom14_to_group, axes_in, p->clash_tol, c->per_res, c->dchi, nullptr,
-                      nullptr, F, c->prox_inv);
-        else if (cands)
+        if (cands)
             PP_LAUNCH(c, (k_clash<true, true>), dim3(c->N), dim3(64 * CL_WAVES), 0, s, c->N, c->seg, c->xyz,
                       rin, c->b.atom_mask, p->bounds_lower, p->bounds_upper, p->atom14_to_group,
-                      axes_in, p->clash_tol, 1.0f / (float)c->N, c->per_res, c->dchi, c->cand, c->cand_cnt, F);
+                      axes_in, p->clash_tol, inv_ntot_unused, c->per_res, c->dchi, c->cand, c->cand_cnt, F);
         else
             PP_LAUNCH(c, (k_clash<false, true>), dim3(c->N), dim3(64 * CL_WAVES), 0, s, c->N, c->seg, c->xyz,
                       rin, c->b.atom_mask, p->bounds_lower, p->bounds_upper, p->atom14_to_group,
-                      axes_in, p->clash_tol, 1.0f / (float)c->N, c->per_res, c->dchi, nullptr, nullptr, F);
+                      axes_in, p->clash_tol, inv_ntot_unused, c->per_res, c->dchi, nullptr, nullptr, F);
         c->prof_armed = false;
         std::swap(rec_in, rec_out);
         std::swap(axes_in, axes_out);
-        const bool chunk_end = U.t == PP_PROX_CHUNK - 1 || t == nsteps - 1;
-        if (chunk_end && seg)
-            hipLaunchKernelGGL(k_prox_losses_seg, dim3(U.t + 1, c->B), dim3(256), 0, s, c->N, off, c->prox_seg, c->prox_part, nsteps,
+        if (U.t == PP_PROX_CHUNK - 1 || t == nsteps - 1)
+            hipLaunchKernelGGL(k_prox_losses, dim3(U.t + 1, c->B), dim3(256), 0, s, c->N, off, c->prox_seg, c->prox_part, nsteps,
                                t - U.t, losses);
-        else if (chunk_end)
-            hipLaunchKernelGGL(k_prox_losses, dim3(U.t + 1), dim3(256), 0, s, c->N, U.inv_n, c->prox_part, losses + (t - U.t));
     }
     PP_HIP_CHECK(hipGetLastError());
     return PP_OK;
@@ -637,15 +772,17 @@ static pp_status prox_loop(pp_ctx *c, const float *chi, float lamda, int nsteps,
 
 pp_status pp_launch_proximal(pp_ctx *c, const float *chi, float lamda, int nsteps, float *traj, float *chi_last,
                              float *losses, hipStream_t s) {
-    return prox_loop(c, chi, lamda, nsteps, nullptr, traj, chi_last, losses, s, false);
+    // B = 1 (pp_proximal checks it): the whole context is the complex, whatever table a packed context came with
+    return prox_loop(c, chi, lamda, nsteps, nullptr, nullptr, traj, chi_last, losses, s);
 }
 
 pp_status pp_launch_proximal_packed(pp_ctx *c, const float *chi, float lamda, int nsteps, bool norm_given, float *traj,
                                     float *chi_last, float *chi_accepted, float *losses, hipStream_t s) {
-    pp_status st = prox_loop(c, chi, lamda, nsteps, norm_given ? c->prox_nrows : nullptr, traj, chi_last, losses, s, true);
+    const int32_t *off = c->packed ? c->seg_off : nullptr;
+    pp_status st = prox_loop(c, chi, lamda, nsteps, off, norm_given ? c->prox_nrows : nullptr, traj, chi_last, losses, s);
     if (st != PP_OK) return st;
     const int longest = c->packed ? c->L : c->N;
-    hipLaunchKernelGGL(k_prox_accept, dim3((longest * 4 + 255) / 256, c->B), dim3(256), 0, s, c->N, c->packed ? c->seg_off : nullptr,
+    hipLaunchKernelGGL(k_prox_accept, dim3((longest * 4 + 255) / 256, c->B), dim3(256), 0, s, c->N, off,
                        losses, nsteps, chi, chi_last, chi_accepted);
     PP_HIP_CHECK(hipGetLastError());
     return PP_OK;

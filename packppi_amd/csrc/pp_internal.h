@@ -167,11 +167,11 @@ struct pp_ctx {
     int32_t *cand;            // [N][4][PP_CL_CAP] proximal: static clash-partner candidates of every (residue, wave of its workgroup)
     int32_t *cand_cnt;        // [N][4] their number, -1 = more than PP_CL_CAP (that wave scans all partners as before)
     float *prox_part;         // [PP_PROX_CHUNK][N] per-residue loss terms of the proximal steps parked before one reduction (k_prox_losses)
-    // pp_proximal_packed (packed contexts and B = 1): one proximal loop per complex, all complexes in the same launches
+    // the proximal loop (packed contexts and B = 1) runs per complex, all complexes in the same launches; a B = 1 context is one complex
     int32_t *seg_off;         // [B + 1] packed context: the first row of every complex, then N (a copy of the caller's table)
     int32_t *prox_nrows;      // [B] the caller's norm_rows (the row count each complex's means divide by)
-    float2 *prox_seg;         // [B] per complex: (mean divisor, 1 / divisor), written by k_prox_init_seg
-    float *prox_inv;          // [N] 1 / divisor of the row's complex: the gradient weight of k_clash_seg
+    float2 *prox_seg;         // [B] per complex: (mean divisor, 1 / divisor), written by k_prox_init
+    float *prox_inv;          // [N] 1 / divisor of the row's complex: the gradient and anchor weight of k_clash<CAND, true>
     float *scal;              // small scalar scratch
     unsigned *sat;            // sticky word: bit 0 = an edge kernel, bit 1 = a node kernel clamped a hidden activation at 65504
     // in-situ kernel timing (pp_profile_kernel): every launch of one hot kernel carries a start / stop event pair
@@ -317,6 +317,8 @@ bool pp_edge_fused();            // does pp_launch_edge_update also compute the 
 pp_status pp_launch_edge_update(pp_ctx *c, int layer, bool keep_hE, hipStream_t s);
 pp_status pp_launch_atom14(pp_ctx *c, const float *chi, float *xyz, hipStream_t s);
 pp_status pp_launch_clash(pp_ctx *c, const float *xyz, float *per_res, float *dchi, hipStream_t s, bool use_candidates = false);
+// One loop for both: pp_launch_proximal is the single-complex call (means over the complex's own rows, losses [nsteps]) without the
+// accept rule; the packed one takes per-complex divisors from c->prox_nrows if norm_given, fills losses [B][nsteps] and chi_accepted.
 pp_status pp_launch_proximal(pp_ctx *c, const float *chi, float lamda, int nsteps, float *traj,
                              float *chi_last, float *losses, hipStream_t s);
 pp_status pp_launch_proximal_packed(pp_ctx *c, const float *chi, float lamda, int nsteps, bool norm_given, float *traj,

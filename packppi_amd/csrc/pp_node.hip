@@ -220,54 +220,9 @@ __device__ void message_inputs(Smem &sm, int &flip, const PreW &w, const float *
     __syncthreads();
 }
 
-// Node embedding for the block's residues -> value (before LN) of feature f (all ks-groups compute the same thing)
-__device__ __forceinline__ VN embed_pre(Smem &sm, const NodeArgs &A, const float *chi, const StepParams &sp, int n0) {
-    const int t = threadIdx.x, f = t & 127;
-    if (t < 6) sm.p[t] = load_rows(A.bb_sincos, 6, n0, A.N, t);
-    else if (t < 14) {
-        int k = (t - 6) >> 1, sc = (t - 6) & 1;
-        VN x = load_rows(chi, 4, n0, A.N, k), m = load_rows(A.sc_mask, 4, n0, A.N, k), v;
-        VN_FOR v.g[gi] = sc ? f4v{cosf(x.g[gi].x), cosf(x.g[gi].y), cosf(x.g[gi].z), cosf(x.g[gi].w)}
-                            : f4v{sinf(x.g[gi].x), sinf(x.g[gi].y), sinf(x.g[gi].z), sinf(x.g[gi].w)};
-        sm.p[t] = vmul(v, m);
-    }
-    __syncthreads();
-    VN acc = vn(A.emb_b[f]);
-    VN_FOR {
-        const int b = n0 + 4 * gi;
-        const int t0 = b + 0 < A.N ? (int)A.rtype[b + 0] : 0, t1 = b + 1 < A.N ? (int)A.rtype[b + 1] : 0;
-        const int t2 = b + 2 < A.N ? (int)A.rtype[b + 2] : 0, t3 = b + 3 < A.N ? (int)A.rtype[b + 3] : 0;
-        acc.g[gi].x += A.embT[t0 * 128 + f]; acc.g[gi].y += A.embT[t1 * 128 + f];
-        acc.g[gi].z += A.embT[t2 * 128 + f]; acc.g[gi].w += A.embT[t3 * 128 + f];
-    }
-#pragma unroll
-    for (int k = 0; k < 14; k++) acc = vfma(A.embT[(21 + k) * 128 + f], sm.p[k], acc);
-    const float *te = sp.temb;
-    float tacc = 0.f;
-#pragma unroll
-    for (int k = 0; k < 16; k++) tacc = fmaf(A.embT[(35 + k) * 128 + f], te[k], tacc);
-    return vadd(acc, vn(tacc));
-}
-
-__global__ void __launch_bounds__(NT)
-k_node_embed(NodeArgs A, PreW pre0, const float *chi, StepParams sp) {
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    Smem &sm = *reinterpret_cast<Smem *>(smem_raw);
-    int flip = 0, rflip = 0;
-    const int f = threadIdx.x & 127, ks = threadIdx.x >> 7, n0 = blockIdx.x * NB;
-    VN v = embed_pre(sm, A, chi, sp, n0);
-    VN h = layernorm(sm, rflip, v, A.emb_g[f], A.emb_beta[f]);
-    if (ks == 0) {
-        store_rows(A.hV, 128, n0, A.N, f, h);
-        sm.h[f] = h;
-    }
-    __syncthreads();
-    message_inputs(sm, flip, pre0, A.frames, n0, A.N, A.ptsN, A.PAn, A.PCn);
-}
-
-// embed_pre without its 16 time columns: bias + the 35 inputs that do not depend on the time, the same arithmetic in the same
-// order (a copy, not a shared helper: k_node_embed must keep compiling to the instructions it had).  Ends behind a barrier that
-// follows the writes to sm.p[0..13], so the caller may fill other slots of sm.p before the call and read them after it.
+// Node embedding for the block's residues without its 16 time columns -> bias + the 35 inputs that do not depend on the time, for
+// feature f (all ks-groups compute the same thing).  Ends behind a barrier that follows the writes to sm.p[0..13], so the caller may
+// fill other slots of sm.p before the call and read them after it.
 __device__ __forceinline__ VN embed_pre35(Smem &sm, const NodeArgs &A, const float *chi, int n0) {
     const int t = threadIdx.x, f = t & 127;
     if (t < 6) sm.p[t] = load_rows(A.bb_sincos, 6, n0, A.N, t);
@@ -290,6 +245,33 @@ __device__ __forceinline__ VN embed_pre35(Smem &sm, const NodeArgs &A, const flo
 #pragma unroll
     for (int k = 0; k < 14; k++) acc = vfma(A.embT[(21 + k) * 128 + f], sm.p[k], acc);
     return acc;
+}
+
+// The whole embedding (before LN) at the one time of a reverse step: embed_pre35 + the 16 time columns, summed on their own first
+__device__ __forceinline__ VN embed_pre(Smem &sm, const NodeArgs &A, const float *chi, const StepParams &sp, int n0) {
+    const int f = threadIdx.x & 127;
+    const VN acc = embed_pre35(sm, A, chi, n0);
+    const float *te = sp.temb;
+    float tacc = 0.f;
+#pragma unroll
+    for (int k = 0; k < 16; k++) tacc = fmaf(A.embT[(35 + k) * 128 + f], te[k], tacc);
+    return vadd(acc, vn(tacc));
+}
+
+__global__ void __launch_bounds__(NT)
+k_node_embed(NodeArgs A, PreW pre0, const float *chi, StepParams sp) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    Smem &sm = *reinterpret_cast<Smem *>(smem_raw);
+    int flip = 0, rflip = 0;
+    const int f = threadIdx.x & 127, ks = threadIdx.x >> 7, n0 = blockIdx.x * NB;
+    VN v = embed_pre(sm, A, chi, sp, n0);
+    VN h = layernorm(sm, rflip, v, A.emb_g[f], A.emb_beta[f]);
+    if (ks == 0) {
+        store_rows(A.hV, 128, n0, A.N, f, h);
+        sm.h[f] = h;
+    }
+    __syncthreads();
+    message_inputs(sm, flip, pre0, A.frames, n0, A.N, A.ptsN, A.PAn, A.PCn);
 }
 
 // Sibling of k_node_embed for a time PER ROW (pp_score_rows: the loss draws one t per complex).  The 16 sinusoidal features of
@@ -890,15 +872,6 @@ struct UpdW {
     PreW pre_edge, pre_next;
     const float *d0_inT, *d0_in_b, *d0_outT, *d0_out_b, *d2_inT, *d2_in_b, *d2_outT, *d2_out_b;
 };
-// small dense layer used by the decoder: width <= 128 outputs, K split over the four ks-groups
-template <int KIN>
-__device__ __forceinline__ VN dense_small(Smem &sm, int &flip, const float *WT, int width, const VN *act,
-                                          const float *bias) {
-    const int f = threadIdx.x & 127, ks = threadIdx.x >> 7;
-    VN p = f < width ? dense_slice<KIN>(WT, width, f, act, ks) : vn(0.f);
-    VN r = meet(sm, flip, p, 128, f, ks);
-    return f < width ? vadd(r, vn(bias[f])) : vn(0.f);
-}
 
 // ---- k_node_update: the same arithmetic as the helpers above, software-pipelined -------------------------------
 // Measured (tools/debug/time_vs_n.py): the kernel takes the same 24 us for 16 and for 256 blocks -- it is one block's
@@ -951,21 +924,16 @@ __device__ __forceinline__ void wdot4(const WSet &w0, const WSet &w1, const WSet
 }
 
 // message_inputs with the weights already in registers (wA, wC: this thread's K-quarter of column f; wP: of column f < 24).
-// refill_ptsT, if not null: the point weights of the NEXT call, fetched into wP as soon as it has been consumed.
-__device__ __forceinline__ void message_inputs_pre(Smem &sm, int &flip, const WSet &wA, const WSet &wC, WSet &wP,
-                                                   const float *refill_ptsT, float in_b, float pts_b, const float *frames,
-                                                   int n0, int N, float *pts, float *PA, float *PC) {
+__device__ __forceinline__ void message_inputs_pre(Smem &sm, int &flip, const WSet &wA, const WSet &wC, const WSet &wP,
+                                                   float in_b, float pts_b, const float *frames, int n0, int N, float *pts,
+                                                   float *PA, float *PC) {
     const int f = threadIdx.x & 127, ks = threadIdx.x >> 7;
     const VN *h = sm.h + ks * 32;
     VN *buf = sm.part[flip];
     flip ^= 1;
     buf[ks * 384 + f] = wdot<32>(wA, h, vn(0.f));
     buf[ks * 384 + 128 + f] = wdot<32>(wC, h, vn(0.f));
-    if (f < 24) {
-        const VN up = wdot<32>(wP, h, vn(0.f));
-        buf[ks * 384 + 256 + f] = up;
-        if (refill_ptsT) wload<32>(wP, refill_ptsT, 24, f, ks * 32, up.g[0].x);
-    }
+    if (f < 24) buf[ks * 384 + 256 + f] = wdot<32>(wP, h, vn(0.f));
     __syncthreads();
     if (ks == 0) {
         VN a = vadd(vadd(buf[f], buf[384 + f]), vadd(buf[768 + f], buf[1152 + f]));
@@ -1228,7 +1196,7 @@ k_node_update_valu(NodeArgs A, UpdW W, float *chi, int step, int sde, const floa
         }
         __syncthreads();
     }
-    message_inputs_pre(sm, flip, wa, wd, we, nullptr, in_b_1, pts_b_1, A.frames, n0, N, A.ptsN, A.PAn, A.PCn);
+    message_inputs_pre(sm, flip, wa, wd, we, in_b_1, pts_b_1, A.frames, n0, N, A.ptsN, A.PAn, A.PCn);
 }
 
 #endif      // !PP_EDGE_F16

@@ -410,6 +410,8 @@ class Context:
         return (per_res, dchi) if need_grad else per_res
 
     def proximal(self, chi, vtf, tol, lamda, num_steps, want_traj=True):
+        """proximal_optimizer for the one complex of a B = 1 batch: the single-complex case of the loop ``proximal_packed`` runs, without
+        the accept rule.  Returns (traj [num_steps, 1, L, 4] or None, last [1, L, 4], losses [num_steps]) on the device."""
         self.plan.set_clash_params(vtf, tol)
         chi = self._chi(chi)
         traj = self._new(num_steps, self.B, self.L, 4) if want_traj else None
@@ -421,7 +423,8 @@ class Context:
 
     def proximal_packed(self, chi, vtf, tol, lamda, num_steps, norm_rows=None, want_traj=False):
         """proximal_optimizer for every complex of a packed batch at once (a B = 1 batch counts as one complex): each complex with its
-        own clash mask, 1/n, losses and accept rule -- the bits ``proximal`` gives it alone.  ``norm_rows`` (one int per complex, or
+        own clash mask, 1/n, losses and accept rule.  The same loop as ``proximal``, which is its one-complex case: a complex gets the
+        bits it gets alone.  ``norm_rows`` (one int per complex, or
         None = the complexes' lengths): the row count each complex's means divide by; pass the padded ``max_size`` to reproduce the
         run on a padded batch.  Returns (traj [num_steps, 1, N, 4] or None, last [1, N, 4], accepted [1, N, 4],
         losses [n_complexes, num_steps]), all on the device; no host synchronisation."""

@@ -261,6 +261,35 @@ def test_proximal(tag):
     assert abs(float(m["atom_rmsd"]) - float(z["metric32.atom_rmsd"])) < 1e-3, (tag, float(m["atom_rmsd"]))
 
 
+@pytest.mark.parametrize("L", [17, 33, 70, 131])
+def test_proximal_small_complexes_match_the_oracle(L):
+    """The single-complex loop is the one-segment case of the packed one, so test_packed_proximal's solo runs share its kernels: this
+    is the independent check.  5 Adam steps against the CPU oracle in fp32 at the smallest sizes where the per-complex pieces can go
+    wrong: one loss group of 16 plus one row; under one 64-partner window; two waves' windows; a third window with a ragged last
+    group.  The oracle masks 4 / 12 / 24 / 47 residues here and moves 2 / 11 / 21 / 45; its own fp32 and fp64 runs differ by at most
+    1.1e-7 relative in loss and 8.1e-7 rad in angle, so the bounds (test_sampling_with_proximal's for 5-step losses, test_proximal's
+    for the first 10 steps' angles) are more than 20 times the reference's noise."""
+    from oracle import ref_cpu as O
+    from packppi_amd import synth
+    from packppi_amd.featurize import protein_to_batch
+    from packppi_amd.functional import _ctx_for
+    b = protein_to_batch(synth.make_complex(L, 1200 + L))
+    chi = ((torch.rand(1, L, 4, generator=torch.Generator().manual_seed(L)) * 2 - 1) * 3.0) * b.SC_D_mask
+    mask = O.clash_mask(b, chi, 12.0, 0.5)
+    assert int(mask[0, :, 0].sum()) > 0
+    ref_chis, ref_losses = O.proximal_optimizer(b, chi, 12.0, 0.5, 1.0, 5)
+    traj, last, losses = _ctx_for(_gpu(b)).proximal(chi.to(DEV), 12.0, 0.5, 1.0, 5)
+    traj, last, losses = traj.cpu(), last.cpu(), losses.cpu().numpy()
+    assert losses.shape == (5,) and traj.shape == (5, 1, L, 4)
+    print(f"L {L}: loss rel {np.abs(losses / np.array(ref_losses) - 1).max():.2e}, "
+          f"angle {max(float(wrapped_absdiff(traj[n], ref_chis[n]).max()) for n in range(5)):.2e} rad")
+    assert np.allclose(losses, np.array(ref_losses), rtol=2e-5, atol=1e-7), (L, losses, ref_losses)
+    for n in range(5):
+        assert wrapped_absdiff(traj[n], ref_chis[n]).max() < 2e-5, (L, n)
+        assert torch.equal(traj[n][~mask], chi[~mask]), (L, n)
+    assert torch.equal(last, traj[-1])
+
+
 def test_proximal_loss_reduction_at_odd_and_large_sizes():
     """The loss of a proximal step is reduced from per-residue terms in a fixed order (k_prox_losses: groups of 16 residues, 256 groups
     at a time).  First loss value of the loop against the same quantity assembled with torch from compute_residue_clash -- optimize.py:47-52
