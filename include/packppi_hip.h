@@ -191,6 +191,37 @@ pp_status pp_score_rows(pp_ctx *ctx, const float *chi, const float *t_rows, floa
 pp_status pp_sample(pp_ctx *ctx, float *chi, const float *schedule, int n_schedule, int mode,
                     const float *sde_noise, void *stream);
 
+/* ---- Seeded sampling noise, generated on the device (no reference counterpart) ---------------------
+ * The reference draws its noise from torch's global generator over the rows of the whole batch (add_sc_noise,
+ * TorsionalDiffusion.py:111-124; torch.normal in SO2VESchedule.step, schedule.py:225).  These calls draw it from a counter-based
+ * generator instead -- Philox4x32-10, key = the 64-bit seed, counter = (row WITHIN the complex, 4 * (step + 1) + chi index,
+ * complex key lo, hi), words (0, 1) -> the 1pi schedule's N(0,1) draw, (2, 3) -> the 2pi schedule's; step = -1 is the initial
+ * noising (csrc/pp_rng.h holds the layout and the normal transform).  The draw is a pure function of (seed, complex key, row in
+ * complex, chi, step, schedule): a complex gets the same noise alone, anywhere in a packed batch, on any rank.  This is NOT
+ * torch's stream: parity with the reference's SDE step stays with pp_sample and its explicit noise tensor.
+ *
+ * pp_ctx_set_rng_keys: the 64-bit keys of the ctx's segments (the complexes of a packed ctx, the B rows of a padded one);
+ * `keys` is a HOST array [n_seg], read before the call returns (the call may block on that copy; it runs once per ctx, not per
+ * sample); NULL restores the default, which also holds if this is never called: a segment's key is its ordinal 0, 1, 2 ... */
+pp_status pp_ctx_set_rng_keys(pp_ctx *ctx, const uint64_t *keys, void *stream);
+
+/* What the seeded sampler draws at `step` (-1: the initial noising; 0 .. n_steps - 1: the reverse steps): noise [2,B*L,4], the
+ * 1pi draw then the 2pi draw -- one step's slice of pp_sample's sde_noise -- and, if not NULL, words [B*L,4,4], the four raw
+ * Philox words of every (row, chi).  The per-step noise hook: a caller may stream explicit noise step by step from it. */
+pp_status pp_noise_seeded(pp_ctx *ctx, uint64_t seed, int step, float *noise, uint32_t *words, void *stream);
+
+/* Replaces add_sc_noise (TorsionalDiffusion.py:111-124) at a time t shared by all rows, with the step = -1 draws z1, z2:
+ * x = chi0 + (z1 sigma(t)) m1; x = x + (z2 sigma(t)) m2; chi = (x + pi) mod 2 pi - pi (torch.remainder semantics), every
+ * operation rounded in fp32 as the reference's tensor operations round; m1 / m2 are the batch's 1pi / 2pi periodic masks.  An
+ * entry outside both masks receives no noise and is copied through bit for bit.  chi0, chi [B,L,4], distinct buffers. */
+pp_status pp_add_noise_seeded(pp_ctx *ctx, const float *chi0, float t, uint64_t seed, float *chi, void *stream);
+
+/* pp_sample with the SDE draws made inside the reverse step, by the lane that steps (residue, chi): no noise tensor, no staging,
+ * and the call never waits for the stream.  Bit-equal to pp_sample on the stack of pp_noise_seeded(step = 0 .. n_schedule - 2).
+ * In PP_MODE_ODE nothing is drawn: the call is pp_sample. */
+pp_status pp_sample_seeded(pp_ctx *ctx, float *chi, const float *schedule, int n_schedule, int mode, uint64_t seed,
+                           void *stream);
+
 /* Replaces get_atom14_coords(X, S, BB_D, SC_D) (components/__init__.py:76-120). xyz [B,L,14,3]. */
 pp_status pp_atom14(pp_ctx *ctx, const float *chi, float *xyz, void *stream);
 

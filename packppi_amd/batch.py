@@ -129,7 +129,9 @@ def pack(complexes: Iterable[Batch], trim: bool = True) -> Batch:
 
     ``trim=False`` keeps every row, trailing padding included (PackPPI-AP: the max over residues of AffinityPrediction.py:186
     sees those rows).  Complexes that all carry the PackPPI-AP keys (``mut_mask``, the ``*_mut`` keys, ``ddg``) keep them:
-    the per-row keys are packed like the others, ``ddg`` becomes [n]."""
+    the per-row keys are packed like the others, ``ddg`` becomes [n].  Complexes that all carry a ``complex_key`` (an int: the
+    key of the seeded sampling noise, ``TDiffusionModule.sampling(seed=...)``) give the batch ``complex_keys``, a list in packing
+    order; batches without it pack as before."""
     complexes = list(complexes)
     keys = TENSOR_KEYS + tuple(k for k in MUT_KEYS if all(k in c for c in complexes))
     rows = {k: [] for k in keys}
@@ -157,6 +159,8 @@ def pack(complexes: Iterable[Batch], trim: bool = True) -> Batch:
         out[k] = torch.cat(rows[k], 0).unsqueeze(0)
     if all("ddg" in c for c in complexes):
         out["ddg"] = torch.cat([c["ddg"].reshape(-1) for c in complexes])
+    if complexes and all(c.get("complex_key") is not None for c in complexes):
+        out["complex_keys"] = [int(c["complex_key"]) for c in complexes]
     out["seg_offsets"] = torch.tensor(offs, dtype=torch.int32).to(out["X"].device, non_blocking=True)
     out["seg_offsets_host"] = offs
     return out

@@ -5,7 +5,8 @@ Same required flags as the reference's src/eval_diffusion.py:86-93 (--input, --o
 the encoder / model / sampling settings from there (eval_diffusion.py:22-41); here --config_dir (or $PACKPPI_CONFIG_DIR)
 names that configs/ directory and the four hot-path YAML files are read as plain YAML (packppi_amd/config.py): sample_cfg
 (mode, annealed_temp, proximal parameters) is applied, the dimensions are checked against what the kernels are compiled for.
---ckpt_path / $PACKPPI_CKPT override the tree's ckpt_path; --steps exposes the number of diffusion steps (reference: 30).
+--ckpt_path / $PACKPPI_CKPT override the tree's ckpt_path; --steps exposes the number of diffusion steps (reference: 30);
+--seed N makes the run reproducible: all sampling noise then comes from the seeded device generator.
 """
 import argparse
 import os
@@ -47,7 +48,9 @@ def evaluate_model(model, args):
     batch = analysis.get_prot(args.input).to(args.device)
     if args.seed is not None:
         torch.manual_seed(args.seed)
-    SC_D_sample = model.sampling(batch, use_proximal=args.use_proximal)
+    # --seed: the initial noise and the sde noise come from the counter-based device generator (module.sampling(seed=...)): the
+    # same seed gives the same structure on any device, shard layout and torch version
+    SC_D_sample = model.sampling(batch, use_proximal=args.use_proximal, seed=args.seed)
     if model.saturated() & 4:
         print("----- WARNING: NaN / infinity in the input coordinates or angles: the reference would return NaN here -----")
     if model.saturated() & 3:
@@ -77,7 +80,8 @@ def main(argv=None):
     p.add_argument("--config_dir", type=str, default=None, help="The reference's configs/ directory (else $PACKPPI_CONFIG_DIR): "
                    "encoder / model / sampling YAML files are read from it.")
     p.add_argument("--steps", type=int, default=None, help="Diffusion steps (reference schedule: 30).")
-    p.add_argument("--seed", type=int, default=None, help="Seed of the device generator for the initial noise.")
+    p.add_argument("--seed", type=int, default=None, help="Seed of the sampling noise (initial and sde), drawn by the "
+                   "counter-based generator on the device; default: unseeded draws from torch's generator.")
     p.add_argument("--random_weights", type=int, default=None, help="Seeded stand-in weights instead of a checkpoint.")
     args = p.parse_args(argv)
     evaluate_model(load_model(args), args)

@@ -417,6 +417,7 @@ static pp_status prepare_impl(pp_plan *plan, const pp_batch *b, const int32_t *s
     ALLOC(prox_part, (size_t)PP_PROX_CHUNK * N);
     if (prox) { ALLOC(prox_nrows, c->B); ALLOC(prox_seg, c->B); ALLOC(prox_inv, N); }
     if (packed) ALLOC(seg_off, (size_t)n_seg + 1);
+    ALLOC(rng_tab, N); ALLOC(rng_keys, c->B);
     c->max_steps = 1 << 20;
 #undef ALLOC
     c->last_stream = static_cast<hipStream_t>(stream);
@@ -543,8 +544,9 @@ bool pp_prof_take(pp_ctx *c, hipEvent_t *e0, hipEvent_t *e1) {
     return true;
 }
 
+// rng (seeded sde sampling, else null): the reverse step draws its own noise
 static pp_status run_network(pp_ctx *c, hipStream_t s, int step, int last_mode, float *chi, int mode, const float *noise,
-                             const StepParams *cur, const StepParams *next) {
+                             const StepParams *cur, const StepParams *next, const PPRng *rng = nullptr) {
     pp_status st;
     for (int l = 0; l < 3; l++) {
         if (l == 0 || !pp_edge_fused()) {   // fused build: layers 1 and 2 come from the tail of the previous edge update
@@ -564,7 +566,7 @@ static pp_status run_network(pp_ctx *c, hipStream_t s, int step, int last_mode, 
             if (st != PP_OK) return st;
         } else {
             prof_arm(c, 2);
-            st = pp_launch_node_update(c, l, last_mode, chi, step, mode, noise, cur, last_mode == PP_NU_STEP ? next : nullptr, s);
+            st = pp_launch_node_update(c, l, last_mode, chi, step, mode, noise, cur, last_mode == PP_NU_STEP ? next : nullptr, s, rng);
             prof_disarm(c);
             if (st != PP_OK) return st;
         }
@@ -629,16 +631,80 @@ extern "C" pp_status pp_affinity_encode(const pp_affinity *a, pp_ctx *c, const i
     return evaluate_and_copy(c, sp, nullptr, hV, s);
 }
 
+// ---- seeded sampling noise (pp_rng.h) -----------------------------------------------------------------------------------------
+// the per-row table with the default keys, if the context has none yet: one small launch, nothing waits
+static pp_status rng_table_ready(pp_ctx *c, hipStream_t s) {
+    return c->rng_tab_set ? PP_OK : pp_launch_rng_table(c, false, s);
+}
+
+extern "C" pp_status pp_ctx_set_rng_keys(pp_ctx *c, const uint64_t *keys, void *stream) {
+    if (c) c->last_stream = static_cast<hipStream_t>(stream);
+    if (!c) FAIL(PP_ERR_INVALID, "pp_ctx_set_rng_keys: null ctx");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    PP_HIP_CHECK(hipSetDevice(c->plan->device));
+    // the host table is caller-owned: from pageable memory, hipMemcpyAsync has taken the data when it returns (it may block)
+    if (keys) PP_HIP_CHECK(hipMemcpyAsync(c->rng_keys, keys, (size_t)c->B * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+    return pp_launch_rng_table(c, keys != nullptr, s);
+}
+
+extern "C" pp_status pp_noise_seeded(pp_ctx *c, uint64_t seed, int step, float *noise, uint32_t *words, void *stream) {
+    if (c) c->last_stream = static_cast<hipStream_t>(stream);
+    if (!c || !noise) FAIL(PP_ERR_INVALID, "pp_noise_seeded: null argument");
+    if (step < -1 || step >= c->max_steps) FAIL(PP_ERR_INVALID, "pp_noise_seeded: step must be -1 (initial noising) .. 2^20 - 1");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    PP_HIP_CHECK(hipSetDevice(c->plan->device));
+    pp_status st;
+    if ((st = rng_table_ready(c, s)) != PP_OK) return st;
+    return pp_launch_noise_seeded(c, seed, step, noise, words, s);
+}
+
+extern "C" pp_status pp_add_noise_seeded(pp_ctx *c, const float *chi0, float t, uint64_t seed, float *chi, void *stream) {
+    if (c) c->last_stream = static_cast<hipStream_t>(stream);
+    if (!c || !chi0 || !chi) FAIL(PP_ERR_INVALID, "pp_add_noise_seeded: null argument");
+    if (!c->b.chi_1pi_periodic_mask || !c->b.chi_2pi_periodic_mask) FAIL(PP_ERR_INVALID, "pp_add_noise_seeded: batch lacks the periodic masks");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    PP_HIP_CHECK(hipSetDevice(c->plan->device));
+    pp_status st;
+    if ((st = rng_table_ready(c, s)) != PP_OK) return st;
+    // sigma(t) in fp32 as fill_step computes it (TorsionalDiffusion.py:84-88)
+    const double PI_D = 3.14159265358979323846;
+    const double lo = log(0.01 * PI_D), hi = log(PI_D);
+    const float sigma = expf((float)lo + (float)(hi - lo) * t);
+    return pp_launch_add_noise_seeded(c, chi0, sigma, seed, chi, s);
+}
+
+// pp_sample and pp_sample_seeded (`who` names the export in messages; rng: the reverse steps draw their own sde noise)
+static pp_status sample_impl(const char *who, pp_ctx *c, float *chi, const float *schedule, int n_schedule, int mode,
+                             const float *sde_noise, const PPRng *rng, hipStream_t s);
+
 extern "C" pp_status pp_sample(pp_ctx *c, float *chi, const float *schedule, int n_schedule, int mode,
                                const float *sde_noise, void *stream) {
     if (c) c->last_stream = static_cast<hipStream_t>(stream);
-    if (!c || !chi || !schedule) FAIL(PP_ERR_INVALID, "pp_sample: null argument");
-    if (!c->plan->has_network) FAIL(PP_ERR_INVALID, "pp_sample: plan was created without network weights");
-    if (n_schedule < 2) FAIL(PP_ERR_INVALID, "pp_sample: schedule needs at least 2 times");
-    if (n_schedule - 1 > c->max_steps) FAIL(PP_ERR_UNSUPPORTED, "pp_sample: more than 2^20 steps");
-    if (mode != PP_MODE_ODE && mode != PP_MODE_SDE) FAIL(PP_ERR_INVALID, "pp_sample: unknown mode");
-    if (mode == PP_MODE_SDE && !sde_noise) FAIL(PP_ERR_INVALID, "pp_sample: sde mode needs the per-step noise tensor");
+    if (c && mode == PP_MODE_SDE && !sde_noise) FAIL(PP_ERR_INVALID, "pp_sample: sde mode needs the per-step noise tensor");
+    return sample_impl("pp_sample", c, chi, schedule, n_schedule, mode, sde_noise, nullptr, static_cast<hipStream_t>(stream));
+}
+
+extern "C" pp_status pp_sample_seeded(pp_ctx *c, float *chi, const float *schedule, int n_schedule, int mode, uint64_t seed,
+                                      void *stream) {
+    if (c) c->last_stream = static_cast<hipStream_t>(stream);
     hipStream_t s = static_cast<hipStream_t>(stream);
+    if (!c || mode != PP_MODE_SDE)       // ode draws nothing: pp_sample
+        return sample_impl("pp_sample_seeded", c, chi, schedule, n_schedule, mode, nullptr, nullptr, s);
+    PP_HIP_CHECK(hipSetDevice(c->plan->device));
+    pp_status st;
+    if ((st = rng_table_ready(c, s)) != PP_OK) return st;
+    const PPRng rng = {c->rng_tab, (uint32_t)seed, (uint32_t)(seed >> 32)};
+    return sample_impl("pp_sample_seeded", c, chi, schedule, n_schedule, mode, nullptr, &rng, s);
+}
+
+static pp_status sample_impl(const char *who, pp_ctx *c, float *chi, const float *schedule, int n_schedule, int mode,
+                             const float *sde_noise, const PPRng *rng, hipStream_t s) {
+    const std::string w(who);
+    if (!c || !chi || !schedule) FAIL(PP_ERR_INVALID, w + ": null argument");
+    if (!c->plan->has_network) FAIL(PP_ERR_INVALID, w + ": plan was created without network weights");
+    if (n_schedule < 2) FAIL(PP_ERR_INVALID, w + ": schedule needs at least 2 times");
+    if (n_schedule - 1 > c->max_steps) FAIL(PP_ERR_UNSUPPORTED, w + ": more than 2^20 steps");
+    if (mode != PP_MODE_ODE && mode != PP_MODE_SDE) FAIL(PP_ERR_INVALID, w + ": unknown mode");
     PP_HIP_CHECK(hipSetDevice(c->plan->device));
     const int nsteps = n_schedule - 1;
     // per-step scalars are kernel arguments: nothing is staged, nothing waits for the stream
@@ -652,7 +718,7 @@ extern "C" pp_status pp_sample(pp_ctx *c, float *chi, const float *schedule, int
     static const bool dbg = PP_GETENV("PP_DEBUG") != nullptr;
     const auto h0 = std::chrono::steady_clock::now();
     for (int j = 0; j < nsteps; j++) {
-        if ((st = run_network(c, s, j, PP_NU_STEP, chi, mode, sde_noise, &steps[j], j + 1 < nsteps ? &steps[j + 1] : nullptr)) != PP_OK) return st;
+        if ((st = run_network(c, s, j, PP_NU_STEP, chi, mode, sde_noise, &steps[j], j + 1 < nsteps ? &steps[j + 1] : nullptr, rng)) != PP_OK) return st;
     }
     if (dbg) {
         const double us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - h0).count();

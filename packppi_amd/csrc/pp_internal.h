@@ -47,6 +47,7 @@
 #define PP_CL_CAP 96       // static clash-partner candidates kept per (residue, wave) -- k_clash_cand / k_clash<true>
 
 #include "pp_weights.h"      // LayerOff / WeightOff / pp_weight_offsets(): offsets into the concatenated weight buffer
+#include "pp_rng.h"          // Philox4x32-10 and the normal transform of the seeded sampling noise (counter layout there)
 
 // Transposed ([in][out]) copies used by the node-level (VALU) kernels, per layer.
 struct LayerT {
@@ -173,6 +174,10 @@ struct pp_ctx {
     float2 *prox_seg;         // [B] per complex: (mean divisor, 1 / divisor), written by k_prox_init
     float *prox_inv;          // [N] 1 / divisor of the row's complex: the gradient and anchor weight of k_clash<CAND, true>
     float *scal;              // small scalar scratch
+    // seeded sampling noise (pp_rng.h): the per-row table of the seeded kernels and the complexes' keys
+    pp_rng_row *rng_tab;      // [N] (row within the complex, key of the complex); filled by pp_launch_rng_table
+    uint64_t *rng_keys;       // [B] the caller's keys (pp_ctx_set_rng_keys), staged for the table kernel
+    bool rng_tab_set = false; // the table holds the default keys (segment ordinals) or the caller's
     unsigned *sat;            // sticky word: bit 0 = an edge kernel, bit 1 = a node kernel clamped a hidden activation at 65504
     // in-situ kernel timing (pp_profile_kernel): every launch of one hot kernel carries a start / stop event pair
     // (hipExtLaunchKernelGGL: the dispatch's own begin / end timestamps, what rocprofv3's kernel trace reports)
@@ -295,7 +300,19 @@ struct pp_affinity {
     const float *d0T, *d0_b, *d2T, *d2_b, *d4_w, *d4_b;        // ddg_predictor.0 / .2 [128][128], .4 [128], [1]
 };
 
+// Seeded sampling noise as a kernel argument: the LAST parameter of k_node_update / k_node_update_valu, read by the seeded
+// instances only (tab == nullptr: the noise, if any, comes from the caller's tensor)
+struct PPRng {
+    const pp_rng_row *tab;
+    uint32_t seed_lo, seed_hi;
+};
+
 // ---- launchers implemented in the kernel translation units ----------------------------------
+// seeded noise (pp_node.hip): the per-row table from the context's segment table (keys_set: c->rng_keys holds the caller's keys,
+// else a complex's key is its ordinal), the draws of one step, the initial noising
+pp_status pp_launch_rng_table(pp_ctx *c, bool keys_set, hipStream_t s);
+pp_status pp_launch_noise_seeded(pp_ctx *c, uint64_t seed, int step, float *noise, uint32_t *words, hipStream_t s);
+pp_status pp_launch_add_noise_seeded(pp_ctx *c, const float *chi0, float sigma, uint64_t seed, float *chi, hipStream_t s);
 // k_affinity_embed (pp_node.hip): the mutation branch's node embedding + fusion -> ctx h_V and layer 0's node-message inputs
 pp_status pp_launch_affinity_embed(pp_ctx *c, const pp_affinity *a, const int64_t *rtype, const float *sc_sincos,
                                    const int64_t *mut_mask, const float *hV_pret, hipStream_t s);
@@ -303,8 +320,10 @@ pp_status pp_launch_prepare(pp_ctx *c, hipStream_t s, const int64_t *E_idx = nul
 pp_status pp_launch_node_embed(pp_ctx *c, const float *chi, const StepParams &sp, hipStream_t s);
 pp_status pp_launch_node_embed_rows(pp_ctx *c, const float *chi, const float *t_rows, hipStream_t s);   // a time per row (DEVICE [N])
 // cur: this step's scalars (layer 2 inside sampling); next: the next step, if its node embedding is to follow (else null)
+// rng (layer 2 inside seeded SDE sampling, else null): the reverse step draws its own noise, `noise` is not read
 pp_status pp_launch_node_update(pp_ctx *c, int layer, int last_mode, float *chi, int step, int mode,
-                                const float *noise, const StepParams *cur, const StepParams *next, hipStream_t s);
+                                const float *noise, const StepParams *cur, const StepParams *next, hipStream_t s,
+                                const PPRng *rng = nullptr);
 pp_status pp_launch_edge_static(pp_ctx *c, hipStream_t s);
 #ifdef PP_EDGE_F16
 pp_status pp_launch_edge_embed_f16(pp_ctx *c, hipStream_t s);   // pp_edge_f16.hip: MFMA form of k_edge_embed

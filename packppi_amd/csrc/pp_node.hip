@@ -555,10 +555,14 @@ __device__ __forceinline__ nf4 ln128(float (*st)[16][2], int wv, int r, int g, c
 // launch lasts as long as ONE CU needs for its workgroup's weight stream, and most CUs idle (47 tiles at T1124); so the tile's
 // common part (W_out, FFN, both LayerNorms: 36 slots) is computed redundantly by CL workgroups on CL CUs, and the 20 slots of
 // projections behind it are dealt out among them -- no exchange between workgroups, identical arithmetic per output.
-template <int MODE, int NU_ND, int CL = 1>
+// SEEDED (the reverse step of pp_sample_seeded in sde mode): the lane that steps (residue r, chi g) makes its own two normals from
+// the counter-based generator of pp_rng.h instead of reading them from `noise`.  A template parameter, and `rng` the LAST kernel
+// argument, so that the other instances keep their instructions.
+template <int MODE, int NU_ND, int CL = 1, bool SEEDED = false>
 __global__ void __launch_bounds__(512)
-k_node_update(NUpdArgs A, float *chi, int step, int sde, const float *noise, int embed_next, StepScalars sp, TimeEmb te_next) {
+k_node_update(NUpdArgs A, float *chi, int step, int sde, const float *noise, int embed_next, StepScalars sp, TimeEmb te_next, PPRng rng) {
     static_assert(CL == 1 || MODE == PP_NU_MID, "only the middle layers have a split form");
+    static_assert(!SEEDED || MODE == PP_NU_STEP, "only the reverse step draws noise");
     constexpr int NU_NRING = NU_ND + 1;
     constexpr bool LAST = MODE != PP_NU_MID;
     constexpr int NSLOT = LAST ? PP_NU_SLOTS_LAST : PP_NU_SLOTS_MID;
@@ -588,6 +592,7 @@ k_node_update(NUpdArgs A, float *chi, int step, int sde, const float *noise, int
     float chi1 = 0.f, scm1 = 0.f, nz1 = 0.f, nz2 = 0.f;       // wave 0: lane (r, g) steps chi g of residue r
     unsigned char m1raw = 0, m2raw = 0;
     int rt = 0;
+    pp_rng_row rrow = {0u, 0u, 0u, 0u};        // SEEDED: (row in complex, key of the complex) of residue r
     nf4 spv = zero4i;                          // c_ode, w, c_drift, c_diff of this step
     if constexpr (MODE == PP_NU_STEP) {
         spv = nf4{sp.c_ode, sp.w, sp.c_drift, sp.c_diff};
@@ -595,7 +600,9 @@ k_node_update(NUpdArgs A, float *chi, int step, int sde, const float *noise, int
         scm1 = A.sc_mask[(size_t)nc * 4 + g];
         m1raw = A.m1pi[(size_t)nc * 4 + g];
         m2raw = A.m2pi[(size_t)nc * 4 + g];
-        if (sde) {           // (the noise tensor only exists in sde mode)
+        if constexpr (SEEDED) {
+            rrow = rng.tab[nc];          // one 16-byte load, unconditional like the others; the draws follow the stream start
+        } else if (sde) {           // (the noise tensor only exists in sde mode)
             const size_t NN = (size_t)N * 4;
             const float *nz = noise + (size_t)step * 2 * NN + (size_t)nc * 4 + g;
             nz1 = nz[0];
@@ -633,6 +640,17 @@ k_node_update(NUpdArgs A, float *chi, int step, int sde, const float *noise, int
 #pragma unroll
     for (int k = 0; k < NU_ND; k++) gload_N(wq, k, AR[k]);
     __builtin_amdgcn_sched_barrier(0);       // the stream is on its way before anything waits for the inputs
+    if constexpr (SEEDED) {
+        // the two N(0,1) draws of (residue r, chi g) at this step: pure ALU on one loaded row, in wave 0 (the wave that steps), in
+        // the shadow of the first weight fetches.  A uniform branch without a load inside; the empty asm keeps the compiler from
+        // sinking the arithmetic into the kernel's tail, where it would sit on the critical path.
+        if (wv == 0) {
+            const pp_rng_words w = pp_rng_draw(rng.seed_lo, rng.seed_hi, rrow, g, step);
+            nz1 = pp_rng_normal(w.o[0], w.o[1]);
+            nz2 = pp_rng_normal(w.o[2], w.o[3]);
+        }
+        asm volatile("" : "+v"(nz1), "+v"(nz2));
+    }
 #pragma unroll
     for (int i = 0; i < NPV; i++) {
         const int q = tid + 512 * i;
@@ -963,10 +981,11 @@ __device__ __forceinline__ void message_inputs_pre(Smem &sm, int &flip, const WS
 
 // LAST_MODE is a template parameter so that the middle-layer variant (two of three launches) gets its own register
 // allocation: as one function the decoder / step / embedding tail cost it ~30 spilled registers.
-template <int LAST_MODE>
+template <int LAST_MODE, bool SEEDED = false>
 __global__ void __launch_bounds__(NT)
 k_node_update_valu(NodeArgs A, UpdW W, float *chi, int step, int sde, const float *noise, int embed_next, PreW pre0,
-                   StepScalars sp, TimeEmb te_next) {
+                   StepScalars sp, TimeEmb te_next, PPRng rng) {
+    static_assert(!SEEDED || LAST_MODE == PP_NU_STEP, "only the reverse step draws noise");
     constexpr int last_mode = LAST_MODE;
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     Smem &sm = *reinterpret_cast<Smem *>(smem_raw);
@@ -1152,10 +1171,21 @@ k_node_update_valu(NodeArgs A, UpdW W, float *chi, int step, int sde, const floa
             if (!sde) {
                 if (m1 || m2) y = x + sp.c_ode * sw;
             } else {
-                size_t NN = (size_t)N * 4;
-                const float *nz = noise + (size_t)step * 2 * NN;
-                if (m1) y = x + (sp.c_drift * sw + sp.c_diff * nz[(size_t)n * 4 + k]);
-                if (m2) y = y + (sp.c_drift * sw + sp.c_diff * nz[NN + (size_t)n * 4 + k]);
+                // the two N(0,1) draws: the caller's tensor, or (SEEDED) this thread's own from the generator of pp_rng.h; one
+                // expression for both, so that the seeded step is the explicit-noise step
+                float z1 = 0.f, z2 = 0.f;
+                if constexpr (SEEDED) {
+                    const pp_rng_words w = pp_rng_draw(rng.seed_lo, rng.seed_hi, rng.tab[n], k, step);
+                    z1 = pp_rng_normal(w.o[0], w.o[1]);
+                    z2 = pp_rng_normal(w.o[2], w.o[3]);
+                } else {
+                    size_t NN = (size_t)N * 4;
+                    const float *nz = noise + (size_t)step * 2 * NN;
+                    if (m1) z1 = nz[(size_t)n * 4 + k];
+                    if (m2) z2 = nz[NN + (size_t)n * 4 + k];
+                }
+                if (m1) y = x + (sp.c_drift * sw + sp.c_diff * z1);
+                if (m2) y = y + (sp.c_drift * sw + sp.c_diff * z2);
             }
             y = wrap_pi(y) * A.sc_mask[(size_t)n * 4 + k];
             chi[(size_t)n * 4 + k] = y;
@@ -1235,7 +1265,7 @@ static PreW make_pre(const pp_plan *p, int layer, bool edge) {
     return w;
 }
 
-typedef void (*nu_kernel_t)(NUpdArgs, float *, int, int, const float *, int, StepScalars, TimeEmb);
+typedef void (*nu_kernel_t)(NUpdArgs, float *, int, int, const float *, int, StepScalars, TimeEmb, PPRng);
 // mode 0 / 1 / 2 = PP_NU_MID / PP_NU_STEP / PP_NU_SCORE; multi: more tiles than CUs (shallower ring, two workgroups per CU)
 static nu_kernel_t nu_kernel(int mode, bool multi) {
     if (multi)
@@ -1243,6 +1273,10 @@ static nu_kernel_t nu_kernel(int mode, bool multi) {
                                                                                     : k_node_update<PP_NU_SCORE, PP_NU_DEPTH_MULTI>;
     return mode == 0 ? k_node_update<PP_NU_MID, PP_NU_DEPTH> : mode == 1 ? k_node_update<PP_NU_STEP, PP_NU_DEPTH>
                                                                           : k_node_update<PP_NU_SCORE, PP_NU_DEPTH>;
+}
+// the reverse step that draws its own noise: both launch depths
+static nu_kernel_t nu_kernel_seeded(bool multi) {
+    return multi ? k_node_update<PP_NU_STEP, PP_NU_DEPTH_MULTI, 1, true> : k_node_update<PP_NU_STEP, PP_NU_DEPTH, 1, true>;
 }
 static nu_kernel_t nu_kernel_split(int cl) {
     return cl == 4 ? k_node_update<PP_NU_MID, PP_NU_DEPTH, 4> : k_node_update<PP_NU_MID, PP_NU_DEPTH, 2>;
@@ -1262,10 +1296,14 @@ static pp_status node_attrs() {
         for (int cl = 2; cl <= 4; cl += 2)
             PP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(nu_kernel_split(cl)),
                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(SmemU)));
+        for (int multi = 0; multi < 2; multi++)
+            PP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(nu_kernel_seeded(multi != 0)),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(SmemU)));
 #ifndef PP_EDGE_F16
         PP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_node_update_valu<PP_NU_MID>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(Smem)));
         PP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_node_update_valu<PP_NU_STEP>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(Smem)));
         PP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_node_update_valu<PP_NU_SCORE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(Smem)));
+        PP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_node_update_valu<PP_NU_STEP, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(Smem)));
 #endif
         int dev = 0;
         hipDeviceProp_t prop;
@@ -1300,8 +1338,12 @@ pp_status pp_launch_node_embed_rows(pp_ctx *c, const float *chi, const float *t_
 }
 
 pp_status pp_launch_node_update(pp_ctx *c, int layer, int last_mode, float *chi, int step, int mode,
-                                const float *noise, const StepParams *cur, const StepParams *next, hipStream_t s) {
+                                const float *noise, const StepParams *cur, const StepParams *next, hipStream_t s,
+                                const PPRng *rng) {
     const bool embed_next_step = next != nullptr;
+    // the seeded instances exist for the reverse step in sde mode only (ode draws nothing)
+    const bool seeded = rng != nullptr && rng->tab != nullptr && last_mode == PP_NU_STEP && mode == PP_MODE_SDE;
+    const PPRng rg = seeded ? *rng : PPRng{nullptr, 0u, 0u};
     pp_status st0 = node_attrs();
     if (st0 != PP_OK) return st0;
     if ((last_mode == PP_NU_MID) != (layer < 2)) {
@@ -1354,12 +1396,15 @@ pp_status pp_launch_node_update(pp_ctx *c, int layer, int last_mode, float *chi,
             W.d2_outT = p->d2_out_T; W.d2_out_b = p->w + p->off.d2_out_b;
             const PreW pre0 = make_pre(p, 0, false);
             const dim3 vgrid((c->N + NB - 1) / NB), vblock(NT);
+            const auto kv_seeded = k_node_update_valu<PP_NU_STEP, true>;
             if (last_mode == PP_NU_MID)
-                PP_LAUNCH(c, k_node_update_valu<PP_NU_MID>, vgrid, vblock, sizeof(Smem), s, NA, W, chi, step, sde, noise, embed_next, pre0, sp, te);
+                PP_LAUNCH(c, k_node_update_valu<PP_NU_MID>, vgrid, vblock, sizeof(Smem), s, NA, W, chi, step, sde, noise, embed_next, pre0, sp, te, rg);
+            else if (seeded)
+                PP_LAUNCH(c, kv_seeded, vgrid, vblock, sizeof(Smem), s, NA, W, chi, step, sde, noise, embed_next, pre0, sp, te, rg);
             else if (last_mode == PP_NU_STEP)
-                PP_LAUNCH(c, k_node_update_valu<PP_NU_STEP>, vgrid, vblock, sizeof(Smem), s, NA, W, chi, step, sde, noise, embed_next, pre0, sp, te);
+                PP_LAUNCH(c, k_node_update_valu<PP_NU_STEP>, vgrid, vblock, sizeof(Smem), s, NA, W, chi, step, sde, noise, embed_next, pre0, sp, te, rg);
             else
-                PP_LAUNCH(c, k_node_update_valu<PP_NU_SCORE>, vgrid, vblock, sizeof(Smem), s, NA, W, chi, step, sde, noise, embed_next, pre0, sp, te);
+                PP_LAUNCH(c, k_node_update_valu<PP_NU_SCORE>, vgrid, vblock, sizeof(Smem), s, NA, W, chi, step, sde, noise, embed_next, pre0, sp, te, rg);
             PP_HIP_CHECK(hipGetLastError());
             return PP_OK;
         }
@@ -1376,12 +1421,101 @@ pp_status pp_launch_node_update(pp_ctx *c, int layer, int last_mode, float *chi,
         // workgroup that starts late (a shared GPU, a busy chip) still reads what it must; the context's pointers swap
         A.hV_out = c->hV_alt;
         std::swap(c->hV, c->hV_alt);
-        PP_LAUNCH(c, nu_kernel_split(cl), dim3(tiles * cl), block, sizeof(SmemU), s, A, chi, step, sde, noise, embed_next, sp, te);
+        PP_LAUNCH(c, nu_kernel_split(cl), dim3(tiles * cl), block, sizeof(SmemU), s, A, chi, step, sde, noise, embed_next, sp, te, rg);
         PP_HIP_CHECK(hipGetLastError());
         return PP_OK;
     }
-    const nu_kernel_t kern = nu_kernel(last_mode == PP_NU_MID ? 0 : last_mode == PP_NU_STEP ? 1 : 2, multi);
-    PP_LAUNCH(c, kern, grid, block, sizeof(SmemU), s, A, chi, step, sde, noise, embed_next, sp, te);
+    const nu_kernel_t kern = seeded ? nu_kernel_seeded(multi) : nu_kernel(last_mode == PP_NU_MID ? 0 : last_mode == PP_NU_STEP ? 1 : 2, multi);
+    PP_LAUNCH(c, kern, grid, block, sizeof(SmemU), s, A, chi, step, sde, noise, embed_next, sp, te, rg);
+    PP_HIP_CHECK(hipGetLastError());
+    return PP_OK;
+}
+
+// ==================================================================================================================
+// Seeded sampling noise outside the reverse step (pp_rng.h has the generator and the counter layout): the per-row table, the
+// export of one step's draws, the initial noising.  One thread per (row, chi); small VALU kernels that run once per context,
+// per inspection call, per sample.
+// ==================================================================================================================
+// tab[n] = (row of n within its complex, key of the complex): the complex is found as k_fill_seg / k_fill_seg_packed find it
+// (pp_api.hip), its key is keys[ordinal] or, without keys, the ordinal itself
+__global__ void k_rng_table(pp_rng_row *__restrict__ tab, int N, int L, const int32_t *__restrict__ seg_off, int n_seg,
+                            const uint64_t *__restrict__ keys) {
+    const int n = blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= N) return;
+    int ord, start;
+    if (seg_off) {
+        int lo = 0, hi = n_seg - 1;                   // last s with seg_off[s] <= n
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (seg_off[mid] <= n) lo = mid; else hi = mid - 1;
+        }
+        ord = lo;
+        start = seg_off[lo];
+        start = start < 0 ? 0 : (start > n ? n : start);      // (a table that disagrees with the batch: stay inside it)
+    } else {
+        ord = n / L;
+        start = ord * L;
+    }
+    const uint64_t key = keys ? keys[ord] : (uint64_t)ord;
+    pp_rng_row t;
+    t.row = (uint32_t)(n - start);
+    t.pad = 0u;
+    t.ckey_lo = (uint32_t)key;
+    t.ckey_hi = (uint32_t)(key >> 32);
+    tab[n] = t;
+}
+
+// noise [2][N][4] (1pi draw, 2pi draw: one step's slice of pp_sample's sde_noise) and, if not null, words [N][4][4]
+__global__ void k_noise_seeded(const pp_rng_row *__restrict__ tab, int N, uint32_t seed_lo, uint32_t seed_hi, int step,
+                               float *__restrict__ noise, uint32_t *__restrict__ words) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N * 4) return;
+    const pp_rng_words w = pp_rng_draw(seed_lo, seed_hi, tab[i >> 2], i & 3, step);
+    noise[i] = pp_rng_normal(w.o[0], w.o[1]);
+    noise[(size_t)N * 4 + i] = pp_rng_normal(w.o[2], w.o[3]);
+    if (words) *reinterpret_cast<uint4 *>(words + (size_t)i * 4) = make_uint4(w.o[0], w.o[1], w.o[2], w.o[3]);
+}
+
+// add_sc_noise at a shared time (TorsionalDiffusion.py:111-124) with the step = -1 draws: x += (z1 sigma) m1, x += (z2 sigma) m2,
+// wrap -- every product and sum rounded on its own, as the reference's tensor operations round.  An entry outside both periodic
+// masks receives no noise and is copied through untouched.
+__global__ void k_add_noise_seeded(const pp_rng_row *__restrict__ tab, int N, const float *__restrict__ chi0, float sigma,
+                                   const uint8_t *__restrict__ m1pi, const uint8_t *__restrict__ m2pi, uint32_t seed_lo,
+                                   uint32_t seed_hi, float *__restrict__ chi) {
+#pragma clang fp contract(off)
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N * 4) return;
+    const bool m1 = m1pi[i] != 0, m2 = m2pi[i] != 0;
+    float x = chi0[i];
+    if (m1 || m2) {
+        const pp_rng_words w = pp_rng_draw(seed_lo, seed_hi, tab[i >> 2], i & 3, -1);
+        const float n1 = pp_rng_normal(w.o[0], w.o[1]) * sigma;
+        x = x + n1 * (m1 ? 1.f : 0.f);
+        const float n2 = pp_rng_normal(w.o[2], w.o[3]) * sigma;
+        x = x + n2 * (m2 ? 1.f : 0.f);
+        x = wrap_pi(x);
+    }
+    chi[i] = x;
+}
+
+pp_status pp_launch_rng_table(pp_ctx *c, bool keys_set, hipStream_t s) {
+    hipLaunchKernelGGL(k_rng_table, dim3((c->N + 255) / 256), dim3(256), 0, s, c->rng_tab, c->N, c->L,
+                       c->packed ? c->seg_off : nullptr, c->B, keys_set ? c->rng_keys : nullptr);
+    PP_HIP_CHECK(hipGetLastError());
+    c->rng_tab_set = true;
+    return PP_OK;
+}
+
+pp_status pp_launch_noise_seeded(pp_ctx *c, uint64_t seed, int step, float *noise, uint32_t *words, hipStream_t s) {
+    hipLaunchKernelGGL(k_noise_seeded, dim3((c->N * 4 + 255) / 256), dim3(256), 0, s, c->rng_tab, c->N, (uint32_t)seed,
+                       (uint32_t)(seed >> 32), step, noise, words);
+    PP_HIP_CHECK(hipGetLastError());
+    return PP_OK;
+}
+
+pp_status pp_launch_add_noise_seeded(pp_ctx *c, const float *chi0, float sigma, uint64_t seed, float *chi, hipStream_t s) {
+    hipLaunchKernelGGL(k_add_noise_seeded, dim3((c->N * 4 + 255) / 256), dim3(256), 0, s, c->rng_tab, c->N, chi0, sigma,
+                       c->b.chi_1pi_periodic_mask, c->b.chi_2pi_periodic_mask, (uint32_t)seed, (uint32_t)(seed >> 32), chi);
     PP_HIP_CHECK(hipGetLastError());
     return PP_OK;
 }

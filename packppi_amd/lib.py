@@ -19,7 +19,8 @@ SYMBOLS = ("pp_version", "pp_last_error", "pp_build_id", "pp_plan_set_knn_ties",
            "pp_complex_prepare", "pp_complex_prepare_packed", "pp_ctx_destroy", "pp_ctx_get_graph", "pp_ctx_set_graph", "pp_score", "pp_sample", "pp_atom14",
            "pp_clash", "pp_proximal", "pp_proximal_packed", "pp_time_kernel", "pp_profile_kernel", "pp_profile_read", "pp_edge_variant", "pp_has_range_check", "pp_range_check", "pp_range_check_parts", "pp_ctx_saturated",
            "pp_affinity_create", "pp_affinity_destroy", "pp_affinity_encode", "pp_affinity_predict",
-           "pp_score_rows", "pp_so2_set_grids", "pp_so2_score", "pp_dsm_loss")
+           "pp_score_rows", "pp_so2_set_grids", "pp_so2_score", "pp_dsm_loss",
+           "pp_ctx_set_rng_keys", "pp_noise_seeded", "pp_add_noise_seeded", "pp_sample_seeded")
 
 
 KNN_TIES = {"lower_index": 0, "aten_cpu": 1, "aten_member": 2}
@@ -113,6 +114,10 @@ def load():
     lib.pp_so2_set_grids.argtypes = [vp, vp, i]
     lib.pp_so2_score.argtypes = [vp, vp, C.c_size_t, i, vp, vp, i, vp]
     lib.pp_dsm_loss.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.pp_ctx_set_rng_keys.argtypes = [vp, vp, vp]
+    lib.pp_noise_seeded.argtypes = [vp, C.c_uint64, i, vp, vp, vp]
+    lib.pp_add_noise_seeded.argtypes = [vp, vp, f, C.c_uint64, vp, vp]
+    lib.pp_sample_seeded.argtypes = [vp, vp, vp, i, i, C.c_uint64, vp]
     _lib = lib
     return lib
 
@@ -129,6 +134,11 @@ def _stream(device):
 
 def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+
+
+def _seed64(seed) -> int:
+    """A seed or complex key as the unsigned 64-bit number the generator takes (negative values wrap)."""
+    return int(seed) & 0xFFFFFFFFFFFFFFFF
 
 
 def ln_operand_scales(state_dict):
@@ -380,11 +390,51 @@ class Context:
                                   _stream(self.plan.device)), "pp_dsm_loss")
         return num, den
 
-    def sample(self, chi, schedule, mode="ode", sde_noise=None):
+    # ---- seeded sampling noise, generated on the device (csrc/pp_rng.h) ----------------------------
+    def set_rng_keys(self, keys=None):
+        """The 64-bit keys of this context's segments (complexes of a packed batch, else the B rows): a list or int64 tensor, one
+        entry per segment; None restores the default 0, 1, 2 ...  The noise of a complex depends on its key, never on where it
+        sits in the batch."""
+        arr = None
+        if keys is not None:
+            keys = keys.tolist() if isinstance(keys, torch.Tensor) else list(keys)
+            arr = np.ascontiguousarray([_seed64(k) for k in keys], dtype=np.uint64)
+            if arr.size != self.n_segments:
+                raise ValueError(f"{arr.size} complex keys for {self.n_segments} complexes")
+        _check(load().pp_ctx_set_rng_keys(self.handle, C.c_void_p(arr.ctypes.data) if arr is not None else C.c_void_p(0),
+                                          _stream(self.plan.device)), "pp_ctx_set_rng_keys")
+
+    def noise(self, seed, step, want_words=False):
+        """What the seeded sampler draws at ``step`` (-1: the initial noising): [2, N, 4] fp32, the 1pi draw then the 2pi draw --
+        one step's slice of ``sample``'s ``sde_noise``.  ``want_words``: also the raw Philox words, int32 [N, 4, 4] holding the
+        unsigned 32-bit patterns."""
+        nz = self._new(2, self.n_rows, 4)
+        words = self._new(self.n_rows, 4, 4, dtype=torch.int32) if want_words else None
+        _check(load().pp_noise_seeded(self.handle, _seed64(seed), int(step), _ptr(nz), _ptr(words), _stream(self.plan.device)),
+               "pp_noise_seeded")
+        return (nz, words) if want_words else nz
+
+    def add_noise(self, chi, t, seed):
+        """``add_sc_noise`` at one shared time ``t`` with the step = -1 draws of ``seed``: [B, L, 4]."""
+        chi = self._chi(chi)
+        out = torch.empty_like(chi)
+        _check(load().pp_add_noise_seeded(self.handle, _ptr(chi), float(t), _seed64(seed), _ptr(out), _stream(self.plan.device)),
+               "pp_add_noise_seeded")
+        return out
+
+    def sample(self, chi, schedule, mode="ode", sde_noise=None, seed=None):
+        """``seed``: the sde draws come from the device generator inside the reverse step (pp_sample_seeded; no noise tensor);
+        ``sde_noise`` must then be None.  Without a seed: pp_sample."""
         chi = self._chi(chi).clone()
         sched = np.ascontiguousarray(torch.as_tensor(schedule, dtype=torch.float32).cpu().numpy())
         if mode not in ("ode", "sde"):
             raise NotImplementedError(mode)
+        if seed is not None:
+            if sde_noise is not None:
+                raise ValueError("seed and sde_noise exclude each other: the seeded sampler draws its own noise")
+            _check(load().pp_sample_seeded(self.handle, _ptr(chi), sched.ctypes.data, int(len(sched)), 0 if mode == "ode" else 1,
+                                           _seed64(seed), _stream(self.plan.device)), "pp_sample_seeded")
+            return chi
         nz = None
         if mode == "sde":
             if sde_noise is None:

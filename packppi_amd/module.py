@@ -279,23 +279,36 @@ class TDiffusionModule:
     def reset_metrics(self):
         self._val_loss, self._test_loss = (0.0, 0), (0.0, 0)
 
-    def sampling(self, batch, use_proximal: bool = False, return_list: bool = False, sde_noise=None):
+    def sampling(self, batch, use_proximal: bool = False, return_list: bool = False, sde_noise=None, seed=None):
+        """``seed`` (an int, None = the reference's behaviour): the initial noising and the sde noise come from the counter-based
+        generator on the device (csrc/pp_rng.h) instead of torch's global one.  The noise of a complex is then a function of
+        (seed, its key, its rows, the step) alone: the same complex gets the same angles alone, anywhere in a packed batch and
+        on any rank.  Keys: ``batch.complex_keys`` (a list or int64 tensor, one per complex; ``batch.pack`` collects them from the
+        complexes' ``complex_key``), else 0, 1, 2 ... in batch order.  This is not torch's stream: a seeded run does not
+        reproduce a reference run under the same ``torch.manual_seed``."""
         cfg = self.hparams.sample_cfg
         packed = batch.get("seg_offsets") is not None if hasattr(batch, "get") else False
         if packed and use_proximal and return_list:
             raise ValueError("return_list=True needs a B = 1 batch; for a packed batch use "
                              "functional.proximal_optimizer_packed (per-complex losses [n_complexes, num_steps])")
-        t = torch.tensor([1.]).repeat_interleave(batch.max_size * batch.num_proteins).to(self.device)
-        SC_D_sample, _ = self.add_sc_noise(batch, t)
-        n_steps = len(self.schedule) - 1
-        if cfg.mode == "sde" and sde_noise is None:
-            # the reference draws torch.normal(size=[B*L, 4], device=...) inside the loop, once per schedule and step, the
-            # 1pi schedule first (schedule.py:225, TorsionalDiffusion.py:271-274): the same calls in the same order, so a
-            # seed gives the stream it gives the reference on this device (one [n, 2, N, 4] draw would not)
-            shape = (batch.num_proteins * batch.max_size, 4)
-            sde_noise = torch.stack([torch.stack([torch.normal(mean=0, std=1, size=shape, device=self.device)
-                                                  for _ in range(2)]) for _ in range(n_steps)])
-        SC_D_sample = self._context(batch).sample(SC_D_sample, self.schedule, cfg.mode, sde_noise)
+        if seed is not None and sde_noise is not None:
+            raise ValueError("seed and sde_noise exclude each other: the seeded sampler draws its own noise")
+        if seed is not None:
+            ctx = self._context(batch)
+            ctx.set_rng_keys(batch.get("complex_keys") if hasattr(batch, "get") else getattr(batch, "complex_keys", None))
+            SC_D_sample = ctx.sample(ctx.add_noise(batch.SC_D, 1.0, seed), self.schedule, cfg.mode, seed=seed)
+        else:
+            t = torch.tensor([1.]).repeat_interleave(batch.max_size * batch.num_proteins).to(self.device)
+            SC_D_sample, _ = self.add_sc_noise(batch, t)
+            n_steps = len(self.schedule) - 1
+            if cfg.mode == "sde" and sde_noise is None:
+                # the reference draws torch.normal(size=[B*L, 4], device=...) inside the loop, once per schedule and step, the
+                # 1pi schedule first (schedule.py:225, TorsionalDiffusion.py:271-274): the same calls in the same order, so a
+                # seed gives the stream it gives the reference on this device (one [n, 2, N, 4] draw would not)
+                shape = (batch.num_proteins * batch.max_size, 4)
+                sde_noise = torch.stack([torch.stack([torch.normal(mean=0, std=1, size=shape, device=self.device)
+                                                      for _ in range(2)]) for _ in range(n_steps)])
+            SC_D_sample = self._context(batch).sample(SC_D_sample, self.schedule, cfg.mode, sde_noise)
         if not use_proximal:
             return SC_D_sample
         if packed:            # every complex optimised on its own terms, accept rule per complex on the device

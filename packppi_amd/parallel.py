@@ -95,8 +95,15 @@ def gather_metric_rows(ids: torch.Tensor, rows: torch.Tensor, group=None) -> Tup
     return all_ids[order], all_rows[order]
 
 
+def _with_key(batch, key):
+    """A shallow copy of a B = 1 batch that carries ``complex_keys = [key]`` (the caller's batch is not touched)."""
+    out = type(batch)(batch)
+    out["complex_keys"] = [int(key)]
+    return out
+
+
 def sample_sharded(model, complexes, use_proximal=False, group=None, init_chi=None, max_rows=200_000, lengths=None,
-                   rank=None, world=None, packed_proximal=True):
+                   rank=None, world=None, packed_proximal=True, seed=None):
     """Run the sampling path on this rank's share of ``complexes`` (list of B = 1 batches already on the rank's device)
     and gather every complex's metric row on every rank.  With ``lengths`` (the residue counts of ALL complexes, known to
     every rank) ``complexes`` may be a dict {complex id: batch} that holds only this rank's share -- a rank need not build
@@ -110,9 +117,14 @@ def sample_sharded(model, complexes, use_proximal=False, group=None, init_chi=No
     ``max_size``, as the per-complex call divides --, losses and accept rule: the same bits); ``packed_proximal=False`` keeps
     one ``proximal_optimizer`` call per complex.  The metrics of the proximal branch run per complex.
     ``init_chi`` (optional, {complex id: [1, L, 4]}) injects the initial noised angles instead of drawing them.
+    ``seed`` (optional): all noise comes from the device generator (``TDiffusionModule.sampling(seed=...)``) and the key of every
+    complex is its global id, in packed groups and single-complex groups alike: a complex's sample does not depend on
+    ``world``, ``rank``, ``max_rows`` or what it was grouped with.  ``seed`` and ``init_chi`` exclude each other.
     Returns (chi per local complex id, ids_all, rows_all)."""
     from .batch import pack, unpack
     from .functional import proximal_optimizer, proximal_optimizer_packed
+    if seed is not None and init_chi is not None:
+        raise ValueError("seed and init_chi exclude each other: a seeded run draws its own initial angles")
     if rank is None:
         rank = dist.get_rank(group) if dist.is_initialized() else 0
     if world is None:
@@ -143,6 +155,8 @@ def sample_sharded(model, complexes, use_proximal=False, group=None, init_chi=No
             i = grp[0]
             if init_chi is not None:
                 chis[i] = model.sample_from(complexes[i], init_chi[i].to(model.device))
+            elif seed is not None:
+                chis[i] = model.sampling(_with_key(complexes[i], i), seed=seed)
             else:
                 chis[i] = model.sampling(complexes[i])
             continue
@@ -151,6 +165,9 @@ def sample_sharded(model, complexes, use_proximal=False, group=None, init_chi=No
             offs = pb["seg_offsets_host"]
             x0 = torch.cat([init_chi[i][:, :b - a] for i, a, b in zip(grp, offs[:-1], offs[1:])], 1).to(model.device)
             out = model.sample_from(pb, x0)
+        elif seed is not None:
+            pb["complex_keys"] = [int(i) for i in grp]
+            out = model.sampling(pb, seed=seed)
         else:
             out = model.sampling(pb)
         if not use_proximal:          # the metrics of the whole group in one go (the proximal stage changes the angles first)
