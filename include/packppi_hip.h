@@ -222,6 +222,32 @@ pp_status pp_add_noise_seeded(pp_ctx *ctx, const float *chi0, float t, uint64_t 
 pp_status pp_sample_seeded(pp_ctx *ctx, float *chi, const float *schedule, int n_schedule, int mode, uint64_t seed,
                            void *stream);
 
+/* ---- Partial repacking (no reference counterpart) ---------------------------------------------------
+ * pp_sample_seeded with some rows held at given angles: fixed is a DEVICE array [B*L] (packed ctx: [N]) of bytes, 1 = the row keeps
+ * chi_ref, 0 = the row is sampled; chi_ref is DEVICE [B*L,4], distinct from chi.  The pin sits inside the reverse step, in the
+ * lane that steps (residue, chi), so the network of the next step sees the pinned value.  After step j (0-based) of the
+ * n = n_schedule - 1 steps:
+ *   free row                   today's step: the ODE formula or the SDE formula with the in-kernel draws, wrap, * SC_D_mask --
+ *                              with fixed all 0 the call gives the bits of pp_sample_seeded in either mode;
+ *   fixed row, PP_FIX_HOLD     chi_ref, bit for bit, at every step: the free rows are conditioned on the clean neighbours;
+ *   fixed row, PP_FIX_RENOISE  j < n - 1: pp_add_noise_seeded's arithmetic on chi_ref with the step-j draws (z1, z2) of that
+ *                              (row, chi) -- which a row that does not step leaves unused -- at sigma(schedule[j + 1]), the level
+ *                              the free rows arrive at: x = chi_ref + (z1 sigma) m1; x = x + (z2 sigma) m2; wrap, every operation
+ *                              rounded on its own; an entry outside both periodic masks is chi_ref bit for bit.  j = n - 1:
+ *                              chi_ref bit for bit whatever the schedule ends at (sigma(0) = 0.01 pi is not 0).  This is
+ *                              replacement conditioning: the network sees the known part at the noise level of its input.
+ * INITIAL STATE: the call does not initialise fixed rows.  chi holds the step-0 state of EVERY row on entry -- for PP_FIX_RENOISE
+ * pp_add_noise_seeded(where(fixed, chi_ref, .), t = schedule[0]) gives it, for PP_FIX_HOLD the fixed rows then set to chi_ref --
+ * and the sample on exit, fixed rows = chi_ref.  The seed and the ctx's rng keys are used exactly as in pp_sample_seeded, in
+ * PP_MODE_ODE too (the free rows draw nothing there; the re-noising does).  chi_traj, if not NULL, receives the angles after every
+ * step [n_schedule-1, B*L, 4], written by the stepping lanes.  Never waits for the stream.  PP_ERR_INVALID: a null argument,
+ * chi_ref == chi, an unknown fix_mode or mode, a batch without the periodic masks. */
+#define PP_FIX_HOLD 0
+#define PP_FIX_RENOISE 1
+pp_status pp_sample_partial(pp_ctx *ctx, float *chi, const float *chi_ref, const uint8_t *fixed, int fix_mode,
+                            const float *schedule, int n_schedule, int mode, uint64_t seed,
+                            float *chi_traj /* [n_schedule-1, B*L, 4] or NULL */, void *stream);
+
 /* Replaces get_atom14_coords(X, S, BB_D, SC_D) (components/__init__.py:76-120). xyz [B,L,14,3]. */
 pp_status pp_atom14(pp_ctx *ctx, const float *chi, float *xyz, void *stream);
 

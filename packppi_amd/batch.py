@@ -30,6 +30,11 @@ AFFINITY_KEYS = (
 )
 
 
+# optional per-residue keys that pack() carries when every complex has them: the rows partial repacking keeps
+# (``TDiffusionModule.sampling(fixed_mask=...)``; [L] or [1, L], 1 = keep)
+ROW_KEYS = ("fixed_mask",)
+
+
 class Batch(dict):
     """Attribute-style dict: ``batch.X``, ``batch['X']``, ``batch.to('cuda')``, ``batch.keys()``."""
 
@@ -131,9 +136,10 @@ def pack(complexes: Iterable[Batch], trim: bool = True) -> Batch:
     sees those rows).  Complexes that all carry the PackPPI-AP keys (``mut_mask``, the ``*_mut`` keys, ``ddg``) keep them:
     the per-row keys are packed like the others, ``ddg`` becomes [n].  Complexes that all carry a ``complex_key`` (an int: the
     key of the seeded sampling noise, ``TDiffusionModule.sampling(seed=...)``) give the batch ``complex_keys``, a list in packing
-    order; batches without it pack as before."""
+    order; batches without it pack as before.  Complexes that all carry a ``fixed_mask`` ([L] or [1, L]: the rows partial
+    repacking keeps) give the batch its ``fixed_mask`` [1, N]; ``unpack`` splits it like any per-row result."""
     complexes = list(complexes)
-    keys = TENSOR_KEYS + tuple(k for k in MUT_KEYS if all(k in c for c in complexes))
+    keys = TENSOR_KEYS + tuple(k for k in MUT_KEYS + ROW_KEYS if all(k in c for c in complexes))
     rows = {k: [] for k in keys}
     offs = [0]
     ends = []

@@ -7,6 +7,9 @@ names that configs/ directory and the four hot-path YAML files are read as plain
 (mode, annealed_temp, proximal parameters) is applied, the dimensions are checked against what the kernels are compiled for.
 --ckpt_path / $PACKPPI_CKPT override the tree's ckpt_path; --steps exposes the number of diffusion steps (reference: 30);
 --seed N makes the run reproducible: all sampling noise then comes from the seeded device generator.
+--repack SPEC|interface repacks only the named residues ("A:45-60,B:12,C": chain and PDB residue number; "interface": residues
+within 10 A of another chain) and keeps every other residue at the input's angles; --fixed_mode chooses
+what the sampled residues are conditioned on.  It needs --seed and excludes --use_proximal.
 """
 import argparse
 import os
@@ -50,7 +53,13 @@ def evaluate_model(model, args):
         torch.manual_seed(args.seed)
     # --seed: the initial noise and the sde noise come from the counter-based device generator (module.sampling(seed=...)): the
     # same seed gives the same structure on any device, shard layout and torch version
-    SC_D_sample = model.sampling(batch, use_proximal=args.use_proximal, seed=args.seed)
+    fixed = None
+    if args.repack is not None:
+        from ..selection import interface_selection, parse_selection
+        sel = interface_selection(protein, args.input) if args.repack == "interface" else parse_selection(args.repack, protein)
+        print(f"----- Repacking {int(sel.sum())} of {len(sel)} residues ({args.fixed_mode}); the others keep the input's angles -----")
+        fixed = torch.from_numpy(~sel).unsqueeze(0)
+    SC_D_sample = model.sampling(batch, use_proximal=args.use_proximal, seed=args.seed, fixed_mask=fixed, fixed_mode=args.fixed_mode)
     if model.saturated() & 4:
         print("----- WARNING: NaN / infinity in the input coordinates or angles: the reference would return NaN here -----")
     if model.saturated() & 3:
@@ -83,7 +92,15 @@ def main(argv=None):
     p.add_argument("--seed", type=int, default=None, help="Seed of the sampling noise (initial and sde), drawn by the "
                    "counter-based generator on the device; default: unseeded draws from torch's generator.")
     p.add_argument("--random_weights", type=int, default=None, help="Seeded stand-in weights instead of a checkpoint.")
+    p.add_argument("--repack", type=str, default=None, metavar="SPEC|interface", help="Repack only these residues, e.g. "
+                   "'A:45-60,B:12,C' (chain and PDB residue number) or 'interface'; the others keep the input's angles. Needs --seed.")
+    p.add_argument("--fixed_mode", choices=("hold", "renoise"), default="renoise", help="With --repack: what the kept residues look "
+                   "like to the network during sampling: re-noised to each step's level (renoise) or clean throughout (hold).")
     args = p.parse_args(argv)
+    if args.repack is not None and args.seed is None:
+        p.error("--repack needs --seed (the kept residues are re-noised with the seeded generator's draws)")
+    if args.repack is not None and args.use_proximal:
+        p.error("--repack excludes --use_proximal: the proximal stage has no pin and would move the kept residues")
     evaluate_model(load_model(args), args)
 
 

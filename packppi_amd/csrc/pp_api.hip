@@ -506,6 +506,13 @@ extern "C" pp_status pp_ctx_set_graph(pp_ctx *c, const int64_t *E_idx, void *str
 
 // ---------------------------------------------------------------------------------------------
 // per-step scalars (schedule.py:165-174,198-235; layers.py:257-268), fp32 like the reference's tensors
+// sigma(t) in fp32 (TorsionalDiffusion.py:84-88): fill_step, the initial noising and the re-noising of pp_sample_partial share it
+static float sigma_f32(float t) {
+    const double PI_D = 3.14159265358979323846;
+    const double lo = log(0.01 * PI_D), hi = log(PI_D);
+    return expf((float)lo + (float)(hi - lo) * t);
+}
+
 static void fill_step(StepParams *sp, float t, float dt, float T) {
     const double PI_D = 3.14159265358979323846;
     const double lo = log(0.01 * PI_D), hi = log(PI_D);
@@ -519,7 +526,7 @@ static void fill_step(StepParams *sp, float t, float dt, float T) {
         sp->temb[i] = (float)sin((double)arg);
         sp->temb[8 + i] = (float)cos((double)arg);
     }
-    float sigma = expf((float)lo + (float)(hi - lo) * t);
+    float sigma = sigma_f32(t);
     float g = sigma * (float)sqrt(2.0 * log(PI_D / (0.01 * PI_D)));
     float ratio = sigma / (float)exp(hi);
     float alpha = 1.0f - ratio * ratio;
@@ -545,8 +552,9 @@ bool pp_prof_take(pp_ctx *c, hipEvent_t *e0, hipEvent_t *e1) {
 }
 
 // rng (seeded sde sampling, else null): the reverse step draws its own noise
+// pin (pp_sample_partial, else null): this step's pinned reverse step
 static pp_status run_network(pp_ctx *c, hipStream_t s, int step, int last_mode, float *chi, int mode, const float *noise,
-                             const StepParams *cur, const StepParams *next, const PPRng *rng = nullptr) {
+                             const StepParams *cur, const StepParams *next, const PPRng *rng = nullptr, const PPPin *pin = nullptr) {
     pp_status st;
     for (int l = 0; l < 3; l++) {
         if (l == 0 || !pp_edge_fused()) {   // fused build: layers 1 and 2 come from the tail of the previous edge update
@@ -566,7 +574,7 @@ static pp_status run_network(pp_ctx *c, hipStream_t s, int step, int last_mode, 
             if (st != PP_OK) return st;
         } else {
             prof_arm(c, 2);
-            st = pp_launch_node_update(c, l, last_mode, chi, step, mode, noise, cur, last_mode == PP_NU_STEP ? next : nullptr, s, rng);
+            st = pp_launch_node_update(c, l, last_mode, chi, step, mode, noise, cur, last_mode == PP_NU_STEP ? next : nullptr, s, rng, pin);
             prof_disarm(c);
             if (st != PP_OK) return st;
         }
@@ -666,16 +674,21 @@ extern "C" pp_status pp_add_noise_seeded(pp_ctx *c, const float *chi0, float t, 
     PP_HIP_CHECK(hipSetDevice(c->plan->device));
     pp_status st;
     if ((st = rng_table_ready(c, s)) != PP_OK) return st;
-    // sigma(t) in fp32 as fill_step computes it (TorsionalDiffusion.py:84-88)
-    const double PI_D = 3.14159265358979323846;
-    const double lo = log(0.01 * PI_D), hi = log(PI_D);
-    const float sigma = expf((float)lo + (float)(hi - lo) * t);
-    return pp_launch_add_noise_seeded(c, chi0, sigma, seed, chi, s);
+    return pp_launch_add_noise_seeded(c, chi0, sigma_f32(t), seed, chi, s);
 }
 
-// pp_sample and pp_sample_seeded (`who` names the export in messages; rng: the reverse steps draw their own sde noise)
+// what pp_sample_partial adds to a sampling run
+struct PartialArgs {
+    const float *chi_ref;      // [N][4]
+    const uint8_t *fixed;      // [N]
+    int fix_mode;              // PP_FIX_HOLD / PP_FIX_RENOISE
+    float *chi_traj;           // [n_schedule - 1][N][4] or null
+};
+
+// pp_sample, pp_sample_seeded and pp_sample_partial (`who` names the export in messages; rng: the reverse steps draw their own sde
+// noise; part: fixed rows are pinned inside the reverse step)
 static pp_status sample_impl(const char *who, pp_ctx *c, float *chi, const float *schedule, int n_schedule, int mode,
-                             const float *sde_noise, const PPRng *rng, hipStream_t s);
+                             const float *sde_noise, const PPRng *rng, hipStream_t s, const PartialArgs *part = nullptr);
 
 extern "C" pp_status pp_sample(pp_ctx *c, float *chi, const float *schedule, int n_schedule, int mode,
                                const float *sde_noise, void *stream) {
@@ -697,8 +710,26 @@ extern "C" pp_status pp_sample_seeded(pp_ctx *c, float *chi, const float *schedu
     return sample_impl("pp_sample_seeded", c, chi, schedule, n_schedule, mode, nullptr, &rng, s);
 }
 
+extern "C" pp_status pp_sample_partial(pp_ctx *c, float *chi, const float *chi_ref, const uint8_t *fixed, int fix_mode,
+                                       const float *schedule, int n_schedule, int mode, uint64_t seed, float *chi_traj,
+                                       void *stream) {
+    if (c) c->last_stream = static_cast<hipStream_t>(stream);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (!c || !chi || !chi_ref || !fixed || !schedule) FAIL(PP_ERR_INVALID, "pp_sample_partial: null argument");
+    if (chi_ref == chi) FAIL(PP_ERR_INVALID, "pp_sample_partial: chi_ref and chi must be distinct buffers");
+    if (fix_mode != PP_FIX_HOLD && fix_mode != PP_FIX_RENOISE) FAIL(PP_ERR_INVALID, "pp_sample_partial: unknown fix_mode");
+    if (mode != PP_MODE_ODE && mode != PP_MODE_SDE) FAIL(PP_ERR_INVALID, "pp_sample_partial: unknown mode");
+    if (!c->b.chi_1pi_periodic_mask || !c->b.chi_2pi_periodic_mask) FAIL(PP_ERR_INVALID, "pp_sample_partial: batch lacks the periodic masks");
+    PP_HIP_CHECK(hipSetDevice(c->plan->device));
+    pp_status st;
+    if ((st = rng_table_ready(c, s)) != PP_OK) return st;
+    const PPRng rng = {c->rng_tab, (uint32_t)seed, (uint32_t)(seed >> 32)};
+    const PartialArgs part = {chi_ref, fixed, fix_mode, chi_traj};
+    return sample_impl("pp_sample_partial", c, chi, schedule, n_schedule, mode, nullptr, &rng, s, &part);
+}
+
 static pp_status sample_impl(const char *who, pp_ctx *c, float *chi, const float *schedule, int n_schedule, int mode,
-                             const float *sde_noise, const PPRng *rng, hipStream_t s) {
+                             const float *sde_noise, const PPRng *rng, hipStream_t s, const PartialArgs *part) {
     const std::string w(who);
     if (!c || !chi || !schedule) FAIL(PP_ERR_INVALID, w + ": null argument");
     if (!c->plan->has_network) FAIL(PP_ERR_INVALID, w + ": plan was created without network weights");
@@ -718,7 +749,18 @@ static pp_status sample_impl(const char *who, pp_ctx *c, float *chi, const float
     static const bool dbg = PP_GETENV("PP_DEBUG") != nullptr;
     const auto h0 = std::chrono::steady_clock::now();
     for (int j = 0; j < nsteps; j++) {
-        if ((st = run_network(c, s, j, PP_NU_STEP, chi, mode, sde_noise, &steps[j], j + 1 < nsteps ? &steps[j + 1] : nullptr, rng)) != PP_OK) return st;
+        PPPin pin = {nullptr, nullptr, nullptr, 0.f, 0};
+        if (part) {
+            // a fixed row arrives at the noise level of schedule[j + 1] like the free rows; after the last step it holds chi_ref itself
+            // (sigma(0) = 0.01 pi is not 0)
+            pin.fixed = part->fixed;
+            pin.chi_ref = part->chi_ref;
+            pin.traj = part->chi_traj ? part->chi_traj + (size_t)j * c->N * 4 : nullptr;
+            pin.sigma = sigma_f32(schedule[j + 1]);
+            pin.renoise = part->fix_mode == PP_FIX_RENOISE && j + 1 < nsteps ? 1 : 0;
+        }
+        if ((st = run_network(c, s, j, PP_NU_STEP, chi, mode, sde_noise, &steps[j], j + 1 < nsteps ? &steps[j + 1] : nullptr, rng,
+                              part ? &pin : nullptr)) != PP_OK) return st;
     }
     if (dbg) {
         const double us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - h0).count();

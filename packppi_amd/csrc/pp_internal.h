@@ -307,6 +307,16 @@ struct PPRng {
     uint32_t seed_lo, seed_hi;
 };
 
+// Partial repacking (pp_sample_partial) as a kernel argument: the LAST parameter of k_node_update / k_node_update_valu, behind
+// PPRng, read by the PINNED instances only.  One per reverse step: the host sets sigma, renoise and traj for step j.
+struct PPPin {
+    const uint8_t *fixed;     // [N] 1 = the row keeps chi_ref, 0 = the row steps
+    const float *chi_ref;     // [N][4]
+    float *traj;              // this step's [N][4] slice of chi_traj, or null
+    float sigma;              // sigma(schedule[j + 1]) in fp32 as fill_step computes it: the noise level the step arrives at
+    int renoise;              // 1: a fixed row gets chi_ref re-noised to sigma with this step's draws; 0: chi_ref itself
+};                            //    (PP_FIX_HOLD, and the last step of PP_FIX_RENOISE)
+
 // ---- launchers implemented in the kernel translation units ----------------------------------
 // seeded noise (pp_node.hip): the per-row table from the context's segment table (keys_set: c->rng_keys holds the caller's keys,
 // else a complex's key is its ordinal), the draws of one step, the initial noising
@@ -321,9 +331,10 @@ pp_status pp_launch_node_embed(pp_ctx *c, const float *chi, const StepParams &sp
 pp_status pp_launch_node_embed_rows(pp_ctx *c, const float *chi, const float *t_rows, hipStream_t s);   // a time per row (DEVICE [N])
 // cur: this step's scalars (layer 2 inside sampling); next: the next step, if its node embedding is to follow (else null)
 // rng (layer 2 inside seeded SDE sampling, else null): the reverse step draws its own noise, `noise` is not read
+// pin (layer 2 inside pp_sample_partial, else null; needs rng in either mode): the PINNED reverse step
 pp_status pp_launch_node_update(pp_ctx *c, int layer, int last_mode, float *chi, int step, int mode,
                                 const float *noise, const StepParams *cur, const StepParams *next, hipStream_t s,
-                                const PPRng *rng = nullptr);
+                                const PPRng *rng = nullptr, const PPPin *pin = nullptr);
 pp_status pp_launch_edge_static(pp_ctx *c, hipStream_t s);
 #ifdef PP_EDGE_F16
 pp_status pp_launch_edge_embed_f16(pp_ctx *c, hipStream_t s);   // pp_edge_f16.hip: MFMA form of k_edge_embed

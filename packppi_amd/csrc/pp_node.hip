@@ -318,14 +318,8 @@ k_node_embed_rows(NodeArgs A, PreW pre0, const float *chi, const float *__restri
     message_inputs(sm, flip, pre0, A.frames, n0, A.N, A.ptsN, A.PAn, A.PCn);
 }
 
-// (x + pi) % (2 pi) - pi with torch.remainder semantics in fp32
-__device__ __forceinline__ float wrap_pi(float x) {
-    const float PIf = 3.14159274101257324f, TWO_PIf = 6.28318548202514648f;
-    float y = x + PIf;
-    float r = fmodf(y, TWO_PIf);
-    if (r != 0.f && r < 0.f) r += TWO_PIf;
-    return r - PIf;
-}
+// (x + pi) % (2 pi) - pi with torch.remainder semantics in fp32 (pp_rng.h: shared with pp_noised_angle)
+__device__ __forceinline__ float wrap_pi(float x) { return pp_wrap_pi(x); }
 
 // ==================================================================================================================
 // k_node_update on the matrix pipe (split-f16 MFMA, fp32-level accuracy)
@@ -558,11 +552,17 @@ __device__ __forceinline__ nf4 ln128(float (*st)[16][2], int wv, int r, int g, c
 // SEEDED (the reverse step of pp_sample_seeded in sde mode): the lane that steps (residue r, chi g) makes its own two normals from
 // the counter-based generator of pp_rng.h instead of reading them from `noise`.  A template parameter, and `rng` the LAST kernel
 // argument, so that the other instances keep their instructions.
-template <int MODE, int NU_ND, int CL = 1, bool SEEDED = false>
+// PINNED (pp_sample_partial; a seeded instance in either mode, `pin` behind `rng` for the same reason): a row with fixed[n] != 0 does
+// not step.  Its lane takes y = chi_ref -- or, while pin.renoise, chi_ref noised to the level the step arrives at with this step's
+// draws, which a row that does not step leaves unused (pp_noised_angle: the initial noising's arithmetic) -- and everything behind y
+// (the store, the trajectory slice, the next embedding) is the free rows' code.
+template <int MODE, int NU_ND, int CL = 1, bool SEEDED = false, bool PINNED = false>
 __global__ void __launch_bounds__(512)
-k_node_update(NUpdArgs A, float *chi, int step, int sde, const float *noise, int embed_next, StepScalars sp, TimeEmb te_next, PPRng rng) {
+k_node_update(NUpdArgs A, float *chi, int step, int sde, const float *noise, int embed_next, StepScalars sp, TimeEmb te_next, PPRng rng,
+              PPPin pin) {
     static_assert(CL == 1 || MODE == PP_NU_MID, "only the middle layers have a split form");
     static_assert(!SEEDED || MODE == PP_NU_STEP, "only the reverse step draws noise");
+    static_assert(!PINNED || SEEDED, "the pinned step is a seeded one: its fixed rows re-noise with the step's own draws");
     constexpr int NU_NRING = NU_ND + 1;
     constexpr bool LAST = MODE != PP_NU_MID;
     constexpr int NSLOT = LAST ? PP_NU_SLOTS_LAST : PP_NU_SLOTS_MID;
@@ -593,6 +593,8 @@ k_node_update(NUpdArgs A, float *chi, int step, int sde, const float *noise, int
     unsigned char m1raw = 0, m2raw = 0;
     int rt = 0;
     pp_rng_row rrow = {0u, 0u, 0u, 0u};        // SEEDED: (row in complex, key of the complex) of residue r
+    unsigned char fixraw = 0;                  // PINNED: fixed[n] and chi_ref[n][g]
+    float cref = 0.f;
     nf4 spv = zero4i;                          // c_ode, w, c_drift, c_diff of this step
     if constexpr (MODE == PP_NU_STEP) {
         spv = nf4{sp.c_ode, sp.w, sp.c_drift, sp.c_diff};
@@ -600,6 +602,10 @@ k_node_update(NUpdArgs A, float *chi, int step, int sde, const float *noise, int
         scm1 = A.sc_mask[(size_t)nc * 4 + g];
         m1raw = A.m1pi[(size_t)nc * 4 + g];
         m2raw = A.m2pi[(size_t)nc * 4 + g];
+        if constexpr (PINNED) {          // with the other per-row loads: a fetch in the tail would sit behind the decoder
+            fixraw = pin.fixed[nc];
+            cref = pin.chi_ref[(size_t)nc * 4 + g];
+        }
         if constexpr (SEEDED) {
             rrow = rng.tab[nc];          // one 16-byte load, unconditional like the others; the draws follow the stream start
         } else if (sde) {           // (the noise tensor only exists in sde mode)
@@ -648,8 +654,23 @@ k_node_update(NUpdArgs A, float *chi, int step, int sde, const float *noise, int
             const pp_rng_words w = pp_rng_draw(rng.seed_lo, rng.seed_hi, rrow, g, step);
             nz1 = pp_rng_normal(w.o[0], w.o[1]);
             nz2 = pp_rng_normal(w.o[2], w.o[3]);
+            if constexpr (PINNED) {
+                // the pinned value as well, folded into the step's own registers (the shallow-ring instance has 128 VGPRs for two
+                // workgroups per CU): a fixed lane carries its value in chi1 and the code 2 in m1raw, so the tail only selects
+                if (pin.renoise) cref = pp_noised_angle(cref, nz1, nz2, pin.sigma, m1raw != 0, m2raw != 0);
+                const bool fx = fixraw != 0;
+                chi1 = fx ? cref : chi1;
+                m1raw = fx ? 2 : (m1raw != 0 ? 1 : 0);
+                m2raw = fx ? 0 : m2raw;
+            }
         }
         asm volatile("" : "+v"(nz1), "+v"(nz2));
+        if constexpr (PINNED) {
+            unsigned mw = m1raw | ((unsigned)m2raw << 8);
+            asm volatile("" : "+v"(chi1), "+v"(mw));
+            m1raw = (unsigned char)mw;
+            m2raw = (unsigned char)(mw >> 8);
+        }
     }
 #pragma unroll
     for (int i = 0; i < NPV; i++) {
@@ -812,15 +833,23 @@ k_node_update(NUpdArgs A, float *chi, int step, int sde, const float *noise, int
                 const float sg = g == 0 ? s0 : g == 1 ? s1 : g == 2 ? s2 : s3;
                 const float sp_c_ode = spv[0], sp_w = spv[1], sp_c_drift = spv[2], sp_c_diff = spv[3];
                 const float sw = sg * sp_w;
+#define NU_M1ON (PINNED ? m1raw == 1 : m1raw != 0)      /* PINNED: m1raw = 2 marks a fixed lane (and its m2raw is 0) */
                 float yk = chi1;
                 if (!sde) {
-                    if (m1raw != 0 || m2raw != 0) yk = chi1 + sp_c_ode * sw;
+                    if (NU_M1ON || m2raw != 0) yk = chi1 + sp_c_ode * sw;
                 } else {
-                    if (m1raw != 0) yk = chi1 + (sp_c_drift * sw + sp_c_diff * nz1);
+                    if (NU_M1ON) yk = chi1 + (sp_c_drift * sw + sp_c_diff * nz1);
                     if (m2raw != 0) yk = yk + (sp_c_drift * sw + sp_c_diff * nz2);
                 }
-                const float y = wrap_pi(yk) * scm1;
+#undef NU_M1ON
+                float y = wrap_pi(yk) * scm1;
+                if constexpr (PINNED) {
+                    if (m1raw == 2) y = chi1;
+                }
                 if (live) chi[(size_t)n * 4 + g] = y;
+                if constexpr (PINNED) {
+                    if (pin.traj != nullptr && live) pin.traj[(size_t)n * 4 + g] = y;
+                }
                 if (embed_next) {          // features 6 + 2 g, 7 + 2 g of the embedding operand
                     unsigned hp, lp;
                     split2(sinf(y) * scm1, cosf(y) * scm1, hp, lp);
@@ -981,11 +1010,13 @@ __device__ __forceinline__ void message_inputs_pre(Smem &sm, int &flip, const WS
 
 // LAST_MODE is a template parameter so that the middle-layer variant (two of three launches) gets its own register
 // allocation: as one function the decoder / step / embedding tail cost it ~30 spilled registers.
-template <int LAST_MODE, bool SEEDED = false>
+// PINNED: as in k_node_update -- thread t < 4 NB pins (residue t >> 2, chi t & 3) if its row is fixed
+template <int LAST_MODE, bool SEEDED = false, bool PINNED = false>
 __global__ void __launch_bounds__(NT)
 k_node_update_valu(NodeArgs A, UpdW W, float *chi, int step, int sde, const float *noise, int embed_next, PreW pre0,
-                   StepScalars sp, TimeEmb te_next, PPRng rng) {
+                   StepScalars sp, TimeEmb te_next, PPRng rng, PPPin pin) {
     static_assert(!SEEDED || LAST_MODE == PP_NU_STEP, "only the reverse step draws noise");
+    static_assert(!PINNED || SEEDED, "the pinned step is a seeded one: its fixed rows re-noise with the step's own draws");
     constexpr int last_mode = LAST_MODE;
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     Smem &sm = *reinterpret_cast<Smem *>(smem_raw);
@@ -1000,6 +1031,13 @@ k_node_update_valu(NodeArgs A, UpdW W, float *chi, int step, int sde, const floa
     // per-feature vectors and row inputs, all up front
     const float out_b = W.out_b[f], g0 = W.g0[f], b0 = W.b0[f], g1 = W.g1[f], b1 = W.b1[f], ffn_out_b = W.ffn_out_b[f];
     const float fib = W.ffn_in_b[t];
+    unsigned char fixraw = 0;      // PINNED: fixed[n] and chi_ref[n][k] of the (residue, chi) thread t < 4 NB steps, up front as well
+    float cref = 0.f;
+    if constexpr (PINNED) {
+        const int pn = n0 + ((t >> 2) % NB) < N ? n0 + ((t >> 2) % NB) : N - 1;
+        fixraw = pin.fixed[pn];
+        cref = pin.chi_ref[(size_t)pn * 4 + (t & 3)];
+    }
     const VN ms = load_rows(A.msum, 1, n0, N, 0);
     const VN hv = load_rows(A.hV, 128, n0, N, f);
     const VN rm = load_rows(A.rmask, 1, n0, N, 0);
@@ -1168,13 +1206,19 @@ k_node_update_valu(NodeArgs A, UpdW W, float *chi, int step, int sde, const floa
             float sw = vcomp(sm.a[112 + k], i) * sp.w;
             bool m1 = A.m1pi[(size_t)n * 4 + k] != 0, m2 = A.m2pi[(size_t)n * 4 + k] != 0;
             float y = x;
+            float z1 = 0.f, z2 = 0.f;
+            if constexpr (PINNED) {      // in either mode: the fixed rows re-noise with the draws a free row's sde step takes
+                const pp_rng_words w = pp_rng_draw(rng.seed_lo, rng.seed_hi, rng.tab[n], k, step);
+                z1 = pp_rng_normal(w.o[0], w.o[1]);
+                z2 = pp_rng_normal(w.o[2], w.o[3]);
+            }
             if (!sde) {
                 if (m1 || m2) y = x + sp.c_ode * sw;
             } else {
                 // the two N(0,1) draws: the caller's tensor, or (SEEDED) this thread's own from the generator of pp_rng.h; one
                 // expression for both, so that the seeded step is the explicit-noise step
-                float z1 = 0.f, z2 = 0.f;
-                if constexpr (SEEDED) {
+                if constexpr (PINNED) {
+                } else if constexpr (SEEDED) {
                     const pp_rng_words w = pp_rng_draw(rng.seed_lo, rng.seed_hi, rng.tab[n], k, step);
                     z1 = pp_rng_normal(w.o[0], w.o[1]);
                     z2 = pp_rng_normal(w.o[2], w.o[3]);
@@ -1188,7 +1232,13 @@ k_node_update_valu(NodeArgs A, UpdW W, float *chi, int step, int sde, const floa
                 if (m2) y = y + (sp.c_drift * sw + sp.c_diff * z2);
             }
             y = wrap_pi(y) * A.sc_mask[(size_t)n * 4 + k];
+            if constexpr (PINNED) {
+                if (fixraw != 0) y = pin.renoise ? pp_noised_angle(cref, z1, z2, pin.sigma, m1, m2) : cref;
+            }
             chi[(size_t)n * 4 + k] = y;
+            if constexpr (PINNED) {
+                if (pin.traj != nullptr) pin.traj[(size_t)n * 4 + k] = y;
+            }
         }
     }
     __syncthreads();
@@ -1265,7 +1315,7 @@ static PreW make_pre(const pp_plan *p, int layer, bool edge) {
     return w;
 }
 
-typedef void (*nu_kernel_t)(NUpdArgs, float *, int, int, const float *, int, StepScalars, TimeEmb, PPRng);
+typedef void (*nu_kernel_t)(NUpdArgs, float *, int, int, const float *, int, StepScalars, TimeEmb, PPRng, PPPin);
 // mode 0 / 1 / 2 = PP_NU_MID / PP_NU_STEP / PP_NU_SCORE; multi: more tiles than CUs (shallower ring, two workgroups per CU)
 static nu_kernel_t nu_kernel(int mode, bool multi) {
     if (multi)
@@ -1277,6 +1327,10 @@ static nu_kernel_t nu_kernel(int mode, bool multi) {
 // the reverse step that draws its own noise: both launch depths
 static nu_kernel_t nu_kernel_seeded(bool multi) {
     return multi ? k_node_update<PP_NU_STEP, PP_NU_DEPTH_MULTI, 1, true> : k_node_update<PP_NU_STEP, PP_NU_DEPTH, 1, true>;
+}
+// the reverse step of pp_sample_partial: both launch depths
+static nu_kernel_t nu_kernel_pinned(bool multi) {
+    return multi ? k_node_update<PP_NU_STEP, PP_NU_DEPTH_MULTI, 1, true, true> : k_node_update<PP_NU_STEP, PP_NU_DEPTH, 1, true, true>;
 }
 static nu_kernel_t nu_kernel_split(int cl) {
     return cl == 4 ? k_node_update<PP_NU_MID, PP_NU_DEPTH, 4> : k_node_update<PP_NU_MID, PP_NU_DEPTH, 2>;
@@ -1299,11 +1353,15 @@ static pp_status node_attrs() {
         for (int multi = 0; multi < 2; multi++)
             PP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(nu_kernel_seeded(multi != 0)),
                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(SmemU)));
+        for (int multi = 0; multi < 2; multi++)
+            PP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(nu_kernel_pinned(multi != 0)),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(SmemU)));
 #ifndef PP_EDGE_F16
         PP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_node_update_valu<PP_NU_MID>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(Smem)));
         PP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_node_update_valu<PP_NU_STEP>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(Smem)));
         PP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_node_update_valu<PP_NU_SCORE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(Smem)));
         PP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_node_update_valu<PP_NU_STEP, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(Smem)));
+        PP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_node_update_valu<PP_NU_STEP, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(Smem)));
 #endif
         int dev = 0;
         hipDeviceProp_t prop;
@@ -1339,11 +1397,18 @@ pp_status pp_launch_node_embed_rows(pp_ctx *c, const float *chi, const float *t_
 
 pp_status pp_launch_node_update(pp_ctx *c, int layer, int last_mode, float *chi, int step, int mode,
                                 const float *noise, const StepParams *cur, const StepParams *next, hipStream_t s,
-                                const PPRng *rng) {
+                                const PPRng *rng, const PPPin *pin) {
     const bool embed_next_step = next != nullptr;
+    // the pinned instances (pp_sample_partial) draw in either mode: a fixed row re-noises with the step's draws
+    const bool pinned = pin != nullptr && last_mode == PP_NU_STEP;
+    if (pinned && (rng == nullptr || rng->tab == nullptr || pin->fixed == nullptr || pin->chi_ref == nullptr)) {
+        pp_set_error("pp_launch_node_update: the pinned reverse step needs the rng table, fixed and chi_ref");
+        return PP_ERR_INVALID;
+    }
     // the seeded instances exist for the reverse step in sde mode only (ode draws nothing)
-    const bool seeded = rng != nullptr && rng->tab != nullptr && last_mode == PP_NU_STEP && mode == PP_MODE_SDE;
+    const bool seeded = rng != nullptr && rng->tab != nullptr && last_mode == PP_NU_STEP && (mode == PP_MODE_SDE || pinned);
     const PPRng rg = seeded ? *rng : PPRng{nullptr, 0u, 0u};
+    const PPPin pn = pinned ? *pin : PPPin{nullptr, nullptr, nullptr, 0.f, 0};
     pp_status st0 = node_attrs();
     if (st0 != PP_OK) return st0;
     if ((last_mode == PP_NU_MID) != (layer < 2)) {
@@ -1397,14 +1462,17 @@ pp_status pp_launch_node_update(pp_ctx *c, int layer, int last_mode, float *chi,
             const PreW pre0 = make_pre(p, 0, false);
             const dim3 vgrid((c->N + NB - 1) / NB), vblock(NT);
             const auto kv_seeded = k_node_update_valu<PP_NU_STEP, true>;
+            const auto kv_pinned = k_node_update_valu<PP_NU_STEP, true, true>;
             if (last_mode == PP_NU_MID)
-                PP_LAUNCH(c, k_node_update_valu<PP_NU_MID>, vgrid, vblock, sizeof(Smem), s, NA, W, chi, step, sde, noise, embed_next, pre0, sp, te, rg);
+                PP_LAUNCH(c, k_node_update_valu<PP_NU_MID>, vgrid, vblock, sizeof(Smem), s, NA, W, chi, step, sde, noise, embed_next, pre0, sp, te, rg, pn);
+            else if (pinned)
+                PP_LAUNCH(c, kv_pinned, vgrid, vblock, sizeof(Smem), s, NA, W, chi, step, sde, noise, embed_next, pre0, sp, te, rg, pn);
             else if (seeded)
-                PP_LAUNCH(c, kv_seeded, vgrid, vblock, sizeof(Smem), s, NA, W, chi, step, sde, noise, embed_next, pre0, sp, te, rg);
+                PP_LAUNCH(c, kv_seeded, vgrid, vblock, sizeof(Smem), s, NA, W, chi, step, sde, noise, embed_next, pre0, sp, te, rg, pn);
             else if (last_mode == PP_NU_STEP)
-                PP_LAUNCH(c, k_node_update_valu<PP_NU_STEP>, vgrid, vblock, sizeof(Smem), s, NA, W, chi, step, sde, noise, embed_next, pre0, sp, te, rg);
+                PP_LAUNCH(c, k_node_update_valu<PP_NU_STEP>, vgrid, vblock, sizeof(Smem), s, NA, W, chi, step, sde, noise, embed_next, pre0, sp, te, rg, pn);
             else
-                PP_LAUNCH(c, k_node_update_valu<PP_NU_SCORE>, vgrid, vblock, sizeof(Smem), s, NA, W, chi, step, sde, noise, embed_next, pre0, sp, te, rg);
+                PP_LAUNCH(c, k_node_update_valu<PP_NU_SCORE>, vgrid, vblock, sizeof(Smem), s, NA, W, chi, step, sde, noise, embed_next, pre0, sp, te, rg, pn);
             PP_HIP_CHECK(hipGetLastError());
             return PP_OK;
         }
@@ -1421,12 +1489,13 @@ pp_status pp_launch_node_update(pp_ctx *c, int layer, int last_mode, float *chi,
         // workgroup that starts late (a shared GPU, a busy chip) still reads what it must; the context's pointers swap
         A.hV_out = c->hV_alt;
         std::swap(c->hV, c->hV_alt);
-        PP_LAUNCH(c, nu_kernel_split(cl), dim3(tiles * cl), block, sizeof(SmemU), s, A, chi, step, sde, noise, embed_next, sp, te, rg);
+        PP_LAUNCH(c, nu_kernel_split(cl), dim3(tiles * cl), block, sizeof(SmemU), s, A, chi, step, sde, noise, embed_next, sp, te, rg, pn);
         PP_HIP_CHECK(hipGetLastError());
         return PP_OK;
     }
-    const nu_kernel_t kern = seeded ? nu_kernel_seeded(multi) : nu_kernel(last_mode == PP_NU_MID ? 0 : last_mode == PP_NU_STEP ? 1 : 2, multi);
-    PP_LAUNCH(c, kern, grid, block, sizeof(SmemU), s, A, chi, step, sde, noise, embed_next, sp, te, rg);
+    const nu_kernel_t kern = pinned ? nu_kernel_pinned(multi)
+                             : seeded ? nu_kernel_seeded(multi) : nu_kernel(last_mode == PP_NU_MID ? 0 : last_mode == PP_NU_STEP ? 1 : 2, multi);
+    PP_LAUNCH(c, kern, grid, block, sizeof(SmemU), s, A, chi, step, sde, noise, embed_next, sp, te, rg, pn);
     PP_HIP_CHECK(hipGetLastError());
     return PP_OK;
 }
@@ -1482,18 +1551,13 @@ __global__ void k_noise_seeded(const pp_rng_row *__restrict__ tab, int N, uint32
 __global__ void k_add_noise_seeded(const pp_rng_row *__restrict__ tab, int N, const float *__restrict__ chi0, float sigma,
                                    const uint8_t *__restrict__ m1pi, const uint8_t *__restrict__ m2pi, uint32_t seed_lo,
                                    uint32_t seed_hi, float *__restrict__ chi) {
-#pragma clang fp contract(off)
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= N * 4) return;
     const bool m1 = m1pi[i] != 0, m2 = m2pi[i] != 0;
     float x = chi0[i];
     if (m1 || m2) {
         const pp_rng_words w = pp_rng_draw(seed_lo, seed_hi, tab[i >> 2], i & 3, -1);
-        const float n1 = pp_rng_normal(w.o[0], w.o[1]) * sigma;
-        x = x + n1 * (m1 ? 1.f : 0.f);
-        const float n2 = pp_rng_normal(w.o[2], w.o[3]) * sigma;
-        x = x + n2 * (m2 ? 1.f : 0.f);
-        x = wrap_pi(x);
+        x = pp_noised_angle(x, pp_rng_normal(w.o[0], w.o[1]), pp_rng_normal(w.o[2], w.o[3]), sigma, m1, m2);
     }
     chi[i] = x;
 }

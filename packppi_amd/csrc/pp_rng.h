@@ -60,3 +60,27 @@ PP_RNG_HD float pp_rng_normal(uint32_t oa, uint32_t ob) {
     const float u1 = pp_rng_uniform(oa), u2 = pp_rng_uniform(ob);
     return sqrtf(-2.f * logf(u1)) * cosf(6.2831855f * u2);
 }
+
+// (x + pi) % (2 pi) - pi with torch.remainder semantics in fp32
+PP_RNG_HD float pp_wrap_pi(float x) {
+    const float PIf = 3.14159274101257324f, TWO_PIf = 6.28318548202514648f;
+    float y = x + PIf;
+    float r = fmodf(y, TWO_PIf);
+    if (r != 0.f && r < 0.f) r += TWO_PIf;
+    return r - PIf;
+}
+
+// add_sc_noise on one angle (TorsionalDiffusion.py:111-124) with the draws z1 (1pi schedule), z2 (2pi schedule) at noise level
+// sigma: x += (z1 sigma) m1, x += (z2 sigma) m2, wrap -- every product and sum rounded on its own, as the reference's tensor
+// operations round.  An entry outside both periodic masks receives no noise and is returned untouched.  The ONE statement of this
+// arithmetic: the initial noising (k_add_noise_seeded) and the re-noising of the fixed rows of pp_sample_partial (both node-update
+// kernels) inline it, so that they cannot round differently.
+PP_RNG_HD float pp_noised_angle(float x, float z1, float z2, float sigma, bool m1, bool m2) {
+#pragma clang fp contract(off)
+    if (!(m1 || m2)) return x;
+    const float n1 = z1 * sigma;
+    x = x + n1 * (m1 ? 1.f : 0.f);
+    const float n2 = z2 * sigma;
+    x = x + n2 * (m2 ? 1.f : 0.f);
+    return pp_wrap_pi(x);
+}

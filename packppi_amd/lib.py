@@ -20,9 +20,11 @@ SYMBOLS = ("pp_version", "pp_last_error", "pp_build_id", "pp_plan_set_knn_ties",
            "pp_clash", "pp_proximal", "pp_proximal_packed", "pp_time_kernel", "pp_profile_kernel", "pp_profile_read", "pp_edge_variant", "pp_has_range_check", "pp_range_check", "pp_range_check_parts", "pp_ctx_saturated",
            "pp_affinity_create", "pp_affinity_destroy", "pp_affinity_encode", "pp_affinity_predict",
            "pp_score_rows", "pp_so2_set_grids", "pp_so2_score", "pp_dsm_loss",
-           "pp_ctx_set_rng_keys", "pp_noise_seeded", "pp_add_noise_seeded", "pp_sample_seeded")
+           "pp_ctx_set_rng_keys", "pp_noise_seeded", "pp_add_noise_seeded", "pp_sample_seeded",
+           "pp_sample_partial")
 
 
+FIX_MODES = {"hold": 0, "renoise": 1}         # PP_FIX_HOLD, PP_FIX_RENOISE
 KNN_TIES = {"lower_index": 0, "aten_cpu": 1, "aten_member": 2}
 
 
@@ -118,6 +120,7 @@ def load():
     lib.pp_noise_seeded.argtypes = [vp, C.c_uint64, i, vp, vp, vp]
     lib.pp_add_noise_seeded.argtypes = [vp, vp, f, C.c_uint64, vp, vp]
     lib.pp_sample_seeded.argtypes = [vp, vp, vp, i, i, C.c_uint64, vp]
+    lib.pp_sample_partial.argtypes = [vp, vp, vp, vp, i, vp, i, i, C.c_uint64, vp, vp]
     _lib = lib
     return lib
 
@@ -444,6 +447,29 @@ class Context:
         _check(load().pp_sample(self.handle, _ptr(chi), sched.ctypes.data, int(len(sched)), 0 if mode == "ode" else 1,
                                 _ptr(nz), _stream(self.plan.device)), "pp_sample")
         return chi
+
+    def sample_partial(self, chi, chi_ref, fixed, schedule, mode, seed, fix_mode="renoise", trajectory=False):
+        """Partial repacking (pp_sample_partial): rows with ``fixed`` != 0 ([B, L] bool / uint8, packed: [1, N])
+        keep ``chi_ref``, the others are sampled as ``sample(..., seed=seed)`` samples them.  ``fix_mode``: "hold" (fixed rows are
+        ``chi_ref`` at every step) or "renoise" (``chi_ref`` re-noised to each step's level with that step's own draws; ``chi_ref``
+        after the last step).  ``chi`` is the step-0 state of EVERY row -- the call does not initialise the fixed ones.  Returns the
+        sample [B, L, 4], with ``trajectory`` also the angles after every step [n_steps, B, L, 4]."""
+        if mode not in ("ode", "sde"):
+            raise NotImplementedError(mode)
+        if fix_mode not in FIX_MODES:
+            raise ValueError(f"fix_mode must be one of {sorted(FIX_MODES)}")
+        chi = self._chi(chi).clone()
+        ref = self._chi(chi_ref)
+        fx = torch.as_tensor(fixed).to(device=self.plan.device)
+        if fx.numel() != self.n_rows:
+            raise ValueError(f"fixed has {fx.numel()} elements, this context has {self.n_rows} rows")
+        fx = (fx != 0).to(torch.uint8).reshape(-1).contiguous()
+        sched = np.ascontiguousarray(torch.as_tensor(schedule, dtype=torch.float32).cpu().numpy())
+        traj = self._new(max(len(sched) - 1, 0), self.B, self.L, 4) if trajectory else None
+        _check(load().pp_sample_partial(self.handle, _ptr(chi), _ptr(ref), _ptr(fx), FIX_MODES[fix_mode], sched.ctypes.data,
+                                        int(len(sched)), 0 if mode == "ode" else 1, _seed64(seed), _ptr(traj),
+                                        _stream(self.plan.device)), "pp_sample_partial")
+        return (chi, traj) if trajectory else chi
 
     def atom14(self, chi):
         chi = self._chi(chi)

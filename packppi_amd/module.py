@@ -279,14 +279,44 @@ class TDiffusionModule:
     def reset_metrics(self):
         self._val_loss, self._test_loss = (0.0, 0), (0.0, 0)
 
-    def sampling(self, batch, use_proximal: bool = False, return_list: bool = False, sde_noise=None, seed=None):
+    def sampling(self, batch, use_proximal: bool = False, return_list: bool = False, sde_noise=None, seed=None,
+                 fixed_mask=None, fixed_chi=None, fixed_mode="renoise", return_trajectory: bool = False):
         """``seed`` (an int, None = the reference's behaviour): the initial noising and the sde noise come from the counter-based
         generator on the device (csrc/pp_rng.h) instead of torch's global one.  The noise of a complex is then a function of
         (seed, its key, its rows, the step) alone: the same complex gets the same angles alone, anywhere in a packed batch and
         on any rank.  Keys: ``batch.complex_keys`` (a list or int64 tensor, one per complex; ``batch.pack`` collects them from the
         complexes' ``complex_key``), else 0, 1, 2 ... in batch order.  This is not torch's stream: a seeded run does not
-        reproduce a reference run under the same ``torch.manual_seed``."""
+        reproduce a reference run under the same ``torch.manual_seed``.
+
+        ``fixed_mask`` (bool / uint8 [B, L], packed batch: [1, N]; 1 = keep; default ``batch.fixed_mask`` if the batch carries one):
+        partial repacking -- those rows keep ``fixed_chi`` (default ``batch.SC_D``), the others are sampled around them
+        (DESIGN.md section 13).  ``fixed_mode``: "renoise" (replacement conditioning: at every step the network sees the fixed rows
+        noised to that step's level) or "hold" (it sees them clean throughout).  Needs ``seed``; fixed rows of the result are
+        ``fixed_chi`` bit for bit.  ``return_trajectory``: (sample, angles after every step [n_steps, B, L, 4])."""
         cfg = self.hparams.sample_cfg
+        if fixed_mask is None:
+            fixed_mask = batch.get("fixed_mask") if hasattr(batch, "get") else getattr(batch, "fixed_mask", None)
+        if fixed_mask is not None:
+            if seed is None:
+                raise ValueError("fixed_mask needs seed: the fixed rows are re-noised with the seeded generator's draws")
+            if sde_noise is not None:
+                raise ValueError("fixed_mask and sde_noise exclude each other: partial repacking draws its own noise")
+            if use_proximal:
+                raise ValueError("fixed_mask with use_proximal=True is not supported: the proximal stage has no pin and would move "
+                                 "the fixed rows (out of scope of partial repacking)")
+            from .lib import FIX_MODES
+            if fixed_mode not in FIX_MODES:
+                raise ValueError(f"fixed_mode must be one of {sorted(FIX_MODES)}")
+            ctx = self._context(batch)
+            ctx.set_rng_keys(batch.get("complex_keys") if hasattr(batch, "get") else getattr(batch, "complex_keys", None))
+            fx = (torch.as_tensor(fixed_mask).to(self.device) != 0).reshape(ctx.B, ctx.L)
+            ref = ctx._chi(batch.SC_D if fixed_chi is None else fixed_chi)
+            init = ctx.add_noise(torch.where(fx.unsqueeze(-1), ref, ctx._chi(batch.SC_D)), 1.0, seed)
+            if fixed_mode == "hold":
+                init = torch.where(fx.unsqueeze(-1), ref, init)
+            return ctx.sample_partial(init, ref, fx, self.schedule, cfg.mode, seed, fixed_mode, trajectory=return_trajectory)
+        if return_trajectory:
+            raise ValueError("return_trajectory needs fixed_mask (the trajectory is written by the partial sampler)")
         packed = batch.get("seg_offsets") is not None if hasattr(batch, "get") else False
         if packed and use_proximal and return_list:
             raise ValueError("return_list=True needs a B = 1 batch; for a packed batch use "

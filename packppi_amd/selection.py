@@ -1,0 +1,56 @@
+"""Residue selections for partial repacking (``TDiffusionModule.sampling(fixed_mask=...)``, ``eval_diffusion --repack``).
+
+A selection names the residues to REPACK; the rows outside it are the ones the sampler keeps (``fixed_mask = ~selection``).
+Residues are addressed as ``featurize.mutant_data`` looks mutations up: by chain ID and the residue number of the PDB file
+(``protein["chain_id"]``, ``protein["residue_index"]``) -- not by the offset numbering the featurisation gives later chains.
+"""
+from typing import Dict
+
+import numpy as np
+
+
+def parse_selection(spec: str, protein: Dict) -> np.ndarray:
+    """Row mask [L] (bool) over ``protein`` of the residues named by ``spec``: comma-separated terms ``CHAIN`` (the whole
+    chain), ``CHAIN:N`` (one residue) or ``CHAIN:N-M`` (an inclusive range; negative numbers as in ``A:-3-5``).  Insertion codes
+    are not part of the protein dict: every row carrying the number is selected.  An unknown chain, a malformed term or a term
+    that matches no residue raises ``ValueError``."""
+    chain_id = np.asarray(protein["chain_id"])
+    number = np.asarray(protein["residue_index"]).astype(np.int64)
+    mask = np.zeros(len(number), dtype=bool)
+    terms = [t.strip() for t in str(spec).split(",") if t.strip()]
+    if not terms:
+        raise ValueError("empty selection")
+    for term in terms:
+        chain, sep, rng = term.partition(":")
+        if chain not in chain_id:
+            raise ValueError(f"selection '{term}': no chain '{chain}' (chains: {', '.join(sorted(set(chain_id.tolist())))})")
+        rows = chain_id == chain
+        if sep:
+            try:
+                cut = rng.find("-", 1)          # a leading '-' is a sign
+                lo, hi = (int(rng), int(rng)) if cut < 0 else (int(rng[:cut]), int(rng[cut + 1:]))
+            except ValueError:
+                raise ValueError(f"selection '{term}': expected CHAIN, CHAIN:N or CHAIN:N-M") from None
+            rows = rows & (number >= lo) & (number <= hi)
+        if not rows.any():
+            raise ValueError(f"selection '{term}' matches no residue")
+        mask |= rows
+    return mask
+
+
+def interface_selection(protein: Dict, pdb, radius: float = 10.0) -> np.ndarray:
+    """Row mask [L] (bool) of the interface: residues with an atom within ``radius`` of another protein chain
+    (``analysis.interface_residues`` on the file, matched by chain ID and file numbering).  ``ValueError`` if the file has fewer
+    than two protein chains or no residue qualifies."""
+    from .analysis import interface_residues
+    inter = interface_residues(pdb, radius)
+    if inter is None:
+        raise ValueError(f"{pdb}: an interface needs at least two protein chains")
+    chain_id = np.asarray(protein["chain_id"])
+    number = np.asarray(protein["residue_index"]).astype(np.int64)
+    mask = np.zeros(len(number), dtype=bool)
+    for chain, numbers in inter.items():
+        mask |= (chain_id == chain) & np.isin(number, numbers)
+    if not mask.any():
+        raise ValueError(f"{pdb}: no residue within {radius} A of another chain")
+    return mask
