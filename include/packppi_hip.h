@@ -280,6 +280,27 @@ pp_status pp_proximal(pp_ctx *ctx, const float *chi, float lamda, int num_steps,
 pp_status pp_proximal_packed(pp_ctx *ctx, const float *chi, float lamda, int num_steps, const int32_t *norm_rows,
                              float *chi_traj, float *chi_last, float *chi_accepted, float *losses, void *stream);
 
+/* The proximal stage of partial repacking (no reference counterpart): pp_proximal_packed with some rows
+ * pinned.  fixed is a DEVICE array [N] of bytes, the `fixed` of pp_sample_partial: 1 = the row keeps its incoming angles, 0 = the
+ * row is free.  It is the reference's optimiser (optimize.py:5-73) with SC_D_clash_mask & ~fixed in place of SC_D_clash_mask at
+ * optimize.py:29 and nothing else changed.  Per complex of the ctx:
+ *   1. the clash statistic is unchanged: per_res at the incoming angles, its mean over ALL rows of the complex, fixed ones
+ *      included, with the divisor of pp_proximal_packed (norm_rows, or the length) -- a repacked shell is judged against the
+ *      whole complex (optimize.py:5-18);
+ *   2. moved[g] = per_res[g] > mean && !fixed[g]: only these rows get z = chi, Adam state and steps (optimize.py:31,47-51); every
+ *      other row, fixed or not, is evaluated at chi and comes out as chi bit for bit in every slice of chi_traj, in chi_last and
+ *      in chi_accepted (optimize.py:34-35,69);
+ *   3. loss, gradient and accept rule are unchanged: anchor term + lamda * mean clash over the whole complex (optimize.py:33-45;
+ *      a free atom overlapping a fixed one counts through both residues' per_res), accepted per complex where
+ *      losses[s][num_steps-1] < losses[s][0], on the device.
+ * With fixed all 0 every output has the bits of pp_proximal_packed.  ctx, norm_rows, chi, chi_traj, chi_last, chi_accepted and
+ * losses as in pp_proximal_packed (a packed ctx or a B = 1 one; a padded B > 1 ctx gives PP_ERR_INVALID); moved (DEVICE [N] bytes,
+ * or NULL) receives the mask of rule 2.  Waits for the stream no more than pp_proximal_packed does.  PP_ERR_INVALID: a null ctx,
+ * chi, fixed, chi_last, chi_accepted or losses (without a pin, call pp_proximal_packed), num_steps < 1. */
+pp_status pp_proximal_pinned(pp_ctx *ctx, const float *chi, const uint8_t *fixed /* DEVICE [N] */, float lamda,
+                             int num_steps, const int32_t *norm_rows, float *chi_traj, float *chi_last,
+                             float *chi_accepted, float *losses, uint8_t *moved /* DEVICE [N] or NULL */, void *stream);
+
 /* ---- PackPPI-AP: binding ddG prediction (src/models/AffinityPrediction.py) ----------------------------------------------
  * The pretrained network at t = 0 is pp_score (get_pret_feature, :109-122: hV of a ctx of the wild-type batch and of one of
  * the mutant batch).  The mutation encoder + MPNN (mode `network`, :50-71) run on a plan of their own: pp_plan_create with

@@ -9,7 +9,8 @@ names that configs/ directory and the four hot-path YAML files are read as plain
 --seed N makes the run reproducible: all sampling noise then comes from the seeded device generator.
 --repack SPEC|interface repacks only the named residues ("A:45-60,B:12,C": chain and PDB residue number; "interface": residues
 within 10 A of another chain) and keeps every other residue at the input's angles; --fixed_mode chooses
-what the sampled residues are conditioned on.  It needs --seed and excludes --use_proximal.
+what the sampled residues are conditioned on.  It needs --seed; with --use_proximal the proximal stage is the pinned one
+(TDiffusionModule.repack): only repacked residues move, the kept ones stay at the input's angles.
 """
 import argparse
 import os
@@ -59,7 +60,10 @@ def evaluate_model(model, args):
         sel = interface_selection(protein, args.input) if args.repack == "interface" else parse_selection(args.repack, protein)
         print(f"----- Repacking {int(sel.sum())} of {len(sel)} residues ({args.fixed_mode}); the others keep the input's angles -----")
         fixed = torch.from_numpy(~sel).unsqueeze(0)
-    SC_D_sample = model.sampling(batch, use_proximal=args.use_proximal, seed=args.seed, fixed_mask=fixed, fixed_mode=args.fixed_mode)
+    if fixed is not None:
+        SC_D_sample = model.repack(batch, fixed, seed=args.seed, fixed_mode=args.fixed_mode, use_proximal=args.use_proximal)
+    else:
+        SC_D_sample = model.sampling(batch, use_proximal=args.use_proximal, seed=args.seed)
     if model.saturated() & 4:
         print("----- WARNING: NaN / infinity in the input coordinates or angles: the reference would return NaN here -----")
     if model.saturated() & 3:
@@ -99,8 +103,6 @@ def main(argv=None):
     args = p.parse_args(argv)
     if args.repack is not None and args.seed is None:
         p.error("--repack needs --seed (the kept residues are re-noised with the seeded generator's draws)")
-    if args.repack is not None and args.use_proximal:
-        p.error("--repack excludes --use_proximal: the proximal stage has no pin and would move the kept residues")
     evaluate_model(load_model(args), args)
 
 

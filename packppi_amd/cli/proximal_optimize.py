@@ -1,6 +1,8 @@
 """``proximal_optimize`` command line (src/proximal_optimize.py:26-78): clash-relax the side chains of a PDB.
 
 Flags as in the reference (:69-78) plus --device (the reference script is CPU only; this path is HIP only).
+--repack SPEC|interface (as in eval_diffusion): only the named residues may move, every other residue keeps
+the input's angles (the pinned optimiser: the clash threshold is still the mean over all residues).
 """
 import argparse
 from pathlib import Path
@@ -20,6 +22,8 @@ def main(argv=None):
     p.add_argument("--lamda", type=float, help="The influence of the proximal term on the gradient.", default=1)
     p.add_argument("--num_steps", type=int, help="Number of optimize steps.", default=50)
     p.add_argument("--device", type=str, default="cuda")
+    p.add_argument("--repack", type=str, default=None, metavar="SPEC|interface", help="Optimise only these residues, e.g. "
+                   "'A:45-60,B:12,C' (chain and PDB residue number) or 'interface'; the others keep the input's angles.")
     args = p.parse_args(argv)
 
     assert contains_sidechains(args.input), "----- No side chain atoms found in the input PDB -----"
@@ -28,8 +32,15 @@ def main(argv=None):
     print(f"----- The input structure clashscore is {analysis.get_clashscore(args.input)} -----")
     protein = from_pdb_file(Path(args.input), mse_to_met=True)
     batch = analysis.get_prot(args.input).to(args.device)
+    fixed = None
+    if args.repack is not None:
+        import torch
+        from ..selection import interface_selection, parse_selection
+        sel = interface_selection(protein, args.input) if args.repack == "interface" else parse_selection(args.repack, protein)
+        print(f"----- Optimising {int(sel.sum())} of {len(sel)} residues; the others keep the input's angles -----")
+        fixed = torch.from_numpy(~sel).unsqueeze(0)
     chis, losses = proximal_optimizer(batch, batch.SC_D, args.violation_tolerance_factor,
-                                      args.clash_overlap_tolerance, args.lamda, args.num_steps)
+                                      args.clash_overlap_tolerance, args.lamda, args.num_steps, fixed_mask=fixed)
     SC_D = chis[-1] if losses[-1] < losses[0] else batch.SC_D
     xyz = get_atom14_coords(batch.X, batch.residue_type, batch.BB_D, SC_D)
     protein["atom_positions"] = xyz.cpu().squeeze(0).numpy()

@@ -800,28 +800,47 @@ extern "C" pp_status pp_proximal(pp_ctx *c, const float *chi, float lamda, int n
     return pp_launch_proximal(c, chi, lamda, num_steps, chi_traj, chi_last, losses, static_cast<hipStream_t>(stream));
 }
 
-extern "C" pp_status pp_proximal_packed(pp_ctx *c, const float *chi, float lamda, int num_steps, const int32_t *norm_rows,
-                                        float *chi_traj, float *chi_last, float *chi_accepted, float *losses, void *stream) {
-    if (c) c->last_stream = static_cast<hipStream_t>(stream);
-    if (!c || !chi || !chi_last || !chi_accepted || !losses) FAIL(PP_ERR_INVALID, "pp_proximal_packed: null argument");
+// pp_proximal_packed and pp_proximal_pinned (`who` names the export in messages; fixed == nullptr: no pin)
+static pp_status proximal_packed_impl(const char *who, pp_ctx *c, const float *chi, const uint8_t *fixed, float lamda, int num_steps,
+                                      const int32_t *norm_rows, float *chi_traj, float *chi_last, float *chi_accepted, float *losses,
+                                      uint8_t *moved, void *stream) {
+    const std::string w(who);
     if (!c->packed && c->B != 1)
-        FAIL(PP_ERR_INVALID, "pp_proximal_packed: needs a context from pp_complex_prepare_packed (or a B = 1 one), not a padded B > 1 batch");
-    if (num_steps < 1) FAIL(PP_ERR_INVALID, "pp_proximal_packed: num_steps must be >= 1");
-    if (!c->plan->clash_params_set) FAIL(PP_ERR_INVALID, "pp_proximal_packed: call pp_plan_set_clash_params first");
-    if (!c->b.atom_mask || !c->b.residue_index) FAIL(PP_ERR_INVALID, "pp_proximal_packed: batch lacks atom_mask / residue_index");
+        FAIL(PP_ERR_INVALID, w + ": needs a context from pp_complex_prepare_packed (or a B = 1 one), not a padded B > 1 batch");
+    if (num_steps < 1) FAIL(PP_ERR_INVALID, w + ": num_steps must be >= 1");
+    if (!c->plan->clash_params_set) FAIL(PP_ERR_INVALID, w + ": call pp_plan_set_clash_params first");
+    if (!c->b.atom_mask || !c->b.residue_index) FAIL(PP_ERR_INVALID, w + ": batch lacks atom_mask / residue_index");
     // every complex is at least min_len rows long (for a B = 1 context: N): an entry below that is shorter than its complex for sure
     // (the exact lengths are on the device only; the kernels take max(entry, length))
     const int shortest = c->packed ? c->shortest : c->N;
     if (norm_rows)
         for (int s = 0; s < c->B; s++)
             if (norm_rows[s] < shortest)
-                FAIL(PP_ERR_INVALID, "pp_proximal_packed: norm_rows[" + std::to_string(s) + "] = " + std::to_string(norm_rows[s]) +
+                FAIL(PP_ERR_INVALID, w + ": norm_rows[" + std::to_string(s) + "] = " + std::to_string(norm_rows[s]) +
                                          " is below the shortest complex (" + std::to_string(shortest) + " rows)");
     PP_HIP_CHECK(hipSetDevice(c->plan->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
     // the host table is caller-owned: from pageable memory, hipMemcpyAsync has taken the data when it returns
     if (norm_rows) PP_HIP_CHECK(hipMemcpyAsync(c->prox_nrows, norm_rows, (size_t)c->B * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    return pp_launch_proximal_packed(c, chi, lamda, num_steps, norm_rows != nullptr, chi_traj, chi_last, chi_accepted, losses, s);
+    return pp_launch_proximal_packed(c, chi, lamda, num_steps, norm_rows != nullptr, chi_traj, chi_last, chi_accepted, losses, s, fixed,
+                                     moved);
+}
+
+extern "C" pp_status pp_proximal_packed(pp_ctx *c, const float *chi, float lamda, int num_steps, const int32_t *norm_rows,
+                                        float *chi_traj, float *chi_last, float *chi_accepted, float *losses, void *stream) {
+    if (c) c->last_stream = static_cast<hipStream_t>(stream);
+    if (!c || !chi || !chi_last || !chi_accepted || !losses) FAIL(PP_ERR_INVALID, "pp_proximal_packed: null argument");
+    return proximal_packed_impl("pp_proximal_packed", c, chi, nullptr, lamda, num_steps, norm_rows, chi_traj, chi_last, chi_accepted,
+                                losses, nullptr, stream);
+}
+
+extern "C" pp_status pp_proximal_pinned(pp_ctx *c, const float *chi, const uint8_t *fixed, float lamda, int num_steps,
+                                        const int32_t *norm_rows, float *chi_traj, float *chi_last, float *chi_accepted,
+                                        float *losses, uint8_t *moved, void *stream) {
+    if (c) c->last_stream = static_cast<hipStream_t>(stream);
+    if (!c || !chi || !fixed || !chi_last || !chi_accepted || !losses) FAIL(PP_ERR_INVALID, "pp_proximal_pinned: null argument");
+    return proximal_packed_impl("pp_proximal_pinned", c, chi, fixed, lamda, num_steps, norm_rows, chi_traj, chi_last, chi_accepted,
+                                losses, moved, stream);
 }
 
 // Measurement aid (bench.py): average duration of one launch of a hot kernel, timed with HIP events on
@@ -909,7 +928,7 @@ extern "C" pp_status pp_debug_score_prefix(pp_ctx *c, const float *chi, float t,
 // pp_profile_read synchronises, sums the pair intervals, reports (total ms, launches) and switches profiling off.
 extern "C" pp_status pp_profile_kernel(pp_ctx *c, int which) {
     if (!c || which < 0 || which > 3)
-        FAIL(PP_ERR_INVALID, "pp_profile_kernel: which must be 0 (node message), 1 (edge update), 2 (node update) or 3 (the Adam-step launch of pp_proximal / pp_proximal_packed: clash + gradient + step + reconstruction)");
+        FAIL(PP_ERR_INVALID, "pp_profile_kernel: which must be 0 (node message), 1 (edge update), 2 (node update) or 3 (the Adam-step launch of pp_proximal / pp_proximal_packed / pp_proximal_pinned: clash + gradient + step + reconstruction)");
     c->prof_which = which;
     c->prof_n = 0;
     return PP_OK;

@@ -588,15 +588,21 @@ __device__ __forceinline__ void seg_rows(const int32_t *__restrict__ off, int s,
 // m = v = 0; xeff = chi.  The divisor of the complex's means is n = max(nrows[s], its length) (nrows == nullptr: the length).  Also
 // writes (n, 1 / n) to seg_norm[s] (k_prox_losses) and 1 / n to inv_row of every row of the complex (k_clash<CAND, true>).
 //
+// PIN (pp_proximal_pinned): mask[g] = per_res[g] > mean && !fixed[g] (optimize.py:29 with SC_D_clash_mask & ~fixed).  The mean is
+// unchanged -- over every row of the complex, the fixed ones included -- and so is everything the fused step does: a row out of the
+// mask gets z = x = 0 here and `outv = mk ? xn : c0v` there, the incoming angle bit for bit at every step.  moved, if not null,
+// receives the mask.  The PIN = false instance is the kernel pp_proximal / pp_proximal_packed have always launched.
+//
 // A complex has the same bits alone in a B = 1 context and as one segment of a packed batch: the divisor is (float)n either way (a
 // B = 1 context: (float)N); 1 / n is one IEEE-rounded fp32 division on the device, the bits of 1.0f / (float)n on the host (HIP's
 // fp32 division is correctly rounded unless fast-math flags say otherwise); the strided sums, the butterfly and the in-order LDS
 // combine run over the complex's own rows counted from its first; and k_prox_losses counts its groups of 16 from that row too.
+template <bool PIN>
 __global__ void __launch_bounds__(1024)
 k_prox_init(int N, const int32_t *__restrict__ off, const int32_t *__restrict__ nrows, const float *__restrict__ per_res,
             const float *__restrict__ chi, uint8_t *__restrict__ mask, float *__restrict__ z, float *__restrict__ x,
             float *__restrict__ m, float *__restrict__ v, float *__restrict__ xeff, float2 *__restrict__ seg_norm,
-            float *__restrict__ inv_row) {
+            float *__restrict__ inv_row, const uint8_t *__restrict__ fixed, uint8_t *__restrict__ moved) {
     __shared__ float s_part[16];
     __shared__ float s_mean;
     int row0, row1;
@@ -621,7 +627,11 @@ k_prox_init(int N, const int32_t *__restrict__ off, const int32_t *__restrict__ 
     const float mean = s_mean;
     for (int r = threadIdx.x; r < len; r += 1024) {
         const int g = row0 + r;
-        const bool mk = per_res[g] > mean;
+        bool mk = per_res[g] > mean;
+        if constexpr (PIN) {
+            mk = mk && fixed[g] == 0;
+            if (moved) moved[g] = mk ? 1 : 0;
+        }
         mask[g] = mk ? 1 : 0;
         inv_row[g] = inv;
         for (int k = 0; k < 4; k++) {
@@ -712,9 +722,10 @@ pp_status pp_launch_clash(pp_ctx *c, const float *xyz, float *per_res, float *dc
 }
 
 // The proximal loop, per complex of the context: each has its own clash mask mean, 1 / n and loss row (losses [B][nsteps]).  off:
-// the device table of first rows, or nullptr = the context is one complex, rows 0 .. N - 1 (its losses are row 0).
+// the device table of first rows, or nullptr = the context is one complex, rows 0 .. N - 1 (its losses are row 0).  fixed (device
+// [N], or nullptr = no pin): rows kept out of the clash mask (k_prox_init<true>); moved (device [N] or nullptr) receives that mask.
 static pp_status prox_loop(pp_ctx *c, const float *chi, float lamda, int nsteps, const int32_t *off, const int32_t *nrows,
-                           float *traj, float *chi_last, float *losses, hipStream_t s) {
+                           const uint8_t *fixed, uint8_t *moved, float *traj, float *chi_last, float *losses, hipStream_t s) {
     pp_status st;
     const pp_plan *p = c->plan;
     // static partner candidates of the whole loop (the backbone does not move): k_clash<true> reads them instead of scanning
@@ -726,8 +737,12 @@ static pp_status prox_loop(pp_ctx *c, const float *chi, float lamda, int nsteps,
     // clash mask at the incoming angles (optimize.py:5-18); per_res does not depend on the normaliser
     if ((st = pp_launch_atom14(c, chi, c->xyz, s)) != PP_OK) return st;
     if ((st = pp_launch_clash(c, c->xyz, c->per_res, nullptr, s, cands)) != PP_OK) return st;
-    hipLaunchKernelGGL(k_prox_init, dim3(c->B), dim3(1024), 0, s, c->N, off, nrows, c->per_res, chi, c->pmask, c->pz, c->px, c->pm,
-                       c->pv, c->pxeff, c->prox_seg, c->prox_inv);
+    if (fixed)
+        hipLaunchKernelGGL(k_prox_init<true>, dim3(c->B), dim3(1024), 0, s, c->N, off, nrows, c->per_res, chi, c->pmask, c->pz, c->px,
+                           c->pm, c->pv, c->pxeff, c->prox_seg, c->prox_inv, fixed, moved);
+    else
+        hipLaunchKernelGGL(k_prox_init<false>, dim3(c->B), dim3(1024), 0, s, c->N, off, nrows, c->per_res, chi, c->pmask, c->pz, c->px,
+                           c->pm, c->pv, c->pxeff, c->prox_seg, c->prox_inv, nullptr, nullptr);
     // ONE launch per Adam step: [clash + gradient at the current angles -> step t on the workgroup's own residue -> its
     // reconstruction at the new angles, into the other record / axes buffer].  Loss terms are parked per residue and reduced in a
     // fixed order, PP_PROX_CHUNK steps at a time.
@@ -773,13 +788,14 @@ static pp_status prox_loop(pp_ctx *c, const float *chi, float lamda, int nsteps,
 pp_status pp_launch_proximal(pp_ctx *c, const float *chi, float lamda, int nsteps, float *traj, float *chi_last,
                              float *losses, hipStream_t s) {
     // B = 1 (pp_proximal checks it): the whole context is the complex, whatever table a packed context came with
-    return prox_loop(c, chi, lamda, nsteps, nullptr, nullptr, traj, chi_last, losses, s);
+    return prox_loop(c, chi, lamda, nsteps, nullptr, nullptr, nullptr, nullptr, traj, chi_last, losses, s);
 }
 
 pp_status pp_launch_proximal_packed(pp_ctx *c, const float *chi, float lamda, int nsteps, bool norm_given, float *traj,
-                                    float *chi_last, float *chi_accepted, float *losses, hipStream_t s) {
+                                    float *chi_last, float *chi_accepted, float *losses, hipStream_t s, const uint8_t *fixed,
+                                    uint8_t *moved) {
     const int32_t *off = c->packed ? c->seg_off : nullptr;
-    pp_status st = prox_loop(c, chi, lamda, nsteps, off, norm_given ? c->prox_nrows : nullptr, traj, chi_last, losses, s);
+    pp_status st = prox_loop(c, chi, lamda, nsteps, off, norm_given ? c->prox_nrows : nullptr, fixed, moved, traj, chi_last, losses, s);
     if (st != PP_OK) return st;
     const int longest = c->packed ? c->L : c->N;
     hipLaunchKernelGGL(k_prox_accept, dim3((longest * 4 + 255) / 256, c->B), dim3(256), 0, s, c->N, off,

@@ -349,10 +349,13 @@ pp_status pp_launch_atom14(pp_ctx *c, const float *chi, float *xyz, hipStream_t 
 pp_status pp_launch_clash(pp_ctx *c, const float *xyz, float *per_res, float *dchi, hipStream_t s, bool use_candidates = false);
 // One loop for both: pp_launch_proximal is the single-complex call (means over the complex's own rows, losses [nsteps]) without the
 // accept rule; the packed one takes per-complex divisors from c->prox_nrows if norm_given, fills losses [B][nsteps] and chi_accepted.
+// fixed (pp_proximal_pinned, else null; device [N]): rows taken out of the clash mask where it is made; moved (device [N] or null)
+// receives the mask that was optimised.
 pp_status pp_launch_proximal(pp_ctx *c, const float *chi, float lamda, int nsteps, float *traj,
                              float *chi_last, float *losses, hipStream_t s);
 pp_status pp_launch_proximal_packed(pp_ctx *c, const float *chi, float lamda, int nsteps, bool norm_given, float *traj,
-                                    float *chi_last, float *chi_accepted, float *losses, hipStream_t s);
+                                    float *chi_last, float *chi_accepted, float *losses, hipStream_t s,
+                                    const uint8_t *fixed = nullptr, uint8_t *moved = nullptr);
 
 void pp_edge_occupancy(int *node_msg, int *edge_upd);
 

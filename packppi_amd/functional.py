@@ -6,6 +6,8 @@
     proximal_optimizer(batch, SC_D, vtf, tol, lamda, steps)    optimize.py:21-73
     proximal_optimizer_packed(packed_batch, SC_D, ...)        the same for every complex of a batch.pack() batch at once
 
+The three proximal functions take ``fixed_mask`` (partial repacking): rows that keep their incoming angles.
+
 All tensors must live on the MI355X; there is no CPU path here.
 """
 from typing import List, Tuple
@@ -52,27 +54,44 @@ def compute_residue_clash(batch, SC_D, violation_tolerance_factor=12., clash_ove
     return _ctx_for(batch).clash(SC_D, violation_tolerance_factor, clash_overlap_tolerance)
 
 
-def find_clash_mask(batch, SC_D, violation_tolerance_factor, clash_overlap_tolerance):
+def find_clash_mask(batch, SC_D, violation_tolerance_factor, clash_overlap_tolerance, fixed_mask=None):
+    """``fixed_mask`` ([B, L], nonzero = kept): the rows the pinned optimiser moves, the clash mask -- its mean over all rows -- less
+    the kept rows."""
     pr = compute_residue_clash(batch, SC_D, violation_tolerance_factor, clash_overlap_tolerance)
-    return (pr > pr.mean()).unsqueeze(-1).expand(-1, -1, 4)
+    mask = pr > pr.mean()
+    if fixed_mask is not None:
+        mask = mask & ~(torch.as_tensor(fixed_mask).to(pr.device) != 0).reshape(pr.shape)
+    return mask.unsqueeze(-1).expand(-1, -1, 4)
 
 
 def proximal_optimizer(batch, SC_D, violation_tolerance_factor, clash_overlap_tolerance, lamda,
-                       num_steps=50) -> Tuple[List[torch.Tensor], List[float]]:
+                       num_steps=50, fixed_mask=None) -> Tuple[List[torch.Tensor], List[float]]:
+    """``fixed_mask`` ([1, L], nonzero = kept): the pinned optimiser (pp_proximal_pinned); kept rows are ``SC_D`` bit for bit in
+    every entry of the list."""
     assert batch.num_proteins == 1
-    traj, _, losses = _ctx_for(batch).proximal(SC_D, violation_tolerance_factor, clash_overlap_tolerance, lamda,
-                                               num_steps, want_traj=True)
+    ctx = _ctx_for(batch)
+    if fixed_mask is None:
+        traj, _, losses = ctx.proximal(SC_D, violation_tolerance_factor, clash_overlap_tolerance, lamda, num_steps, want_traj=True)
+    else:
+        traj, _, _, losses = ctx.proximal_packed(SC_D, violation_tolerance_factor, clash_overlap_tolerance, lamda, num_steps,
+                                                 want_traj=True, fixed=fixed_mask)
+        losses = losses[0]
     loss_list = [float(v) for v in losses.cpu()]          # the one host sync of the whole optimisation
     return [traj[i] for i in range(num_steps)], loss_list
 
 
 def proximal_optimizer_packed(packed_batch, SC_D, violation_tolerance_factor, clash_overlap_tolerance, lamda, num_steps=50,
-                              norm_rows=None, want_traj=False):
+                              norm_rows=None, want_traj=False, fixed_mask=None, return_moved=False):
     """``proximal_optimizer`` for every complex of a packed batch (``batch.pack``; a B = 1 batch counts as one complex) in the same
     launches, each complex with the reference's per-complex semantics (optimize.py:5-73: its own clash mask, 1/n, loss list) and
     the accept rule of TDiffusionModule.sampling (TorsionalDiffusion.py:296-298) decided on the device.  ``norm_rows``: the row
     count each complex's means divide by (None: its packed length; its padded ``max_size`` reproduces the run on the padded
     batch, whose padding rows pack() dropped).  Returns (trajectory [num_steps, 1, N, 4] or None, last [1, N, 4],
-    accepted [1, N, 4], losses [n_complexes, num_steps]), all left on the device."""
+    accepted [1, N, 4], losses [n_complexes, num_steps]), all left on the device.
+
+    ``fixed_mask`` ([1, N], nonzero = kept; pp_proximal_pinned): kept rows leave the clash mask, whose mean stays over all rows of
+    the complex, and come out as ``SC_D`` bit for bit; all zero gives the bits of the call without it.  ``return_moved`` appends
+    the mask that was optimised (bool [1, N])."""
     return _ctx_for(packed_batch).proximal_packed(SC_D, violation_tolerance_factor, clash_overlap_tolerance, lamda, num_steps,
-                                                  norm_rows=norm_rows, want_traj=want_traj)
+                                                  norm_rows=norm_rows, want_traj=want_traj, fixed=fixed_mask,
+                                                  return_moved=return_moved)

@@ -21,7 +21,7 @@ SYMBOLS = ("pp_version", "pp_last_error", "pp_build_id", "pp_plan_set_knn_ties",
            "pp_affinity_create", "pp_affinity_destroy", "pp_affinity_encode", "pp_affinity_predict",
            "pp_score_rows", "pp_so2_set_grids", "pp_so2_score", "pp_dsm_loss",
            "pp_ctx_set_rng_keys", "pp_noise_seeded", "pp_add_noise_seeded", "pp_sample_seeded",
-           "pp_sample_partial")
+           "pp_sample_partial", "pp_proximal_pinned")
 
 
 FIX_MODES = {"hold": 0, "renoise": 1}         # PP_FIX_HOLD, PP_FIX_RENOISE
@@ -121,6 +121,7 @@ def load():
     lib.pp_add_noise_seeded.argtypes = [vp, vp, f, C.c_uint64, vp, vp]
     lib.pp_sample_seeded.argtypes = [vp, vp, vp, i, i, C.c_uint64, vp]
     lib.pp_sample_partial.argtypes = [vp, vp, vp, vp, i, vp, i, i, C.c_uint64, vp, vp]
+    lib.pp_proximal_pinned.argtypes = [vp, vp, vp, f, i, vp, vp, vp, vp, vp, vp, vp]
     _lib = lib
     return lib
 
@@ -497,13 +498,19 @@ class Context:
                                   _ptr(losses), _stream(self.plan.device)), "pp_proximal")
         return traj, last, losses
 
-    def proximal_packed(self, chi, vtf, tol, lamda, num_steps, norm_rows=None, want_traj=False):
+    def proximal_packed(self, chi, vtf, tol, lamda, num_steps, norm_rows=None, want_traj=False, fixed=None, return_moved=False):
         """proximal_optimizer for every complex of a packed batch at once (a B = 1 batch counts as one complex): each complex with its
         own clash mask, 1/n, losses and accept rule.  The same loop as ``proximal``, which is its one-complex case: a complex gets the
         bits it gets alone.  ``norm_rows`` (one int per complex, or
         None = the complexes' lengths): the row count each complex's means divide by; pass the padded ``max_size`` to reproduce the
         run on a padded batch.  Returns (traj [num_steps, 1, N, 4] or None, last [1, N, 4], accepted [1, N, 4],
-        losses [n_complexes, num_steps]), all on the device; no host synchronisation."""
+        losses [n_complexes, num_steps]), all on the device; no host synchronisation.
+
+        ``fixed`` ([1, N] bool / uint8, as in ``sample_partial``; pp_proximal_pinned): rows with ``fixed`` != 0 are
+        taken out of the clash mask -- its mean stays over all rows -- and come out as ``chi`` bit for bit; with ``return_moved`` the
+        mask that was optimised (bool [1, N]) is appended to the tuple."""
+        if return_moved and fixed is None:
+            raise ValueError("return_moved needs fixed: the unpinned call does not report its mask (functional.find_clash_mask does)")
         self.plan.set_clash_params(vtf, tol)
         offs = self.seg_offsets_host if self.seg_offsets_host is not None else [0, self.L]
         n_seg = len(offs) - 1 if self.B == 1 else self.B
@@ -521,10 +528,19 @@ class Context:
         traj = self._new(num_steps, self.B, self.L, 4) if want_traj else None
         last, accepted = self._new(self.B, self.L, 4), self._new(self.B, self.L, 4)
         losses = self._new(n_seg, max(int(num_steps), 1))
-        _check(load().pp_proximal_packed(self.handle, _ptr(chi), float(lamda), int(num_steps),
-                                         C.c_void_p(nr.ctypes.data) if nr is not None else C.c_void_p(0), _ptr(traj), _ptr(last),
-                                         _ptr(accepted), _ptr(losses), _stream(self.plan.device)), "pp_proximal_packed")
-        return traj, last, accepted, losses
+        nrp = C.c_void_p(nr.ctypes.data) if nr is not None else C.c_void_p(0)
+        if fixed is None:
+            _check(load().pp_proximal_packed(self.handle, _ptr(chi), float(lamda), int(num_steps), nrp, _ptr(traj), _ptr(last),
+                                             _ptr(accepted), _ptr(losses), _stream(self.plan.device)), "pp_proximal_packed")
+            return traj, last, accepted, losses
+        fx = torch.as_tensor(fixed).to(device=self.plan.device)
+        if fx.numel() != self.n_rows:
+            raise ValueError(f"fixed has {fx.numel()} elements, this context has {self.n_rows} rows")
+        fx = (fx != 0).to(torch.uint8).reshape(-1).contiguous()
+        moved = self._new(self.B, self.L, dtype=torch.uint8) if return_moved else None
+        _check(load().pp_proximal_pinned(self.handle, _ptr(chi), _ptr(fx), float(lamda), int(num_steps), nrp, _ptr(traj), _ptr(last),
+                                         _ptr(accepted), _ptr(losses), _ptr(moved), _stream(self.plan.device)), "pp_proximal_pinned")
+        return (traj, last, accepted, losses, moved.bool()) if return_moved else (traj, last, accepted, losses)
 
     def saturated(self) -> int:
         """Sticky flag word of this context: 0 = clean; bit 0 / bit 1 = a hidden activation was clamped at 65504 in an edge-level /

@@ -302,8 +302,8 @@ class TDiffusionModule:
             if sde_noise is not None:
                 raise ValueError("fixed_mask and sde_noise exclude each other: partial repacking draws its own noise")
             if use_proximal:
-                raise ValueError("fixed_mask with use_proximal=True is not supported: the proximal stage has no pin and would move "
-                                 "the fixed rows (out of scope of partial repacking)")
+                raise ValueError("fixed_mask with use_proximal=True is not supported here: this proximal stage has no pin and would "
+                                 "move the fixed rows; repack(batch, fixed_mask, seed=..., use_proximal=True) runs the pinned one")
             from .lib import FIX_MODES
             if fixed_mode not in FIX_MODES:
                 raise ValueError(f"fixed_mode must be one of {sorted(FIX_MODES)}")
@@ -351,6 +351,34 @@ class TDiffusionModule:
         if loss_list[-1] < loss_list[0]:
             return SC_D_resample_list[-1]
         return SC_D_sample
+
+    def repack(self, batch, fixed_mask=None, *, seed, fixed_chi=None, fixed_mode="renoise", use_proximal: bool = False,
+               return_list: bool = False, norm_rows=None):
+        """Partial repacking in one call (DESIGN.md sections 13 and 14): ``sampling(batch, seed=seed, fixed_mask=...)`` -- the rows
+        of ``fixed_mask`` (default ``batch.fixed_mask``) keep ``fixed_chi`` (default ``batch.SC_D``), the others are sampled around
+        them -- and then, with ``use_proximal``, the PINNED proximal stage (pp_proximal_pinned): the clash mask of every complex, its
+        mean over all of the complex's rows, less the kept rows; the accept rule of ``sampling`` per complex, on the device.  A B = 1
+        batch or a packed one (``batch.pack``); ``norm_rows`` as in ``functional.proximal_optimizer_packed`` (the sharded driver passes
+        the padded sizes).  Kept rows of the result are ``fixed_chi`` bit for bit with or without the proximal stage.
+        ``return_list`` (B = 1, with ``use_proximal``): (sample, per-step angles, losses) as ``sampling`` returns them."""
+        if fixed_mask is None:
+            fixed_mask = batch.get("fixed_mask") if hasattr(batch, "get") else getattr(batch, "fixed_mask", None)
+        if fixed_mask is None:
+            raise ValueError("repack needs fixed_mask (or a batch that carries one); sampling() samples every row")
+        packed = batch.get("seg_offsets") is not None if hasattr(batch, "get") else False
+        if return_list and (packed or not use_proximal):
+            raise ValueError("return_list=True needs use_proximal=True and a B = 1 batch; for a packed batch use "
+                             "functional.proximal_optimizer_packed (per-complex losses [n_complexes, num_steps])")
+        cfg = self.hparams.sample_cfg
+        SC_D_sample = self.sampling(batch, seed=seed, fixed_mask=fixed_mask, fixed_chi=fixed_chi, fixed_mode=fixed_mode)
+        if not use_proximal:
+            return SC_D_sample
+        traj, _, accepted, losses = proximal_optimizer_packed(batch, SC_D_sample, cfg.violation_tolerance_factor,
+                                                              cfg.clash_overlap_tolerance, cfg.lamda, cfg.num_steps,
+                                                              norm_rows=norm_rows, want_traj=return_list, fixed_mask=fixed_mask)
+        if return_list:
+            return SC_D_sample, [traj[i] for i in range(cfg.num_steps)], [float(v) for v in losses[0].cpu()]
+        return accepted
 
     def sample_from(self, batch, SC_D_init, sde_noise=None):
         """The reverse-diffusion loop of ``sampling`` from given initial noised angles (parity runs inject the reference's

@@ -102,8 +102,16 @@ def _with_key(batch, key):
     return out
 
 
+def _with_mask(batch, key, mask):
+    """``_with_key`` plus the rows partial repacking keeps (``fixed_mask``, [1, L]; ``batch.pack`` carries both)."""
+    out = _with_key(batch, key)
+    out["complex_key"] = int(key)
+    out["fixed_mask"] = (torch.as_tensor(mask).to(batch["X"].device) != 0).reshape(1, -1)
+    return out
+
+
 def sample_sharded(model, complexes, use_proximal=False, group=None, init_chi=None, max_rows=200_000, lengths=None,
-                   rank=None, world=None, packed_proximal=True, seed=None):
+                   rank=None, world=None, packed_proximal=True, seed=None, fixed_masks=None):
     """Run the sampling path on this rank's share of ``complexes`` (list of B = 1 batches already on the rank's device)
     and gather every complex's metric row on every rank.  With ``lengths`` (the residue counts of ALL complexes, known to
     every rank) ``complexes`` may be a dict {complex id: batch} that holds only this rank's share -- a rank need not build
@@ -120,11 +128,17 @@ def sample_sharded(model, complexes, use_proximal=False, group=None, init_chi=No
     ``seed`` (optional): all noise comes from the device generator (``TDiffusionModule.sampling(seed=...)``) and the key of every
     complex is its global id, in packed groups and single-complex groups alike: a complex's sample does not depend on
     ``world``, ``rank``, ``max_rows`` or what it was grouped with.  ``seed`` and ``init_chi`` exclude each other.
+    ``fixed_masks`` (optional, {complex id: [1, L] mask} or a list, 1 = keep; needs ``seed``): partial repacking -- every group goes
+    through ``TDiffusionModule.repack`` with the global ids as keys, the kept rows come out as the complex's ``SC_D`` bit for bit,
+    and the proximal stage is the pinned one (one call per packed group with the padded sizes, or one per complex), with the same
+    independence of ``world``, ``rank``, ``max_rows`` and grouping.
     Returns (chi per local complex id, ids_all, rows_all)."""
     from .batch import pack, unpack
     from .functional import proximal_optimizer, proximal_optimizer_packed
     if seed is not None and init_chi is not None:
         raise ValueError("seed and init_chi exclude each other: a seeded run draws its own initial angles")
+    if fixed_masks is not None and seed is None:
+        raise ValueError("fixed_masks needs seed: partial repacking draws its noise from the seeded device generator")
     if rank is None:
         rank = dist.get_rank(group) if dist.is_initialized() else 0
     if world is None:
@@ -150,7 +164,27 @@ def sample_sharded(model, complexes, use_proximal=False, group=None, init_chi=No
     if cur:
         groups.append(cur)
     chis, row_of, proxed = {}, {}, set()
+    cfg_prox = (cfg.violation_tolerance_factor, cfg.clash_overlap_tolerance, cfg.lamda, cfg.num_steps)
     for grp in groups:
+        if fixed_masks is not None:       # partial repacking: the pinned sampler, then the pinned proximal stage
+            if len(grp) == 1:
+                i = grp[0]
+                chis[i] = model.repack(_with_mask(complexes[i], i, fixed_masks[i]), seed=seed, use_proximal=use_proximal)
+                proxed.add(i)
+                continue
+            pb = pack([_with_mask(complexes[i], i, fixed_masks[i]) for i in grp])
+            sizes = [int(complexes[i]["max_size"]) for i in grp]
+            out = model.repack(pb, seed=seed, use_proximal=use_proximal and packed_proximal, norm_rows=sizes)
+            if not use_proximal:
+                for i, row in zip(grp, packed_metric_rows(model, pb, out, sizes)):
+                    row_of[i] = row
+            elif packed_proximal:
+                proxed.update(grp)
+            for i, chi in zip(grp, unpack(pb, out)):
+                full = torch.zeros(1, int(complexes[i]["max_size"]), 4, device=chi.device, dtype=chi.dtype)
+                full[:, :chi.shape[1]] = chi
+                chis[i] = full
+            continue
         if len(grp) == 1:
             i = grp[0]
             if init_chi is not None:
@@ -187,7 +221,9 @@ def sample_sharded(model, complexes, use_proximal=False, group=None, init_chi=No
                 chis[i] = full
     rows = []
     for i in mine:
-        if use_proximal and i not in proxed:
+        if use_proximal and i not in proxed and fixed_masks is not None:      # the per-complex pinned call, accept rule on the device
+            chis[i] = proximal_optimizer_packed(complexes[i], chis[i], *cfg_prox, fixed_mask=fixed_masks[i])[2]
+        elif use_proximal and i not in proxed:
             lst, losses = proximal_optimizer(complexes[i], chis[i], cfg.violation_tolerance_factor,
                                              cfg.clash_overlap_tolerance, cfg.lamda, cfg.num_steps)
             if losses[-1] < losses[0]:
