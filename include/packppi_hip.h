@@ -141,6 +141,9 @@ pp_status pp_topk_aten_host(const float *values, int n, int k, int32_t *idx_out)
 /* Replaces the timestep-invariant part of ProteinEncoder.forward (encoder.py:198-246):
  * kNN graph, 468-d edge features, edge embedding + LayerNorm, backbone frames.  The batch
  * pointers must stay valid for the lifetime of the ctx.
+ * The complexes of a padded batch [B][L] are its B rows, padding rows included: the ctx describes them by the same kind
+ * of segment table a packed ctx has (below), here 0, L, 2L ..., which it writes itself.  Every per-complex quantity (noise
+ * keys, loss segments, proximal means) is computed from that table by the same code for both kinds of ctx.
  * A ctx keeps all its device workspaces in one allocation that pp_ctx_destroy hands back to the plan
  * (a pool of up to four) instead of freeing it: creating a ctx per batch costs no hipMalloc/hipFree.
  * pp_ctx_destroy does not wait for work already enqueued on the ctx's stream; the next ctx that takes
@@ -151,7 +154,8 @@ void pp_ctx_destroy(pp_ctx *ctx);
 
 /* The same for complexes of different lengths WITHOUT the padding rows of collate_fn
  * (complex_datamodule.py:196-226): the batch tensors are [1, sum of lengths, ...] with the complexes'
- * rows back to back, `seg_offsets` (DEVICE, int32 [n_seg + 1], caller-owned like the batch) gives the first
+ * rows back to back, `seg_offsets` (DEVICE, int32 [n_seg + 1], caller-owned like the batch; the ctx keeps a copy, the
+ * caller's need not outlive the stream work of this call) gives the first
  * row of every complex and the total, min_len / max_len their shortest and longest length.  Neighbour
  * search, clash partners and E_idx numbering stay inside each complex; every other stage is per row or per
  * edge.  Results equal those of each complex prepared on its own (K = min(32, length): complexes shorter

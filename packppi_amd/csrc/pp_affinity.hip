@@ -30,9 +30,8 @@ k_affinity_head(const float *__restrict__ h_wt, const float *__restrict__ h_mt, 
     __shared__ float red[2][2][128];     // [half][direction][feature]
     __shared__ float act[2][2][128];     // [direction][ping-pong][feature]
     const int s = blockIdx.x, t = threadIdx.x, f = t & 127, half = t >> 7;
-    int a = seg_off[s], b = seg_off[s + 1];
-    a = a < 0 ? 0 : (a > n_rows ? n_rows : a);
-    b = b < a ? a : (b > n_rows ? n_rows : b);
+    int a, b;
+    pp_seg_rows(seg_off, s, n_rows, a, b);
     float m_fwd = -INFINITY, m_inv = -INFINITY;
     for (int r = a + half; r < b; r += 2) {
         const float w = h_wt[(size_t)r * 128 + f], m = h_mt[(size_t)r * 128 + f];

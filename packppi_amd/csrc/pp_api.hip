@@ -332,27 +332,18 @@ extern "C" void pp_ctx_destroy(pp_ctx *c) {
     delete c;
 }
 
-// (first row, length) of the complex every row belongs to: a padded batch [B][L] ...
-__global__ void k_fill_seg(int2 *__restrict__ seg, int N, int L) {
-    const int n = blockIdx.x * blockDim.x + threadIdx.x;
-    if (n < N) seg[n] = make_int2((n / L) * L, L);
+// the table of a padded batch [B][L]: complex s is rows s * L .. s * L + L - 1
+__global__ void k_seg_uniform(int32_t *__restrict__ off, int n_seg, int L) {
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s <= n_seg) off[s] = s * L;
 }
-// ... or complexes packed back to back, rows off[s] .. off[s + 1] - 1 (pp_complex_prepare_packed)
-__global__ void k_fill_seg_packed(int2 *__restrict__ seg, int N, const int32_t *__restrict__ off, int n_seg, int max_len) {
+// (first row, length) of the complex every row belongs to, from the context's table (pp_segments.h pp_seg_fill: on the uniform
+// table of a padded batch its clamps are no-ops and this is ((n / L) * L, L))
+__global__ void k_fill_seg(int2 *__restrict__ seg, int N, const int32_t *__restrict__ off, int n_seg, int max_len) {
     const int n = blockIdx.x * blockDim.x + threadIdx.x;
     if (n >= N) return;
-    int lo = 0, hi = n_seg - 1;                   // last s with off[s] <= n
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (off[mid] <= n) lo = mid; else hi = mid - 1;
-    }
-    // the launches are sized by the caller's max_len (LDS of the neighbour search): a segment table that disagrees with it
-    // is clamped to stay inside the batch and the LDS, its results are meaningless
-    int start = off[lo], len = off[lo + 1] - off[lo];
-    start = start < 0 ? 0 : (start > n ? n : start);
-    len = len > max_len ? max_len : len;
-    if (start + len > N) len = N - start;
-    if (n >= start + len) len = n - start + 1 <= max_len ? n - start + 1 : max_len;
+    int start, len;
+    pp_seg_fill(off, n_seg, N, max_len, n, start, len);
     seg[n] = make_int2(start, len);
 }
 
@@ -416,7 +407,7 @@ static pp_status prepare_impl(pp_plan *plan, const pp_batch *b, const int32_t *s
     ALLOC(seg, N);
     ALLOC(prox_part, (size_t)PP_PROX_CHUNK * N);
     if (prox) { ALLOC(prox_nrows, c->B); ALLOC(prox_seg, c->B); ALLOC(prox_inv, N); }
-    if (packed) ALLOC(seg_off, (size_t)n_seg + 1);
+    ALLOC(seg_off, (size_t)c->B + 1);
     ALLOC(rng_tab, N); ALLOC(rng_keys, c->B);
     c->max_steps = 1 << 20;
 #undef ALLOC
@@ -442,12 +433,16 @@ static pp_status prepare_impl(pp_plan *plan, const pp_batch *b, const int32_t *s
     char *base = static_cast<char *>(c->arena);
     for (const Slot &sl : slots) { *sl.p = base; base += sl.bytes; }
     hipStream_t s_ = static_cast<hipStream_t>(stream);
-    if (packed) hipLaunchKernelGGL(k_fill_seg_packed, dim3((c->N + 255) / 256), dim3(256), 0, s_, c->seg, c->N, seg_offsets, n_seg, c->L);
-    else hipLaunchKernelGGL(k_fill_seg, dim3((c->N + 255) / 256), dim3(256), 0, s_, c->seg, c->N, c->L);
+    // the context's segment table, before anything reads it: a copy of the caller's (which need not outlive this call's stream
+    // work), or 0, L, 2L ... written on the device -- nothing is staged, nothing waits
+    if (packed) {
+        if (hipMemcpyAsync(c->seg_off, seg_offsets, ((size_t)n_seg + 1) * sizeof(int32_t), hipMemcpyDeviceToDevice, s_) != hipSuccess)
+            FAIL(PP_ERR_HIP, "copying the segment offsets failed");
+    } else {
+        hipLaunchKernelGGL(k_seg_uniform, dim3((c->B + 256) / 256), dim3(256), 0, s_, c->seg_off, c->B, c->L);
+    }
+    hipLaunchKernelGGL(k_fill_seg, dim3((c->N + 255) / 256), dim3(256), 0, s_, c->seg, c->N, c->seg_off, c->B, c->L);
     if (hipGetLastError() != hipSuccess) FAIL(PP_ERR_HIP, "segment table launch failed");
-    // the complexes' first rows, kept for pp_proximal_packed (the caller's table need not outlive this call's stream work)
-    if (packed && hipMemcpyAsync(c->seg_off, seg_offsets, ((size_t)n_seg + 1) * sizeof(int32_t), hipMemcpyDeviceToDevice, s_) != hipSuccess)
-        FAIL(PP_ERR_HIP, "copying the segment offsets failed");
     if (hipMemsetAsync(c->sat, 0, 4 * sizeof(unsigned), s_) != hipSuccess) FAIL(PP_ERR_HIP, "clearing the saturation word failed");
     if (net) {
         pp_status st;
@@ -508,14 +503,12 @@ extern "C" pp_status pp_ctx_set_graph(pp_ctx *c, const int64_t *E_idx, void *str
 // per-step scalars (schedule.py:165-174,198-235; layers.py:257-268), fp32 like the reference's tensors
 // sigma(t) in fp32 (TorsionalDiffusion.py:84-88): fill_step, the initial noising and the re-noising of pp_sample_partial share it
 static float sigma_f32(float t) {
-    const double PI_D = 3.14159265358979323846;
-    const double lo = log(0.01 * PI_D), hi = log(PI_D);
+    const double lo = pp_log_sigma_min(), hi = pp_log_sigma_max();
     return expf((float)lo + (float)(hi - lo) * t);
 }
 
 static void fill_step(StepParams *sp, float t, float dt, float T) {
-    const double PI_D = 3.14159265358979323846;
-    const double lo = log(0.01 * PI_D), hi = log(PI_D);
+    const double PI_D = PP_PI_D, hi = pp_log_sigma_max();
     memset(sp, 0, sizeof(*sp));
     // sinusoidal embedding of t * 10000
     const float ts = t * 10000.0f;
@@ -810,9 +803,9 @@ static pp_status proximal_packed_impl(const char *who, pp_ctx *c, const float *c
     if (num_steps < 1) FAIL(PP_ERR_INVALID, w + ": num_steps must be >= 1");
     if (!c->plan->clash_params_set) FAIL(PP_ERR_INVALID, w + ": call pp_plan_set_clash_params first");
     if (!c->b.atom_mask || !c->b.residue_index) FAIL(PP_ERR_INVALID, w + ": batch lacks atom_mask / residue_index");
-    // every complex is at least min_len rows long (for a B = 1 context: N): an entry below that is shorter than its complex for sure
-    // (the exact lengths are on the device only; the kernels take max(entry, length))
-    const int shortest = c->packed ? c->shortest : c->N;
+    // every complex is at least c->shortest rows long (min_len; for an unpacked B = 1 context: N): an entry below that is shorter
+    // than its complex for sure (the exact lengths are on the device only; the kernels take max(entry, length))
+    const int shortest = c->shortest;
     if (norm_rows)
         for (int s = 0; s < c->B; s++)
             if (norm_rows[s] < shortest)

@@ -575,15 +575,7 @@ k_clash_cand(int N, const int2 *__restrict__ seg, const float *__restrict__ X, c
 // ---------------------------------------------------------------------------------------------
 // proximal optimiser pieces: per complex (segment) of the context.  pp_proximal is the one-segment case of pp_proximal_packed.
 // ---------------------------------------------------------------------------------------------
-// Rows [row0, row1) of complex s: off[s], off[s + 1] of the packed table (off == nullptr: one complex, rows 0 .. N - 1, a B = 1
-// context); a table that breaks the contract of pp_complex_prepare_packed is clamped to stay inside the batch.
-__device__ __forceinline__ void seg_rows(const int32_t *__restrict__ off, int s, int N, int &row0, int &row1) {
-    row0 = off ? off[s] : 0;
-    row1 = off ? off[s + 1] : N;
-    row0 = row0 < 0 ? 0 : (row0 > N ? N : row0);
-    row1 = row1 < row0 ? row0 : (row1 > N ? N : row1);
-}
-
+// off is the context's segment table (pp_ctx::seg_off; an unpacked B = 1 context: 0, N); complex s has the rows pp_seg_rows gives.
 // For complex s = blockIdx.x, in its own row coordinates: mean of per_res; mask[g] = per_res[g] > mean; z = chi * mask; x = z;
 // m = v = 0; xeff = chi.  The divisor of the complex's means is n = max(nrows[s], its length) (nrows == nullptr: the length).  Also
 // writes (n, 1 / n) to seg_norm[s] (k_prox_losses) and 1 / n to inv_row of every row of the complex (k_clash<CAND, true>).
@@ -606,7 +598,7 @@ k_prox_init(int N, const int32_t *__restrict__ off, const int32_t *__restrict__ 
     __shared__ float s_part[16];
     __shared__ float s_mean;
     int row0, row1;
-    seg_rows(off, blockIdx.x, N, row0, row1);
+    pp_seg_rows(off, blockIdx.x, N, row0, row1);
     const int len = row1 - row0;
     int n = nrows ? nrows[blockIdx.x] : len;
     n = n > len ? n : len;
@@ -657,7 +649,7 @@ k_prox_losses(int N, const int32_t *__restrict__ off, const float2 *__restrict__
     __shared__ float s_tt[256];
     const int t = blockIdx.x, sg = blockIdx.y;
     int row0, row1;
-    seg_rows(off, sg, N, row0, row1);
+    pp_seg_rows(off, sg, N, row0, row1);
     const int len = row1 - row0;
     const float *p = part + (size_t)t * N + row0;
     const int ngroups = (len + 15) / 16;
@@ -685,7 +677,7 @@ k_prox_accept(int N, const int32_t *__restrict__ off, const float *__restrict__ 
               const float *__restrict__ last, float *__restrict__ out) {
     const int s = blockIdx.y;
     int row0, row1;
-    seg_rows(off, s, N, row0, row1);
+    pp_seg_rows(off, s, N, row0, row1);
     const int e = blockIdx.x * 256 + threadIdx.x;
     if (e >= (row1 - row0) * 4) return;
     const float *ls = losses + (size_t)s * nsteps;
@@ -721,10 +713,10 @@ pp_status pp_launch_clash(pp_ctx *c, const float *xyz, float *per_res, float *dc
     return PP_OK;
 }
 
-// The proximal loop, per complex of the context: each has its own clash mask mean, 1 / n and loss row (losses [B][nsteps]).  off:
-// the device table of first rows, or nullptr = the context is one complex, rows 0 .. N - 1 (its losses are row 0).  fixed (device
-// [N], or nullptr = no pin): rows kept out of the clash mask (k_prox_init<true>); moved (device [N] or nullptr) receives that mask.
-static pp_status prox_loop(pp_ctx *c, const float *chi, float lamda, int nsteps, const int32_t *off, const int32_t *nrows,
+// The proximal loop, per complex of the context: each has its own clash mask mean, 1 / n and loss row (losses [B][nsteps]), its
+// rows from the context's segment table (a B = 1 context is one complex, its losses are row 0).  fixed (device [N], or nullptr =
+// no pin): rows kept out of the clash mask (k_prox_init<true>); moved (device [N] or nullptr) receives that mask.
+static pp_status prox_loop(pp_ctx *c, const float *chi, float lamda, int nsteps, const int32_t *nrows,
                            const uint8_t *fixed, uint8_t *moved, float *traj, float *chi_last, float *losses, hipStream_t s) {
     pp_status st;
     const pp_plan *p = c->plan;
@@ -738,10 +730,10 @@ static pp_status prox_loop(pp_ctx *c, const float *chi, float lamda, int nsteps,
     if ((st = pp_launch_atom14(c, chi, c->xyz, s)) != PP_OK) return st;
     if ((st = pp_launch_clash(c, c->xyz, c->per_res, nullptr, s, cands)) != PP_OK) return st;
     if (fixed)
-        hipLaunchKernelGGL(k_prox_init<true>, dim3(c->B), dim3(1024), 0, s, c->N, off, nrows, c->per_res, chi, c->pmask, c->pz, c->px,
+        hipLaunchKernelGGL(k_prox_init<true>, dim3(c->B), dim3(1024), 0, s, c->N, c->seg_off, nrows, c->per_res, chi, c->pmask, c->pz, c->px,
                            c->pm, c->pv, c->pxeff, c->prox_seg, c->prox_inv, fixed, moved);
     else
-        hipLaunchKernelGGL(k_prox_init<false>, dim3(c->B), dim3(1024), 0, s, c->N, off, nrows, c->per_res, chi, c->pmask, c->pz, c->px,
+        hipLaunchKernelGGL(k_prox_init<false>, dim3(c->B), dim3(1024), 0, s, c->N, c->seg_off, nrows, c->per_res, chi, c->pmask, c->pz, c->px,
                            c->pm, c->pv, c->pxeff, c->prox_seg, c->prox_inv, nullptr, nullptr);
     // ONE launch per Adam step: [clash + gradient at the current angles -> step t on the workgroup's own residue -> its
     // reconstruction at the new angles, into the other record / axes buffer].  Loss terms are parked per residue and reduced in a
@@ -778,7 +770,7 @@ static pp_status prox_loop(pp_ctx *c, const float *chi, float lamda, int nsteps,
         std::swap(rec_in, rec_out);
         std::swap(axes_in, axes_out);
         if (U.t == PP_PROX_CHUNK - 1 || t == nsteps - 1)
-            hipLaunchKernelGGL(k_prox_losses, dim3(U.t + 1, c->B), dim3(256), 0, s, c->N, off, c->prox_seg, c->prox_part, nsteps,
+            hipLaunchKernelGGL(k_prox_losses, dim3(U.t + 1, c->B), dim3(256), 0, s, c->N, c->seg_off, c->prox_seg, c->prox_part, nsteps,
                                t - U.t, losses);
     }
     PP_HIP_CHECK(hipGetLastError());
@@ -787,18 +779,16 @@ static pp_status prox_loop(pp_ctx *c, const float *chi, float lamda, int nsteps,
 
 pp_status pp_launch_proximal(pp_ctx *c, const float *chi, float lamda, int nsteps, float *traj, float *chi_last,
                              float *losses, hipStream_t s) {
-    // B = 1 (pp_proximal checks it): the whole context is the complex, whatever table a packed context came with
-    return prox_loop(c, chi, lamda, nsteps, nullptr, nullptr, nullptr, nullptr, traj, chi_last, losses, s);
+    // B = 1 (pp_proximal checks it): the one-complex case
+    return prox_loop(c, chi, lamda, nsteps, nullptr, nullptr, nullptr, traj, chi_last, losses, s);
 }
 
 pp_status pp_launch_proximal_packed(pp_ctx *c, const float *chi, float lamda, int nsteps, bool norm_given, float *traj,
                                     float *chi_last, float *chi_accepted, float *losses, hipStream_t s, const uint8_t *fixed,
                                     uint8_t *moved) {
-    const int32_t *off = c->packed ? c->seg_off : nullptr;
-    pp_status st = prox_loop(c, chi, lamda, nsteps, off, norm_given ? c->prox_nrows : nullptr, fixed, moved, traj, chi_last, losses, s);
+    pp_status st = prox_loop(c, chi, lamda, nsteps, norm_given ? c->prox_nrows : nullptr, fixed, moved, traj, chi_last, losses, s);
     if (st != PP_OK) return st;
-    const int longest = c->packed ? c->L : c->N;
-    hipLaunchKernelGGL(k_prox_accept, dim3((longest * 4 + 255) / 256, c->B), dim3(256), 0, s, c->N, off,
+    hipLaunchKernelGGL(k_prox_accept, dim3((c->L * 4 + 255) / 256, c->B), dim3(256), 0, s, c->N, c->seg_off,
                        losses, nsteps, chi, chi_last, chi_accepted);
     PP_HIP_CHECK(hipGetLastError());
     return PP_OK;

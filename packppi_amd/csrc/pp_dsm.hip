@@ -133,16 +133,15 @@ extern "C" pp_status pp_so2_score(const float *x, const float *sigma, size_t n, 
 // One 256-thread workgroup per segment.  Thread t takes elements t, t + 256, ... of the segment's [rows][4] block, then the 256
 // partial sums meet in a binary tree in LDS: the order of every addition is fixed, two runs give the same bits.
 __global__ void __launch_bounds__(256)
-k_dsm_loss(int N, int L, const int32_t *__restrict__ seg_off, const float *__restrict__ pred, const float *__restrict__ target,
+k_dsm_loss(int N, const int32_t *__restrict__ seg_off, const float *__restrict__ pred, const float *__restrict__ target,
            const float *__restrict__ t_rows, const float *__restrict__ sc_mask, const uint8_t *__restrict__ m1pi,
            const double *__restrict__ score_norm, So2Consts k1, So2Consts k2, float sig_lo, float sig_span,
            double *__restrict__ num, double *__restrict__ den) {
 #pragma clang fp contract(off)
     __shared__ double red[2][256];
     const int s = blockIdx.x, tid = threadIdx.x;
-    int a = seg_off ? seg_off[s] : s * L, b = seg_off ? seg_off[s + 1] : (s + 1) * L;
-    a = a < 0 ? 0 : (a > N ? N : a);
-    b = b < a ? a : (b > N ? N : b);
+    int a, b;
+    pp_seg_rows(seg_off, s, N, a, b);
     double sn_acc = 0.0, sd_acc = 0.0;
     for (int e = 4 * a + tid; e < 4 * b; e += 256) {
         const int n = e >> 2;
@@ -175,11 +174,9 @@ extern "C" pp_status pp_dsm_loss(pp_ctx *c, const float *pred_score, const float
     if (!c || !pred_score || !target_score || !t_rows || !score_norm || !num || !den) FAIL(PP_ERR_INVALID, "pp_dsm_loss: null argument");
     if (!c->b.SC_D_mask || !c->b.chi_1pi_periodic_mask) FAIL(PP_ERR_INVALID, "pp_dsm_loss: the batch of this ctx has no SC_D_mask / chi_1pi_periodic_mask");
     PP_HIP_CHECK(hipSetDevice(c->plan->device));
-    const double PI_D = 3.14159265358979323846;
-    const double lo = log(0.01 * PI_D), hi = log(PI_D);
-    hipLaunchKernelGGL(k_dsm_loss, dim3(c->B), dim3(256), 0, static_cast<hipStream_t>(stream), c->N, c->L,
-                       c->packed ? c->seg_off : nullptr, pred_score, target_score, t_rows, c->b.SC_D_mask, c->b.chi_1pi_periodic_mask,
-                       score_norm, so2_consts(1), so2_consts(0), (float)lo, (float)(hi - lo), num, den);
+    const double lo = pp_log_sigma_min(), hi = pp_log_sigma_max();
+    hipLaunchKernelGGL(k_dsm_loss, dim3(c->B), dim3(256), 0, static_cast<hipStream_t>(stream), c->N, c->seg_off,
+                       pred_score, target_score, t_rows, c->b.SC_D_mask, c->b.chi_1pi_periodic_mask, score_norm, so2_consts(1), so2_consts(0), (float)lo, (float)(hi - lo), num, den);
     PP_HIP_CHECK(hipGetLastError());
     return PP_OK;
 }

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
+#include <cmath>
 #include <vector>
 #include <mutex>
 #include <stdint.h>
@@ -48,6 +49,7 @@
 
 #include "pp_weights.h"      // LayerOff / WeightOff / pp_weight_offsets(): offsets into the concatenated weight buffer
 #include "pp_rng.h"          // Philox4x32-10 and the normal transform of the seeded sampling noise (counter layout there)
+#include "pp_segments.h"     // pp_seg_of_row / pp_seg_rows: the arithmetic of the context's segment table (pp_ctx::seg_off)
 
 // Transposed ([in][out]) copies used by the node-level (VALU) kernels, per layer.
 struct LayerT {
@@ -117,6 +119,12 @@ struct pp_plan {
     bool clash_params_set;
 };
 
+// log sigma_min, log sigma_max of t_to_sigma (schedule.py:165-174; sigma from 0.01 pi to pi) in fp64: sigma(t), the step scalars
+// and the loss round them to fp32 the same way, (float)lo + (float)(hi - lo) * t
+#define PP_PI_D 3.14159265358979323846
+static inline double pp_log_sigma_min() { return log(0.01 * PP_PI_D); }
+static inline double pp_log_sigma_max() { return log(PP_PI_D); }
+
 // Per-step scalars of the reverse process, computed on the host (schedule.py:198-235) and handed to the kernels as arguments.
 struct StepParams {
     float temb[16];     // sinusoidal embedding of t
@@ -130,10 +138,13 @@ struct StepParams {
 struct pp_ctx {
     pp_plan *plan;
     pp_batch b;               // caller-owned device pointers
-    int B, L, K, N;           // N = B*L nodes (packed context: B = number of complexes, L = longest, N = sum of lengths)
-    bool packed = false;      // rows of the complexes back to back, no padding rows (pp_complex_prepare_packed)
-    int shortest = 0;         // packed context: the caller's min_len (else L)
-    int2 *seg;                // [N] (first row, length) of the complex each row belongs to
+    int B, L, K, N;           // B complexes, L = the longest, N rows: a padded batch [B][L] (N = B*L) or, packed, the sum of lengths
+    bool packed = false;      // rows of the complexes back to back, no padding rows (pp_complex_prepare_packed).  Read only for what
+                              // differs by creation: which contexts the proximal exports take and what their workspaces hold
+    int shortest = 0;         // the shortest complex: the caller's min_len (padded: L)
+    int32_t *seg_off;         // [B + 1] THE segment table: the first row of every complex, then N (pp_segments.h).  Packed: a copy
+                              // of the caller's; padded: 0, L, 2L ...  Everything per complex reads it; no consumer forks on `packed`
+    int2 *seg;                // [N] (first row, length) of the complex each row belongs to, made from seg_off (k_fill_seg)
     // static per complex
     int32_t *eidx;            // [N][K] global node index of each neighbour
     float *mask_att;          // [N][32] mask_i*mask_j (0 for slots >= K)
@@ -168,8 +179,7 @@ struct pp_ctx {
     int32_t *cand;            // [N][4][PP_CL_CAP] proximal: static clash-partner candidates of every (residue, wave of its workgroup)
     int32_t *cand_cnt;        // [N][4] their number, -1 = more than PP_CL_CAP (that wave scans all partners as before)
     float *prox_part;         // [PP_PROX_CHUNK][N] per-residue loss terms of the proximal steps parked before one reduction (k_prox_losses)
-    // the proximal loop (packed contexts and B = 1) runs per complex, all complexes in the same launches; a B = 1 context is one complex
-    int32_t *seg_off;         // [B + 1] packed context: the first row of every complex, then N (a copy of the caller's table)
+    // the proximal loop (packed contexts and B = 1) runs per complex of seg_off, all complexes in the same launches
     int32_t *prox_nrows;      // [B] the caller's norm_rows (the row count each complex's means divide by)
     float2 *prox_seg;         // [B] per complex: (mean divisor, 1 / divisor), written by k_prox_init
     float *prox_inv;          // [N] 1 / divisor of the row's complex: the gradient and anchor weight of k_clash<CAND, true>

@@ -1505,26 +1505,14 @@ pp_status pp_launch_node_update(pp_ctx *c, int layer, int last_mode, float *chi,
 // export of one step's draws, the initial noising.  One thread per (row, chi); small VALU kernels that run once per context,
 // per inspection call, per sample.
 // ==================================================================================================================
-// tab[n] = (row of n within its complex, key of the complex): the complex is found as k_fill_seg / k_fill_seg_packed find it
-// (pp_api.hip), its key is keys[ordinal] or, without keys, the ordinal itself
-__global__ void k_rng_table(pp_rng_row *__restrict__ tab, int N, int L, const int32_t *__restrict__ seg_off, int n_seg,
+// tab[n] = (row of n within its complex, key of the complex): the complex is found in the context's table (pp_segments.h), its key
+// is keys[ordinal] or, without keys, the ordinal itself
+__global__ void k_rng_table(pp_rng_row *__restrict__ tab, int N, const int32_t *__restrict__ seg_off, int n_seg,
                             const uint64_t *__restrict__ keys) {
     const int n = blockIdx.x * blockDim.x + threadIdx.x;
     if (n >= N) return;
-    int ord, start;
-    if (seg_off) {
-        int lo = 0, hi = n_seg - 1;                   // last s with seg_off[s] <= n
-        while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            if (seg_off[mid] <= n) lo = mid; else hi = mid - 1;
-        }
-        ord = lo;
-        start = seg_off[lo];
-        start = start < 0 ? 0 : (start > n ? n : start);      // (a table that disagrees with the batch: stay inside it)
-    } else {
-        ord = n / L;
-        start = ord * L;
-    }
+    const int ord = pp_seg_of_row(seg_off, n_seg, n);
+    const int start = pp_seg_start(seg_off, ord, n);      // (a table that disagrees with the batch: stay inside it)
     const uint64_t key = keys ? keys[ord] : (uint64_t)ord;
     pp_rng_row t;
     t.row = (uint32_t)(n - start);
@@ -1563,8 +1551,8 @@ __global__ void k_add_noise_seeded(const pp_rng_row *__restrict__ tab, int N, co
 }
 
 pp_status pp_launch_rng_table(pp_ctx *c, bool keys_set, hipStream_t s) {
-    hipLaunchKernelGGL(k_rng_table, dim3((c->N + 255) / 256), dim3(256), 0, s, c->rng_tab, c->N, c->L,
-                       c->packed ? c->seg_off : nullptr, c->B, keys_set ? c->rng_keys : nullptr);
+    hipLaunchKernelGGL(k_rng_table, dim3((c->N + 255) / 256), dim3(256), 0, s, c->rng_tab, c->N, c->seg_off,
+                       c->B, keys_set ? c->rng_keys : nullptr);
     PP_HIP_CHECK(hipGetLastError());
     c->rng_tab_set = true;
     return PP_OK;

@@ -304,9 +304,12 @@ class Context:
         pb = PPBatch(self.B, self.L, *[(self._t[k].data_ptr() if self._t[k] is not None else None)
                                        for k, _ in _BATCH_SPEC])
         h = C.c_void_p()
-        self.seg_offsets_host = None          # packed batch: the complexes' first rows and the total (host list)
+        # every context has one segment table (csrc/pp_segments.h): the complexes' first rows and the total (host list) --
+        # a padded batch 0, L, 2L ..., a packed batch (``packed``) its own
         seg = _get(batch, "seg_offsets")
-        if seg is None:
+        self.packed = seg is not None
+        if not self.packed:
+            self.seg_offsets_host = [s * self.L for s in range(self.B + 1)]
             _check(lib.pp_complex_prepare(plan.handle, C.byref(pb), _stream(dev), C.byref(h)), "pp_complex_prepare")
         else:
             # ragged batch without padding rows (batch.pack): [1, sum of lengths, ...] + the complexes' first rows; the host
@@ -367,7 +370,7 @@ class Context:
     @property
     def n_segments(self) -> int:
         """Complexes of a packed context, else the B rows of the padded batch."""
-        return len(self.seg_offsets_host) - 1 if self.seg_offsets_host is not None else self.B
+        return len(self.seg_offsets_host) - 1
 
     def _rows(self, t, what, width=1):
         t = t.to(device=self.plan.device, dtype=torch.float32).contiguous()
@@ -512,8 +515,7 @@ class Context:
         if return_moved and fixed is None:
             raise ValueError("return_moved needs fixed: the unpinned call does not report its mask (functional.find_clash_mask does)")
         self.plan.set_clash_params(vtf, tol)
-        offs = self.seg_offsets_host if self.seg_offsets_host is not None else [0, self.L]
-        n_seg = len(offs) - 1 if self.B == 1 else self.B
+        offs, n_seg = self.seg_offsets_host, self.n_segments
         nr = None
         if norm_rows is not None:
             nr = np.ascontiguousarray([int(x) for x in norm_rows], dtype=np.int32)
@@ -641,7 +643,7 @@ class AffinityHead:
         sc = sc_sincos.to(device=dev, dtype=torch.float32).contiguous()
         mm = mut_mask.to(device=dev, dtype=torch.int64).contiguous()
         hp = hV_pret.to(device=dev, dtype=torch.float32).contiguous()
-        n = ctx.B * ctx.L if ctx.seg_offsets_host is None else ctx.L
+        n = ctx.n_rows
         if rt.numel() != n or sc.numel() != 8 * n or mm.numel() != n or hp.numel() != 128 * n:
             raise RuntimeError("pp_affinity_encode: tensors do not match the context's rows")
         hV = torch.empty(hp.shape, dtype=torch.float32, device=dev)

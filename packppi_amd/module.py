@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from .functional import proximal_optimizer, proximal_optimizer_packed
-from .lib import BatchKey, Context, Plan
+from .lib import BatchKey, Context, Plan, _get
 
 SAMPLE_DEFAULTS = dict(eval_epochs=1, sample_during_training=True, annealed_temp=3, mode="ode", use_proximal=True,
                        violation_tolerance_factor=12., clash_overlap_tolerance=0.5, lamda=1., num_steps=50)
@@ -219,9 +219,9 @@ class TDiffusionModule:
         return self
 
     def _segments(self, batch):
-        offs = batch.get("seg_offsets_host") if hasattr(batch, "get") else None
-        if offs is None and hasattr(batch, "get") and batch.get("seg_offsets") is not None:
-            offs = [int(v) for v in batch["seg_offsets"].tolist()]
+        offs = _get(batch, "seg_offsets_host")
+        if offs is None and _get(batch, "seg_offsets") is not None:
+            offs = [int(v) for v in _get(batch, "seg_offsets").tolist()]
         if offs is not None:
             return [b - a for a, b in zip(offs[:-1], offs[1:])]
         return [int(batch.max_size)] * int(batch.num_proteins)
@@ -295,7 +295,7 @@ class TDiffusionModule:
         ``fixed_chi`` bit for bit.  ``return_trajectory``: (sample, angles after every step [n_steps, B, L, 4])."""
         cfg = self.hparams.sample_cfg
         if fixed_mask is None:
-            fixed_mask = batch.get("fixed_mask") if hasattr(batch, "get") else getattr(batch, "fixed_mask", None)
+            fixed_mask = _get(batch, "fixed_mask")
         if fixed_mask is not None:
             if seed is None:
                 raise ValueError("fixed_mask needs seed: the fixed rows are re-noised with the seeded generator's draws")
@@ -308,7 +308,7 @@ class TDiffusionModule:
             if fixed_mode not in FIX_MODES:
                 raise ValueError(f"fixed_mode must be one of {sorted(FIX_MODES)}")
             ctx = self._context(batch)
-            ctx.set_rng_keys(batch.get("complex_keys") if hasattr(batch, "get") else getattr(batch, "complex_keys", None))
+            ctx.set_rng_keys(_get(batch, "complex_keys"))
             fx = (torch.as_tensor(fixed_mask).to(self.device) != 0).reshape(ctx.B, ctx.L)
             ref = ctx._chi(batch.SC_D if fixed_chi is None else fixed_chi)
             init = ctx.add_noise(torch.where(fx.unsqueeze(-1), ref, ctx._chi(batch.SC_D)), 1.0, seed)
@@ -317,7 +317,7 @@ class TDiffusionModule:
             return ctx.sample_partial(init, ref, fx, self.schedule, cfg.mode, seed, fixed_mode, trajectory=return_trajectory)
         if return_trajectory:
             raise ValueError("return_trajectory needs fixed_mask (the trajectory is written by the partial sampler)")
-        packed = batch.get("seg_offsets") is not None if hasattr(batch, "get") else False
+        packed = _get(batch, "seg_offsets") is not None
         if packed and use_proximal and return_list:
             raise ValueError("return_list=True needs a B = 1 batch; for a packed batch use "
                              "functional.proximal_optimizer_packed (per-complex losses [n_complexes, num_steps])")
@@ -325,7 +325,7 @@ class TDiffusionModule:
             raise ValueError("seed and sde_noise exclude each other: the seeded sampler draws its own noise")
         if seed is not None:
             ctx = self._context(batch)
-            ctx.set_rng_keys(batch.get("complex_keys") if hasattr(batch, "get") else getattr(batch, "complex_keys", None))
+            ctx.set_rng_keys(_get(batch, "complex_keys"))
             SC_D_sample = ctx.sample(ctx.add_noise(batch.SC_D, 1.0, seed), self.schedule, cfg.mode, seed=seed)
         else:
             t = torch.tensor([1.]).repeat_interleave(batch.max_size * batch.num_proteins).to(self.device)
@@ -362,10 +362,10 @@ class TDiffusionModule:
         the padded sizes).  Kept rows of the result are ``fixed_chi`` bit for bit with or without the proximal stage.
         ``return_list`` (B = 1, with ``use_proximal``): (sample, per-step angles, losses) as ``sampling`` returns them."""
         if fixed_mask is None:
-            fixed_mask = batch.get("fixed_mask") if hasattr(batch, "get") else getattr(batch, "fixed_mask", None)
+            fixed_mask = _get(batch, "fixed_mask")
         if fixed_mask is None:
             raise ValueError("repack needs fixed_mask (or a batch that carries one); sampling() samples every row")
-        packed = batch.get("seg_offsets") is not None if hasattr(batch, "get") else False
+        packed = _get(batch, "seg_offsets") is not None
         if return_list and (packed or not use_proximal):
             raise ValueError("return_list=True needs use_proximal=True and a B = 1 batch; for a packed batch use "
                              "functional.proximal_optimizer_packed (per-complex losses [n_complexes, num_steps])")
