@@ -418,7 +418,9 @@ pp_status pp_ctx_saturated(pp_ctx *ctx, int *flags, void *stream);
 pp_status pp_debug_edge(pp_ctx *ctx, int layer, void *stream);     /* one edge-update launch (+ next node message) */
 pp_status pp_debug_nm(pp_ctx *ctx, int layer, void *stream);       /* one node-message launch */
 pp_status pp_debug_set_hE(pp_ctx *ctx, const float *src, size_t n);
-/* which: 0 h_E [N,K,128], 1 S [N,128], 2 msum [N], 3 h_E0, 4 Z_em, 5 h_V [N,128], 6 score [N,4]; waits for the device.
+/* which: 0 h_E [N,K,128], 1 S [N,128], 2 msum [N], 3 h_E0, 4 Z_em, 5 h_V [N,128], 6 score [N,4], 7 the proximal loop's static
+ * candidate counts [N,4] (int32 bits in the 4-byte slots; -1 = that wave scans), 8 the plan's side-chain extents [21]; waits for
+ * the device.
  * After pp_score / pp_sample, h_E holds layer 0's edges: the layer-1 edge update of an evaluation does not write it back
  * (pp_debug_score_prefix and pp_debug_edge do). */
 pp_status pp_debug_buffer(pp_ctx *ctx, int which, float *dst, size_t n);

@@ -883,11 +883,17 @@ extern "C" pp_status pp_debug_set_hE(pp_ctx *c, const float *src, size_t n) {
     PP_HIP_CHECK(hipMemcpy(c->hE, src, n * sizeof(float), hipMemcpyDeviceToDevice));
     return PP_OK;
 }
-// which: 0 h_E, 1 S, 2 msum, 3 h_E0, 4 Z_em, 5 h_V, 6 score
+// which: 0 h_E, 1 S, 2 msum, 3 h_E0, 4 Z_em, 5 h_V, 6 score, 7 cand_cnt [N][4] (the int32 bits in the 4-byte slots: what the last
+// proximal call's k_clash_cand left), 8 the plan's side_extent [21]
 extern "C" pp_status pp_debug_buffer(pp_ctx *c, int which, float *dst, size_t n) {
     if (!c || !dst) FAIL(PP_ERR_INVALID, "pp_debug_buffer: null");
     const float *src = which == 0 ? c->hE : which == 1 ? c->S : which == 2 ? c->msum : which == 3 ? c->hE0 : which == 4 ? c->Zem :
                        which == 6 ? c->score : c->hV;
+    if (which == 7 || which == 8) {
+        src = which == 7 ? reinterpret_cast<const float *>(c->cand_cnt) : c->plan->side_extent;
+        if (!src) FAIL(PP_ERR_INVALID, "pp_debug_buffer: this context has no candidate lists");
+        if (n > (which == 7 ? (size_t)c->N * 4 : (size_t)21)) FAIL(PP_ERR_INVALID, "pp_debug_buffer: n is larger than the table");
+    }
     PP_HIP_CHECK(hipDeviceSynchronize());
     PP_HIP_CHECK(hipMemcpy(dst, src, n * sizeof(float), hipMemcpyDeviceToDevice));
     return PP_OK;
