@@ -407,8 +407,17 @@ pp_status pp_range_check_parts(unsigned long long *edge_events, unsigned long lo
  * context are not fp32-equivalent for this checkpoint (run python -m packppi_amd.rangecheck for the details).
  * Bit 2 (value 4): a NaN or infinity ENTERED with the caller's tensors (backbone coordinates of an unmasked row at
  * pp_complex_prepare, an angle at pp_score / pp_sample).  The reference propagates it to its output (layers.py:22-33 has no
- * clamp); these kernels' clamps turn it into finite numbers that mean nothing -- the flag is how a caller learns of it. */
+ * clamp); these kernels' clamps turn it into finite numbers that mean nothing -- the flag is how a caller learns of it.
+ * Inside a sampling run the last node update of an evaluation reports bit 1 only for rows whose angles can move (the live rows
+ * below, without the fixed rows of pp_sample_partial): what it computes for the others is returned to nobody. */
 pp_status pp_ctx_saturated(pp_ctx *ctx, int *flags, void *stream);
+
+/* Live rows (no reference counterpart): the rows of the context whose angles a sampling run can move --
+ * residue_mask != 0 and at least one SC_D_mask entry != 0 --, in ascending order.  pp_sample / pp_sample_seeded run the layer-1
+ * edge update of every evaluation on these rows only (nothing it computes for another row reaches the returned angles);
+ * pp_sample_partial also leaves out the call's fixed rows.  PP_EDGE_LIVE=0 in the environment restores the launch over all rows
+ * (same results).  rows is a DEVICE array [B*L] (packed ctx: [N]); the entries behind *count are -1.  Waits for `stream`. */
+pp_status pp_ctx_live_rows(pp_ctx *ctx, int32_t *rows, int *count, void *stream);
 
 /* Diagnostics -- ONLY in libpackppi_hip.dbg.so (built with -DPP_DIAG; same kernels and results as the default library):
  * single launches, internal-buffer copies and a prefix of one network evaluation, for tools/debug/ and the per-layer parity

@@ -108,6 +108,21 @@ extern "C" pp_status pp_ctx_saturated(pp_ctx *c, int *flags, void *stream) {
     return PP_OK;
 }
 
+// The context's live rows (the rows a sampling run can move: residue_mask != 0 and a non-zero SC_D_mask entry), ascending:
+// rows is a DEVICE array [N] (entries behind the count are -1), *count their number.  Waits for `stream`.
+extern "C" pp_status pp_ctx_live_rows(pp_ctx *c, int32_t *rows, int *count, void *stream) {
+    if (!c || !rows || !count) FAIL(PP_ERR_INVALID, "pp_ctx_live_rows: null argument");
+    if (!c->plan->has_network) FAIL(PP_ERR_INVALID, "pp_ctx_live_rows: plan was created without network weights");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    PP_HIP_CHECK(hipSetDevice(c->plan->device));
+    int32_t cnt = 0;
+    PP_HIP_CHECK(hipMemcpyAsync(rows, c->live_rows[0], (size_t)c->N * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    PP_HIP_CHECK(hipMemcpyAsync(&cnt, c->live_cnt[0], sizeof(cnt), hipMemcpyDeviceToHost, s));
+    PP_HIP_CHECK(hipStreamSynchronize(s));
+    *count = (int)cnt;
+    return PP_OK;
+}
+
 // How far a side-chain atom can get from its CA whatever the chi angles are, per residue type: the atom sits at chain(lit) in the
 // backbone frame (origin CA), the chain composes default frames and rotations about x, a rotation keeps the norm and a frame adds at
 // most the length of its translation: |atom - CA| <= |lit| + sum of |t_k| over the frames of its chain (features.py:95-194).
@@ -160,6 +175,7 @@ extern "C" pp_status pp_plan_create(const float *weights, size_t n_weights, cons
     std::unique_ptr<pp_plan, PlanDeleter> p(new (std::nothrow) pp_plan());
     if (!p) FAIL(PP_ERR_INVALID, "out of host memory");
     p->device = device;
+    p->num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     p->off = off;
     p->has_network = has_net;
     p->knn_ties = PP_KNN_TIES_ATEN_CPU;
@@ -396,6 +412,7 @@ static pp_status prepare_impl(pp_plan *plan, const pp_batch *b, const int32_t *s
         ALLOC(ptsN, N * 48); ALLOC(PAn, N * 128); ALLOC(PCn, N * 128);
         ALLOC(ptsE, N * 48); ALLOC(PAe, N * 128); ALLOC(PCe, N * 128);
         ALLOC(score, N * 4); ALLOC(chi_tmp, N * 4);
+        for (int k = 0; k < 2; k++) { ALLOC(live_rows[k], N + 2); ALLOC(live_mix[k], N); ALLOC(live_cnt[k], 1); }
     }
     ALLOC(xyz, N * 42); ALLOC(rec, N * 64); ALLOC(axes, N * 24); ALLOC(rec2, N * 64); ALLOC(axes2, N * 24); ALLOC(brad, N); ALLOC(per_res, N); ALLOC(dchi, N * 4);
     ALLOC(px, N * 4); ALLOC(pm, N * 4); ALLOC(pv, N * 4); ALLOC(pz, N * 4); ALLOC(pxeff, N * 4); ALLOC(pmask, N);
@@ -449,6 +466,7 @@ static pp_status prepare_impl(pp_plan *plan, const pp_batch *b, const int32_t *s
         flag_nonfinite(c, c->b.X, 42, 12, s_);      // N, CA, C, O of the unmasked rows
         if ((st = pp_launch_prepare(c, s_)) != PP_OK) return st;
         if ((st = pp_launch_edge_static(c, s_)) != PP_OK) return st;
+        if ((st = pp_launch_live_rows(c, 0, nullptr, s_)) != PP_OK) return st;
     }
     *out = owner.release();
     return PP_OK;
@@ -544,10 +562,27 @@ bool pp_prof_take(pp_ctx *c, hipEvent_t *e0, hipEvent_t *e1) {
     return true;
 }
 
+// The layer-1 edge update of a sampling run takes only the context's live rows.  PP_EDGE_LIVE=0 in the
+// environment restores the launch over all rows -- read by every build: it is the A/B switch of the tests and the benchmark.
+static bool edge_live_on() {
+    static const char *e = getenv("PP_EDGE_LIVE");
+    static const bool on = !(e && atoi(e) == 0);
+    return on;
+}
+
 // rng (seeded sde sampling, else null): the reverse step draws its own noise
 // pin (pp_sample_partial, else null): this step's pinned reverse step
+// live (sampling runs, else null): the rows whose layer-1 edge update has a reader.  That launch makes h_E (not stored) and the
+// layer-2 message S / msum of row i, which feed only the layer-2 node update of row i, whose h_V feeds only the decoder and the
+// reverse step of row i: nothing of it reaches the returned angles of a row that cannot move (y = wrap(..) * SC_D_mask = 0, or
+// the pinned value), and the next evaluation starts from a fresh embedding.  S / msum of a skipped row keep what THIS evaluation's
+// layer-0 launch wrote there -- the row's layer-1 message, or the zeros of a masked row: finite values of the same run, never
+// uninitialised memory -- and the layer-2 node update computes on them as on any other message.  What it computes for such a row is
+// read by nobody, and it must not be reported either: k_node_update<PP_NU_STEP> leaves the rows that cannot move out of the sticky
+// saturation word (pp_node.hip, `satrow`), so the word does not depend on which message a skipped row was given.
 static pp_status run_network(pp_ctx *c, hipStream_t s, int step, int last_mode, float *chi, int mode, const float *noise,
-                             const StepParams *cur, const StepParams *next, const PPRng *rng = nullptr, const PPPin *pin = nullptr) {
+                             const StepParams *cur, const StepParams *next, const PPRng *rng = nullptr, const PPPin *pin = nullptr,
+                             const PPLive *live = nullptr) {
     pp_status st;
     for (int l = 0; l < 3; l++) {
         if (l == 0 || !pp_edge_fused()) {   // fused build: layers 1 and 2 come from the tail of the previous edge update
@@ -562,7 +597,7 @@ static pp_status run_network(pp_ctx *c, hipStream_t s, int step, int last_mode, 
             prof_disarm(c);
             if (st != PP_OK) return st;
             prof_arm(c, 1);
-            st = pp_launch_edge_update(c, l, l == 0 || !pp_edge_fused(), s);   // layer 1's h_E has no reader here
+            st = pp_launch_edge_update(c, l, l == 0 || !pp_edge_fused(), s, l == 1 ? live : nullptr);   // layer 1's h_E has no reader here
             prof_disarm(c);
             if (st != PP_OK) return st;
         } else {
@@ -741,6 +776,16 @@ static pp_status sample_impl(const char *who, pp_ctx *c, float *chi, const float
     if ((st = pp_launch_node_embed(c, chi, steps[0], s)) != PP_OK) return st;
     static const bool dbg = PP_GETENV("PP_DEBUG") != nullptr;
     const auto h0 = std::chrono::steady_clock::now();
+    // the live rows of this run: the context's, or without the call's fixed rows (made here, on the stream).  The in-situ timing
+    // runs of pp_profile_kernel launch all rows (their rates are quoted per row of the context)
+    PPLive live = {nullptr, nullptr};
+    const bool use_live = edge_live_on() && pp_edge_fused() && c->prof_which < 0;
+    if (use_live) {
+        const int set = part ? 1 : 0;
+        if (part && (st = pp_launch_live_rows(c, 1, part->fixed, s)) != PP_OK) return st;
+        live.rows = c->live_rows[set];
+        live.mix = c->live_mix_set[set] ? c->live_mix[set] : nullptr;      // null: not filled, the mixed launch refuses it
+    }
     for (int j = 0; j < nsteps; j++) {
         PPPin pin = {nullptr, nullptr, nullptr, 0.f, 0};
         if (part) {
@@ -753,7 +798,7 @@ static pp_status sample_impl(const char *who, pp_ctx *c, float *chi, const float
             pin.renoise = part->fix_mode == PP_FIX_RENOISE && j + 1 < nsteps ? 1 : 0;
         }
         if ((st = run_network(c, s, j, PP_NU_STEP, chi, mode, sde_noise, &steps[j], j + 1 < nsteps ? &steps[j + 1] : nullptr, rng,
-                              part ? &pin : nullptr)) != PP_OK) return st;
+                              part ? &pin : nullptr, use_live ? &live : nullptr)) != PP_OK) return st;
     }
     if (dbg) {
         const double us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - h0).count();

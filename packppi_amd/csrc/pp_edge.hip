@@ -40,7 +40,11 @@ unsigned int pp_edge_range_hits(int) { return 0; }
 struct EdgeArgs {
     int N, K;
     float inv_K;
-    const float *rmask;        // [N]
+    union {                    // one slot, so that the argument block of every instance is laid out as it always was:
+        const float *rmask;        // [N]
+        const int32_t *live_rows;  // LIVE instance (it never reads rmask: the list holds no masked row): [N + 2] the rows that get a
+                                   // workgroup, ascending, then -1 (pp_prepare.hip k_live_rows)
+    };
     const int32_t *eidx;       // [N][K]
     const float *mask_att;     // [N][32]
     const float *frames;       // [N][12]
@@ -315,7 +319,10 @@ k_node_message(EdgeArgs A) {
 // one launch, one prologue and one read of h_E less per layer.
 // WB: the new h_E is written back to A.hE_out (masked rows as zeros).  Without it (the layer-1 launch of a fused evaluation,
 // whose only consumer of h_E is the fused message below, fed from registers through xbuf) neither store is issued.
-template <int S, bool ST0, bool FUSE, bool WB = true>
+// LIVE (the layer-1 launch of a sampling run): workgroup b takes row live_rows[b] of the context's live-row list, which holds no
+// masked row -- the lookup stands where the other instances read residue_mask -- and leaves behind the list's end.  A row that
+// is not listed gets no workgroup: its S / msum keep what layer 0's launch wrote (pp_api.hip run_network).
+template <int S, bool ST0, bool FUSE, bool WB = true, bool LIVE = false>
 __global__ void __launch_bounds__(ET, PP_EU_WGS)
 k_edge_update(EdgeArgs A) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -323,10 +330,12 @@ k_edge_update(EdgeArgs A) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int j = lane & 31, h = lane >> 5;
-    const int n = blockIdx.x;
+    static_assert(!LIVE || !WB, "a launch over the live rows alone leaves the other rows' h_E unwritten");
+    const int n = LIVE ? A.live_rows[blockIdx.x] : (int)blockIdx.x;
     const int K = A.K;
     const int jj = j < K ? j : K - 1;
-    if (A.rmask[n] == 0.f) {              // masked / padded residue: its edges are zero, whole workgroup leaves
+    if (LIVE && n < 0) return;            // behind the end of the list (the launch is sized for all rows)
+    if (!LIVE && A.rmask[n] == 0.f) {     // masked / padded residue: its edges are zero, whole workgroup leaves
         if (WB && j < K) {
             f32x4v z = {0.f, 0.f, 0.f, 0.f};
             float *orow = A.hE_out + ((size_t)n * K + j) * 128 + 32 * wave;
@@ -578,7 +587,8 @@ static bool edge_attrs() {
              set(reinterpret_cast<const void *>(k_node_message<PP_NM_SLOTS, true>), NM_SMEM) &&
              set(reinterpret_cast<const void *>(k_edge_update<PP_EU_SLOTS, false, true>), EU_SMEM) &&
              set(reinterpret_cast<const void *>(k_edge_update<PP_EU_SLOTS, true, true>), EU_SMEM) &&
-             set(reinterpret_cast<const void *>(k_edge_update<PP_EU_SLOTS, false, true, false>), EU_SMEM);
+             set(reinterpret_cast<const void *>(k_edge_update<PP_EU_SLOTS, false, true, false>), EU_SMEM) &&
+             set(reinterpret_cast<const void *>(k_edge_update<PP_EU_SLOTS, false, true, false, true>), EU_SMEM);
     }
     return ok;
 }
@@ -619,12 +629,15 @@ pp_status pp_launch_node_message(pp_ctx *c, int layer, hipStream_t s) {
 
 // layers 0 and 1 only (the reference's layer-2 edge update is dead code); also produces S / msum of layer + 1.
 // keep_hE = false skips the h_E write-back of a layer-1 launch (layer 0 always stores: layer 1 reads it)
-pp_status pp_launch_edge_update(pp_ctx *c, int layer, bool keep_hE, hipStream_t s) {
+pp_status pp_launch_edge_update(pp_ctx *c, int layer, bool keep_hE, hipStream_t s, const PPLive *live) {
     EDGE_ATTR_CHECK()
     if (layer < 0 || layer > 1) { pp_set_error("pp_launch_edge_update: layer must be 0 or 1"); return PP_ERR_INVALID; }
+    if (live && (layer != 1 || keep_hE)) { pp_set_error("pp_launch_edge_update: the live-row launch is layer 1's, without write-back"); return PP_ERR_INVALID; }
     EdgeArgs A = edge_args(c, layer, true);
+    if (live) A.live_rows = live->rows;      // (the slot of rmask)
     if (layer == 0) PP_LAUNCH(c, (k_edge_update<PP_EU_SLOTS, true, true>), dim3(c->N), dim3(ET), EU_SMEM, s, A);
     else if (keep_hE) PP_LAUNCH(c, (k_edge_update<PP_EU_SLOTS, false, true>), dim3(c->N), dim3(ET), EU_SMEM, s, A);
+    else if (live) PP_LAUNCH(c, (k_edge_update<PP_EU_SLOTS, false, true, false, true>), dim3(c->N), dim3(ET), EU_SMEM, s, A);
     else PP_LAUNCH(c, (k_edge_update<PP_EU_SLOTS, false, true, false>), dim3(c->N), dim3(ET), EU_SMEM, s, A);
     PP_HIP_CHECK(hipGetLastError());
     return PP_OK;

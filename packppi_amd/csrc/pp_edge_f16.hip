@@ -109,7 +109,12 @@ __device__ __forceinline__ void join_tile(const HT &t, f32x16 &v) {
 struct EdgeArgs {
     int N, K;
     float inv_K;
-    const float *rmask;        // [N]
+    union {                    // one slot, so that the argument block of every instance is laid out as it always was:
+        const float *rmask;        // [N]
+        const int32_t *live_rows;  // LIVE instances (they never read rmask: the list holds no masked row): [N + 2] the rows that get a
+                                   // workgroup, ascending, then -1 (pp_prepare.hip k_live_rows)
+        const int2 *live_mix;      // ... k_edge_update_mix: [N] the rows of workgroup b
+    };
     const int32_t *eidx;       // [N][K]
     const float *mask_att;     // [N][32]
     const float *frames;       // [N][12]
@@ -462,8 +467,10 @@ __device__ __forceinline__ void geometry_put(const GeoI &g, const float (&pj)[3]
 #define GROUP_SETUP()                                                                          \
     int n[R];                                                                                  \
     bool live[R], inr[R];                                                                      \
-    float rm_[R];                                                                              \
     int first = -1;                                                                            \
+    GROUP_SETUP_ROWS()
+#define GROUP_SETUP_ROWS()                                                                     \
+    float rm_[R];                                                                              \
     _Pragma("unroll") for (int r = 0; r < R; r++) {                                            \
         const int nr = res0 + r;                                                               \
         inr[r] = nr < A.N;                                                                     \
@@ -660,8 +667,12 @@ k_node_message(EdgeArgs A) {
 // are multiplied by their power-of-two scale vector before the split (the default instances contain none of it).
 // WB: the new h_E is written back to A.hE_out (masked rows as zeros).  Without it (the layer-1 launch of a fused evaluation,
 // whose only consumer of h_E is the fused message below, fed from registers through xbuf) neither store is issued.
-template <int R, bool ST0, bool FUSE, bool LNS = false, bool WB = true>
-__device__ __forceinline__ void edge_update_body(const EdgeArgs &A, const int res0, float *smem) {
+// LIVE (the layer-1 launch of a sampling run): the workgroup's rows are lrow.x and, R = 2, lrow.y -- entries of the context's
+// live-row list, -1 for an empty second slot -- instead of res0 .. res0 + R - 1.  The list holds no masked row, so its lookup at
+// the kernel's entry stands where the other instances read residue_mask: the prologue keeps its four dependent round trips.  A
+// row that is not listed gets no workgroup: its S / msum keep what layer 0's launch wrote (pp_api.hip run_network).
+template <int R, bool ST0, bool FUSE, bool LNS = false, bool WB = true, bool LIVE = false>
+__device__ __forceinline__ void edge_update_body(const EdgeArgs &A, const int res0, float *smem, const int2 lrow = {-1, -1}) {
     float *const xbuf = smem, *const x1buf = smem + R * XBUF_FLOATS, *const stat = x1buf + R * XBUF_FLOATS,
                  *const prm = stat + R * STAT_FLOATS;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -670,10 +681,23 @@ __device__ __forceinline__ void edge_update_body(const EdgeArgs &A, const int re
     const int K = A.K;
     const int jj = j < K ? j : K - 1;
     unsigned sat = 0;
-    GROUP_SETUP()
+    int n[R];
+    bool live[R], inr[R];
+    int first = -1;
+    if constexpr (LIVE) {
+        static_assert(!WB, "a launch over the live rows alone leaves the other rows' h_E unwritten");
+#pragma unroll
+        for (int r = 0; r < R; r++) {
+            n[r] = r == 0 ? lrow.x : lrow.y;
+            inr[r] = live[r] = n[r] >= 0;
+        }
+        first = lrow.x;                   // (the caller left if the workgroup has no row)
+    } else {
+        GROUP_SETUP_ROWS()
+    }
 #pragma unroll
     for (int r = 0; r < R; r++)
-        if (inr[r] && !live[r]) {         // masked / padded residue: its edges are zero
+        if (!LIVE && inr[r] && !live[r]) {         // masked / padded residue: its edges are zero
             if (WB && j < K) {
                 f32x4v z = {0.f, 0.f, 0.f, 0.f};
                 float *orow = A.hE_out + ((size_t)n[r] * K + j) * 128 + 32 * wave;
@@ -897,11 +921,19 @@ __device__ __forceinline__ void edge_update_body(const EdgeArgs &A, const int re
 #endif
 }
 
-template <int R, bool ST0, bool FUSE, bool LNS = false, bool WB = true>
+template <int R, bool ST0, bool FUSE, bool LNS = false, bool WB = true, bool LIVE = false>
 __global__ void __launch_bounds__(ET, R == 1 ? PP_WGS : PP_WGS2)
 k_edge_update(EdgeArgs A) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    edge_update_body<R, ST0, FUSE, LNS, WB>(A, blockIdx.x * R, smem);
+    if constexpr (LIVE) {
+        int2 lrow = {-1, -1};
+        if constexpr (R == 2) lrow = *reinterpret_cast<const int2 *>(A.live_rows + 2 * blockIdx.x);
+        else lrow.x = A.live_rows[blockIdx.x];
+        if (lrow.x < 0) return;           // behind the end of the list (the launch is sized for all rows)
+        edge_update_body<R, ST0, FUSE, LNS, WB, true>(A, 0, smem, lrow);
+    } else {
+        edge_update_body<R, ST0, FUSE, LNS, WB>(A, blockIdx.x * R, smem);
+    }
 }
 
 // MIXED launch for one complex that fills the chip once (2 < residues per CU <= 3).  Every workgroup streams the layer's
@@ -911,11 +943,20 @@ k_edge_update(EdgeArgs A) {
 // for two passes of the stream instead of three.  Workgroups 0 .. n_pairs - 1 take residues (2 b, 2 b + 1), the others one
 // residue each; in dispatch order the first half lands on distinct CUs, so a CU mostly gets one of each kind (placement is
 // the hardware's choice: it only affects speed).  A residue's kind is a function of (index, N): results are reproducible.
-template <bool ST0, bool FUSE, bool LNS = false, bool WB = true>
+// LIVE: workgroup b takes the one or two rows of A.live_mix[b] (k_live_rows deals the live rows out: the split between pair and
+// one-row workgroups and their dispatch order are the table's).
+template <bool ST0, bool FUSE, bool LNS = false, bool WB = true, bool LIVE = false>
 __global__ void __launch_bounds__(ET, 2)
 k_edge_update_mix(EdgeArgs A) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int b = blockIdx.x;
+    if constexpr (LIVE) {
+        const int2 lrow = A.live_mix[b];
+        if (lrow.x < 0) return;
+        if (lrow.y >= 0) edge_update_body<2, ST0, FUSE, LNS, WB, true>(A, 0, smem, lrow);
+        else edge_update_body<1, ST0, FUSE, LNS, WB, true>(A, 0, smem, lrow);
+        return;
+    }
     int pair = -1, single = -1;
     if (A.mix_mode == 2) {               // experiment: kinds interleaved in dispatch order
         const int ns = gridDim.x - A.n_pairs;
@@ -1210,12 +1251,15 @@ template <int R> static edge_kernel_t nm_kernel(bool st0) {
 }
 // wb = false selects the instances without the h_E write-back.  They exist for layer 1 only (ST0 = false): layer 0's h_E is
 // the next layer's input, so its launch always stores.
-template <int R> static edge_kernel_t eu_kernel(bool st0, bool lns, bool wb) {
+// live = true (with wb = false, layer 1) selects the instances that take their rows from the live-row list.
+template <int R> static edge_kernel_t eu_kernel(bool st0, bool lns, bool wb, bool live = false) {
+    if (live) return lns ? k_edge_update<R, false, PP_FUSED, true, false, true> : k_edge_update<R, false, PP_FUSED, false, false, true>;
     if (!wb && !st0) return lns ? k_edge_update<R, false, PP_FUSED, true, false> : k_edge_update<R, false, PP_FUSED, false, false>;
     if (lns) return st0 ? k_edge_update<R, true, PP_FUSED, true> : k_edge_update<R, false, PP_FUSED, true>;
     return st0 ? k_edge_update<R, true, PP_FUSED> : k_edge_update<R, false, PP_FUSED>;
 }
-static edge_kernel_t mix_kernel(bool st0, bool lns, bool wb) {
+static edge_kernel_t mix_kernel(bool st0, bool lns, bool wb, bool live = false) {
+    if (live) return lns ? k_edge_update_mix<false, PP_FUSED, true, false, true> : k_edge_update_mix<false, PP_FUSED, false, false, true>;
     if (!wb && !st0) return lns ? k_edge_update_mix<false, PP_FUSED, true, false> : k_edge_update_mix<false, PP_FUSED, false, false>;
     if (lns) return st0 ? k_edge_update_mix<true, PP_FUSED, true> : k_edge_update_mix<false, PP_FUSED, true>;
     return st0 ? k_edge_update_mix<true, PP_FUSED> : k_edge_update_mix<false, PP_FUSED>;
@@ -1224,8 +1268,8 @@ static edge_kernel_t mix_kernel(bool st0, bool lns, bool wb) {
 static edge_kernel_t nm_kernel_r(int R, bool st0) {
     return R == 1 ? nm_kernel<1>(st0) : nm_kernel<2>(st0);
 }
-static edge_kernel_t eu_kernel_r(int R, bool st0, bool lns = false, bool wb = true) {
-    return R == 1 ? eu_kernel<1>(st0, lns, wb) : eu_kernel<2>(st0, lns, wb);
+static edge_kernel_t eu_kernel_r(int R, bool st0, bool lns = false, bool wb = true, bool live = false) {
+    return R == 1 ? eu_kernel<1>(st0, lns, wb, live) : eu_kernel<2>(st0, lns, wb, live);
 }
 
 
@@ -1245,6 +1289,10 @@ static bool edge_attrs() {
                      set(reinterpret_cast<const void *>(eu_kernel_r(R, st0, true, true)), MAX_SMEM) &&
                      set(reinterpret_cast<const void *>(eu_kernel_r(R, st0, false, false)), MAX_SMEM) &&
                      set(reinterpret_cast<const void *>(eu_kernel_r(R, st0, true, false)), MAX_SMEM);
+        for (int R = 1; R <= PP_RMAX && ok; R++)
+            for (int lns = 0; lns < 2 && ok; lns++)
+                ok = set(reinterpret_cast<const void *>(eu_kernel_r(R, false, lns, false, true)), MAX_SMEM);
+        for (int lns = 0; lns < 2 && ok; lns++) ok = set(reinterpret_cast<const void *>(mix_kernel(false, lns, false, true)), MAX_SMEM);
         for (int st0 = 0; st0 < 2 && ok; st0++)
             for (int lns = 0; lns < 2 && ok; lns++)
                 ok = set(reinterpret_cast<const void *>(mix_kernel(st0, lns, true)), MAX_SMEM) &&
@@ -1339,23 +1387,34 @@ bool pp_edge_fused() { return PP_FUSED; }
 
 // layers 0 and 1 only (the reference's layer-2 edge update is dead code); keep_hE = false skips the h_E write-back of a
 // layer-1 launch (layer 0 always stores: layer 1 reads it)
-pp_status pp_launch_edge_update(pp_ctx *c, int layer, bool keep_hE, hipStream_t s) {
+pp_status pp_launch_edge_update(pp_ctx *c, int layer, bool keep_hE, hipStream_t s, const PPLive *live) {
     EDGE_ATTR_CHECK()
     if (layer < 0 || layer > 1) { pp_set_error("pp_launch_edge_update: layer must be 0 or 1"); return PP_ERR_INVALID; }
+    if (live && (layer != 1 || keep_hE || !PP_FUSED)) { pp_set_error("pp_launch_edge_update: the live-row launch is layer 1's, without write-back"); return PP_ERR_INVALID; }
     EdgeArgs A = edge_args(c, layer, true);
     const int R = pick_R(c->N);
+    const bool mixed = use_mix(c->N);
+    if (live) {                     // (the slot of rmask)
+        // the table is filled by pp_launch_live_rows for the sizes it expects the mixed launch at: never launch on one it did not fill
+        if (mixed && !live->mix) { pp_set_error("pp_launch_edge_update: the mixed launch has no live-row work table for this context"); return PP_ERR_INVALID; }
+        if (mixed) A.live_mix = live->mix;
+        else A.live_rows = live->rows;
+    }
     const bool lns = c->plan->ln_scale != nullptr;      // operand scales behind small LayerNorm gains: the LNS instances
     if (lns && !PP_FUSED) { pp_set_error("pp_launch_edge_update: a plan with LayerNorm operand scales needs the fused build"); return PP_ERR_UNSUPPORTED; }
-    if (use_mix(c->N)) {
+    if (mixed) {
         // three residues per CU as one two-residue and one one-residue workgroup
         A.n_pairs = (c->N + 2) / 3;
         A.mix_mode = g_mix;
         const int singles = c->N - 2 * A.n_pairs > 0 ? c->N - 2 * A.n_pairs : 0;
-        PP_LAUNCH(c, mix_kernel(layer == 0, lns, keep_hE), dim3(A.n_pairs + singles), dim3(ET), eu_smem(2) > eu_smem(1) ? eu_smem(2) : eu_smem(1), s, A);
+        // live rows: the table deals M <= N <= 3 C rows out to (M + 2) / 3 pair and M - 2 pairs one-row workgroups (k_live_rows),
+        // no more than 2 M / 3 + 1 <= 2 C in all
+        const int wgs = live ? (c->N < 2 * g_num_cu ? c->N : 2 * g_num_cu) : A.n_pairs + singles;
+        PP_LAUNCH(c, mix_kernel(layer == 0, lns, keep_hE, live != nullptr), dim3(wgs), dim3(ET), eu_smem(2) > eu_smem(1) ? eu_smem(2) : eu_smem(1), s, A);
         PP_HIP_CHECK(hipGetLastError());
         return PP_OK;
     }
-    PP_LAUNCH(c, eu_kernel_r(R, layer == 0, lns, keep_hE), dim3((c->N + R - 1) / R), dim3(ET), eu_smem(R), s, A);
+    PP_LAUNCH(c, eu_kernel_r(R, layer == 0, lns, keep_hE, live != nullptr), dim3((c->N + R - 1) / R), dim3(ET), eu_smem(R), s, A);
     PP_HIP_CHECK(hipGetLastError());
     return PP_OK;
 }

@@ -117,6 +117,7 @@ struct pp_plan {
     float *bounds_lower, *bounds_upper;   // [21][14][14]
     float clash_tol;
     bool clash_params_set;
+    int num_cu = 0;           // compute units of the device (which context sizes take the mixed edge launch and its live-row table)
 };
 
 // log sigma_min, log sigma_max of t_to_sigma (schedule.py:165-174; sigma from 0.01 pi to pi) in fp64: sigma(t), the step scalars
@@ -188,6 +189,12 @@ struct pp_ctx {
     pp_rng_row *rng_tab;      // [N] (row within the complex, key of the complex); filled by pp_launch_rng_table
     uint64_t *rng_keys;       // [B] the caller's keys (pp_ctx_set_rng_keys), staged for the table kernel
     bool rng_tab_set = false; // the table holds the default keys (segment ordinals) or the caller's
+    // live rows (pp_prepare.hip k_live_rows): the rows whose side chain a sampling run can move.  Set 0 is made
+    // when the context is prepared, set 1 by every pp_sample_partial (it also drops the call's fixed rows)
+    int32_t *live_rows[2];    // [N + 2] the rows in ascending order, then -1 up to the end
+    int2 *live_mix[2];        // [N] k_edge_update_mix: the one or two rows of every workgroup in dispatch order ((-1, -1): none; (r, -1): one)
+    int32_t *live_cnt[2];     // [1] number of live rows
+    bool live_mix_set[2] = {false, false};   // pp_launch_live_rows filled live_mix of this set (only contexts of the mixed launch's size)
     unsigned *sat;            // sticky word: bit 0 = an edge kernel, bit 1 = a node kernel clamped a hidden activation at 65504
     // in-situ kernel timing (pp_profile_kernel): every launch of one hot kernel carries a start / stop event pair
     // (hipExtLaunchKernelGGL: the dispatch's own begin / end timestamps, what rocprofv3's kernel trace reports)
@@ -327,7 +334,16 @@ struct PPPin {
     int renoise;              // 1: a fixed row gets chi_ref re-noised to sigma with this step's draws; 0: chi_ref itself
 };                            //    (PP_FIX_HOLD, and the last step of PP_FIX_RENOISE)
 
+// The live rows of a sampling run as the layer-1 edge update takes them (pp_ctx::live_*): rows for the one- and two-row instances
+// (workgroup b reads rows[R b .. R b + R - 1]), mix for the mixed launch (workgroup b reads mix[b])
+struct PPLive {
+    const int32_t *rows;
+    const int2 *mix;
+};
+
 // ---- launchers implemented in the kernel translation units ----------------------------------
+// live-row set `set` of the context (0: every row with an angle to move; 1: those that are not `fixed` either), on the stream
+pp_status pp_launch_live_rows(pp_ctx *c, int set, const uint8_t *fixed, hipStream_t s);
 // seeded noise (pp_node.hip): the per-row table from the context's segment table (keys_set: c->rng_keys holds the caller's keys,
 // else a complex's key is its ordinal), the draws of one step, the initial noising
 pp_status pp_launch_rng_table(pp_ctx *c, bool keys_set, hipStream_t s);
@@ -354,7 +370,9 @@ bool pp_edge_fused();            // does pp_launch_edge_update also compute the 
 // + node message of layer + 1.  keep_hE: write the new h_E back to c->hE.  A fused evaluation passes false for layer 1, where
 // the fused message takes h_E from registers and the next evaluation's layer 0 overwrites c->hE before anything reads it;
 // the unfused build (whose layer-2 node message reads c->hE) and the diagnostics pass true.  Layer 0 always stores.
-pp_status pp_launch_edge_update(pp_ctx *c, int layer, bool keep_hE, hipStream_t s);
+// live (layer 1 of a sampling run without write-back, else null): only the listed rows get a workgroup; S / msum of the others keep
+// what layer 0's launch wrote (see pp_api.hip run_network)
+pp_status pp_launch_edge_update(pp_ctx *c, int layer, bool keep_hE, hipStream_t s, const PPLive *live = nullptr);
 pp_status pp_launch_atom14(pp_ctx *c, const float *chi, float *xyz, hipStream_t s);
 pp_status pp_launch_clash(pp_ctx *c, const float *xyz, float *per_res, float *dchi, hipStream_t s, bool use_candidates = false);
 // One loop for both: pp_launch_proximal is the single-complex call (means over the complex's own rows, losses [nsteps]) without the

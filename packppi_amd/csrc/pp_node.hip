@@ -701,6 +701,18 @@ k_node_update(NUpdArgs A, float *chi, int step, int sde, const float *noise, int
         publish4(sm.e_hi, sm.e_lo, erow * NU_S32 + 28, nf4{ev[3][2], ev[3][3], 0.f, 0.f});
     }
     publish4(sm.a_hi, sm.a_lo, srow * NU_S128 + scol, s4);
+    // The reverse step reports saturation only for rows whose angles can move -- not masked, a non-zero SC_D_mask entry, not pinned:
+    // the rows of the context's live-row list (pp_prepare.hip k_live_rows).  What this kernel computes for any other row is read by
+    // nobody, and a sampling run hands such a row the layer-1 message in S (its layer-1 edge update is skipped, pp_api.hip
+    // run_network): the sticky word must not depend on that.  Lane (r, g) holds SC_D_mask[r][g]: two ballots folded over g into one
+    // bit per row, in scalar registers (a per-lane flag kept to the FFN would cost the shallow-ring instance its 128 VGPRs); made
+    // here, where the parameter stores above have waited for every prologue load already.
+    unsigned satrows = 0xffffu;
+    if constexpr (MODE == PP_NU_STEP) {
+        const unsigned long long bs = __ballot(scm1 != 0.f);
+        const unsigned long long br = __ballot(rm != 0.f && (!PINNED || fixraw == 0));
+        satrows = (unsigned)((bs | (bs >> 16) | (bs >> 32) | (bs >> 48)) & br & 0xffffull);
+    }
     __syncthreads();
 
     nh8 bh[4], bl[4];
@@ -724,7 +736,8 @@ k_node_update(NUpdArgs A, float *chi, int step, int sde, const float *noise, int
     publish4(sm.c_hi, sm.c_lo, r * NU_S512 + 16 * (4 * wv + (c)) + 4 * g,                                  \
              relu_sat(fold(cH, cL) + *reinterpret_cast<const nf4 *>(par + NU_P_FIB + 16 * (4 * wv + (c)) + 4 * g), satm));
     FFN_IN_TILE(0) FFN_IN_TILE(1) FFN_IN_TILE(2) FFN_IN_TILE(3)
-    if (!(satm < 65504.f)) atomicOr(A.sat, 2u);
+    const bool satrow = (satrows >> r) & 1u;
+    if (!(satm < 65504.f) && satrow) atomicOr(A.sat, 2u);
     __syncthreads();
     // ---- FFN 512 -> 128, LayerNorm, mask ------------------------------------------------------------------------------
     nh8 fh[2], fl[2];
@@ -823,7 +836,7 @@ k_node_update(NUpdArgs A, float *chi, int step, int sde, const float *noise, int
         }
         if (w0) {
             // registers 0..3 of lane group 0 = the four scores of residue r
-            if (!(satm < 65504.f)) atomicOr(A.sat, 2u);          // decoder hidden layers (the FFN's were reported above)
+            if (!(satm < 65504.f) && satrow) atomicOr(A.sat, 2u);          // decoder hidden layers (the FFN's were reported above)
             const nf4 sc = fold(cH, cL) + *reinterpret_cast<const nf4 *>(par + NU_P_DB3);
             if (g == 0 && live) *reinterpret_cast<nf4 *>(A.score + (size_t)n * 4) = sc;
             if constexpr (MODE == PP_NU_STEP) {

@@ -401,3 +401,65 @@ pp_status pp_launch_prepare(pp_ctx *c, hipStream_t s, const int64_t *E_idx) {
     return PP_OK;
 #endif
 }
+
+// ---- live rows ------------------------------------------------------------------------------------------
+// The rows whose angles a sampling run can move: residue_mask != 0, at least one SC_D_mask entry != 0 and (pp_sample_partial) not
+// fixed.  Only they need the layer-1 edge update of an evaluation.  ONE workgroup, so that the order needs no atomics: every thread
+// counts a contiguous slice of the rows, the 1024 counts are scanned in LDS, every thread writes its slice's rows behind its offset.
+//   rows [N + 2]  the live rows, ascending, then -1: workgroup b of a one- / two-row launch reads rows[R b .. R b + R - 1], so a
+//                 launch sized for N rows needs no count -- the surplus workgroups read -1 and leave;
+//   mix  [N]      (or null) the work table of the mixed launch k_edge_update_mix in dispatch order: with M live rows (M + 2) / 3
+//                 pair workgroups -- the rule of the all-rows launch -- FIRST, then the M - 2 pairs one-row workgroups, then
+//                 (-1, -1).  The other rule (M - 2 CUs pairs: as few CUs with three rows as M allows) and the other order were
+//                 measured at T1124 and were slower (profiles/r17_live_rows.json t1124_split);
+//   cnt  [1]      M.
+#define LIVE_THREADS 1024
+__global__ void __launch_bounds__(LIVE_THREADS)
+k_live_rows(const float *__restrict__ rmask, const float *__restrict__ scm, const uint8_t *__restrict__ fixed, int N,
+            int32_t *__restrict__ rows, int2 *__restrict__ mix, int32_t *__restrict__ cnt) {
+    __shared__ int part[LIVE_THREADS];
+    const int t = threadIdx.x;
+    const int per = (N + LIVE_THREADS - 1) / LIVE_THREADS;
+    const int lo = min(t * per, N), hi = min(lo + per, N);
+    auto is_live = [&](int i) {
+        const float *m = scm + (size_t)i * 4;
+        return rmask[i] != 0.f && (m[0] != 0.f || m[1] != 0.f || m[2] != 0.f || m[3] != 0.f) && !(fixed && fixed[i] != 0);
+    };
+    int c = 0;
+    for (int i = lo; i < hi; i++) c += is_live(i) ? 1 : 0;
+    part[t] = c;
+    __syncthreads();
+    for (int d = 1; d < LIVE_THREADS; d <<= 1) {      // inclusive scan
+        const int v = t >= d ? part[t - d] : 0;
+        __syncthreads();
+        part[t] += v;
+        __syncthreads();
+    }
+    const int M = part[LIVE_THREADS - 1];
+    int o = part[t] - c;
+    for (int i = lo; i < hi; i++)
+        if (is_live(i)) rows[o++] = i;
+    for (int i = M + t; i < N + 2; i += LIVE_THREADS) rows[i] = -1;
+    if (mix) {
+        const int np = (M + 2) / 3, ns = max(M - 2 * np, 0);      // (M = 1: one pair workgroup whose second row is -1)
+        __syncthreads();                                // the workgroup's own writes to rows[] are visible to all of it
+        for (int b = t; b < N; b += LIVE_THREADS) {
+            int2 e = make_int2(-1, -1);
+            if (b < np) e = make_int2(rows[2 * b], rows[2 * b + 1]);
+            else if (b - np < ns) e.x = rows[2 * np + b - np];
+            mix[b] = e;
+        }
+    }
+    if (t == 0) cnt[0] = M;
+}
+
+pp_status pp_launch_live_rows(pp_ctx *c, int set, const uint8_t *fixed, hipStream_t s) {
+    const int num_cu = c->plan->num_cu;
+    // the mixed launch serves 2 C < N <= 3 C rows (pp_edge_f16.hip use_mix); other sizes never read the table
+    const bool want_mix = c->N > 2 * num_cu && c->N <= 3 * num_cu;
+    hipLaunchKernelGGL(k_live_rows, dim3(1), dim3(LIVE_THREADS), 0, s, c->b.residue_mask, c->b.SC_D_mask, fixed, c->N,
+                       c->live_rows[set], want_mix ? c->live_mix[set] : nullptr, c->live_cnt[set]);
+    c->live_mix_set[set] = want_mix;      // what the sampling loop hands to the mixed launch, or null (pp_api.hip sample_impl)
+    PP_HIP_CHECK(hipGetLastError());
+    return PP_OK;
+}

@@ -21,7 +21,7 @@ SYMBOLS = ("pp_version", "pp_last_error", "pp_build_id", "pp_plan_set_knn_ties",
            "pp_affinity_create", "pp_affinity_destroy", "pp_affinity_encode", "pp_affinity_predict",
            "pp_score_rows", "pp_so2_set_grids", "pp_so2_score", "pp_dsm_loss",
            "pp_ctx_set_rng_keys", "pp_noise_seeded", "pp_add_noise_seeded", "pp_sample_seeded",
-           "pp_sample_partial", "pp_proximal_pinned")
+           "pp_sample_partial", "pp_proximal_pinned", "pp_ctx_live_rows")
 
 
 FIX_MODES = {"hold": 0, "renoise": 1}         # PP_FIX_HOLD, PP_FIX_RENOISE
@@ -122,6 +122,7 @@ def load():
     lib.pp_sample_seeded.argtypes = [vp, vp, vp, i, i, C.c_uint64, vp]
     lib.pp_sample_partial.argtypes = [vp, vp, vp, vp, i, vp, i, i, C.c_uint64, vp, vp]
     lib.pp_proximal_pinned.argtypes = [vp, vp, vp, f, i, vp, vp, vp, vp, vp, vp, vp]
+    lib.pp_ctx_live_rows.argtypes = [vp, vp, C.POINTER(C.c_int), vp]
     _lib = lib
     return lib
 
@@ -551,6 +552,13 @@ class Context:
         v = C.c_int(0)
         _check(load().pp_ctx_saturated(self.handle, C.byref(v), _stream(self.plan.device)), "pp_ctx_saturated")
         return int(v.value)
+
+    def live_rows(self):
+        """The rows a sampling run can move (residue_mask != 0 and a non-zero SC_D_mask entry), ascending: int32 [count] on the
+        device.  The layer-1 edge update of ``sample`` runs on these rows only (pp_ctx_live_rows).  Waits for the stream."""
+        rows, n = self._new(self.n_rows, dtype=torch.int32), C.c_int(0)
+        _check(load().pp_ctx_live_rows(self.handle, _ptr(rows), C.byref(n), _stream(self.plan.device)), "pp_ctx_live_rows")
+        return rows[:int(n.value)]
 
     def time_kernel(self, which: int, iters: int = 20) -> float:
         """Average ms per launch of the node-message (0) / edge-update (1) kernel, HIP events on the current stream."""
