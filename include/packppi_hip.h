@@ -368,6 +368,32 @@ pp_status pp_so2_score(const float *x, const float *sigma, size_t n, int pi_peri
 pp_status pp_dsm_loss(pp_ctx *ctx, const float *pred_score, const float *target_score, const float *t_rows,
                       const double *score_norm, double *num, double *den, void *stream);
 
+/* ---- Decoy ensembles (no reference counterpart; csrc/pp_ensemble.hip holds the arithmetic) -------------
+ * D decoys of every complex -> consensus, per-angle confidence, a score per decoy and a selected decoy.  The ctx is a packed one
+ * (or B = 1 with n_decoys = 1) whose B segments are B / D groups of D consecutive segments of equal length: segment g * D + d is
+ * decoy d of group g (packppi_amd/batch.py replicate / replicate_many).  The consensus row of (group g, row r) is
+ * seg_off[g * D] / D + r.  All pointers DEVICE:
+ *   chi [N][4] the decoys' angles; per_res [N] (pp_clash at those angles) or NULL;
+ *   mean, resultant [N / D][4]: the circular mean of the D angles (period pi where chi_1pi_periodic_mask is set, else 2 pi) and the
+ *     length of their mean resultant, 1 = all decoys agree; both 0 where SC_D_mask is 0;
+ *   dev fp64 [B]: the root mean square over the segment's unmasked angles of the wrapped difference to the STORED fp32 mean;
+ *   clash fp64 [B]: the mean of per_res over the segment's rows (untouched if per_res is NULL);
+ *   best int32 [B / D]: per group the decoy with the smallest clash (select = 1) or dev (select = 2), the lowest index on ties, a
+ *     NaN losing to any number; select = 0: decoy 0;  chi_best [N / D][4] (or NULL): that decoy's rows, bit for bit.
+ * fp64 sums in a fixed order, no float atomics: every output is bit-reproducible, and a group's outputs do not depend on the
+ * other groups of the ctx.  Three launches, never waits for the stream.  The rows come from the clamped segment table: a group whose
+ * segments differ in length reads nothing outside the batch and reports best = -1 (dev NaN, its chi_best rows not written).
+ * PP_ERR_INVALID: n_decoys < 1, B or N not a multiple of n_decoys, a null ctx / chi / mean / resultant / dev / best, per_res
+ * without clash, select outside 0 .. 2, select = 1 without per_res, a padded B > 1 ctx, a batch without SC_D_mask /
+ * chi_1pi_periodic_mask. */
+#define PP_SELECT_NONE 0
+#define PP_SELECT_CLASH 1
+#define PP_SELECT_MEDOID 2
+pp_status pp_ensemble_reduce(pp_ctx *ctx, const float *chi /* [N][4] */, int n_decoys, const float *per_res /* [N] or NULL */,
+                             int select, float *mean /* [N/D][4] */, float *resultant /* [N/D][4] */, double *dev /* [B] */,
+                             double *clash /* [B] */, int32_t *best /* [B/D] */, float *chi_best /* [N/D][4] or NULL */,
+                             void *stream);
+
 /* Measurement aid, no reference counterpart: average duration (ms) of one launch of a hot kernel
  * (which: 0 = node-message kernel, 1 = edge-update kernel), timed with HIP events on `stream`
  * around `iters` launches.  Synchronises the stream. */

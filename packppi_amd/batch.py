@@ -176,3 +176,101 @@ def unpack(packed: Batch, t: torch.Tensor) -> List[torch.Tensor]:
     """Split a per-row result [1, sum of lengths, ...] of a packed batch into one [1, L_i, ...] tensor per complex."""
     offs = packed.get("seg_offsets_host") or [int(x) for x in packed["seg_offsets"].tolist()]
     return [t[:, a:b] for a, b in zip(offs[:-1], offs[1:])]
+
+
+# ---- decoy ensembles (DESIGN.md section 16) ---------------------------------------------------------------------------------------
+_M64 = (1 << 64) - 1
+
+
+def decoy_key(key: int, d: int) -> int:
+    """The 64-bit noise key of decoy ``d`` of the complex whose key is ``key`` (``TDiffusionModule.sampling(seed=...)`` keys,
+    DESIGN.md section 12).  ``decoy_key(k, 0) == k``: decoy 0 is the complex as it is sampled today.  For ``d >= 1`` it is the
+    SplitMix64 finaliser of ``z = (k + d * 0x9E3779B97F4A7C15) mod 2**64``::
+
+        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9 mod 2**64
+        z = (z ^ (z >> 27)) * 0x94D049BB133111EB mod 2**64
+        z =  z ^ (z >> 31)
+
+    The finaliser is a bijection of the 64-bit words, so for one ``d`` different complexes keep different keys; no bits of ``k``
+    are set aside for ``d`` (keys of 2**40 and above are in use)."""
+    key, d = int(key) & _M64, int(d)
+    if d < 0:
+        raise ValueError("decoy index must not be negative")
+    if d == 0:
+        return key
+    z = (key + d * 0x9E3779B97F4A7C15) & _M64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    return z ^ (z >> 31)
+
+
+def _base_key(c, ordinal: int) -> int:
+    """The key ``sampling(seed=...)`` would give this complex alone or at place ``ordinal`` of a batch: its ``complex_key``, a B = 1
+    batch's one ``complex_keys`` entry, else the ordinal."""
+    k = c.get("complex_key") if hasattr(c, "get") else None
+    if k is None and hasattr(c, "get") and c.get("complex_keys") is not None:
+        ks = c["complex_keys"]
+        ks = ks.tolist() if isinstance(ks, torch.Tensor) else list(ks)
+        if len(ks) != 1:
+            raise ValueError(f"a B = 1 batch carries one complex key, this one has {len(ks)}")
+        k = ks[0]
+    return (int(k) if k is not None else int(ordinal)) & _M64
+
+
+def replicate_many(complexes: Iterable[Batch], n_decoys: int, keys=None) -> Batch:
+    """``n_decoys`` copies of every complex in one packed batch, group-major: segment ``g * n_decoys + d`` is decoy ``d`` of complex
+    ``g`` and carries the key ``decoy_key(k_g, d)``, where ``k_g`` is ``keys[g]`` if given, else the complex's ``complex_key`` if it
+    has one, else ``g``.  The batch gets ``complex_keys`` (what the seeded sampler reads), ``n_decoys`` and ``n_groups``.  Takes what
+    ``pack`` takes: per-complex data or B = 1 batches.
+
+    ``ValueError``: ``n_decoys < 1``, no complex, keys of this call that are not pairwise distinct (two segments would draw the same
+    noise), or a group whose copies differ in length (impossible through this function; ``lib.Context.ensemble_reduce`` relies on it)."""
+    complexes = list(complexes)
+    n_decoys = int(n_decoys)
+    if n_decoys < 1:
+        raise ValueError(f"n_decoys must be at least 1, got {n_decoys}")
+    if not complexes:
+        raise ValueError("replicate_many needs at least one complex")
+    if keys is not None and len(keys) != len(complexes):
+        raise ValueError(f"{len(keys)} keys for {len(complexes)} complexes")
+    base = [(int(keys[g]) & _M64) if keys is not None else _base_key(c, g) for g, c in enumerate(complexes)]
+    all_keys = [decoy_key(k, d) for k in base for d in range(n_decoys)]
+    if len(set(all_keys)) != len(all_keys):
+        raise ValueError("the decoy keys of this call are not pairwise distinct: two segments would draw the same noise "
+                         f"(base keys {base}, n_decoys {n_decoys})")
+    # a copy must not bring a key of its own into pack(): the keys are set below
+    plain = [Batch({k: v for k, v in c.items() if k not in ("complex_key", "complex_keys")}) for c in complexes]
+    out = pack([c for c in plain for _ in range(n_decoys)])
+    check_groups(out["seg_offsets_host"], n_decoys)
+    out["complex_keys"] = all_keys
+    out["n_decoys"] = n_decoys
+    out["n_groups"] = len(complexes)
+    return out
+
+
+def replicate(complex_or_b1_batch: Batch, n_decoys: int, key=None) -> Batch:
+    """``pack([c] * n_decoys)`` with ``complex_keys = [decoy_key(k, d) for d in range(n_decoys)]``, ``n_decoys`` and
+    ``n_groups = 1``: the decoys of one complex as the segments of one packed batch.  ``k`` is ``key`` if given, else the complex's
+    own key (``complex_key``, or a B = 1 batch's ``complex_keys`` entry), else 0 -- the key the complex has when it is sampled alone.
+    ``ValueError`` as ``replicate_many``."""
+    return replicate_many([complex_or_b1_batch], n_decoys, keys=None if key is None else [key])
+
+
+def check_groups(seg_offsets: List[int], n_decoys: int) -> List[int]:
+    """The group lengths of a segment table made of groups of ``n_decoys`` consecutive segments of equal length; ``ValueError`` if
+    the table is not one (what ``pp_ensemble_reduce`` takes: the consensus row of (group g, row r) is
+    ``seg_offsets[g * n_decoys] / n_decoys + r``)."""
+    offs = [int(x) for x in seg_offsets]
+    n_seg = len(offs) - 1
+    if n_decoys < 1:
+        raise ValueError(f"n_decoys must be at least 1, got {n_decoys}")
+    if n_seg < 1 or n_seg % n_decoys:
+        raise ValueError(f"{n_seg} segments are not groups of {n_decoys} decoys")
+    lens = [b - a for a, b in zip(offs[:-1], offs[1:])]
+    out = []
+    for g in range(n_seg // n_decoys):
+        grp = lens[g * n_decoys:(g + 1) * n_decoys]
+        if min(grp) < 1 or len(set(grp)) != 1:
+            raise ValueError(f"the {n_decoys} decoys of group {g} differ in length: {grp}")
+        out.append(grp[0])
+    return out

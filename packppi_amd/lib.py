@@ -21,11 +21,22 @@ SYMBOLS = ("pp_version", "pp_last_error", "pp_build_id", "pp_plan_set_knn_ties",
            "pp_affinity_create", "pp_affinity_destroy", "pp_affinity_encode", "pp_affinity_predict",
            "pp_score_rows", "pp_so2_set_grids", "pp_so2_score", "pp_dsm_loss",
            "pp_ctx_set_rng_keys", "pp_noise_seeded", "pp_add_noise_seeded", "pp_sample_seeded",
-           "pp_sample_partial", "pp_proximal_pinned", "pp_ctx_live_rows")
+           "pp_sample_partial", "pp_proximal_pinned", "pp_ctx_live_rows", "pp_ensemble_reduce")
 
 
 FIX_MODES = {"hold": 0, "renoise": 1}         # PP_FIX_HOLD, PP_FIX_RENOISE
 KNN_TIES = {"lower_index": 0, "aten_cpu": 1, "aten_member": 2}
+SELECT = {None: 0, "none": 0, "clash": 1, "medoid": 2}       # PP_SELECT_NONE, PP_SELECT_CLASH, PP_SELECT_MEDOID
+
+
+class EnsembleResult(dict):
+    """What ``Context.ensemble_reduce`` returns: a dict with attribute access (``res.mean``, ``res["mean"]``)."""
+
+    def __getattr__(self, k):
+        try:
+            return self[k]
+        except KeyError as e:
+            raise AttributeError(k) from e
 
 
 class PPTables(C.Structure):
@@ -123,6 +134,7 @@ def load():
     lib.pp_sample_partial.argtypes = [vp, vp, vp, vp, i, vp, i, i, C.c_uint64, vp, vp]
     lib.pp_proximal_pinned.argtypes = [vp, vp, vp, f, i, vp, vp, vp, vp, vp, vp, vp]
     lib.pp_ctx_live_rows.argtypes = [vp, vp, C.POINTER(C.c_int), vp]
+    lib.pp_ensemble_reduce.argtypes = [vp, vp, i, vp, i, vp, vp, vp, vp, vp, vp, vp]
     _lib = lib
     return lib
 
@@ -544,6 +556,36 @@ class Context:
         _check(load().pp_proximal_pinned(self.handle, _ptr(chi), _ptr(fx), float(lamda), int(num_steps), nrp, _ptr(traj), _ptr(last),
                                          _ptr(accepted), _ptr(losses), _ptr(moved), _stream(self.plan.device)), "pp_proximal_pinned")
         return (traj, last, accepted, losses, moved.bool()) if return_moved else (traj, last, accepted, losses)
+
+    def ensemble_reduce(self, chi, n_decoys, per_res=None, select=None, want_best=True):
+        """Consensus, confidence, scores and selection over the decoys of this context (pp_ensemble_reduce).
+        The context's segments are groups of ``n_decoys`` consecutive segments of equal length (``batch.replicate`` /
+        ``replicate_many``); checked here against the host table, before any launch.  ``chi`` [1, N, 4]; ``per_res`` [N]: ``clash`` at
+        those angles, or None; ``select``: "clash" (needs ``per_res``), "medoid" (the decoy closest to the consensus) or None
+        (decoy 0); the numbers 1, 2, 0 are accepted too.  Returns an ``EnsembleResult``: ``mean``, ``resultant`` [1, N / D, 4] fp32,
+        ``dev``, ``clash`` fp64 [n_segments] (``clash`` None without ``per_res``), ``best`` int32 [n_groups], ``chi_best``
+        [1, N / D, 4] (None without ``want_best``), all on the device; no host synchronisation."""
+        from .batch import check_groups
+        sel = SELECT.get(select, select) if isinstance(select, (str, type(None))) else select
+        if isinstance(sel, bool) or sel not in (0, 1, 2):
+            raise ValueError(f"select must be one of 'clash', 'medoid' or None, got {select!r}")
+        D = int(n_decoys)
+        if not self.packed and self.B != 1:
+            raise ValueError("ensemble_reduce needs a packed context (or a B = 1 one), not a padded B > 1 batch")
+        check_groups(self.seg_offsets_host, D)
+        if sel == 1 and per_res is None:
+            raise ValueError("select='clash' needs per_res (Context.clash at these angles)")
+        chi = self._chi(chi)
+        pr = self._rows(per_res, "per_res") if per_res is not None else None
+        n_cons, n_seg = self.n_rows // D, self.n_segments
+        mean, resultant = self._new(1, n_cons, 4), self._new(1, n_cons, 4)
+        dev = self._new(n_seg, dtype=torch.float64)
+        clash = self._new(n_seg, dtype=torch.float64) if pr is not None else None
+        best = self._new(n_seg // D, dtype=torch.int32)
+        chi_best = self._new(1, n_cons, 4) if want_best else None
+        _check(load().pp_ensemble_reduce(self.handle, _ptr(chi), D, _ptr(pr), int(sel), _ptr(mean), _ptr(resultant), _ptr(dev),
+                                         _ptr(clash), _ptr(best), _ptr(chi_best), _stream(self.plan.device)), "pp_ensemble_reduce")
+        return EnsembleResult(mean=mean, resultant=resultant, dev=dev, clash=clash, best=best, chi_best=chi_best)
 
     def saturated(self) -> int:
         """Sticky flag word of this context: 0 = clean; bit 0 / bit 1 = a hidden activation was clamped at 65504 in an edge-level /

@@ -380,6 +380,45 @@ class TDiffusionModule:
             return SC_D_sample, [traj[i] for i in range(cfg.num_steps)], [float(v) for v in losses[0].cpu()]
         return accepted
 
+    def sample_ensemble(self, batch, n_decoys, *, seed=None, use_proximal: bool = False, select="clash", return_all: bool = False):
+        """``n_decoys`` seeded samples of every complex in ONE packed pass, reduced on the device.  ``batch``: a
+        B = 1 batch, or a list of complexes (``batch.replicate_many``: group-major, complex g's decoys are segments
+        g * n_decoys .. g * n_decoys + n_decoys - 1).  Decoy d of a complex with key k is sampled under the key
+        ``batch.decoy_key(k, d)``: it is bit-equal to ``sampling(seed=seed)`` of that complex alone under that key, decoy 0 to what
+        ``sampling(seed=seed)`` gives today.  With ``use_proximal`` every decoy then goes through the packed proximal stage and its
+        accept rule, as ``sampling`` does for packed batches.  The per-residue clash at the final angles and
+        ``Context.ensemble_reduce`` follow: ``select`` "clash" keeps the decoy with the lowest mean clash, "medoid" the one closest
+        to the circular consensus, None decoy 0.
+
+        Returns the selected angles [1, sum of the complexes' lengths, 4]; with ``return_all`` a dict: ``decoys`` = (angles
+        [1, N, 4] of the packed batch, the packed batch), ``selected``, ``best`` [n_complexes] int32, ``dev`` / ``clash``
+        [n_complexes * n_decoys] fp64, ``consensus`` / ``confidence`` [1, sum of lengths, 4] (circular mean; resultant length, 1 = all
+        decoys agree) and ``keys`` (the decoys' noise keys, a list)."""
+        from .batch import replicate, replicate_many
+        from .lib import SELECT
+        if seed is None:
+            raise ValueError("sample_ensemble needs seed: unseeded noise is laid out over the rows of the whole batch, so a decoy would "
+                             "depend on its place in the packed batch; the seeded generator keys it by (seed, decoy key) alone")
+        if select not in SELECT:
+            raise ValueError(f"select must be one of 'clash', 'medoid' or None, got {select!r}")
+        if isinstance(batch, (list, tuple)):
+            packed = replicate_many(batch, n_decoys)
+        else:
+            if _get(batch, "seg_offsets") is not None or int(batch.num_proteins) != 1:
+                raise ValueError("sample_ensemble takes a B = 1 batch or a list of complexes")
+            packed = replicate(batch, n_decoys)
+        if _get(packed, "fixed_mask") is not None:
+            raise ValueError("ensembles under a fixed_mask are not supported: sample_ensemble samples every row")
+        cfg = self.hparams.sample_cfg
+        chi = self.sampling(packed, use_proximal=use_proximal, seed=seed)
+        ctx = self._context(packed)
+        per_res = ctx.clash(chi, cfg.violation_tolerance_factor, cfg.clash_overlap_tolerance)
+        res = ctx.ensemble_reduce(chi, packed.n_decoys, per_res=per_res, select=select)
+        if not return_all:
+            return res.chi_best
+        return dict(decoys=(chi, packed), selected=res.chi_best, best=res.best, dev=res.dev, clash=res.clash, consensus=res.mean,
+                    confidence=res.resultant, keys=list(packed.complex_keys))
+
     def sample_from(self, batch, SC_D_init, sde_noise=None):
         """The reverse-diffusion loop of ``sampling`` from given initial noised angles (parity runs inject the reference's
         own draw; the packed multi-complex path injects per-complex draws)."""
