@@ -394,6 +394,29 @@ pp_status pp_ensemble_reduce(pp_ctx *ctx, const float *chi /* [N][4] */, int n_d
                              double *clash /* [B] */, int32_t *best /* [B/D] */, float *chi_best /* [N/D][4] or NULL */,
                              void *stream);
 
+/* ---- Shell masks (csrc/pp_shell.hip holds the arithmetic) ------------------------------------------------
+ * "Which rows lie near these rows", per segment of the ctx's segment table (the complexes of a packed ctx, the B rows of a padded
+ * one, padding rows included).  PP_SHELL_CA replaces AffinityPrediction.get_local_subgraph (AffinityPrediction.py:124-145); the
+ * result, inverted, is the `fixed` array of pp_sample_partial / pp_proximal_pinned, made without a read-back.
+ *   shell[n] = 1 iff a row j of the SAME segment exists with seeds[j] != 0, (PP_SHELL_OTHER_CHAIN) chain_indices[j] !=
+ *   chain_indices[n], and
+ *     mode CA:   d2(CA_n, CA_j) < r2 (atom14 slot 1; atom_mask is not read);
+ *     mode ATOM: atoms a of n, b of j with atom_mask[n][a] != 0, atom_mask[j][b] != 0 and d2 < r2.
+ *   j = n counts: a seed row is in its own shell.  residue_mask is not consulted (the reference's get_local_subgraph does not
+ *   consult it either).  count[s] (or NULL) = the number of shell rows of segment s.
+ * Arithmetic: fp32, fp contract off; d = p - q per component, d2 = ((dx dx) + (dy dy)) + (dz dz), r2 = radius radius computed
+ * once, strict <: a NumPy float32 restatement gives the same bytes.  The pruning (ATOM mode: a CA pre-filter with bounding radii
+ * computed in the launch from the coordinates given; the seed rows compacted in LDS) changes no output byte.  xyz NULL = the batch's
+ * X.  Every output byte has one writer (count: integer atomics); one kernel behind one memset; never waits for the stream.
+ * PP_ERR_INVALID: a null ctx, seeds or shell; an unknown mode or flag bit; radius not finite or <= 0; PP_SHELL_ATOM on a batch
+ * without atom_mask; PP_SHELL_OTHER_CHAIN on a batch without chain_indices. */
+#define PP_SHELL_CA 0          /* CA-CA distance (atom14 slot 1): AffinityPrediction.get_local_subgraph */
+#define PP_SHELL_ATOM 1        /* any pair of present atoms */
+#define PP_SHELL_OTHER_CHAIN 1 /* flag: the partner row must have a different chain_indices */
+pp_status pp_ctx_shell(pp_ctx *ctx, const uint8_t *seeds /* DEVICE [N] */, int mode, float radius, int flags,
+                       const float *xyz /* DEVICE [N,14,3] or NULL = the batch's X */,
+                       uint8_t *shell /* DEVICE [N] */, int32_t *count /* DEVICE [n_seg] or NULL */, void *stream);
+
 /* Measurement aid, no reference counterpart: average duration (ms) of one launch of a hot kernel
  * (which: 0 = node-message kernel, 1 = edge-update kernel), timed with HIP events on `stream`
  * around `iters` launches.  Synchronises the stream. */

@@ -10,7 +10,8 @@ Where the work runs: the pretrained network at t = 0 is ``pp_score`` (the h_V it
 a second plan of the score-network kernels (weights.mutation_branch_state_dict) on a context whose residue_mask is the
 local mask; ``k_affinity_embed`` does what lies between the two networks and ``k_affinity_head`` the max over residues and
 ddg_predictor (csrc/pp_node.hip, csrc/pp_affinity.hip).  Only the local mask is computed on the host, with torch.cdist on a
-CPU copy of the CA coordinates, which is the reference CPU path exactly.
+CPU copy of the CA coordinates, which is the reference CPU path exactly; ``predict_many(local_mask="device")`` takes the masks
+of all sets from one pp_ctx_shell launch instead.
 """
 from typing import Any, Dict, List, Optional
 
@@ -157,23 +158,33 @@ class AffinityPrediction:
     __call__ = forward
 
     @torch.no_grad()
-    def predict_many(self, batches):
+    def predict_many(self, batches, local_mask="host"):
         """ddg and ddg_inv [n] of n mutation sets (``featurize.mutant_data`` outputs or B = 1 batches): one packed context
-        per branch.  Every row of every set is kept (batch.pack(trim=False)); each set gets the bits of its own forward."""
+        per branch.  Every row of every set is kept (batch.pack(trim=False)); each set gets the bits of its own forward.
+        ``local_mask``: "host" (default, the pinned reference path: ``get_local_subgraph`` once per set, torch.cdist on CPU copies)
+        or "device": the local masks of all sets come from ONE ``Context.shell(mode="ca", radius=10)`` launch on the wild-type
+        context of the pretrained network (pp_ctx_shell) -- no copy of the coordinates to the host.  The two
+        agree wherever no CA pair lies within rounding of the radius; mode ``linear`` has no local mask and ignores the switch."""
+        if local_mask not in ("host", "device"):
+            raise ValueError("local_mask must be 'host' or 'device'")
         batches = list(batches)
         wt = pack(batches, trim=False).to(self.device)
         missing = [k for k in MUT_KEYS if k not in wt]
         if missing:
             raise RuntimeError(f"predict_many needs mutation batches (missing {missing})")
         offs = wt["seg_offsets_host"]
-        h_wt, h_mt = self._features(wt) if self.hparams.mode != "network" else self._packed_network(batches, wt)
+        h_wt, h_mt = self._features(wt) if self.hparams.mode != "network" else self._packed_network(batches, wt, local_mask)
         ddg, inv = self.head.predict(h_wt, h_mt, offs)
         return ddg, inv
 
-    def _packed_network(self, batches, wt):
+    def _packed_network(self, batches, wt, local_mask="host"):
         self._contexts = []
         mt = mutant_view(wt)
         p_wt, p_mt = self.get_pret_feature(wt), self.get_pret_feature(mt)
+        if local_mask == "device":
+            # the wild-type context get_pret_feature just made: its segment table keeps every set's shell inside the set
+            ctx = self._mutation_context(wt, self._contexts[0].shell(wt["mut_mask"], radius=10.0, mode="ca"))
+            return self.encode(wt, p_wt, ctx), self.encode(mt, p_mt, ctx)
         local = []
         for b in batches:
             X = b["X"] if b["X"].dim() == 4 else b["X"].unsqueeze(0)

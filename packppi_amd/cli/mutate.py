@@ -1,0 +1,119 @@
+"""``mutate`` command line: PDB + mutation sets in -> one repacked mutant structure per set (``TDiffusionModule.mutate``,
+DESIGN.md section 17).
+
+    python -m packppi_amd.cli.mutate --input x.pdb (--mutstr RA47A,EA48A | --mutlist FILE) --ckpt_path model.ckpt --seed 7
+        [--n_decoys 8] [--select clash|medoid] [--use_proximal] [--radius 10] [--shell ca|atom] [--fixed_mode hold|renoise]
+        --outdir out [--ap_ckpt ap.ckpt --pre_ckpt_path pre.ckpt]
+
+Every set is put into the complex, the residues within --radius of a mutated residue (the shell, chosen on the device) are
+repacked around the new side chains, every other residue keeps the input's angles bit for bit.  All sets go through one packed
+pass.  Writes ``mutant_<tag>.pdb`` per set (the mutant's residue names and atoms) and ``mutants.csv``.  --mutlist FILE: one set
+per line, comma-separated as --mutstr, ``#`` lines skipped (the format of eval_affinity --mutlist).
+"""
+import argparse
+import os
+
+import numpy as np
+
+from ..featurize import parse_mutstr
+from ..pdb_io import from_pdb_file, to_pdb
+from .eval_diffusion import load_model
+
+AP_NOTE = ("The ddG values come from the unchanged AffinityPrediction.predict_many on featurize.mutant_data. The AP model was "
+           "trained with zeroed mutant angles, so it does not see the packed mutant.")
+
+
+def read_sets(args):
+    if args.mutlist:
+        with open(args.mutlist) as fh:
+            return [ln.strip() for ln in fh if ln.strip() and not ln.lstrip().startswith("#")]
+    return [args.mutstr]
+
+
+def predict_ddg(protein, sets, args):
+    """(ddg, ddg_inv) lists of PackPPI-AP for the sets, from the wild type and the zero-angle mutant of ``mutant_data``."""
+    from ..affinity import AffinityPrediction
+    from ..featurize import mutant_data
+    print(f"----- Loading {args.ap_ckpt} checkpoint! -----")
+    ap = AffinityPrediction.load_from_checkpoint(args.ap_ckpt, pre_checkpoint_path=args.pre_ckpt_path, map_location=args.device).eval()
+    ddg, inv = ap.predict_many([mutant_data(protein, parse_mutstr(s)) for s in sets])
+    return ddg.cpu().tolist(), inv.cpu().tolist()
+
+
+def evaluate_model(model, args):
+    print("----- Starting evaluation! -----")
+    os.makedirs(args.outdir, exist_ok=True)
+    protein = from_pdb_file(args.input, mse_to_met=True)
+    protein["pdb_path"] = args.input
+    sets = read_sets(args)
+    results = model.mutate([(protein, s) for s in sets], seed=args.seed, radius=args.radius, shell=args.shell,
+                           n_decoys=args.n_decoys, use_proximal=args.use_proximal, select=args.select, fixed_mode=args.fixed_mode)
+    ddg = predict_ddg(protein, sets, args) if args.ap_ckpt else None
+    rows = ["tag,shell_rows,selected_decoy,clash,dev" + (",ddg,ddg_inv" if ddg else "")]
+    for i, (s, r) in enumerate(zip(sets, results)):
+        tag = (r["tag"] or s).replace(",", "_")
+        b = r["batch"]
+        mutant = dict(protein, atom_positions=r["X"][0].cpu().numpy(), atom_mask=b["atom_mask"][0].cpu().numpy(),
+                      aaindex=np.where(b["residue_mask"][0].cpu().numpy() > 0, b["residue_type"][0].cpu().numpy(),
+                                       np.asarray(protein["aaindex"])))
+        with open(os.path.join(args.outdir, f"mutant_{tag}.pdb"), "w") as fh:
+            fh.write(to_pdb(mutant))
+        best = int(r["best"])
+        line = f"{tag},{int(r['shell'].sum())},{best},{float(r['clash'][best])!r},{float(r['dev'][best])!r}"
+        if ddg:
+            line += f",{ddg[0][i]!r},{ddg[1][i]!r}"
+        rows.append(line)
+        print(f"----- {tag}: {int(r['shell'].sum())} residues repacked, decoy {best} of {args.n_decoys} selected -----")
+    with open(os.path.join(args.outdir, "mutants.csv"), "w") as fh:
+        fh.write("\n".join(rows) + "\n")
+    if model.saturated():
+        print("----- WARNING: sticky flag %d (f16 saturation or non-finite input) in the score network -----" % model.saturated())
+    print("----- Finishing evaluation! -----")
+
+
+def build_parser():
+    p = argparse.ArgumentParser(description="Model mutants: repack the shell around each mutation set. " + AP_NOTE)
+    p.add_argument("--input", type=str, help="The input pdb file path.", required=True)
+    g = p.add_mutually_exclusive_group(required=True)
+    g.add_argument("--mutstr", type=str, help='One mutation set: wild-type residue, chain ID, position and mutant residue, several '
+                   'separated by commas (e.g. "RA47A,EA48A").')
+    g.add_argument("--mutlist", type=str, help="File with one mutation set per line (as eval_affinity --mutlist); all sets run in "
+                   "one packed pass.")
+    p.add_argument("--outdir", type=str, help="Directory to store outputs.", required=True)
+    p.add_argument("--device", type=str, help="cuda (the MI355X HIP device)", default="cuda")
+    p.add_argument("--ckpt_path", type=str, default=None, help="Lightning checkpoint of the score network (else $PACKPPI_CKPT, else "
+                   "the config tree's ckpt_path).")
+    p.add_argument("--config_dir", type=str, default=None, help="The reference's configs/ directory (else $PACKPPI_CONFIG_DIR).")
+    p.add_argument("--steps", type=int, default=None, help="Diffusion steps (reference schedule: 30).")
+    p.add_argument("--random_weights", type=int, default=None, help="Seeded stand-in weights instead of a checkpoint.")
+    p.add_argument("--seed", type=int, required=True, help="Seed of the sampling noise, drawn by the counter-based generator on the "
+                   "device; set i of the call has the noise key i.")
+    p.add_argument("--n_decoys", type=int, default=1, metavar="D", help="Decoys per set, drawn in one packed pass; the selected one "
+                   "is written.")
+    p.add_argument("--select", choices=("clash", "medoid"), default="clash", help="Keep the decoy with the lowest mean clash (clash) "
+                   "or the one closest to the circular consensus (medoid).")
+    p.add_argument("--use_proximal", action="store_true", help="Run the pinned proximal clash optimisation on the shell.")
+    p.add_argument("--radius", type=float, default=10.0, help="Shell radius in Angstrom.")
+    p.add_argument("--shell", choices=("ca", "atom"), default="ca", help="Shell rule: CA within the radius of a mutated CA (ca, the "
+                   "local subgraph of PackPPI-AP) or any atom within it of an atom of a mutated residue (atom).")
+    p.add_argument("--fixed_mode", choices=("hold", "renoise"), default="renoise", help="What the kept residues look like to the "
+                   "network during sampling: re-noised to each step's level (renoise) or clean throughout (hold).")
+    p.add_argument("--ap_ckpt", type=str, default=None, help="AffinityPrediction checkpoint: adds ddg and ddg_inv to mutants.csv. "
+                   + AP_NOTE)
+    p.add_argument("--pre_ckpt_path", type=str, default=None, help="With --ap_ckpt: the pretrained PackPPI checkpoint (default: the "
+                   "one named in the AP checkpoint's hyper_parameters).")
+    return p
+
+
+def main(argv=None):
+    p = build_parser()
+    args = p.parse_args(argv)
+    if args.n_decoys < 1:
+        p.error("--n_decoys must be at least 1")
+    if args.pre_ckpt_path and not args.ap_ckpt:
+        p.error("--pre_ckpt_path belongs to --ap_ckpt")
+    evaluate_model(load_model(args), args)
+
+
+if __name__ == "__main__":
+    main()

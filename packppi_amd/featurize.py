@@ -125,6 +125,32 @@ def parse_mutstr(mutstr: str):
     return muts
 
 
+def resolve_mutations(protein: Dict, mutations, log=print):
+    """The lookup of ``mutant_data`` (skempi_dataset.py:150-185), shared with ``mutant_model_data``: [(row mask [L] bool, mutant
+    residue type, tag)] of the mutations that apply, in order.  A mutation is looked up by chain and the RAW PDB residue number; one
+    whose chain is absent or whose target is not one of the 20 types is skipped with the reference's message; one that matches no
+    or several residues, or whose wild-type letter disagrees with the structure, raises ValueError."""
+    rtype = torch.from_numpy(np.asarray(protein["aaindex"])).long()
+    raw_index = np.asarray(protein["residue_index"]).astype(np.int64)
+    chain_id = np.asarray(protein["chain_id"])
+    path = protein.get("pdb_path")
+    out = []
+    for m in mutations:
+        tag = f"{m['wt']}{m['chain']}{m['resseq']}{m['mt']}"
+        if m["chain"] not in chain_id or m["mt"] not in rc.restypes:
+            log(f"Ignore the mutation: {tag}")
+            continue
+        index = torch.from_numpy((chain_id == m["chain"]) & (raw_index == int(m["resseq"])))
+        hits = int(index.sum())
+        if hits != 1:
+            raise ValueError(f"The mutation: {tag} matches {hits} residues of chain {m['chain']} in {path} file")
+        ref_wt = rc.restypes[int(rtype[index])]
+        if ref_wt != m["wt"]:
+            raise ValueError(f"The mutation: {tag} is inconsistent with wild-type {ref_wt} in {path} file")
+        out.append((index, rc.restype_order[m["mt"]], tag))
+    return out
+
+
 def mutant_data(protein: Dict, mutations=None, ddg=None, log=print) -> Batch:
     """Per-complex wild-type and mutant tensors, as ``SkempiDataset.prot_to_data`` lays them out without ESM
     (skempi_dataset.py:73-262): the keys of ``protein_to_data`` plus ``ddg``, ``mut_mask`` and the ``*_mut`` keys.
@@ -142,7 +168,6 @@ def mutant_data(protein: Dict, mutations=None, ddg=None, log=print) -> Batch:
     rtype = torch.from_numpy(np.asarray(protein["aaindex"])).long()
     amask = torch.from_numpy(np.asarray(protein["atom_mask"])).float()
     raw_index = torch.from_numpy(np.asarray(protein["residue_index"])).long()
-    chain_id = np.asarray(protein["chain_id"])
     if ddg is None:
         ddg = protein.get("ddG", 0.0)
     ddg = torch.tensor(ddg, dtype=torch.float32)
@@ -156,20 +181,7 @@ def mutant_data(protein: Dict, mutations=None, ddg=None, log=print) -> Batch:
     pi1 = torch.from_numpy(rc.chi_pi_periodic)[rtype].bool()
 
     rtype_mut, amask_mut, sc_mut, sc_sc_mut = rtype.clone(), amask.clone(), sc.clone(), sc_sc.clone()
-    path = protein.get("pdb_path")
-    for m in mutations:
-        tag = f"{m['wt']}{m['chain']}{m['resseq']}{m['mt']}"
-        if m["chain"] not in chain_id or m["mt"] not in rc.restypes:
-            log(f"Ignore the mutation: {tag}")
-            continue
-        index = torch.from_numpy((chain_id == m["chain"]) & (raw_index.numpy() == int(m["resseq"])))
-        hits = int(index.sum())
-        if hits != 1:
-            raise ValueError(f"The mutation: {tag} matches {hits} residues of chain {m['chain']} in {path} file")
-        ref_wt = rc.restypes[int(rtype[index])]
-        if ref_wt != m["wt"]:
-            raise ValueError(f"The mutation: {tag} is inconsistent with wild-type {ref_wt} in {path} file")
-        mt = rc.restype_order[m["mt"]]
+    for index, mt, _ in resolve_mutations(protein, mutations, log):
         rtype_mut[index] = mt
         amask_mut[index] = torch.tensor([1.0 if a else 0.0 for a in rc.atom14_names[mt]], dtype=torch.float32)
         sc_mut[index] = 0.0
@@ -213,3 +225,52 @@ def mutant_data(protein: Dict, mutations=None, ddg=None, log=print) -> Batch:
 def mutant_batch(protein: Dict, mutstr: str, log=print) -> Batch:
     """B = 1 batch of one mutation string, as eval_affinity.py:45-73 builds it (``ddg`` of shape [1])."""
     return as_single(mutant_data(protein, parse_mutstr(mutstr), log=log))
+
+
+# ---- the mutant as a sampling input (DESIGN.md section 17) -----------------------------------------------------------------------
+
+def mutant_model_data(protein: Dict, mutations=None, log=print) -> Batch:
+    """The mutant as a batch the sampler can pack: ``protein_to_data`` with the mutated rows rewritten for their NEW residue type.
+    ``mutant_data`` builds the mutant the way PackPPI-AP consumes it (chi mask from the wild-type atoms, zero angles); this one
+    builds it for ``TDiffusionModule.repack`` / ``mutate``.  Lookup, skipping and errors are ``mutant_data``'s (``resolve_mutations``).
+
+    Every row no mutation names carries exactly what ``protein_to_data`` gives it.  A mutated row gets the new ``residue_type``,
+    ``atom_mask`` from the new type's atom14 table, ``SC_D`` = ``SC_D_sincos`` = 0, ``SC_D_mask`` = the new type's chi table x
+    ``residue_mask`` (not the wild-type atoms), the periodic masks from ``chi_pi_periodic`` of the new type, and X with the
+    backbone slots 0-3 kept and the side-chain slots 4-13 zeroed: the old side chain is out of the way, ``atom14`` rebuilds the new
+    one from the backbone frame.  The batch also carries ``mut_mask`` (int64 [L], 1 on every row a mutation that applied names --
+    also one to the residue's own type: that row is rebuilt and resampled like the others) and ``mutation_tag`` (the applied tags,
+    comma-separated)."""
+    if mutations is None:
+        mutations = protein.get("mutations", [])
+    data = protein_to_data(protein)
+    for k in ("X", "atom_mask", "residue_type", "SC_D", "SC_D_sincos", "SC_D_mask", "chi_1pi_periodic_mask", "chi_2pi_periodic_mask"):
+        data[k] = data[k].clone()
+    rmask = data["residue_mask"]
+    mut_mask = torch.zeros(int(data["num_nodes"]), dtype=torch.int64)
+    chi_table, pi_table = torch.from_numpy(rc.chi_mask_atom14).float(), torch.from_numpy(rc.chi_pi_periodic).bool()
+    atom_table = torch.from_numpy(np.asarray(rc.atom14_mask)).float()
+    tags = []
+    for index, mt, tag in resolve_mutations(protein, mutations, log):
+        m1 = rmask[index]                                               # [1]
+        sc_mask = chi_table[mt][None] * m1[:, None]
+        data["residue_type"][index] = (mt * m1).long()
+        data["atom_mask"][index] = atom_table[mt][None] * m1[:, None]
+        data["SC_D"][index] = 0.0
+        data["SC_D_sincos"][index] = 0.0
+        data["SC_D_mask"][index] = sc_mask
+        data["chi_1pi_periodic_mask"][index] = torch.logical_and(sc_mask, pi_table[mt][None])
+        data["chi_2pi_periodic_mask"][index] = torch.logical_and(sc_mask, ~pi_table[mt][None])
+        X = data["X"][index]
+        X[:, 4:] = 0.0
+        data["X"][index] = X
+        mut_mask[index] = 1
+        tags.append(tag)
+    data["mut_mask"] = mut_mask
+    data["mutation_tag"] = ",".join(tags)
+    return data
+
+
+def mutant_model_batch(protein: Dict, mutstr: str, log=print) -> Batch:
+    """B = 1 batch of ``mutant_model_data`` for one mutation string ("RA47A,EA48A")."""
+    return as_single(mutant_model_data(protein, parse_mutstr(mutstr), log=log))

@@ -21,12 +21,14 @@ SYMBOLS = ("pp_version", "pp_last_error", "pp_build_id", "pp_plan_set_knn_ties",
            "pp_affinity_create", "pp_affinity_destroy", "pp_affinity_encode", "pp_affinity_predict",
            "pp_score_rows", "pp_so2_set_grids", "pp_so2_score", "pp_dsm_loss",
            "pp_ctx_set_rng_keys", "pp_noise_seeded", "pp_add_noise_seeded", "pp_sample_seeded",
-           "pp_sample_partial", "pp_proximal_pinned", "pp_ctx_live_rows", "pp_ensemble_reduce")
+           "pp_sample_partial", "pp_proximal_pinned", "pp_ctx_live_rows", "pp_ensemble_reduce", "pp_ctx_shell")
 
 
 FIX_MODES = {"hold": 0, "renoise": 1}         # PP_FIX_HOLD, PP_FIX_RENOISE
 KNN_TIES = {"lower_index": 0, "aten_cpu": 1, "aten_member": 2}
 SELECT = {None: 0, "none": 0, "clash": 1, "medoid": 2}       # PP_SELECT_NONE, PP_SELECT_CLASH, PP_SELECT_MEDOID
+SHELL_MODES = {"ca": 0, "atom": 1}            # PP_SHELL_CA, PP_SHELL_ATOM
+SHELL_OTHER_CHAIN = 1                         # PP_SHELL_OTHER_CHAIN
 
 
 class EnsembleResult(dict):
@@ -135,6 +137,7 @@ def load():
     lib.pp_proximal_pinned.argtypes = [vp, vp, vp, f, i, vp, vp, vp, vp, vp, vp, vp]
     lib.pp_ctx_live_rows.argtypes = [vp, vp, C.POINTER(C.c_int), vp]
     lib.pp_ensemble_reduce.argtypes = [vp, vp, i, vp, i, vp, vp, vp, vp, vp, vp, vp]
+    lib.pp_ctx_shell.argtypes = [vp, vp, i, f, i, vp, vp, vp, vp]
     _lib = lib
     return lib
 
@@ -586,6 +589,30 @@ class Context:
         _check(load().pp_ensemble_reduce(self.handle, _ptr(chi), D, _ptr(pr), int(sel), _ptr(mean), _ptr(resultant), _ptr(dev),
                                          _ptr(clash), _ptr(best), _ptr(chi_best), _stream(self.plan.device)), "pp_ensemble_reduce")
         return EnsembleResult(mean=mean, resultant=resultant, dev=dev, clash=clash, best=best, chi_best=chi_best)
+
+    def shell(self, seeds, radius=10.0, mode="ca", other_chain=False, xyz=None, want_count=False):
+        """The rows near the ``seeds`` rows, per complex, on the device (pp_ctx_shell): bool [B, L] (packed:
+        [1, N]), with ``want_count`` also the shell rows per segment, int32 [n_segments].  ``seeds``: [B, L] bool / uint8 / int (any
+        non-zero entry is a seed), on the host or the device.  ``mode`` "ca": CA-CA distance below ``radius``, the local mask of
+        AffinityPrediction.get_local_subgraph; "atom": any pair of present atoms below it.  ``other_chain``: the seed must lie in
+        another chain -- ``shell(all rows, mode="atom", other_chain=True)`` is the interface.  ``xyz`` [B, L, 14, 3]: coordinates
+        other than the batch's X (``atom14`` of sampled angles).  A seed row is in its own shell; ``residue_mask`` is not consulted.
+        ``~shell`` is the ``fixed`` mask of ``sample_partial`` / ``proximal_packed``.  No host synchronisation."""
+        if mode not in SHELL_MODES:
+            raise ValueError(f"mode must be one of {sorted(SHELL_MODES)}")
+        sd = torch.as_tensor(seeds).to(device=self.plan.device)
+        if sd.numel() != self.n_rows:
+            raise ValueError(f"seeds has {sd.numel()} elements, this context has {self.n_rows} rows")
+        sd = (sd != 0).to(torch.uint8).reshape(-1).contiguous()
+        if xyz is not None:
+            xyz = xyz.to(device=self.plan.device, dtype=torch.float32).contiguous()
+            if xyz.numel() != self.n_rows * 42:
+                raise ValueError(f"xyz has {xyz.numel()} elements, this context has {self.n_rows} rows x 14 x 3")
+        out = self._new(self.B, self.L, dtype=torch.uint8)
+        count = self._new(self.n_segments, dtype=torch.int32) if want_count else None
+        _check(load().pp_ctx_shell(self.handle, _ptr(sd), SHELL_MODES[mode], float(radius), SHELL_OTHER_CHAIN if other_chain else 0,
+                                   _ptr(xyz), _ptr(out), _ptr(count), _stream(self.plan.device)), "pp_ctx_shell")
+        return (out.bool(), count) if want_count else out.bool()
 
     def saturated(self) -> int:
         """Sticky flag word of this context: 0 = clean; bit 0 / bit 1 = a hidden activation was clamped at 65504 in an edge-level /

@@ -419,6 +419,149 @@ class TDiffusionModule:
         return dict(decoys=(chi, packed), selected=res.chi_best, best=res.best, dev=res.dev, clash=res.clash, consensus=res.mean,
                     confidence=res.resultant, keys=list(packed.complex_keys))
 
+    def repack_ensemble(self, batch, fixed_mask=None, *, n_decoys, seed, fixed_chi=None, fixed_mode="renoise",
+                        use_proximal: bool = False, select="clash", return_all: bool = False):
+        """``sample_ensemble`` under a pin: ``n_decoys`` seeded partial repackings of every complex in ONE packed
+        pass, reduced on the device.  ``batch``: a B = 1 batch, or a list of complexes (per-complex data or B = 1 batches).  Every
+        complex carries its ``fixed_mask`` (1 = keep; [1, L] on a B = 1 batch, [L] on per-complex data), or ``fixed_mask`` gives it:
+        one mask for a B = 1 batch, a list of masks for a list.  ``fixed_chi`` likewise ([1, L, 4], or a list; default each
+        complex's ``SC_D``).  The complexes are replicated with ``batch.replicate_many`` -- ``pack`` concatenates the masks --, the
+        packed batch goes through ``repack`` (with ``use_proximal`` the pinned proximal stage, every decoy divided by its complex's
+        unpacked size as the complex alone divides), then ``Context.clash`` and ``Context.ensemble_reduce``.
+
+        Decoy d of a complex with key k has exactly the bits of ``repack`` of that complex alone under the key ``decoy_key(k, d)``,
+        with and without ``use_proximal``.  pp_ensemble_reduce is used unchanged: kept rows are identical in every decoy, so their
+        ``resultant`` is 1 to rounding and they add (to rounding) nothing to ``dev``; they enter the per-decoy means of ``dev`` and
+        ``clash`` with the same weight in all decoys of a group, so they dilute both equally and do not change the ranking.
+        Returns what ``sample_ensemble`` returns."""
+        from .batch import Batch, replicate_many
+        from .lib import SELECT
+        if select not in SELECT:
+            raise ValueError(f"select must be one of 'clash', 'medoid' or None, got {select!r}")
+        single = not isinstance(batch, (list, tuple))
+        if single and (_get(batch, "seg_offsets") is not None or int(batch.num_proteins) != 1):
+            raise ValueError("repack_ensemble takes a B = 1 batch or a list of complexes")
+        complexes = [batch] if single else list(batch)
+        masks = [fixed_mask] if single else (list(fixed_mask) if fixed_mask is not None else [None] * len(complexes))
+        refs = [fixed_chi] if single else (list(fixed_chi) if fixed_chi is not None else [None] * len(complexes))
+        if len(masks) != len(complexes) or len(refs) != len(complexes):
+            raise ValueError(f"{len(masks)} fixed masks / {len(refs)} fixed_chi for {len(complexes)} complexes")
+        pinned, sizes = [], []
+        for c, m in zip(complexes, masks):
+            lead = c["residue_type"].dim() == 2
+            n = int(c["residue_type"].shape[-1])
+            m = _get(c, "fixed_mask") if m is None else m
+            if m is None:
+                raise ValueError("repack_ensemble needs a fixed_mask for every complex; sample_ensemble samples every row")
+            m = torch.as_tensor(m).to(c["residue_type"].device) != 0
+            if m.numel() != n:
+                raise ValueError(f"fixed_mask has {m.numel()} elements, the complex has {n} rows")
+            p = Batch(c)
+            p["fixed_mask"] = m.reshape(1, n) if lead else m.reshape(n)
+            pinned.append(p)
+            sizes.append(n)
+        packed = replicate_many(pinned, n_decoys)
+        D = int(packed.n_decoys)
+        ref = None
+        if any(r is not None for r in refs):
+            # the kept angles of every decoy, cut to the rows pack() kept: D copies per complex, in the order of the segments
+            offs = packed.seg_offsets_host
+            ref = torch.cat([torch.as_tensor(c["SC_D"] if r is None else r).to(device=packed.SC_D.device, dtype=torch.float32)
+                             .reshape(-1, 4)[:offs[g * D + 1] - offs[g * D]]
+                             for g, (c, r) in enumerate(zip(complexes, refs)) for _ in range(D)]).unsqueeze(0)
+        cfg = self.hparams.sample_cfg
+        chi = self.repack(packed, seed=seed, fixed_chi=ref, fixed_mode=fixed_mode, use_proximal=use_proximal,
+                          norm_rows=[n for n in sizes for _ in range(D)] if use_proximal else None)
+        ctx = self._context(packed)
+        per_res = ctx.clash(chi, cfg.violation_tolerance_factor, cfg.clash_overlap_tolerance)
+        res = ctx.ensemble_reduce(chi, D, per_res=per_res, select=select)
+        if not return_all:
+            return res.chi_best
+        return dict(decoys=(chi, packed), selected=res.chi_best, best=res.best, dev=res.dev, clash=res.clash, consensus=res.mean,
+                    confidence=res.resultant, keys=list(packed.complex_keys))
+
+    def mutate(self, proteins_and_mutations, *, seed, radius=10.0, shell="ca", n_decoys=1, use_proximal: bool = False,
+               select="clash", fixed_mode="renoise", max_rows=200_000, log=print):
+        """Mutant modelling: put each mutation set into its complex, repack what it touches, return the mutant.
+        ``proteins_and_mutations``: a list of ``(protein dict, mutations)`` pairs, ``mutations`` a string ("RA47A,EA48A") or dicts as
+        ``featurize.parse_mutstr`` returns them; several sets of one protein are repeated pairs.  Set i of the call gets the noise
+        key i unless its pair carries a third entry, the ``complex_key``.
+
+        Per chunk of sets (packed so that ``n_decoys`` x rows <= ``max_rows``, as ``parallel.sample_sharded`` groups; a set shorter
+        than 32 rows goes alone): ``featurize.mutant_model_data`` per set, one packed batch, one context, ONE ``Context.shell`` launch
+        with seeds = ``mut_mask`` (``shell`` "ca": CA within ``radius`` of a mutated CA, PackPPI-AP's local subgraph; "atom": any
+        atom within ``radius`` of an atom of a mutated residue, on the coordinates ``atom14`` builds at the batch's angles, the new
+        side chains at chi = 0), ``fixed = ~shell`` on the device without a read-back, ``repack_ensemble``, and ``atom14`` of the
+        selected decoy.
+
+        A set's result does not depend on what it was packed with, and every row outside its shell keeps the wild type's ``SC_D``
+        bit for bit.  Returns one dict per set: ``tag``, ``key``, ``SC_D`` [1, L, 4] (the selected decoy), ``X`` [1, L, 14, 3],
+        ``shell`` bool [1, L], ``best`` (int32 scalar tensor), ``clash`` / ``dev`` fp64 [n_decoys], ``keys`` (the decoys' noise keys)
+        and ``batch`` (the mutant B = 1 batch: residue types and atom mask of the mutant), tensors on the device."""
+        from .batch import as_single, pack, unpack
+        from .featurize import mutant_model_data, parse_mutstr
+        from .functional import _ctx_for
+        from .lib import SHELL_MODES
+        if shell not in SHELL_MODES:
+            raise ValueError(f"shell must be one of {sorted(SHELL_MODES)}")
+        n_decoys = int(n_decoys)
+        if n_decoys < 1:
+            raise ValueError(f"n_decoys must be at least 1, got {n_decoys}")
+        sets, alone = [], []
+        for i, pair in enumerate(proteins_and_mutations):
+            protein, muts = pair[0], pair[1]
+            key = int(pair[2]) if len(pair) > 2 and pair[2] is not None else i
+            data = mutant_model_data(protein, parse_mutstr(muts) if isinstance(muts, str) else muts, log=log)
+            n = int(data["num_nodes"])
+            alone.append(n < 32 or int((data["residue_mask"] > 0).sum()) < 32)            # host tensors: no device read-back
+            b = as_single(data).to(self.device)
+            b["complex_key"] = key
+            sets.append(b)
+        groups, cur, rows_in = [], [], 0
+        for i, b in enumerate(sets):
+            n = int(b["max_size"])
+            if alone[i]:
+                groups.append([i])
+                continue
+            if cur and n_decoys * (rows_in + n) > max_rows:
+                groups.append(cur)
+                cur, rows_in = [], 0
+            cur.append(i)
+            rows_in += n
+        if cur:
+            groups.append(cur)
+        results = [None] * len(sets)
+        for grp in groups:
+            members = [sets[i] for i in grp]
+            pb = pack(members)
+            gctx = _ctx_for(pb)
+            xyz = gctx.atom14(pb.SC_D) if shell == "atom" else None
+            sh = gctx.shell(pb.mut_mask, radius=radius, mode=shell, xyz=xyz)              # bool [1, N], stays on the device
+            pinned = []
+            for b, part in zip(members, unpack(pb, ~sh)):
+                n = int(b["max_size"])
+                fx = part
+                if part.shape[1] != n:            # pack() dropped trailing rows without a residue: they keep their (zero) angles
+                    fx = torch.ones(1, n, dtype=torch.bool, device=part.device)
+                    fx[:, :part.shape[1]] = part
+                p = type(b)(b)
+                p["fixed_mask"] = fx
+                pinned.append(p)
+            out = self.repack_ensemble(pinned, n_decoys=n_decoys, seed=seed, fixed_mode=fixed_mode, use_proximal=use_proximal,
+                                       select=select, return_all=True)
+            pos = gctx.atom14(out["selected"])
+            parts = zip(grp, members, unpack(pb, out["selected"]), unpack(pb, pos), unpack(pb, sh))
+            for g, (i, b, chi, x, s) in enumerate(parts):
+                n, m = int(b["max_size"]), chi.shape[1]
+                if m != n:
+                    chi = torch.cat([chi, b["SC_D"][:, m:]], 1)
+                    x = torch.cat([x, b["X"][:, m:]], 1)
+                    s = torch.cat([s, torch.zeros(1, n - m, dtype=torch.bool, device=s.device)], 1)
+                results[i] = dict(tag=b["mutation_tag"], key=int(b["complex_key"]), SC_D=chi, X=x, shell=s, best=out["best"][g],
+                                  clash=out["clash"][g * n_decoys:(g + 1) * n_decoys], dev=out["dev"][g * n_decoys:(g + 1) * n_decoys],
+                                  keys=out["keys"][g * n_decoys:(g + 1) * n_decoys], batch=b)
+        return results
+
     def sample_from(self, batch, SC_D_init, sde_noise=None):
         """The reverse-diffusion loop of ``sampling`` from given initial noised angles (parity runs inject the reference's
         own draw; the packed multi-complex path injects per-complex draws)."""

@@ -3,6 +3,12 @@
 A selection names the residues to REPACK; the rows outside it are the ones the sampler keeps (``fixed_mask = ~selection``).
 Residues are addressed as ``featurize.mutant_data`` looks mutations up: by chain ID and the residue number of the PDB file
 (``protein["chain_id"]``, ``protein["residue_index"]``) -- not by the offset numbering the featurisation gives later chains.
+
+A selection can also be made on the device, from the batch itself: ``Context.shell(seeds, radius, mode, other_chain)``
+(pp_ctx_shell) returns the rows near the ``seeds`` rows as a bool [B, L] tensor, and ``~shell`` is the
+``fixed_mask`` of the partial sampler without a read-back.  ``ctx.shell(torch.ones(B, L), radius, mode="atom", other_chain=True)``
+is the device interface selection: every row with an atom within ``radius`` of an atom of another chain of its complex.
+``interface_selection`` below is left as it is: it reads the PDB file, so it also sees HETATM records the batch does not carry.
 """
 from typing import Dict
 
