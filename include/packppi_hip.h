@@ -394,6 +394,40 @@ pp_status pp_ensemble_reduce(pp_ctx *ctx, const float *chi /* [N][4] */, int n_d
                              double *clash /* [B] */, int32_t *best /* [B/D] */, float *chi_best /* [N/D][4] or NULL */,
                              void *stream);
 
+/* ---- Recombination of a decoy ensemble per residue (no reference counterpart; csrc/pp_recombine.hip holds
+ * the arithmetic).  The ctx is an ensemble ctx as for pp_ensemble_reduce.  The D sampled states of every consensus row are that
+ * row's candidates; an assignment s gives every consensus row a decoy, and a conflict-free parallel descent lowers
+ *   F(s) = sum_r U(r, s_r) + 1/2 sum_r sum_{r' != r} W(r, s_r; r', s_r'),
+ * which is the sum over the complex of pp_clash's per_res at the recombined angles (U: the within-residue term; W: the pair
+ * term with both residues' weights; fp32, pp_clash's masks, exclusions and parameters).  One sweep: every row proposes the
+ * candidate d with the smallest local energy E_r(d | s) = U(r, d) + sum_r' W(r, d; r', s_r') (lowest d on ties, a NaN loses to
+ * any number) and its gain E_r(s_r | s) - E_r(d | s); a row takes its proposal iff its gain is positive and every partner row
+ * (the static predicate of the proximal loop's candidate lists) with a positive gain has a smaller one, or an equal one and a
+ * higher row number.  Accepted rows are pairwise non-partners: F drops by the sum of their gains.  All pointers DEVICE:
+ *   chi [N][4] the decoys' angles (the atom records are reconstructed at them, as in pp_clash);
+ *   start int32 [B / D] the decoy every row of the group starts from -- `best` of pp_ensemble_reduce --, or NULL = decoy 0;
+ *   pick int32 [N / D] the final s_r;  chi_out [N / D][4] row r of decoy pick[r], bit for bit;
+ *   trace fp64 [B / D][max_sweeps + 1]: clash(s) = F(s) / L_g after k sweeps, summed in fp64 in a fixed order from the fp32 row
+ *     terms, on the scale of pp_ensemble_reduce's clash; entries behind convergence repeat the last value;
+ *   sweeps int32 [B / D] the number of sweeps in which a row of the group moved;
+ *   converged int32 [B / D] 1 iff a sweep without a positive gain was seen (max_sweeps = 0: 0, except n_decoys = 1: 1);
+ *   energy [N / D][n_decoys] (or NULL): E_r(d | s) at the START assignment.
+ * Rows whose candidates are the same in every decoy (no chi angle, padding, the kept rows of a pinned ensemble) get the same E
+ * bits for every d, gain exactly 0 and never move.  A group whose start is outside 0 .. D - 1 (the -1 pp_ensemble_reduce gives a
+ * ragged group) or whose clamped segments differ in length is left alone: pick -1, its chi_out rows not written, trace NaN, sweeps
+ * 0, converged 0, nothing read outside the batch.  Exactly max_sweeps sweeps are enqueued (two launches each, one pass in front,
+ * two behind); a converged group's later launches return at once.  Never waits for the stream, reads nothing back.  No float
+ * atomics: every output is bit-reproducible, and a group's outputs do not depend on the other groups of the ctx.  Works on a
+ * geometry-only plan.  The call uses the proximal loop's workspaces: do not overlap it with pp_proximal* on the same ctx.
+ * PP_ERR_INVALID: a null ctx / chi / pick / chi_out / trace / sweeps / converged, n_decoys < 1, B or N not a multiple of n_decoys,
+ * max_sweeps < 0, a padded B > 1 ctx, a batch without atom_mask / residue_index, no pp_plan_set_clash_params before. */
+pp_status pp_ensemble_recombine(pp_ctx *ctx, const float *chi /* [N][4] */, int n_decoys,
+                                const int32_t *start /* DEVICE [B/D] or NULL = decoy 0 */, int max_sweeps,
+                                int32_t *pick /* [N/D] */, float *chi_out /* [N/D][4] */,
+                                double *trace /* [B/D][max_sweeps+1] */, int32_t *sweeps /* [B/D] */,
+                                int32_t *converged /* [B/D] */, float *energy /* [N/D][n_decoys] or NULL */,
+                                void *stream);
+
 /* ---- Shell masks (csrc/pp_shell.hip holds the arithmetic) ------------------------------------------------
  * "Which rows lie near these rows", per segment of the ctx's segment table (the complexes of a packed ctx, the B rows of a padded
  * one, padding rows included).  PP_SHELL_CA replaces AffinityPrediction.get_local_subgraph (AffinityPrediction.py:124-145); the

@@ -12,7 +12,7 @@ LIB = os.path.join(CSRC, "libpackppi_hip.so")
 # and pp_edge.hip (PACKPPI_EDGE=f32: exact-fp32 MFMA, three workgroups per CU).  Same launchers, same results to ~1e-6.
 EDGE_F16 = os.environ.get("PACKPPI_EDGE", "f16") != "f32"
 SOURCES = ["pp_api.hip", "pp_prepare.hip", "pp_node.hip", "pp_edge_f16.hip" if EDGE_F16 else "pp_edge.hip", "pp_clash.hip",
-           "pp_affinity.hip", "pp_dsm.hip", "pp_ensemble.hip", "pp_shell.hip"]
+           "pp_affinity.hip", "pp_dsm.hip", "pp_ensemble.hip", "pp_shell.hip", "pp_recombine.hip"]
 # The flags of the PRODUCT libraries are fixed here: PACKPPI_CFLAGS / -D arguments only reach TAGGED variant libraries
 # (python -m packppi_amd.build --tag NAME -DPP_LAB -DPP_X_...), which lib.load() refuses unless PACKPPI_ALLOW_LAB_LIBRARY=1.
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-variable",
@@ -128,7 +128,7 @@ def build_other_variant(verbose=True):
     The GPU tests run the end-to-end parity cases on it as well (PACKPPI_LIB)."""
     out = other_variant_path()
     tag = "f32" if EDGE_F16 else "f16"
-    sources = ["pp_api.hip", "pp_prepare.hip", "pp_node.hip", "pp_edge.hip" if EDGE_F16 else "pp_edge_f16.hip", "pp_clash.hip", "pp_affinity.hip", "pp_dsm.hip", "pp_ensemble.hip", "pp_shell.hip"]
+    sources = ["pp_api.hip", "pp_prepare.hip", "pp_node.hip", "pp_edge.hip" if EDGE_F16 else "pp_edge_f16.hip", "pp_clash.hip", "pp_affinity.hip", "pp_dsm.hip", "pp_ensemble.hip", "pp_shell.hip", "pp_recombine.hip"]
     flags = [f for f in FLAGS if f != "-DPP_EDGE_F16"] + ([] if EDGE_F16 else ["-DPP_EDGE_F16"])
     if not needs_build(out, flags, sources):
         return out
@@ -160,8 +160,8 @@ def build_diag_variant(verbose=True):
 
 def product_flag_stamps():
     """{flags half of pp_build_id(): library name} of the four libraries this file builds without laboratory flags."""
-    f32_sources = ["pp_api.hip", "pp_prepare.hip", "pp_node.hip", "pp_edge.hip", "pp_clash.hip", "pp_affinity.hip", "pp_dsm.hip", "pp_ensemble.hip", "pp_shell.hip"]
-    f16_sources = ["pp_api.hip", "pp_prepare.hip", "pp_node.hip", "pp_edge_f16.hip", "pp_clash.hip", "pp_affinity.hip", "pp_dsm.hip", "pp_ensemble.hip", "pp_shell.hip"]
+    f32_sources = ["pp_api.hip", "pp_prepare.hip", "pp_node.hip", "pp_edge.hip", "pp_clash.hip", "pp_affinity.hip", "pp_dsm.hip", "pp_ensemble.hip", "pp_shell.hip", "pp_recombine.hip"]
+    f16_sources = ["pp_api.hip", "pp_prepare.hip", "pp_node.hip", "pp_edge_f16.hip", "pp_clash.hip", "pp_affinity.hip", "pp_dsm.hip", "pp_ensemble.hip", "pp_shell.hip", "pp_recombine.hip"]
     base = [f for f in FLAGS if f != "-DPP_EDGE_F16"]
     return {flags_hash(base + ["-DPP_EDGE_F16"], f16_sources): "default (split-f16)",
             flags_hash(base, f32_sources): "f32",

@@ -15,6 +15,9 @@ what the sampled residues are conditioned on.  It needs --seed; with --use_proxi
 OUTDIR/decoy_000.pdb ..., structure.pdb (the decoy --select picks: lowest mean clash, or the medoid), ensemble.csv (decoy, key, dev,
 clash, selected) and confidence.csv (chain, residue number, residue name, resultant length of chi 1..4).  It needs --seed, combines
 with --use_proximal and is refused together with --repack.
+--recombine (with --n_decoys) recombines the decoys per residue by clash descent from the selected one, at most
+--recombine_sweeps sweeps: recombined.pdb, recombine.csv (chain, residue number, residue name, the decoy the residue was taken from,
+its local clash energy before and after) and structure.pdb = recombined.pdb; the other files are as without the flag.
 """
 import argparse
 import os
@@ -53,8 +56,9 @@ def load_model(args):
 def write_ensemble(model, batch, protein, args, analysis):
     """--n_decoys: sample, write every decoy, the two tables and the selected decoy; returns the selected angles [1, L, 4]."""
     from .. import constants as rc
+    kw = dict(recombine=True, recombine_sweeps=args.recombine_sweeps) if args.recombine else {}
     out = model.sample_ensemble(batch, args.n_decoys, seed=args.seed, use_proximal=args.use_proximal, select=args.select,
-                                return_all=True)
+                                return_all=True, **kw)
     chi, packed = out["decoys"]
     best = int(out["best"][0])
     dev, clash = out["dev"].cpu().tolist(), out["clash"].cpu().tolist()
@@ -69,8 +73,9 @@ def write_ensemble(model, batch, protein, args, analysis):
         texts.append(to_pdb(dict(protein, atom_positions=pos)))
         with open(os.path.join(args.outdir, f"decoy_{d:03d}.pdb"), "w") as fh:
             fh.write(texts[-1])
+    final = write_recombined(model, batch, protein, args, out) if args.recombine else texts[best]
     with open(analysis.tmp_pdb, "w") as fh:
-        fh.write(texts[best])
+        fh.write(final)
     with open(os.path.join(args.outdir, "ensemble.csv"), "w") as fh:
         fh.write("decoy,key,dev,clash,selected\n")
         for d, key in enumerate(out["keys"]):
@@ -81,7 +86,43 @@ def write_ensemble(model, batch, protein, args, analysis):
         fh.write("chain,residue_number,residue_name,resultant_chi1,resultant_chi2,resultant_chi3,resultant_chi4\n")
         for cid, num, aa, r in zip(protein["chain_id"], protein["residue_index"], protein["aaindex"], conf):
             fh.write(f"{cid},{int(num)},{rc.resnames[int(aa)]}," + ",".join(f"{v:.6f}" for v in r) + "\n")
-    return out["selected"]
+    return out["recombined"] if args.recombine else out["selected"]
+
+
+def write_recombined(model, batch, protein, args, out):
+    """--recombine: recombined.pdb and recombine.csv from ``sample_ensemble(recombine=True, return_all=True)``; returns the text of
+    recombined.pdb.  The local energies come from two more calls of the same entry without sweeps: E_r(best | all rows at best) on
+    the ensemble, E_r(pick_r | the picks) on one copy of the complex at the recombined angles."""
+    from .. import constants as rc
+    from ..batch import replicate
+    from ..functional import _ctx_for
+    chi, packed = out["decoys"]
+    cfg = model.hparams.sample_cfg
+    clash_kw = dict(vtf=cfg.violation_tolerance_factor, tol=cfg.clash_overlap_tolerance)
+    best = int(out["best"][0])
+    one = replicate(batch, 1)
+    before = model._context(packed).ensemble_recombine(chi, args.n_decoys, start=out["best"], max_sweeps=0, want_energy=True,
+                                                       **clash_kw).energy[:, best].cpu().tolist()
+    after = _ctx_for(one).ensemble_recombine(out["recombined"], 1, max_sweeps=0, want_energy=True, **clash_kw).energy[:, 0].cpu().tolist()
+    pick = out["pick"].cpu().tolist()
+    trace = out["clash_trace"][0].cpu().tolist()
+    moved = sum(int(p != best) for p in pick)
+    print(f"----- recombined per residue: {moved} of {len(pick)} residues from another decoy, {int(out['sweeps'][0])} sweeps"
+          f"{'' if int(out['converged'][0]) else ' (not converged)'}, mean clash {trace[0]:.4f} -> {trace[-1]:.4f} -----")
+    xyz = get_atom14_coords(one.X, one.residue_type, one.BB_D, out["recombined"]).cpu().squeeze(0).numpy()
+    pos = np.array(protein["atom_positions"], dtype=np.float32)
+    pos[:len(xyz)] = xyz
+    text = to_pdb(dict(protein, atom_positions=pos))
+    with open(os.path.join(args.outdir, "recombined.pdb"), "w") as fh:
+        fh.write(text)
+    n = len(protein["aaindex"])
+    pad = n - len(pick)                   # trailing rows without a residue: not part of the ensemble, they keep the selected decoy
+    with open(os.path.join(args.outdir, "recombine.csv"), "w") as fh:
+        fh.write("chain,residue_number,residue_name,decoy,energy_before,energy_after\n")
+        for cid, num, aa, d, e0, e1 in zip(protein["chain_id"], protein["residue_index"], protein["aaindex"], pick + [best] * pad,
+                                           before + [0.0] * pad, after + [0.0] * pad):
+            fh.write(f"{cid},{int(num)},{rc.resnames[int(aa)]},{d},{e0!r},{e1!r}\n")
+    return text
 
 
 def evaluate_model(model, args):
@@ -146,6 +187,9 @@ def build_parser():
                    "decoy_000.pdb ..., structure.pdb (the selected decoy), ensemble.csv and confidence.csv. Needs --seed.")
     p.add_argument("--select", choices=("clash", "medoid"), default="clash", help="With --n_decoys: keep the decoy with the lowest "
                    "mean clash (clash) or the one closest to the circular consensus (medoid).")
+    p.add_argument("--recombine", action="store_true", help="With --n_decoys: recombine the decoys per residue by clash descent from "
+                   "the selected one; writes recombined.pdb and recombine.csv, and structure.pdb is the recombined structure.")
+    p.add_argument("--recombine_sweeps", type=int, default=64, metavar="K", help="With --recombine: the largest number of sweeps.")
     return p
 
 
@@ -161,6 +205,10 @@ def parse_args(argv=None):
             p.error("--n_decoys must be at least 1")
         if args.repack is not None:
             p.error("--n_decoys together with --repack is not supported: ensembles under a fixed mask are not implemented")
+    if args.recombine and args.n_decoys is None:
+        p.error("--recombine needs --n_decoys (it recombines the decoys of an ensemble)")
+    if args.recombine_sweeps < 0:
+        p.error("--recombine_sweeps must not be negative")
     return args
 
 

@@ -3,12 +3,15 @@ DESIGN.md section 17).
 
     python -m packppi_amd.cli.mutate --input x.pdb (--mutstr RA47A,EA48A | --mutlist FILE) --ckpt_path model.ckpt --seed 7
         [--n_decoys 8] [--select clash|medoid] [--use_proximal] [--radius 10] [--shell ca|atom] [--fixed_mode hold|renoise]
+        [--recombine [--recombine_sweeps 64]]
         --outdir out [--ap_ckpt ap.ckpt --pre_ckpt_path pre.ckpt]
 
 Every set is put into the complex, the residues within --radius of a mutated residue (the shell, chosen on the device) are
 repacked around the new side chains, every other residue keeps the input's angles bit for bit.  All sets go through one packed
 pass.  Writes ``mutant_<tag>.pdb`` per set (the mutant's residue names and atoms) and ``mutants.csv``.  --mutlist FILE: one set
-per line, comma-separated as --mutstr, ``#`` lines skipped (the format of eval_affinity --mutlist).
+per line, comma-separated as --mutstr, ``#`` lines skipped (the format of eval_affinity --mutlist).  --recombine: the decoys of
+every set are recombined per residue by clash descent from the selected one; ``mutant_<tag>.pdb`` is then the
+recombined structure and ``mutants.csv`` gains the columns ``clash_recombined`` and ``rows_recombined``.
 """
 import argparse
 import os
@@ -47,9 +50,11 @@ def evaluate_model(model, args):
     protein["pdb_path"] = args.input
     sets = read_sets(args)
     results = model.mutate([(protein, s) for s in sets], seed=args.seed, radius=args.radius, shell=args.shell,
-                           n_decoys=args.n_decoys, use_proximal=args.use_proximal, select=args.select, fixed_mode=args.fixed_mode)
+                           n_decoys=args.n_decoys, use_proximal=args.use_proximal, select=args.select, fixed_mode=args.fixed_mode,
+                           **(dict(recombine=True, recombine_sweeps=args.recombine_sweeps) if args.recombine else {}))
     ddg = predict_ddg(protein, sets, args) if args.ap_ckpt else None
-    rows = ["tag,shell_rows,selected_decoy,clash,dev" + (",ddg,ddg_inv" if ddg else "")]
+    rows = ["tag,shell_rows,selected_decoy,clash,dev" + (",clash_recombined,rows_recombined" if args.recombine else "")
+            + (",ddg,ddg_inv" if ddg else "")]
     for i, (s, r) in enumerate(zip(sets, results)):
         tag = (r["tag"] or s).replace(",", "_")
         b = r["batch"]
@@ -60,10 +65,13 @@ def evaluate_model(model, args):
             fh.write(to_pdb(mutant))
         best = int(r["best"])
         line = f"{tag},{int(r['shell'].sum())},{best},{float(r['clash'][best])!r},{float(r['dev'][best])!r}"
+        if args.recombine:
+            line += f",{float(r['clash_recombined'])!r},{int(r['rows_recombined'])}"
         if ddg:
             line += f",{ddg[0][i]!r},{ddg[1][i]!r}"
         rows.append(line)
-        print(f"----- {tag}: {int(r['shell'].sum())} residues repacked, decoy {best} of {args.n_decoys} selected -----")
+        print(f"----- {tag}: {int(r['shell'].sum())} residues repacked, decoy {best} of {args.n_decoys} selected"
+              + (f", {int(r['rows_recombined'])} residues recombined from other decoys" if args.recombine else "") + " -----")
     with open(os.path.join(args.outdir, "mutants.csv"), "w") as fh:
         fh.write("\n".join(rows) + "\n")
     if model.saturated():
@@ -93,6 +101,9 @@ def build_parser():
     p.add_argument("--select", choices=("clash", "medoid"), default="clash", help="Keep the decoy with the lowest mean clash (clash) "
                    "or the one closest to the circular consensus (medoid).")
     p.add_argument("--use_proximal", action="store_true", help="Run the pinned proximal clash optimisation on the shell.")
+    p.add_argument("--recombine", action="store_true", help="Recombine the decoys per residue by clash descent from the selected "
+                   "one; the written mutant is the recombined structure.")
+    p.add_argument("--recombine_sweeps", type=int, default=64, metavar="K", help="With --recombine: the largest number of sweeps.")
     p.add_argument("--radius", type=float, default=10.0, help="Shell radius in Angstrom.")
     p.add_argument("--shell", choices=("ca", "atom"), default="ca", help="Shell rule: CA within the radius of a mutated CA (ca, the "
                    "local subgraph of PackPPI-AP) or any atom within it of an atom of a mutated residue (atom).")
@@ -110,6 +121,8 @@ def main(argv=None):
     args = p.parse_args(argv)
     if args.n_decoys < 1:
         p.error("--n_decoys must be at least 1")
+    if args.recombine_sweeps < 0:
+        p.error("--recombine_sweeps must not be negative")
     if args.pre_ckpt_path and not args.ap_ckpt:
         p.error("--pre_ckpt_path belongs to --ap_ckpt")
     evaluate_model(load_model(args), args)

@@ -21,7 +21,8 @@ SYMBOLS = ("pp_version", "pp_last_error", "pp_build_id", "pp_plan_set_knn_ties",
            "pp_affinity_create", "pp_affinity_destroy", "pp_affinity_encode", "pp_affinity_predict",
            "pp_score_rows", "pp_so2_set_grids", "pp_so2_score", "pp_dsm_loss",
            "pp_ctx_set_rng_keys", "pp_noise_seeded", "pp_add_noise_seeded", "pp_sample_seeded",
-           "pp_sample_partial", "pp_proximal_pinned", "pp_ctx_live_rows", "pp_ensemble_reduce", "pp_ctx_shell")
+           "pp_sample_partial", "pp_proximal_pinned", "pp_ctx_live_rows", "pp_ensemble_reduce", "pp_ctx_shell",
+           "pp_ensemble_recombine")
 
 
 FIX_MODES = {"hold": 0, "renoise": 1}         # PP_FIX_HOLD, PP_FIX_RENOISE
@@ -138,6 +139,7 @@ def load():
     lib.pp_ctx_live_rows.argtypes = [vp, vp, C.POINTER(C.c_int), vp]
     lib.pp_ensemble_reduce.argtypes = [vp, vp, i, vp, i, vp, vp, vp, vp, vp, vp, vp]
     lib.pp_ctx_shell.argtypes = [vp, vp, i, f, i, vp, vp, vp, vp]
+    lib.pp_ensemble_recombine.argtypes = [vp, vp, i, vp, i, vp, vp, vp, vp, vp, vp, vp]
     _lib = lib
     return lib
 
@@ -589,6 +591,40 @@ class Context:
         _check(load().pp_ensemble_reduce(self.handle, _ptr(chi), D, _ptr(pr), int(sel), _ptr(mean), _ptr(resultant), _ptr(dev),
                                          _ptr(clash), _ptr(best), _ptr(chi_best), _stream(self.plan.device)), "pp_ensemble_reduce")
         return EnsembleResult(mean=mean, resultant=resultant, dev=dev, clash=clash, best=best, chi_best=chi_best)
+
+    def ensemble_recombine(self, chi, n_decoys, start=None, max_sweeps=64, want_energy=False, vtf=12.0, tol=0.5):
+        """Recombine the decoys of this context per residue by clash descent (pp_ensemble_recombine): every
+        consensus row takes its four angles from one of the ``n_decoys`` decoys, chosen so that the clash loss of the recombined
+        structure goes down monotonically from that of the ``start`` decoy.  The context is an ensemble context as for
+        ``ensemble_reduce`` (checked against the host table before any launch).  ``chi`` [1, N, 4]; ``start`` int32 [n_groups] on
+        the device (``best`` of ``ensemble_reduce``) or None = decoy 0; a group whose entry is outside 0 .. D - 1 is left alone.
+        Returns an ``EnsembleResult``: ``pick`` int32 [N / D], ``chi`` [1, N / D, 4] (row r of decoy ``pick[r]``, bit for bit),
+        ``clash_trace`` fp64 [n_groups, max_sweeps + 1] (the mean clash after k sweeps), ``sweeps``, ``converged`` int32 [n_groups],
+        ``energy`` [N / D, D] (the local energies at the start; None without ``want_energy``), all on the device; no host
+        synchronisation."""
+        from .batch import check_groups
+        D, K = int(n_decoys), int(max_sweeps)
+        if K < 0:
+            raise ValueError("max_sweeps must not be negative")
+        if not self.packed and self.B != 1:
+            raise ValueError("ensemble_recombine needs a packed context (or a B = 1 one), not a padded B > 1 batch")
+        check_groups(self.seg_offsets_host, D)
+        self.plan.set_clash_params(vtf, tol)
+        chi = self._chi(chi)
+        n_cons, n_grp = self.n_rows // D, self.n_segments // D
+        st = None
+        if start is not None:
+            st = torch.as_tensor(start).to(device=self.plan.device, dtype=torch.int32).reshape(-1).contiguous()
+            if st.numel() != n_grp:
+                raise ValueError(f"start has {st.numel()} entries for {n_grp} groups")
+        pick = self._new(n_cons, dtype=torch.int32)
+        out = self._new(1, n_cons, 4)
+        trace = self._new(n_grp, K + 1, dtype=torch.float64)
+        sweeps, conv = self._new(n_grp, dtype=torch.int32), self._new(n_grp, dtype=torch.int32)
+        energy = self._new(n_cons, D) if want_energy else None
+        _check(load().pp_ensemble_recombine(self.handle, _ptr(chi), D, _ptr(st), K, _ptr(pick), _ptr(out), _ptr(trace), _ptr(sweeps),
+                                            _ptr(conv), _ptr(energy), _stream(self.plan.device)), "pp_ensemble_recombine")
+        return EnsembleResult(pick=pick, chi=out, clash_trace=trace, sweeps=sweeps, converged=conv, energy=energy)
 
     def shell(self, seeds, radius=10.0, mode="ca", other_chain=False, xyz=None, want_count=False):
         """The rows near the ``seeds`` rows, per complex, on the device (pp_ctx_shell): bool [B, L] (packed:

@@ -380,7 +380,16 @@ class TDiffusionModule:
             return SC_D_sample, [traj[i] for i in range(cfg.num_steps)], [float(v) for v in losses[0].cpu()]
         return accepted
 
-    def sample_ensemble(self, batch, n_decoys, *, seed=None, use_proximal: bool = False, select="clash", return_all: bool = False):
+    def _recombine(self, ctx, chi, n_decoys, res, recombine_sweeps):
+        """``Context.ensemble_recombine`` from the decoy ``ensemble_reduce`` selected (``res.best``, taken on the device) with the
+        clash parameters of the sampling configuration, and the keys it adds to a ``return_all`` dict."""
+        cfg = self.hparams.sample_cfg
+        rec = ctx.ensemble_recombine(chi, n_decoys, start=res.best, max_sweeps=recombine_sweeps,
+                                     vtf=cfg.violation_tolerance_factor, tol=cfg.clash_overlap_tolerance)
+        return rec, dict(recombined=rec.chi, pick=rec.pick, clash_trace=rec.clash_trace, sweeps=rec.sweeps, converged=rec.converged)
+
+    def sample_ensemble(self, batch, n_decoys, *, seed=None, use_proximal: bool = False, select="clash", return_all: bool = False,
+                        recombine: bool = False, recombine_sweeps: int = 64):
         """``n_decoys`` seeded samples of every complex in ONE packed pass, reduced on the device.  ``batch``: a
         B = 1 batch, or a list of complexes (``batch.replicate_many``: group-major, complex g's decoys are segments
         g * n_decoys .. g * n_decoys + n_decoys - 1).  Decoy d of a complex with key k is sampled under the key
@@ -393,7 +402,13 @@ class TDiffusionModule:
         Returns the selected angles [1, sum of the complexes' lengths, 4]; with ``return_all`` a dict: ``decoys`` = (angles
         [1, N, 4] of the packed batch, the packed batch), ``selected``, ``best`` [n_complexes] int32, ``dev`` / ``clash``
         [n_complexes * n_decoys] fp64, ``consensus`` / ``confidence`` [1, sum of lengths, 4] (circular mean; resultant length, 1 = all
-        decoys agree) and ``keys`` (the decoys' noise keys, a list)."""
+        decoys agree) and ``keys`` (the decoys' noise keys, a list).
+
+        ``recombine``: the decoys are then recombined per residue by clash descent, starting from the decoy
+        ``select`` picks (None: decoy 0), at most ``recombine_sweeps`` sweeps; the returned angles are the recombined ones, and
+        ``return_all`` keeps every key above as it is and adds ``recombined`` [1, sum of lengths, 4], ``pick`` int32 [sum of lengths]
+        (the decoy every row was taken from), ``clash_trace`` fp64 [n_complexes, recombine_sweeps + 1], ``sweeps`` and ``converged``
+        int32 [n_complexes]."""
         from .batch import replicate, replicate_many
         from .lib import SELECT
         if seed is None:
@@ -414,13 +429,15 @@ class TDiffusionModule:
         ctx = self._context(packed)
         per_res = ctx.clash(chi, cfg.violation_tolerance_factor, cfg.clash_overlap_tolerance)
         res = ctx.ensemble_reduce(chi, packed.n_decoys, per_res=per_res, select=select)
+        rec, extra = self._recombine(ctx, chi, int(packed.n_decoys), res, recombine_sweeps) if recombine else (None, {})
         if not return_all:
-            return res.chi_best
+            return rec.chi if recombine else res.chi_best
         return dict(decoys=(chi, packed), selected=res.chi_best, best=res.best, dev=res.dev, clash=res.clash, consensus=res.mean,
-                    confidence=res.resultant, keys=list(packed.complex_keys))
+                    confidence=res.resultant, keys=list(packed.complex_keys), **extra)
 
     def repack_ensemble(self, batch, fixed_mask=None, *, n_decoys, seed, fixed_chi=None, fixed_mode="renoise",
-                        use_proximal: bool = False, select="clash", return_all: bool = False):
+                        use_proximal: bool = False, select="clash", return_all: bool = False, recombine: bool = False,
+                        recombine_sweeps: int = 64):
         """``sample_ensemble`` under a pin: ``n_decoys`` seeded partial repackings of every complex in ONE packed
         pass, reduced on the device.  ``batch``: a B = 1 batch, or a list of complexes (per-complex data or B = 1 batches).  Every
         complex carries its ``fixed_mask`` (1 = keep; [1, L] on a B = 1 batch, [L] on per-complex data), or ``fixed_mask`` gives it:
@@ -475,13 +492,15 @@ class TDiffusionModule:
         ctx = self._context(packed)
         per_res = ctx.clash(chi, cfg.violation_tolerance_factor, cfg.clash_overlap_tolerance)
         res = ctx.ensemble_reduce(chi, D, per_res=per_res, select=select)
+        rec, extra = self._recombine(ctx, chi, D, res, recombine_sweeps) if recombine else (None, {})
         if not return_all:
-            return res.chi_best
+            return rec.chi if recombine else res.chi_best
         return dict(decoys=(chi, packed), selected=res.chi_best, best=res.best, dev=res.dev, clash=res.clash, consensus=res.mean,
-                    confidence=res.resultant, keys=list(packed.complex_keys))
+                    confidence=res.resultant, keys=list(packed.complex_keys), **extra)
 
     def mutate(self, proteins_and_mutations, *, seed, radius=10.0, shell="ca", n_decoys=1, use_proximal: bool = False,
-               select="clash", fixed_mode="renoise", max_rows=200_000, log=print):
+               select="clash", fixed_mode="renoise", max_rows=200_000, log=print, recombine: bool = False,
+               recombine_sweeps: int = 64):
         """Mutant modelling: put each mutation set into its complex, repack what it touches, return the mutant.
         ``proteins_and_mutations``: a list of ``(protein dict, mutations)`` pairs, ``mutations`` a string ("RA47A,EA48A") or dicts as
         ``featurize.parse_mutstr`` returns them; several sets of one protein are repeated pairs.  Set i of the call gets the noise
@@ -497,7 +516,12 @@ class TDiffusionModule:
         A set's result does not depend on what it was packed with, and every row outside its shell keeps the wild type's ``SC_D``
         bit for bit.  Returns one dict per set: ``tag``, ``key``, ``SC_D`` [1, L, 4] (the selected decoy), ``X`` [1, L, 14, 3],
         ``shell`` bool [1, L], ``best`` (int32 scalar tensor), ``clash`` / ``dev`` fp64 [n_decoys], ``keys`` (the decoys' noise keys)
-        and ``batch`` (the mutant B = 1 batch: residue types and atom mask of the mutant), tensors on the device."""
+        and ``batch`` (the mutant B = 1 batch: residue types and atom mask of the mutant), tensors on the device.
+
+        ``recombine``: ``SC_D`` and ``X`` are those of the decoys recombined per residue from the selected
+        one, and every dict gains ``pick`` int32 [1, L] (the decoy each row was taken from; ``best`` outside the shell),
+        ``clash_recombined`` (fp64 scalar tensor, on the scale of ``clash``) and ``rows_recombined`` (scalar tensor: rows with
+        ``pick != best``)."""
         from .batch import as_single, pack, unpack
         from .featurize import mutant_model_data, parse_mutstr
         from .functional import _ctx_for
@@ -548,9 +572,11 @@ class TDiffusionModule:
                 p["fixed_mask"] = fx
                 pinned.append(p)
             out = self.repack_ensemble(pinned, n_decoys=n_decoys, seed=seed, fixed_mode=fixed_mode, use_proximal=use_proximal,
-                                       select=select, return_all=True)
-            pos = gctx.atom14(out["selected"])
-            parts = zip(grp, members, unpack(pb, out["selected"]), unpack(pb, pos), unpack(pb, sh))
+                                       select=select, return_all=True, recombine=recombine, recombine_sweeps=recombine_sweeps)
+            final = out["recombined"] if recombine else out["selected"]
+            pos = gctx.atom14(final)
+            picks = unpack(pb, out["pick"].reshape(1, -1)) if recombine else [None] * len(members)
+            parts = zip(grp, members, unpack(pb, final), unpack(pb, pos), unpack(pb, sh))
             for g, (i, b, chi, x, s) in enumerate(parts):
                 n, m = int(b["max_size"]), chi.shape[1]
                 if m != n:
@@ -560,6 +586,12 @@ class TDiffusionModule:
                 results[i] = dict(tag=b["mutation_tag"], key=int(b["complex_key"]), SC_D=chi, X=x, shell=s, best=out["best"][g],
                                   clash=out["clash"][g * n_decoys:(g + 1) * n_decoys], dev=out["dev"][g * n_decoys:(g + 1) * n_decoys],
                                   keys=out["keys"][g * n_decoys:(g + 1) * n_decoys], batch=b)
+                if recombine:
+                    pk = picks[g]
+                    moved = (pk != out["best"][g]).sum()
+                    if m != n:
+                        pk = torch.cat([pk, out["best"][g].expand(1, n - m)], 1)
+                    results[i].update(pick=pk, clash_recombined=out["clash_trace"][g, -1], rows_recombined=moved)
         return results
 
     def sample_from(self, batch, SC_D_init, sde_noise=None):
