@@ -305,6 +305,36 @@ pp_status pp_proximal_pinned(pp_ctx *ctx, const float *chi, const uint8_t *fixed
                              int num_steps, const int32_t *norm_rows, float *chi_traj, float *chi_last,
                              float *chi_accepted, float *losses, uint8_t *moved /* DEVICE [N] or NULL */, void *stream);
 
+/* ---- Obstacle atoms (no reference counterpart) -------------------------------------------------------------
+ * Fixed spheres -- the heavy atoms of ligands, cofactors, nucleic acids, modified residues -- that the side chains of a segment must
+ * not overlap.  A segment is a complex of a packed ctx, or the one complex of a B = 1 ctx.  With a set installed, pp_clash, the three
+ * pp_proximal* calls and pp_ensemble_recombine add, for every row i of a segment, every own atom a in slots 4..13 with
+ * exists * radius = r_a != 0 and every obstacle o of that segment with r_o > 0,
+ *     err = max((r_a + r_o) - tol - sqrt(1e-10 + |p_a - q_o|^2), 0)        (fp32, tol of pp_plan_set_clash_params)
+ * to atom a's loss sum: it enters per_res[i] = sum_{a >= 4}(...) / (nsc + 1e-10) beside the between-residue and within-residue sums.
+ * No exclusions: backbone slots never take part, there is no slot-5 rule and no peptide rule.  Only p_a moves: the gradient gains
+ * -w_i / d (p_a - q_o), pushed through the chi axes like every other force.  Everything built on per_res and dchi (the clash mask,
+ * the Adam step, the loss list and accept rule, the `moved` mask, pp_ensemble_reduce on that per_res) carries the term unchanged.
+ * ANCHOR: take a complex of chains A and B, remove B's rows and hand B's atoms (without its slot-5 atoms) in as obstacles: pp_clash on
+ * A's rows gives what it gives on the full complex with B's slot 5 masked, to fp32 rounding.
+ *   xyzr       DEVICE [M][4] (x, y, z, radius); the ctx keeps a copy of its own, the caller may free it;
+ *   seg_range  HOST int32 [n_seg][2] (first, count) into xyzr per segment, read before the call returns; ranges may overlap or
+ *              coincide (the decoys of an ensemble group share theirs: pp_ensemble_recombine leaves a group alone, pick -1, whose
+ *              decoys point at different ranges);
+ *   M = 0 or xyzr == NULL clears the set: every call then behaves, bit for bit, as on a ctx that never had one.
+ * The summation order is fixed (obstacle l of a range belongs to wave (l / 64) mod 4 and partner stripe l mod 4 of the residue's
+ * workgroup, ascending l per lane): results are bit-reproducible and a segment's do not depend on the other segments.  The Adam loop
+ * does not scan a segment's range at every step: it builds static candidates per row once per pp_proximal* call (|CA_i - q_o| <
+ * e_i + r_o + 1.8 - tol, e_i the extent of the residue-partner lists), up to PP_OBSTACLE_CAP = 256 per row; a row with more scans its
+ * range, same order, same bits.  pp_clash outside the loop scans.  Cost: 1 KB of ctx memory per row.
+ * Does not wait for the stream, except when the set is larger than any this ctx held before (the copy is reallocated, which waits
+ * for the device); pp_ctx_destroy of a ctx that ever held obstacles frees that copy and waits likewise.
+ * PP_ERR_INVALID: a null ctx, M < 0, a null seg_range with M > 0, a range outside [0, M], a padded B > 1 ctx.  A non-finite
+ * coordinate or radius, or a negative radius, is found on the device: it sets bit 2 of pp_ctx_saturated (no read-back here). */
+#define PP_OBSTACLE_CAP 256
+pp_status pp_ctx_set_obstacles(pp_ctx *ctx, const float *xyzr /* DEVICE [M][4] */, const int32_t *seg_range /* HOST [n_seg][2] */,
+                               int M, void *stream);
+
 /* ---- PackPPI-AP: binding ddG prediction (src/models/AffinityPrediction.py) ----------------------------------------------
  * The pretrained network at t = 0 is pp_score (get_pret_feature, :109-122: hV of a ctx of the wild-type batch and of one of
  * the mutant batch).  The mutation encoder + MPNN (mode `network`, :50-71) run on a plan of their own: pp_plan_create with
@@ -511,8 +541,8 @@ pp_status pp_debug_edge(pp_ctx *ctx, int layer, void *stream);     /* one edge-u
 pp_status pp_debug_nm(pp_ctx *ctx, int layer, void *stream);       /* one node-message launch */
 pp_status pp_debug_set_hE(pp_ctx *ctx, const float *src, size_t n);
 /* which: 0 h_E [N,K,128], 1 S [N,128], 2 msum [N], 3 h_E0, 4 Z_em, 5 h_V [N,128], 6 score [N,4], 7 the proximal loop's static
- * candidate counts [N,4] (int32 bits in the 4-byte slots; -1 = that wave scans), 8 the plan's side-chain extents [21]; waits for
- * the device.
+ * candidate counts [N,4] (int32 bits in the 4-byte slots; -1 = that wave scans), 8 the plan's side-chain extents [21], 9 the
+ * loop's static obstacle candidate counts [N] (int32 bits; -1 = that row scans its range); waits for the device.
  * After pp_score / pp_sample, h_E holds layer 0's edges: the layer-1 edge update of an evaluation does not write it back
  * (pp_debug_score_prefix and pp_debug_edge do). */
 pp_status pp_debug_buffer(pp_ctx *ctx, int which, float *dst, size_t n);

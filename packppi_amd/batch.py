@@ -35,6 +35,39 @@ AFFINITY_KEYS = (
 ROW_KEYS = ("fixed_mask",)
 
 
+# obstacle atoms (``featurize.protein_to_batch(..., obstacles=...)``): ``obstacle_xyzr`` [M, 4] float32
+# (x, y, z, radius) and ``obstacle_offsets`` int32 [n + 1] -- complex (or, in a batch of decoys, group) k owns the atoms
+# obstacle_offsets[k] .. obstacle_offsets[k + 1] - 1 --, with ``obstacle_offsets_host``, the same as a list.  Not per-residue
+# tensors: nothing gives them a batch axis, pads or slices them.  A batch without obstacles has none of the keys.
+OBSTACLE_KEYS = ("obstacle_xyzr", "obstacle_offsets", "obstacle_offsets_host")
+
+
+def has_obstacles(b) -> bool:
+    return hasattr(b, "get") and b.get("obstacle_xyzr") is not None
+
+
+def _obstacles_of(c):
+    """(xyzr [M, 4], M) of one complex (per-complex data or a B = 1 batch); (None, 0) without obstacles."""
+    if not has_obstacles(c):
+        return None, 0
+    offs = c.get("obstacle_offsets_host") or [int(x) for x in c["obstacle_offsets"].tolist()]
+    if len(offs) != 2:
+        raise ValueError(f"a single complex carries one obstacle range, this one has {len(offs) - 1}")
+    x = c["obstacle_xyzr"].reshape(-1, 4)
+    return x[offs[0]:offs[1]], offs[1] - offs[0]
+
+
+def _set_obstacles(out, parts, like):
+    """Store the obstacle keys of a batch whose complexes (groups) own the atom blocks ``parts`` ([M_k, 4] or None), in order."""
+    offs = [0]
+    for p in parts:
+        offs.append(offs[-1] + (0 if p is None else int(p.shape[0])))
+    blocks = [p.to(device=like.device, dtype=torch.float32) for p in parts if p is not None]
+    out["obstacle_xyzr"] = torch.cat(blocks, 0) if blocks else torch.zeros(0, 4, device=like.device)
+    out["obstacle_offsets"] = torch.tensor(offs, dtype=torch.int32).to(like.device, non_blocking=True)
+    out["obstacle_offsets_host"] = offs
+
+
 class Batch(dict):
     """Attribute-style dict: ``batch.X``, ``batch['X']``, ``batch.to('cuda')``, ``batch.keys()``."""
 
@@ -72,15 +105,18 @@ def as_single(data: Batch) -> Batch:
     """Add the leading batch axis the way ``ProteinAnalysis.get_prot`` does (protein_analysis.py:115-120)."""
     out = Batch()
     for k, v in data.items():
-        out[k] = v.unsqueeze(0) if isinstance(v, torch.Tensor) else v
+        out[k] = v.unsqueeze(0) if isinstance(v, torch.Tensor) and k not in OBSTACLE_KEYS else v
     out["num_proteins"] = 1
     out["max_size"] = int(data["num_nodes"])
     return out
 
 
 def collate(proteins: Iterable[Batch]) -> Batch:
-    """Pad every per-residue tensor to the longest complex and stack (complex_datamodule.py:196-226)."""
+    """Pad every per-residue tensor to the longest complex and stack (complex_datamodule.py:196-226).  Obstacle atoms are not
+    supported in padded batches (``ValueError``): use ``pack``."""
     proteins = list(proteins)
+    if any(has_obstacles(p) for p in proteins):
+        raise ValueError("collate: a padded batch cannot carry obstacle atoms; use batch.pack()")
     max_size = max(int(p["num_nodes"]) for p in proteins)
 
     def pad(p, key):
@@ -116,6 +152,10 @@ def split(batch: Batch) -> List[Batch]:
         o = Batch(num_proteins=1, max_size=int(batch["max_size"]))
         for k in TENSOR_KEYS:
             o[k] = batch[k][b:b + 1]
+        if has_obstacles(batch):          # only a B = 1 batch can have them (collate refuses): its one complex keeps them
+            for k in OBSTACLE_KEYS:
+                if k in batch:
+                    o[k] = batch[k]
         outs.append(o)
     return outs
 
@@ -137,7 +177,9 @@ def pack(complexes: Iterable[Batch], trim: bool = True) -> Batch:
     the per-row keys are packed like the others, ``ddg`` becomes [n].  Complexes that all carry a ``complex_key`` (an int: the
     key of the seeded sampling noise, ``TDiffusionModule.sampling(seed=...)``) give the batch ``complex_keys``, a list in packing
     order; batches without it pack as before.  Complexes that all carry a ``fixed_mask`` ([L] or [1, L]: the rows partial
-    repacking keeps) give the batch its ``fixed_mask`` [1, N]; ``unpack`` splits it like any per-row result."""
+    repacking keeps) give the batch its ``fixed_mask`` [1, N]; ``unpack`` splits it like any per-row result.  If any complex
+    carries obstacle atoms (``OBSTACLE_KEYS``) the batch does: the blocks back to back, one range per complex (empty for a complex
+    without); if none does, the batch has none of the keys."""
     complexes = list(complexes)
     keys = TENSOR_KEYS + tuple(k for k in MUT_KEYS + ROW_KEYS if all(k in c for c in complexes))
     rows = {k: [] for k in keys}
@@ -169,6 +211,8 @@ def pack(complexes: Iterable[Batch], trim: bool = True) -> Batch:
         out["complex_keys"] = [int(c["complex_key"]) for c in complexes]
     out["seg_offsets"] = torch.tensor(offs, dtype=torch.int32).to(out["X"].device, non_blocking=True)
     out["seg_offsets_host"] = offs
+    if any(has_obstacles(c) for c in complexes):
+        _set_obstacles(out, [_obstacles_of(c)[0] for c in complexes], out["X"])
     return out
 
 
@@ -223,6 +267,8 @@ def replicate_many(complexes: Iterable[Batch], n_decoys: int, keys=None) -> Batc
     has one, else ``g``.  The batch gets ``complex_keys`` (what the seeded sampler reads), ``n_decoys`` and ``n_groups``.  Takes what
     ``pack`` takes: per-complex data or B = 1 batches.
 
+    Obstacle atoms (``OBSTACLE_KEYS``) are carried per GROUP: ``obstacle_offsets`` has one range per complex, shared by its decoys.
+
     ``ValueError``: ``n_decoys < 1``, no complex, keys of this call that are not pairwise distinct (two segments would draw the same
     noise), or a group whose copies differ in length (impossible through this function; ``lib.Context.ensemble_reduce`` relies on it)."""
     complexes = list(complexes)
@@ -239,9 +285,13 @@ def replicate_many(complexes: Iterable[Batch], n_decoys: int, keys=None) -> Batc
         raise ValueError("the decoy keys of this call are not pairwise distinct: two segments would draw the same noise "
                          f"(base keys {base}, n_decoys {n_decoys})")
     # a copy must not bring a key of its own into pack(): the keys are set below
-    plain = [Batch({k: v for k, v in c.items() if k not in ("complex_key", "complex_keys")}) for c in complexes]
+    plain = [Batch({k: v for k, v in c.items() if k not in ("complex_key", "complex_keys") + OBSTACLE_KEYS}) for c in complexes]
     out = pack([c for c in plain for _ in range(n_decoys)])
     check_groups(out["seg_offsets_host"], n_decoys)
+    # obstacles belong to the group: one range per complex, which its n_decoys segments share (lib.Context maps segment s to
+    # range s // n_decoys)
+    if any(has_obstacles(c) for c in complexes):
+        _set_obstacles(out, [_obstacles_of(c)[0] for c in complexes], out["X"])
     out["complex_keys"] = all_keys
     out["n_decoys"] = n_decoys
     out["n_groups"] = len(complexes)

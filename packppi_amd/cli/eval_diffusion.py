@@ -18,6 +18,12 @@ with --use_proximal and is refused together with --repack.
 --recombine (with --n_decoys) recombines the decoys per residue by clash descent from the selected one, at most
 --recombine_sweeps sweeps: recombined.pdb, recombine.csv (chain, residue number, residue name, the decoy the residue was taken from,
 its local clash energy before and after) and structure.pdb = recombined.pdb; the other files are as without the flag.
+--obstacles hetero|hetero+water (default none: every output byte as before): the file's HETATM records and
+non-standard residues -- ligands, cofactors, nucleic acids, with hetero+water the waters -- become fixed obstacle atoms of every
+clash stage (--use_proximal, the clash ranking of --n_decoys, --recombine).  The diffusion network itself does NOT see them:
+sampling is unchanged, the clash stages repair what it puts into the pocket.  Every structure file written gets those records'
+original lines, verbatim, between the protein's last TER and END, and obstacles.csv lists per residue its clash against the
+obstacles (Context.clash with the set minus Context.clash without it) at the input's angles and at the result's.
 """
 import argparse
 import os
@@ -29,7 +35,7 @@ import torch
 from ..analysis import ProteinAnalysis
 from ..functional import get_atom14_coords
 from ..module import TDiffusionModule
-from ..pdb_io import contains_sidechains, from_pdb_file, to_pdb
+from ..pdb_io import OBSTACLE_MODES, contains_sidechains, from_pdb_file, insert_obstacle_lines, obstacles_for, to_pdb
 
 
 def load_model(args):
@@ -70,7 +76,7 @@ def write_ensemble(model, batch, protein, args, analysis):
         # pack() drops trailing rows without a residue (no backbone): they keep the input's coordinates, as they carry no side chain
         pos = np.array(protein["atom_positions"], dtype=np.float32)
         pos[:offs[d + 1] - offs[d]] = xyz[offs[d]:offs[d + 1]]
-        texts.append(to_pdb(dict(protein, atom_positions=pos)))
+        texts.append(insert_obstacle_lines(to_pdb(dict(protein, atom_positions=pos)), args.obstacle_lines))
         with open(os.path.join(args.outdir, f"decoy_{d:03d}.pdb"), "w") as fh:
             fh.write(texts[-1])
     final = write_recombined(model, batch, protein, args, out) if args.recombine else texts[best]
@@ -112,7 +118,7 @@ def write_recombined(model, batch, protein, args, out):
     xyz = get_atom14_coords(one.X, one.residue_type, one.BB_D, out["recombined"]).cpu().squeeze(0).numpy()
     pos = np.array(protein["atom_positions"], dtype=np.float32)
     pos[:len(xyz)] = xyz
-    text = to_pdb(dict(protein, atom_positions=pos))
+    text = insert_obstacle_lines(to_pdb(dict(protein, atom_positions=pos)), args.obstacle_lines)
     with open(os.path.join(args.outdir, "recombined.pdb"), "w") as fh:
         fh.write(text)
     n = len(protein["aaindex"])
@@ -125,11 +131,42 @@ def write_recombined(model, batch, protein, args, out):
     return text
 
 
+def obstacle_share(model, batch, chi):
+    """[L] the clash of every residue against the obstacles at ``chi``: Context.clash with the set minus Context.clash after
+    clearing it (the set is put back)."""
+    from ..functional import _ctx_for
+    cfg = model.hparams.sample_cfg
+    kw = dict(vtf=cfg.violation_tolerance_factor, tol=cfg.clash_overlap_tolerance)
+    ctx = _ctx_for(batch)
+    with_set = ctx.clash(chi, **kw)
+    ctx.set_obstacles(None)
+    without = ctx.clash(chi, **kw)
+    ctx.set_obstacles(batch.obstacle_xyzr, ctx._obstacle_ranges(batch))
+    return (with_set - without)[0].cpu().tolist()
+
+
+def write_obstacles_csv(model, batch, protein, args, chi_after):
+    """obstacles.csv: residue, chain, clash against obstacles before (the input's angles) and after (the result's)."""
+    before, after = obstacle_share(model, batch, batch.SC_D), obstacle_share(model, batch, chi_after)
+    with open(os.path.join(args.outdir, "obstacles.csv"), "w") as fh:
+        fh.write("residue,chain,clash_obstacles_before,clash_obstacles_after\n")
+        for num, cid, b, a in zip(protein["residue_index"], protein["chain_id"], before, after):
+            fh.write(f"{int(num)},{cid},{b!r},{a!r}\n")
+    hit = sum(1 for a in after if a > 0)
+    print(f"----- obstacles: clash against them {sum(before):.4f} -> {sum(after):.4f} (summed over residues; {hit} residues still touch) -----")
+
+
 def evaluate_model(model, args):
     print("----- Starting evaluation! -----")
     analysis = ProteinAnalysis(args.molprobity_clash_loc, args.outdir, args.device)
     protein = from_pdb_file(Path(args.input), mse_to_met=True)
-    batch = analysis.get_prot(args.input).to(args.device)
+    obstacles = obstacles_for(args.input, args.obstacles)
+    args.obstacle_lines = obstacles["lines"] if obstacles else []
+    batch = analysis.get_prot(args.input)
+    if obstacles is not None:
+        from ..featurize import _add_obstacles
+        _add_obstacles(batch, obstacles)
+    batch = batch.to(args.device)
     if args.seed is not None:
         torch.manual_seed(args.seed)
     # --seed: the initial noise and the sde noise come from the counter-based device generator (module.sampling(seed=...)): the
@@ -156,7 +193,9 @@ def evaluate_model(model, args):
         xyz = get_atom14_coords(batch.X, batch.residue_type, batch.BB_D, SC_D_sample)
         protein["atom_positions"] = xyz.cpu().squeeze(0).numpy()
         with open(analysis.tmp_pdb, "w") as fh:
-            fh.writelines(to_pdb(protein))
+            fh.writelines(insert_obstacle_lines(to_pdb(protein), args.obstacle_lines))
+    if obstacles is not None:
+        write_obstacles_csv(model, batch, protein, args, SC_D_sample)
     if contains_sidechains(args.input):
         metric = analysis.get_metric(true_pdb=args.input, pred_pdb=analysis.tmp_pdb)
         print(f"----- Metric: ----- {metric}")
@@ -190,6 +229,10 @@ def build_parser():
     p.add_argument("--recombine", action="store_true", help="With --n_decoys: recombine the decoys per residue by clash descent from "
                    "the selected one; writes recombined.pdb and recombine.csv, and structure.pdb is the recombined structure.")
     p.add_argument("--recombine_sweeps", type=int, default=64, metavar="K", help="With --recombine: the largest number of sweeps.")
+    p.add_argument("--obstacles", choices=OBSTACLE_MODES, default="none", help="Fixed atoms the clash stages keep the side chains off (DESIGN.md section 19): none (default), hetero = every HETATM record and "
+                   "every non-standard residue (ligands, cofactors, nucleic acids; no hydrogens, waters or metals), hetero+water = the "
+                   "waters too. The diffusion network does not see them: sampling is unchanged, the clash stages (--use_proximal, "
+                   "decoy ranking, --recombine) repair what it puts into the pocket. Written structures keep the records.")
     return p
 
 

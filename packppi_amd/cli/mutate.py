@@ -12,6 +12,10 @@ pass.  Writes ``mutant_<tag>.pdb`` per set (the mutant's residue names and atoms
 per line, comma-separated as --mutstr, ``#`` lines skipped (the format of eval_affinity --mutlist).  --recombine: the decoys of
 every set are recombined per residue by clash descent from the selected one; ``mutant_<tag>.pdb`` is then the
 recombined structure and ``mutants.csv`` gains the columns ``clash_recombined`` and ``rows_recombined``.
+--obstacles hetero|hetero+water (default none: every output byte as before): the file's HETATM records and
+non-standard residues become fixed obstacle atoms of every clash stage (--use_proximal, the clash ranking, --recombine); the
+network does not see them.  Every ``mutant_<tag>.pdb`` keeps their lines and ``obstacles.csv`` lists, per set and residue, the
+clash against them at the wild type's angles (new side chains at chi = 0) and at the result's.
 """
 import argparse
 import os
@@ -19,7 +23,7 @@ import os
 import numpy as np
 
 from ..featurize import parse_mutstr
-from ..pdb_io import from_pdb_file, to_pdb
+from ..pdb_io import OBSTACLE_MODES, from_pdb_file, insert_obstacle_lines, obstacles_for, to_pdb
 from .eval_diffusion import load_model
 
 AP_NOTE = ("The ddG values come from the unchanged AffinityPrediction.predict_many on featurize.mutant_data. The AP model was "
@@ -48,6 +52,10 @@ def evaluate_model(model, args):
     os.makedirs(args.outdir, exist_ok=True)
     protein = from_pdb_file(args.input, mse_to_met=True)
     protein["pdb_path"] = args.input
+    obstacles = obstacles_for(args.input, args.obstacles)
+    if obstacles is not None:
+        protein["obstacles"] = obstacles
+    ob_rows = ["tag,residue,chain,clash_obstacles_before,clash_obstacles_after"]
     sets = read_sets(args)
     results = model.mutate([(protein, s) for s in sets], seed=args.seed, radius=args.radius, shell=args.shell,
                            n_decoys=args.n_decoys, use_proximal=args.use_proximal, select=args.select, fixed_mode=args.fixed_mode,
@@ -62,7 +70,12 @@ def evaluate_model(model, args):
                       aaindex=np.where(b["residue_mask"][0].cpu().numpy() > 0, b["residue_type"][0].cpu().numpy(),
                                        np.asarray(protein["aaindex"])))
         with open(os.path.join(args.outdir, f"mutant_{tag}.pdb"), "w") as fh:
-            fh.write(to_pdb(mutant))
+            fh.write(insert_obstacle_lines(to_pdb(mutant), obstacles["lines"] if obstacles else []))
+        if obstacles is not None:
+            from .eval_diffusion import obstacle_share
+            before, after = obstacle_share(model, b, b["SC_D"]), obstacle_share(model, b, r["SC_D"])
+            ob_rows += [f"{tag},{int(num)},{cid},{x!r},{y!r}" for num, cid, x, y in
+                        zip(protein["residue_index"], protein["chain_id"], before, after)]
         best = int(r["best"])
         line = f"{tag},{int(r['shell'].sum())},{best},{float(r['clash'][best])!r},{float(r['dev'][best])!r}"
         if args.recombine:
@@ -74,6 +87,9 @@ def evaluate_model(model, args):
               + (f", {int(r['rows_recombined'])} residues recombined from other decoys" if args.recombine else "") + " -----")
     with open(os.path.join(args.outdir, "mutants.csv"), "w") as fh:
         fh.write("\n".join(rows) + "\n")
+    if obstacles is not None:
+        with open(os.path.join(args.outdir, "obstacles.csv"), "w") as fh:
+            fh.write("\n".join(ob_rows) + "\n")
     if model.saturated():
         print("----- WARNING: sticky flag %d (f16 saturation or non-finite input) in the score network -----" % model.saturated())
     print("----- Finishing evaluation! -----")
@@ -113,6 +129,10 @@ def build_parser():
                    + AP_NOTE)
     p.add_argument("--pre_ckpt_path", type=str, default=None, help="With --ap_ckpt: the pretrained PackPPI checkpoint (default: the "
                    "one named in the AP checkpoint's hyper_parameters).")
+    p.add_argument("--obstacles", choices=OBSTACLE_MODES, default="none", help="Fixed atoms the clash stages keep the side chains off (DESIGN.md section 19): none (default), hetero = every HETATM record and "
+                   "every non-standard residue (ligands, cofactors, nucleic acids; no hydrogens, waters or metals), hetero+water = the "
+                   "waters too. The diffusion network does not see them: sampling is unchanged, the clash stages (--use_proximal, "
+                   "decoy ranking, --recombine) repair what it puts into the pocket. Written structures keep the records.")
     return p
 
 

@@ -3,16 +3,19 @@
 Flags as in the reference (:69-78) plus --device (the reference script is CPU only; this path is HIP only).
 --repack SPEC|interface (as in eval_diffusion): only the named residues may move, every other residue keeps
 the input's angles (the pinned optimiser: the clash threshold is still the mean over all residues).
+--obstacles hetero|hetero+water (default none: every output byte as before): the file's HETATM records and
+non-standard residues become fixed obstacle atoms of the clash loss; structure.pdb keeps their lines and obstacles.csv lists every
+residue's clash against them before and after.
 """
 import argparse
 from pathlib import Path
 
 from ..analysis import ProteinAnalysis
 from ..functional import get_atom14_coords, proximal_optimizer
-from ..pdb_io import contains_sidechains, from_pdb_file, to_pdb
+from ..pdb_io import OBSTACLE_MODES, contains_sidechains, from_pdb_file, insert_obstacle_lines, obstacles_for, to_pdb
 
 
-def main(argv=None):
+def build_parser():
     p = argparse.ArgumentParser()
     p.add_argument("--input", type=str, help="The input pdb file path.", required=True)
     p.add_argument("--outdir", type=str, help="Directory to store outputs.", required=True)
@@ -24,14 +27,27 @@ def main(argv=None):
     p.add_argument("--device", type=str, default="cuda")
     p.add_argument("--repack", type=str, default=None, metavar="SPEC|interface", help="Optimise only these residues, e.g. "
                    "'A:45-60,B:12,C' (chain and PDB residue number) or 'interface'; the others keep the input's angles.")
-    args = p.parse_args(argv)
+    p.add_argument("--obstacles", choices=OBSTACLE_MODES, default="none", help="Fixed atoms the clash stages keep the side chains off (DESIGN.md section 19): none (default), hetero = every HETATM record and "
+                   "every non-standard residue (ligands, cofactors, nucleic acids; no hydrogens, waters or metals), hetero+water = the "
+                   "waters too. The diffusion network does not see them: the clash stages of this tool repair"
+                   " what it puts into the pocket. Written structures keep the records.")
+    return p
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
 
     assert contains_sidechains(args.input), "----- No side chain atoms found in the input PDB -----"
     print("----- Starting optimize! -----")
     analysis = ProteinAnalysis(args.molprobity_clash_loc, args.outdir, args.device)
     print(f"----- The input structure clashscore is {analysis.get_clashscore(args.input)} -----")
     protein = from_pdb_file(Path(args.input), mse_to_met=True)
-    batch = analysis.get_prot(args.input).to(args.device)
+    obstacles = obstacles_for(args.input, args.obstacles)
+    batch = analysis.get_prot(args.input)
+    if obstacles is not None:
+        from ..featurize import _add_obstacles
+        _add_obstacles(batch, obstacles)
+    batch = batch.to(args.device)
     fixed = None
     if args.repack is not None:
         import torch
@@ -45,7 +61,21 @@ def main(argv=None):
     xyz = get_atom14_coords(batch.X, batch.residue_type, batch.BB_D, SC_D)
     protein["atom_positions"] = xyz.cpu().squeeze(0).numpy()
     with open(analysis.tmp_pdb, "w") as fh:
-        fh.writelines(to_pdb(protein))
+        fh.writelines(insert_obstacle_lines(to_pdb(protein), obstacles["lines"] if obstacles else []))
+    if obstacles is not None:
+        import os
+        from ..functional import _ctx_for
+        kw = dict(vtf=args.violation_tolerance_factor, tol=args.clash_overlap_tolerance)
+        ctx, shares = _ctx_for(batch), []
+        for chi in (batch.SC_D, SC_D):
+            with_set = ctx.clash(chi, **kw)
+            ctx.set_obstacles(None)
+            shares.append((with_set - ctx.clash(chi, **kw))[0].cpu().tolist())
+            ctx.set_obstacles(batch.obstacle_xyzr, ctx._obstacle_ranges(batch))
+        with open(os.path.join(args.outdir, "obstacles.csv"), "w") as fh:
+            fh.write("residue,chain,clash_obstacles_before,clash_obstacles_after\n")
+            for num, cid, b, a in zip(protein["residue_index"], protein["chain_id"], *shares):
+                fh.write(f"{int(num)},{cid},{b!r},{a!r}\n")
     print(f"----- The optimized structure clashscore is {analysis.get_clashscore(analysis.tmp_pdb)} -----")
     print("----- Finishing optimize! -----")
 

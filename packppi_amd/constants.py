@@ -33,6 +33,14 @@ bond_rows = _z["bond_rows"]                      # [n,5] f64  (restype, a, b, le
 slot_radius = _z["slot_radius"]                  # [21,14] f64 element vdW radius, 0 for empty slot
 between_radius = _z["between_radius"]            # [21,14] f64 radius table of clash.py:263-287
 
+# van der Waals radii by element: the four the reference's clash loss knows (residue_constants.py:280-285, what slot_radius and
+# between_radius above are made of) ...
+van_der_waals_radius = {"C": 1.7, "N": 1.55, "O": 1.52, "S": 1.8}
+# ... and, for obstacle atoms (pdb_io.obstacle_atoms), Bondi's values (J. Phys. Chem. 68, 441, 1964) for the
+# other elements of common ligands, cofactors and nucleic acids.  Metals are left out on purpose: an ion coordinates side chains at
+# 2.0-2.3 A, which is not a clash.
+obstacle_radius = dict(van_der_waals_radius, P=1.80, F=1.47, CL=1.75, BR=1.85, I=1.98, SE=1.90)
+
 
 @lru_cache(maxsize=16)
 def make_atom14_dists_bounds(overlap_tolerance: float = 1.5,

@@ -345,6 +345,7 @@ extern "C" void pp_ctx_destroy(pp_ctx *c) {
         }
     }
     for (hipEvent_t e : c->prof_ev) (void)hipEventDestroy(e);
+    if (c->obst) (void)hipFree(c->obst);              // waits for the device: only a context that ever held obstacles pays it
     delete c;
 }
 
@@ -424,6 +425,7 @@ static pp_status prepare_impl(pp_plan *plan, const pp_batch *b, const int32_t *s
     ALLOC(seg, N);
     ALLOC(prox_part, (size_t)PP_PROX_CHUNK * N);
     if (prox) { ALLOC(prox_nrows, c->B); ALLOC(prox_seg, c->B); ALLOC(prox_inv, N); }
+    if (prox) { ALLOC(obst_seg, c->B); ALLOC(obst_row, N); ALLOC(obst_cand, (size_t)N * PP_OB_CAP); ALLOC(obst_cnt, N); }
     ALLOC(seg_off, (size_t)c->B + 1);
     ALLOC(rng_tab, N); ALLOC(rng_keys, c->B);
     c->max_steps = 1 << 20;
@@ -838,6 +840,61 @@ extern "C" pp_status pp_proximal(pp_ctx *c, const float *chi, float lamda, int n
     return pp_launch_proximal(c, chi, lamda, num_steps, chi_traj, chi_last, losses, static_cast<hipStream_t>(stream));
 }
 
+// ---- obstacle atoms ----------------------------------------------------------------------------------------
+// the context's copy of the caller's atoms; a non-finite coordinate or radius, or a negative radius, sets bit 2 of the sticky word
+__global__ void k_obst_copy(const float4 *__restrict__ src, float4 *__restrict__ dst, int M, unsigned *__restrict__ sat) {
+    const int o = blockIdx.x * blockDim.x + threadIdx.x;
+    if (o >= M) return;
+    const float4 q = src[o];
+    dst[o] = q;
+    const float big = 3.402823466e38f;
+    const bool fin = __builtin_fabsf(q.x) <= big && __builtin_fabsf(q.y) <= big && __builtin_fabsf(q.z) <= big && __builtin_fabsf(q.w) <= big;
+    if (!fin || q.w < 0.f) atomicOr(sat, 4u);
+}
+// obst_row[n] = the range of the segment row n belongs to
+__global__ void k_obst_rows(int N, const int32_t *__restrict__ off, int n_seg, const int2 *__restrict__ oseg, int2 *__restrict__ orow) {
+    const int n = blockIdx.x * blockDim.x + threadIdx.x;
+    if (n < N) orow[n] = oseg[pp_seg_of_row(off, n_seg, n)];
+}
+
+extern "C" pp_status pp_ctx_set_obstacles(pp_ctx *c, const float *xyzr, const int32_t *seg_range, int M, void *stream) {
+    if (!c) FAIL(PP_ERR_INVALID, "pp_ctx_set_obstacles: null ctx");
+    c->last_stream = static_cast<hipStream_t>(stream);
+    if (!c->packed && c->B != 1)
+        FAIL(PP_ERR_INVALID, "pp_ctx_set_obstacles: needs a context from pp_complex_prepare_packed (or a B = 1 one), not a padded B > 1 batch");
+    if (M < 0) FAIL(PP_ERR_INVALID, "pp_ctx_set_obstacles: M must not be negative");
+    if (M == 0 || !xyzr) {          // clear: the launchers go back to the instances without obstacles; the allocation stays for the next set
+        c->obst_M = 0;
+        return PP_OK;
+    }
+    if (!seg_range) FAIL(PP_ERR_INVALID, "pp_ctx_set_obstacles: null seg_range");
+    for (int s = 0; s < c->B; s++) {
+        const long long first = seg_range[2 * s], count = seg_range[2 * s + 1];
+        if (first < 0 || count < 0 || first + count > M)
+            FAIL(PP_ERR_INVALID, "pp_ctx_set_obstacles: the range of segment " + std::to_string(s) + " (" + std::to_string(first) + ", " +
+                                     std::to_string(count) + ") lies outside the " + std::to_string(M) + " atoms");
+    }
+    PP_HIP_CHECK(hipSetDevice(c->plan->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (M > c->obst_cap) {
+        // a larger copy: hipFree waits for the device, so nothing enqueued can still read the old one (the only wait of this call, and
+        // only when the set grows)
+        if (c->obst) (void)hipFree(c->obst);
+        c->obst = nullptr;
+        c->obst_cap = 0;
+        c->obst_M = 0;
+        PP_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&c->obst), (size_t)M * sizeof(float4)));
+        c->obst_cap = M;
+    }
+    // the host table is caller-owned: from pageable memory, hipMemcpyAsync has taken the data when it returns
+    PP_HIP_CHECK(hipMemcpyAsync(c->obst_seg, seg_range, (size_t)c->B * sizeof(int2), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_obst_copy, dim3((M + 255) / 256), dim3(256), 0, s, reinterpret_cast<const float4 *>(xyzr), c->obst, M, c->sat);
+    hipLaunchKernelGGL(k_obst_rows, dim3((c->N + 255) / 256), dim3(256), 0, s, c->N, c->seg_off, c->B, c->obst_seg, c->obst_row);
+    PP_HIP_CHECK(hipGetLastError());
+    c->obst_M = M;
+    return PP_OK;
+}
+
 // pp_proximal_packed and pp_proximal_pinned (`who` names the export in messages; fixed == nullptr: no pin)
 static pp_status proximal_packed_impl(const char *who, pp_ctx *c, const float *chi, const uint8_t *fixed, float lamda, int num_steps,
                                       const int32_t *norm_rows, float *chi_traj, float *chi_last, float *chi_accepted, float *losses,
@@ -929,15 +986,15 @@ extern "C" pp_status pp_debug_set_hE(pp_ctx *c, const float *src, size_t n) {
     return PP_OK;
 }
 // which: 0 h_E, 1 S, 2 msum, 3 h_E0, 4 Z_em, 5 h_V, 6 score, 7 cand_cnt [N][4] (the int32 bits in the 4-byte slots: what the last
-// proximal call's k_clash_cand left), 8 the plan's side_extent [21]
+// proximal call's k_clash_cand left), 8 the plan's side_extent [21], 9 obst_cnt [N] (int32 bits: what its k_obst_cand left)
 extern "C" pp_status pp_debug_buffer(pp_ctx *c, int which, float *dst, size_t n) {
     if (!c || !dst) FAIL(PP_ERR_INVALID, "pp_debug_buffer: null");
     const float *src = which == 0 ? c->hE : which == 1 ? c->S : which == 2 ? c->msum : which == 3 ? c->hE0 : which == 4 ? c->Zem :
                        which == 6 ? c->score : c->hV;
-    if (which == 7 || which == 8) {
-        src = which == 7 ? reinterpret_cast<const float *>(c->cand_cnt) : c->plan->side_extent;
+    if (which == 7 || which == 8 || which == 9) {
+        src = which == 7 ? reinterpret_cast<const float *>(c->cand_cnt) : which == 9 ? reinterpret_cast<const float *>(c->obst_cnt) : c->plan->side_extent;
         if (!src) FAIL(PP_ERR_INVALID, "pp_debug_buffer: this context has no candidate lists");
-        if (n > (which == 7 ? (size_t)c->N * 4 : (size_t)21)) FAIL(PP_ERR_INVALID, "pp_debug_buffer: n is larger than the table");
+        if (n > (which == 7 ? (size_t)c->N * 4 : which == 9 ? (size_t)c->N : (size_t)21)) FAIL(PP_ERR_INVALID, "pp_debug_buffer: n is larger than the table");
     }
     PP_HIP_CHECK(hipDeviceSynchronize());
     PP_HIP_CHECK(hipMemcpy(dst, src, n * sizeof(float), hipMemcpyDeviceToDevice));

@@ -279,13 +279,32 @@ struct ClashFuse {
 // (The tail's reconstruction chain wants ~130 registers; with the 33 KB candidate lists the compiler holds the kernel to the 128 of four
 // waves per SIMD and spills twenty dwords in the tail.  Buying them with amdgpu_waves_per_eu(1, 3) -- 129 registers, no scratch -- made
 // the launch 2.2x SLOWER, 36 instead of 16 us at T1124: profiles/r05_prox_fused_step.txt.  The spill stays.)
-template <bool CAND, bool FUSE>
+//
+// OBST (a context that holds obstacle atoms, pp_ctx_set_obstacles): behind the partner loop and in front of the
+// first stripe fold every own side-chain atom a (slots 4..13, exists * radius = r_a != 0) takes the hinge against the obstacle atoms
+// of its segment, err = max((r_a + r_o) - tol - sqrt(1e-10 + |p_a - q_o|^2), 0), into the same loss_a and ga with the residue's own
+// weight wi (an obstacle has no residue and does not move).  Obstacle number l of the segment's range (l counted from the range's
+// first atom) belongs to wave (l / 64) mod CL_WAVES and to stripe l mod 4 -- a function of l alone --, and every (wave, stripe) lane
+// adds its obstacles in ascending l: the sum has one fixed order whatever list the obstacles came from.  They come from the static
+// candidates of the row (O.cand, k_obst_cand: the Adam loop) or from a scan of the range (O.cand == nullptr, or a row whose count is
+// -1); both put a bounding-sphere test in front that drops only obstacles whose hinge is identically zero on every atom, so the two
+// paths agree bit for bit.  The survivors are compacted per stripe into the four quarters of s_list[wave], which is free here.
+// The OBST = false instances do not read O and are, to the instruction, the kernels of before (profiles/r19_obstacles_isa.txt).
+struct ClashObst {
+    const float4 *atoms;          // [M] (x, y, z, radius)
+    const int2 *row;              // [N] (first, count): the range of the row's segment
+    const int32_t *cand;          // [N][PP_OB_CAP] static candidates (indices into atoms, ascending), or nullptr: scan
+    const int32_t *cand_cnt;      // [N] their number, -1: scan
+};
+#define CL_OB_Q (CL_MAXC / 4)     // obstacle indices one stripe holds in LDS before the wave works them off
+#define CL_RA_MAX 1.8f            // the largest between-residue radius of a protein atom (S): reach = 3.6 - tol is twice this
+template <bool CAND, bool FUSE, bool OBST>
 __global__ void __launch_bounds__(64 * CL_WAVES)
 k_clash(int N, const int2 *__restrict__ seg, const float *__restrict__ xyz, const float4 *__restrict__ rec, const float *__restrict__ exists,
         const float *__restrict__ lower, const float *__restrict__ upper, const int32_t *__restrict__ a2g,
         const float *__restrict__ axes, float tol, float inv_ntot,
         float *__restrict__ per_res, float *__restrict__ dchi, const int32_t *__restrict__ cand, const int32_t *__restrict__ cand_cnt,
-        ClashFuse F) {
+        ClashFuse F, ClashObst O) {
     __shared__ int s_list[CL_WAVES][CL_MAXC];
     __shared__ float s_red[CL_WAVES][16][4];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -407,6 +426,61 @@ k_clash(int N, const int2 *__restrict__ seg, const float *__restrict__ xyz, cons
             }
         }
         __builtin_amdgcn_wave_barrier();
+    }
+    if constexpr (OBST) {
+        const int2 orng = O.row[i];
+        const int n_ost = O.cand ? O.cand_cnt[i] : -1;
+        const bool ost = n_ost >= 0;                          // uniform over the workgroup
+        const int32_t *oc = ost ? O.cand + (size_t)i * PP_OB_CAP : nullptr;
+        const int nsl = ost ? n_ost : orng.y;
+        const int ostep = ost ? 64 : 64 * CL_WAVES;
+        const float oreach = CL_RA_MAX - tol;
+        const bool act = own && a >= 4 && ea != 0.f;
+        int ocnt[4] = {0, 0, 0, 0};
+        for (int c0 = ost ? 0 : 64 * wave; c0 < nsl; c0 += ostep) {
+            const int ci = c0 + lane;
+            bool keep = false;
+            int og = 0, ol = 0;
+            if (ci < nsl) {
+                og = ost ? oc[ci] : orng.x + ci;
+                ol = og - orng.x;
+                if (((ol >> 6) & (CL_WAVES - 1)) == wave) {
+                    const float4 q = O.atoms[og];
+                    const float dx = q.x - cai[0], dy = q.y - cai[1], dz = q.z - cai[2];
+                    const float lim = radi + q.w + oreach;
+                    keep = q.w > 0.f && lim > 0.f && (dx * dx + dy * dy + dz * dz < lim * lim);
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const bool mine = keep && (ol & 3) == k;
+                const unsigned long long bal = __ballot(mine);
+                if (mine) list[k * CL_OB_Q + ocnt[k] + __popcll(bal & ((1ull << lane) - 1ull))] = og;
+                ocnt[k] += __popcll(bal);
+            }
+            const int most = max(max(ocnt[0], ocnt[1]), max(ocnt[2], ocnt[3]));
+            if (most + 64 <= CL_OB_Q && c0 + ostep < nsl) continue;
+            __builtin_amdgcn_wave_barrier();
+            const int mycnt = slot == 0 ? ocnt[0] : (slot == 1 ? ocnt[1] : (slot == 2 ? ocnt[2] : ocnt[3]));
+            for (int c = 0; c < mycnt; c++) {
+                const float4 q = O.atoms[list[slot * CL_OB_Q + c]];
+                if (act) {
+                    const float dx = pa[0] - q.x, dy = pa[1] - q.y, dz = pa[2] - q.z;
+                    const float d2 = 1e-10f + dx * dx + dy * dy + dz * dz;
+                    const float thr = (ra + q.w) - tol;
+                    if (!(thr > 0.f && d2 < thr * thr)) continue;
+                    const float d = sqrtf(d2);
+                    const float err = thr - d;
+                    if (err > 0.f) {
+                        loss_a += err;
+                        const float sc = -wi / d;
+                        ga[0] = fmaf(sc, dx, ga[0]); ga[1] = fmaf(sc, dy, ga[1]); ga[2] = fmaf(sc, dz, ga[2]);
+                    }
+                }
+            }
+            __builtin_amdgcn_wave_barrier();
+            ocnt[0] = ocnt[1] = ocnt[2] = ocnt[3] = 0;
+        }
     }
     // fold the 4 partner stripes, then the 4 waves (fixed order: reproducible)
     for (int o = 16; o <= 32; o <<= 1) {
@@ -572,6 +646,48 @@ k_clash_cand(int N, const int2 *__restrict__ seg, const float *__restrict__ X, c
     if (lane == 0) cand_cnt[(size_t)i * CL_WAVES + wave] = cnt <= PP_CL_CAP ? cnt : -1;
 }
 
+// Static obstacle candidates of the proximal loop, once per pp_proximal* beside k_clash_cand: obstacle o of row i's segment is kept iff
+//   |CA_i - q_o| < e_i + r_o + (1.8 - tol)        (e_i as above; 1.8 = the largest radius of a protein atom),
+// outside of which its hinge is zero on every atom of the residue at every chi.  One wave per row walks the segment's range in order,
+// so the list is ascending; more than PP_OB_CAP of them and the row keeps the scan (count -1).  Obstacles with r_o <= 0 are never kept.
+__global__ void __launch_bounds__(256)
+k_obst_cand(int N, const float *__restrict__ X, const float *__restrict__ amask, const int64_t *__restrict__ rtype,
+            const float *__restrict__ side_extent, float tol, const float4 *__restrict__ atoms, const int2 *__restrict__ orow,
+            int32_t *__restrict__ cand, int32_t *__restrict__ cand_cnt) {
+    const int lane = threadIdx.x & 63;
+    const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= N) return;
+    const float *x = X + (size_t)i * 42;
+    const float ca[3] = {x[3], x[4], x[5]};
+    float e = side_extent[(int)rtype[i]];
+    const float *m = amask + (size_t)i * 14;
+#pragma unroll
+    for (int a = 0; a < 4; a++) {
+        if (a == 1 || m[a] == 0.f) continue;
+        const float dx = x[3 * a] - ca[0], dy = x[3 * a + 1] - ca[1], dz = x[3 * a + 2] - ca[2];
+        e = fmaxf(e, sqrtf(dx * dx + dy * dy + dz * dz) * 1.0001f + 1e-3f);
+    }
+    const int2 rng = orow[i];
+    const float reach = CL_RA_MAX - tol;
+    int32_t *out = cand + (size_t)i * PP_OB_CAP;
+    int cnt = 0;
+    for (int c0 = 0; c0 < rng.y; c0 += 64) {
+        const int ol = c0 + lane;
+        bool keep = false;
+        if (ol < rng.y) {
+            const float4 q = atoms[rng.x + ol];
+            const float dx = q.x - ca[0], dy = q.y - ca[1], dz = q.z - ca[2];
+            const float lim = e + q.w + reach;
+            keep = q.w > 0.f && lim > 0.f && dx * dx + dy * dy + dz * dz < lim * lim;
+        }
+        const unsigned long long bal = __ballot(keep);
+        const int at = cnt + __popcll(bal & ((1ull << lane) - 1ull));
+        if (keep && at < PP_OB_CAP) out[at] = rng.x + ol;
+        cnt += __popcll(bal);
+    }
+    if (lane == 0) cand_cnt[i] = cnt <= PP_OB_CAP ? cnt : -1;
+}
+
 // ---------------------------------------------------------------------------------------------
 // proximal optimiser pieces: per complex (segment) of the context.  pp_proximal is the one-segment case of pp_proximal_packed.
 // ---------------------------------------------------------------------------------------------
@@ -697,18 +813,41 @@ pp_status pp_launch_atom14(pp_ctx *c, const float *chi, float *xyz, hipStream_t 
     return PP_OK;
 }
 
+// the obstacle argument of k_clash<., ., true>: with `cands` the static candidates k_obst_cand left, else every row scans its range
+static ClashObst clash_obst(const pp_ctx *c, bool cands) {
+    ClashObst O{};
+    O.atoms = c->obst;
+    O.row = c->obst_row;
+    if (cands) { O.cand = c->obst_cand; O.cand_cnt = c->obst_cnt; }
+    return O;
+}
+
 pp_status pp_launch_clash(pp_ctx *c, const float *xyz, float *per_res, float *dchi, hipStream_t s, bool use_candidates) {
     const pp_plan *p = c->plan;
-    if (use_candidates && c->cand)
-        PP_LAUNCH(c, (k_clash<true, false>), dim3(c->N), dim3(64 * CL_WAVES), 0, s, c->N, c->seg, xyz,
+    const bool ca = use_candidates && c->cand;
+    // the instance is chosen here, by whether the context holds obstacles: the OBST = false kernels carry no test for them
+    if (c->obst_M > 0) {
+        const ClashObst O = clash_obst(c, ca);
+        if (ca)
+            PP_LAUNCH(c, (k_clash<true, false, true>), dim3(c->N), dim3(64 * CL_WAVES), 0, s, c->N, c->seg, xyz,
+                      reinterpret_cast<const float4 *>(c->rec), c->b.atom_mask,
+                      p->bounds_lower, p->bounds_upper, p->atom14_to_group, c->axes, p->clash_tol,
+                      1.0f / (float)c->N, per_res, dchi, c->cand, c->cand_cnt, ClashFuse{}, O);
+        else
+            PP_LAUNCH(c, (k_clash<false, false, true>), dim3(c->N), dim3(64 * CL_WAVES), 0, s, c->N, c->seg, xyz,
+                      reinterpret_cast<const float4 *>(c->rec), c->b.atom_mask,
+                      p->bounds_lower, p->bounds_upper, p->atom14_to_group, c->axes, p->clash_tol,
+                      1.0f / (float)c->N, per_res, dchi, nullptr, nullptr, ClashFuse{}, O);
+    } else if (ca)
+        PP_LAUNCH(c, (k_clash<true, false, false>), dim3(c->N), dim3(64 * CL_WAVES), 0, s, c->N, c->seg, xyz,
                   reinterpret_cast<const float4 *>(c->rec), c->b.atom_mask,
                   p->bounds_lower, p->bounds_upper, p->atom14_to_group, c->axes, p->clash_tol,
-                  1.0f / (float)c->N, per_res, dchi, c->cand, c->cand_cnt, ClashFuse{});
+                  1.0f / (float)c->N, per_res, dchi, c->cand, c->cand_cnt, ClashFuse{}, ClashObst{});
     else
-        PP_LAUNCH(c, (k_clash<false, false>), dim3(c->N), dim3(64 * CL_WAVES), 0, s, c->N, c->seg, xyz,
+        PP_LAUNCH(c, (k_clash<false, false, false>), dim3(c->N), dim3(64 * CL_WAVES), 0, s, c->N, c->seg, xyz,
                   reinterpret_cast<const float4 *>(c->rec), c->b.atom_mask,
                   p->bounds_lower, p->bounds_upper, p->atom14_to_group, c->axes, p->clash_tol,
-                  1.0f / (float)c->N, per_res, dchi, nullptr, nullptr, ClashFuse{});
+                  1.0f / (float)c->N, per_res, dchi, nullptr, nullptr, ClashFuse{}, ClashObst{});
     PP_HIP_CHECK(hipGetLastError());
     return PP_OK;
 }
@@ -726,6 +865,12 @@ static pp_status prox_loop(pp_ctx *c, const float *chi, float lamda, int nsteps,
     if (cands)
         hipLaunchKernelGGL(k_clash_cand, dim3(c->N), dim3(64 * CL_WAVES), 0, s, c->N, c->seg, c->b.X, c->b.atom_mask, c->b.residue_type,
                            c->b.residue_index, p->side_extent, p->clash_tol, c->cand, c->cand_cnt);
+    // the same for the obstacle atoms of a context that holds some: the Adam loop never scans a complex's whole range
+    const bool obst = c->obst_M > 0;
+    if (obst && cands)
+        hipLaunchKernelGGL(k_obst_cand, dim3((c->N + 3) / 4), dim3(256), 0, s, c->N, c->b.X, c->b.atom_mask, c->b.residue_type,
+                           p->side_extent, p->clash_tol, c->obst, c->obst_row, c->obst_cand, c->obst_cnt);
+    const ClashObst O = obst ? clash_obst(c, cands) : ClashObst{};
     // clash mask at the incoming angles (optimize.py:5-18); per_res does not depend on the normaliser
     if ((st = pp_launch_atom14(c, chi, c->xyz, s)) != PP_OK) return st;
     if ((st = pp_launch_clash(c, c->xyz, c->per_res, nullptr, s, cands)) != PP_OK) return st;
@@ -758,14 +903,22 @@ static pp_status prox_loop(pp_ctx *c, const float *chi, float lamda, int nsteps,
         U.traj = traj ? traj + (size_t)(t - U.t) * c->N * 4 : nullptr;     // U.t indexes within the chunk
         c->prof_armed = c->prof_which == 3;          // pp_profile_kernel(3): the fused clash + Adam step + reconstruction
         const float4 *rin = reinterpret_cast<const float4 *>(rec_in);
-        if (cands)
-            PP_LAUNCH(c, (k_clash<true, true>), dim3(c->N), dim3(64 * CL_WAVES), 0, s, c->N, c->seg, c->xyz,
+        if (obst && cands)
+            PP_LAUNCH(c, (k_clash<true, true, true>), dim3(c->N), dim3(64 * CL_WAVES), 0, s, c->N, c->seg, c->xyz,
                       rin, c->b.atom_mask, p->bounds_lower, p->bounds_upper, p->atom14_to_group,
-                      axes_in, p->clash_tol, inv_ntot_unused, c->per_res, c->dchi, c->cand, c->cand_cnt, F);
+                      axes_in, p->clash_tol, inv_ntot_unused, c->per_res, c->dchi, c->cand, c->cand_cnt, F, O);
+        else if (obst)
+            PP_LAUNCH(c, (k_clash<false, true, true>), dim3(c->N), dim3(64 * CL_WAVES), 0, s, c->N, c->seg, c->xyz,
+                      rin, c->b.atom_mask, p->bounds_lower, p->bounds_upper, p->atom14_to_group,
+                      axes_in, p->clash_tol, inv_ntot_unused, c->per_res, c->dchi, nullptr, nullptr, F, O);
+        else if (cands)
+            PP_LAUNCH(c, (k_clash<true, true, false>), dim3(c->N), dim3(64 * CL_WAVES), 0, s, c->N, c->seg, c->xyz,
+                      rin, c->b.atom_mask, p->bounds_lower, p->bounds_upper, p->atom14_to_group,
+                      axes_in, p->clash_tol, inv_ntot_unused, c->per_res, c->dchi, c->cand, c->cand_cnt, F, O);
         else
-            PP_LAUNCH(c, (k_clash<false, true>), dim3(c->N), dim3(64 * CL_WAVES), 0, s, c->N, c->seg, c->xyz,
+            PP_LAUNCH(c, (k_clash<false, true, false>), dim3(c->N), dim3(64 * CL_WAVES), 0, s, c->N, c->seg, c->xyz,
                       rin, c->b.atom_mask, p->bounds_lower, p->bounds_upper, p->atom14_to_group,
-                      axes_in, p->clash_tol, inv_ntot_unused, c->per_res, c->dchi, nullptr, nullptr, F);
+                      axes_in, p->clash_tol, inv_ntot_unused, c->per_res, c->dchi, nullptr, nullptr, F, O);
         c->prof_armed = false;
         std::swap(rec_in, rec_out);
         std::swap(axes_in, axes_out);

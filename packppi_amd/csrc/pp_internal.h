@@ -46,6 +46,7 @@
 #define PP_NPTS 8         // invariant points per node
 #define PP_PROX_CHUNK 64   // proximal steps whose loss terms are parked before one reduction
 #define PP_CL_CAP 96       // static clash-partner candidates kept per (residue, wave) -- k_clash_cand / k_clash<true>
+#define PP_OB_CAP PP_OBSTACLE_CAP      // static obstacle candidates kept per residue -- k_obst_cand / k_clash<CAND, FUSE, true> (include/packppi_hip.h)
 
 #include "pp_weights.h"      // LayerOff / WeightOff / pp_weight_offsets(): offsets into the concatenated weight buffer
 #include "pp_rng.h"          // Philox4x32-10 and the normal transform of the seeded sampling noise (counter layout there)
@@ -185,6 +186,14 @@ struct pp_ctx {
     float2 *prox_seg;         // [B] per complex: (mean divisor, 1 / divisor), written by k_prox_init
     float *prox_inv;          // [N] 1 / divisor of the row's complex: the gradient and anchor weight of k_clash<CAND, true>
     float *scal;              // small scalar scratch
+    // obstacle atoms (pp_ctx_set_obstacles): fixed spheres the side chains of a segment must not overlap
+    float4 *obst = nullptr;   // [obst_M] (x, y, z, radius): the context's own copy, ONE allocation outside the arena, freed with the ctx
+    int obst_M = 0;           // 0 = the context holds no obstacles: every launcher takes the instances it has always taken
+    int obst_cap = 0;         // atoms the allocation holds
+    int2 *obst_seg;           // [B] (first, count) of every segment's range in obst
+    int2 *obst_row;           // [N] the range of the row's segment (k_obst_rows)
+    int32_t *obst_cand;       // [N][PP_OB_CAP] proximal: static obstacle candidates of every residue, ascending (k_obst_cand)
+    int32_t *obst_cnt;        // [N] their number, -1 = more than PP_OB_CAP (the residue scans its segment's range)
     // seeded sampling noise (pp_rng.h): the per-row table of the seeded kernels and the complexes' keys
     pp_rng_row *rng_tab;      // [N] (row within the complex, key of the complex); filled by pp_launch_rng_table
     uint64_t *rng_keys;       // [B] the caller's keys (pp_ctx_set_rng_keys), staged for the table kernel

@@ -50,6 +50,10 @@ struct RcArgs {
     const float *X, *amask, *side_extent, *lower, *upper;
     const int64_t *rtype, *rindex;
     float tol;
+    // obstacle atoms of the context (pp_ctx_set_obstacles), or oatoms == nullptr: none.  They belong to the group: U(r, d) gains the
+    // obstacle term of row r at decoy d's angles, so F(s) stays the sum of pp_clash's per_res at the recombined angles
+    const float4 *oatoms;            // [.] (x, y, z, radius)
+    const int2 *oseg;                // [B] (first, count) of every segment's range
     // workspace (the context's proximal buffers: the two never run at once on one context)
     int2 *info;                      // [M] (group, row within it), (-1, .) = not a row of a group that is recombined
     int32_t *s, *prop;               // [M] the assignment; this sweep's proposals
@@ -75,6 +79,17 @@ __device__ __forceinline__ bool rc_group(const int32_t *__restrict__ seg_off, in
     for (int d = 1; d < D; d++) {
         pp_seg_rows(seg_off, g * D + d, N, a, b);
         ok = ok && (b - a == len);
+    }
+    return ok;
+}
+// obstacles belong to the group: its decoys must point at one range (a group that does not is left alone like a ragged one)
+__device__ __forceinline__ bool rc_obst_same(const RcArgs &A, int g) {
+    if (!A.oatoms) return true;
+    const int2 r0 = A.oseg[g * A.D];
+    bool ok = true;
+    for (int d = 1; d < A.D; d++) {
+        const int2 r = A.oseg[g * A.D + d];
+        ok = ok && r.x == r0.x && r.y == r0.y;
     }
     return ok;
 }
@@ -127,7 +142,7 @@ k_rc_setup(RcArgs A) {
         int base, len, row0;
         bool ok = rc_group(A.seg_off, g, A.D, A.N, base, len, row0);
         const int st = A.start ? A.start[g] : 0;
-        ok = ok && st >= 0 && st < A.D;
+        ok = ok && st >= 0 && st < A.D && rc_obst_same(A, g);
         if (threadIdx.x == 0) {
             A.ginfo[g] = make_int4(base, len, ok ? 1 : 0, 0);
             A.cnt[2 * g] = 0;
@@ -154,7 +169,7 @@ k_rc_setup(RcArgs A) {
     bool ok = rc_group(A.seg_off, g, A.D, A.N, base, len, row0);
     const int r = cr - base;
     const int st = A.start ? A.start[g] : 0;
-    ok = ok && st >= 0 && st < A.D && r >= 0 && r < len;
+    ok = ok && st >= 0 && st < A.D && r >= 0 && r < len && rc_obst_same(A, g);
     if (!ok) {
         if (lane == 0) A.info[cr] = make_int2(-1, 0);
         return;
@@ -298,6 +313,37 @@ k_rc_propose(RcArgs A, int k, int full, int count) {
                 const float dd = sqrtf(1e-10f + dx * dx + dy * dy + dz * dz);
                 const float lo = A.lower[(S * 14 + a) * 14 + bb], up = A.upper[(S * 14 + a) * 14 + bb];
                 ua += 2.f * (fmaxf(lo - dd, 0.f) + fmaxf(dd - up, 0.f));          // row sum + column sum of a symmetric table
+            }
+        }
+        // the obstacle term of k_clash<., ., true>: obstacle l of the group's range goes to stripe l mod 4, ascending l per lane; the
+        // residue's bounding sphere drops obstacles whose hinge is zero on every atom
+        if (A.oatoms) {
+            const int2 orng = A.oseg[g * D];
+            const float oreach = 1.8f - tol;
+            const bool act = own && a >= 4 && ea != 0.f;
+            for (int c0 = 0; c0 < orng.y; c0 += 64) {
+                bool keep = false;
+                if (c0 + lane < orng.y) {
+                    const float4 q = A.oatoms[orng.x + c0 + lane];
+                    const float dx = q.x - cme.x, dy = q.y - cme.y, dz = q.z - cme.z;
+                    const float lim = cme.w + q.w + oreach;
+                    keep = q.w > 0.f && lim > 0.f && (dx * dx + dy * dy + dz * dz < lim * lim);
+                }
+                unsigned long long bal = __ballot(keep);
+                while (bal) {
+                    const int l = c0 + __builtin_ctzll(bal);
+                    bal &= bal - 1ull;
+                    const float4 q = A.oatoms[orng.x + l];
+                    if (act && (l & 3) == slot) {
+                        const float dx = pa[0] - q.x, dy = pa[1] - q.y, dz = pa[2] - q.z;
+                        const float d2 = 1e-10f + dx * dx + dy * dy + dz * dz;
+                        const float thr = (ra + q.w) - tol;
+                        if (thr > 0.f && d2 < thr * thr) {
+                            const float err = thr - sqrtf(d2);
+                            if (err > 0.f) ua += err;
+                        }
+                    }
+                }
             }
         }
         // fold the 4 stripes, then the 16 atoms (fixed order)
@@ -468,6 +514,7 @@ extern "C" pp_status pp_ensemble_recombine(pp_ctx *c, const float *chi, int n_de
     A.seg_off = c->seg_off; A.chi = chi; A.rec = reinterpret_cast<const float4 *>(c->rec);
     A.X = c->b.X; A.amask = c->b.atom_mask; A.side_extent = p->side_extent; A.lower = p->bounds_lower; A.upper = p->bounds_upper;
     A.rtype = c->b.residue_type; A.rindex = c->b.residue_index; A.tol = p->clash_tol;
+    A.oatoms = c->obst_M > 0 ? c->obst : nullptr; A.oseg = c->obst_seg;
     // workspace: M <= N consensus rows and G <= N groups fit the [N][4] buffers of the proximal loop; the partner lists fit its
     // candidate lists (M RC_LCAP <= N 4 PP_CL_CAP), which every context this call accepts has
     A.info = reinterpret_cast<int2 *>(c->pm);

@@ -71,8 +71,26 @@ def chain_numbers_and_offset_index(protein: Dict):
     return chain, rindex
 
 
-def protein_to_data(protein: Dict) -> Batch:
-    """Per-complex tensors (no batch axis), as ``prot_to_data`` lays them out."""
+def _add_obstacles(data: Batch, obstacles) -> Batch:
+    """Store obstacle atoms (``pdb_io.obstacle_atoms`` output, or any dict with ``xyz`` [M, 3] and ``radius`` [M]; None = none) in
+    per-complex data as ``obstacle_xyzr`` [M, 4] float32 and ``obstacle_offsets`` [2] (batch.OBSTACLE_KEYS)."""
+    if obstacles is None:
+        return data
+    xyz = torch.as_tensor(np.asarray(obstacles["xyz"], np.float32)).reshape(-1, 3)
+    rad = torch.as_tensor(np.asarray(obstacles["radius"], np.float32)).reshape(-1)
+    if xyz.shape[0] != rad.shape[0]:
+        raise ValueError(f"obstacles: {xyz.shape[0]} positions, {rad.shape[0]} radii")
+    if not bool(torch.isfinite(xyz).all()) or not bool(torch.isfinite(rad).all()) or bool((rad < 0).any()):
+        raise ValueError("obstacles: coordinates and radii must be finite, radii not negative")
+    M = int(xyz.shape[0])
+    data["obstacle_xyzr"] = torch.cat((xyz, rad[:, None]), 1).contiguous()
+    data["obstacle_offsets"] = torch.tensor([0, M], dtype=torch.int32)
+    data["obstacle_offsets_host"] = [0, M]
+    return data
+
+
+def protein_to_data(protein: Dict, obstacles=None) -> Batch:
+    """Per-complex tensors (no batch axis), as ``prot_to_data`` lays them out.  ``obstacles``: see ``protein_to_batch``."""
     X = torch.from_numpy(np.asarray(protein["atom_positions"])).float()
     L = X.shape[0]
     rtype = torch.from_numpy(np.asarray(protein["aaindex"])).long()
@@ -107,12 +125,16 @@ def protein_to_data(protein: Dict) -> Batch:
         chi_2pi_periodic_mask=torch.logical_and(sc_mask, pi2 * m2),
     )
     data.apply(lambda v: torch.nan_to_num(v) if isinstance(v, torch.Tensor) and v.is_floating_point() else v)
-    return data
+    return _add_obstacles(data, obstacles)
 
 
-def protein_to_batch(protein: Dict) -> Batch:
-    """B=1 batch, the form ``ProteinAnalysis.get_prot`` hands to ``sampling`` (protein_analysis.py:103-122)."""
-    return as_single(protein_to_data(protein))
+def protein_to_batch(protein: Dict, obstacles=None) -> Batch:
+    """B=1 batch, the form ``ProteinAnalysis.get_prot`` hands to ``sampling`` (protein_analysis.py:103-122).
+
+    ``obstacles`` (``pdb_io.obstacle_atoms(pdb_file)``, or None): fixed atoms -- ligands, cofactors, nucleic acids -- that every
+    clash stage keeps the side chains off.  The batch then carries ``obstacle_xyzr`` and
+    ``obstacle_offsets``; without them it has exactly the keys it has always had.  The network does not see obstacles."""
+    return as_single(protein_to_data(protein, obstacles))
 
 
 # ---- PackPPI-AP: wild type + mutant featurisation ------------------------------------------------------------------------
@@ -151,7 +173,7 @@ def resolve_mutations(protein: Dict, mutations, log=print):
     return out
 
 
-def mutant_data(protein: Dict, mutations=None, ddg=None, log=print) -> Batch:
+def mutant_data(protein: Dict, mutations=None, ddg=None, log=print, obstacles=None) -> Batch:
     """Per-complex wild-type and mutant tensors, as ``SkempiDataset.prot_to_data`` lays them out without ESM
     (skempi_dataset.py:73-262): the keys of ``protein_to_data`` plus ``ddg``, ``mut_mask`` and the ``*_mut`` keys.
 
@@ -219,7 +241,7 @@ def mutant_data(protein: Dict, mutations=None, ddg=None, log=print) -> Batch:
         chi_2pi_periodic_mask_mut=torch.logical_and(sc_mask_mut, ~pi1_mut * m2),
     )
     data.apply(lambda v: torch.nan_to_num(v) if isinstance(v, torch.Tensor) and v.is_floating_point() else v)
-    return data
+    return _add_obstacles(data, obstacles)
 
 
 def mutant_batch(protein: Dict, mutstr: str, log=print) -> Batch:
@@ -229,7 +251,7 @@ def mutant_batch(protein: Dict, mutstr: str, log=print) -> Batch:
 
 # ---- the mutant as a sampling input -----------------------------------------------------------------------
 
-def mutant_model_data(protein: Dict, mutations=None, log=print) -> Batch:
+def mutant_model_data(protein: Dict, mutations=None, log=print, obstacles=None) -> Batch:
     """The mutant as a batch the sampler can pack: ``protein_to_data`` with the mutated rows rewritten for their NEW residue type.
     ``mutant_data`` builds the mutant the way PackPPI-AP consumes it (chi mask from the wild-type atoms, zero angles); this one
     builds it for ``TDiffusionModule.repack`` / ``mutate``.  Lookup, skipping and errors are ``mutant_data``'s (``resolve_mutations``).
@@ -243,7 +265,7 @@ def mutant_model_data(protein: Dict, mutations=None, log=print) -> Batch:
     comma-separated)."""
     if mutations is None:
         mutations = protein.get("mutations", [])
-    data = protein_to_data(protein)
+    data = protein_to_data(protein, obstacles)
     for k in ("X", "atom_mask", "residue_type", "SC_D", "SC_D_sincos", "SC_D_mask", "chi_1pi_periodic_mask", "chi_2pi_periodic_mask"):
         data[k] = data[k].clone()
     rmask = data["residue_mask"]
@@ -271,6 +293,6 @@ def mutant_model_data(protein: Dict, mutations=None, log=print) -> Batch:
     return data
 
 
-def mutant_model_batch(protein: Dict, mutstr: str, log=print) -> Batch:
-    """B = 1 batch of ``mutant_model_data`` for one mutation string ("RA47A,EA48A")."""
-    return as_single(mutant_model_data(protein, parse_mutstr(mutstr), log=log))
+def mutant_model_batch(protein: Dict, mutstr: str, log=print, obstacles=None) -> Batch:
+    """B = 1 batch of ``mutant_model_data`` for one mutation string ("RA47A,EA48A"); ``obstacles`` as in ``protein_to_batch``."""
+    return as_single(mutant_model_data(protein, parse_mutstr(mutstr), log=log, obstacles=obstacles))

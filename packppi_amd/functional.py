@@ -51,12 +51,14 @@ def get_atom14_coords(X, S, BB_D, SC_D):
 
 
 def compute_residue_clash(batch, SC_D, violation_tolerance_factor=12., clash_overlap_tolerance=0.5):
+    """On a batch with obstacle atoms (``protein_to_batch(..., obstacles=...)``) the clash reported
+    includes every side-chain atom's overlap with the obstacles of its complex."""
     return _ctx_for(batch).clash(SC_D, violation_tolerance_factor, clash_overlap_tolerance)
 
 
 def find_clash_mask(batch, SC_D, violation_tolerance_factor, clash_overlap_tolerance, fixed_mask=None):
     """``fixed_mask`` ([B, L], nonzero = kept): the rows the pinned optimiser moves, the clash mask -- its mean over all rows -- less
-    the kept rows."""
+    the kept rows.  The clash behind the mask includes obstacle atoms, if the batch carries any."""
     pr = compute_residue_clash(batch, SC_D, violation_tolerance_factor, clash_overlap_tolerance)
     mask = pr > pr.mean()
     if fixed_mask is not None:
@@ -67,7 +69,7 @@ def find_clash_mask(batch, SC_D, violation_tolerance_factor, clash_overlap_toler
 def proximal_optimizer(batch, SC_D, violation_tolerance_factor, clash_overlap_tolerance, lamda,
                        num_steps=50, fixed_mask=None) -> Tuple[List[torch.Tensor], List[float]]:
     """``fixed_mask`` ([1, L], nonzero = kept): the pinned optimiser (pp_proximal_pinned); kept rows are ``SC_D`` bit for bit in
-    every entry of the list."""
+    every entry of the list.  On a batch with obstacle atoms the clash in the mask, the loss and the gradient includes them."""
     assert batch.num_proteins == 1
     ctx = _ctx_for(batch)
     if fixed_mask is None:
@@ -91,7 +93,8 @@ def proximal_optimizer_packed(packed_batch, SC_D, violation_tolerance_factor, cl
 
     ``fixed_mask`` ([1, N], nonzero = kept; pp_proximal_pinned): kept rows leave the clash mask, whose mean stays over all rows of
     the complex, and come out as ``SC_D`` bit for bit; all zero gives the bits of the call without it.  ``return_moved`` appends
-    the mask that was optimised (bool [1, N])."""
+    the mask that was optimised (bool [1, N]).  On a batch with obstacle atoms (``batch.pack`` carries them per complex) the clash
+    in every mask, loss and gradient includes the obstacles of the row's own complex."""
     return _ctx_for(packed_batch).proximal_packed(SC_D, violation_tolerance_factor, clash_overlap_tolerance, lamda, num_steps,
                                                   norm_rows=norm_rows, want_traj=want_traj, fixed=fixed_mask,
                                                   return_moved=return_moved)

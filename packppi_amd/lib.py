@@ -22,7 +22,7 @@ SYMBOLS = ("pp_version", "pp_last_error", "pp_build_id", "pp_plan_set_knn_ties",
            "pp_score_rows", "pp_so2_set_grids", "pp_so2_score", "pp_dsm_loss",
            "pp_ctx_set_rng_keys", "pp_noise_seeded", "pp_add_noise_seeded", "pp_sample_seeded",
            "pp_sample_partial", "pp_proximal_pinned", "pp_ctx_live_rows", "pp_ensemble_reduce", "pp_ctx_shell",
-           "pp_ensemble_recombine")
+           "pp_ensemble_recombine", "pp_ctx_set_obstacles")
 
 
 FIX_MODES = {"hold": 0, "renoise": 1}         # PP_FIX_HOLD, PP_FIX_RENOISE
@@ -140,6 +140,7 @@ def load():
     lib.pp_ensemble_reduce.argtypes = [vp, vp, i, vp, i, vp, vp, vp, vp, vp, vp, vp]
     lib.pp_ctx_shell.argtypes = [vp, vp, i, f, i, vp, vp, vp, vp]
     lib.pp_ensemble_recombine.argtypes = [vp, vp, i, vp, i, vp, vp, vp, vp, vp, vp, vp]
+    lib.pp_ctx_set_obstacles.argtypes = [vp, vp, vp, i, vp]
     _lib = lib
     return lib
 
@@ -278,7 +279,7 @@ class BatchKey:
     them on every call (encoder.py:198-246).  A tensor the context had to copy (dtype / layout) is covered the same way: the
     key watches the caller's tensor, not the copy."""
 
-    KEYS = tuple(k for k, _ in _BATCH_SPEC) + ("seg_offsets",)
+    KEYS = tuple(k for k, _ in _BATCH_SPEC) + ("seg_offsets", "obstacle_xyzr", "obstacle_offsets")
 
     def __init__(self, batch):
         self.tensors = [t if isinstance(t, torch.Tensor) else None for t in (_get(batch, k) for k in self.KEYS)]
@@ -350,6 +351,50 @@ class Context:
                                                  min(lens), max(lens), _stream(dev), C.byref(h)),
                    "pp_complex_prepare_packed")
         self.handle = h
+        self.n_obstacles = 0
+        ox = _get(batch, "obstacle_xyzr")
+        if ox is not None:
+            self.set_obstacles(ox, self._obstacle_ranges(batch))
+
+    def _obstacle_ranges(self, batch):
+        """(first, count) per segment from the batch's ``obstacle_offsets``: one range per segment, or, in a batch of decoys
+        (``n_decoys``), one per group, shared by the group's segments."""
+        host = _get(batch, "obstacle_offsets_host")
+        offs = [int(x) for x in (host if host is not None else _get(batch, "obstacle_offsets").tolist())]
+        n_seg, n_rng = self.n_segments, len(offs) - 1
+        D = int(_get(batch, "n_decoys") or 1)
+        if n_rng == n_seg:
+            D = 1
+        elif n_rng * D != n_seg:
+            raise RuntimeError(f"obstacle_offsets describes {n_rng} ranges, the batch has {n_seg} segments (n_decoys {D})")
+        return [(offs[s // D], offs[s // D + 1] - offs[s // D]) for s in range(n_seg)]
+
+    def set_obstacles(self, xyzr=None, seg_range=None):
+        """Install fixed obstacle atoms (pp_ctx_set_obstacles): ``xyzr`` [M, 4] (x, y, z, radius),
+        ``seg_range`` one (first, count) per segment (default: every segment owns all M).  ``clash``, the ``proximal*`` calls and
+        ``ensemble_recombine`` then count the overlap of every side-chain atom with the obstacles of its segment.  ``xyzr`` None or
+        empty clears the set: every call then gives the bits of a context that never had one.  The context keeps its own copy.
+        ``ValueError``: a range outside the atoms; non-finite coordinates or radii or a negative radius in a host tensor (in a device
+        tensor they are found on the device and set bit 2 of ``saturated()``: no read-back here)."""
+        dev = self.plan.device
+        if xyzr is None or xyzr.numel() == 0:
+            _check(load().pp_ctx_set_obstacles(self.handle, None, None, 0, _stream(dev)), "pp_ctx_set_obstacles")
+            self.n_obstacles = 0
+            return
+        src = torch.as_tensor(xyzr)
+        if src.device.type == "cpu" and (not bool(torch.isfinite(src).all()) or bool((src.reshape(-1, 4)[:, 3] < 0).any())):
+            raise ValueError("obstacle coordinates and radii must be finite, radii not negative")
+        x = src.to(device=dev, dtype=torch.float32).reshape(-1, 4).contiguous()
+        M = int(x.shape[0])
+        if seg_range is None:
+            seg_range = [(0, M)] * self.n_segments
+        rng = np.ascontiguousarray([[int(a), int(b)] for a, b in seg_range], dtype=np.int32)
+        if rng.shape != (self.n_segments, 2):
+            raise ValueError(f"seg_range has {rng.shape[0]} entries for {self.n_segments} segments")
+        if (rng < 0).any() or (rng.sum(1) > M).any():
+            raise ValueError(f"seg_range reaches outside the {M} obstacle atoms")
+        _check(load().pp_ctx_set_obstacles(self.handle, _ptr(x), C.c_void_p(rng.ctypes.data), M, _stream(dev)), "pp_ctx_set_obstacles")
+        self.n_obstacles = M
 
     def _new(self, *shape, dtype=torch.float32):
         return torch.empty(*shape, dtype=dtype, device=self.plan.device)
@@ -500,6 +545,7 @@ class Context:
         return xyz
 
     def clash(self, chi, vtf=12.0, tol=0.5, need_grad=False):
+        """per_res [B, L] (and its chi gradient) of pp_clash; on a context with obstacle atoms the overlap with them is included."""
         self.plan.set_clash_params(vtf, tol)
         chi = self._chi(chi)
         per_res = self._new(self.B, self.L)

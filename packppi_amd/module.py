@@ -292,7 +292,11 @@ class TDiffusionModule:
         partial repacking -- those rows keep ``fixed_chi`` (default ``batch.SC_D``), the others are sampled around them
         (DESIGN.md section 13).  ``fixed_mode``: "renoise" (replacement conditioning: at every step the network sees the fixed rows
         noised to that step's level) or "hold" (it sees them clean throughout).  Needs ``seed``; fixed rows of the result are
-        ``fixed_chi`` bit for bit.  ``return_trajectory``: (sample, angles after every step [n_steps, B, L, 4])."""
+        ``fixed_chi`` bit for bit.  ``return_trajectory``: (sample, angles after every step [n_steps, B, L, 4]).
+
+        Obstacle atoms (a batch from ``protein_to_batch(..., obstacles=...)``): the network does not see
+        them, the sample is what it is without them; with ``use_proximal`` the clash the proximal stage reports and optimises
+        includes every side-chain atom's overlap with the obstacles of its complex."""
         cfg = self.hparams.sample_cfg
         if fixed_mask is None:
             fixed_mask = _get(batch, "fixed_mask")
@@ -359,7 +363,8 @@ class TDiffusionModule:
         them -- and then, with ``use_proximal``, the PINNED proximal stage (pp_proximal_pinned): the clash mask of every complex, its
         mean over all of the complex's rows, less the kept rows; the accept rule of ``sampling`` per complex, on the device.  A B = 1
         batch or a packed one (``batch.pack``); ``norm_rows`` as in ``functional.proximal_optimizer_packed`` (the sharded driver passes
-        the padded sizes).  Kept rows of the result are ``fixed_chi`` bit for bit with or without the proximal stage.
+        the padded sizes).  Kept rows of the result are ``fixed_chi`` bit for bit with or without the proximal stage.  On a batch with
+        obstacle atoms the clash of the pinned stage -- mask, loss, gradient -- includes them.
         ``return_list`` (B = 1, with ``use_proximal``): (sample, per-step angles, losses) as ``sampling`` returns them."""
         if fixed_mask is None:
             fixed_mask = _get(batch, "fixed_mask")
@@ -390,7 +395,9 @@ class TDiffusionModule:
 
     def sample_ensemble(self, batch, n_decoys, *, seed=None, use_proximal: bool = False, select="clash", return_all: bool = False,
                         recombine: bool = False, recombine_sweeps: int = 64):
-        """``n_decoys`` seeded samples of every complex in ONE packed pass, reduced on the device.  ``batch``: a
+        """``n_decoys`` seeded samples of every complex in ONE packed pass, reduced on the device.  On
+        complexes with obstacle atoms the decoys of a group share the group's obstacles, and the clash that
+        ranks them, the proximal stage and the recombination include the overlap with them.  ``batch``: a
         B = 1 batch, or a list of complexes (``batch.replicate_many``: group-major, complex g's decoys are segments
         g * n_decoys .. g * n_decoys + n_decoys - 1).  Decoy d of a complex with key k is sampled under the key
         ``batch.decoy_key(k, d)``: it is bit-equal to ``sampling(seed=seed)`` of that complex alone under that key, decoy 0 to what
@@ -521,7 +528,11 @@ class TDiffusionModule:
         ``recombine``: ``SC_D`` and ``X`` are those of the decoys recombined per residue from the selected
         one, and every dict gains ``pick`` int32 [1, L] (the decoy each row was taken from; ``best`` outside the shell),
         ``clash_recombined`` (fp64 scalar tensor, on the scale of ``clash``) and ``rows_recombined`` (scalar tensor: rows with
-        ``pick != best``)."""
+        ``pick != best``).
+
+        A protein dict with an ``obstacles`` entry (``pdb_io.obstacle_atoms``) gives its sets those fixed
+        atoms: the clash every stage reports and optimises -- the pinned proximal stage, the ranking, the recombination -- includes
+        the overlap with them.  The network and the shell rule do not see them."""
         from .batch import as_single, pack, unpack
         from .featurize import mutant_model_data, parse_mutstr
         from .functional import _ctx_for
@@ -535,7 +546,8 @@ class TDiffusionModule:
         for i, pair in enumerate(proteins_and_mutations):
             protein, muts = pair[0], pair[1]
             key = int(pair[2]) if len(pair) > 2 and pair[2] is not None else i
-            data = mutant_model_data(protein, parse_mutstr(muts) if isinstance(muts, str) else muts, log=log)
+            data = mutant_model_data(protein, parse_mutstr(muts) if isinstance(muts, str) else muts, log=log,
+                                     obstacles=protein.get("obstacles"))
             n = int(data["num_nodes"])
             alone.append(n < 32 or int((data["residue_mask"] > 0).sum()) < 32)            # host tensors: no device read-back
             b = as_single(data).to(self.device)

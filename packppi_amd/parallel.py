@@ -132,9 +132,12 @@ def sample_sharded(model, complexes, use_proximal=False, group=None, init_chi=No
     through ``TDiffusionModule.repack`` with the global ids as keys, the kept rows come out as the complex's ``SC_D`` bit for bit,
     and the proximal stage is the pinned one (one call per packed group with the padded sizes, or one per complex), with the same
     independence of ``world``, ``rank``, ``max_rows`` and grouping.
+    Complexes that carry obstacle atoms (``protein_to_batch(..., obstacles=...)``) are refused with ``ValueError``.
     Returns (chi per local complex id, ids_all, rows_all)."""
-    from .batch import pack, unpack
+    from .batch import has_obstacles, pack, unpack
     from .functional import proximal_optimizer, proximal_optimizer_packed
+    if any(has_obstacles(c) for c in (complexes.values() if isinstance(complexes, dict) else complexes)):
+        raise ValueError("sample_sharded does not support complexes with obstacle atoms (DESIGN.md section 19: out of scope)")
     if seed is not None and init_chi is not None:
         raise ValueError("seed and init_chi exclude each other: a seeded run draws its own initial angles")
     if fixed_masks is not None and seed is None:

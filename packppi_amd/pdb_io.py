@@ -123,6 +123,124 @@ def from_pdb_file(pdb_file, mse_to_met: bool = True) -> Dict:
     return parse_atom_records(_atom_records(Path(pdb_file)), mse_to_met=mse_to_met)
 
 
+_WATERS = ("HOH", "WAT", "DOD")
+
+
+def _raw_lines(path) -> List[str]:
+    path = str(path)
+    if path.endswith("pdb.gz"):
+        with gzip.open(path, "rb") as fh:
+            return [ln.decode() for ln in fh]
+    if path.endswith("pdb"):
+        with open(path, "r") as fh:
+            return list(fh)
+    raise ValueError("Unrecognized file type.")
+
+
+def _element(ln: str) -> str:
+    """Element of an ATOM / HETATM record: columns 77-78; if blank, the leading letters of the name field by the PDB alignment rule
+    (a one-letter element's name starts in column 14, a two-letter element's in column 13)."""
+    el = ln[76:78].strip().upper()
+    if el:
+        return el
+    field = ln[12:16]
+    if field[0].isalpha() and not (field[0] == "H" and len(field.strip()) == 4):
+        return field[:2].strip().upper()
+    letters = [c for c in field if c.isalpha()]
+    return letters[0].upper() if letters else ""
+
+
+def obstacle_atoms(pdb_file, water: bool = False, mse_to_met: bool = True, log=None) -> Dict:
+    """The atoms of a PDB file that ``from_pdb_file`` does not return and that side chains must not overlap:
+    every ``HETATM`` record and every ``ATOM`` record of a residue the protein dict drops as non-standard (after MSE -> MET) --
+    ligands, cofactors, nucleic acids, modified residues.  Alternate locations are resolved by the protein rule (highest occupancy,
+    the first record wins ties; a repeated atom keeps its first record).  Skipped: hydrogens and deuterium; waters (HOH, WAT, DOD)
+    unless ``water``; any element without a radius in ``constants.obstacle_radius`` (metals: coordination is not a clash), named
+    once in a warning (``log``, default ``warnings.warn``).
+
+    Returns ``dict(xyz [M, 3] float32, radius [M] float32, element, resname, chain, resseq (lists of M), lines)``.  ``lines`` is
+    for writing the groups back as deposited: the original line, without the newline, of every record of the groups read here
+    (waters only with ``water``), in file order -- their hydrogens, radius-less atoms and every alternate location included, so
+    that a written structure carries the whole ligand, not only the atoms that act as obstacles."""
+    kept: Dict[tuple, list] = {}           # (chain, resseq, icode, resname, atom name) -> [occ, has altloc, line, element, xyz]
+    order: List[tuple] = []
+    skipped = set()
+    lines: List[str] = []
+    for raw in _raw_lines(Path(pdb_file)):
+        het = raw.startswith("HETATM")
+        if not het and not raw.startswith("ATOM"):
+            continue
+        line = raw.rstrip("\r\n")
+        ln = line.ljust(80)
+        resname = ln[17:20].strip()
+        if not het:
+            std = "MET" if (mse_to_met and resname == "MSE") else resname
+            if rc.resname_to_idx.get(std, 20) != 20:
+                continue                                   # a standard residue: the protein dict has it
+        if resname in _WATERS and not water:
+            continue
+        lines.append(line)
+        el = _element(ln)
+        if el in ("H", "D"):
+            continue
+        try:
+            resseq = int(ln[22:26].split()[0])
+            xyz = (float(ln[30:38]), float(ln[38:46]), float(ln[46:54]))
+        except (ValueError, IndexError):
+            continue
+        if el not in rc.obstacle_radius:
+            skipped.add(el or "?")
+            continue
+        try:
+            occ = float(ln[54:60])
+        except ValueError:
+            occ = -1.0
+        altloc = ln[16]
+        key = (ln[21], resseq, ln[26], resname, ln[12:16])
+        slot = kept.get(key)
+        if slot is None:
+            kept[key] = [occ, altloc != " ", line, el, xyz]
+            order.append(key)
+        elif altloc != " " and slot[1] and occ > slot[0]:
+            kept[key] = [occ, True, line, el, xyz]
+    if skipped:
+        msg = ("obstacle_atoms: no van der Waals radius for element(s) " + ", ".join(sorted(skipped)) + " in " + str(pdb_file) +
+               ": those atoms are not obstacles")
+        if log is not None:
+            log(msg)
+        else:
+            import warnings
+            warnings.warn(msg)
+    recs = [kept[k] for k in order]
+    return dict(xyz=np.array([r[4] for r in recs], np.float32).reshape(-1, 3),
+                radius=np.array([rc.obstacle_radius[r[3]] for r in recs], np.float32),
+                element=[r[3] for r in recs], resname=[k[3] for k in order], chain=[k[0] for k in order],
+                resseq=[k[1] for k in order], lines=lines)
+
+
+OBSTACLE_MODES = ("none", "hetero", "hetero+water")
+
+
+def obstacles_for(pdb_file, mode: str, log=print):
+    """The ``--obstacles`` flag of the command lines: None for "none", else ``obstacle_atoms`` (with the waters for "hetero+water")."""
+    if mode not in OBSTACLE_MODES:
+        raise ValueError(f"obstacles must be one of {OBSTACLE_MODES}")
+    if mode == "none":
+        return None
+    o = obstacle_atoms(pdb_file, water=mode == "hetero+water", log=log)
+    log(f"----- {len(o['radius'])} obstacle atoms ({mode}) from {len(o['lines'])} records; the network does not see them -----")
+    return o
+
+
+def insert_obstacle_lines(pdb_text: str, lines: List[str]) -> str:
+    """``to_pdb`` output with the obstacle records' original lines, verbatim, between the protein's last TER and END."""
+    if not lines:
+        return pdb_text
+    out = pdb_text.split("\n")
+    at = max(i for i, ln in enumerate(out) if ln.startswith("TER")) + 1
+    return "\n".join(out[:at] + list(lines) + out[at:])
+
+
 def contains_sidechains(pdb_file) -> bool:
     """eval_diffusion.py:43-50."""
     with open(pdb_file, "r") as fh:

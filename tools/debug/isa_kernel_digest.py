@@ -4,7 +4,8 @@
 Per-kernel digests of a device assembly file written by tools/debug/isa_digest.sh: for every function its demangled name, the
 number of instruction lines and a digest of its instructions and labels (directives and comments dropped, the compilation-unit id
 and the per-file numbering of local labels masked).  With two files (A = the older tree): a kernel of B whose name is one of A's
-with a trailing `, false` template argument appended counts as that kernel (a new defaulted template parameter); which kernels have the same
+with a trailing `, false` template argument appended -- and possibly one more kernel parameter behind the old ones -- counts as that
+kernel (a new template parameter whose `false` instances must be the old kernels); which kernels have the same
 instructions in both, which differ, which exist in one only -- what a pull request that adds template instances quotes to show
 that the existing instances kept theirs (profiles/r17_live_rows.json)."""
 import hashlib
@@ -23,8 +24,10 @@ def kernels(path):
         if name is not None:
             if ln.startswith(".Lfunc_end"):
                 ins = [b for b in body if b.strip() and not b.lstrip().startswith(";") and not (b.startswith("\t") and b.lstrip().startswith("."))]
+                ins = [b.split(";")[0].rstrip() + "\n" for b in ins]          # trailing comments: loop notes padded to the label's width
                 text = re.sub(r"__hip_cuid_[0-9a-f]+", "__hip_cuid_X", "".join(ins))
                 text = re.sub(r"\.LBB\d+_", ".LBB_", text)
+                text = re.sub(r"\bBB\d+_", "BB_", text)          # the same numbering in the comments that trail label lines
                 n_ins = sum(1 for b in ins if b.startswith("\t"))
                 out[name] = (hashlib.sha256(text.encode()).hexdigest()[:16], n_ins)
                 name = None
@@ -52,10 +55,12 @@ def main(argv):
     d = demangle(sorted(set(a) | set(b)))
     a = {d[n]: v for n, v in a.items()}
     b = {d[n]: v for n, v in b.items()}
-    for n in list(b):          # a new defaulted template parameter
+    for n in list(b):          # a new defaulted template parameter, with or without a new last kernel parameter for it
         old = re.sub(r", false>\(", ">(", n, count=1)
-        if n not in a and old in a and old not in b:
-            b[old] = b.pop(n)
+        for cand in (old, re.sub(r", [\w:]+\)$", ")", old)):
+            if n not in a and cand in a and cand not in b:
+                b[cand] = b.pop(n)
+                break
     d = {n: n for n in set(a) | set(b)}
     same = [n for n in a if n in b and a[n] == b[n]]
     diff = [n for n in a if n in b and a[n] != b[n]]
