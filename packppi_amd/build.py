@@ -11,8 +11,15 @@ LIB = os.path.join(CSRC, "libpackppi_hip.so")
 # The edge kernels exist twice: pp_edge_f16.hip (default: split-f16 MFMA, fp32-equivalent accuracy, one workgroup per CU)
 # and pp_edge.hip (PACKPPI_EDGE=f32: exact-fp32 MFMA, three workgroups per CU).  Same launchers, same results to ~1e-6.
 EDGE_F16 = os.environ.get("PACKPPI_EDGE", "f16") != "f32"
-SOURCES = ["pp_api.hip", "pp_prepare.hip", "pp_node.hip", "pp_edge_f16.hip" if EDGE_F16 else "pp_edge.hip", "pp_clash.hip",
-           "pp_affinity.hip", "pp_dsm.hip", "pp_ensemble.hip", "pp_shell.hip", "pp_recombine.hip"]
+
+
+def sources_for(edge_f16):
+    """The translation units of a library, in link order, by edge-kernel variant: THE list (tools/debug/isa_digest.sh reads it too)."""
+    return ["pp_api.hip", "pp_prepare.hip", "pp_node.hip", "pp_edge_f16.hip" if edge_f16 else "pp_edge.hip", "pp_clash.hip",
+            "pp_affinity.hip", "pp_dsm.hip", "pp_ensemble.hip", "pp_shell.hip", "pp_recombine.hip"]
+
+
+SOURCES = sources_for(EDGE_F16)
 # The flags of the PRODUCT libraries are fixed here: PACKPPI_CFLAGS / -D arguments only reach TAGGED variant libraries
 # (python -m packppi_amd.build --tag NAME -DPP_LAB -DPP_X_...), which lib.load() refuses unless PACKPPI_ALLOW_LAB_LIBRARY=1.
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-variable",
@@ -128,7 +135,7 @@ def build_other_variant(verbose=True):
     The GPU tests run the end-to-end parity cases on it as well (PACKPPI_LIB)."""
     out = other_variant_path()
     tag = "f32" if EDGE_F16 else "f16"
-    sources = ["pp_api.hip", "pp_prepare.hip", "pp_node.hip", "pp_edge.hip" if EDGE_F16 else "pp_edge_f16.hip", "pp_clash.hip", "pp_affinity.hip", "pp_dsm.hip", "pp_ensemble.hip", "pp_shell.hip", "pp_recombine.hip"]
+    sources = sources_for(not EDGE_F16)
     flags = [f for f in FLAGS if f != "-DPP_EDGE_F16"] + ([] if EDGE_F16 else ["-DPP_EDGE_F16"])
     if not needs_build(out, flags, sources):
         return out
@@ -160,8 +167,7 @@ def build_diag_variant(verbose=True):
 
 def product_flag_stamps():
     """{flags half of pp_build_id(): library name} of the four libraries this file builds without laboratory flags."""
-    f32_sources = ["pp_api.hip", "pp_prepare.hip", "pp_node.hip", "pp_edge.hip", "pp_clash.hip", "pp_affinity.hip", "pp_dsm.hip", "pp_ensemble.hip", "pp_shell.hip", "pp_recombine.hip"]
-    f16_sources = ["pp_api.hip", "pp_prepare.hip", "pp_node.hip", "pp_edge_f16.hip", "pp_clash.hip", "pp_affinity.hip", "pp_dsm.hip", "pp_ensemble.hip", "pp_shell.hip", "pp_recombine.hip"]
+    f32_sources, f16_sources = sources_for(False), sources_for(True)
     base = [f for f in FLAGS if f != "-DPP_EDGE_F16"]
     return {flags_hash(base + ["-DPP_EDGE_F16"], f16_sources): "default (split-f16)",
             flags_hash(base, f32_sources): "f32",
@@ -171,6 +177,10 @@ def product_flag_stamps():
 
 if __name__ == "__main__":
     # python -m packppi_amd.build [--force] [--tag NAME -DFLAG ...]   (a tagged build is a variant library for experiments)
+    # python packppi_amd/build.py --sources f16|f32   prints that variant's translation units and builds nothing
     argv = sys.argv[1:]
+    if "--sources" in argv:
+        print(" ".join(sources_for(argv[argv.index("--sources") + 1] != "f32")))
+        sys.exit(0)
     tag = argv[argv.index("--tag") + 1] if "--tag" in argv else ""
     build_library(force="--force" in argv, extra_flags=[a for a in argv if a.startswith("-D")], tag=tag)

@@ -13,12 +13,6 @@
 
 #include "pp_internal.h"
 
-#define FAIL(code, msg)          \
-    do {                         \
-        pp_set_error(msg);       \
-        return code;             \
-    } while (0)
-
 // torch.max semantics: a NaN wins and stays
 __device__ __forceinline__ float max_nan(float m, float v) { return (v != v || v > m) ? v : m; }
 

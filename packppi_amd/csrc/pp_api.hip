@@ -31,12 +31,6 @@ extern "C" int pp_version(void) { return 101; }
 static const char g_build_id[] = "PP_BUILD_ID=" PP_BUILD_ID;
 extern "C" const char *pp_build_id(void) { return g_build_id + 12; }
 
-#define FAIL(code, msg)      \
-    do {                     \
-        pp_set_error(msg);   \
-        return code;         \
-    } while (0)
-
 template <typename T>
 static pp_status upload(T **dst, const T *src, size_t n) {
     PP_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(dst), n * sizeof(T)));

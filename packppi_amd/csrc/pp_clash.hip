@@ -9,7 +9,9 @@
 // own atoms (a gather formulation, so no atomics and a run-to-run reproducible sum) and folds it into
 // dLoss/dchi with d p/d chi_k = axis_k x (p - origin_k) for atoms downstream of chi_k.
 #include "pp_internal.h"
+#include "pp_clash_geom.h"      // cl_extent, cl_reach, CL_RA_MAX: what the static candidate lists rest on
 #include <math.h>
+#include <type_traits>
 
 struct M3 { float m[9]; };
 struct Rig { M3 R; float t[3]; };
@@ -297,7 +299,6 @@ struct ClashObst {
     const int32_t *cand_cnt;      // [N] their number, -1: scan
 };
 #define CL_OB_Q (CL_MAXC / 4)     // obstacle indices one stripe holds in LDS before the wave works them off
-#define CL_RA_MAX 1.8f            // the largest between-residue radius of a protein atom (S): reach = 3.6 - tol is twice this
 template <bool CAND, bool FUSE, bool OBST>
 __global__ void __launch_bounds__(64 * CL_WAVES)
 k_clash(int N, const int2 *__restrict__ seg, const float *__restrict__ xyz, const float4 *__restrict__ rec, const float *__restrict__ exists,
@@ -332,7 +333,7 @@ k_clash(int N, const int2 *__restrict__ seg, const float *__restrict__ xyz, cons
     const float4 cme = rec[(size_t)i * 16 + 14];          // bounding sphere (centroid, radius)
     const float cai[3] = {cme.x, cme.y, cme.z};
     const float radi = cme.w;
-    const float reach = 3.6f - tol;                 // largest r_a + r_b - tol (S-S)
+    const float reach = cl_reach(tol);              // largest r_a + r_b - tol (S-S)
 
     float loss_a = 0.f, ga[3] = {0.f, 0.f, 0.f};
     int *list = s_list[wave];
@@ -386,6 +387,7 @@ k_clash(int N, const int2 *__restrict__ seg, const float *__restrict__ xyz, cons
         __builtin_amdgcn_wave_barrier();
         for (int c = slot; c < cnt; c += 4) {
             const int jg = list[c];
+            // (this atom-pair loop has a copy without the gradient in k_rc_propose, pp_recombine.hip: change both or neither)
             // all of the partner's records first, unconditionally: inside the branches below the compiler may not hoist them,
             // and fourteen dependent round trips per candidate were 13 of this kernel's 20 us at T1124 (fetching the next
             // candidate's records one iteration ahead on top of this gains nothing)
@@ -434,7 +436,7 @@ k_clash(int N, const int2 *__restrict__ seg, const float *__restrict__ xyz, cons
         const int32_t *oc = ost ? O.cand + (size_t)i * PP_OB_CAP : nullptr;
         const int nsl = ost ? n_ost : orng.y;
         const int ostep = ost ? 64 : 64 * CL_WAVES;
-        const float oreach = CL_RA_MAX - tol;
+        const float oreach = cl_obst_reach(tol);
         const bool act = own && a >= 4 && ea != 0.f;
         int ocnt[4] = {0, 0, 0, 0};
         for (int c0 = ost ? 0 : 64 * wave; c0 < nsl; c0 += ostep) {
@@ -461,6 +463,7 @@ k_clash(int N, const int2 *__restrict__ seg, const float *__restrict__ xyz, cons
             const int most = max(max(ocnt[0], ocnt[1]), max(ocnt[2], ocnt[3]));
             if (most + 64 <= CL_OB_Q && c0 + ostep < nsl) continue;
             __builtin_amdgcn_wave_barrier();
+            // (this obstacle loop has a copy without the gradient in k_rc_propose, pp_recombine.hip: change both or neither)
             const int mycnt = slot == 0 ? ocnt[0] : (slot == 1 ? ocnt[1] : (slot == 2 ? ocnt[2] : ocnt[3]));
             for (int c = 0; c < mycnt; c++) {
                 const float4 q = O.atoms[list[slot * CL_OB_Q + c]];
@@ -500,7 +503,7 @@ k_clash(int N, const int2 *__restrict__ seg, const float *__restrict__ xyz, cons
     } else {
         loss_a = 0.f; ga[0] = ga[1] = ga[2] = 0.f;
     }
-    // within-residue bounds: stripes of partner atoms b = slot, slot+4, ...
+    // within-residue bounds: stripes of partner atoms b = slot, slot+4, ...  (copy without the gradient: k_rc_propose, pp_recombine.hip)
     if (own && ea != 0.f) {
         for (int bb = slot; bb < 14; bb += 4) {
             if (bb == a || (a < 4 && bb < 4)) continue;
@@ -592,11 +595,10 @@ k_clash(int N, const int2 *__restrict__ seg, const float *__restrict__ xyz, cons
 // static clash-partner candidates of the proximal loop: once per pp_proximal
 // ---------------------------------------------------------------------------------------------
 // The Adam loop moves side chains, never the backbone.  An atom of residue i can only ever overlap an atom of residue j if
-//   |CA_i - CA_j| < e_i + e_j + (3.6 - tol)      e = how far an atom of the residue can be from its CA for ANY chi:
-// the side-chain bound of the residue type (plan->side_extent) or the actual distance of its N / C / O, whichever is larger.  Every
-// other pair has a zero hinge at every step, so k_clash<true> need not look at it: instead of scanning the L partners of the
-// complex at every step (O(L^2) sphere tests per launch: 98 % of them culled at T1124, 99 % at S1500) a wave reads its few dozen
-// candidates.  Same workgroup shape and wave / window assignment as the scan of k_clash: wave w of residue i's workgroup gets the
+//   |CA_i - CA_j| < e_i + e_j + cl_reach(tol)      e = cl_extent: how far an atom of the residue can be from its CA for ANY chi
+// (pp_clash_geom.h, with the argument).  Every other pair has a zero hinge at every step, so k_clash<true> need not look at it:
+// instead of scanning the L partners of the complex at every step (O(L^2) sphere tests per launch: 98 % of them culled at T1124,
+// 99 % at S1500) a wave reads its few dozen candidates.  Same workgroup shape and wave / window assignment as the scan of k_clash: wave w of residue i's workgroup gets the
 // partners of windows 64 w + 256 m, ascending; more than PP_CL_CAP of them and the wave keeps the full scan (count -1).
 __global__ void __launch_bounds__(64 * CL_WAVES)
 k_clash_cand(int N, const int2 *__restrict__ seg, const float *__restrict__ X, const float *__restrict__ amask, const int64_t *__restrict__ rtype,
@@ -606,23 +608,10 @@ k_clash_cand(int N, const int2 *__restrict__ seg, const float *__restrict__ X, c
     const int i = blockIdx.x;
     if (i >= N) return;
     const int row0 = seg[i].x, L = seg[i].y;
-    auto extent = [&](int n, float (&ca)[3]) {
-        const float *x = X + (size_t)n * 42;
-        ca[0] = x[3]; ca[1] = x[4]; ca[2] = x[5];
-        float e = side_extent[(int)rtype[n]];
-        const float *m = amask + (size_t)n * 14;
-#pragma unroll
-        for (int a = 0; a < 4; a++) {
-            if (a == 1 || m[a] == 0.f) continue;
-            const float dx = x[3 * a] - ca[0], dy = x[3 * a + 1] - ca[1], dz = x[3 * a + 2] - ca[2];
-            e = fmaxf(e, sqrtf(dx * dx + dy * dy + dz * dz) * 1.0001f + 1e-3f);
-        }
-        return e;
-    };
     float cai[3];
-    const float ei = extent(i, cai);
+    const float ei = cl_extent(X, amask, rtype, side_extent, i, cai);
     const int ri = (int)rindex[i];
-    const float reach = 3.6f - tol;
+    const float reach = cl_reach(tol);
     int32_t *out = cand + ((size_t)i * CL_WAVES + wave) * PP_CL_CAP;
     int cnt = 0;
     for (int jscan = 64 * wave; jscan < L; jscan += 64 * CL_WAVES) {
@@ -632,7 +621,7 @@ k_clash_cand(int N, const int2 *__restrict__ seg, const float *__restrict__ X, c
             const int jg = row0 + jl;
             if (jg != i && (int)rindex[jg] != ri) {
                 float caj[3];
-                const float ej = extent(jg, caj);
+                const float ej = cl_extent(X, amask, rtype, side_extent, jg, caj);
                 const float dx = caj[0] - cai[0], dy = caj[1] - cai[1], dz = caj[2] - cai[2];
                 const float lim = ei + ej + reach;
                 keep = lim > 0.f && dx * dx + dy * dy + dz * dz < lim * lim;
@@ -647,7 +636,7 @@ k_clash_cand(int N, const int2 *__restrict__ seg, const float *__restrict__ X, c
 }
 
 // Static obstacle candidates of the proximal loop, once per pp_proximal* beside k_clash_cand: obstacle o of row i's segment is kept iff
-//   |CA_i - q_o| < e_i + r_o + (1.8 - tol)        (e_i as above; 1.8 = the largest radius of a protein atom),
+//   |CA_i - q_o| < e_i + r_o + cl_obst_reach(tol)        (e_i = cl_extent; pp_clash_geom.h),
 // outside of which its hinge is zero on every atom of the residue at every chi.  One wave per row walks the segment's range in order,
 // so the list is ascending; more than PP_OB_CAP of them and the row keeps the scan (count -1).  Obstacles with r_o <= 0 are never kept.
 __global__ void __launch_bounds__(256)
@@ -657,18 +646,10 @@ k_obst_cand(int N, const float *__restrict__ X, const float *__restrict__ amask,
     const int lane = threadIdx.x & 63;
     const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (i >= N) return;
-    const float *x = X + (size_t)i * 42;
-    const float ca[3] = {x[3], x[4], x[5]};
-    float e = side_extent[(int)rtype[i]];
-    const float *m = amask + (size_t)i * 14;
-#pragma unroll
-    for (int a = 0; a < 4; a++) {
-        if (a == 1 || m[a] == 0.f) continue;
-        const float dx = x[3 * a] - ca[0], dy = x[3 * a + 1] - ca[1], dz = x[3 * a + 2] - ca[2];
-        e = fmaxf(e, sqrtf(dx * dx + dy * dy + dz * dz) * 1.0001f + 1e-3f);
-    }
+    float ca[3];
+    const float e = cl_extent(X, amask, rtype, side_extent, i, ca);
     const int2 rng = orow[i];
-    const float reach = CL_RA_MAX - tol;
+    const float reach = cl_obst_reach(tol);
     int32_t *out = cand + (size_t)i * PP_OB_CAP;
     int cnt = 0;
     for (int c0 = 0; c0 < rng.y; c0 += 64) {
@@ -822,32 +803,37 @@ static ClashObst clash_obst(const pp_ctx *c, bool cands) {
     return O;
 }
 
-pp_status pp_launch_clash(pp_ctx *c, const float *xyz, float *per_res, float *dchi, hipStream_t s, bool use_candidates) {
+// THE k_clash launch: (cands, fuse, obst) -> the instance, the argument list written once.  cands: the static lists of the context
+// (k_clash_cand); F is read by the FUSE instances only, O by the OBST ones; inv_ntot by the instances without FUSE.
+static void launch_k_clash(pp_ctx *c, bool cands, bool fuse, bool obst, const float *xyz, const float *rec, const float *axes,
+                           float inv_ntot, float *per_res, float *dchi, const ClashFuse &F, const ClashObst &O, hipStream_t s) {
     const pp_plan *p = c->plan;
+    auto go = [&](auto cand_c, auto fuse_c, auto obst_c) {
+        PP_LAUNCH(c, (k_clash<decltype(cand_c)::value, decltype(fuse_c)::value, decltype(obst_c)::value>), dim3(c->N),
+                  dim3(64 * CL_WAVES), 0, s, c->N, c->seg, xyz, reinterpret_cast<const float4 *>(rec), c->b.atom_mask, p->bounds_lower,
+                  p->bounds_upper, p->atom14_to_group, axes, p->clash_tol, inv_ntot, per_res, dchi, cands ? c->cand : nullptr,
+                  cands ? c->cand_cnt : nullptr, F, O);
+    };
+    const std::true_type y;
+    const std::false_type n;
+    switch (4 * cands + 2 * fuse + obst) {
+        case 0: go(n, n, n); break;
+        case 1: go(n, n, y); break;
+        case 2: go(n, y, n); break;
+        case 3: go(n, y, y); break;
+        case 4: go(y, n, n); break;
+        case 5: go(y, n, y); break;
+        case 6: go(y, y, n); break;
+        default: go(y, y, y); break;
+    }
+}
+
+pp_status pp_launch_clash(pp_ctx *c, const float *xyz, float *per_res, float *dchi, hipStream_t s, bool use_candidates) {
     const bool ca = use_candidates && c->cand;
-    // the instance is chosen here, by whether the context holds obstacles: the OBST = false kernels carry no test for them
-    if (c->obst_M > 0) {
-        const ClashObst O = clash_obst(c, ca);
-        if (ca)
-            PP_LAUNCH(c, (k_clash<true, false, true>), dim3(c->N), dim3(64 * CL_WAVES), 0, s, c->N, c->seg, xyz,
-                      reinterpret_cast<const float4 *>(c->rec), c->b.atom_mask,
-                      p->bounds_lower, p->bounds_upper, p->atom14_to_group, c->axes, p->clash_tol,
-                      1.0f / (float)c->N, per_res, dchi, c->cand, c->cand_cnt, ClashFuse{}, O);
-        else
-            PP_LAUNCH(c, (k_clash<false, false, true>), dim3(c->N), dim3(64 * CL_WAVES), 0, s, c->N, c->seg, xyz,
-                      reinterpret_cast<const float4 *>(c->rec), c->b.atom_mask,
-                      p->bounds_lower, p->bounds_upper, p->atom14_to_group, c->axes, p->clash_tol,
-                      1.0f / (float)c->N, per_res, dchi, nullptr, nullptr, ClashFuse{}, O);
-    } else if (ca)
-        PP_LAUNCH(c, (k_clash<true, false, false>), dim3(c->N), dim3(64 * CL_WAVES), 0, s, c->N, c->seg, xyz,
-                  reinterpret_cast<const float4 *>(c->rec), c->b.atom_mask,
-                  p->bounds_lower, p->bounds_upper, p->atom14_to_group, c->axes, p->clash_tol,
-                  1.0f / (float)c->N, per_res, dchi, c->cand, c->cand_cnt, ClashFuse{}, ClashObst{});
-    else
-        PP_LAUNCH(c, (k_clash<false, false, false>), dim3(c->N), dim3(64 * CL_WAVES), 0, s, c->N, c->seg, xyz,
-                  reinterpret_cast<const float4 *>(c->rec), c->b.atom_mask,
-                  p->bounds_lower, p->bounds_upper, p->atom14_to_group, c->axes, p->clash_tol,
-                  1.0f / (float)c->N, per_res, dchi, nullptr, nullptr, ClashFuse{}, ClashObst{});
+    // the instance is chosen by whether the context holds obstacles: the OBST = false kernels carry no test for them
+    const bool obst = c->obst_M > 0;
+    launch_k_clash(c, ca, false, obst, xyz, c->rec, c->axes, 1.0f / (float)c->N, per_res, dchi, ClashFuse{},
+                   obst ? clash_obst(c, ca) : ClashObst{}, s);
     PP_HIP_CHECK(hipGetLastError());
     return PP_OK;
 }
@@ -886,39 +872,26 @@ static pp_status prox_loop(pp_ctx *c, const float *chi, float lamda, int nsteps,
     // (records and axes at the start angles are in c->rec / c->axes already: the atom14 launch above ran at `chi`, which is what
     // k_prox_init has just copied into xeff, and the clash launch between them writes neither)
     float *rec_in = c->rec, *rec_out = c->rec2, *axes_in = c->axes, *axes_out = c->axes2;
+    // what every step of the loop passes; t, traj, step_size, bc2s and the two ping-pong buffers are set per step below
+    ClashFuse F;
+    F.X = c->b.X; F.BB_D = c->b.BB_D; F.default_frames = p->default_frames; F.amask14 = p->atom14_mask; F.lit = p->lit_positions;
+    F.atom_exists = c->b.atom_mask; F.between_radius = p->between_radius; F.rindex = c->b.residue_index;
+    F.xyz = c->xyz; F.brad = c->brad;
+    ProxUpd &U = F.U;
+    U.nblocks = 0;
+    U.lamda = lamda;
+    U.chi0 = chi; U.z = c->pz; U.inv_row = c->prox_inv; U.mask = c->pmask;
+    U.x = c->px; U.m = c->pm; U.v = c->pv; U.xeff = c->pxeff; U.last = chi_last;
+    U.loss_part = c->prox_part;
     const float inv_ntot_unused = 0.f;          // k_clash's scalar 1 / N is pp_clash's: the fused instances read U.inv_row
     for (int t = 0; t < nsteps; t++) {
         const double bc1 = 1.0 - pow(0.9, (double)(t + 1)), bc2 = 1.0 - pow(0.999, (double)(t + 1));
-        ClashFuse F;
-        F.X = c->b.X; F.BB_D = c->b.BB_D; F.default_frames = p->default_frames; F.amask14 = p->atom14_mask; F.lit = p->lit_positions;
-        F.atom_exists = c->b.atom_mask; F.between_radius = p->between_radius; F.rindex = c->b.residue_index;
-        F.xyz = c->xyz; F.axes_out = axes_out; F.brad = c->brad; F.rec_out = reinterpret_cast<float4 *>(rec_out);
-        ProxUpd &U = F.U;
-        U.nblocks = 0;
-        U.lamda = lamda; U.step_size = (float)(1e-2 / bc1); U.bc2s = (float)sqrt(bc2);
-        U.chi0 = chi; U.z = c->pz; U.inv_row = c->prox_inv; U.mask = c->pmask;
-        U.x = c->px; U.m = c->pm; U.v = c->pv; U.xeff = c->pxeff; U.last = chi_last;
-        U.loss_part = c->prox_part;
+        U.step_size = (float)(1e-2 / bc1); U.bc2s = (float)sqrt(bc2);
         U.t = t % PP_PROX_CHUNK;
         U.traj = traj ? traj + (size_t)(t - U.t) * c->N * 4 : nullptr;     // U.t indexes within the chunk
+        F.axes_out = axes_out; F.rec_out = reinterpret_cast<float4 *>(rec_out);
         c->prof_armed = c->prof_which == 3;          // pp_profile_kernel(3): the fused clash + Adam step + reconstruction
-        const float4 *rin = reinterpret_cast<const float4 *>(rec_in);
-        if (obst && cands)
-            PP_LAUNCH(c, (k_clash<true, true, true>), dim3(c->N), dim3(64 * CL_WAVES), 0, s, c->N, c->seg, c->xyz,
-                      rin, c->b.atom_mask, p->bounds_lower, p->bounds_upper, p->atom14_to_group,
-                      axes_in, p->clash_tol, inv_ntot_unused, c->per_res, c->dchi, c->cand, c->cand_cnt, F, O);
-        else if (obst)
-            PP_LAUNCH(c, (k_clash<false, true, true>), dim3(c->N), dim3(64 * CL_WAVES), 0, s, c->N, c->seg, c->xyz,
-                      rin, c->b.atom_mask, p->bounds_lower, p->bounds_upper, p->atom14_to_group,
-                      axes_in, p->clash_tol, inv_ntot_unused, c->per_res, c->dchi, nullptr, nullptr, F, O);
-        else if (cands)
-            PP_LAUNCH(c, (k_clash<true, true, false>), dim3(c->N), dim3(64 * CL_WAVES), 0, s, c->N, c->seg, c->xyz,
-                      rin, c->b.atom_mask, p->bounds_lower, p->bounds_upper, p->atom14_to_group,
-                      axes_in, p->clash_tol, inv_ntot_unused, c->per_res, c->dchi, c->cand, c->cand_cnt, F, O);
-        else
-            PP_LAUNCH(c, (k_clash<false, true, false>), dim3(c->N), dim3(64 * CL_WAVES), 0, s, c->N, c->seg, c->xyz,
-                      rin, c->b.atom_mask, p->bounds_lower, p->bounds_upper, p->atom14_to_group,
-                      axes_in, p->clash_tol, inv_ntot_unused, c->per_res, c->dchi, nullptr, nullptr, F, O);
+        launch_k_clash(c, cands, true, obst, c->xyz, rec_in, axes_in, inv_ntot_unused, c->per_res, c->dchi, F, O, s);
         c->prof_armed = false;
         std::swap(rec_in, rec_out);
         std::swap(axes_in, axes_out);

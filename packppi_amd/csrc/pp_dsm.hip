@@ -19,12 +19,6 @@
 
 #include "pp_internal.h"
 
-#define FAIL(code, msg)          \
-    do {                         \
-        pp_set_error(msg);       \
-        return code;             \
-    } while (0)
-
 #define SO2_N 5000                 // X_N = SIGMA_N: 5001 grid points each
 #define SO2_TERMS 100              // series terms -100 .. 100 (schedule.py:48-49)
 #define PP_MAX_DEVICES 64

@@ -27,33 +27,13 @@
 //
 // A TABLE THAT BREAKS THE CONTRACT.  Rows come from pp_seg_rows, which clamps into the N rows of the batch.  A group is CONSISTENT
 // when its D clamped segments have the same length len >= 1 and its consensus rows base .. base + len - 1 (base = first row / D) lie
-// inside the N / D consensus rows.  An inconsistent group reads nothing outside the batch and writes nothing outside the outputs:
+// inside the N / D consensus rows (pp_group_rows, pp_segments.h: the one copy of this rule).  An inconsistent group reads nothing outside the batch and writes nothing outside the outputs:
 // its best is -1, the dev of its segments NaN, its chi_best rows are not written, and a consensus row that maps into it gets 0, 0.
 #include <cmath>
 
 #include "pp_internal.h"
 
-#define FAIL(code, msg)          \
-    do {                         \
-        pp_set_error(msg);       \
-        return code;             \
-    } while (0)
-
 #define ENS_PI 3.14159265358979323846
-
-// First consensus row and length of group g; false for an inconsistent group (above).  Reads seg_off[g * D .. g * D + D] only.
-__device__ __forceinline__ bool ens_group(const int32_t *__restrict__ seg_off, int g, int D, int N, int &base, int &len) {
-    int a, b;
-    pp_seg_rows(seg_off, g * D, N, a, b);
-    base = a / D;
-    len = b - a;
-    bool ok = len >= 1 && base + len <= N / D;
-    for (int d = 1; d < D; d++) {
-        pp_seg_rows(seg_off, g * D + d, N, a, b);
-        ok = ok && (b - a == len);
-    }
-    return ok;
-}
 
 __global__ void __launch_bounds__(256)
 k_ens_consensus(int N, int G, int D, const int32_t *__restrict__ seg_off, const float *__restrict__ chi,
@@ -63,28 +43,18 @@ k_ens_consensus(int N, int G, int D, const int32_t *__restrict__ seg_off, const 
     const int n_cons = N / D;
     for (int e = blockIdx.x * 256 + threadIdx.x; e < 4 * n_cons; e += gridDim.x * 256) {
         const int crow = e >> 2, c = e & 3;
-        // the group of this consensus row: the last g whose first consensus row is <= crow
-        int lo = 0, hi = G - 1;
-        while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            int a, b;
-            pp_seg_rows(seg_off, mid * D, N, a, b);
-            if (a / D <= crow) lo = mid; else hi = mid - 1;
-        }
-        int base, len;
-        const bool ok = ens_group(seg_off, lo, D, N, base, len);
+        const int g = pp_group_of_cons_row(seg_off, G, D, N, crow);
+        int base, len, row0;
+        const bool ok = pp_group_rows(seg_off, g, D, N, base, len, row0);
         const int r = crow - base;
         float mu = 0.f, R = 0.f;
         if (ok && r >= 0 && r < len) {
-            int a, b;
-            pp_seg_rows(seg_off, lo * D, N, a, b);
-            const int e0 = 4 * (a + r) + c;
+            const int e0 = 4 * (row0 + r) + c;
             if (sc_mask[e0] != 0.f) {
                 const double p = m1pi[e0] ? 2.0 : 1.0;
                 double S = 0.0, C = 0.0;
                 for (int d = 0; d < D; d++) {
-                    pp_seg_rows(seg_off, lo * D + d, N, a, b);
-                    const double x = p * (double)chi[4 * (a + r) + c];
+                    const double x = p * (double)chi[4 * (pp_decoy_row0(seg_off, g, D, N, d) + r) + c];
                     S += sin(x);
                     C += cos(x);
                 }
@@ -104,9 +74,9 @@ k_ens_per_decoy(int N, int D, const int32_t *__restrict__ seg_off, const float *
 #pragma clang fp contract(off)
     __shared__ double red[3][256];
     const int s = blockIdx.x, tid = threadIdx.x;
-    int a, b, base, len;
+    int a, b, base, len, row0;
     pp_seg_rows(seg_off, s, N, a, b);
-    const bool ok = ens_group(seg_off, s / D, D, N, base, len);
+    const bool ok = pp_group_rows(seg_off, s / D, D, N, base, len, row0);
     double sq = 0.0, sm = 0.0, sc = 0.0;
     if (ok) {
         for (int e = 4 * a + tid; e < 4 * b; e += 256) {
@@ -145,8 +115,8 @@ k_ens_select(int N, int D, int select, const int32_t *__restrict__ seg_off, cons
              float *__restrict__ chi_best) {
     __shared__ int pick;
     const int g = blockIdx.x, tid = threadIdx.x;
-    int base, len;
-    const bool ok = ens_group(seg_off, g, D, N, base, len);
+    int base, len, row0;
+    const bool ok = pp_group_rows(seg_off, g, D, N, base, len, row0);
     if (tid == 0) {
         int k = -1;
         if (ok) {
@@ -163,9 +133,17 @@ k_ens_select(int N, int D, int select, const int32_t *__restrict__ seg_off, cons
     }
     __syncthreads();
     if (!chi_best || pick < 0) return;
-    int a, b;
-    pp_seg_rows(seg_off, g * D + pick, N, a, b);
+    const int a = pp_decoy_row0(seg_off, g, D, N, pick);
     for (int e = tid; e < 4 * len; e += 256) chi_best[4 * base + e] = chi[4 * a + e];
+}
+
+pp_status pp_check_decoy_groups(const pp_ctx *c, int n_decoys, const char *who) {
+    if (!c->packed && c->B != 1)
+        FAIL(PP_ERR_INVALID, std::string(who) + ": needs a context from pp_complex_prepare_packed (or a B = 1 one), not a padded B > 1 batch");
+    if (c->B % n_decoys != 0 || c->N % n_decoys != 0)
+        FAIL(PP_ERR_INVALID, std::string(who) + ": the context's " + std::to_string(c->B) + " segments / " + std::to_string(c->N) +
+                                 " rows are not groups of " + std::to_string(n_decoys) + " decoys");
+    return PP_OK;
 }
 
 extern "C" pp_status pp_ensemble_reduce(pp_ctx *c, const float *chi, int n_decoys, const float *per_res, int select, float *mean,
@@ -176,11 +154,7 @@ extern "C" pp_status pp_ensemble_reduce(pp_ctx *c, const float *chi, int n_decoy
     if (n_decoys < 1) FAIL(PP_ERR_INVALID, "pp_ensemble_reduce: n_decoys must be at least 1");
     if (select < 0 || select > 2) FAIL(PP_ERR_INVALID, "pp_ensemble_reduce: select must be 0 (none), 1 (clash) or 2 (medoid)");
     if (select == 1 && !per_res) FAIL(PP_ERR_INVALID, "pp_ensemble_reduce: select = 1 (clash) needs per_res");
-    if (!c->packed && c->B != 1)
-        FAIL(PP_ERR_INVALID, "pp_ensemble_reduce: needs a context from pp_complex_prepare_packed (or a B = 1 one), not a padded B > 1 batch");
-    if (c->B % n_decoys != 0 || c->N % n_decoys != 0)
-        FAIL(PP_ERR_INVALID, "pp_ensemble_reduce: the context's " + std::to_string(c->B) + " segments / " + std::to_string(c->N) +
-                                 " rows are not groups of " + std::to_string(n_decoys) + " decoys");
+    if (pp_status gs = pp_check_decoy_groups(c, n_decoys, "pp_ensemble_reduce"); gs != PP_OK) return gs;
     if (!c->b.SC_D_mask || !c->b.chi_1pi_periodic_mask)
         FAIL(PP_ERR_INVALID, "pp_ensemble_reduce: the batch of this ctx has no SC_D_mask / chi_1pi_periodic_mask");
     PP_HIP_CHECK(hipSetDevice(c->plan->device));

@@ -50,7 +50,7 @@
 
 #include "pp_weights.h"      // LayerOff / WeightOff / pp_weight_offsets(): offsets into the concatenated weight buffer
 #include "pp_rng.h"          // Philox4x32-10 and the normal transform of the seeded sampling noise (counter layout there)
-#include "pp_segments.h"     // pp_seg_of_row / pp_seg_rows: the arithmetic of the context's segment table (pp_ctx::seg_off)
+#include "pp_segments.h"     // pp_seg_of_row / pp_seg_rows / pp_group_rows: the arithmetic of the context's segment table (pp_ctx::seg_off)
 
 // Transposed ([in][out]) copies used by the node-level (VALU) kernels, per layer.
 struct LayerT {
@@ -222,6 +222,15 @@ void pp_set_error(const std::string &msg);
             return PP_ERR_HIP;                                                               \
         }                                                                                    \
     } while (0)
+// refuse a call: leave the message for pp_last_error, return the status
+#define FAIL(code, msg)          \
+    do {                         \
+        pp_set_error(msg);       \
+        return code;             \
+    } while (0)
+// what the ensemble calls (`who`: pp_ensemble_reduce, pp_ensemble_recombine) ask of the context: packed or B = 1, and its segments
+// and rows groups of n_decoys (pp_ensemble.hip)
+pp_status pp_check_decoy_groups(const pp_ctx *c, int n_decoys, const char *who);
 
 // ---- f16 operand range check (-DPP_CHECK_RANGE: the libpackppi_hip.chk.so build; packppi_amd/rangecheck.py) -----------------
 // The split-f16 kernels saturate hidden activations at the f16 maximum (65504) and assume every other operand is far below it.

@@ -13,8 +13,8 @@
 // with k_clash's masks and exclusions, in fp32.  E_r(d | s) = U(r, d) + sum_{r'} W(r, d; r', s_r'): moving row r alone from s_r
 // to d changes F by E_r(d | s) - E_r(s_r | s).
 //
-// PARTNERS.  P(r) = the rows r' != r of the group with another residue_index and |CA_r - CA_r'| < e_r + e_r' + (3.6 - tol), the
-// predicate of k_clash_cand: symmetric, a function of the backbone and the types only, and a superset of every pair whose W can
+// PARTNERS.  P(r) = the rows r' != r of the group with another residue_index and |CA_r - CA_r'| < e_r + e_r' + cl_reach(tol), e =
+// cl_extent (pp_clash_geom.h): symmetric, a function of the backbone and the types only, and a superset of every pair whose W can
 // be non-zero at any angles.  k_rc_setup lists them per consensus row, ascending, up to RC_LCAP; a row with more scans the rows of
 // its group with the same predicate, in the same order, wherever the list would be read: same partners, same order, same bits.
 //
@@ -32,12 +32,7 @@
 // A group without a positive gain is converged: its later launches return at once.  Everything that crosses workgroups (s, prop,
 // gain, the counters) crosses a kernel boundary; the only atomics are integer counters.  No float atomics: bit-reproducible.
 #include "pp_internal.h"
-
-#define FAIL(code, msg)          \
-    do {                         \
-        pp_set_error(msg);       \
-        return code;             \
-    } while (0)
+#include "pp_clash_geom.h"      // cl_extent, cl_reach: the bound the static partner lists rest on
 
 #define RC_LCAP (2 * PP_CL_CAP)      // static partners listed per consensus row (more: the row scans its group instead)
 #define RC_WCAP 256                  // partners one wave holds in LDS before it works them off (>= RC_LCAP, a multiple of 64)
@@ -54,7 +49,7 @@ struct RcArgs {
     // obstacle term of row r at decoy d's angles, so F(s) stays the sum of pp_clash's per_res at the recombined angles
     const float4 *oatoms;            // [.] (x, y, z, radius)
     const int2 *oseg;                // [B] (first, count) of every segment's range
-    // workspace (the context's proximal buffers: the two never run at once on one context)
+    // workspace (rc_workspace: carved from the context's proximal buffers, the two never run at once on one context)
     int2 *info;                      // [M] (group, row within it), (-1, .) = not a row of a group that is recombined
     int32_t *s, *prop;               // [M] the assignment; this sweep's proposals
     float *gain, *rowU, *rowW;       // [M] this sweep's gains; U(r, s_r) and sum_r' W(r, s_r; r', s_r') at the sweep's start
@@ -68,20 +63,6 @@ struct RcArgs {
     double *trace;
 };
 
-// first consensus row and length of group g, false for an inconsistent group: the rule of pp_ensemble.hip (ens_group)
-__device__ __forceinline__ bool rc_group(const int32_t *__restrict__ seg_off, int g, int D, int N, int &base, int &len, int &row0) {
-    int a, b;
-    pp_seg_rows(seg_off, g * D, N, a, b);
-    row0 = a;
-    base = a / D;
-    len = b - a;
-    bool ok = len >= 1 && base + len <= N / D;
-    for (int d = 1; d < D; d++) {
-        pp_seg_rows(seg_off, g * D + d, N, a, b);
-        ok = ok && (b - a == len);
-    }
-    return ok;
-}
 // obstacles belong to the group: its decoys must point at one range (a group that does not is left alone like a ragged one)
 __device__ __forceinline__ bool rc_obst_same(const RcArgs &A, int g) {
     if (!A.oatoms) return true;
@@ -93,35 +74,19 @@ __device__ __forceinline__ bool rc_obst_same(const RcArgs &A, int g) {
     }
     return ok;
 }
-// first row of decoy d of group g (clamped into the batch like every row of the table)
-__device__ __forceinline__ int rc_decoy_row0(const RcArgs &A, int g, int d) {
-    int a, b;
-    pp_seg_rows(A.seg_off, g * A.D + d, A.N, a, b);
-    return a;
-}
-
-// what the static partner predicate reads of a row: CA, the extent e of k_clash_cand, residue_index
+// what the static partner predicate reads of a row: CA, the extent e (cl_extent), residue_index
 struct RcRow {
     float ca[3], e;
     int ri;
 };
 __device__ __forceinline__ RcRow rc_row(const RcArgs &A, int n) {
     RcRow o;
-    const float *x = A.X + (size_t)n * 42;
-    o.ca[0] = x[3]; o.ca[1] = x[4]; o.ca[2] = x[5];
-    float e = A.side_extent[(int)A.rtype[n]];
-    const float *m = A.amask + (size_t)n * 14;
-#pragma unroll
-    for (int a = 0; a < 4; a++) {
-        if (a == 1 || m[a] == 0.f) continue;
-        const float dx = x[3 * a] - o.ca[0], dy = x[3 * a + 1] - o.ca[1], dz = x[3 * a + 2] - o.ca[2];
-        e = fmaxf(e, sqrtf(dx * dx + dy * dy + dz * dz) * 1.0001f + 1e-3f);
-    }
-    o.e = e;
+    o.e = cl_extent(A.X, A.amask, A.rtype, A.side_extent, n, o.ca);
     o.ri = (int)A.rindex[n];
     return o;
 }
-// symmetric in its two rows: squares of differences, a commutative sum of the extents
+// symmetric in its two rows: squares of differences, a commutative sum of the extents.  Not k_clash_cand's comparison, which is
+// compiled with contraction on (pp_clash_geom.h)
 __device__ __forceinline__ bool rc_near(const RcRow &p, const RcRow &q, float reach) {
 #pragma clang fp contract(off)
     const float dx = q.ca[0] - p.ca[0], dy = q.ca[1] - p.ca[1], dz = q.ca[2] - p.ca[2];
@@ -140,7 +105,7 @@ k_rc_setup(RcArgs A) {
     if ((int)blockIdx.x >= nrb) {
         const int g = blockIdx.x - nrb;
         int base, len, row0;
-        bool ok = rc_group(A.seg_off, g, A.D, A.N, base, len, row0);
+        bool ok = pp_group_rows(A.seg_off, g, A.D, A.N, base, len, row0);
         const int st = A.start ? A.start[g] : 0;
         ok = ok && st >= 0 && st < A.D && rc_obst_same(A, g);
         if (threadIdx.x == 0) {
@@ -156,17 +121,9 @@ k_rc_setup(RcArgs A) {
     }
     const int cr = blockIdx.x * 4 + wave;
     if (cr >= A.M) return;
-    // the group of this consensus row: the last g whose first consensus row is <= cr (k_ens_consensus)
-    int lo = 0, hi = A.G - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        int a, b;
-        pp_seg_rows(A.seg_off, mid * A.D, A.N, a, b);
-        if (a / A.D <= cr) lo = mid; else hi = mid - 1;
-    }
-    const int g = lo;
+    const int g = pp_group_of_cons_row(A.seg_off, A.G, A.D, A.N, cr);
     int base, len, row0;
-    bool ok = rc_group(A.seg_off, g, A.D, A.N, base, len, row0);
+    bool ok = pp_group_rows(A.seg_off, g, A.D, A.N, base, len, row0);
     const int r = cr - base;
     const int st = A.start ? A.start[g] : 0;
     ok = ok && st >= 0 && st < A.D && r >= 0 && r < len && rc_obst_same(A, g);
@@ -180,7 +137,7 @@ k_rc_setup(RcArgs A) {
     }
     // static partners: the backbone and the types are those of every decoy, read from decoy 0
     const RcRow me = rc_row(A, row0 + r);
-    const float reach = 3.6f - A.tol;
+    const float reach = cl_reach(A.tol);
     int32_t *out = A.plist + (size_t)cr * RC_LCAP;
     int cnt = 0;
     for (int j0 = 0; j0 < len; j0 += 64) {
@@ -216,10 +173,10 @@ k_rc_propose(RcArgs A, int k, int full, int count) {
     const int a = lane & 15, slot = lane >> 4;
     const bool own = a < 14;
     const float4 *__restrict__ rec = A.rec;
-    const float tol = A.tol, reach = 3.6f - tol;
+    const float tol = A.tol, reach = cl_reach(tol);
     const int nst = A.pcnt[cr];
     const int32_t *pl = A.plist + (size_t)cr * RC_LCAP;
-    const int row00 = rc_decoy_row0(A, g, 0);
+    const int row00 = pp_decoy_row0(A.seg_off, g, A.D, A.N, 0);
     RcRow me0 = {};
     if (nst < 0) me0 = rc_row(A, row00 + r);
     const int nslots = nst >= 0 ? nst : len;
@@ -229,7 +186,7 @@ k_rc_propose(RcArgs A, int k, int full, int count) {
     int bestD = -1;
     const int dfirst = full ? wave : (wave == 0 ? sr : D), dstep = full ? 4 : D;
     for (int d = dfirst; d < D; d += dstep) {
-        const int ig = rc_decoy_row0(A, g, d) + r;
+        const int ig = pp_decoy_row0(A.seg_off, g, A.D, A.N, d) + r;
         const float4 me = rec[(size_t)ig * 16 + 15];
         const int S = __float_as_int(me.z);
         const int ri = __float_as_int(me.y);
@@ -252,7 +209,7 @@ k_rc_propose(RcArgs A, int k, int full, int count) {
                 const int jl = nst >= 0 ? pl[ci] : ci;
                 const bool partner = nst >= 0 ? true : (jl != r && rc_near(me0, rc_row(A, row00 + jl), reach));
                 if (partner) {
-                    jg = rc_decoy_row0(A, g, A.s[base + jl]) + jl;          // the partner's records at ITS current decoy
+                    jg = pp_decoy_row0(A.seg_off, g, A.D, A.N, A.s[base + jl]) + jl;          // the partner's records at ITS current decoy
                     const float4 cj = rec[(size_t)jg * 16 + 14];
                     const float dx = cj.x - cme.x, dy = cj.y - cme.y, dz = cj.z - cme.z;
                     const float lim = cme.w + cj.w + reach;
@@ -267,6 +224,7 @@ k_rc_propose(RcArgs A, int k, int full, int count) {
             // partner number ord + c of the sequence belongs to stripe (ord + c) mod 4
             for (int c = (slot - ord) & 3; c < cnt; c += 4) {
                 const int jp = list[c];
+                // (k_clash's atom-pair loop without the gradient, pp_clash.hip: change both or neither)
                 float4 pbr[14];
 #pragma unroll
                 for (int bb = 0; bb < 14; bb++) pbr[bb] = rec[(size_t)jp * 16 + bb];
@@ -302,7 +260,7 @@ k_rc_propose(RcArgs A, int k, int full, int count) {
             ord += cnt;
             cnt = 0;
         }
-        // the within-residue bounds (k_clash's tail): stripes of partner atoms b = slot, slot + 4, ...
+        // the within-residue bounds (k_clash's tail, a copy: change both or neither): stripes of partner atoms b = slot, slot + 4, ...
         float ua = 0.f;
         if (own && ea != 0.f) {
             for (int bb = slot; bb < 14; bb += 4) {
@@ -315,11 +273,11 @@ k_rc_propose(RcArgs A, int k, int full, int count) {
                 ua += 2.f * (fmaxf(lo - dd, 0.f) + fmaxf(dd - up, 0.f));          // row sum + column sum of a symmetric table
             }
         }
-        // the obstacle term of k_clash<., ., true>: obstacle l of the group's range goes to stripe l mod 4, ascending l per lane; the
-        // residue's bounding sphere drops obstacles whose hinge is zero on every atom
+        // the obstacle term of k_clash<., ., true> (a copy of its hinge: change both or neither): obstacle l of the group's range goes to
+        // stripe l mod 4, ascending l per lane; the residue's bounding sphere drops obstacles whose hinge is zero on every atom
         if (A.oatoms) {
             const int2 orng = A.oseg[g * D];
-            const float oreach = 1.8f - tol;
+            const float oreach = cl_obst_reach(tol);
             const bool act = own && a >= 4 && ea != 0.f;
             for (int c0 = 0; c0 < orng.y; c0 += 64) {
                 bool keep = false;
@@ -453,10 +411,10 @@ k_rc_apply(RcArgs A, int k) {
     const int base = gi.x, len = gi.y;
     const int nst = A.pcnt[cr];
     const int32_t *pl = A.plist + (size_t)cr * RC_LCAP;
-    const int row00 = rc_decoy_row0(A, g, 0);
+    const int row00 = pp_decoy_row0(A.seg_off, g, A.D, A.N, 0);
     RcRow me0 = {};
     if (nst < 0) me0 = rc_row(A, row00 + r);
-    const float reach = 3.6f - A.tol;
+    const float reach = cl_reach(A.tol);
     const int nslots = nst >= 0 ? nst : len;
     bool blocked = false;
     for (int c0 = 0; c0 < nslots; c0 += 64) {
@@ -487,9 +445,33 @@ k_rc_finish(RcArgs A) {
     const int2 inf = A.info[cr];
     if (inf.x < 0) return;                              // pick stays -1, chi_out is not written
     const int sr = A.s[cr];
-    const int row = rc_decoy_row0(A, inf.x, sr) + inf.y;
+    const int row = pp_decoy_row0(A.seg_off, inf.x, A.D, A.N, sr) + inf.y;
     A.chi_out[e] = A.chi[(size_t)row * 4 + c];
     if (c == 0) A.pick[cr] = sr;
+}
+
+// The workspace of A (A.M, A.G set) out of the proximal buffers of the context: no allocation.  pm, pv, pz, pxeff and cand_cnt hold
+// 4 N four-byte words each, cand 4 N PP_CL_CAP (pp_api.hip); every line below says how many words of which donor it takes.
+static pp_status rc_workspace(const pp_ctx *c, RcArgs &A) {
+    const size_t M = A.M, G = A.G, w = 4 * (size_t)c->N;
+    const size_t fit[][2] = {{4 * M, w},                         // pm:       info [M] int2 | s [M] | prop [M]
+                             {3 * M, w},                         // pv:       gain [M] | rowU [M] | rowW [M]
+                             {4 * G, w},                         // pz:       ginfo [G] int4
+                             {2 * G, w},                         // pxeff:    cnt [G][2]
+                             {M * RC_LCAP, w * PP_CL_CAP},       // cand:     plist [M][RC_LCAP]
+                             {M, w}};                            // cand_cnt: pcnt [M]
+    bool ok = c->cand != nullptr;
+    for (const auto &f : fit) ok = ok && f[0] <= f[1];
+    if (!ok)
+        FAIL(PP_ERR_INVALID, "pp_ensemble_recombine: " + std::to_string(M) + " consensus rows / " + std::to_string(G) +
+                                 " groups do not fit the proximal workspace of this " + std::to_string(c->N) + "-row context");
+    int32_t *pm = reinterpret_cast<int32_t *>(c->pm);
+    A.info = reinterpret_cast<int2 *>(pm); A.s = pm + 2 * M; A.prop = pm + 3 * M;
+    A.gain = c->pv; A.rowU = c->pv + M; A.rowW = c->pv + 2 * M;
+    A.ginfo = reinterpret_cast<int4 *>(c->pz);
+    A.cnt = reinterpret_cast<int32_t *>(c->pxeff);
+    A.plist = c->cand; A.pcnt = c->cand_cnt;
+    return PP_OK;
 }
 
 extern "C" pp_status pp_ensemble_recombine(pp_ctx *c, const float *chi, int n_decoys, const int32_t *start, int max_sweeps,
@@ -499,11 +481,8 @@ extern "C" pp_status pp_ensemble_recombine(pp_ctx *c, const float *chi, int n_de
     if (!c || !chi || !pick || !chi_out || !trace || !sweeps || !converged) FAIL(PP_ERR_INVALID, "pp_ensemble_recombine: null argument");
     if (n_decoys < 1) FAIL(PP_ERR_INVALID, "pp_ensemble_recombine: n_decoys must be at least 1");
     if (max_sweeps < 0) FAIL(PP_ERR_INVALID, "pp_ensemble_recombine: max_sweeps must not be negative");
-    if (!c->packed && c->B != 1)
-        FAIL(PP_ERR_INVALID, "pp_ensemble_recombine: needs a context from pp_complex_prepare_packed (or a B = 1 one), not a padded B > 1 batch");
-    if (c->B % n_decoys != 0 || c->N % n_decoys != 0)
-        FAIL(PP_ERR_INVALID, "pp_ensemble_recombine: the context's " + std::to_string(c->B) + " segments / " + std::to_string(c->N) +
-                                 " rows are not groups of " + std::to_string(n_decoys) + " decoys");
+    pp_status st;
+    if ((st = pp_check_decoy_groups(c, n_decoys, "pp_ensemble_recombine")) != PP_OK) return st;
     if (!c->plan->clash_params_set) FAIL(PP_ERR_INVALID, "pp_ensemble_recombine: call pp_plan_set_clash_params first");
     if (!c->b.atom_mask || !c->b.residue_index) FAIL(PP_ERR_INVALID, "pp_ensemble_recombine: batch lacks atom_mask / residue_index");
     PP_HIP_CHECK(hipSetDevice(c->plan->device));
@@ -515,21 +494,12 @@ extern "C" pp_status pp_ensemble_recombine(pp_ctx *c, const float *chi, int n_de
     A.X = c->b.X; A.amask = c->b.atom_mask; A.side_extent = p->side_extent; A.lower = p->bounds_lower; A.upper = p->bounds_upper;
     A.rtype = c->b.residue_type; A.rindex = c->b.residue_index; A.tol = p->clash_tol;
     A.oatoms = c->obst_M > 0 ? c->obst : nullptr; A.oseg = c->obst_seg;
-    // workspace: M <= N consensus rows and G <= N groups fit the [N][4] buffers of the proximal loop; the partner lists fit its
-    // candidate lists (M RC_LCAP <= N 4 PP_CL_CAP), which every context this call accepts has
-    A.info = reinterpret_cast<int2 *>(c->pm);
-    A.s = reinterpret_cast<int32_t *>(c->pm) + 2 * (size_t)A.M;
-    A.prop = A.s + A.M;
-    A.gain = c->pv; A.rowU = c->pv + A.M; A.rowW = c->pv + 2 * (size_t)A.M;
-    A.ginfo = reinterpret_cast<int4 *>(c->pz);
-    A.cnt = reinterpret_cast<int32_t *>(c->pxeff);
-    A.plist = c->cand; A.pcnt = c->cand_cnt;
+    if ((st = rc_workspace(c, A)) != PP_OK) return st;
     A.start = start; A.pick = pick; A.sweeps = sweeps; A.converged = converged; A.chi_out = chi_out; A.energy = energy; A.trace = trace;
     PP_HIP_CHECK(hipMemsetAsync(pick, 0xff, (size_t)A.M * sizeof(int32_t), s));          // -1: rows of groups that are left alone
     const int nrb = (A.M + 3) / 4;
     hipLaunchKernelGGL(k_rc_setup, dim3(nrb + A.G), dim3(256), 0, s, A);
     PP_HIP_CHECK(hipGetLastError());
-    pp_status st;
     if ((st = pp_launch_atom14(c, chi, c->xyz, s)) != PP_OK) return st;                 // the records of every decoy at chi
     for (int k = 0; k < max_sweeps; k++) {
         hipLaunchKernelGGL(k_rc_propose, dim3(A.M), dim3(256), 0, s, A, k, 1, 1);

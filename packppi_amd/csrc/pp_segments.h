@@ -52,3 +52,43 @@ PP_SEG_FN void pp_seg_fill(const int32_t *off, int n_seg, int N, int max_len, in
     if (start + len > N) len = N - start;
     if (n >= start + len) len = n - start + 1 <= max_len ? n - start + 1 : max_len;
 }
+
+// ---- decoy groups (pp_ensemble.hip, pp_recombine.hip; DESIGN.md sections 16, 18) --------------------------------------------------------
+// A table of G * D segments read as G groups of D decoys: segment g * D + d is decoy d of group g.  Consensus row (g, r) has index
+// off[g * D] / D + r, so the consensus rows of the groups lie back to back in [N / D] buffers.  Rows are the clamped ones of pp_seg_rows.
+
+// Group g: row0 = first row of its decoy 0, base = its first consensus row (row0 / D), len = its length.  True iff the group is
+// CONSISTENT: its D clamped segments have the same length len >= 1 and its consensus rows base .. base + len - 1 lie inside the N / D
+// consensus rows.  Reads off[g * D .. g * D + D] only.
+PP_SEG_FN bool pp_group_rows(const int32_t *off, int g, int D, int N, int &base, int &len, int &row0) {
+    int a, b;
+    pp_seg_rows(off, g * D, N, a, b);
+    row0 = a;
+    base = a / D;
+    len = b - a;
+    bool ok = len >= 1 && base + len <= N / D;
+    for (int d = 1; d < D; d++) {
+        pp_seg_rows(off, g * D + d, N, a, b);
+        ok = ok && (b - a == len);
+    }
+    return ok;
+}
+
+// The group of consensus row crow: the last g in 0 .. G - 1 whose first consensus row is <= crow (0 if there is none).
+PP_SEG_FN int pp_group_of_cons_row(const int32_t *off, int G, int D, int N, int crow) {
+    int lo = 0, hi = G - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        int a, b;
+        pp_seg_rows(off, mid * D, N, a, b);
+        if (a / D <= crow) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+// The first row of decoy d of group g (clamped into the batch like every row of the table).
+PP_SEG_FN int pp_decoy_row0(const int32_t *off, int g, int D, int N, int d) {
+    int a, b;
+    pp_seg_rows(off, g * D + d, N, a, b);
+    return a;
+}

@@ -33,12 +33,6 @@
 // tested in full.  A row without a present atom is in no ATOM shell and seeds none; it is dropped where the list is made.
 #include "pp_internal.h"
 
-#define FAIL(code, msg)          \
-    do {                         \
-        pp_set_error(msg);       \
-        return code;             \
-    } while (0)
-
 #define SH_T 256        // threads of a workgroup = rows it decides = seed candidates it looks at per pass
 
 __device__ __forceinline__ float sh_d2(float px, float py, float pz, float qx, float qy, float qz) {

@@ -4,7 +4,9 @@ Every context describes its complexes by one table ``off[0 .. n_seg]`` (first ro
 against (a) a brute-force linear scan on well-formed tables, uniform (a padded [B][L] batch) and ragged (a packed one), (b) on
 tables that break the contract, a NumPy restatement of what the kernels computed before the header existed, when each carried its
 own copy: the packed segment fill, the seeded-noise row table, the proximal / loss row ranges -- a malformed table must keep giving
-the clamped answers it gave, and (c) the padded forms ``n / L``, ``s * L`` those kernels had next to the packed ones."""
+the clamped answers it gave, (c) the padded forms ``n / L``, ``s * L`` those kernels had next to the packed ones, and (d) the
+decoy-group functions against a restatement of the header comment of csrc/pp_ensemble.hip, whose kernels and those of
+csrc/pp_recombine.hip each carried a copy of them."""
 import ctypes
 import os
 import subprocess
@@ -38,6 +40,18 @@ class Table:
         out = np.zeros(2, np.int32)
         self.h.seg_rows(self.p, int(s), int(N), out.ctypes.data_as(ctypes.c_void_p))
         return int(out[0]), int(out[1])
+
+    def group(self, g, D, N):
+        """(consistent?, first consensus row, length, first row of decoy 0) of group g."""
+        out = np.zeros(4, np.int32)
+        self.h.group_rows(self.p, int(g), int(D), int(N), out.ctypes.data_as(ctypes.c_void_p))
+        return bool(out[0]), int(out[1]), int(out[2]), int(out[3])
+
+    def group_of(self, G, D, N, crow):
+        return self.h.group_of_cons_row(self.p, int(G), int(D), int(N), int(crow))
+
+    def decoy_row0(self, g, D, N, d):
+        return self.h.decoy_row0(self.p, int(g), int(D), int(N), int(d))
 
     def fill(self, N, max_len):
         out = np.zeros((N, 2), np.int32)
@@ -163,3 +177,79 @@ def test_malformed_tables_keep_their_clamped_answers(harness):
             a, b = t.rows(s, N)
             assert (a, b) == old_seg_rows(off, s, N), (name, s)
             assert 0 <= a <= b <= N
+
+
+# ---- decoy groups: G * D segments read as G groups of D decoys (pp_group_rows, pp_group_of_cons_row, pp_decoy_row0) --------------------
+# Restated from the header comment of csrc/pp_ensemble.hip (LAYOUT and A TABLE THAT BREAKS THE CONTRACT), by looking at every
+# segment: segment g * D + d is decoy d of group g; rows are the clamped ones; the consensus row of (g, r) is (first row of decoy 0)
+# / D + r; a group is consistent when its D clamped segments have one length >= 1 and its consensus rows lie inside the N / D.
+def brute_group(off, g, D, N):
+    segs = [old_seg_rows(off, g * D + d, N) for d in range(D)]
+    lens = [b - a for a, b in segs]
+    row0 = segs[0][0]
+    base = row0 // D
+    consensus_rows = range(base, base + lens[0])
+    ok = len(set(lens)) == 1 and lens[0] >= 1 and all(0 <= r < N // D for r in (consensus_rows[0], consensus_rows[-1]))
+    return ok, base, lens[0], row0
+
+
+def brute_group_of(off, G, D, N, crow):
+    """The last g whose first consensus row is <= crow, as the kernels have always searched for it: by bisection, which on a table
+    whose first rows do not ascend is not the last such g of a linear scan -- and must stay what it was."""
+    lo, hi = 0, G - 1
+    while lo < hi:
+        mid = (lo + hi + 1) >> 1
+        if old_seg_rows(off, mid * D, N)[0] // D <= crow:
+            lo = mid
+        else:
+            hi = mid - 1
+    return lo
+
+
+def group_tables():
+    """(name, off, N, D, what every group must come out as: consistent or not, or None = only the comparison)"""
+    yield "G = 2, D = 3, lengths 5 and 1", [0, 5, 10, 15, 16, 17, 18], 18, 3, [True, True]
+    yield "D = 1", [0, 7, 20, 21], 21, 1, [True, True, True]
+    yield "one decoy shorter", [0, 4, 7, 11, 12, 13, 14, 16, 18, 20], 20, 3, [False, True, True]
+    yield "one decoy longer, in the last group", [0, 2, 4, 6, 8, 10, 13], 13, 2, [True, True, False]
+    yield "consensus rows past N / D", [0, 3, 6, 14, 12, 20], 20, 2, [True, False]
+    yield "negative and beyond N", [-5, 4, 8, 30, 40], 16, 2, [True, False]
+    yield "zero-length group", [0, 0, 0, 6, 12], 12, 2, [False, True]
+    for name, off, N, _ in malformed_tables():
+        for D in range(1, len(off)):
+            if (len(off) - 1) % D == 0:
+                yield f"{name}, D = {D}", off, N, D, None
+
+
+def test_decoy_groups_against_the_ensemble_header(harness):
+    for name, off, N, D, want in group_tables():
+        t = Table(harness, off)
+        G = t.n_seg // D
+        got = [t.group(g, D, N) for g in range(G)]
+        for g in range(G):
+            ok, base, ln, row0 = brute_group(off, g, D, N)
+            assert got[g] == (ok, base, ln, row0), (name, g)
+            for d in range(D):
+                assert t.decoy_row0(g, D, N, d) == old_seg_rows(off, g * D + d, N)[0], (name, g, d)
+            if ok:           # what the rule is for: every row of every decoy is a row of the batch, every consensus row one of the N / D
+                assert 0 <= base and base + ln <= N // D
+                assert all(0 <= t.decoy_row0(g, D, N, d) and t.decoy_row0(g, D, N, d) + ln <= N for d in range(D))
+        if want is not None:
+            assert [g[0] for g in got] == want, name
+        for crow in range(-2, N // D + 3):
+            assert t.group_of(G, D, N, crow) == brute_group_of(off, G, D, N, crow), (name, crow)
+
+
+def test_consensus_rows_of_well_formed_ensembles_find_their_group(harness):
+    """Groups of D equal decoys back to back: consensus rows 0 .. N / D - 1, each in the group a linear scan of the lengths gives."""
+    rng = np.random.default_rng(16)
+    for _ in range(100):
+        D, lens = int(rng.integers(1, 6)), rng.integers(1, 80, int(rng.integers(1, 7)))
+        off = [0] + [int(v) for v in np.cumsum(np.repeat(lens, D))]
+        t, N, G = Table(harness, off), off[-1], len(lens)
+        first = np.concatenate([[0], np.cumsum(lens)])
+        for g in range(G):
+            assert t.group(g, D, N) == (True, int(first[g]), int(lens[g]), int(first[g]) * D)
+            assert [t.decoy_row0(g, D, N, d) for d in range(D)] == [int(first[g]) * D + d * int(lens[g]) for d in range(D)]
+        for crow in range(N // D):
+            assert t.group_of(G, D, N, crow) == int(np.searchsorted(first, crow, side="right")) - 1
