@@ -481,6 +481,35 @@ pp_status pp_ctx_shell(pp_ctx *ctx, const uint8_t *seeds /* DEVICE [N] */, int m
                        const float *xyz /* DEVICE [N,14,3] or NULL = the batch's X */,
                        uint8_t *shell /* DEVICE [N] */, int32_t *count /* DEVICE [n_seg] or NULL */, void *stream);
 
+/* ---- Solvent-accessible surface (no reference kernel; csrc/pp_sasa.hip holds the arithmetic) -------------
+ * Shrake-Rupley test points with four nested occluder levels in one pass, per segment of the ctx's segment table (the complexes of
+ * a packed ctx, the decoys of a group, the B rows of a padded batch).  The reference's interface (src/utils/interface.py: a residue
+ * whose accessible area in the isolated chain exceeds that in the complex) needs freesasa; this makes the same statement on the
+ * device.  An atom (row n, slot a) is present iff radius[n][a] > 0; residue_mask is not consulted.  The occluders of a present atom
+ * are, by class: 0 the other present atoms of its row; 1 those of other rows of the segment with the same chain_indices; 2 those of
+ * rows of the segment with another chain_indices; 3 the obstacle atoms of the segment with r_o > 0 (pp_ctx_set_obstacles).
+ * Arithmetic (fp32, fp contract off):  R_a = r_a + probe;  q = p_a + (R_a u_k) per component;  for occluder b  R_b = r_b + probe,
+ * d = q - p_b,  d2 = ((dx dx) + (dy dy)) + (dz dz);  the point is buried iff d2 < R_b R_b (strict; a NaN buries nothing and is
+ * buried by nothing).  m(a, k) = the smallest class that buries point k, 4 if none.
+ *   counts[n][a][L] = #{k : m(a, k) > L}, 0 for an absent atom: exposed next to the own residue alone (L = 0), in the isolated
+ *                     chain (1), in the protein complex (2), with the obstacles too (3); non-increasing in L; without obstacles
+ *                     level 3 = level 2;
+ *   area[n][L]      = sum over ascending present slots a of ((kf R_a) R_a) (float)counts[n][a][L], kf = (float)(4 pi / n_points);
+ *   seg_area[s][L]  = the fp64 sum of area over the rows of segment s, in a fixed binary tree (no float atomics).
+ * m is a minimum over a set: a segment gets the same bits alone, packed in front of or behind others, or as a decoy of a group, and
+ * two runs give the same bits.  The candidate search (per-row bounding spheres, an LDS list of at most PP_SASA_LIST_CAP atoms that
+ * is worked off and refilled) changes no output word.  points are caller data and are not normalised.  xyz NULL = the batch's X.
+ * Absolute areas belong to the radii given; they are not freesasa's numbers.  Never waits for the stream; every output word has
+ * one writer.
+ * PP_ERR_INVALID: a null ctx, radius, points or area; n_points outside 1 .. PP_SASA_MAX_POINTS; probe negative or not finite; a
+ * batch without chain_indices. */
+#define PP_SASA_LIST_CAP 768    /* occluder atoms the LDS list of one row holds before it is worked off */
+#define PP_SASA_MAX_POINTS 256
+pp_status pp_sasa(pp_ctx *ctx, const float *xyz /* DEVICE [N,14,3] or NULL = the batch's X */, const float *radius /* DEVICE [N][14] */,
+                  const float *points /* DEVICE [n_points][3] */, int n_points, float probe,
+                  int32_t *counts /* DEVICE [N][14][4] or NULL */, float *area /* DEVICE [N][4] */,
+                  double *seg_area /* DEVICE [n_seg][4] or NULL */, void *stream);
+
 /* Measurement aid, no reference counterpart: average duration (ms) of one launch of a hot kernel
  * (which: 0 = node-message kernel, 1 = edge-update kernel), timed with HIP events on `stream`
  * around `iters` launches.  Synchronises the stream. */

@@ -65,6 +65,47 @@ def interface_mask(protein, pdb, radius=10.0):
     return torch.from_numpy(np.concatenate(parts)).float()
 
 
+def sphere_points(n_points):
+    """The test points of ``Context.sasa``: ``n_points`` unit vectors on the golden spiral, float32 [P, 3].
+    Computed in float64 -- z_k = 1 - (2k + 1) / P, phi_k = k pi (3 - sqrt 5), (sqrt(1 - z^2) cos phi, sqrt(1 - z^2) sin phi, z) --
+    and rounded to float32 once: deterministic, the same table on every host."""
+    P = int(n_points)
+    if P < 1:
+        raise ValueError(f"n_points must be at least 1, got {n_points}")
+    k = np.arange(P, dtype=np.float64)
+    z = 1.0 - (2.0 * k + 1.0) / P
+    phi = k * (np.pi * (3.0 - np.sqrt(5.0)))
+    s = np.sqrt(1.0 - z * z)
+    return np.ascontiguousarray(np.stack([s * np.cos(phi), s * np.sin(phi), z], 1).astype(np.float32))
+
+
+SASA_CSV_HEADER = "chain,number,name,sasa_residue,sasa_chain,sasa_complex,sasa_ligand,bsa,exposure"
+
+
+def sasa_csv_text(protein, area, bsa, exposure):
+    """The text of ``sasa.csv``: one line per residue of ``protein`` -- chain, residue number, residue name, the four areas of
+    ``Context.sasa`` in A^2 (next to the own residue alone, in the isolated chain, in the complex, with the obstacle atoms), the
+    buried interface area and the exposure.  ``area`` [n, 4], ``bsa`` / ``exposure`` [n] (lists or arrays); rows of ``protein``
+    beyond n (trailing rows without a residue) get zeros."""
+    from . import constants as rc
+    area, bsa, exposure = np.asarray(area, dtype=np.float64).reshape(-1, 4), np.asarray(bsa, dtype=np.float64), np.asarray(exposure, dtype=np.float64)
+    lines = [SASA_CSV_HEADER]
+    for r, (cid, num, aa) in enumerate(zip(protein["chain_id"], protein["residue_index"], protein["aaindex"])):
+        a, b, e = (area[r], bsa[r], exposure[r]) if r < len(area) else (np.zeros(4), 0.0, 0.0)
+        lines.append(f"{cid},{int(num)},{rc.resnames[int(aa)]}," + ",".join(f"{v:.3f}" for v in a) + f",{b:.3f},{e:.4f}")
+    return "\n".join(lines) + "\n"
+
+
+def write_sasa_csv(path, protein, res, row=0):
+    """``sasa.csv`` at ``path`` from what ``Context.sasa`` returned for a B = 1 batch of ``protein``; prints the summary line."""
+    area = res.area[row].cpu().numpy()
+    with open(path, "w") as fh:
+        fh.write(sasa_csv_text(protein, area, res.bsa[row].cpu().numpy(), res.exposure[row].cpu().numpy()))
+    seg = res.seg_area[row].cpu().tolist()
+    print(f"----- sasa: {seg[2]:.1f} A^2 accessible in the complex, {seg[1] - seg[2]:.1f} A^2 buried between chains, "
+          f"{seg[2] - seg[3]:.1f} A^2 buried by obstacle atoms; {int(res.interface[row].sum())} interface residues -----")
+
+
 class ProteinAnalysis:
     def __init__(self, molprobity_clash_loc, tmp_dir, device="cuda"):
         self.molprobity_clash_loc = molprobity_clash_loc

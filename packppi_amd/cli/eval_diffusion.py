@@ -24,6 +24,14 @@ clash stage (--use_proximal, the clash ranking of --n_decoys, --recombine).  The
 sampling is unchanged, the clash stages repair what it puts into the pocket.  Every structure file written gets those records'
 original lines, verbatim, between the protein's last TER and END, and obstacles.csv lists per residue its clash against the
 obstacles (Context.clash with the set minus Context.clash without it) at the input's angles and at the result's.
+--sasa (without it every output byte as before) writes sasa.csv for the structure written as structure.pdb:
+chain, number, name, the solvent-accessible area of every residue next to itself alone, in its isolated chain, in the complex and
+with the obstacle atoms, the buried interface area (chain minus complex) and the exposure (last over first); with --n_decoys
+ensemble.csv gains the column bsa, the interface area every decoy buries.  The areas belong to this radius set (element van der
+Waals radii, heavy atoms, probe 1.4 A, 96 points): they are not freesasa's numbers.
+--repack interface:sasa selects the delta-SASA interface of the input structure -- residues with surface that is exposed in the
+isolated chain and buried in the complex, the reference's interface.py rule -- on the device, without reading the file again;
+--repack pocket selects the residues whose surface the obstacle atoms bury and needs --obstacles other than none.
 """
 import argparse
 import os
@@ -64,7 +72,7 @@ def write_ensemble(model, batch, protein, args, analysis):
     from .. import constants as rc
     kw = dict(recombine=True, recombine_sweeps=args.recombine_sweeps) if args.recombine else {}
     out = model.sample_ensemble(batch, args.n_decoys, seed=args.seed, use_proximal=args.use_proximal, select=args.select,
-                                return_all=True, **kw)
+                                return_all=True, **kw, **(dict(sasa=True) if args.sasa else {}))
     chi, packed = out["decoys"]
     best = int(out["best"][0])
     dev, clash = out["dev"].cpu().tolist(), out["clash"].cpu().tolist()
@@ -83,9 +91,10 @@ def write_ensemble(model, batch, protein, args, analysis):
     with open(analysis.tmp_pdb, "w") as fh:
         fh.write(final)
     with open(os.path.join(args.outdir, "ensemble.csv"), "w") as fh:
-        fh.write("decoy,key,dev,clash,selected\n")
+        bsa = out["bsa"].cpu().tolist() if args.sasa else None
+        fh.write("decoy,key,dev,clash,selected" + (",bsa" if args.sasa else "") + "\n")
         for d, key in enumerate(out["keys"]):
-            fh.write(f"{d},{key},{dev[d]!r},{clash[d]!r},{int(d == best)}\n")
+            fh.write(f"{d},{key},{dev[d]!r},{clash[d]!r},{int(d == best)}" + (f",{bsa[d]!r}" if args.sasa else "") + "\n")
     conf = out["confidence"][0].cpu().tolist()
     conf += [[0.0] * 4] * (len(protein["aaindex"]) - len(conf))
     with open(os.path.join(args.outdir, "confidence.csv"), "w") as fh:
@@ -156,6 +165,17 @@ def write_obstacles_csv(model, batch, protein, args, chi_after):
     print(f"----- obstacles: clash against them {sum(before):.4f} -> {sum(after):.4f} (summed over residues; {hit} residues still touch) -----")
 
 
+def write_sasa(batch, protein, outdir, chi, name="sasa.csv"):
+    """--sasa: sasa.csv of the B = 1 ``batch`` at the angles ``chi`` [1, n, 4] (n < L: the trailing rows without a residue that
+    pack() dropped keep the batch's angles)."""
+    from ..analysis import write_sasa_csv
+    from ..functional import solvent_accessibility
+    chi = chi.to(batch.SC_D.device)
+    if chi.shape[1] != batch.SC_D.shape[1]:
+        chi = torch.cat([chi, batch.SC_D[:, chi.shape[1]:]], 1)
+    write_sasa_csv(os.path.join(outdir, name), protein, solvent_accessibility(batch, chi))
+
+
 def evaluate_model(model, args):
     print("----- Starting evaluation! -----")
     analysis = ProteinAnalysis(args.molprobity_clash_loc, args.outdir, args.device)
@@ -173,8 +193,12 @@ def evaluate_model(model, args):
     # same seed gives the same structure on any device, shard layout and torch version
     fixed = None
     if args.repack is not None:
-        from ..selection import interface_selection, parse_selection
-        sel = interface_selection(protein, args.input) if args.repack == "interface" else parse_selection(args.repack, protein)
+        from ..selection import device_selector, interface_selection, parse_selection, sasa_selection
+        kind = device_selector(args.repack, args.obstacles)
+        if kind is not None:
+            sel = sasa_selection(batch, kind)
+        else:
+            sel = interface_selection(protein, args.input) if args.repack == "interface" else parse_selection(args.repack, protein)
         print(f"----- Repacking {int(sel.sum())} of {len(sel)} residues ({args.fixed_mode}); the others keep the input's angles -----")
         fixed = torch.from_numpy(~sel).unsqueeze(0)
     if args.n_decoys is not None:
@@ -196,6 +220,8 @@ def evaluate_model(model, args):
             fh.writelines(insert_obstacle_lines(to_pdb(protein), args.obstacle_lines))
     if obstacles is not None:
         write_obstacles_csv(model, batch, protein, args, SC_D_sample)
+    if args.sasa:
+        write_sasa(batch, protein, args.outdir, SC_D_sample)
     if contains_sidechains(args.input):
         metric = analysis.get_metric(true_pdb=args.input, pred_pdb=analysis.tmp_pdb)
         print(f"----- Metric: ----- {metric}")
@@ -233,12 +259,22 @@ def build_parser():
                    "every non-standard residue (ligands, cofactors, nucleic acids; no hydrogens, waters or metals), hetero+water = the "
                    "waters too. The diffusion network does not see them: sampling is unchanged, the clash stages (--use_proximal, "
                    "decoy ranking, --recombine) repair what it puts into the pocket. Written structures keep the records.")
+    p.add_argument("--sasa", action="store_true", help="Write sasa.csv for the written structure (DESIGN.md section 20): per residue "
+                   "the solvent-accessible area next to itself alone, in its isolated chain, in the complex and with the obstacle "
+                   "atoms, the buried interface area and the exposure; with --n_decoys ensemble.csv gains the column bsa. "
+                   "--repack also takes interface:sasa (the delta-SASA interface of the input, made on the device) and pocket "
+                   "(residues whose surface the obstacle atoms bury; needs --obstacles).")
     return p
 
 
 def parse_args(argv=None):
     p = build_parser()
     args = p.parse_args(argv)
+    try:
+        from ..selection import device_selector
+        device_selector(args.repack, args.obstacles)
+    except ValueError as e:
+        p.error(str(e))
     if args.repack is not None and args.seed is None:
         p.error("--repack needs --seed (the kept residues are re-noised with the seeded generator's draws)")
     if args.n_decoys is not None:

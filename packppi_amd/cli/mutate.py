@@ -16,6 +16,10 @@ recombined structure and ``mutants.csv`` gains the columns ``clash_recombined`` 
 non-standard residues become fixed obstacle atoms of every clash stage (--use_proximal, the clash ranking, --recombine); the
 network does not see them.  Every ``mutant_<tag>.pdb`` keeps their lines and ``obstacles.csv`` lists, per set and residue, the
 clash against them at the wild type's angles (new side chains at chi = 0) and at the result's.
+--sasa (without it every output byte as before): next to every ``mutant_<tag>.pdb`` a ``sasa_<tag>.csv`` of
+that structure (per residue the solvent-accessible area at four nested levels, the buried interface area and the exposure; the file
+``eval_diffusion --sasa`` writes as sasa.csv), and ``mutants.csv`` gains the column ``bsa``, the interface area the selected decoy
+buries.
 """
 import argparse
 import os
@@ -59,10 +63,11 @@ def evaluate_model(model, args):
     sets = read_sets(args)
     results = model.mutate([(protein, s) for s in sets], seed=args.seed, radius=args.radius, shell=args.shell,
                            n_decoys=args.n_decoys, use_proximal=args.use_proximal, select=args.select, fixed_mode=args.fixed_mode,
-                           **(dict(recombine=True, recombine_sweeps=args.recombine_sweeps) if args.recombine else {}))
+                           **(dict(recombine=True, recombine_sweeps=args.recombine_sweeps) if args.recombine else {}),
+                           **(dict(sasa=True) if args.sasa else {}))
     ddg = predict_ddg(protein, sets, args) if args.ap_ckpt else None
     rows = ["tag,shell_rows,selected_decoy,clash,dev" + (",clash_recombined,rows_recombined" if args.recombine else "")
-            + (",ddg,ddg_inv" if ddg else "")]
+            + (",ddg,ddg_inv" if ddg else "") + (",bsa" if args.sasa else "")]
     for i, (s, r) in enumerate(zip(sets, results)):
         tag = (r["tag"] or s).replace(",", "_")
         b = r["batch"]
@@ -82,6 +87,10 @@ def evaluate_model(model, args):
             line += f",{float(r['clash_recombined'])!r},{int(r['rows_recombined'])}"
         if ddg:
             line += f",{ddg[0][i]!r},{ddg[1][i]!r}"
+        if args.sasa:
+            from .eval_diffusion import write_sasa
+            line += f",{float(r['bsa'][best])!r}"
+            write_sasa(b, mutant, args.outdir, r["SC_D"], name=f"sasa_{tag}.csv")
         rows.append(line)
         print(f"----- {tag}: {int(r['shell'].sum())} residues repacked, decoy {best} of {args.n_decoys} selected"
               + (f", {int(r['rows_recombined'])} residues recombined from other decoys" if args.recombine else "") + " -----")
@@ -133,6 +142,9 @@ def build_parser():
                    "every non-standard residue (ligands, cofactors, nucleic acids; no hydrogens, waters or metals), hetero+water = the "
                    "waters too. The diffusion network does not see them: sampling is unchanged, the clash stages (--use_proximal, "
                    "decoy ranking, --recombine) repair what it puts into the pocket. Written structures keep the records.")
+    p.add_argument("--sasa", action="store_true", help="Write sasa_<tag>.csv next to every mutant (DESIGN.md section 20): per residue "
+                   "the solvent-accessible area at four nested levels, the buried interface area and the exposure; mutants.csv gains "
+                   "the column bsa.")
     return p
 
 

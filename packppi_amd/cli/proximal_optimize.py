@@ -6,6 +6,9 @@ the input's angles (the pinned optimiser: the clash threshold is still the mean 
 --obstacles hetero|hetero+water (default none: every output byte as before): the file's HETATM records and
 non-standard residues become fixed obstacle atoms of the clash loss; structure.pdb keeps their lines and obstacles.csv lists every
 residue's clash against them before and after.
+--sasa (without it every output byte as before) writes sasa.csv for the optimised structure, as eval_diffusion
+does; --repack also takes interface:sasa (the delta-SASA interface of the input, made on the device) and pocket (residues whose
+surface the obstacle atoms bury; needs --obstacles other than none).
 """
 import argparse
 from pathlib import Path
@@ -31,11 +34,25 @@ def build_parser():
                    "every non-standard residue (ligands, cofactors, nucleic acids; no hydrogens, waters or metals), hetero+water = the "
                    "waters too. The diffusion network does not see them: the clash stages of this tool repair"
                    " what it puts into the pocket. Written structures keep the records.")
+    p.add_argument("--sasa", action="store_true", help="Write sasa.csv for the optimised structure (DESIGN.md section 20): per "
+                   "residue the solvent-accessible area at four nested levels, the buried interface area and the exposure. --repack "
+                   "also takes interface:sasa and pocket (needs --obstacles).")
     return p
 
 
+def parse_args(argv=None):
+    from ..selection import device_selector
+    p = build_parser()
+    args = p.parse_args(argv)
+    try:
+        device_selector(args.repack, args.obstacles)
+    except ValueError as e:
+        p.error(str(e))
+    return args
+
+
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    args = parse_args(argv)
 
     assert contains_sidechains(args.input), "----- No side chain atoms found in the input PDB -----"
     print("----- Starting optimize! -----")
@@ -51,8 +68,12 @@ def main(argv=None):
     fixed = None
     if args.repack is not None:
         import torch
-        from ..selection import interface_selection, parse_selection
-        sel = interface_selection(protein, args.input) if args.repack == "interface" else parse_selection(args.repack, protein)
+        from ..selection import device_selector, interface_selection, parse_selection, sasa_selection
+        kind = device_selector(args.repack, args.obstacles)
+        if kind is not None:
+            sel = sasa_selection(batch, kind)
+        else:
+            sel = interface_selection(protein, args.input) if args.repack == "interface" else parse_selection(args.repack, protein)
         print(f"----- Optimising {int(sel.sum())} of {len(sel)} residues; the others keep the input's angles -----")
         fixed = torch.from_numpy(~sel).unsqueeze(0)
     chis, losses = proximal_optimizer(batch, batch.SC_D, args.violation_tolerance_factor,
@@ -76,6 +97,9 @@ def main(argv=None):
             fh.write("residue,chain,clash_obstacles_before,clash_obstacles_after\n")
             for num, cid, b, a in zip(protein["residue_index"], protein["chain_id"], *shares):
                 fh.write(f"{int(num)},{cid},{b!r},{a!r}\n")
+    if args.sasa:
+        from .eval_diffusion import write_sasa
+        write_sasa(batch, protein, args.outdir, SC_D)
     print(f"----- The optimized structure clashscore is {analysis.get_clashscore(analysis.tmp_pdb)} -----")
     print("----- Finishing optimize! -----")
 

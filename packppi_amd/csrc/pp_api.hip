@@ -420,6 +420,7 @@ static pp_status prepare_impl(pp_plan *plan, const pp_batch *b, const int32_t *s
     ALLOC(prox_part, (size_t)PP_PROX_CHUNK * N);
     if (prox) { ALLOC(prox_nrows, c->B); ALLOC(prox_seg, c->B); ALLOC(prox_inv, N); }
     if (prox) { ALLOC(obst_seg, c->B); ALLOC(obst_row, N); ALLOC(obst_cand, (size_t)N * PP_OB_CAP); ALLOC(obst_cnt, N); }
+    ALLOC(sasa_row, N * 8);
     ALLOC(seg_off, (size_t)c->B + 1);
     ALLOC(rng_tab, N); ALLOC(rng_keys, c->B);
     c->max_steps = 1 << 20;

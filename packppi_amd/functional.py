@@ -5,6 +5,7 @@
     find_clash_mask(batch, SC_D, vtf, tol)                     optimize.py:5-18
     proximal_optimizer(batch, SC_D, vtf, tol, lamda, steps)    optimize.py:21-73
     proximal_optimizer_packed(packed_batch, SC_D, ...)        the same for every complex of a batch.pack() batch at once
+    solvent_accessibility(batch, SC_D=None, ...)              no reference counterpart (interface.py needs freesasa): pp_sasa
 
 The three proximal functions take ``fixed_mask`` (partial repacking): rows that keep their incoming angles.
 
@@ -80,6 +81,14 @@ def proximal_optimizer(batch, SC_D, violation_tolerance_factor, clash_overlap_to
         losses = losses[0]
     loss_list = [float(v) for v in losses.cpu()]          # the one host sync of the whole optimisation
     return [traj[i] for i in range(num_steps)], loss_list
+
+
+def solvent_accessibility(batch, SC_D=None, n_points=96, probe=1.4, radius=None, want_counts=False):
+    """Solvent-accessible surface of every residue at four nested levels (``lib.Context.sasa``, pp_sasa), on
+    the geometry plan: at the angles ``SC_D`` (through atom14), else at the batch's X.  Padded, packed and decoy batches alike: the
+    occluders of a row are the rows and the obstacle atoms of its own complex.  Returns ``area`` [B, L, 4], ``seg_area`` fp64
+    [n_complexes, 4], ``counts`` (with ``want_counts``), ``bsa``, ``interface``, ``pocket`` and ``exposure``."""
+    return _ctx_for(batch).sasa(chi=SC_D, n_points=n_points, probe=probe, radius=radius, want_counts=want_counts)
 
 
 def proximal_optimizer_packed(packed_batch, SC_D, violation_tolerance_factor, clash_overlap_tolerance, lamda, num_steps=50,

@@ -22,7 +22,7 @@ SYMBOLS = ("pp_version", "pp_last_error", "pp_build_id", "pp_plan_set_knn_ties",
            "pp_score_rows", "pp_so2_set_grids", "pp_so2_score", "pp_dsm_loss",
            "pp_ctx_set_rng_keys", "pp_noise_seeded", "pp_add_noise_seeded", "pp_sample_seeded",
            "pp_sample_partial", "pp_proximal_pinned", "pp_ctx_live_rows", "pp_ensemble_reduce", "pp_ctx_shell",
-           "pp_ensemble_recombine", "pp_ctx_set_obstacles")
+           "pp_ensemble_recombine", "pp_ctx_set_obstacles", "pp_sasa")
 
 
 FIX_MODES = {"hold": 0, "renoise": 1}         # PP_FIX_HOLD, PP_FIX_RENOISE
@@ -141,6 +141,7 @@ def load():
     lib.pp_ctx_shell.argtypes = [vp, vp, i, f, i, vp, vp, vp, vp]
     lib.pp_ensemble_recombine.argtypes = [vp, vp, i, vp, i, vp, vp, vp, vp, vp, vp, vp]
     lib.pp_ctx_set_obstacles.argtypes = [vp, vp, vp, i, vp]
+    lib.pp_sasa.argtypes = [vp, vp, vp, vp, i, f, vp, vp, vp, vp]
     _lib = lib
     return lib
 
@@ -695,6 +696,51 @@ class Context:
         _check(load().pp_ctx_shell(self.handle, _ptr(sd), SHELL_MODES[mode], float(radius), SHELL_OTHER_CHAIN if other_chain else 0,
                                    _ptr(xyz), _ptr(out), _ptr(count), _stream(self.plan.device)), "pp_ctx_shell")
         return (out.bool(), count) if want_count else out.bool()
+
+    def sasa(self, chi=None, xyz=None, n_points=96, probe=1.4, radius=None, want_counts=False):
+        """Solvent-accessible surface per residue at four nested levels, on the device (pp_sasa).  Coordinates:
+        ``atom14(chi)`` if ``chi`` is given, else ``xyz`` [B, L, 14, 3], else the batch's X.  ``radius`` [B, L, 14] (an atom is
+        present iff its radius is > 0; default ``constants.slot_radius[residue_type] * (atom_mask != 0)``: the reference's element
+        van der Waals radii, heavy atoms only); ``n_points`` test points per atom (``analysis.sphere_points``), ``probe`` in A.
+        Returns an ``EnsembleResult``: ``area`` fp32 [B, L, 4] -- A^2 exposed next to the own residue alone (0), in the isolated
+        chain (1), in the protein complex (2), with the context's obstacle atoms too (3) --, ``seg_area`` fp64 [n_segments, 4],
+        ``counts`` int32 [B, L, 14, 4] (None without ``want_counts``) and, derived here: ``bsa`` = area[1] - area[2] (the surface
+        a row buries in the interface), ``interface`` / ``pocket`` bool [B, L] (a test point of the row is buried by another
+        chain / by an obstacle atom: integer tests on the counts; the reference's delta-ASA > 0 rule) and ``exposure`` =
+        area[3] / area[0] (0 where area[0] is 0).  Areas are those of this radius set, not freesasa's.  No host synchronisation."""
+        from .analysis import sphere_points
+        dev = self.plan.device
+        if self._t.get("chain_indices") is None:
+            raise RuntimeError("sasa needs a batch with chain_indices")
+        if chi is not None:
+            xyz = self.atom14(chi)
+        elif xyz is not None:
+            xyz = xyz.to(device=dev, dtype=torch.float32).contiguous()
+            if xyz.numel() != self.n_rows * 42:
+                raise ValueError(f"xyz has {xyz.numel()} elements, this context has {self.n_rows} rows x 14 x 3")
+        if radius is None:
+            if getattr(self, "_sasa_radius", None) is None:
+                if self._t.get("atom_mask") is None:
+                    raise RuntimeError("sasa needs a batch with atom_mask (or radius)")
+                table = torch.from_numpy(np.asarray(rc.slot_radius, dtype=np.float32)).to(dev)
+                self._sasa_radius = (table[self._t["residue_type"]] * (self._t["atom_mask"] != 0)).contiguous()
+            radius = self._sasa_radius
+        else:
+            radius = self._rows(torch.as_tensor(radius), "radius", 14)
+        P = int(n_points)
+        cache = self.__dict__.setdefault("_sasa_points", {})
+        if P not in cache:
+            cache[P] = torch.from_numpy(sphere_points(P)).to(dev) if 1 <= P <= 256 else torch.zeros(1, 3, device=dev)
+        counts = self._new(self.B, self.L, 14, 4, dtype=torch.int32)
+        area = self._new(self.B, self.L, 4)
+        seg_area = self._new(self.n_segments, 4, dtype=torch.float64)
+        _check(load().pp_sasa(self.handle, _ptr(xyz), _ptr(radius), _ptr(cache[P]), P, float(probe), _ptr(counts), _ptr(area),
+                              _ptr(seg_area), _stream(dev)), "pp_sasa")
+        per_row = counts.sum(2)
+        a0 = area[..., 0]
+        return EnsembleResult(area=area, seg_area=seg_area, counts=counts if want_counts else None, bsa=area[..., 1] - area[..., 2],
+                              interface=per_row[..., 1] - per_row[..., 2] > 0, pocket=per_row[..., 2] - per_row[..., 3] > 0,
+                              exposure=torch.where(a0 > 0, area[..., 3] / a0, torch.zeros_like(a0)))
 
     def saturated(self) -> int:
         """Sticky flag word of this context: 0 = clean; bit 0 / bit 1 = a hidden activation was clamped at 65504 in an edge-level /

@@ -393,8 +393,14 @@ class TDiffusionModule:
                                      vtf=cfg.violation_tolerance_factor, tol=cfg.clash_overlap_tolerance)
         return rec, dict(recombined=rec.chi, pick=rec.pick, clash_trace=rec.clash_trace, sweeps=rec.sweeps, converged=rec.converged)
 
+    @staticmethod
+    def _decoy_bsa(ctx, chi):
+        """fp64 [n_segments]: the surface every segment (decoy) buries between its chains at ``chi``."""
+        seg = ctx.sasa(chi=chi).seg_area
+        return seg[:, 1] - seg[:, 2]
+
     def sample_ensemble(self, batch, n_decoys, *, seed=None, use_proximal: bool = False, select="clash", return_all: bool = False,
-                        recombine: bool = False, recombine_sweeps: int = 64):
+                        recombine: bool = False, recombine_sweeps: int = 64, sasa: bool = False):
         """``n_decoys`` seeded samples of every complex in ONE packed pass, reduced on the device.  On
         complexes with obstacle atoms the decoys of a group share the group's obstacles, and the clash that
         ranks them, the proximal stage and the recombination include the overlap with them.  ``batch``: a
@@ -415,7 +421,10 @@ class TDiffusionModule:
         ``select`` picks (None: decoy 0), at most ``recombine_sweeps`` sweeps; the returned angles are the recombined ones, and
         ``return_all`` keeps every key above as it is and adds ``recombined`` [1, sum of lengths, 4], ``pick`` int32 [sum of lengths]
         (the decoy every row was taken from), ``clash_trace`` fp64 [n_complexes, recombine_sweeps + 1], ``sweeps`` and ``converged``
-        int32 [n_complexes]."""
+        int32 [n_complexes].
+
+        ``sasa``: ``return_all`` gains ``bsa``, fp64 [n_complexes * n_decoys]: the surface every decoy buries
+        between its chains (``Context.sasa`` at the decoy's angles, ``seg_area[1] - seg_area[2]``).  Nothing else changes."""
         from .batch import replicate, replicate_many
         from .lib import SELECT
         if seed is None:
@@ -437,6 +446,8 @@ class TDiffusionModule:
         per_res = ctx.clash(chi, cfg.violation_tolerance_factor, cfg.clash_overlap_tolerance)
         res = ctx.ensemble_reduce(chi, packed.n_decoys, per_res=per_res, select=select)
         rec, extra = self._recombine(ctx, chi, int(packed.n_decoys), res, recombine_sweeps) if recombine else (None, {})
+        if sasa and return_all:
+            extra = dict(extra, bsa=self._decoy_bsa(ctx, chi))
         if not return_all:
             return rec.chi if recombine else res.chi_best
         return dict(decoys=(chi, packed), selected=res.chi_best, best=res.best, dev=res.dev, clash=res.clash, consensus=res.mean,
@@ -444,7 +455,7 @@ class TDiffusionModule:
 
     def repack_ensemble(self, batch, fixed_mask=None, *, n_decoys, seed, fixed_chi=None, fixed_mode="renoise",
                         use_proximal: bool = False, select="clash", return_all: bool = False, recombine: bool = False,
-                        recombine_sweeps: int = 64):
+                        recombine_sweeps: int = 64, sasa: bool = False):
         """``sample_ensemble`` under a pin: ``n_decoys`` seeded partial repackings of every complex in ONE packed
         pass, reduced on the device.  ``batch``: a B = 1 batch, or a list of complexes (per-complex data or B = 1 batches).  Every
         complex carries its ``fixed_mask`` (1 = keep; [1, L] on a B = 1 batch, [L] on per-complex data), or ``fixed_mask`` gives it:
@@ -457,7 +468,7 @@ class TDiffusionModule:
         with and without ``use_proximal``.  pp_ensemble_reduce is used unchanged: kept rows are identical in every decoy, so their
         ``resultant`` is 1 to rounding and they add (to rounding) nothing to ``dev``; they enter the per-decoy means of ``dev`` and
         ``clash`` with the same weight in all decoys of a group, so they dilute both equally and do not change the ranking.
-        Returns what ``sample_ensemble`` returns."""
+        Returns what ``sample_ensemble`` returns (``sasa``: the ``bsa`` key as there)."""
         from .batch import Batch, replicate_many
         from .lib import SELECT
         if select not in SELECT:
@@ -500,6 +511,8 @@ class TDiffusionModule:
         per_res = ctx.clash(chi, cfg.violation_tolerance_factor, cfg.clash_overlap_tolerance)
         res = ctx.ensemble_reduce(chi, D, per_res=per_res, select=select)
         rec, extra = self._recombine(ctx, chi, D, res, recombine_sweeps) if recombine else (None, {})
+        if sasa and return_all:
+            extra = dict(extra, bsa=self._decoy_bsa(ctx, chi))
         if not return_all:
             return rec.chi if recombine else res.chi_best
         return dict(decoys=(chi, packed), selected=res.chi_best, best=res.best, dev=res.dev, clash=res.clash, consensus=res.mean,
@@ -507,7 +520,7 @@ class TDiffusionModule:
 
     def mutate(self, proteins_and_mutations, *, seed, radius=10.0, shell="ca", n_decoys=1, use_proximal: bool = False,
                select="clash", fixed_mode="renoise", max_rows=200_000, log=print, recombine: bool = False,
-               recombine_sweeps: int = 64):
+               recombine_sweeps: int = 64, sasa: bool = False):
         """Mutant modelling: put each mutation set into its complex, repack what it touches, return the mutant.
         ``proteins_and_mutations``: a list of ``(protein dict, mutations)`` pairs, ``mutations`` a string ("RA47A,EA48A") or dicts as
         ``featurize.parse_mutstr`` returns them; several sets of one protein are repeated pairs.  Set i of the call gets the noise
@@ -532,7 +545,9 @@ class TDiffusionModule:
 
         A protein dict with an ``obstacles`` entry (``pdb_io.obstacle_atoms``) gives its sets those fixed
         atoms: the clash every stage reports and optimises -- the pinned proximal stage, the ranking, the recombination -- includes
-        the overlap with them.  The network and the shell rule do not see them."""
+        the overlap with them.  The network and the shell rule do not see them.
+
+        ``sasa``: every dict gains ``bsa`` fp64 [n_decoys], the surface each decoy buries between its chains."""
         from .batch import as_single, pack, unpack
         from .featurize import mutant_model_data, parse_mutstr
         from .functional import _ctx_for
@@ -584,7 +599,8 @@ class TDiffusionModule:
                 p["fixed_mask"] = fx
                 pinned.append(p)
             out = self.repack_ensemble(pinned, n_decoys=n_decoys, seed=seed, fixed_mode=fixed_mode, use_proximal=use_proximal,
-                                       select=select, return_all=True, recombine=recombine, recombine_sweeps=recombine_sweeps)
+                                       select=select, return_all=True, recombine=recombine, recombine_sweeps=recombine_sweeps,
+                                       sasa=sasa)
             final = out["recombined"] if recombine else out["selected"]
             pos = gctx.atom14(final)
             picks = unpack(pb, out["pick"].reshape(1, -1)) if recombine else [None] * len(members)
@@ -604,6 +620,8 @@ class TDiffusionModule:
                     if m != n:
                         pk = torch.cat([pk, out["best"][g].expand(1, n - m)], 1)
                     results[i].update(pick=pk, clash_recombined=out["clash_trace"][g, -1], rows_recombined=moved)
+                if sasa:
+                    results[i]["bsa"] = out["bsa"][g * n_decoys:(g + 1) * n_decoys]
         return results
 
     def sample_from(self, batch, SC_D_init, sde_noise=None):

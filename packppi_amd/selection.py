@@ -44,6 +44,36 @@ def parse_selection(spec: str, protein: Dict) -> np.ndarray:
     return mask
 
 
+DEVICE_SELECTORS = {"interface:sasa": "interface", "pocket": "pocket"}       # --repack words answered by Context.sasa
+
+
+def device_selector(spec, obstacles: str = "none"):
+    """"interface" / "pocket" if ``spec`` is one of the ``--repack`` words that ``sasa_selection`` answers ("interface:sasa",
+    "pocket"), else None (a residue list, or the file-based "interface").  ``obstacles``: the command line's ``--obstacles``
+    mode; "pocket" selects the rows whose surface the obstacle atoms bury, so without any it is refused (``ValueError``)."""
+    kind = DEVICE_SELECTORS.get(str(spec).strip()) if spec is not None else None
+    if kind == "pocket" and obstacles in (None, "none"):
+        raise ValueError("--repack pocket selects the residues whose surface the obstacle atoms bury: it needs --obstacles "
+                         "hetero or hetero+water")
+    return kind
+
+
+def sasa_selection(batch, kind: str, n_points: int = 96, probe: float = 1.4) -> np.ndarray:
+    """Row mask [L] (bool) of a B = 1 batch on the device, made there from the batch's own coordinates (``Context.sasa``, DESIGN.md
+    section 20; no PDB re-read): ``kind`` "interface" = the delta-SASA interface, rows with a test point that is exposed in the
+    isolated chain and buried in the complex (the rule of the reference's interface.py, which needs freesasa); "pocket" = rows
+    with a test point that only the batch's obstacle atoms bury.  ``ValueError`` if no row qualifies."""
+    from .functional import solvent_accessibility
+    if kind not in ("interface", "pocket"):
+        raise ValueError(f"kind must be 'interface' or 'pocket', got {kind!r}")
+    res = solvent_accessibility(batch, n_points=n_points, probe=probe)
+    mask = (res.interface if kind == "interface" else res.pocket)[0].cpu().numpy().astype(bool)
+    if not mask.any():
+        raise ValueError("no residue buries surface against another chain" if kind == "interface" else
+                         "no residue's surface is buried by an obstacle atom")
+    return mask
+
+
 def interface_selection(protein: Dict, pdb, radius: float = 10.0) -> np.ndarray:
     """Row mask [L] (bool) of the interface: residues with an atom within ``radius`` of another protein chain
     (``analysis.interface_residues`` on the file, matched by chain ID and file numbering).  ``ValueError`` if the file has fewer
