@@ -252,6 +252,41 @@ pp_status pp_sample_partial(pp_ctx *ctx, float *chi, const float *chi_ref, const
                             const float *schedule, int n_schedule, int mode, uint64_t seed,
                             float *chi_traj /* [n_schedule-1, B*L, 4] or NULL */, void *stream);
 
+/* ---- Clash-guided sampling (no reference counterpart) ------------------------------------------------
+ * pp_sample_seeded (chi_ref and fixed NULL) or pp_sample_partial (both given) with a gradient step on the clash loss between the
+ * network evaluations.  With n = n_schedule - 1 there are n + 1 nudge points: point j < n in front of evaluation j, point n behind
+ * the last reverse step.  At a point with eta[j] != 0, on the current angles x:
+ *   1. atom records at x, as pp_clash builds them;
+ *   2. G[r][k] = d/d chi_{r,k} of the sum over the rows i of r's segment of per_res_i(x): pp_clash's value and gradient in fp32
+ *      with its masks, exclusions and parameters and the obstacle term of a ctx that holds a set (pp_ctx_set_obstacles), the 1 / N
+ *      of its mean replaced by exactly 1 -- a row's weight is 1 / (nsc + 1e-10) whatever else the ctx holds.  No float atomics,
+ *      pp_clash's fixed summation order;
+ *   3. an entry (r, k) is movable iff it is in the 1pi or the 2pi periodic mask, SC_D_mask != 0, row r is not fixed and G is finite:
+ *      d = eta[j] * G;  d = fminf(fmaxf(d, -cap), cap);  x' = wrap_pi(x - d) * SC_D_mask, every operation rounded in fp32, wrap_pi
+ *      the reverse step's ((x + pi) mod 2 pi - pi, torch.remainder semantics).  Every other entry keeps its bits;
+ *   4. clash_trace[s][j] (if not NULL) = the fp64 sum of per_res over segment s at x -- BEFORE the step -- divided by the segment's
+ *      length, summed in a fixed tree: the scale of pp_ensemble_reduce's clash.  Entries with eta[j] == 0 are NaN: nothing is
+ *      computed there.
+ * Evaluation j and today's reverse step (ODE or SDE formula, the seeded in-kernel draws, the pin with either fix mode) then run
+ * from x'.  chi_traj[j] (DEVICE [n_schedule-1, N, 4] or NULL) is the state after reverse step j, in front of nudge j + 1; the
+ * returned chi includes nudge n.  Fixed rows are never nudged and end as chi_ref bit for bit; under PP_FIX_RENOISE a free row's
+ * gradient sees the fixed rows as they are at that moment.  With eta all zero the call gives the bits of pp_sample_seeded /
+ * pp_sample_partial and clash_trace is all NaN.
+ *   eta  HOST [n_schedule], read before the call returns;  cap > 0, INFINITY = no clamp.
+ * Cost: the static partner and obstacle candidate lists of the proximal loop are built once per call; a point with eta[j] == 0
+ * enqueues nothing; a nudge is two launches (reconstruction; clash + gradient + step in the residue's own workgroup) plus the node
+ * embedding launch of the next evaluation, which the evaluation in front of the nudge then does not fuse, plus one small launch
+ * for the trace when it is asked for.  Never waits for the stream, reads nothing back.  The call uses the proximal loop's
+ * workspaces: do not overlap it with pp_proximal* or pp_ensemble_recombine on the same ctx.
+ * PP_ERR_INVALID: a null ctx, chi, schedule or eta; only one of chi_ref and fixed; chi_ref == chi; an unknown mode or (with a pin)
+ * fix_mode; eta[j] negative or not finite; cap <= 0 or NaN; no pp_plan_set_clash_params before; a batch without atom_mask,
+ * residue_index, SC_D_mask or the periodic masks; a padded B > 1 ctx; a geometry-only plan. */
+pp_status pp_sample_guided(pp_ctx *ctx, float *chi, const float *chi_ref /* or NULL */,
+                           const uint8_t *fixed /* or NULL: both or neither */, int fix_mode, const float *schedule,
+                           int n_schedule, int mode, uint64_t seed, const float *eta /* HOST [n_schedule] */, float cap,
+                           float *chi_traj /* DEVICE [n_schedule-1,N,4] or NULL */,
+                           double *clash_trace /* DEVICE [n_seg][n_schedule] or NULL */, void *stream);
+
 /* Replaces get_atom14_coords(X, S, BB_D, SC_D) (components/__init__.py:76-120). xyz [B,L,14,3]. */
 pp_status pp_atom14(pp_ctx *ctx, const float *chi, float *xyz, void *stream);
 
@@ -517,7 +552,8 @@ pp_status pp_time_kernel(pp_ctx *ctx, int which, int iters, float *avg_ms, void 
 
 /* Measurement aid, no reference counterpart: in-situ duration of a hot kernel.  After
  * pp_profile_kernel(ctx, which) (0 node message, 1 edge update, 2 node update; 3 the one launch per Adam step
- * inside pp_proximal / pp_proximal_packed: clash loss + gradient, the step, the reconstruction at the new angles) every launch of that
+ * inside pp_proximal / pp_proximal_packed: clash loss + gradient, the step, the reconstruction at the new angles; 4, 5, 6 the
+ * launches of a nudge of pp_sample_guided: reconstruction, clash loss + gradient + step, the node embedding behind it) every launch of that
  * kernel made by pp_score / pp_sample / pp_proximal carries a start / stop HIP event pair on the launch stream
  * (hipExtLaunchKernelGGL: the dispatch's own begin and end, the interval rocprofv3's kernel trace reports);
  * pp_profile_read waits for the last one, returns the summed intervals (ms) and the number of

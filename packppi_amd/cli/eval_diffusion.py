@@ -32,6 +32,12 @@ Waals radii, heavy atoms, probe 1.4 A, 96 points): they are not freesasa's numbe
 --repack interface:sasa selects the delta-SASA interface of the input structure -- residues with surface that is exposed in the
 isolated chain and buried in the complex, the reference's interface.py rule -- on the device, without reading the file again;
 --repack pocket selects the residues whose surface the obstacle atoms bury and needs --obstacles other than none.
+--guide SCALE [--guide_schedule late|constant] [--guide_from T] [--guide_cap RAD] (without --guide every output
+byte as before): clash-guided sampling -- between the network evaluations the angles take a gradient step of size SCALE on the clash
+loss, obstacle atoms included, at most RAD radians per angle, from time T of the schedule on (late) or at every step (constant).  The
+defaults (0.02, late from 0.3, 0.1 rad) are starting values, not tuned against a trained checkpoint.  Combines with --repack,
+--n_decoys and --use_proximal; needs --seed with --repack and in sde mode.  Writes guide.csv (complex or decoy, nudge point, t, eta,
+mean clash in front of that nudge; empty where no nudge runs) and prints the first and last traced clash.
 """
 import argparse
 import os
@@ -67,12 +73,68 @@ def load_model(args):
     return model.eval()
 
 
+def add_guide_arguments(p):
+    """--guide and its companions.  Their defaults are SUPPRESSed: without the flags the namespace is what it was before them."""
+    S = argparse.SUPPRESS
+    p.add_argument("--guide", type=float, default=S, metavar="SCALE", help="Clash-guided sampling (DESIGN.md section 21): the step size "
+                   "of the gradient step on the clash loss (obstacle atoms included) between the network evaluations; 0.02 is the "
+                   "starting value the CPU oracle suggests, not a tuned one. Writes guide.csv.")
+    p.add_argument("--guide_schedule", choices=("late", "constant"), default=S, help="With --guide: nudge from --guide_from on (late, "
+                   "default) or at every step (constant).")
+    p.add_argument("--guide_from", type=float, default=S, metavar="T", help="With --guide_schedule late: nudge where the schedule's "
+                   "time is at most T (default 0.3).")
+    p.add_argument("--guide_cap", type=float, default=S, metavar="RAD", help="With --guide: the largest step of one angle at one "
+                   "nudge, in radians (default 0.1).")
+
+
+def guide_from_args(args, p=None):
+    """The ``guide`` dict of ``TDiffusionModule.sampling`` from the command line, None without --guide."""
+    given = [k for k in ("guide_schedule", "guide_from", "guide_cap") if hasattr(args, k)]
+    if not hasattr(args, "guide"):
+        if given and p is not None:
+            p.error("--" + given[0] + " belongs to --guide")
+        return None
+    g = dict(scale=args.guide)
+    for key, name in (("guide_schedule", "kind"), ("guide_from", "t_on"), ("guide_cap", "cap")):
+        if hasattr(args, key):
+            g[name] = getattr(args, key)
+    if p is not None:
+        if not (np.isfinite(g["scale"]) and g["scale"] >= 0):
+            p.error("--guide must be a finite, non-negative step size")
+        if "cap" in g and not g["cap"] > 0:
+            p.error("--guide_cap must be positive")
+    return g
+
+
+def write_guide_csv(model, outdir):
+    """guide.csv from the traces the guided runs left in ``model.guide_traces``: one line per (complex or decoy, nudge point)."""
+    sched = [float(t) for t in model.schedule]
+    rows, n = ["complex,nudge_point,t,eta,mean_clash"], 0
+    first = last = None
+    for eta, trace in model.guide_traces:
+        for seg in trace.cpu().tolist():
+            for j, (t, e, c) in enumerate(zip(sched, eta.tolist(), seg)):
+                rows.append(f"{n},{j},{t!r},{e!r}," + ("" if c != c else repr(c)))
+            traced = [c for c in seg if c == c]
+            if traced and first is None:
+                first = traced[0]
+            if traced:
+                last = traced[-1]
+            n += 1
+    with open(os.path.join(outdir, "guide.csv"), "w") as fh:
+        fh.write("\n".join(rows) + "\n")
+    if first is not None:
+        print(f"----- guide: mean clash in front of the first nudge {first:.4f}, in front of the last {last:.4f} -----")
+    else:
+        print("----- guide: no nudge ran (every eta is 0) -----")
+
+
 def write_ensemble(model, batch, protein, args, analysis):
     """--n_decoys: sample, write every decoy, the two tables and the selected decoy; returns the selected angles [1, L, 4]."""
     from .. import constants as rc
     kw = dict(recombine=True, recombine_sweeps=args.recombine_sweeps) if args.recombine else {}
     out = model.sample_ensemble(batch, args.n_decoys, seed=args.seed, use_proximal=args.use_proximal, select=args.select,
-                                return_all=True, **kw, **(dict(sasa=True) if args.sasa else {}))
+                                return_all=True, **kw, **(dict(sasa=True) if args.sasa else {}), **args.guide_kw)
     chi, packed = out["decoys"]
     best = int(out["best"][0])
     dev, clash = out["dev"].cpu().tolist(), out["clash"].cpu().tolist()
@@ -191,6 +253,9 @@ def evaluate_model(model, args):
         torch.manual_seed(args.seed)
     # --seed: the initial noise and the sde noise come from the counter-based device generator (module.sampling(seed=...)): the
     # same seed gives the same structure on any device, shard layout and torch version
+    guide = guide_from_args(args)
+    args.guide_kw = dict(guide=guide) if guide is not None else {}
+    model.keep_guide_trace = guide is not None
     fixed = None
     if args.repack is not None:
         from ..selection import device_selector, interface_selection, parse_selection, sasa_selection
@@ -204,9 +269,12 @@ def evaluate_model(model, args):
     if args.n_decoys is not None:
         SC_D_sample = write_ensemble(model, batch, protein, args, analysis)
     elif fixed is not None:
-        SC_D_sample = model.repack(batch, fixed, seed=args.seed, fixed_mode=args.fixed_mode, use_proximal=args.use_proximal)
+        SC_D_sample = model.repack(batch, fixed, seed=args.seed, fixed_mode=args.fixed_mode, use_proximal=args.use_proximal,
+                                   **args.guide_kw)
     else:
-        SC_D_sample = model.sampling(batch, use_proximal=args.use_proximal, seed=args.seed)
+        SC_D_sample = model.sampling(batch, use_proximal=args.use_proximal, seed=args.seed, **args.guide_kw)
+    if guide is not None:
+        write_guide_csv(model, args.outdir)
     if model.saturated() & 4:
         print("----- WARNING: NaN / infinity in the input coordinates or angles: the reference would return NaN here -----")
     if model.saturated() & 3:
@@ -264,6 +332,7 @@ def build_parser():
                    "atoms, the buried interface area and the exposure; with --n_decoys ensemble.csv gains the column bsa. "
                    "--repack also takes interface:sasa (the delta-SASA interface of the input, made on the device) and pocket "
                    "(residues whose surface the obstacle atoms bury; needs --obstacles).")
+    add_guide_arguments(p)
     return p
 
 
@@ -288,6 +357,7 @@ def parse_args(argv=None):
         p.error("--recombine needs --n_decoys (it recombines the decoys of an ensemble)")
     if args.recombine_sweeps < 0:
         p.error("--recombine_sweeps must not be negative")
+    guide_from_args(args, p)
     return args
 
 

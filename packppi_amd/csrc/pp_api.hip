@@ -710,10 +710,19 @@ struct PartialArgs {
     float *chi_traj;           // [n_schedule - 1][N][4] or null
 };
 
-// pp_sample, pp_sample_seeded and pp_sample_partial (`who` names the export in messages; rng: the reverse steps draw their own sde
-// noise; part: fixed rows are pinned inside the reverse step)
+// what pp_sample_guided adds to a sampling run
+struct GuideArgs {
+    const float *eta;          // HOST [n_schedule]: the step size of nudge point j, 0 = no nudge there
+    float cap;                 // largest |step| of one angle at one nudge
+    float *chi_traj;           // [n_schedule - 1][N][4] or null: a run without a pin has no stepping lane that writes it (copied)
+    double *trace;             // [B][n_schedule] or null
+};
+
+// pp_sample, pp_sample_seeded, pp_sample_partial and pp_sample_guided (`who` names the export in messages; rng: the reverse steps
+// draw their own sde noise; part: fixed rows are pinned inside the reverse step; guide: nudges between the evaluations)
 static pp_status sample_impl(const char *who, pp_ctx *c, float *chi, const float *schedule, int n_schedule, int mode,
-                             const float *sde_noise, const PPRng *rng, hipStream_t s, const PartialArgs *part = nullptr);
+                             const float *sde_noise, const PPRng *rng, hipStream_t s, const PartialArgs *part = nullptr,
+                             const GuideArgs *guide = nullptr);
 
 extern "C" pp_status pp_sample(pp_ctx *c, float *chi, const float *schedule, int n_schedule, int mode,
                                const float *sde_noise, void *stream) {
@@ -753,8 +762,49 @@ extern "C" pp_status pp_sample_partial(pp_ctx *c, float *chi, const float *chi_r
     return sample_impl("pp_sample_partial", c, chi, schedule, n_schedule, mode, nullptr, &rng, s, &part);
 }
 
+// ---- clash-guided sampling -----------------------------------------------------------------------------------
+extern "C" pp_status pp_sample_guided(pp_ctx *c, float *chi, const float *chi_ref, const uint8_t *fixed, int fix_mode,
+                                      const float *schedule, int n_schedule, int mode, uint64_t seed, const float *eta, float cap,
+                                      float *chi_traj, double *clash_trace, void *stream) {
+    if (c) c->last_stream = static_cast<hipStream_t>(stream);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (!c) FAIL(PP_ERR_INVALID, "pp_sample_guided: null ctx");
+    if (!chi) FAIL(PP_ERR_INVALID, "pp_sample_guided: null chi");
+    if (!schedule) FAIL(PP_ERR_INVALID, "pp_sample_guided: null schedule");
+    if (!eta) FAIL(PP_ERR_INVALID, "pp_sample_guided: null eta");
+    if ((chi_ref == nullptr) != (fixed == nullptr))
+        FAIL(PP_ERR_INVALID, "pp_sample_guided: chi_ref and fixed must be given together (both, or neither for a run without a pin)");
+    if (chi_ref && chi_ref == chi) FAIL(PP_ERR_INVALID, "pp_sample_guided: chi_ref and chi must be distinct buffers");
+    if (fixed && fix_mode != PP_FIX_HOLD && fix_mode != PP_FIX_RENOISE) FAIL(PP_ERR_INVALID, "pp_sample_guided: unknown fix_mode");
+    if (mode != PP_MODE_ODE && mode != PP_MODE_SDE) FAIL(PP_ERR_INVALID, "pp_sample_guided: unknown mode");
+    if (n_schedule < 2) FAIL(PP_ERR_INVALID, "pp_sample_guided: schedule needs at least 2 times");
+    for (int j = 0; j < n_schedule; j++)
+        if (!(eta[j] >= 0.f) || std::isinf(eta[j]))
+            FAIL(PP_ERR_INVALID, "pp_sample_guided: eta[" + std::to_string(j) + "] must be finite and not negative");
+    if (!(cap > 0.f)) FAIL(PP_ERR_INVALID, "pp_sample_guided: cap must be positive (INFINITY = no clamp)");
+    if (!c->plan->has_network) FAIL(PP_ERR_INVALID, "pp_sample_guided: plan was created without network weights (a geometry-only plan)");
+    if (!c->plan->clash_params_set) FAIL(PP_ERR_INVALID, "pp_sample_guided: call pp_plan_set_clash_params first");
+    if (!c->b.atom_mask || !c->b.residue_index) FAIL(PP_ERR_INVALID, "pp_sample_guided: batch lacks atom_mask / residue_index");
+    if (!c->b.SC_D_mask || !c->b.chi_1pi_periodic_mask || !c->b.chi_2pi_periodic_mask)
+        FAIL(PP_ERR_INVALID, "pp_sample_guided: batch lacks SC_D_mask / the periodic masks");
+    if (!c->packed && c->B != 1)
+        FAIL(PP_ERR_INVALID, "pp_sample_guided: needs a context from pp_complex_prepare_packed (or a B = 1 one), not a padded B > 1 batch");
+    PP_HIP_CHECK(hipSetDevice(c->plan->device));
+    pp_status st;
+    PPRng rng = {nullptr, 0u, 0u};
+    const bool seeded = fixed != nullptr || mode == PP_MODE_SDE;          // ode without a pin draws nothing: pp_sample's instances
+    if (seeded) {
+        if ((st = rng_table_ready(c, s)) != PP_OK) return st;
+        rng = {c->rng_tab, (uint32_t)seed, (uint32_t)(seed >> 32)};
+    }
+    const PartialArgs part = {chi_ref, fixed, fix_mode, chi_traj};
+    const GuideArgs guide = {eta, cap, chi_traj, clash_trace};
+    return sample_impl("pp_sample_guided", c, chi, schedule, n_schedule, mode, nullptr, seeded ? &rng : nullptr, s,
+                       fixed ? &part : nullptr, &guide);
+}
+
 static pp_status sample_impl(const char *who, pp_ctx *c, float *chi, const float *schedule, int n_schedule, int mode,
-                             const float *sde_noise, const PPRng *rng, hipStream_t s, const PartialArgs *part) {
+                             const float *sde_noise, const PPRng *rng, hipStream_t s, const PartialArgs *part, const GuideArgs *guide) {
     const std::string w(who);
     if (!c || !chi || !schedule) FAIL(PP_ERR_INVALID, w + ": null argument");
     if (!c->plan->has_network) FAIL(PP_ERR_INVALID, w + ": plan was created without network weights");
@@ -770,7 +820,24 @@ static pp_status sample_impl(const char *who, pp_ctx *c, float *chi, const float
     // (A hipGraph replay of the loop was measured and dropped: with no stray event records in the stream the kernel
     // trace shows back-to-back dispatches, and capture + replay was 2 % slower than plain launches.)
     flag_nonfinite(c, chi, 4, 4, s);
-    if ((st = pp_launch_node_embed(c, chi, steps[0], s)) != PP_OK) return st;
+    // Guided run: nudge point j < nsteps sits in front of evaluation j, nudge point nsteps behind the last reverse step.  A point with
+    // eta == 0 enqueues nothing: the evaluation in front of it keeps its fused next-step embedding.  An evaluation followed by a nudge
+    // drops it (next = nullptr): the angles the next evaluation embeds exist only behind the nudge, which the embedding launch follows.
+    auto nudge_at = [&](int j) { return guide != nullptr && guide->eta[j] != 0.f; };
+    auto nudge = [&](int j) {
+        return pp_launch_guide_nudge(c, chi, part ? part->fixed : nullptr, guide->eta[j], guide->cap, guide->trace, n_schedule, j, s);
+    };
+    if (guide) {
+        if (guide->trace) PP_HIP_CHECK(hipMemsetAsync(guide->trace, 0xff, (size_t)c->B * n_schedule * sizeof(double), s));   // NaN
+        bool any = false;
+        for (int j = 0; j <= nsteps; j++) any = any || guide->eta[j] != 0.f;
+        if (any && (st = pp_launch_guide_begin(c, s)) != PP_OK) return st;
+        if (nudge_at(0) && (st = nudge(0)) != PP_OK) return st;
+    }
+    if (nudge_at(0)) prof_arm(c, 6);          // pp_profile_kernel(6): the embedding launch behind a nudge
+    st = pp_launch_node_embed(c, chi, steps[0], s);
+    prof_disarm(c);
+    if (st != PP_OK) return st;
     static const bool dbg = PP_GETENV("PP_DEBUG") != nullptr;
     const auto h0 = std::chrono::steady_clock::now();
     // the live rows of this run: the context's, or without the call's fixed rows (made here, on the stream).  The in-situ timing
@@ -794,8 +861,22 @@ static pp_status sample_impl(const char *who, pp_ctx *c, float *chi, const float
             pin.sigma = sigma_f32(schedule[j + 1]);
             pin.renoise = part->fix_mode == PP_FIX_RENOISE && j + 1 < nsteps ? 1 : 0;
         }
-        if ((st = run_network(c, s, j, PP_NU_STEP, chi, mode, sde_noise, &steps[j], j + 1 < nsteps ? &steps[j + 1] : nullptr, rng,
-                              part ? &pin : nullptr, use_live ? &live : nullptr)) != PP_OK) return st;
+        const bool then_nudge = nudge_at(j + 1);
+        if ((st = run_network(c, s, j, PP_NU_STEP, chi, mode, sde_noise, &steps[j],
+                              j + 1 < nsteps && !then_nudge ? &steps[j + 1] : nullptr, rng, part ? &pin : nullptr,
+                              use_live ? &live : nullptr)) != PP_OK) return st;
+        if (guide && guide->chi_traj && !part)
+            PP_HIP_CHECK(hipMemcpyAsync(guide->chi_traj + (size_t)j * c->N * 4, chi, (size_t)c->N * 4 * sizeof(float),
+                                        hipMemcpyDeviceToDevice, s));
+        if (then_nudge) {
+            if ((st = nudge(j + 1)) != PP_OK) return st;
+            if (j + 1 < nsteps) {
+                prof_arm(c, 6);
+                st = pp_launch_node_embed(c, chi, steps[j + 1], s);
+                prof_disarm(c);
+                if (st != PP_OK) return st;
+            }
+        }
     }
     if (dbg) {
         const double us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - h0).count();
@@ -1023,8 +1104,8 @@ extern "C" pp_status pp_debug_score_prefix(pp_ctx *c, const float *chi, float t,
 // dispatch's own begin and end timestamps);
 // pp_profile_read synchronises, sums the pair intervals, reports (total ms, launches) and switches profiling off.
 extern "C" pp_status pp_profile_kernel(pp_ctx *c, int which) {
-    if (!c || which < 0 || which > 3)
-        FAIL(PP_ERR_INVALID, "pp_profile_kernel: which must be 0 (node message), 1 (edge update), 2 (node update) or 3 (the Adam-step launch of pp_proximal / pp_proximal_packed / pp_proximal_pinned: clash + gradient + step + reconstruction)");
+    if (!c || which < 0 || which > 6)
+        FAIL(PP_ERR_INVALID, "pp_profile_kernel: which must be 0 (node message), 1 (edge update), 2 (node update), 3 (the Adam-step launch of pp_proximal / pp_proximal_packed / pp_proximal_pinned: clash + gradient + step + reconstruction) or 4, 5, 6 (the launches of a nudge of pp_sample_guided: reconstruction, clash + gradient + step, node embedding)");
     c->prof_which = which;
     c->prof_n = 0;
     return PP_OK;

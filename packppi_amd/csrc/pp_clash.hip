@@ -299,13 +299,28 @@ struct ClashObst {
     const int32_t *cand_cnt;      // [N] their number, -1: scan
 };
 #define CL_OB_Q (CL_MAXC / 4)     // obstacle indices one stripe holds in LDS before the wave works them off
-template <bool CAND, bool FUSE, bool OBST>
+// NUDGE (pp_sample_guided): the gradient step of clash-guided sampling in the tail of the residue's own workgroup,
+// where dchi[i] is final, as the fused Adam step sits there.  Launched without FUSE and with inv_ntot = 1: dk[k] is then the derivative
+// of the sum of per_res over the rows of the residue's segment by chi_k of row i, a row's weight 1 / (nsc + 1e-10) whatever else is
+// packed.  Lane k < 4 of wave 0 owns (i, k): a movable entry -- in a periodic mask, SC_D_mask != 0, row not fixed, gradient finite --
+// takes d = clamp(eta * dk, -cap, cap) and chi = wrap_pi(chi - d) * SC_D_mask, every operation rounded on its own, wrap_pi the reverse
+// step's; every other entry is not written.  chi is read by no workgroup of this launch (they read the records k_atom14 made of
+// it), so the step is in place.  The NUDGE = false instances do not read G and are, to the instruction, the kernels of before
+// (profiles/r21_guided_isa.txt).
+struct ClashNudge {
+    float *chi;                       // [N][4] stepped in place
+    const float *sc_mask;             // [N][4]
+    const uint8_t *m1pi, *m2pi;       // [N][4]
+    const uint8_t *fixed;             // [N] rows that are never nudged, or nullptr
+    float eta, cap;
+};
+template <bool CAND, bool FUSE, bool OBST, bool NUDGE = false>
 __global__ void __launch_bounds__(64 * CL_WAVES)
 k_clash(int N, const int2 *__restrict__ seg, const float *__restrict__ xyz, const float4 *__restrict__ rec, const float *__restrict__ exists,
         const float *__restrict__ lower, const float *__restrict__ upper, const int32_t *__restrict__ a2g,
         const float *__restrict__ axes, float tol, float inv_ntot,
         float *__restrict__ per_res, float *__restrict__ dchi, const int32_t *__restrict__ cand, const int32_t *__restrict__ cand_cnt,
-        ClashFuse F, ClashObst O) {
+        ClashFuse F, ClashObst O, ClashNudge G) {
     __shared__ int s_list[CL_WAVES][CL_MAXC];
     __shared__ float s_red[CL_WAVES][16][4];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -531,7 +546,7 @@ k_clash(int N, const int2 *__restrict__ seg, const float *__restrict__ xyz, cons
     const float pres = lres / (nsc + 1e-10f);
     if (lane == 0) per_res[i] = pres;
     float dk[4] = {0.f, 0.f, 0.f, 0.f};
-    if (dchi || FUSE) {
+    if (dchi || FUSE || NUDGE) {
         if (own && a >= 5) {
             const int g = a2g[S * 14 + a];
 #pragma unroll
@@ -549,6 +564,23 @@ k_clash(int N, const int2 *__restrict__ seg, const float *__restrict__ xyz, cons
             for (int o = 8; o > 0; o >>= 1) dk[k] += __shfl_xor(dk[k], o);
         }
         if (dchi && lane < 4) dchi[(size_t)i * 4 + lane] = lane == 0 ? dk[0] : (lane == 1 ? dk[1] : (lane == 2 ? dk[2] : dk[3]));
+    }
+    if constexpr (NUDGE) {
+        if (lane < 4) {
+#pragma clang fp contract(off)
+            const size_t e = (size_t)i * 4 + lane;
+            const float g = lane == 0 ? dk[0] : (lane == 1 ? dk[1] : (lane == 2 ? dk[2] : dk[3]));
+            const float scm = G.sc_mask[e];
+            const bool periodic = (G.m1pi[e] | G.m2pi[e]) != 0;
+            const bool pinned = G.fixed != nullptr && G.fixed[i] != 0;
+            const bool finite = __builtin_fabsf(g) <= 3.402823466e38f;          // false for NaN and the infinities
+            if (periodic && scm != 0.f && !pinned && finite) {
+                float d = G.eta * g;
+                d = fminf(fmaxf(d, -G.cap), G.cap);
+                const float x = G.chi[e];
+                G.chi[e] = pp_wrap_pi(x - d) * scm;
+            }
+        }
     }
     if constexpr (FUSE) {
         const ProxUpd &U = F.U;
@@ -787,9 +819,9 @@ pp_status pp_launch_atom14(pp_ctx *c, const float *chi, float *xyz, hipStream_t 
     const pp_plan *p = c->plan;
     // the packed records feed k_clash; they need the residue numbering, which geometry-only batches may not carry
     float4 *rec = c->b.residue_index ? reinterpret_cast<float4 *>(c->rec) : nullptr;
-    hipLaunchKernelGGL(k_atom14, dim3((c->N + 15) / 16), dim3(256), 0, s, c->N, c->b.X, c->b.residue_type, c->b.BB_D, chi,
-                       p->default_frames, p->atom14_to_group, p->atom14_mask, p->lit_positions, c->b.atom_mask,
-                       p->between_radius, c->b.residue_index, xyz, c->axes, c->brad, rec);
+    PP_LAUNCH(c, k_atom14, dim3((c->N + 15) / 16), dim3(256), 0, s, c->N, c->b.X, c->b.residue_type, c->b.BB_D, chi,
+              p->default_frames, p->atom14_to_group, p->atom14_mask, p->lit_positions, c->b.atom_mask,
+              p->between_radius, c->b.residue_index, xyz, c->axes, c->brad, rec);
     PP_HIP_CHECK(hipGetLastError());
     return PP_OK;
 }
@@ -804,27 +836,33 @@ static ClashObst clash_obst(const pp_ctx *c, bool cands) {
 }
 
 // THE k_clash launch: (cands, fuse, obst) -> the instance, the argument list written once.  cands: the static lists of the context
-// (k_clash_cand); F is read by the FUSE instances only, O by the OBST ones; inv_ntot by the instances without FUSE.
+// (k_clash_cand); F is read by the FUSE instances only, O by the OBST ones; inv_ntot by the instances without FUSE.  nudge (not null:
+// pp_sample_guided; never with fuse): the NUDGE instances, which alone read it.
 static void launch_k_clash(pp_ctx *c, bool cands, bool fuse, bool obst, const float *xyz, const float *rec, const float *axes,
-                           float inv_ntot, float *per_res, float *dchi, const ClashFuse &F, const ClashObst &O, hipStream_t s) {
+                           float inv_ntot, float *per_res, float *dchi, const ClashFuse &F, const ClashObst &O, hipStream_t s,
+                           const ClashNudge *nudge = nullptr) {
     const pp_plan *p = c->plan;
-    auto go = [&](auto cand_c, auto fuse_c, auto obst_c) {
-        PP_LAUNCH(c, (k_clash<decltype(cand_c)::value, decltype(fuse_c)::value, decltype(obst_c)::value>), dim3(c->N),
-                  dim3(64 * CL_WAVES), 0, s, c->N, c->seg, xyz, reinterpret_cast<const float4 *>(rec), c->b.atom_mask, p->bounds_lower,
-                  p->bounds_upper, p->atom14_to_group, axes, p->clash_tol, inv_ntot, per_res, dchi, cands ? c->cand : nullptr,
-                  cands ? c->cand_cnt : nullptr, F, O);
+    auto go = [&](auto cand_c, auto fuse_c, auto obst_c, auto nudge_c) {
+        PP_LAUNCH(c, (k_clash<decltype(cand_c)::value, decltype(fuse_c)::value, decltype(obst_c)::value, decltype(nudge_c)::value>),
+                  dim3(c->N), dim3(64 * CL_WAVES), 0, s, c->N, c->seg, xyz, reinterpret_cast<const float4 *>(rec), c->b.atom_mask,
+                  p->bounds_lower, p->bounds_upper, p->atom14_to_group, axes, p->clash_tol, inv_ntot, per_res, dchi,
+                  cands ? c->cand : nullptr, cands ? c->cand_cnt : nullptr, F, O, nudge ? *nudge : ClashNudge{});
     };
     const std::true_type y;
     const std::false_type n;
+    if (nudge) {          // always on the static lists (pp_launch_guide_begin), never fused: two instances
+        if (obst) go(y, n, y, y); else go(y, n, n, y);
+        return;
+    }
     switch (4 * cands + 2 * fuse + obst) {
-        case 0: go(n, n, n); break;
-        case 1: go(n, n, y); break;
-        case 2: go(n, y, n); break;
-        case 3: go(n, y, y); break;
-        case 4: go(y, n, n); break;
-        case 5: go(y, n, y); break;
-        case 6: go(y, y, n); break;
-        default: go(y, y, y); break;
+        case 0: go(n, n, n, n); break;
+        case 1: go(n, n, y, n); break;
+        case 2: go(n, y, n, n); break;
+        case 3: go(n, y, y, n); break;
+        case 4: go(y, n, n, n); break;
+        case 5: go(y, n, y, n); break;
+        case 6: go(y, y, n, n); break;
+        default: go(y, y, y, n); break;
     }
 }
 
@@ -916,6 +954,67 @@ pp_status pp_launch_proximal_packed(pp_ctx *c, const float *chi, float lamda, in
     if (st != PP_OK) return st;
     hipLaunchKernelGGL(k_prox_accept, dim3((c->L * 4 + 255) / 256, c->B), dim3(256), 0, s, c->N, c->seg_off,
                        losses, nsteps, chi, chi_last, chi_accepted);
+    PP_HIP_CHECK(hipGetLastError());
+    return PP_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// clash-guided sampling (pp_sample_guided): the nudge between two network evaluations
+// ---------------------------------------------------------------------------------------------
+// trace[s][j] (row stride n_schedule) = the fp64 sum of per_res over the rows of segment s = blockIdx.x, divided by its length: lane
+// tid takes rows tid, tid + 256 ... counted from the segment's first, the 256 partial sums meet in a binary tree in LDS (the
+// pattern and the scale of k_ens_per_decoy's clash): a segment gets the same bits alone and packed, and two runs agree.
+__global__ void __launch_bounds__(256)
+k_guide_trace(int N, const int32_t *__restrict__ off, const float *__restrict__ per_res, int n_schedule, int j,
+              double *__restrict__ trace) {
+#pragma clang fp contract(off)
+    __shared__ double red[256];
+    const int s = blockIdx.x, tid = threadIdx.x;
+    int a, b;
+    pp_seg_rows(off, s, N, a, b);
+    double sc = 0.0;
+    for (int n = a + tid; n < b; n += 256) sc += (double)per_res[n];
+    red[tid] = sc;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if (tid < w) red[tid] += red[tid + w];
+        __syncthreads();
+    }
+    if (tid == 0) trace[(size_t)s * n_schedule + j] = red[0] / (double)(b - a > 0 ? b - a : 1);
+}
+
+// once per pp_sample_guided: the static partner lists and obstacle candidates of the proximal loop (the backbone does not move
+// during sampling either)
+pp_status pp_launch_guide_begin(pp_ctx *c, hipStream_t s) {
+    const pp_plan *p = c->plan;
+    hipLaunchKernelGGL(k_clash_cand, dim3(c->N), dim3(64 * CL_WAVES), 0, s, c->N, c->seg, c->b.X, c->b.atom_mask, c->b.residue_type,
+                       c->b.residue_index, p->side_extent, p->clash_tol, c->cand, c->cand_cnt);
+    if (c->obst_M > 0)
+        hipLaunchKernelGGL(k_obst_cand, dim3((c->N + 3) / 4), dim3(256), 0, s, c->N, c->b.X, c->b.atom_mask, c->b.residue_type,
+                           p->side_extent, p->clash_tol, c->obst, c->obst_row, c->obst_cand, c->obst_cnt);
+    PP_HIP_CHECK(hipGetLastError());
+    return PP_OK;
+}
+
+// One nudge at `chi`, in place: reconstruction, then clash + gradient + step in one launch; trace (or null) receives the mean clash
+// of every segment BEFORE the step at column j.  Two launches, three with the trace.
+pp_status pp_launch_guide_nudge(pp_ctx *c, float *chi, const uint8_t *fixed, float eta, float cap, double *trace, int n_schedule,
+                                int j, hipStream_t s) {
+    pp_status st;
+    c->prof_armed = c->prof_which == 4;          // pp_profile_kernel(4): the reconstruction of a nudge; (5): its clash + step launch
+    st = pp_launch_atom14(c, chi, c->xyz, s);
+    c->prof_armed = false;
+    if (st != PP_OK) return st;
+    const bool obst = c->obst_M > 0;
+    ClashNudge G;
+    G.chi = chi; G.sc_mask = c->b.SC_D_mask; G.m1pi = c->b.chi_1pi_periodic_mask; G.m2pi = c->b.chi_2pi_periodic_mask;
+    G.fixed = fixed; G.eta = eta; G.cap = cap;
+    c->prof_armed = c->prof_which == 5;
+    launch_k_clash(c, true, false, obst, c->xyz, c->rec, c->axes, 1.0f, c->per_res, nullptr, ClashFuse{},
+                   obst ? clash_obst(c, true) : ClashObst{}, s, &G);
+    c->prof_armed = false;
+    if (trace)
+        hipLaunchKernelGGL(k_guide_trace, dim3(c->B), dim3(256), 0, s, c->N, c->seg_off, c->per_res, n_schedule, j, trace);
     PP_HIP_CHECK(hipGetLastError());
     return PP_OK;
 }

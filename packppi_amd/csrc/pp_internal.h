@@ -404,6 +404,14 @@ pp_status pp_launch_proximal_packed(pp_ctx *c, const float *chi, float lamda, in
                                     float *chi_last, float *chi_accepted, float *losses, hipStream_t s,
                                     const uint8_t *fixed = nullptr, uint8_t *moved = nullptr);
 
+// pp_sample_guided (pp_clash.hip).  begin: the static partner lists and obstacle candidates, once per call.
+// nudge: chi stepped in place against the clash gradient at chi (rows of `fixed`, device [N] or null, are left alone); trace
+// (device [B][n_schedule] or null) receives every segment's mean clash before the step at column j.  They use the proximal loop's
+// workspaces (cand, obst_cand, xyz, rec, axes, per_res).
+pp_status pp_launch_guide_begin(pp_ctx *c, hipStream_t s);
+pp_status pp_launch_guide_nudge(pp_ctx *c, float *chi, const uint8_t *fixed, float eta, float cap, double *trace, int n_schedule,
+                                int j, hipStream_t s);
+
 void pp_edge_occupancy(int *node_msg, int *edge_upd);
 
 // last_mode values for pp_launch_node_update

@@ -1390,7 +1390,7 @@ pp_status pp_launch_node_embed(pp_ctx *c, const float *chi, const StepParams &sp
     if (st != PP_OK) return st;
     NodeArgs A = make_args(c);
     PreW pre0 = make_pre(c->plan, 0, false);
-    hipLaunchKernelGGL(k_node_embed, dim3((c->N + NB - 1) / NB), dim3(NT), sizeof(Smem), s, A, pre0, chi, sp);
+    PP_LAUNCH(c, k_node_embed, dim3((c->N + NB - 1) / NB), dim3(NT), sizeof(Smem), s, A, pre0, chi, sp);
     PP_HIP_CHECK(hipGetLastError());
     return PP_OK;
 }

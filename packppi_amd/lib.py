@@ -22,7 +22,7 @@ SYMBOLS = ("pp_version", "pp_last_error", "pp_build_id", "pp_plan_set_knn_ties",
            "pp_score_rows", "pp_so2_set_grids", "pp_so2_score", "pp_dsm_loss",
            "pp_ctx_set_rng_keys", "pp_noise_seeded", "pp_add_noise_seeded", "pp_sample_seeded",
            "pp_sample_partial", "pp_proximal_pinned", "pp_ctx_live_rows", "pp_ensemble_reduce", "pp_ctx_shell",
-           "pp_ensemble_recombine", "pp_ctx_set_obstacles", "pp_sasa")
+           "pp_ensemble_recombine", "pp_ctx_set_obstacles", "pp_sasa", "pp_sample_guided")
 
 
 FIX_MODES = {"hold": 0, "renoise": 1}         # PP_FIX_HOLD, PP_FIX_RENOISE
@@ -142,6 +142,7 @@ def load():
     lib.pp_ensemble_recombine.argtypes = [vp, vp, i, vp, i, vp, vp, vp, vp, vp, vp, vp]
     lib.pp_ctx_set_obstacles.argtypes = [vp, vp, vp, i, vp]
     lib.pp_sasa.argtypes = [vp, vp, vp, vp, i, f, vp, vp, vp, vp]
+    lib.pp_sample_guided.argtypes = [vp, vp, vp, vp, i, vp, i, i, C.c_uint64, vp, f, vp, vp, vp]
     _lib = lib
     return lib
 
@@ -539,6 +540,44 @@ class Context:
                                         _stream(self.plan.device)), "pp_sample_partial")
         return (chi, traj) if trajectory else chi
 
+    def sample_guided(self, chi, schedule, mode, seed, eta, cap=0.1, chi_ref=None, fixed=None, fix_mode="renoise",
+                      trajectory=False, want_trace=False, vtf=12.0, tol=0.5):
+        """Clash-guided sampling (pp_sample_guided): ``sample(..., seed=seed)`` -- with ``chi_ref`` and
+        ``fixed`` ``sample_partial`` -- with a gradient step on the clash loss (obstacle atoms included) at every nudge point j whose
+        ``eta[j]`` is not 0: point j < n_schedule - 1 in front of network evaluation j, the last one behind the last reverse step.
+        ``eta``: n_schedule step sizes (``schedule.guide_eta``), finite and not negative; ``cap``: the largest step of one angle at one
+        nudge in radians (inf = no clamp).  Fixed rows are never nudged.  With ``eta`` all 0 the result has the bits of ``sample`` /
+        ``sample_partial``.  Needs a packed or B = 1 context.  Returns the sample [B, L, 4]; with ``trajectory`` also the angles after
+        every reverse step [n_steps, B, L, 4] (in front of the nudge that follows); with ``want_trace`` also the mean clash of every
+        segment in front of every nudge, fp64 [n_segments, n_schedule], NaN where ``eta`` is 0.  No host synchronisation."""
+        if mode not in ("ode", "sde"):
+            raise NotImplementedError(mode)
+        if (chi_ref is None) != (fixed is None):
+            raise ValueError("chi_ref and fixed go together: give both (a pinned run) or neither")
+        if fixed is not None and fix_mode not in FIX_MODES:
+            raise ValueError(f"fix_mode must be one of {sorted(FIX_MODES)}")
+        sched = np.ascontiguousarray(torch.as_tensor(schedule, dtype=torch.float32).cpu().numpy())
+        et = np.ascontiguousarray(torch.as_tensor(eta, dtype=torch.float32).cpu().numpy()).reshape(-1)
+        if et.size != sched.size:
+            raise ValueError(f"eta has {et.size} entries, the schedule has {sched.size} times (one nudge point per time)")
+        self.plan.set_clash_params(vtf, tol)
+        chi = self._chi(chi).clone()
+        ref = fx = None
+        if fixed is not None:
+            ref = self._chi(chi_ref)
+            fx = torch.as_tensor(fixed).to(device=self.plan.device)
+            if fx.numel() != self.n_rows:
+                raise ValueError(f"fixed has {fx.numel()} elements, this context has {self.n_rows} rows")
+            fx = (fx != 0).to(torch.uint8).reshape(-1).contiguous()
+        traj = self._new(max(len(sched) - 1, 0), self.B, self.L, 4) if trajectory else None
+        trace = self._new(self.n_segments, len(sched), dtype=torch.float64) if want_trace else None
+        _check(load().pp_sample_guided(self.handle, _ptr(chi), _ptr(ref), _ptr(fx), FIX_MODES.get(fix_mode, 1), sched.ctypes.data,
+                                       int(len(sched)), 0 if mode == "ode" else 1, _seed64(seed if seed is not None else 0),
+                                       et.ctypes.data, float(cap), _ptr(traj), _ptr(trace), _stream(self.plan.device)),
+               "pp_sample_guided")
+        out = (chi,) + ((traj,) if trajectory else ()) + ((trace,) if want_trace else ())
+        return out if len(out) > 1 else chi
+
     def atom14(self, chi):
         chi = self._chi(chi)
         xyz = self._new(self.B, self.L, 14, 3)
@@ -765,8 +804,9 @@ class Context:
         return float(ms.value)
 
     def profile_kernel(self, which: int):
-        """Bracket every later launch of kernel `which` (0 node message, 1 edge update, 2 node update; inside proximal(): 3 clash
-        loss + gradient, 4 Adam step + reconstruction) with HIP events."""
+        """Bracket every later launch of kernel `which` (0 node message, 1 edge update, 2 node update; inside the proximal
+        calls: 3 the one launch per Adam step; inside sample_guided(): 4 the reconstruction of a nudge, 5 its clash + gradient +
+        step launch, 6 the node embedding launch behind it) with HIP events."""
         _check(load().pp_profile_kernel(self.handle, int(which)), "pp_profile_kernel")
 
     def profile_read(self):

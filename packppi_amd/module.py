@@ -108,6 +108,8 @@ class TDiffusionModule:
         self._ctx_key, self._ctx = None, None
         self._score_norm = None           # [2, 5001] fp64 on the device: set_score_norm, or made at the first forward
         self._knn_ties = knn_ties         # None: the library default (the reference CPU path's torch.topk choice)
+        self.keep_guide_trace = False     # True: guided sampling runs append (eta, clash trace) to guide_traces
+        self.guide_traces = []
         self.to(device)
 
     # ---- construction ----------------------------------------------------------------------
@@ -280,7 +282,7 @@ class TDiffusionModule:
         self._val_loss, self._test_loss = (0.0, 0), (0.0, 0)
 
     def sampling(self, batch, use_proximal: bool = False, return_list: bool = False, sde_noise=None, seed=None,
-                 fixed_mask=None, fixed_chi=None, fixed_mode="renoise", return_trajectory: bool = False):
+                 fixed_mask=None, fixed_chi=None, fixed_mode="renoise", return_trajectory: bool = False, guide=None):
         """``seed`` (an int, None = the reference's behaviour): the initial noising and the sde noise come from the counter-based
         generator on the device (csrc/pp_rng.h) instead of torch's global one.  The noise of a complex is then a function of
         (seed, its key, its rows, the step) alone: the same complex gets the same angles alone, anywhere in a packed batch and
@@ -296,10 +298,34 @@ class TDiffusionModule:
 
         Obstacle atoms (a batch from ``protein_to_batch(..., obstacles=...)``): the network does not see
         them, the sample is what it is without them; with ``use_proximal`` the clash the proximal stage reports and optimises
-        includes every side-chain atom's overlap with the obstacles of its complex."""
+        includes every side-chain atom's overlap with the obstacles of its complex.
+
+        ``guide`` (None = today's code path, untouched): clash-guided sampling -- a gradient step on the clash
+        loss, obstacle atoms included, in front of the network evaluations and behind the last reverse step
+        (``Context.sample_guided``).  A number is the step size of the default preset (``schedule.GUIDE_DEFAULTS``: nudges from
+        t = 0.3 on, at most 0.1 rad per angle and nudge -- starting values, not tuned ones), a dict holds any of ``scale``, ``kind``
+        ("late" / "constant"), ``t_on``, ``cap``, anything else is an explicit sequence of n_schedule step sizes.  Needs ``seed`` in
+        sde mode and with ``fixed_mask`` (fixed rows are never nudged); excludes ``sde_noise``; a packed or B = 1 batch.  With
+        ``return_trajectory``: (sample, angles after every reverse step, mean clash in front of every nudge, fp64
+        [n_complexes, n_schedule], NaN where no nudge runs).  ``use_proximal`` runs behind it, as today."""
         cfg = self.hparams.sample_cfg
         if fixed_mask is None:
             fixed_mask = _get(batch, "fixed_mask")
+        eta = cap = None
+        if guide is not None:
+            from .schedule import resolve_guide
+            eta, cap = resolve_guide(guide, self.schedule)
+            if sde_noise is not None:
+                raise ValueError("guide and sde_noise exclude each other: guided sde sampling draws its noise from the seeded generator")
+            if seed is None and cfg.mode == "sde":
+                raise ValueError("guide needs seed in sde mode: the guided sampler draws its noise inside the reverse step")
+            if seed is None and fixed_mask is not None:
+                raise ValueError("guide with fixed_mask needs seed: the fixed rows are re-noised with the seeded generator's draws")
+            if return_trajectory and use_proximal:
+                raise ValueError("return_trajectory with guide returns the sampler's trajectory: run the proximal stage separately")
+            if _get(batch, "seg_offsets") is None and int(batch.num_proteins) != 1:
+                raise ValueError("guide needs a B = 1 batch or a packed one (batch.pack), not a padded B > 1 batch")
+            gkw = dict(eta=eta, cap=cap, vtf=cfg.violation_tolerance_factor, tol=cfg.clash_overlap_tolerance)
         if fixed_mask is not None:
             if seed is None:
                 raise ValueError("fixed_mask needs seed: the fixed rows are re-noised with the seeded generator's draws")
@@ -318,8 +344,10 @@ class TDiffusionModule:
             init = ctx.add_noise(torch.where(fx.unsqueeze(-1), ref, ctx._chi(batch.SC_D)), 1.0, seed)
             if fixed_mode == "hold":
                 init = torch.where(fx.unsqueeze(-1), ref, init)
+            if guide is not None:
+                return self._guided(ctx, init, seed, return_trajectory, chi_ref=ref, fixed=fx, fix_mode=fixed_mode, **gkw)
             return ctx.sample_partial(init, ref, fx, self.schedule, cfg.mode, seed, fixed_mode, trajectory=return_trajectory)
-        if return_trajectory:
+        if return_trajectory and guide is None:
             raise ValueError("return_trajectory needs fixed_mask (the trajectory is written by the partial sampler)")
         packed = _get(batch, "seg_offsets") is not None
         if packed and use_proximal and return_list:
@@ -327,7 +355,19 @@ class TDiffusionModule:
                              "functional.proximal_optimizer_packed (per-complex losses [n_complexes, num_steps])")
         if seed is not None and sde_noise is not None:
             raise ValueError("seed and sde_noise exclude each other: the seeded sampler draws its own noise")
-        if seed is not None:
+        if guide is not None:
+            ctx = self._context(batch)
+            if seed is not None:
+                ctx.set_rng_keys(_get(batch, "complex_keys"))
+                init = ctx.add_noise(batch.SC_D, 1.0, seed)
+            else:           # ode: the initial noising from torch's generator, as the unseeded path below draws it
+                t = torch.tensor([1.]).repeat_interleave(batch.max_size * batch.num_proteins).to(self.device)
+                init, _ = self.add_sc_noise(batch, t)
+            out = self._guided(ctx, init, seed, return_trajectory, **gkw)
+            if return_trajectory:
+                return out
+            SC_D_sample = out
+        elif seed is not None:
             ctx = self._context(batch)
             ctx.set_rng_keys(_get(batch, "complex_keys"))
             SC_D_sample = ctx.sample(ctx.add_noise(batch.SC_D, 1.0, seed), self.schedule, cfg.mode, seed=seed)
@@ -356,8 +396,21 @@ class TDiffusionModule:
             return SC_D_resample_list[-1]
         return SC_D_sample
 
+    def _guided(self, ctx, init, seed, return_trajectory, **kw):
+        """``Context.sample_guided`` for ``sampling``: the sample, with ``return_trajectory`` (sample, trajectory, clash trace).
+        With ``keep_guide_trace`` set every guided run also appends (eta, clash trace on the device) to ``guide_traces`` (the
+        command lines write guide.csv from it); otherwise no trace launch is enqueued unless the caller asked for it."""
+        keep = self.keep_guide_trace
+        out = ctx.sample_guided(init, self.schedule, self.hparams.sample_cfg.mode, seed, trajectory=return_trajectory,
+                                want_trace=return_trajectory or keep, **kw)
+        if keep:
+            self.guide_traces.append((kw["eta"], out[-1]))
+        if return_trajectory:
+            return out
+        return out[0] if keep else out
+
     def repack(self, batch, fixed_mask=None, *, seed, fixed_chi=None, fixed_mode="renoise", use_proximal: bool = False,
-               return_list: bool = False, norm_rows=None):
+               return_list: bool = False, norm_rows=None, guide=None):
         """Partial repacking in one call (DESIGN.md sections 13 and 14): ``sampling(batch, seed=seed, fixed_mask=...)`` -- the rows
         of ``fixed_mask`` (default ``batch.fixed_mask``) keep ``fixed_chi`` (default ``batch.SC_D``), the others are sampled around
         them -- and then, with ``use_proximal``, the PINNED proximal stage (pp_proximal_pinned): the clash mask of every complex, its
@@ -365,7 +418,8 @@ class TDiffusionModule:
         batch or a packed one (``batch.pack``); ``norm_rows`` as in ``functional.proximal_optimizer_packed`` (the sharded driver passes
         the padded sizes).  Kept rows of the result are ``fixed_chi`` bit for bit with or without the proximal stage.  On a batch with
         obstacle atoms the clash of the pinned stage -- mask, loss, gradient -- includes them.
-        ``return_list`` (B = 1, with ``use_proximal``): (sample, per-step angles, losses) as ``sampling`` returns them."""
+        ``return_list`` (B = 1, with ``use_proximal``): (sample, per-step angles, losses) as ``sampling`` returns them.
+        ``guide``: as in ``sampling`` (clash-guided sampling of the free rows); None = today's path."""
         if fixed_mask is None:
             fixed_mask = _get(batch, "fixed_mask")
         if fixed_mask is None:
@@ -375,7 +429,7 @@ class TDiffusionModule:
             raise ValueError("return_list=True needs use_proximal=True and a B = 1 batch; for a packed batch use "
                              "functional.proximal_optimizer_packed (per-complex losses [n_complexes, num_steps])")
         cfg = self.hparams.sample_cfg
-        SC_D_sample = self.sampling(batch, seed=seed, fixed_mask=fixed_mask, fixed_chi=fixed_chi, fixed_mode=fixed_mode)
+        SC_D_sample = self.sampling(batch, seed=seed, fixed_mask=fixed_mask, fixed_chi=fixed_chi, fixed_mode=fixed_mode, guide=guide)
         if not use_proximal:
             return SC_D_sample
         traj, _, accepted, losses = proximal_optimizer_packed(batch, SC_D_sample, cfg.violation_tolerance_factor,
@@ -400,7 +454,7 @@ class TDiffusionModule:
         return seg[:, 1] - seg[:, 2]
 
     def sample_ensemble(self, batch, n_decoys, *, seed=None, use_proximal: bool = False, select="clash", return_all: bool = False,
-                        recombine: bool = False, recombine_sweeps: int = 64, sasa: bool = False):
+                        recombine: bool = False, recombine_sweeps: int = 64, sasa: bool = False, guide=None):
         """``n_decoys`` seeded samples of every complex in ONE packed pass, reduced on the device.  On
         complexes with obstacle atoms the decoys of a group share the group's obstacles, and the clash that
         ranks them, the proximal stage and the recombination include the overlap with them.  ``batch``: a
@@ -424,7 +478,10 @@ class TDiffusionModule:
         int32 [n_complexes].
 
         ``sasa``: ``return_all`` gains ``bsa``, fp64 [n_complexes * n_decoys]: the surface every decoy buries
-        between its chains (``Context.sasa`` at the decoy's angles, ``seg_area[1] - seg_area[2]``).  Nothing else changes."""
+        between its chains (``Context.sasa`` at the decoy's angles, ``seg_area[1] - seg_area[2]``).  Nothing else changes.
+
+        ``guide``: every decoy is sampled with clash guidance, as ``sampling(guide=...)`` samples the complex
+        alone under the decoy's key; None = today's path."""
         from .batch import replicate, replicate_many
         from .lib import SELECT
         if seed is None:
@@ -441,7 +498,7 @@ class TDiffusionModule:
         if _get(packed, "fixed_mask") is not None:
             raise ValueError("ensembles under a fixed_mask are not supported: sample_ensemble samples every row")
         cfg = self.hparams.sample_cfg
-        chi = self.sampling(packed, use_proximal=use_proximal, seed=seed)
+        chi = self.sampling(packed, use_proximal=use_proximal, seed=seed, guide=guide)
         ctx = self._context(packed)
         per_res = ctx.clash(chi, cfg.violation_tolerance_factor, cfg.clash_overlap_tolerance)
         res = ctx.ensemble_reduce(chi, packed.n_decoys, per_res=per_res, select=select)
@@ -455,7 +512,7 @@ class TDiffusionModule:
 
     def repack_ensemble(self, batch, fixed_mask=None, *, n_decoys, seed, fixed_chi=None, fixed_mode="renoise",
                         use_proximal: bool = False, select="clash", return_all: bool = False, recombine: bool = False,
-                        recombine_sweeps: int = 64, sasa: bool = False):
+                        recombine_sweeps: int = 64, sasa: bool = False, guide=None):
         """``sample_ensemble`` under a pin: ``n_decoys`` seeded partial repackings of every complex in ONE packed
         pass, reduced on the device.  ``batch``: a B = 1 batch, or a list of complexes (per-complex data or B = 1 batches).  Every
         complex carries its ``fixed_mask`` (1 = keep; [1, L] on a B = 1 batch, [L] on per-complex data), or ``fixed_mask`` gives it:
@@ -468,7 +525,7 @@ class TDiffusionModule:
         with and without ``use_proximal``.  pp_ensemble_reduce is used unchanged: kept rows are identical in every decoy, so their
         ``resultant`` is 1 to rounding and they add (to rounding) nothing to ``dev``; they enter the per-decoy means of ``dev`` and
         ``clash`` with the same weight in all decoys of a group, so they dilute both equally and do not change the ranking.
-        Returns what ``sample_ensemble`` returns (``sasa``: the ``bsa`` key as there)."""
+        Returns what ``sample_ensemble`` returns (``sasa``: the ``bsa`` key as there).  ``guide``: as in ``sampling``."""
         from .batch import Batch, replicate_many
         from .lib import SELECT
         if select not in SELECT:
@@ -506,7 +563,7 @@ class TDiffusionModule:
                              for g, (c, r) in enumerate(zip(complexes, refs)) for _ in range(D)]).unsqueeze(0)
         cfg = self.hparams.sample_cfg
         chi = self.repack(packed, seed=seed, fixed_chi=ref, fixed_mode=fixed_mode, use_proximal=use_proximal,
-                          norm_rows=[n for n in sizes for _ in range(D)] if use_proximal else None)
+                          norm_rows=[n for n in sizes for _ in range(D)] if use_proximal else None, guide=guide)
         ctx = self._context(packed)
         per_res = ctx.clash(chi, cfg.violation_tolerance_factor, cfg.clash_overlap_tolerance)
         res = ctx.ensemble_reduce(chi, D, per_res=per_res, select=select)
@@ -520,7 +577,7 @@ class TDiffusionModule:
 
     def mutate(self, proteins_and_mutations, *, seed, radius=10.0, shell="ca", n_decoys=1, use_proximal: bool = False,
                select="clash", fixed_mode="renoise", max_rows=200_000, log=print, recombine: bool = False,
-               recombine_sweeps: int = 64, sasa: bool = False):
+               recombine_sweeps: int = 64, sasa: bool = False, guide=None):
         """Mutant modelling: put each mutation set into its complex, repack what it touches, return the mutant.
         ``proteins_and_mutations``: a list of ``(protein dict, mutations)`` pairs, ``mutations`` a string ("RA47A,EA48A") or dicts as
         ``featurize.parse_mutstr`` returns them; several sets of one protein are repeated pairs.  Set i of the call gets the noise
@@ -547,7 +604,10 @@ class TDiffusionModule:
         atoms: the clash every stage reports and optimises -- the pinned proximal stage, the ranking, the recombination -- includes
         the overlap with them.  The network and the shell rule do not see them.
 
-        ``sasa``: every dict gains ``bsa`` fp64 [n_decoys], the surface each decoy buries between its chains."""
+        ``sasa``: every dict gains ``bsa`` fp64 [n_decoys], the surface each decoy buries between its chains.
+
+        ``guide``: the shell is sampled with clash guidance, as in ``sampling``; rows outside the shell are
+        fixed rows, which are never nudged."""
         from .batch import as_single, pack, unpack
         from .featurize import mutant_model_data, parse_mutstr
         from .functional import _ctx_for
@@ -600,7 +660,7 @@ class TDiffusionModule:
                 pinned.append(p)
             out = self.repack_ensemble(pinned, n_decoys=n_decoys, seed=seed, fixed_mode=fixed_mode, use_proximal=use_proximal,
                                        select=select, return_all=True, recombine=recombine, recombine_sweeps=recombine_sweeps,
-                                       sasa=sasa)
+                                       sasa=sasa, guide=guide)
             final = out["recombined"] if recombine else out["selected"]
             pos = gctx.atom14(final)
             picks = unpack(pb, out["pick"].reshape(1, -1)) if recombine else [None] * len(members)

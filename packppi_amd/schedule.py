@@ -49,3 +49,58 @@ def load_score_norm(tables) -> np.ndarray:
     if arr.shape != (2, SO2_GRID) or not np.isfinite(arr).all() or (arr < 0).any():
         raise ValueError(f"score_norm tables must be [2, {SO2_GRID}] finite non-negative numbers (1pi schedule, then 2pi), got {arr.shape}")
     return arr
+
+
+# ---- clash-guided sampling --------------------------------------------------------------------------------
+# Starting values from the CPU oracle on seeded random weights, NOT tuned against a trained checkpoint.
+GUIDE_DEFAULTS = dict(scale=0.02, kind="late", t_on=0.3, cap=0.1)
+GUIDE_KINDS = ("late", "constant")
+
+
+def guide_eta(schedule, scale, kind="late", t_on=0.3) -> np.ndarray:
+    """The nudge step sizes of ``Context.sample_guided``: float32 [n_schedule], entry j the step size at nudge point j, which sits
+    at time ``schedule[j]`` (entry n = n_schedule - 1 belongs to ``schedule[n]``, behind the last reverse step).
+    ``kind`` "constant": every entry is ``scale``; "late": ``scale`` where ``schedule[j] <= t_on``, else 0 (no nudge while the
+    angles are still mostly noise).  ``scale`` may also be an explicit sequence of n_schedule step sizes, which is passed through
+    after validation.  ``ValueError``: a negative or non-finite entry, a wrong length, an unknown kind."""
+    sched = np.asarray(torch.as_tensor(schedule, dtype=torch.float32).cpu().numpy(), dtype=np.float32).reshape(-1)
+    if sched.size < 2:
+        raise ValueError("schedule needs at least 2 times")
+    if not np.isscalar(scale) and not (isinstance(scale, (torch.Tensor, np.ndarray)) and np.ndim(scale) == 0):
+        eta = np.asarray(torch.as_tensor(scale, dtype=torch.float32).cpu().numpy(), dtype=np.float32).reshape(-1)
+        if eta.size != sched.size:
+            raise ValueError(f"eta has {eta.size} entries for the {sched.size} nudge points of a schedule of {sched.size} times")
+    else:
+        scale = float(scale)
+        if kind == "constant":
+            eta = np.full(sched.size, scale, dtype=np.float32)
+        elif kind == "late":
+            if not np.isfinite(float(t_on)):
+                raise ValueError(f"t_on must be finite, got {t_on!r}")
+            eta = np.where(sched <= np.float32(t_on), np.float32(scale), np.float32(0)).astype(np.float32)
+        else:
+            raise ValueError(f"kind must be one of {list(GUIDE_KINDS)}, got {kind!r}")
+    if not np.isfinite(eta).all() or (eta < 0).any():
+        raise ValueError("eta entries must be finite and not negative")
+    return np.ascontiguousarray(eta, dtype=np.float32)
+
+
+def resolve_guide(guide, schedule):
+    """``guide`` as ``TDiffusionModule.sampling`` takes it -> (eta float32 [n_schedule], cap): a number is the scale of the
+    default preset, a dict holds any of ``scale``, ``kind``, ``t_on``, ``cap`` (or ``eta``, an explicit sequence), anything else is
+    an explicit eta sequence."""
+    cfg = dict(GUIDE_DEFAULTS)
+    if isinstance(guide, dict):
+        unknown = sorted(set(guide) - set(cfg) - {"eta"})
+        if unknown:
+            raise ValueError(f"guide has unknown keys {unknown}; known: {sorted(cfg) + ['eta']}")
+        cfg.update({k: v for k, v in guide.items() if k != "eta"})
+        scale = guide["eta"] if "eta" in guide else cfg["scale"]
+    elif isinstance(guide, bool):
+        raise ValueError("guide must be a scale, a dict or an eta sequence, not a bool")
+    else:
+        scale = guide
+    cap = float(cfg["cap"])
+    if not cap > 0:
+        raise ValueError(f"guide cap must be positive (inf = no clamp), got {cfg['cap']!r}")
+    return guide_eta(schedule, scale, cfg["kind"], cfg["t_on"]), cap
