@@ -222,6 +222,40 @@ def unpack(packed: Batch, t: torch.Tensor) -> List[torch.Tensor]:
     return [t[:, a:b] for a, b in zip(offs[:-1], offs[1:])]
 
 
+def pad_rows(t: torch.Tensor, n: int, tail=0, fresh: bool = False) -> torch.Tensor:
+    """A per-row result [1, m, ...] of one complex with the trailing rows ``pack`` dropped put back: [1, n, ...].  ``tail``: what
+    the rows m .. n - 1 hold -- a number, or a tensor [1, n, ...] whose rows m .. n - 1 they are.  m == n: ``t`` itself, a view of
+    the packed result, unless ``fresh`` asks for a tensor of its own."""
+    m = t.shape[1]
+    if m == n and not fresh:
+        return t
+    if isinstance(tail, torch.Tensor):
+        return torch.cat([t, tail[:, m:]], 1)
+    full = torch.full((1, n) + tuple(t.shape[2:]), tail, device=t.device, dtype=t.dtype)
+    full[:, :m] = t
+    return full
+
+
+def group_rows(sizes, alone, max_rows, mult: int = 1) -> List[List[int]]:
+    """How the drivers cut a list of complexes into packed batches: groups of indices into ``sizes`` (rows per complex), in order.
+    An ``alone`` complex (shorter than 32 rows: K = min(32, L) is a property of the batch) is a group of its own, put down where it
+    stands; the others fill a group while ``mult`` x its rows stays within ``max_rows`` (``mult``: rows launched per row of the
+    group, the decoys of an ensemble)."""
+    groups, cur, rows_in = [], [], 0
+    for i, (n, solo) in enumerate(zip(sizes, alone)):
+        if solo:
+            groups.append([i])
+            continue
+        if cur and mult * (rows_in + n) > max_rows:
+            groups.append(cur)
+            cur, rows_in = [], 0
+        cur.append(i)
+        rows_in += n
+    if cur:
+        groups.append(cur)
+    return groups
+
+
 # ---- decoy ensembles (DESIGN.md section 16) ---------------------------------------------------------------------------------------
 _M64 = (1 << 64) - 1
 

@@ -567,8 +567,7 @@ static bool edge_live_on() {
     return on;
 }
 
-// rng (seeded sde sampling, else null): the reverse step draws its own noise
-// pin (pp_sample_partial, else null): this step's pinned reverse step
+// ev: what the evaluation is given (pp_internal.h NodeEval)
 // live (sampling runs, else null): the rows whose layer-1 edge update has a reader.  That launch makes h_E (not stored) and the
 // layer-2 message S / msum of row i, which feed only the layer-2 node update of row i, whose h_V feeds only the decoder and the
 // reverse step of row i: nothing of it reaches the returned angles of a row that cannot move (y = wrap(..) * SC_D_mask = 0, or
@@ -577,9 +576,7 @@ static bool edge_live_on() {
 // uninitialised memory -- and the layer-2 node update computes on them as on any other message.  What it computes for such a row is
 // read by nobody, and it must not be reported either: k_node_update<PP_NU_STEP> leaves the rows that cannot move out of the sticky
 // saturation word (pp_node.hip, `satrow`), so the word does not depend on which message a skipped row was given.
-static pp_status run_network(pp_ctx *c, hipStream_t s, int step, int last_mode, float *chi, int mode, const float *noise,
-                             const StepParams *cur, const StepParams *next, const PPRng *rng = nullptr, const PPPin *pin = nullptr,
-                             const PPLive *live = nullptr) {
+static pp_status run_network(pp_ctx *c, hipStream_t s, int last_mode, const NodeEval &ev, const PPLive *live) {
     pp_status st;
     for (int l = 0; l < 3; l++) {
         if (l == 0 || !pp_edge_fused()) {   // fused build: layers 1 and 2 come from the tail of the previous edge update
@@ -588,18 +585,13 @@ static pp_status run_network(pp_ctx *c, hipStream_t s, int step, int last_mode, 
             prof_disarm(c);
             if (st != PP_OK) return st;
         }
+        prof_arm(c, 2);
+        st = pp_launch_node_update(c, l, l < 2 ? PP_NU_MID : last_mode, ev, s);
+        prof_disarm(c);
+        if (st != PP_OK) return st;
         if (l < 2) {
-            prof_arm(c, 2);
-            st = pp_launch_node_update(c, l, PP_NU_MID, chi, step, mode, noise, nullptr, nullptr, s);
-            prof_disarm(c);
-            if (st != PP_OK) return st;
             prof_arm(c, 1);
             st = pp_launch_edge_update(c, l, l == 0 || !pp_edge_fused(), s, l == 1 ? live : nullptr);   // layer 1's h_E has no reader here
-            prof_disarm(c);
-            if (st != PP_OK) return st;
-        } else {
-            prof_arm(c, 2);
-            st = pp_launch_node_update(c, l, last_mode, chi, step, mode, noise, cur, last_mode == PP_NU_STEP ? next : nullptr, s, rng, pin);
             prof_disarm(c);
             if (st != PP_OK) return st;
         }
@@ -611,7 +603,8 @@ static pp_status run_network(pp_ctx *c, hipStream_t s, int step, int last_mode, 
 // (`score` or `hV` may be null).  `sp`: PP_NU_SCORE reads no per-step scalar and no time embedding from it
 static pp_status evaluate_and_copy(pp_ctx *c, const StepParams &sp, float *score, float *hV, hipStream_t s) {
     pp_status st;
-    if ((st = run_network(c, s, 0, PP_NU_SCORE, nullptr, PP_MODE_ODE, nullptr, &sp, nullptr)) != PP_OK) return st;
+    const NodeEval ev = {nullptr, 0, PP_MODE_ODE, nullptr, &sp, nullptr, nullptr, nullptr};
+    if ((st = run_network(c, s, PP_NU_SCORE, ev, nullptr)) != PP_OK) return st;
     if (score) PP_HIP_CHECK(hipMemcpyAsync(score, c->score, (size_t)c->N * 4 * sizeof(float), hipMemcpyDeviceToDevice, s));
     if (hV) PP_HIP_CHECK(hipMemcpyAsync(hV, c->hV, (size_t)c->N * 128 * sizeof(float), hipMemcpyDeviceToDevice, s));
     return PP_OK;
@@ -702,64 +695,51 @@ extern "C" pp_status pp_add_noise_seeded(pp_ctx *c, const float *chi0, float t, 
     return pp_launch_add_noise_seeded(c, chi0, sigma_f32(t), seed, chi, s);
 }
 
-// what pp_sample_partial adds to a sampling run
-struct PartialArgs {
-    const float *chi_ref;      // [N][4]
-    const uint8_t *fixed;      // [N]
-    int fix_mode;              // PP_FIX_HOLD / PP_FIX_RENOISE
-    float *chi_traj;           // [n_schedule - 1][N][4] or null
+// What one sampling run is: the four exports fill one and call sample_impl.
+struct SampleRun {
+    const char *who;                    // the export, for messages
+    const float *sde_noise = nullptr;   // pp_sample: the per-step noise tensor, or
+    bool seeded = false;                // the reverse steps draw their own noise
+    uint64_t seed = 0;                  //   from this seed
+    const float *chi_ref = nullptr;     // the pin (partial repacking), or null: [N][4]
+    const uint8_t *fixed = nullptr;     //   [N]: fixed rows are pinned inside the reverse step
+    int fix_mode = PP_FIX_RENOISE;      //   PP_FIX_HOLD / PP_FIX_RENOISE
+    const float *eta = nullptr;         // the guide, or null: HOST [n_schedule], the step size of nudge point j, 0 = none
+    float cap = 0.f;                    //   largest |step| of one angle at one nudge
+    double *trace = nullptr;            //   [B][n_schedule] or null
+    float *chi_traj = nullptr;          // [n_schedule - 1][N][4] or null: written by the pinned step's lanes, copied in a run without a pin
 };
-
-// what pp_sample_guided adds to a sampling run
-struct GuideArgs {
-    const float *eta;          // HOST [n_schedule]: the step size of nudge point j, 0 = no nudge there
-    float cap;                 // largest |step| of one angle at one nudge
-    float *chi_traj;           // [n_schedule - 1][N][4] or null: a run without a pin has no stepping lane that writes it (copied)
-    double *trace;             // [B][n_schedule] or null
-};
-
-// pp_sample, pp_sample_seeded, pp_sample_partial and pp_sample_guided (`who` names the export in messages; rng: the reverse steps
-// draw their own sde noise; part: fixed rows are pinned inside the reverse step; guide: nudges between the evaluations)
-static pp_status sample_impl(const char *who, pp_ctx *c, float *chi, const float *schedule, int n_schedule, int mode,
-                             const float *sde_noise, const PPRng *rng, hipStream_t s, const PartialArgs *part = nullptr,
-                             const GuideArgs *guide = nullptr);
+static pp_status sample_impl(pp_ctx *c, float *chi, const float *schedule, int n_schedule, int mode, const SampleRun &run, hipStream_t s);
 
 extern "C" pp_status pp_sample(pp_ctx *c, float *chi, const float *schedule, int n_schedule, int mode,
                                const float *sde_noise, void *stream) {
     if (c) c->last_stream = static_cast<hipStream_t>(stream);
     if (c && mode == PP_MODE_SDE && !sde_noise) FAIL(PP_ERR_INVALID, "pp_sample: sde mode needs the per-step noise tensor");
-    return sample_impl("pp_sample", c, chi, schedule, n_schedule, mode, sde_noise, nullptr, static_cast<hipStream_t>(stream));
+    SampleRun run = {"pp_sample"};
+    run.sde_noise = sde_noise;
+    return sample_impl(c, chi, schedule, n_schedule, mode, run, static_cast<hipStream_t>(stream));
 }
 
 extern "C" pp_status pp_sample_seeded(pp_ctx *c, float *chi, const float *schedule, int n_schedule, int mode, uint64_t seed,
                                       void *stream) {
     if (c) c->last_stream = static_cast<hipStream_t>(stream);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (!c || mode != PP_MODE_SDE)       // ode draws nothing: pp_sample
-        return sample_impl("pp_sample_seeded", c, chi, schedule, n_schedule, mode, nullptr, nullptr, s);
-    PP_HIP_CHECK(hipSetDevice(c->plan->device));
-    pp_status st;
-    if ((st = rng_table_ready(c, s)) != PP_OK) return st;
-    const PPRng rng = {c->rng_tab, (uint32_t)seed, (uint32_t)(seed >> 32)};
-    return sample_impl("pp_sample_seeded", c, chi, schedule, n_schedule, mode, nullptr, &rng, s);
+    SampleRun run = {"pp_sample_seeded"};
+    run.seeded = mode == PP_MODE_SDE;       // ode draws nothing: pp_sample
+    run.seed = seed;
+    return sample_impl(c, chi, schedule, n_schedule, mode, run, static_cast<hipStream_t>(stream));
 }
 
 extern "C" pp_status pp_sample_partial(pp_ctx *c, float *chi, const float *chi_ref, const uint8_t *fixed, int fix_mode,
                                        const float *schedule, int n_schedule, int mode, uint64_t seed, float *chi_traj,
                                        void *stream) {
     if (c) c->last_stream = static_cast<hipStream_t>(stream);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (!c || !chi || !chi_ref || !fixed || !schedule) FAIL(PP_ERR_INVALID, "pp_sample_partial: null argument");
-    if (chi_ref == chi) FAIL(PP_ERR_INVALID, "pp_sample_partial: chi_ref and chi must be distinct buffers");
-    if (fix_mode != PP_FIX_HOLD && fix_mode != PP_FIX_RENOISE) FAIL(PP_ERR_INVALID, "pp_sample_partial: unknown fix_mode");
-    if (mode != PP_MODE_ODE && mode != PP_MODE_SDE) FAIL(PP_ERR_INVALID, "pp_sample_partial: unknown mode");
-    if (!c->b.chi_1pi_periodic_mask || !c->b.chi_2pi_periodic_mask) FAIL(PP_ERR_INVALID, "pp_sample_partial: batch lacks the periodic masks");
-    PP_HIP_CHECK(hipSetDevice(c->plan->device));
-    pp_status st;
-    if ((st = rng_table_ready(c, s)) != PP_OK) return st;
-    const PPRng rng = {c->rng_tab, (uint32_t)seed, (uint32_t)(seed >> 32)};
-    const PartialArgs part = {chi_ref, fixed, fix_mode, chi_traj};
-    return sample_impl("pp_sample_partial", c, chi, schedule, n_schedule, mode, nullptr, &rng, s, &part);
+    if (!chi_ref || !fixed) FAIL(PP_ERR_INVALID, "pp_sample_partial: null argument");
+    SampleRun run = {"pp_sample_partial"};
+    run.seeded = true;
+    run.seed = seed;
+    run.chi_ref = chi_ref; run.fixed = fixed; run.fix_mode = fix_mode;
+    run.chi_traj = chi_traj;
+    return sample_impl(c, chi, schedule, n_schedule, mode, run, static_cast<hipStream_t>(stream));
 }
 
 // ---- clash-guided sampling -----------------------------------------------------------------------------------
@@ -767,70 +747,84 @@ extern "C" pp_status pp_sample_guided(pp_ctx *c, float *chi, const float *chi_re
                                       const float *schedule, int n_schedule, int mode, uint64_t seed, const float *eta, float cap,
                                       float *chi_traj, double *clash_trace, void *stream) {
     if (c) c->last_stream = static_cast<hipStream_t>(stream);
-    hipStream_t s = static_cast<hipStream_t>(stream);
     if (!c) FAIL(PP_ERR_INVALID, "pp_sample_guided: null ctx");
     if (!chi) FAIL(PP_ERR_INVALID, "pp_sample_guided: null chi");
     if (!schedule) FAIL(PP_ERR_INVALID, "pp_sample_guided: null schedule");
     if (!eta) FAIL(PP_ERR_INVALID, "pp_sample_guided: null eta");
     if ((chi_ref == nullptr) != (fixed == nullptr))
         FAIL(PP_ERR_INVALID, "pp_sample_guided: chi_ref and fixed must be given together (both, or neither for a run without a pin)");
-    if (chi_ref && chi_ref == chi) FAIL(PP_ERR_INVALID, "pp_sample_guided: chi_ref and chi must be distinct buffers");
-    if (fixed && fix_mode != PP_FIX_HOLD && fix_mode != PP_FIX_RENOISE) FAIL(PP_ERR_INVALID, "pp_sample_guided: unknown fix_mode");
-    if (mode != PP_MODE_ODE && mode != PP_MODE_SDE) FAIL(PP_ERR_INVALID, "pp_sample_guided: unknown mode");
-    if (n_schedule < 2) FAIL(PP_ERR_INVALID, "pp_sample_guided: schedule needs at least 2 times");
-    for (int j = 0; j < n_schedule; j++)
-        if (!(eta[j] >= 0.f) || std::isinf(eta[j]))
-            FAIL(PP_ERR_INVALID, "pp_sample_guided: eta[" + std::to_string(j) + "] must be finite and not negative");
-    if (!(cap > 0.f)) FAIL(PP_ERR_INVALID, "pp_sample_guided: cap must be positive (INFINITY = no clamp)");
-    if (!c->plan->has_network) FAIL(PP_ERR_INVALID, "pp_sample_guided: plan was created without network weights (a geometry-only plan)");
-    if (!c->plan->clash_params_set) FAIL(PP_ERR_INVALID, "pp_sample_guided: call pp_plan_set_clash_params first");
-    if (!c->b.atom_mask || !c->b.residue_index) FAIL(PP_ERR_INVALID, "pp_sample_guided: batch lacks atom_mask / residue_index");
-    if (!c->b.SC_D_mask || !c->b.chi_1pi_periodic_mask || !c->b.chi_2pi_periodic_mask)
-        FAIL(PP_ERR_INVALID, "pp_sample_guided: batch lacks SC_D_mask / the periodic masks");
-    if (!c->packed && c->B != 1)
-        FAIL(PP_ERR_INVALID, "pp_sample_guided: needs a context from pp_complex_prepare_packed (or a B = 1 one), not a padded B > 1 batch");
-    PP_HIP_CHECK(hipSetDevice(c->plan->device));
-    pp_status st;
-    PPRng rng = {nullptr, 0u, 0u};
-    const bool seeded = fixed != nullptr || mode == PP_MODE_SDE;          // ode without a pin draws nothing: pp_sample's instances
-    if (seeded) {
-        if ((st = rng_table_ready(c, s)) != PP_OK) return st;
-        rng = {c->rng_tab, (uint32_t)seed, (uint32_t)(seed >> 32)};
-    }
-    const PartialArgs part = {chi_ref, fixed, fix_mode, chi_traj};
-    const GuideArgs guide = {eta, cap, chi_traj, clash_trace};
-    return sample_impl("pp_sample_guided", c, chi, schedule, n_schedule, mode, nullptr, seeded ? &rng : nullptr, s,
-                       fixed ? &part : nullptr, &guide);
+    SampleRun run = {"pp_sample_guided"};
+    run.seeded = fixed != nullptr || mode == PP_MODE_SDE;          // ode without a pin draws nothing: pp_sample's instances
+    run.seed = seed;
+    run.chi_ref = chi_ref; run.fixed = fixed; run.fix_mode = fix_mode;
+    run.eta = eta; run.cap = cap; run.trace = clash_trace;
+    run.chi_traj = chi_traj;
+    return sample_impl(c, chi, schedule, n_schedule, mode, run, static_cast<hipStream_t>(stream));
 }
 
-static pp_status sample_impl(const char *who, pp_ctx *c, float *chi, const float *schedule, int n_schedule, int mode,
-                             const float *sde_noise, const PPRng *rng, hipStream_t s, const PartialArgs *part, const GuideArgs *guide) {
-    const std::string w(who);
+// The argument checks of a run, each written once, in the one order that reports a call with several faults as every export always
+// has: the exports with a pin or a guide name an unknown mode in front of the plan's and the schedule's faults, the other two behind.
+static pp_status check_run(const pp_ctx *c, const float *chi, const float *schedule, int n_schedule, int mode, const SampleRun &run) {
+    const std::string w(run.who);
+    const bool pinned = run.fixed != nullptr, guided = run.eta != nullptr;
+    const bool bad_mode = mode != PP_MODE_ODE && mode != PP_MODE_SDE;
     if (!c || !chi || !schedule) FAIL(PP_ERR_INVALID, w + ": null argument");
-    if (!c->plan->has_network) FAIL(PP_ERR_INVALID, w + ": plan was created without network weights");
+    if (pinned && run.chi_ref == chi) FAIL(PP_ERR_INVALID, w + ": chi_ref and chi must be distinct buffers");
+    if (pinned && run.fix_mode != PP_FIX_HOLD && run.fix_mode != PP_FIX_RENOISE) FAIL(PP_ERR_INVALID, w + ": unknown fix_mode");
+    if ((pinned || guided) && bad_mode) FAIL(PP_ERR_INVALID, w + ": unknown mode");
+    if (pinned && !guided && (!c->b.chi_1pi_periodic_mask || !c->b.chi_2pi_periodic_mask))
+        FAIL(PP_ERR_INVALID, w + ": batch lacks the periodic masks");
+    if (!guided && !c->plan->has_network) FAIL(PP_ERR_INVALID, w + ": plan was created without network weights");
     if (n_schedule < 2) FAIL(PP_ERR_INVALID, w + ": schedule needs at least 2 times");
+    if (guided) {
+        for (int j = 0; j < n_schedule; j++)
+            if (!(run.eta[j] >= 0.f) || std::isinf(run.eta[j]))
+                FAIL(PP_ERR_INVALID, w + ": eta[" + std::to_string(j) + "] must be finite and not negative");
+        if (!(run.cap > 0.f)) FAIL(PP_ERR_INVALID, w + ": cap must be positive (INFINITY = no clamp)");
+        if (!c->plan->has_network) FAIL(PP_ERR_INVALID, w + ": plan was created without network weights (a geometry-only plan)");
+        if (!c->plan->clash_params_set) FAIL(PP_ERR_INVALID, w + ": call pp_plan_set_clash_params first");
+        if (!c->b.atom_mask || !c->b.residue_index) FAIL(PP_ERR_INVALID, w + ": batch lacks atom_mask / residue_index");
+        if (!c->b.SC_D_mask || !c->b.chi_1pi_periodic_mask || !c->b.chi_2pi_periodic_mask)
+            FAIL(PP_ERR_INVALID, w + ": batch lacks SC_D_mask / the periodic masks");
+        if (!c->packed && c->B != 1)
+            FAIL(PP_ERR_INVALID, w + ": needs a context from pp_complex_prepare_packed (or a B = 1 one), not a padded B > 1 batch");
+    }
     if (n_schedule - 1 > c->max_steps) FAIL(PP_ERR_UNSUPPORTED, w + ": more than 2^20 steps");
-    if (mode != PP_MODE_ODE && mode != PP_MODE_SDE) FAIL(PP_ERR_INVALID, w + ": unknown mode");
+    if (bad_mode) FAIL(PP_ERR_INVALID, w + ": unknown mode");
+    return PP_OK;
+}
+
+// the pin of reverse step j: a fixed row arrives at the noise level of schedule[j + 1] like the free rows; after the last step it
+// holds chi_ref itself (sigma(0) = 0.01 pi is not 0)
+static PPPin step_pin(const SampleRun &run, const float *schedule, int j, int nsteps, int N) {
+    return {run.fixed, run.chi_ref, run.chi_traj ? run.chi_traj + (size_t)j * N * 4 : nullptr, sigma_f32(schedule[j + 1]),
+            run.fix_mode == PP_FIX_RENOISE && j + 1 < nsteps ? 1 : 0};
+}
+
+// pp_sample, pp_sample_seeded, pp_sample_partial and pp_sample_guided
+static pp_status sample_impl(pp_ctx *c, float *chi, const float *schedule, int n_schedule, int mode, const SampleRun &run, hipStream_t s) {
+    pp_status st;
+    if ((st = check_run(c, chi, schedule, n_schedule, mode, run)) != PP_OK) return st;
     PP_HIP_CHECK(hipSetDevice(c->plan->device));
+    const bool pinned = run.fixed != nullptr, guided = run.eta != nullptr;
+    if (run.seeded && (st = rng_table_ready(c, s)) != PP_OK) return st;
+    const PPRng rng = {c->rng_tab, (uint32_t)run.seed, (uint32_t)(run.seed >> 32)};
     const int nsteps = n_schedule - 1;
     // per-step scalars are kernel arguments: nothing is staged, nothing waits for the stream
     std::vector<StepParams> steps((size_t)nsteps);
     for (int j = 0; j < nsteps; j++) fill_step(&steps[j], schedule[j], schedule[j] - schedule[j + 1], c->plan->annealed_temp);
-    pp_status st;
     // (A hipGraph replay of the loop was measured and dropped: with no stray event records in the stream the kernel
     // trace shows back-to-back dispatches, and capture + replay was 2 % slower than plain launches.)
     flag_nonfinite(c, chi, 4, 4, s);
     // Guided run: nudge point j < nsteps sits in front of evaluation j, nudge point nsteps behind the last reverse step.  A point with
     // eta == 0 enqueues nothing: the evaluation in front of it keeps its fused next-step embedding.  An evaluation followed by a nudge
     // drops it (next = nullptr): the angles the next evaluation embeds exist only behind the nudge, which the embedding launch follows.
-    auto nudge_at = [&](int j) { return guide != nullptr && guide->eta[j] != 0.f; };
-    auto nudge = [&](int j) {
-        return pp_launch_guide_nudge(c, chi, part ? part->fixed : nullptr, guide->eta[j], guide->cap, guide->trace, n_schedule, j, s);
-    };
-    if (guide) {
-        if (guide->trace) PP_HIP_CHECK(hipMemsetAsync(guide->trace, 0xff, (size_t)c->B * n_schedule * sizeof(double), s));   // NaN
+    auto nudge_at = [&](int j) { return guided && run.eta[j] != 0.f; };
+    auto nudge = [&](int j) { return pp_launch_guide_nudge(c, chi, run.fixed, run.eta[j], run.cap, run.trace, n_schedule, j, s); };
+    if (guided) {
+        if (run.trace) PP_HIP_CHECK(hipMemsetAsync(run.trace, 0xff, (size_t)c->B * n_schedule * sizeof(double), s));   // NaN
         bool any = false;
-        for (int j = 0; j <= nsteps; j++) any = any || guide->eta[j] != 0.f;
+        for (int j = 0; j <= nsteps; j++) any = any || run.eta[j] != 0.f;
         if (any && (st = pp_launch_guide_begin(c, s)) != PP_OK) return st;
         if (nudge_at(0) && (st = nudge(0)) != PP_OK) return st;
     }
@@ -845,28 +839,19 @@ static pp_status sample_impl(const char *who, pp_ctx *c, float *chi, const float
     PPLive live = {nullptr, nullptr};
     const bool use_live = edge_live_on() && pp_edge_fused() && c->prof_which < 0;
     if (use_live) {
-        const int set = part ? 1 : 0;
-        if (part && (st = pp_launch_live_rows(c, 1, part->fixed, s)) != PP_OK) return st;
+        const int set = pinned ? 1 : 0;
+        if (pinned && (st = pp_launch_live_rows(c, 1, run.fixed, s)) != PP_OK) return st;
         live.rows = c->live_rows[set];
         live.mix = c->live_mix_set[set] ? c->live_mix[set] : nullptr;      // null: not filled, the mixed launch refuses it
     }
     for (int j = 0; j < nsteps; j++) {
-        PPPin pin = {nullptr, nullptr, nullptr, 0.f, 0};
-        if (part) {
-            // a fixed row arrives at the noise level of schedule[j + 1] like the free rows; after the last step it holds chi_ref itself
-            // (sigma(0) = 0.01 pi is not 0)
-            pin.fixed = part->fixed;
-            pin.chi_ref = part->chi_ref;
-            pin.traj = part->chi_traj ? part->chi_traj + (size_t)j * c->N * 4 : nullptr;
-            pin.sigma = sigma_f32(schedule[j + 1]);
-            pin.renoise = part->fix_mode == PP_FIX_RENOISE && j + 1 < nsteps ? 1 : 0;
-        }
+        const PPPin pin = pinned ? step_pin(run, schedule, j, nsteps, c->N) : PPPin{nullptr, nullptr, nullptr, 0.f, 0};
         const bool then_nudge = nudge_at(j + 1);
-        if ((st = run_network(c, s, j, PP_NU_STEP, chi, mode, sde_noise, &steps[j],
-                              j + 1 < nsteps && !then_nudge ? &steps[j + 1] : nullptr, rng, part ? &pin : nullptr,
-                              use_live ? &live : nullptr)) != PP_OK) return st;
-        if (guide && guide->chi_traj && !part)
-            PP_HIP_CHECK(hipMemcpyAsync(guide->chi_traj + (size_t)j * c->N * 4, chi, (size_t)c->N * 4 * sizeof(float),
+        const NodeEval ev = {chi, j, mode, run.sde_noise, &steps[j], j + 1 < nsteps && !then_nudge ? &steps[j + 1] : nullptr,
+                             run.seeded ? &rng : nullptr, pinned ? &pin : nullptr};
+        if ((st = run_network(c, s, PP_NU_STEP, ev, use_live ? &live : nullptr)) != PP_OK) return st;
+        if (guided && run.chi_traj && !pinned)
+            PP_HIP_CHECK(hipMemcpyAsync(run.chi_traj + (size_t)j * c->N * 4, chi, (size_t)c->N * 4 * sizeof(float),
                                         hipMemcpyDeviceToDevice, s));
         if (then_nudge) {
             if ((st = nudge(j + 1)) != PP_OK) return st;
@@ -1089,10 +1074,11 @@ extern "C" pp_status pp_debug_score_prefix(pp_ctx *c, const float *chi, float t,
     pp_status st = PP_OK;
     int k = 0;
     auto more = [&]() { return st == PP_OK && k++ < n_launches; };
+    const NodeEval ev = {nullptr, 0, PP_MODE_ODE, nullptr, &sp, nullptr, nullptr, nullptr};
     if (more()) st = pp_launch_node_embed(c, chi, sp, s);
     if (more()) st = pp_launch_node_message(c, 0, s);
     for (int l = 0; l < 3; l++) {
-        if (more()) st = pp_launch_node_update(c, l, l < 2 ? PP_NU_MID : PP_NU_SCORE, nullptr, 0, PP_MODE_ODE, nullptr, l < 2 ? nullptr : &sp, nullptr, s);
+        if (more()) st = pp_launch_node_update(c, l, l < 2 ? PP_NU_MID : PP_NU_SCORE, ev, s);
         if (l < 2 && more()) st = pp_launch_edge_update(c, l, true, s);     // every h_E stays readable
     }
     return st;

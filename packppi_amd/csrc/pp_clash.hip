@@ -876,6 +876,17 @@ pp_status pp_launch_clash(pp_ctx *c, const float *xyz, float *per_res, float *dc
     return PP_OK;
 }
 
+// The static candidate lists of a whole proximal loop or guided run (the backbone does not move): every row's partner residues and,
+// on a context that holds obstacle atoms, its obstacle candidates -- neither loop ever scans a complex's whole range
+static void launch_clash_candidates(pp_ctx *c, hipStream_t s) {
+    const pp_plan *p = c->plan;
+    hipLaunchKernelGGL(k_clash_cand, dim3(c->N), dim3(64 * CL_WAVES), 0, s, c->N, c->seg, c->b.X, c->b.atom_mask, c->b.residue_type,
+                       c->b.residue_index, p->side_extent, p->clash_tol, c->cand, c->cand_cnt);
+    if (c->obst_M > 0)
+        hipLaunchKernelGGL(k_obst_cand, dim3((c->N + 3) / 4), dim3(256), 0, s, c->N, c->b.X, c->b.atom_mask, c->b.residue_type,
+                           p->side_extent, p->clash_tol, c->obst, c->obst_row, c->obst_cand, c->obst_cnt);
+}
+
 // The proximal loop, per complex of the context: each has its own clash mask mean, 1 / n and loss row (losses [B][nsteps]), its
 // rows from the context's segment table (a B = 1 context is one complex, its losses are row 0).  fixed (device [N], or nullptr =
 // no pin): rows kept out of the clash mask (k_prox_init<true>); moved (device [N] or nullptr) receives that mask.
@@ -886,14 +897,8 @@ static pp_status prox_loop(pp_ctx *c, const float *chi, float lamda, int nsteps,
     // static partner candidates of the whole loop (the backbone does not move): k_clash<true> reads them instead of scanning
     static const char *scan_env = PP_GETENV("PP_CLASH_SCAN");          // diagnostic builds: 1 = the per-step scan of all partners (A/B)
     const bool cands = c->cand != nullptr && !(scan_env && atoi(scan_env));
-    if (cands)
-        hipLaunchKernelGGL(k_clash_cand, dim3(c->N), dim3(64 * CL_WAVES), 0, s, c->N, c->seg, c->b.X, c->b.atom_mask, c->b.residue_type,
-                           c->b.residue_index, p->side_extent, p->clash_tol, c->cand, c->cand_cnt);
-    // the same for the obstacle atoms of a context that holds some: the Adam loop never scans a complex's whole range
+    if (cands) launch_clash_candidates(c, s);       // the obstacle candidates only with the static lists
     const bool obst = c->obst_M > 0;
-    if (obst && cands)
-        hipLaunchKernelGGL(k_obst_cand, dim3((c->N + 3) / 4), dim3(256), 0, s, c->N, c->b.X, c->b.atom_mask, c->b.residue_type,
-                           p->side_extent, p->clash_tol, c->obst, c->obst_row, c->obst_cand, c->obst_cnt);
     const ClashObst O = obst ? clash_obst(c, cands) : ClashObst{};
     // clash mask at the incoming angles (optimize.py:5-18); per_res does not depend on the normaliser
     if ((st = pp_launch_atom14(c, chi, c->xyz, s)) != PP_OK) return st;
@@ -986,12 +991,7 @@ k_guide_trace(int N, const int32_t *__restrict__ off, const float *__restrict__ 
 // once per pp_sample_guided: the static partner lists and obstacle candidates of the proximal loop (the backbone does not move
 // during sampling either)
 pp_status pp_launch_guide_begin(pp_ctx *c, hipStream_t s) {
-    const pp_plan *p = c->plan;
-    hipLaunchKernelGGL(k_clash_cand, dim3(c->N), dim3(64 * CL_WAVES), 0, s, c->N, c->seg, c->b.X, c->b.atom_mask, c->b.residue_type,
-                       c->b.residue_index, p->side_extent, p->clash_tol, c->cand, c->cand_cnt);
-    if (c->obst_M > 0)
-        hipLaunchKernelGGL(k_obst_cand, dim3((c->N + 3) / 4), dim3(256), 0, s, c->N, c->b.X, c->b.atom_mask, c->b.residue_type,
-                           p->side_extent, p->clash_tol, c->obst, c->obst_row, c->obst_cand, c->obst_cnt);
+    launch_clash_candidates(c, s);
     PP_HIP_CHECK(hipGetLastError());
     return PP_OK;
 }

@@ -374,12 +374,18 @@ pp_status pp_launch_affinity_embed(pp_ctx *c, const pp_affinity *a, const int64_
 pp_status pp_launch_prepare(pp_ctx *c, hipStream_t s, const int64_t *E_idx = nullptr);   // E_idx: given neighbour lists instead of the kNN search
 pp_status pp_launch_node_embed(pp_ctx *c, const float *chi, const StepParams &sp, hipStream_t s);
 pp_status pp_launch_node_embed_rows(pp_ctx *c, const float *chi, const float *t_rows, hipStream_t s);   // a time per row (DEVICE [N])
-// cur: this step's scalars (layer 2 inside sampling); next: the next step, if its node embedding is to follow (else null)
-// rng (layer 2 inside seeded SDE sampling, else null): the reverse step draws its own noise, `noise` is not read
-// pin (layer 2 inside pp_sample_partial, else null; needs rng in either mode): the PINNED reverse step
-pp_status pp_launch_node_update(pp_ctx *c, int layer, int last_mode, float *chi, int step, int mode,
-                                const float *noise, const StepParams *cur, const StepParams *next, hipStream_t s,
-                                const PPRng *rng = nullptr, const PPPin *pin = nullptr);
+// What one network evaluation is given besides the context (host side; a single evaluation leaves all but `cur` zero).  The middle
+// layers read none of it but chi, step, mode and noise, which they hand to their kernel unread.
+struct NodeEval {
+    float *chi;                 // the angles the reverse step moves, or null
+    int step, mode;             // the step's index; PP_MODE_ODE / PP_MODE_SDE
+    const float *noise;         // pp_sample's sde noise tensor, or null
+    const StepParams *cur;      // layer 2: this step's scalars
+    const StepParams *next;     // layer 2 inside sampling: the next step, if its node embedding is to follow (else null)
+    const PPRng *rng;           // layer 2 inside seeded sampling, else null: the reverse step draws its own noise, `noise` is not read
+    const PPPin *pin;           // layer 2 inside pp_sample_partial, else null (needs rng in either mode): the PINNED reverse step
+};
+pp_status pp_launch_node_update(pp_ctx *c, int layer, int last_mode, const NodeEval &ev, hipStream_t s);
 pp_status pp_launch_edge_static(pp_ctx *c, hipStream_t s);
 #ifdef PP_EDGE_F16
 pp_status pp_launch_edge_embed_f16(pp_ctx *c, hipStream_t s);   // pp_edge_f16.hip: MFMA form of k_edge_embed

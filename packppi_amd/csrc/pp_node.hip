@@ -1328,25 +1328,49 @@ static PreW make_pre(const pp_plan *p, int layer, bool edge) {
     return w;
 }
 
+// Every instance of the node update that exists, once: node_attrs() sets the shared-memory attribute of each entry and the
+// launcher looks its kernel up here.  depth: the weight stages in flight (PP_NU_DEPTH_MULTI when a launch has more tiles than CUs:
+// the shallower ring, two workgroups per CU); split: workgroups per tile (middle layers of a launch that leaves most CUs idle);
+// seeded: the reverse step draws its own noise; pinned: the reverse step of pp_sample_partial, which draws in either mode.
+// (The compiler emits the instances in the order of the table: a reordering moves no instruction but changes the object file.)
+template <typename F>
+struct NuInstance {
+    int mode, depth, split;
+    bool seeded, pinned;
+    F fn;
+};
 typedef void (*nu_kernel_t)(NUpdArgs, float *, int, int, const float *, int, StepScalars, TimeEmb, PPRng, PPPin);
-// mode 0 / 1 / 2 = PP_NU_MID / PP_NU_STEP / PP_NU_SCORE; multi: more tiles than CUs (shallower ring, two workgroups per CU)
-static nu_kernel_t nu_kernel(int mode, bool multi) {
-    if (multi)
-        return mode == 0 ? k_node_update<PP_NU_MID, PP_NU_DEPTH_MULTI> : mode == 1 ? k_node_update<PP_NU_STEP, PP_NU_DEPTH_MULTI>
-                                                                                    : k_node_update<PP_NU_SCORE, PP_NU_DEPTH_MULTI>;
-    return mode == 0 ? k_node_update<PP_NU_MID, PP_NU_DEPTH> : mode == 1 ? k_node_update<PP_NU_STEP, PP_NU_DEPTH>
-                                                                          : k_node_update<PP_NU_SCORE, PP_NU_DEPTH>;
-}
-// the reverse step that draws its own noise: both launch depths
-static nu_kernel_t nu_kernel_seeded(bool multi) {
-    return multi ? k_node_update<PP_NU_STEP, PP_NU_DEPTH_MULTI, 1, true> : k_node_update<PP_NU_STEP, PP_NU_DEPTH, 1, true>;
-}
-// the reverse step of pp_sample_partial: both launch depths
-static nu_kernel_t nu_kernel_pinned(bool multi) {
-    return multi ? k_node_update<PP_NU_STEP, PP_NU_DEPTH_MULTI, 1, true, true> : k_node_update<PP_NU_STEP, PP_NU_DEPTH, 1, true, true>;
-}
-static nu_kernel_t nu_kernel_split(int cl) {
-    return cl == 4 ? k_node_update<PP_NU_MID, PP_NU_DEPTH, 4> : k_node_update<PP_NU_MID, PP_NU_DEPTH, 2>;
+static const NuInstance<nu_kernel_t> nu_table[] = {
+    {PP_NU_STEP, PP_NU_DEPTH_MULTI, 1, false, false, k_node_update<PP_NU_STEP, PP_NU_DEPTH_MULTI>},
+    {PP_NU_SCORE, PP_NU_DEPTH_MULTI, 1, false, false, k_node_update<PP_NU_SCORE, PP_NU_DEPTH_MULTI>},
+    {PP_NU_MID, PP_NU_DEPTH_MULTI, 1, false, false, k_node_update<PP_NU_MID, PP_NU_DEPTH_MULTI>},
+    {PP_NU_STEP, PP_NU_DEPTH, 1, false, false, k_node_update<PP_NU_STEP, PP_NU_DEPTH>},
+    {PP_NU_SCORE, PP_NU_DEPTH, 1, false, false, k_node_update<PP_NU_SCORE, PP_NU_DEPTH>},
+    {PP_NU_MID, PP_NU_DEPTH, 1, false, false, k_node_update<PP_NU_MID, PP_NU_DEPTH>},
+    {PP_NU_STEP, PP_NU_DEPTH_MULTI, 1, true, false, k_node_update<PP_NU_STEP, PP_NU_DEPTH_MULTI, 1, true>},
+    {PP_NU_STEP, PP_NU_DEPTH, 1, true, false, k_node_update<PP_NU_STEP, PP_NU_DEPTH, 1, true>},
+    {PP_NU_STEP, PP_NU_DEPTH_MULTI, 1, true, true, k_node_update<PP_NU_STEP, PP_NU_DEPTH_MULTI, 1, true, true>},
+    {PP_NU_STEP, PP_NU_DEPTH, 1, true, true, k_node_update<PP_NU_STEP, PP_NU_DEPTH, 1, true, true>},
+    {PP_NU_MID, PP_NU_DEPTH, 4, false, false, k_node_update<PP_NU_MID, PP_NU_DEPTH, 4>},
+    {PP_NU_MID, PP_NU_DEPTH, 2, false, false, k_node_update<PP_NU_MID, PP_NU_DEPTH, 2>},
+};
+#ifndef PP_EDGE_F16
+// the VALU kernel of the exact-fp32 library: no ring, no split
+typedef void (*nv_kernel_t)(NodeArgs, UpdW, float *, int, int, const float *, int, PreW, StepScalars, TimeEmb, PPRng, PPPin);
+static const NuInstance<nv_kernel_t> nv_table[] = {
+    {PP_NU_MID, 0, 1, false, false, k_node_update_valu<PP_NU_MID>},
+    {PP_NU_STEP, 0, 1, false, false, k_node_update_valu<PP_NU_STEP>},
+    {PP_NU_SCORE, 0, 1, false, false, k_node_update_valu<PP_NU_SCORE>},
+    {PP_NU_STEP, 0, 1, true, false, k_node_update_valu<PP_NU_STEP, true>},
+    {PP_NU_STEP, 0, 1, true, true, k_node_update_valu<PP_NU_STEP, true, true>},
+};
+#endif
+// the instance of `tab` with these properties, or null: there is none (the launcher refuses)
+template <typename F, size_t n>
+static F nu_find(const NuInstance<F> (&tab)[n], int mode, int depth, int split, bool seeded, bool pinned) {
+    for (const NuInstance<F> &k : tab)
+        if (k.mode == mode && k.depth == depth && k.split == split && k.seeded == seeded && k.pinned == pinned) return k.fn;
+    return nullptr;
 }
 static int g_nu_cus = 0;
 static pp_status node_attrs() {
@@ -1356,25 +1380,11 @@ static pp_status node_attrs() {
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(Smem)));
         PP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_node_embed_rows),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(Smem)));
-        for (int multi = 0; multi < 2; multi++)
-            for (int mode = 0; mode < 3; mode++)
-                PP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(nu_kernel(mode, multi != 0)),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(SmemU)));
-        for (int cl = 2; cl <= 4; cl += 2)
-            PP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(nu_kernel_split(cl)),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(SmemU)));
-        for (int multi = 0; multi < 2; multi++)
-            PP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(nu_kernel_seeded(multi != 0)),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(SmemU)));
-        for (int multi = 0; multi < 2; multi++)
-            PP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(nu_kernel_pinned(multi != 0)),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(SmemU)));
+        for (const auto &k : nu_table)
+            PP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k.fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(SmemU)));
 #ifndef PP_EDGE_F16
-        PP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_node_update_valu<PP_NU_MID>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(Smem)));
-        PP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_node_update_valu<PP_NU_STEP>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(Smem)));
-        PP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_node_update_valu<PP_NU_SCORE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(Smem)));
-        PP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_node_update_valu<PP_NU_STEP, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(Smem)));
-        PP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_node_update_valu<PP_NU_STEP, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(Smem)));
+        for (const auto &k : nv_table)
+            PP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k.fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(Smem)));
 #endif
         int dev = 0;
         hipDeviceProp_t prop;
@@ -1408,20 +1418,22 @@ pp_status pp_launch_node_embed_rows(pp_ctx *c, const float *chi, const float *t_
     return PP_OK;
 }
 
-pp_status pp_launch_node_update(pp_ctx *c, int layer, int last_mode, float *chi, int step, int mode,
-                                const float *noise, const StepParams *cur, const StepParams *next, hipStream_t s,
-                                const PPRng *rng, const PPPin *pin) {
-    const bool embed_next_step = next != nullptr;
+pp_status pp_launch_node_update(pp_ctx *c, int layer, int last_mode, const NodeEval &ev, hipStream_t s) {
+    float *const chi = ev.chi;
+    const int step = ev.step;
+    const float *const noise = ev.noise;
+    // the middle layers take no step scalars, only the reverse step is followed by the next step's embedding
+    const StepParams *cur = last_mode != PP_NU_MID ? ev.cur : nullptr, *next = last_mode == PP_NU_STEP ? ev.next : nullptr;
     // the pinned instances (pp_sample_partial) draw in either mode: a fixed row re-noises with the step's draws
-    const bool pinned = pin != nullptr && last_mode == PP_NU_STEP;
-    if (pinned && (rng == nullptr || rng->tab == nullptr || pin->fixed == nullptr || pin->chi_ref == nullptr)) {
+    const bool pinned = ev.pin != nullptr && last_mode == PP_NU_STEP;
+    if (pinned && (ev.rng == nullptr || ev.rng->tab == nullptr || ev.pin->fixed == nullptr || ev.pin->chi_ref == nullptr)) {
         pp_set_error("pp_launch_node_update: the pinned reverse step needs the rng table, fixed and chi_ref");
         return PP_ERR_INVALID;
     }
     // the seeded instances exist for the reverse step in sde mode only (ode draws nothing)
-    const bool seeded = rng != nullptr && rng->tab != nullptr && last_mode == PP_NU_STEP && (mode == PP_MODE_SDE || pinned);
-    const PPRng rg = seeded ? *rng : PPRng{nullptr, 0u, 0u};
-    const PPPin pn = pinned ? *pin : PPPin{nullptr, nullptr, nullptr, 0.f, 0};
+    const bool seeded = ev.rng != nullptr && ev.rng->tab != nullptr && last_mode == PP_NU_STEP && (ev.mode == PP_MODE_SDE || pinned);
+    const PPRng rg = seeded ? *ev.rng : PPRng{nullptr, 0u, 0u};
+    const PPPin pn = pinned ? *ev.pin : PPPin{nullptr, nullptr, nullptr, 0.f, 0};
     pp_status st0 = node_attrs();
     if (st0 != PP_OK) return st0;
     if ((last_mode == PP_NU_MID) != (layer < 2)) {
@@ -1447,9 +1459,9 @@ pp_status pp_launch_node_update(pp_ctx *c, int layer, int last_mode, float *chi,
     A.ptsE = c->ptsE; A.PAe = c->PAe; A.PCe = c->PCe;
     A.score = c->score;
     A.sat = c->sat;
-    int embed_next = (last_mode == PP_NU_STEP && embed_next_step) ? 1 : 0;    // node embedding for step + 1 afterwards
+    const int embed_next = next != nullptr ? 1 : 0;    // node embedding for step + 1 afterwards
     const dim3 grid((c->N + 15) / 16), block(512);
-    const int sde = mode == PP_MODE_SDE ? 1 : 0;
+    const int sde = ev.mode == PP_MODE_SDE ? 1 : 0;
     StepScalars sp = {0.f, 0.f, 0.f, 0.f};
     TimeEmb te = {};
     if (cur) sp = {cur->c_ode, cur->w, cur->c_drift, cur->c_diff};
@@ -1474,18 +1486,9 @@ pp_status pp_launch_node_update(pp_ctx *c, int layer, int last_mode, float *chi,
             W.d2_outT = p->d2_out_T; W.d2_out_b = p->w + p->off.d2_out_b;
             const PreW pre0 = make_pre(p, 0, false);
             const dim3 vgrid((c->N + NB - 1) / NB), vblock(NT);
-            const auto kv_seeded = k_node_update_valu<PP_NU_STEP, true>;
-            const auto kv_pinned = k_node_update_valu<PP_NU_STEP, true, true>;
-            if (last_mode == PP_NU_MID)
-                PP_LAUNCH(c, k_node_update_valu<PP_NU_MID>, vgrid, vblock, sizeof(Smem), s, NA, W, chi, step, sde, noise, embed_next, pre0, sp, te, rg, pn);
-            else if (pinned)
-                PP_LAUNCH(c, kv_pinned, vgrid, vblock, sizeof(Smem), s, NA, W, chi, step, sde, noise, embed_next, pre0, sp, te, rg, pn);
-            else if (seeded)
-                PP_LAUNCH(c, kv_seeded, vgrid, vblock, sizeof(Smem), s, NA, W, chi, step, sde, noise, embed_next, pre0, sp, te, rg, pn);
-            else if (last_mode == PP_NU_STEP)
-                PP_LAUNCH(c, k_node_update_valu<PP_NU_STEP>, vgrid, vblock, sizeof(Smem), s, NA, W, chi, step, sde, noise, embed_next, pre0, sp, te, rg, pn);
-            else
-                PP_LAUNCH(c, k_node_update_valu<PP_NU_SCORE>, vgrid, vblock, sizeof(Smem), s, NA, W, chi, step, sde, noise, embed_next, pre0, sp, te, rg, pn);
+            const nv_kernel_t kv = nu_find(nv_table, last_mode, 0, 1, seeded, pinned);
+            if (!kv) FAIL(PP_ERR_UNSUPPORTED, "pp_launch_node_update: no such instance of k_node_update_valu");
+            PP_LAUNCH(c, kv, vgrid, vblock, sizeof(Smem), s, NA, W, chi, step, sde, noise, embed_next, pre0, sp, te, rg, pn);
             PP_HIP_CHECK(hipGetLastError());
             return PP_OK;
         }
@@ -1502,13 +1505,10 @@ pp_status pp_launch_node_update(pp_ctx *c, int layer, int last_mode, float *chi,
         // workgroup that starts late (a shared GPU, a busy chip) still reads what it must; the context's pointers swap
         A.hV_out = c->hV_alt;
         std::swap(c->hV, c->hV_alt);
-        PP_LAUNCH(c, nu_kernel_split(cl), dim3(tiles * cl), block, sizeof(SmemU), s, A, chi, step, sde, noise, embed_next, sp, te, rg, pn);
-        PP_HIP_CHECK(hipGetLastError());
-        return PP_OK;
     }
-    const nu_kernel_t kern = pinned ? nu_kernel_pinned(multi)
-                             : seeded ? nu_kernel_seeded(multi) : nu_kernel(last_mode == PP_NU_MID ? 0 : last_mode == PP_NU_STEP ? 1 : 2, multi);
-    PP_LAUNCH(c, kern, grid, block, sizeof(SmemU), s, A, chi, step, sde, noise, embed_next, sp, te, rg, pn);
+    const nu_kernel_t kern = nu_find(nu_table, last_mode, cl > 1 || !multi ? PP_NU_DEPTH : PP_NU_DEPTH_MULTI, cl, seeded, pinned);
+    if (!kern) FAIL(PP_ERR_UNSUPPORTED, "pp_launch_node_update: no such instance of k_node_update");
+    PP_LAUNCH(c, kern, dim3(tiles * cl), block, sizeof(SmemU), s, A, chi, step, sde, noise, embed_next, sp, te, rg, pn);
     PP_HIP_CHECK(hipGetLastError());
     return PP_OK;
 }

@@ -161,6 +161,17 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
+def _host_f32(seq):
+    """A schedule (or the guide's step sizes) as the sampling exports read it: a contiguous float32 array on the host."""
+    return np.ascontiguousarray(torch.as_tensor(seq, dtype=torch.float32).cpu().numpy())
+
+
+def _mode_code(mode) -> int:      # PP_MODE_ODE / PP_MODE_SDE
+    if mode not in ("ode", "sde"):
+        raise NotImplementedError(mode)
+    return 0 if mode == "ode" else 1
+
+
 def _seed64(seed) -> int:
     """A seed or complex key as the unsigned 64-bit number the generator takes (negative values wrap)."""
     return int(seed) & 0xFFFFFFFFFFFFFFFF
@@ -402,8 +413,7 @@ class Context:
         return torch.empty(*shape, dtype=dtype, device=self.plan.device)
 
     def _chi(self, chi):
-        chi = chi.to(device=self.plan.device, dtype=torch.float32).reshape(self.B, self.L, 4).contiguous()
-        return chi
+        return chi.to(device=self.plan.device, dtype=torch.float32).reshape(self.B, self.L, 4).contiguous()
 
     def graph(self):
         E = self._new(self.B, self.L, self.K, dtype=torch.int64)
@@ -442,6 +452,19 @@ class Context:
         if t.numel() != self.n_rows * width:
             raise ValueError(f"{what} has {t.numel()} elements, this context has {self.n_rows} rows x {width}")
         return t
+
+    def _mask(self, t, what):
+        """A per-row mask (one element per row, host or device; non-zero = set) as the exports read it: uint8 [N] on the device."""
+        t = torch.as_tensor(t).to(device=self.plan.device)
+        if t.numel() != self.n_rows:
+            raise ValueError(f"{what} has {t.numel()} elements, this context has {self.n_rows} rows")
+        return (t != 0).to(torch.uint8).reshape(-1).contiguous()
+
+    def _xyz(self, xyz):
+        xyz = xyz.to(device=self.plan.device, dtype=torch.float32).contiguous()
+        if xyz.numel() != self.n_rows * 42:
+            raise ValueError(f"xyz has {xyz.numel()} elements, this context has {self.n_rows} rows x 14 x 3")
+        return xyz
 
     def score_rows(self, chi, t_rows):
         """``score`` with a time per row ([B*L], packed: [N]): pp_score_rows.  ``t_rows`` is not modified."""
@@ -498,14 +521,13 @@ class Context:
         """``seed``: the sde draws come from the device generator inside the reverse step (pp_sample_seeded; no noise tensor);
         ``sde_noise`` must then be None.  Without a seed: pp_sample."""
         chi = self._chi(chi).clone()
-        sched = np.ascontiguousarray(torch.as_tensor(schedule, dtype=torch.float32).cpu().numpy())
-        if mode not in ("ode", "sde"):
-            raise NotImplementedError(mode)
+        sched = _host_f32(schedule)
+        md = _mode_code(mode)
         if seed is not None:
             if sde_noise is not None:
                 raise ValueError("seed and sde_noise exclude each other: the seeded sampler draws its own noise")
-            _check(load().pp_sample_seeded(self.handle, _ptr(chi), sched.ctypes.data, int(len(sched)), 0 if mode == "ode" else 1,
-                                           _seed64(seed), _stream(self.plan.device)), "pp_sample_seeded")
+            _check(load().pp_sample_seeded(self.handle, _ptr(chi), sched.ctypes.data, int(len(sched)), md, _seed64(seed),
+                                           _stream(self.plan.device)), "pp_sample_seeded")
             return chi
         nz = None
         if mode == "sde":
@@ -513,8 +535,8 @@ class Context:
                 raise RuntimeError("sde sampling needs the per-step noise tensor")
             nz = sde_noise.to(device=self.plan.device, dtype=torch.float32).contiguous()
             assert nz.numel() == (len(sched) - 1) * 2 * self.B * self.L * 4
-        _check(load().pp_sample(self.handle, _ptr(chi), sched.ctypes.data, int(len(sched)), 0 if mode == "ode" else 1,
-                                _ptr(nz), _stream(self.plan.device)), "pp_sample")
+        _check(load().pp_sample(self.handle, _ptr(chi), sched.ctypes.data, int(len(sched)), md, _ptr(nz), _stream(self.plan.device)),
+               "pp_sample")
         return chi
 
     def sample_partial(self, chi, chi_ref, fixed, schedule, mode, seed, fix_mode="renoise", trajectory=False):
@@ -523,21 +545,16 @@ class Context:
         ``chi_ref`` at every step) or "renoise" (``chi_ref`` re-noised to each step's level with that step's own draws; ``chi_ref``
         after the last step).  ``chi`` is the step-0 state of EVERY row -- the call does not initialise the fixed ones.  Returns the
         sample [B, L, 4], with ``trajectory`` also the angles after every step [n_steps, B, L, 4]."""
-        if mode not in ("ode", "sde"):
-            raise NotImplementedError(mode)
+        md = _mode_code(mode)
         if fix_mode not in FIX_MODES:
             raise ValueError(f"fix_mode must be one of {sorted(FIX_MODES)}")
         chi = self._chi(chi).clone()
         ref = self._chi(chi_ref)
-        fx = torch.as_tensor(fixed).to(device=self.plan.device)
-        if fx.numel() != self.n_rows:
-            raise ValueError(f"fixed has {fx.numel()} elements, this context has {self.n_rows} rows")
-        fx = (fx != 0).to(torch.uint8).reshape(-1).contiguous()
-        sched = np.ascontiguousarray(torch.as_tensor(schedule, dtype=torch.float32).cpu().numpy())
+        fx = self._mask(fixed, "fixed")
+        sched = _host_f32(schedule)
         traj = self._new(max(len(sched) - 1, 0), self.B, self.L, 4) if trajectory else None
         _check(load().pp_sample_partial(self.handle, _ptr(chi), _ptr(ref), _ptr(fx), FIX_MODES[fix_mode], sched.ctypes.data,
-                                        int(len(sched)), 0 if mode == "ode" else 1, _seed64(seed), _ptr(traj),
-                                        _stream(self.plan.device)), "pp_sample_partial")
+                                        int(len(sched)), md, _seed64(seed), _ptr(traj), _stream(self.plan.device)), "pp_sample_partial")
         return (chi, traj) if trajectory else chi
 
     def sample_guided(self, chi, schedule, mode, seed, eta, cap=0.1, chi_ref=None, fixed=None, fix_mode="renoise",
@@ -550,29 +567,24 @@ class Context:
         ``sample_partial``.  Needs a packed or B = 1 context.  Returns the sample [B, L, 4]; with ``trajectory`` also the angles after
         every reverse step [n_steps, B, L, 4] (in front of the nudge that follows); with ``want_trace`` also the mean clash of every
         segment in front of every nudge, fp64 [n_segments, n_schedule], NaN where ``eta`` is 0.  No host synchronisation."""
-        if mode not in ("ode", "sde"):
-            raise NotImplementedError(mode)
+        md = _mode_code(mode)
         if (chi_ref is None) != (fixed is None):
             raise ValueError("chi_ref and fixed go together: give both (a pinned run) or neither")
         if fixed is not None and fix_mode not in FIX_MODES:
             raise ValueError(f"fix_mode must be one of {sorted(FIX_MODES)}")
-        sched = np.ascontiguousarray(torch.as_tensor(schedule, dtype=torch.float32).cpu().numpy())
-        et = np.ascontiguousarray(torch.as_tensor(eta, dtype=torch.float32).cpu().numpy()).reshape(-1)
+        sched = _host_f32(schedule)
+        et = _host_f32(eta).reshape(-1)
         if et.size != sched.size:
             raise ValueError(f"eta has {et.size} entries, the schedule has {sched.size} times (one nudge point per time)")
         self.plan.set_clash_params(vtf, tol)
         chi = self._chi(chi).clone()
         ref = fx = None
         if fixed is not None:
-            ref = self._chi(chi_ref)
-            fx = torch.as_tensor(fixed).to(device=self.plan.device)
-            if fx.numel() != self.n_rows:
-                raise ValueError(f"fixed has {fx.numel()} elements, this context has {self.n_rows} rows")
-            fx = (fx != 0).to(torch.uint8).reshape(-1).contiguous()
+            ref, fx = self._chi(chi_ref), self._mask(fixed, "fixed")
         traj = self._new(max(len(sched) - 1, 0), self.B, self.L, 4) if trajectory else None
         trace = self._new(self.n_segments, len(sched), dtype=torch.float64) if want_trace else None
         _check(load().pp_sample_guided(self.handle, _ptr(chi), _ptr(ref), _ptr(fx), FIX_MODES.get(fix_mode, 1), sched.ctypes.data,
-                                       int(len(sched)), 0 if mode == "ode" else 1, _seed64(seed if seed is not None else 0),
+                                       int(len(sched)), md, _seed64(seed if seed is not None else 0),
                                        et.ctypes.data, float(cap), _ptr(traj), _ptr(trace), _stream(self.plan.device)),
                "pp_sample_guided")
         out = (chi,) + ((traj,) if trajectory else ()) + ((trace,) if want_trace else ())
@@ -639,10 +651,7 @@ class Context:
             _check(load().pp_proximal_packed(self.handle, _ptr(chi), float(lamda), int(num_steps), nrp, _ptr(traj), _ptr(last),
                                              _ptr(accepted), _ptr(losses), _stream(self.plan.device)), "pp_proximal_packed")
             return traj, last, accepted, losses
-        fx = torch.as_tensor(fixed).to(device=self.plan.device)
-        if fx.numel() != self.n_rows:
-            raise ValueError(f"fixed has {fx.numel()} elements, this context has {self.n_rows} rows")
-        fx = (fx != 0).to(torch.uint8).reshape(-1).contiguous()
+        fx = self._mask(fixed, "fixed")
         moved = self._new(self.B, self.L, dtype=torch.uint8) if return_moved else None
         _check(load().pp_proximal_pinned(self.handle, _ptr(chi), _ptr(fx), float(lamda), int(num_steps), nrp, _ptr(traj), _ptr(last),
                                          _ptr(accepted), _ptr(losses), _ptr(moved), _stream(self.plan.device)), "pp_proximal_pinned")
@@ -722,14 +731,9 @@ class Context:
         ``~shell`` is the ``fixed`` mask of ``sample_partial`` / ``proximal_packed``.  No host synchronisation."""
         if mode not in SHELL_MODES:
             raise ValueError(f"mode must be one of {sorted(SHELL_MODES)}")
-        sd = torch.as_tensor(seeds).to(device=self.plan.device)
-        if sd.numel() != self.n_rows:
-            raise ValueError(f"seeds has {sd.numel()} elements, this context has {self.n_rows} rows")
-        sd = (sd != 0).to(torch.uint8).reshape(-1).contiguous()
+        sd = self._mask(seeds, "seeds")
         if xyz is not None:
-            xyz = xyz.to(device=self.plan.device, dtype=torch.float32).contiguous()
-            if xyz.numel() != self.n_rows * 42:
-                raise ValueError(f"xyz has {xyz.numel()} elements, this context has {self.n_rows} rows x 14 x 3")
+            xyz = self._xyz(xyz)
         out = self._new(self.B, self.L, dtype=torch.uint8)
         count = self._new(self.n_segments, dtype=torch.int32) if want_count else None
         _check(load().pp_ctx_shell(self.handle, _ptr(sd), SHELL_MODES[mode], float(radius), SHELL_OTHER_CHAIN if other_chain else 0,
@@ -754,9 +758,7 @@ class Context:
         if chi is not None:
             xyz = self.atom14(chi)
         elif xyz is not None:
-            xyz = xyz.to(device=dev, dtype=torch.float32).contiguous()
-            if xyz.numel() != self.n_rows * 42:
-                raise ValueError(f"xyz has {xyz.numel()} elements, this context has {self.n_rows} rows x 14 x 3")
+            xyz = self._xyz(xyz)
         if radius is None:
             if getattr(self, "_sasa_radius", None) is None:
                 if self._t.get("atom_mask") is None:

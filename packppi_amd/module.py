@@ -81,6 +81,47 @@ def read_checkpoint_state_dict(path, map_location="cpu") -> Dict[str, torch.Tens
     return {k: v for k, v in sd.items() if isinstance(v, torch.Tensor)}
 
 
+def _sampling_refusals(cfg, schedule, batch, use_proximal, return_list, sde_noise, seed, fixed_mask, fixed_mode, return_trajectory,
+                       guide):
+    """Every refusal of ``sampling``, in the order a call with several faults has always met them.  Returns the guide's keywords
+    for ``Context.sample_guided`` (None without a guide)."""
+    gkw = None
+    if guide is not None:
+        from .schedule import resolve_guide
+        eta, cap = resolve_guide(guide, schedule)
+        if sde_noise is not None:
+            raise ValueError("guide and sde_noise exclude each other: guided sde sampling draws its noise from the seeded generator")
+        if seed is None and cfg.mode == "sde":
+            raise ValueError("guide needs seed in sde mode: the guided sampler draws its noise inside the reverse step")
+        if seed is None and fixed_mask is not None:
+            raise ValueError("guide with fixed_mask needs seed: the fixed rows are re-noised with the seeded generator's draws")
+        if return_trajectory and use_proximal:
+            raise ValueError("return_trajectory with guide returns the sampler's trajectory: run the proximal stage separately")
+        if _get(batch, "seg_offsets") is None and int(batch.num_proteins) != 1:
+            raise ValueError("guide needs a B = 1 batch or a packed one (batch.pack), not a padded B > 1 batch")
+        gkw = dict(eta=eta, cap=cap, vtf=cfg.violation_tolerance_factor, tol=cfg.clash_overlap_tolerance)
+    if fixed_mask is not None:
+        if seed is None:
+            raise ValueError("fixed_mask needs seed: the fixed rows are re-noised with the seeded generator's draws")
+        if sde_noise is not None:
+            raise ValueError("fixed_mask and sde_noise exclude each other: partial repacking draws its own noise")
+        if use_proximal:
+            raise ValueError("fixed_mask with use_proximal=True is not supported here: this proximal stage has no pin and would "
+                             "move the fixed rows; repack(batch, fixed_mask, seed=..., use_proximal=True) runs the pinned one")
+        from .lib import FIX_MODES
+        if fixed_mode not in FIX_MODES:
+            raise ValueError(f"fixed_mode must be one of {sorted(FIX_MODES)}")
+        return gkw
+    if return_trajectory and guide is None:
+        raise ValueError("return_trajectory needs fixed_mask (the trajectory is written by the partial sampler)")
+    if _get(batch, "seg_offsets") is not None and use_proximal and return_list:
+        raise ValueError("return_list=True needs a B = 1 batch; for a packed batch use "
+                         "functional.proximal_optimizer_packed (per-complex losses [n_complexes, num_steps])")
+    if seed is not None and sde_noise is not None:
+        raise ValueError("seed and sde_noise exclude each other: the seeded sampler draws its own noise")
+    return gkw
+
+
 class TDiffusionModule:
     NUM_CHI_ANGLES = 4
     eps = 1e-6
@@ -308,84 +349,58 @@ class TDiffusionModule:
         sde mode and with ``fixed_mask`` (fixed rows are never nudged); excludes ``sde_noise``; a packed or B = 1 batch.  With
         ``return_trajectory``: (sample, angles after every reverse step, mean clash in front of every nudge, fp64
         [n_complexes, n_schedule], NaN where no nudge runs).  ``use_proximal`` runs behind it, as today."""
-        cfg = self.hparams.sample_cfg
         if fixed_mask is None:
             fixed_mask = _get(batch, "fixed_mask")
-        eta = cap = None
-        if guide is not None:
-            from .schedule import resolve_guide
-            eta, cap = resolve_guide(guide, self.schedule)
-            if sde_noise is not None:
-                raise ValueError("guide and sde_noise exclude each other: guided sde sampling draws its noise from the seeded generator")
-            if seed is None and cfg.mode == "sde":
-                raise ValueError("guide needs seed in sde mode: the guided sampler draws its noise inside the reverse step")
-            if seed is None and fixed_mask is not None:
-                raise ValueError("guide with fixed_mask needs seed: the fixed rows are re-noised with the seeded generator's draws")
-            if return_trajectory and use_proximal:
-                raise ValueError("return_trajectory with guide returns the sampler's trajectory: run the proximal stage separately")
-            if _get(batch, "seg_offsets") is None and int(batch.num_proteins) != 1:
-                raise ValueError("guide needs a B = 1 batch or a packed one (batch.pack), not a padded B > 1 batch")
-            gkw = dict(eta=eta, cap=cap, vtf=cfg.violation_tolerance_factor, tol=cfg.clash_overlap_tolerance)
-        if fixed_mask is not None:
-            if seed is None:
-                raise ValueError("fixed_mask needs seed: the fixed rows are re-noised with the seeded generator's draws")
-            if sde_noise is not None:
-                raise ValueError("fixed_mask and sde_noise exclude each other: partial repacking draws its own noise")
-            if use_proximal:
-                raise ValueError("fixed_mask with use_proximal=True is not supported here: this proximal stage has no pin and would "
-                                 "move the fixed rows; repack(batch, fixed_mask, seed=..., use_proximal=True) runs the pinned one")
-            from .lib import FIX_MODES
-            if fixed_mode not in FIX_MODES:
-                raise ValueError(f"fixed_mode must be one of {sorted(FIX_MODES)}")
-            ctx = self._context(batch)
+        gkw = _sampling_refusals(self.hparams.sample_cfg, self.schedule, batch, use_proximal, return_list, sde_noise, seed, fixed_mask,
+                                 fixed_mode, return_trajectory, guide)
+        ctx = self._context(batch)
+        init, sde_noise, pin = self._initial_angles(ctx, batch, sde_noise, seed, fixed_mask, fixed_chi, fixed_mode)
+        out = self._run_sampler(ctx, init, sde_noise, seed, pin, return_trajectory, gkw)
+        if return_trajectory:
+            return out
+        return self._proximal_tail(batch, out, use_proximal, return_list)
+
+    def _initial_angles(self, ctx, batch, sde_noise, seed, fixed_mask, fixed_chi, fixed_mode):
+        """(the angles noised to t = 1, the sde noise tensor of an unseeded run or None, the pin's keywords or None).  Seeded: the
+        device generator's draws under the batch's keys; with a pin the fixed rows start from ``fixed_chi``, noised like the others
+        ("renoise") or clean ("hold").  Unseeded: torch's global generator, call for call as the reference draws."""
+        if seed is not None:
             ctx.set_rng_keys(_get(batch, "complex_keys"))
+        if fixed_mask is not None:
             fx = (torch.as_tensor(fixed_mask).to(self.device) != 0).reshape(ctx.B, ctx.L)
             ref = ctx._chi(batch.SC_D if fixed_chi is None else fixed_chi)
             init = ctx.add_noise(torch.where(fx.unsqueeze(-1), ref, ctx._chi(batch.SC_D)), 1.0, seed)
             if fixed_mode == "hold":
                 init = torch.where(fx.unsqueeze(-1), ref, init)
-            if guide is not None:
-                return self._guided(ctx, init, seed, return_trajectory, chi_ref=ref, fixed=fx, fix_mode=fixed_mode, **gkw)
-            return ctx.sample_partial(init, ref, fx, self.schedule, cfg.mode, seed, fixed_mode, trajectory=return_trajectory)
-        if return_trajectory and guide is None:
-            raise ValueError("return_trajectory needs fixed_mask (the trajectory is written by the partial sampler)")
-        packed = _get(batch, "seg_offsets") is not None
-        if packed and use_proximal and return_list:
-            raise ValueError("return_list=True needs a B = 1 batch; for a packed batch use "
-                             "functional.proximal_optimizer_packed (per-complex losses [n_complexes, num_steps])")
-        if seed is not None and sde_noise is not None:
-            raise ValueError("seed and sde_noise exclude each other: the seeded sampler draws its own noise")
-        if guide is not None:
-            ctx = self._context(batch)
-            if seed is not None:
-                ctx.set_rng_keys(_get(batch, "complex_keys"))
-                init = ctx.add_noise(batch.SC_D, 1.0, seed)
-            else:           # ode: the initial noising from torch's generator, as the unseeded path below draws it
-                t = torch.tensor([1.]).repeat_interleave(batch.max_size * batch.num_proteins).to(self.device)
-                init, _ = self.add_sc_noise(batch, t)
-            out = self._guided(ctx, init, seed, return_trajectory, **gkw)
-            if return_trajectory:
-                return out
-            SC_D_sample = out
-        elif seed is not None:
-            ctx = self._context(batch)
-            ctx.set_rng_keys(_get(batch, "complex_keys"))
-            SC_D_sample = ctx.sample(ctx.add_noise(batch.SC_D, 1.0, seed), self.schedule, cfg.mode, seed=seed)
-        else:
-            t = torch.tensor([1.]).repeat_interleave(batch.max_size * batch.num_proteins).to(self.device)
-            SC_D_sample, _ = self.add_sc_noise(batch, t)
-            n_steps = len(self.schedule) - 1
-            if cfg.mode == "sde" and sde_noise is None:
-                # the reference draws torch.normal(size=[B*L, 4], device=...) inside the loop, once per schedule and step, the
-                # 1pi schedule first (schedule.py:225, TorsionalDiffusion.py:271-274): the same calls in the same order, so a
-                # seed gives the stream it gives the reference on this device (one [n, 2, N, 4] draw would not)
-                shape = (batch.num_proteins * batch.max_size, 4)
-                sde_noise = torch.stack([torch.stack([torch.normal(mean=0, std=1, size=shape, device=self.device)
-                                                      for _ in range(2)]) for _ in range(n_steps)])
-            SC_D_sample = self._context(batch).sample(SC_D_sample, self.schedule, cfg.mode, sde_noise)
+            return init, None, dict(chi_ref=ref, fixed=fx, fix_mode=fixed_mode)
+        if seed is not None:
+            return ctx.add_noise(batch.SC_D, 1.0, seed), None, None
+        t = torch.tensor([1.]).repeat_interleave(batch.max_size * batch.num_proteins).to(self.device)
+        init, _ = self.add_sc_noise(batch, t)
+        if self.hparams.sample_cfg.mode == "sde" and sde_noise is None:
+            # the reference draws torch.normal(size=[B*L, 4], device=...) inside the loop, once per schedule and step, the
+            # 1pi schedule first (schedule.py:225, TorsionalDiffusion.py:271-274): the same calls in the same order, so a
+            # seed gives the stream it gives the reference on this device (one [n, 2, N, 4] draw would not)
+            shape = (batch.num_proteins * batch.max_size, 4)
+            sde_noise = torch.stack([torch.stack([torch.normal(mean=0, std=1, size=shape, device=self.device)
+                                                  for _ in range(2)]) for _ in range(len(self.schedule) - 1)])
+        return init, sde_noise, None
+
+    def _run_sampler(self, ctx, init, sde_noise, seed, pin, return_trajectory, gkw):
+        """The reverse diffusion on the context: guided, pinned, seeded or from the caller's noise tensor, each through its export."""
+        mode = self.hparams.sample_cfg.mode
+        if gkw is not None:
+            return self._guided(ctx, init, seed, return_trajectory, **(pin or {}), **gkw)
+        if pin is not None:
+            return ctx.sample_partial(init, pin["chi_ref"], pin["fixed"], self.schedule, mode, seed, pin["fix_mode"],
+                                      trajectory=return_trajectory)
+        return ctx.sample(init, self.schedule, mode, sde_noise, seed=seed)
+
+    def _proximal_tail(self, batch, SC_D_sample, use_proximal, return_list):
         if not use_proximal:
             return SC_D_sample
-        if packed:            # every complex optimised on its own terms, accept rule per complex on the device
+        cfg = self.hparams.sample_cfg
+        if _get(batch, "seg_offsets") is not None:            # every complex optimised on its own terms, accept rule per complex on the device
             return proximal_optimizer_packed(batch, SC_D_sample, cfg.violation_tolerance_factor, cfg.clash_overlap_tolerance,
                                              cfg.lamda, cfg.num_steps)[2]
         SC_D_resample_list, loss_list = proximal_optimizer(batch, SC_D_sample, cfg.violation_tolerance_factor,
@@ -453,6 +468,27 @@ class TDiffusionModule:
         seg = ctx.sasa(chi=chi).seg_area
         return seg[:, 1] - seg[:, 2]
 
+    @staticmethod
+    def _check_select(select):
+        from .lib import SELECT
+        if select not in SELECT:
+            raise ValueError(f"select must be one of 'clash', 'medoid' or None, got {select!r}")
+
+    def _reduce_ensemble(self, packed, chi, select, return_all, recombine, recombine_sweeps, sasa):
+        """What the two ensemble calls do with the decoys' angles: the per-residue clash, ``Context.ensemble_reduce``, the
+        recombination and the buried surface if asked for; the selected (or recombined) angles, or the ``return_all`` dict."""
+        cfg = self.hparams.sample_cfg
+        ctx, D = self._context(packed), int(packed.n_decoys)
+        per_res = ctx.clash(chi, cfg.violation_tolerance_factor, cfg.clash_overlap_tolerance)
+        res = ctx.ensemble_reduce(chi, D, per_res=per_res, select=select)
+        rec, extra = self._recombine(ctx, chi, D, res, recombine_sweeps) if recombine else (None, {})
+        if sasa and return_all:
+            extra = dict(extra, bsa=self._decoy_bsa(ctx, chi))
+        if not return_all:
+            return rec.chi if recombine else res.chi_best
+        return dict(decoys=(chi, packed), selected=res.chi_best, best=res.best, dev=res.dev, clash=res.clash, consensus=res.mean,
+                    confidence=res.resultant, keys=list(packed.complex_keys), **extra)
+
     def sample_ensemble(self, batch, n_decoys, *, seed=None, use_proximal: bool = False, select="clash", return_all: bool = False,
                         recombine: bool = False, recombine_sweeps: int = 64, sasa: bool = False, guide=None):
         """``n_decoys`` seeded samples of every complex in ONE packed pass, reduced on the device.  On
@@ -483,12 +519,10 @@ class TDiffusionModule:
         ``guide``: every decoy is sampled with clash guidance, as ``sampling(guide=...)`` samples the complex
         alone under the decoy's key; None = today's path."""
         from .batch import replicate, replicate_many
-        from .lib import SELECT
         if seed is None:
             raise ValueError("sample_ensemble needs seed: unseeded noise is laid out over the rows of the whole batch, so a decoy would "
                              "depend on its place in the packed batch; the seeded generator keys it by (seed, decoy key) alone")
-        if select not in SELECT:
-            raise ValueError(f"select must be one of 'clash', 'medoid' or None, got {select!r}")
+        self._check_select(select)
         if isinstance(batch, (list, tuple)):
             packed = replicate_many(batch, n_decoys)
         else:
@@ -497,18 +531,8 @@ class TDiffusionModule:
             packed = replicate(batch, n_decoys)
         if _get(packed, "fixed_mask") is not None:
             raise ValueError("ensembles under a fixed_mask are not supported: sample_ensemble samples every row")
-        cfg = self.hparams.sample_cfg
         chi = self.sampling(packed, use_proximal=use_proximal, seed=seed, guide=guide)
-        ctx = self._context(packed)
-        per_res = ctx.clash(chi, cfg.violation_tolerance_factor, cfg.clash_overlap_tolerance)
-        res = ctx.ensemble_reduce(chi, packed.n_decoys, per_res=per_res, select=select)
-        rec, extra = self._recombine(ctx, chi, int(packed.n_decoys), res, recombine_sweeps) if recombine else (None, {})
-        if sasa and return_all:
-            extra = dict(extra, bsa=self._decoy_bsa(ctx, chi))
-        if not return_all:
-            return rec.chi if recombine else res.chi_best
-        return dict(decoys=(chi, packed), selected=res.chi_best, best=res.best, dev=res.dev, clash=res.clash, consensus=res.mean,
-                    confidence=res.resultant, keys=list(packed.complex_keys), **extra)
+        return self._reduce_ensemble(packed, chi, select, return_all, recombine, recombine_sweeps, sasa)
 
     def repack_ensemble(self, batch, fixed_mask=None, *, n_decoys, seed, fixed_chi=None, fixed_mode="renoise",
                         use_proximal: bool = False, select="clash", return_all: bool = False, recombine: bool = False,
@@ -527,9 +551,7 @@ class TDiffusionModule:
         ``clash`` with the same weight in all decoys of a group, so they dilute both equally and do not change the ranking.
         Returns what ``sample_ensemble`` returns (``sasa``: the ``bsa`` key as there).  ``guide``: as in ``sampling``."""
         from .batch import Batch, replicate_many
-        from .lib import SELECT
-        if select not in SELECT:
-            raise ValueError(f"select must be one of 'clash', 'medoid' or None, got {select!r}")
+        self._check_select(select)
         single = not isinstance(batch, (list, tuple))
         if single and (_get(batch, "seg_offsets") is not None or int(batch.num_proteins) != 1):
             raise ValueError("repack_ensemble takes a B = 1 batch or a list of complexes")
@@ -561,19 +583,9 @@ class TDiffusionModule:
             ref = torch.cat([torch.as_tensor(c["SC_D"] if r is None else r).to(device=packed.SC_D.device, dtype=torch.float32)
                              .reshape(-1, 4)[:offs[g * D + 1] - offs[g * D]]
                              for g, (c, r) in enumerate(zip(complexes, refs)) for _ in range(D)]).unsqueeze(0)
-        cfg = self.hparams.sample_cfg
         chi = self.repack(packed, seed=seed, fixed_chi=ref, fixed_mode=fixed_mode, use_proximal=use_proximal,
                           norm_rows=[n for n in sizes for _ in range(D)] if use_proximal else None, guide=guide)
-        ctx = self._context(packed)
-        per_res = ctx.clash(chi, cfg.violation_tolerance_factor, cfg.clash_overlap_tolerance)
-        res = ctx.ensemble_reduce(chi, D, per_res=per_res, select=select)
-        rec, extra = self._recombine(ctx, chi, D, res, recombine_sweeps) if recombine else (None, {})
-        if sasa and return_all:
-            extra = dict(extra, bsa=self._decoy_bsa(ctx, chi))
-        if not return_all:
-            return rec.chi if recombine else res.chi_best
-        return dict(decoys=(chi, packed), selected=res.chi_best, best=res.best, dev=res.dev, clash=res.clash, consensus=res.mean,
-                    confidence=res.resultant, keys=list(packed.complex_keys), **extra)
+        return self._reduce_ensemble(packed, chi, select, return_all, recombine, recombine_sweeps, sasa)
 
     def mutate(self, proteins_and_mutations, *, seed, radius=10.0, shell="ca", n_decoys=1, use_proximal: bool = False,
                select="clash", fixed_mode="renoise", max_rows=200_000, log=print, recombine: bool = False,
@@ -608,7 +620,7 @@ class TDiffusionModule:
 
         ``guide``: the shell is sampled with clash guidance, as in ``sampling``; rows outside the shell are
         fixed rows, which are never nudged."""
-        from .batch import as_single, pack, unpack
+        from .batch import as_single, group_rows, pack, pad_rows, unpack
         from .featurize import mutant_model_data, parse_mutstr
         from .functional import _ctx_for
         from .lib import SHELL_MODES
@@ -628,21 +640,8 @@ class TDiffusionModule:
             b = as_single(data).to(self.device)
             b["complex_key"] = key
             sets.append(b)
-        groups, cur, rows_in = [], [], 0
-        for i, b in enumerate(sets):
-            n = int(b["max_size"])
-            if alone[i]:
-                groups.append([i])
-                continue
-            if cur and n_decoys * (rows_in + n) > max_rows:
-                groups.append(cur)
-                cur, rows_in = [], 0
-            cur.append(i)
-            rows_in += n
-        if cur:
-            groups.append(cur)
         results = [None] * len(sets)
-        for grp in groups:
+        for grp in group_rows([int(b["max_size"]) for b in sets], alone, max_rows, n_decoys):
             members = [sets[i] for i in grp]
             pb = pack(members)
             gctx = _ctx_for(pb)
@@ -650,13 +649,8 @@ class TDiffusionModule:
             sh = gctx.shell(pb.mut_mask, radius=radius, mode=shell, xyz=xyz)              # bool [1, N], stays on the device
             pinned = []
             for b, part in zip(members, unpack(pb, ~sh)):
-                n = int(b["max_size"])
-                fx = part
-                if part.shape[1] != n:            # pack() dropped trailing rows without a residue: they keep their (zero) angles
-                    fx = torch.ones(1, n, dtype=torch.bool, device=part.device)
-                    fx[:, :part.shape[1]] = part
                 p = type(b)(b)
-                p["fixed_mask"] = fx
+                p["fixed_mask"] = pad_rows(part, int(b["max_size"]), True)      # trailing rows pack() dropped keep their (zero) angles
                 pinned.append(p)
             out = self.repack_ensemble(pinned, n_decoys=n_decoys, seed=seed, fixed_mode=fixed_mode, use_proximal=use_proximal,
                                        select=select, return_all=True, recombine=recombine, recombine_sweeps=recombine_sweeps,
@@ -666,20 +660,15 @@ class TDiffusionModule:
             picks = unpack(pb, out["pick"].reshape(1, -1)) if recombine else [None] * len(members)
             parts = zip(grp, members, unpack(pb, final), unpack(pb, pos), unpack(pb, sh))
             for g, (i, b, chi, x, s) in enumerate(parts):
-                n, m = int(b["max_size"]), chi.shape[1]
-                if m != n:
-                    chi = torch.cat([chi, b["SC_D"][:, m:]], 1)
-                    x = torch.cat([x, b["X"][:, m:]], 1)
-                    s = torch.cat([s, torch.zeros(1, n - m, dtype=torch.bool, device=s.device)], 1)
+                n = int(b["max_size"])
+                chi, x, s = pad_rows(chi, n, b["SC_D"]), pad_rows(x, n, b["X"]), pad_rows(s, n, False)
                 results[i] = dict(tag=b["mutation_tag"], key=int(b["complex_key"]), SC_D=chi, X=x, shell=s, best=out["best"][g],
                                   clash=out["clash"][g * n_decoys:(g + 1) * n_decoys], dev=out["dev"][g * n_decoys:(g + 1) * n_decoys],
                                   keys=out["keys"][g * n_decoys:(g + 1) * n_decoys], batch=b)
                 if recombine:
                     pk = picks[g]
                     moved = (pk != out["best"][g]).sum()
-                    if m != n:
-                        pk = torch.cat([pk, out["best"][g].expand(1, n - m)], 1)
-                    results[i].update(pick=pk, clash_recombined=out["clash_trace"][g, -1], rows_recombined=moved)
+                    results[i].update(pick=pad_rows(pk, n, out["best"][g].expand(1, n)), clash_recombined=out["clash_trace"][g, -1], rows_recombined=moved)
                 if sasa:
                     results[i]["bsa"] = out["bsa"][g * n_decoys:(g + 1) * n_decoys]
         return results

@@ -134,7 +134,7 @@ def sample_sharded(model, complexes, use_proximal=False, group=None, init_chi=No
     independence of ``world``, ``rank``, ``max_rows`` and grouping.
     Complexes that carry obstacle atoms (``protein_to_batch(..., obstacles=...)``) are refused with ``ValueError``.
     Returns (chi per local complex id, ids_all, rows_all)."""
-    from .batch import has_obstacles, pack, unpack
+    from .batch import group_rows, has_obstacles, pack, pad_rows, unpack
     from .functional import proximal_optimizer, proximal_optimizer_packed
     if any(has_obstacles(c) for c in (complexes.values() if isinstance(complexes, dict) else complexes)):
         raise ValueError("sample_sharded does not support complexes with obstacle atoms (DESIGN.md section 19: out of scope)")
@@ -150,22 +150,12 @@ def sample_sharded(model, complexes, use_proximal=False, group=None, init_chi=No
         lengths = [int(c["max_size"]) for c in complexes]
     mine = shard_complexes(lengths, world)[rank]
     cfg = model.hparams.sample_cfg
-    groups, cur, rows_in = [], [], 0
     true_counts = (torch.stack([(complexes[i]["residue_mask"] > 0).sum() for i in mine]).tolist() if mine else [])   # one read-back
-    for i, n_true in zip(mine, true_counts):
-        n = int(complexes[i]["max_size"])
-        # K = min(32, L) is a property of the batch (encoder.py:115): a complex that is shorter than 32 rows once its trailing
-        # padding is dropped goes through the plain B = 1 path with its own tensors, as the reference would run it
-        if n_true < 32 or n < 32:
-            groups.append([i])
-            continue
-        if cur and rows_in + n > max_rows:
-            groups.append(cur)
-            cur, rows_in = [], 0
-        cur.append(i)
-        rows_in += n
-    if cur:
-        groups.append(cur)
+    mine_sizes = [int(complexes[i]["max_size"]) for i in mine]
+    # K = min(32, L) is a property of the batch (encoder.py:115): a complex that is shorter than 32 rows once its trailing
+    # padding is dropped goes through the plain B = 1 path with its own tensors, as the reference would run it
+    alone = [n_true < 32 or n < 32 for n_true, n in zip(true_counts, mine_sizes)]
+    groups = [[mine[k] for k in g] for g in group_rows(mine_sizes, alone, max_rows)]
     chis, row_of, proxed = {}, {}, set()
     cfg_prox = (cfg.violation_tolerance_factor, cfg.clash_overlap_tolerance, cfg.lamda, cfg.num_steps)
     for grp in groups:
@@ -184,9 +174,7 @@ def sample_sharded(model, complexes, use_proximal=False, group=None, init_chi=No
             elif packed_proximal:
                 proxed.update(grp)
             for i, chi in zip(grp, unpack(pb, out)):
-                full = torch.zeros(1, int(complexes[i]["max_size"]), 4, device=chi.device, dtype=chi.dtype)
-                full[:, :chi.shape[1]] = chi
-                chis[i] = full
+                chis[i] = pad_rows(chi, int(complexes[i]["max_size"]), fresh=True)
             continue
         if len(grp) == 1:
             i = grp[0]
@@ -215,13 +203,7 @@ def sample_sharded(model, complexes, use_proximal=False, group=None, init_chi=No
                                             cfg.num_steps, norm_rows=[int(complexes[i]["max_size"]) for i in grp])[2]
             proxed.update(grp)
         for i, chi in zip(grp, unpack(pb, out)):
-            L = int(complexes[i]["max_size"])
-            if chi.shape[1] == L:
-                chis[i] = chi
-            else:
-                full = torch.zeros(1, L, 4, device=chi.device, dtype=chi.dtype)
-                full[:, :chi.shape[1]] = chi
-                chis[i] = full
+            chis[i] = pad_rows(chi, int(complexes[i]["max_size"]))
     rows = []
     for i in mine:
         if use_proximal and i not in proxed and fixed_masks is not None:      # the per-complex pinned call, accept rule on the device
