@@ -287,6 +287,48 @@ pp_status pp_sample_guided(pp_ctx *ctx, float *chi, const float *chi_ref /* or N
                            float *chi_traj /* DEVICE [n_schedule-1,N,4] or NULL */,
                            double *clash_trace /* DEVICE [n_seg][n_schedule] or NULL */, void *stream);
 
+/* ---- Predictor-corrector sampling (SO2VESchedule.step_correct, schedule.py:238-273, which the reference's own sampling() never
+ * calls; csrc/pp_correct.hip holds the arithmetic) ------------------------------------------------------------
+ * pp_sample_seeded / pp_sample_partial (chi_ref and fixed given) / pp_sample_guided (eta given) with one Langevin corrector behind
+ * every reverse step j of the n = n_schedule - 1 whose snr[j] != 0.  It runs on the state x after reverse step j and its pin, at
+ * t' = schedule[j + 1]:
+ *   1. s = the network's score at (x, t'), the bits of pp_score(ctx, x, t'): all rows, one more evaluation;
+ *   2. an entry (r, k) is movable iff it is in the 1pi or the 2pi periodic mask, SC_D_mask != 0, row r is not fixed and s is finite;
+ *   3. z[r][k] = the N(0,1) draw of words (0, 1) of the seeded generator's counter at step 2^20 + j (the reverse steps use
+ *      0 .. 2^20 - 1, the initial noising -1: disjoint ranges; words 2, 3 unused), in PP_MODE_ODE too: the corrector always draws;
+ *   4. per segment of the ctx's segment table  s2 = sum (double)s^2,  n2 = sum (double)z^2  over its movable entries, fp64 in an
+ *      order that depends on (row in the complex, k) only, no atomics: the same bits alone, padded or anywhere in a packed batch;
+ *   5. eps = (float)(2 snr[j]^2 n2 / s2) (fp64 until the cast),  amp = (float)sqrt(2 (double)eps): step_correct's step size and noise
+ *      amplitude for ONE complex.  A segment without a movable entry, with s2 == 0 or with eps or amp not finite has no corrector
+ *      at this point: its entries keep their bits;
+ *   6. movable entries:  y = x + eps s;  y = y + amp z;  x' = wrap_pi(y) * SC_D_mask, every product and sum rounded in fp32, wrap_pi
+ *      the reverse step's.  Every other entry keeps its bits; fixed rows are never moved and never counted.
+ * Nudge j + 1 (if eta is given and eta[j + 1] != 0), the node embedding of evaluation j + 1 and that evaluation follow.
+ * NOT the reference to the letter: step_correct averages the two norms over the complexes of the batch and forms one step size,
+ * and it is called per periodic mask; here every complex has its own step size -- the same thing for one complex, and the only
+ * choice under which batching does not change a result -- and one corrector covers both masks.
+ *   snr         HOST [n_schedule - 1], read before the call returns; finite, not negative; 0 = no corrector behind that step;
+ *   eta         HOST [n_schedule] or NULL = no guide (cap, clash_trace and pp_sample_guided's preconditions then do not apply);
+ *   chi_traj    (or NULL) the state after reverse step j, IN FRONT OF corrector j; the returned chi includes the last corrector
+ *               and nudge;
+ *   corr_trace  (or NULL) DEVICE fp64 [n_seg][n_schedule - 1][4] = (s2, n2, eps, amp); NaN where snr[j] == 0 or the segment has no
+ *               corrector.
+ * Always seeded: seed and the ctx's rng keys as in pp_sample_seeded.  With snr all zero the call gives the bits of pp_sample_guided
+ * / pp_sample_partial / pp_sample_seeded with the same arguments and corr_trace is all NaN.  Works on packed, B = 1 and padded
+ * B > 1 contexts (with eta: the guide's restriction).  Cost of a corrected step: one evaluation, one launch of one workgroup per
+ * segment, and the node embedding launch of the next evaluation, which the reverse step in front can no longer fuse.  Never waits
+ * for the stream, reads nothing back.
+ * PP_ERR_INVALID: a null ctx, chi, schedule or snr; only one of chi_ref and fixed; chi_ref == chi; an unknown mode or (with a pin)
+ * fix_mode; snr[j] negative or not finite; a batch without SC_D_mask or the periodic masks; a geometry-only plan; with eta,
+ * everything pp_sample_guided refuses. */
+pp_status pp_sample_corrected(pp_ctx *ctx, float *chi, const float *chi_ref /* or NULL */,
+                              const uint8_t *fixed /* or NULL: both or neither */, int fix_mode, const float *schedule,
+                              int n_schedule, int mode, uint64_t seed, const float *snr /* HOST [n_schedule-1] */,
+                              const float *eta /* HOST [n_schedule] or NULL */, float cap,
+                              float *chi_traj /* DEVICE [n_schedule-1,N,4] or NULL */, double *clash_trace /* or NULL */,
+                              double *corr_trace /* DEVICE [n_seg][n_schedule-1][4] = (s2, n2, eps, amp) or NULL */,
+                              void *stream);
+
 /* Replaces get_atom14_coords(X, S, BB_D, SC_D) (components/__init__.py:76-120). xyz [B,L,14,3]. */
 pp_status pp_atom14(pp_ctx *ctx, const float *chi, float *xyz, void *stream);
 
@@ -553,7 +595,8 @@ pp_status pp_time_kernel(pp_ctx *ctx, int which, int iters, float *avg_ms, void 
 /* Measurement aid, no reference counterpart: in-situ duration of a hot kernel.  After
  * pp_profile_kernel(ctx, which) (0 node message, 1 edge update, 2 node update; 3 the one launch per Adam step
  * inside pp_proximal / pp_proximal_packed: clash loss + gradient, the step, the reconstruction at the new angles; 4, 5, 6 the
- * launches of a nudge of pp_sample_guided: reconstruction, clash loss + gradient + step, the node embedding behind it) every launch of that
+ * launches of a nudge of pp_sample_guided: reconstruction, clash loss + gradient + step, the node embedding behind it; 7 the corrector
+ * launch of pp_sample_corrected) every launch of that
  * kernel made by pp_score / pp_sample / pp_proximal carries a start / stop HIP event pair on the launch stream
  * (hipExtLaunchKernelGGL: the dispatch's own begin and end, the interval rocprofv3's kernel trace reports);
  * pp_profile_read waits for the last one, returns the summed intervals (ms) and the number of

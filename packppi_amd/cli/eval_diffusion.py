@@ -38,6 +38,11 @@ loss, obstacle atoms included, at most RAD radians per angle, from time T of the
 defaults (0.02, late from 0.3, 0.1 rad) are starting values, not tuned against a trained checkpoint.  Combines with --repack,
 --n_decoys and --use_proximal; needs --seed with --repack and in sde mode.  Writes guide.csv (complex or decoy, nudge point, t, eta,
 mean clash in front of that nudge; empty where no nudge runs) and prints the first and last traced clash.
+--corrector SNR [--corrector_from T] (without --corrector every output byte as before): predictor-corrector
+sampling -- behind every reverse step but the last, from time T of the schedule on (default 1: everywhere), one more network
+evaluation and a Langevin step of signal-to-noise ratio SNR with a step size per complex.  0.16 is the reference's constant
+(step_correct); nothing here is tuned against a trained checkpoint.  Needs --seed; combines with --repack, --n_decoys, --guide and
+--use_proximal.  Writes corrector.csv (step, t, complex or decoy, s2, n2, eps, amp; empty where no corrector ran).
 """
 import argparse
 import os
@@ -127,6 +132,49 @@ def write_guide_csv(model, outdir):
         print(f"----- guide: mean clash in front of the first nudge {first:.4f}, in front of the last {last:.4f} -----")
     else:
         print("----- guide: no nudge ran (every eta is 0) -----")
+
+
+def add_corrector_arguments(p):
+    """--corrector and --corrector_from.  Their defaults are SUPPRESSed, like the guide's."""
+    S = argparse.SUPPRESS
+    p.add_argument("--corrector", type=float, default=S, metavar="SNR", help="Predictor-corrector sampling (DESIGN.md section 23): one "
+                   "Langevin corrector of this signal-to-noise ratio behind every reverse step but the last, with a step size per "
+                   "complex; 0.16 is the reference's constant (step_correct), nothing here is tuned against a trained checkpoint. "
+                   "Needs --seed. Writes corrector.csv.")
+    p.add_argument("--corrector_from", type=float, default=S, metavar="T", help="With --corrector: correct where the schedule's time "
+                   "behind the step is at most T (default 1: everywhere).")
+
+
+def corrector_from_args(args, p=None):
+    """The ``corrector`` dict of ``TDiffusionModule.sampling`` from the command line, None without --corrector."""
+    if not hasattr(args, "corrector"):
+        if hasattr(args, "corrector_from") and p is not None:
+            p.error("--corrector_from belongs to --corrector")
+        return None
+    c = dict(snr=args.corrector)
+    if hasattr(args, "corrector_from"):
+        c["t_on"] = args.corrector_from
+    if p is not None:
+        if not (np.isfinite(c["snr"]) and c["snr"] >= 0):
+            p.error("--corrector must be a finite, non-negative signal-to-noise ratio")
+        if not np.isfinite(c.get("t_on", 1.0)):
+            p.error("--corrector_from must be finite")
+        if getattr(args, "seed", None) is None:
+            p.error("--corrector needs --seed (the corrector draws its noise from the seeded generator)")
+    return c
+
+
+def write_corrector_csv(model, outdir):
+    """corrector.csv from ``model.corrector_traces``: one line per (reverse step, complex or decoy); empty where no corrector ran."""
+    sched = [float(t) for t in model.schedule]
+    rows, n = ["step,t,complex,s2,n2,eps,amp"], 0
+    for _, trace in model.corrector_traces:
+        for seg in trace.cpu().tolist():
+            for j, vals in enumerate(seg):
+                rows.append(f"{j},{sched[j + 1]!r},{n}," + ",".join("" if v != v else repr(v) for v in vals))
+            n += 1
+    with open(os.path.join(outdir, "corrector.csv"), "w") as fh:
+        fh.write("\n".join(rows) + "\n")
 
 
 def write_ensemble(model, batch, protein, args, analysis):
@@ -256,6 +304,10 @@ def evaluate_model(model, args):
     guide = guide_from_args(args)
     args.guide_kw = dict(guide=guide) if guide is not None else {}
     model.keep_guide_trace = guide is not None
+    corrector = corrector_from_args(args)
+    if corrector is not None:
+        args.guide_kw["corrector"] = corrector
+    model.keep_corrector_trace = corrector is not None
     fixed = None
     if args.repack is not None:
         from ..selection import device_selector, interface_selection, parse_selection, sasa_selection
@@ -275,6 +327,8 @@ def evaluate_model(model, args):
         SC_D_sample = model.sampling(batch, use_proximal=args.use_proximal, seed=args.seed, **args.guide_kw)
     if guide is not None:
         write_guide_csv(model, args.outdir)
+    if corrector is not None:
+        write_corrector_csv(model, args.outdir)
     if model.saturated() & 4:
         print("----- WARNING: NaN / infinity in the input coordinates or angles: the reference would return NaN here -----")
     if model.saturated() & 3:
@@ -333,6 +387,7 @@ def build_parser():
                    "--repack also takes interface:sasa (the delta-SASA interface of the input, made on the device) and pocket "
                    "(residues whose surface the obstacle atoms bury; needs --obstacles).")
     add_guide_arguments(p)
+    add_corrector_arguments(p)
     return p
 
 
@@ -358,6 +413,7 @@ def parse_args(argv=None):
     if args.recombine_sweeps < 0:
         p.error("--recombine_sweeps must not be negative")
     guide_from_args(args, p)
+    corrector_from_args(args, p)
     return args
 
 

@@ -4,6 +4,7 @@ DESIGN.md section 17).
     python -m packppi_amd.cli.mutate --input x.pdb (--mutstr RA47A,EA48A | --mutlist FILE) --ckpt_path model.ckpt --seed 7
         [--n_decoys 8] [--select clash|medoid] [--use_proximal] [--radius 10] [--shell ca|atom] [--fixed_mode hold|renoise]
         [--recombine [--recombine_sweeps 64]] [--guide 0.02 [--guide_schedule late|constant] [--guide_from 0.3] [--guide_cap 0.1]]
+        [--corrector 0.16 [--corrector_from 1.0]]
         --outdir out [--ap_ckpt ap.ckpt --pre_ckpt_path pre.ckpt]
 
 Every set is put into the complex, the residues within --radius of a mutated residue (the shell, chosen on the device) are
@@ -22,6 +23,8 @@ that structure (per residue the solvent-accessible area at four nested levels, t
 buries.
 --guide SCALE ... (without it every output byte as before): the shell is sampled with clash guidance, as
 ``eval_diffusion --guide``; ``guide.csv`` has one block of lines per decoy of every set.
+--corrector SNR [--corrector_from T] (without it every output byte as before): the shell is sampled with a
+Langevin corrector behind the reverse steps, as ``eval_diffusion --corrector``; ``corrector.csv`` has one block per decoy of every set.
 """
 import argparse
 import os
@@ -30,7 +33,8 @@ import numpy as np
 
 from ..featurize import parse_mutstr
 from ..pdb_io import OBSTACLE_MODES, from_pdb_file, insert_obstacle_lines, obstacles_for, to_pdb
-from .eval_diffusion import add_guide_arguments, guide_from_args, load_model, write_guide_csv
+from .eval_diffusion import (add_corrector_arguments, add_guide_arguments, corrector_from_args, guide_from_args, load_model,
+                             write_corrector_csv, write_guide_csv)
 
 AP_NOTE = ("The ddG values come from the unchanged AffinityPrediction.predict_many on featurize.mutant_data. The AP model was "
            "trained with zeroed mutant angles, so it does not see the packed mutant.")
@@ -65,12 +69,17 @@ def evaluate_model(model, args):
     sets = read_sets(args)
     guide = guide_from_args(args)
     model.keep_guide_trace = guide is not None
+    corrector = corrector_from_args(args)
+    model.keep_corrector_trace = corrector is not None
     results = model.mutate([(protein, s) for s in sets], seed=args.seed, radius=args.radius, shell=args.shell,
                            n_decoys=args.n_decoys, use_proximal=args.use_proximal, select=args.select, fixed_mode=args.fixed_mode,
                            **(dict(recombine=True, recombine_sweeps=args.recombine_sweeps) if args.recombine else {}),
-                           **(dict(sasa=True) if args.sasa else {}), **(dict(guide=guide) if guide is not None else {}))
+                           **(dict(sasa=True) if args.sasa else {}), **(dict(guide=guide) if guide is not None else {}),
+                           **(dict(corrector=corrector) if corrector is not None else {}))
     if guide is not None:
         write_guide_csv(model, args.outdir)
+    if corrector is not None:
+        write_corrector_csv(model, args.outdir)
     ddg = predict_ddg(protein, sets, args) if args.ap_ckpt else None
     rows = ["tag,shell_rows,selected_decoy,clash,dev" + (",clash_recombined,rows_recombined" if args.recombine else "")
             + (",ddg,ddg_inv" if ddg else "") + (",bsa" if args.sasa else "")]
@@ -152,6 +161,7 @@ def build_parser():
                    "the solvent-accessible area at four nested levels, the buried interface area and the exposure; mutants.csv gains "
                    "the column bsa.")
     add_guide_arguments(p)
+    add_corrector_arguments(p)
     return p
 
 
@@ -165,6 +175,7 @@ def main(argv=None):
     if args.pre_ckpt_path and not args.ap_ckpt:
         p.error("--pre_ckpt_path belongs to --ap_ckpt")
     guide_from_args(args, p)
+    corrector_from_args(args, p)
     evaluate_model(load_model(args), args)
 
 

@@ -695,7 +695,7 @@ extern "C" pp_status pp_add_noise_seeded(pp_ctx *c, const float *chi0, float t, 
     return pp_launch_add_noise_seeded(c, chi0, sigma_f32(t), seed, chi, s);
 }
 
-// What one sampling run is: the four exports fill one and call sample_impl.
+// What one sampling run is: the five exports fill one and call sample_impl.
 struct SampleRun {
     const char *who;                    // the export, for messages
     const float *sde_noise = nullptr;   // pp_sample: the per-step noise tensor, or
@@ -708,6 +708,8 @@ struct SampleRun {
     float cap = 0.f;                    //   largest |step| of one angle at one nudge
     double *trace = nullptr;            //   [B][n_schedule] or null
     float *chi_traj = nullptr;          // [n_schedule - 1][N][4] or null: written by the pinned step's lanes, copied in a run without a pin
+    const float *snr = nullptr;         // the corrector, or null: HOST [n_schedule - 1], 0 = none behind reverse step j
+    double *corr_trace = nullptr;       //   [B][n_schedule - 1][4] = (s2, n2, eps, amp) or null
 };
 static pp_status sample_impl(pp_ctx *c, float *chi, const float *schedule, int n_schedule, int mode, const SampleRun &run, hipStream_t s);
 
@@ -762,20 +764,50 @@ extern "C" pp_status pp_sample_guided(pp_ctx *c, float *chi, const float *chi_re
     return sample_impl(c, chi, schedule, n_schedule, mode, run, static_cast<hipStream_t>(stream));
 }
 
+// ---- predictor-corrector sampling ----------------------------------------------------------------------------
+extern "C" pp_status pp_sample_corrected(pp_ctx *c, float *chi, const float *chi_ref, const uint8_t *fixed, int fix_mode,
+                                         const float *schedule, int n_schedule, int mode, uint64_t seed, const float *snr,
+                                         const float *eta, float cap, float *chi_traj, double *clash_trace, double *corr_trace,
+                                         void *stream) {
+    if (c) c->last_stream = static_cast<hipStream_t>(stream);
+    if (!c) FAIL(PP_ERR_INVALID, "pp_sample_corrected: null ctx");
+    if (!chi) FAIL(PP_ERR_INVALID, "pp_sample_corrected: null chi");
+    if (!schedule) FAIL(PP_ERR_INVALID, "pp_sample_corrected: null schedule");
+    if (!snr) FAIL(PP_ERR_INVALID, "pp_sample_corrected: null snr");
+    if ((chi_ref == nullptr) != (fixed == nullptr))
+        FAIL(PP_ERR_INVALID, "pp_sample_corrected: chi_ref and fixed must be given together (both, or neither for a run without a pin)");
+    SampleRun run = {"pp_sample_corrected"};
+    run.seeded = fixed != nullptr || mode == PP_MODE_SDE;          // the reverse steps of ode without a pin draw nothing; the corrector draws
+    run.seed = seed;
+    run.chi_ref = chi_ref; run.fixed = fixed; run.fix_mode = fix_mode;
+    run.eta = eta; run.cap = cap; run.trace = eta ? clash_trace : nullptr;
+    run.chi_traj = chi_traj;
+    run.snr = snr; run.corr_trace = corr_trace;
+    return sample_impl(c, chi, schedule, n_schedule, mode, run, static_cast<hipStream_t>(stream));
+}
+
 // The argument checks of a run, each written once, in the one order that reports a call with several faults as every export always
 // has: the exports with a pin or a guide name an unknown mode in front of the plan's and the schedule's faults, the other two behind.
 static pp_status check_run(const pp_ctx *c, const float *chi, const float *schedule, int n_schedule, int mode, const SampleRun &run) {
     const std::string w(run.who);
-    const bool pinned = run.fixed != nullptr, guided = run.eta != nullptr;
+    const bool pinned = run.fixed != nullptr, guided = run.eta != nullptr, corrected = run.snr != nullptr;
     const bool bad_mode = mode != PP_MODE_ODE && mode != PP_MODE_SDE;
     if (!c || !chi || !schedule) FAIL(PP_ERR_INVALID, w + ": null argument");
     if (pinned && run.chi_ref == chi) FAIL(PP_ERR_INVALID, w + ": chi_ref and chi must be distinct buffers");
     if (pinned && run.fix_mode != PP_FIX_HOLD && run.fix_mode != PP_FIX_RENOISE) FAIL(PP_ERR_INVALID, w + ": unknown fix_mode");
-    if ((pinned || guided) && bad_mode) FAIL(PP_ERR_INVALID, w + ": unknown mode");
+    if ((pinned || guided || corrected) && bad_mode) FAIL(PP_ERR_INVALID, w + ": unknown mode");
     if (pinned && !guided && (!c->b.chi_1pi_periodic_mask || !c->b.chi_2pi_periodic_mask))
         FAIL(PP_ERR_INVALID, w + ": batch lacks the periodic masks");
     if (!guided && !c->plan->has_network) FAIL(PP_ERR_INVALID, w + ": plan was created without network weights");
     if (n_schedule < 2) FAIL(PP_ERR_INVALID, w + ": schedule needs at least 2 times");
+    if (corrected) {
+        for (int j = 0; j < n_schedule - 1; j++)
+            if (!(run.snr[j] >= 0.f) || std::isinf(run.snr[j]))
+                FAIL(PP_ERR_INVALID, w + ": snr[" + std::to_string(j) + "] must be finite and not negative");
+        if (!c->plan->has_network) FAIL(PP_ERR_INVALID, w + ": plan was created without network weights (a geometry-only plan)");
+        if (!c->b.SC_D_mask || !c->b.chi_1pi_periodic_mask || !c->b.chi_2pi_periodic_mask)
+            FAIL(PP_ERR_INVALID, w + ": batch lacks SC_D_mask / the periodic masks");
+    }
     if (guided) {
         for (int j = 0; j < n_schedule; j++)
             if (!(run.eta[j] >= 0.f) || std::isinf(run.eta[j]))
@@ -801,15 +833,20 @@ static PPPin step_pin(const SampleRun &run, const float *schedule, int j, int ns
             run.fix_mode == PP_FIX_RENOISE && j + 1 < nsteps ? 1 : 0};
 }
 
-// pp_sample, pp_sample_seeded, pp_sample_partial and pp_sample_guided
+// pp_sample, pp_sample_seeded, pp_sample_partial, pp_sample_guided and pp_sample_corrected
 static pp_status sample_impl(pp_ctx *c, float *chi, const float *schedule, int n_schedule, int mode, const SampleRun &run, hipStream_t s) {
     pp_status st;
     if ((st = check_run(c, chi, schedule, n_schedule, mode, run)) != PP_OK) return st;
     PP_HIP_CHECK(hipSetDevice(c->plan->device));
     const bool pinned = run.fixed != nullptr, guided = run.eta != nullptr;
-    if (run.seeded && (st = rng_table_ready(c, s)) != PP_OK) return st;
-    const PPRng rng = {c->rng_tab, (uint32_t)run.seed, (uint32_t)(run.seed >> 32)};
     const int nsteps = n_schedule - 1;
+    // Corrected run: the corrector of reverse step j sits behind it (and its pin), in front of nudge point j + 1.  snr[j] == 0
+    // enqueues nothing.  The corrector always draws, in ode mode too
+    auto corr_at = [&](int j) { return run.snr != nullptr && run.snr[j] != 0.f; };
+    bool corrected = false;
+    for (int j = 0; j < nsteps; j++) corrected = corrected || corr_at(j);
+    if ((run.seeded || corrected) && (st = rng_table_ready(c, s)) != PP_OK) return st;
+    const PPRng rng = {c->rng_tab, (uint32_t)run.seed, (uint32_t)(run.seed >> 32)};
     // per-step scalars are kernel arguments: nothing is staged, nothing waits for the stream
     std::vector<StepParams> steps((size_t)nsteps);
     for (int j = 0; j < nsteps; j++) fill_step(&steps[j], schedule[j], schedule[j] - schedule[j + 1], c->plan->annealed_temp);
@@ -828,6 +865,9 @@ static pp_status sample_impl(pp_ctx *c, float *chi, const float *schedule, int n
         if (any && (st = pp_launch_guide_begin(c, s)) != PP_OK) return st;
         if (nudge_at(0) && (st = nudge(0)) != PP_OK) return st;
     }
+    if (run.corr_trace) PP_HIP_CHECK(hipMemsetAsync(run.corr_trace, 0xff, (size_t)c->B * nsteps * 4 * sizeof(double), s));   // NaN
+    StepParams sp_end;                        // the corrector behind the last reverse step embeds at schedule[nsteps]
+    if (corrected && corr_at(nsteps - 1)) fill_step(&sp_end, schedule[nsteps], 0.f, c->plan->annealed_temp);
     if (nudge_at(0)) prof_arm(c, 6);          // pp_profile_kernel(6): the embedding launch behind a nudge
     st = pp_launch_node_embed(c, chi, steps[0], s);
     prof_disarm(c);
@@ -846,21 +886,34 @@ static pp_status sample_impl(pp_ctx *c, float *chi, const float *schedule, int n
     }
     for (int j = 0; j < nsteps; j++) {
         const PPPin pin = pinned ? step_pin(run, schedule, j, nsteps, c->N) : PPPin{nullptr, nullptr, nullptr, 0.f, 0};
-        const bool then_nudge = nudge_at(j + 1);
-        const NodeEval ev = {chi, j, mode, run.sde_noise, &steps[j], j + 1 < nsteps && !then_nudge ? &steps[j + 1] : nullptr,
+        const bool then_corr = corr_at(j), then_nudge = nudge_at(j + 1);
+        // an evaluation followed by a corrector or a nudge drops its fused embedding: the angles evaluation j + 1 embeds exist only
+        // behind them, and the corrector's own evaluation starts from pp_score's embedding launch (below)
+        const NodeEval ev = {chi, j, mode, run.sde_noise, &steps[j], j + 1 < nsteps && !then_corr && !then_nudge ? &steps[j + 1] : nullptr,
                              run.seeded ? &rng : nullptr, pinned ? &pin : nullptr};
         if ((st = run_network(c, s, PP_NU_STEP, ev, use_live ? &live : nullptr)) != PP_OK) return st;
-        if (guided && run.chi_traj && !pinned)
+        if (run.chi_traj && !pinned)
             PP_HIP_CHECK(hipMemcpyAsync(run.chi_traj + (size_t)j * c->N * 4, chi, (size_t)c->N * 4 * sizeof(float),
                                         hipMemcpyDeviceToDevice, s));
-        if (then_nudge) {
-            if ((st = nudge(j + 1)) != PP_OK) return st;
-            if (j + 1 < nsteps) {
-                prof_arm(c, 6);
-                st = pp_launch_node_embed(c, chi, steps[j + 1], s);
-                prof_disarm(c);
-                if (st != PP_OK) return st;
-            }
+        if (then_corr) {
+            // the score at the new state and time: pp_score's launch sequence, the embedding launch included (all rows, no fused
+            // embedding behind it) -- the bits of pp_score(ctx, chi, schedule[j + 1]) behind any step.  The embedding the reverse step
+            // could fuse is the same function in the matrix pipe's arithmetic, not the same bits.  Then the update in one launch
+            const StepParams &sp = j + 1 < nsteps ? steps[j + 1] : sp_end;
+            if ((st = pp_launch_node_embed(c, chi, sp, s)) != PP_OK) return st;
+            const NodeEval evs = {nullptr, 0, PP_MODE_ODE, nullptr, &sp, nullptr, nullptr, nullptr};
+            if ((st = run_network(c, s, PP_NU_SCORE, evs, nullptr)) != PP_OK) return st;
+            prof_arm(c, 7);                   // pp_profile_kernel(7): k_correct
+            st = pp_launch_correct(c, chi, run.fixed, run.snr[j], j, nsteps, rng, run.corr_trace, s);
+            prof_disarm(c);
+            if (st != PP_OK) return st;
+        }
+        if (then_nudge && (st = nudge(j + 1)) != PP_OK) return st;
+        if ((then_corr || then_nudge) && j + 1 < nsteps) {      // the angles evaluation j + 1 embeds exist only now
+            if (then_nudge) prof_arm(c, 6);
+            st = pp_launch_node_embed(c, chi, steps[j + 1], s);
+            prof_disarm(c);
+            if (st != PP_OK) return st;
         }
     }
     if (dbg) {
@@ -1090,8 +1143,8 @@ extern "C" pp_status pp_debug_score_prefix(pp_ctx *c, const float *chi, float t,
 // dispatch's own begin and end timestamps);
 // pp_profile_read synchronises, sums the pair intervals, reports (total ms, launches) and switches profiling off.
 extern "C" pp_status pp_profile_kernel(pp_ctx *c, int which) {
-    if (!c || which < 0 || which > 6)
-        FAIL(PP_ERR_INVALID, "pp_profile_kernel: which must be 0 (node message), 1 (edge update), 2 (node update), 3 (the Adam-step launch of pp_proximal / pp_proximal_packed / pp_proximal_pinned: clash + gradient + step + reconstruction) or 4, 5, 6 (the launches of a nudge of pp_sample_guided: reconstruction, clash + gradient + step, node embedding)");
+    if (!c || which < 0 || which > 7)
+        FAIL(PP_ERR_INVALID, "pp_profile_kernel: which must be 0 (node message), 1 (edge update), 2 (node update), 3 (the Adam-step launch of pp_proximal / pp_proximal_packed / pp_proximal_pinned: clash + gradient + step + reconstruction), 4, 5, 6 (the launches of a nudge of pp_sample_guided: reconstruction, clash + gradient + step, node embedding) or 7 (the corrector launch of pp_sample_corrected)");
     c->prof_which = which;
     c->prof_n = 0;
     return PP_OK;

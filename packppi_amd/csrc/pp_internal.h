@@ -418,6 +418,12 @@ pp_status pp_launch_guide_begin(pp_ctx *c, hipStream_t s);
 pp_status pp_launch_guide_nudge(pp_ctx *c, float *chi, const uint8_t *fixed, float eta, float cap, double *trace, int n_schedule,
                                 int j, hipStream_t s);
 
+// pp_sample_corrected (pp_correct.hip): the Langevin corrector behind reverse step j on chi, in place, from the
+// score in c->score; per segment of the context's table, one workgroup each.  snr = snr[j]; the draws are those of counter step
+// 2^20 + j.  trace (device [n_seg][n_steps][4] or null) receives (s2, n2, eps, amp) at row j of every segment that has a corrector.
+pp_status pp_launch_correct(pp_ctx *c, float *chi, const uint8_t *fixed, float snr, int j, int n_steps, const PPRng &rng,
+                            double *trace, hipStream_t s);
+
 void pp_edge_occupancy(int *node_msg, int *edge_upd);
 
 // last_mode values for pp_launch_node_update

@@ -22,7 +22,7 @@ SYMBOLS = ("pp_version", "pp_last_error", "pp_build_id", "pp_plan_set_knn_ties",
            "pp_score_rows", "pp_so2_set_grids", "pp_so2_score", "pp_dsm_loss",
            "pp_ctx_set_rng_keys", "pp_noise_seeded", "pp_add_noise_seeded", "pp_sample_seeded",
            "pp_sample_partial", "pp_proximal_pinned", "pp_ctx_live_rows", "pp_ensemble_reduce", "pp_ctx_shell",
-           "pp_ensemble_recombine", "pp_ctx_set_obstacles", "pp_sasa", "pp_sample_guided")
+           "pp_ensemble_recombine", "pp_ctx_set_obstacles", "pp_sasa", "pp_sample_guided", "pp_sample_corrected")
 
 
 FIX_MODES = {"hold": 0, "renoise": 1}         # PP_FIX_HOLD, PP_FIX_RENOISE
@@ -143,6 +143,7 @@ def load():
     lib.pp_ctx_set_obstacles.argtypes = [vp, vp, vp, i, vp]
     lib.pp_sasa.argtypes = [vp, vp, vp, vp, i, f, vp, vp, vp, vp]
     lib.pp_sample_guided.argtypes = [vp, vp, vp, vp, i, vp, i, i, C.c_uint64, vp, f, vp, vp, vp]
+    lib.pp_sample_corrected.argtypes = [vp, vp, vp, vp, i, vp, i, i, C.c_uint64, vp, vp, f, vp, vp, vp, vp]
     _lib = lib
     return lib
 
@@ -590,6 +591,50 @@ class Context:
         out = (chi,) + ((traj,) if trajectory else ()) + ((trace,) if want_trace else ())
         return out if len(out) > 1 else chi
 
+    def sample_corrected(self, chi, schedule, mode, seed, snr, eta=None, cap=0.1, chi_ref=None, fixed=None, fix_mode="renoise",
+                         trajectory=False, want_trace=False, want_corr=False, vtf=12.0, tol=0.5):
+        """Predictor-corrector sampling (pp_sample_corrected): ``sample(..., seed=seed)`` -- with ``chi_ref`` and
+        ``fixed`` ``sample_partial``, with ``eta`` ``sample_guided`` -- with one Langevin corrector behind every reverse step j whose
+        ``snr[j]`` is not 0: a network evaluation at the new state and time, then x += eps s + sqrt(2 eps) z on the movable angles,
+        eps = 2 (snr |z| / |s|)^2 with the two norms taken PER COMPLEX (the reference's ``step_correct`` averages them over the
+        batch), z from the device generator at counter step 2^20 + j.  ``snr``: n_schedule - 1 values (``schedule.corrector_snr``),
+        finite and not negative.  Fixed rows are never moved and never counted.  With ``snr`` all 0 the result has the bits of
+        ``sample`` / ``sample_partial`` / ``sample_guided``.  Any context; with ``eta`` a packed or B = 1 one.  Returns the sample
+        [B, L, 4]; with ``trajectory`` also the angles after every reverse step [n_steps, B, L, 4], IN FRONT OF that step's corrector;
+        with ``want_trace`` (needs ``eta``) the guide's clash trace; with ``want_corr`` (s2, n2, eps, amp) of every segment and
+        step, fp64 [n_segments, n_steps, 4], NaN where there is no corrector.  No host synchronisation."""
+        md = _mode_code(mode)
+        if (chi_ref is None) != (fixed is None):
+            raise ValueError("chi_ref and fixed go together: give both (a pinned run) or neither")
+        if fixed is not None and fix_mode not in FIX_MODES:
+            raise ValueError(f"fix_mode must be one of {sorted(FIX_MODES)}")
+        if want_trace and eta is None:
+            raise ValueError("want_trace is the guide's clash trace: it needs eta")
+        sched = _host_f32(schedule)
+        sn = _host_f32(snr).reshape(-1)
+        if sn.size != max(sched.size - 1, 0):
+            raise ValueError(f"snr has {sn.size} entries, the schedule has {max(sched.size - 1, 0)} reverse steps (one corrector point per step)")
+        et = None
+        if eta is not None:
+            et = _host_f32(eta).reshape(-1)
+            if et.size != sched.size:
+                raise ValueError(f"eta has {et.size} entries, the schedule has {sched.size} times (one nudge point per time)")
+            self.plan.set_clash_params(vtf, tol)
+        chi = self._chi(chi).clone()
+        ref = fx = None
+        if fixed is not None:
+            ref, fx = self._chi(chi_ref), self._mask(fixed, "fixed")
+        n = max(len(sched) - 1, 0)
+        traj = self._new(n, self.B, self.L, 4) if trajectory else None
+        trace = self._new(self.n_segments, len(sched), dtype=torch.float64) if want_trace else None
+        corr = self._new(self.n_segments, n, 4, dtype=torch.float64) if want_corr else None
+        _check(load().pp_sample_corrected(self.handle, _ptr(chi), _ptr(ref), _ptr(fx), FIX_MODES.get(fix_mode, 1), sched.ctypes.data,
+                                          int(len(sched)), md, _seed64(seed), sn.ctypes.data,
+                                          et.ctypes.data if et is not None else None, float(cap), _ptr(traj), _ptr(trace), _ptr(corr),
+                                          _stream(self.plan.device)), "pp_sample_corrected")
+        out = (chi,) + ((traj,) if trajectory else ()) + ((trace,) if want_trace else ()) + ((corr,) if want_corr else ())
+        return out if len(out) > 1 else chi
+
     def atom14(self, chi):
         chi = self._chi(chi)
         xyz = self._new(self.B, self.L, 14, 3)
@@ -808,7 +853,7 @@ class Context:
     def profile_kernel(self, which: int):
         """Bracket every later launch of kernel `which` (0 node message, 1 edge update, 2 node update; inside the proximal
         calls: 3 the one launch per Adam step; inside sample_guided(): 4 the reconstruction of a nudge, 5 its clash + gradient +
-        step launch, 6 the node embedding launch behind it) with HIP events."""
+        step launch, 6 the node embedding launch behind it; inside sample_corrected(): 7 the corrector launch) with HIP events."""
         _check(load().pp_profile_kernel(self.handle, int(which)), "pp_profile_kernel")
 
     def profile_read(self):

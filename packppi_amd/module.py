@@ -81,10 +81,20 @@ def read_checkpoint_state_dict(path, map_location="cpu") -> Dict[str, torch.Tens
     return {k: v for k, v in sd.items() if isinstance(v, torch.Tensor)}
 
 
+def _corrector_refusals(corrector, schedule, sde_noise, seed):
+    """The refusals of ``sampling(corrector=)``, behind every other one: the snr array of ``Context.sample_corrected``."""
+    if sde_noise is not None:
+        raise ValueError("corrector and sde_noise exclude each other: corrected sampling draws its noise from the seeded generator")
+    if seed is None:
+        raise ValueError("corrector needs seed: the corrector draws its noise from the seeded generator")
+    from .schedule import resolve_corrector
+    return resolve_corrector(corrector, schedule)          # snr must be finite and not negative
+
+
 def _sampling_refusals(cfg, schedule, batch, use_proximal, return_list, sde_noise, seed, fixed_mask, fixed_mode, return_trajectory,
-                       guide):
-    """Every refusal of ``sampling``, in the order a call with several faults has always met them.  Returns the guide's keywords
-    for ``Context.sample_guided`` (None without a guide)."""
+                       guide, corrector=None):
+    """Every refusal of ``sampling``, in the order a call with several faults has always met them.  Returns (the guide's keywords
+    for ``Context.sample_guided``, None without a guide; the corrector's snr array, None without a corrector)."""
     gkw = None
     if guide is not None:
         from .schedule import resolve_guide
@@ -111,15 +121,15 @@ def _sampling_refusals(cfg, schedule, batch, use_proximal, return_list, sde_nois
         from .lib import FIX_MODES
         if fixed_mode not in FIX_MODES:
             raise ValueError(f"fixed_mode must be one of {sorted(FIX_MODES)}")
-        return gkw
-    if return_trajectory and guide is None:
+        return gkw, None if corrector is None else _corrector_refusals(corrector, schedule, sde_noise, seed)
+    if return_trajectory and guide is None and corrector is None:
         raise ValueError("return_trajectory needs fixed_mask (the trajectory is written by the partial sampler)")
     if _get(batch, "seg_offsets") is not None and use_proximal and return_list:
         raise ValueError("return_list=True needs a B = 1 batch; for a packed batch use "
                          "functional.proximal_optimizer_packed (per-complex losses [n_complexes, num_steps])")
     if seed is not None and sde_noise is not None:
         raise ValueError("seed and sde_noise exclude each other: the seeded sampler draws its own noise")
-    return gkw
+    return gkw, None if corrector is None else _corrector_refusals(corrector, schedule, sde_noise, seed)
 
 
 class TDiffusionModule:
@@ -151,6 +161,8 @@ class TDiffusionModule:
         self._knn_ties = knn_ties         # None: the library default (the reference CPU path's torch.topk choice)
         self.keep_guide_trace = False     # True: guided sampling runs append (eta, clash trace) to guide_traces
         self.guide_traces = []
+        self.keep_corrector_trace = False     # True: corrected runs append (snr, (s2, n2, eps, amp) on the device) to corrector_traces (section 23)
+        self.corrector_traces = []
         self.to(device)
 
     # ---- construction ----------------------------------------------------------------------
@@ -323,7 +335,7 @@ class TDiffusionModule:
         self._val_loss, self._test_loss = (0.0, 0), (0.0, 0)
 
     def sampling(self, batch, use_proximal: bool = False, return_list: bool = False, sde_noise=None, seed=None,
-                 fixed_mask=None, fixed_chi=None, fixed_mode="renoise", return_trajectory: bool = False, guide=None):
+                 fixed_mask=None, fixed_chi=None, fixed_mode="renoise", return_trajectory: bool = False, guide=None, corrector=None):
         """``seed`` (an int, None = the reference's behaviour): the initial noising and the sde noise come from the counter-based
         generator on the device (csrc/pp_rng.h) instead of torch's global one.  The noise of a complex is then a function of
         (seed, its key, its rows, the step) alone: the same complex gets the same angles alone, anywhere in a packed batch and
@@ -348,14 +360,24 @@ class TDiffusionModule:
         ("late" / "constant"), ``t_on``, ``cap``, anything else is an explicit sequence of n_schedule step sizes.  Needs ``seed`` in
         sde mode and with ``fixed_mask`` (fixed rows are never nudged); excludes ``sde_noise``; a packed or B = 1 batch.  With
         ``return_trajectory``: (sample, angles after every reverse step, mean clash in front of every nudge, fp64
-        [n_complexes, n_schedule], NaN where no nudge runs).  ``use_proximal`` runs behind it, as today."""
+        [n_complexes, n_schedule], NaN where no nudge runs).  ``use_proximal`` runs behind it, as today.
+
+        ``corrector`` (None = today's code path, untouched): predictor-corrector sampling -- one Langevin
+        corrector behind the reverse steps (``Context.sample_corrected``): one more network evaluation at the new state, then a
+        step along the score plus noise, with a step size PER COMPLEX from the ratio of its noise norm to its score norm (the
+        reference's ``step_correct`` averages the norms over the batch; here batching changes no result).  A number is the snr of
+        the default preset (``schedule.CORRECTOR_DEFAULTS``: behind every reverse step but the last; 0.16 is the reference's
+        constant, not a tuned one), a dict holds any of ``snr``, ``t_on``, ``last``, anything else is an explicit sequence of
+        n_schedule - 1 values.  Needs ``seed``; excludes ``sde_noise``; works with ``fixed_mask`` (fixed rows are never moved and
+        never counted) and with ``guide``.  With ``return_trajectory`` the tuple ends with (s2, n2, eps, amp) per complex and step,
+        fp64 [n_complexes, n_steps, 4], NaN where no corrector ran; the trajectory holds the angles IN FRONT OF each corrector."""
         if fixed_mask is None:
             fixed_mask = _get(batch, "fixed_mask")
-        gkw = _sampling_refusals(self.hparams.sample_cfg, self.schedule, batch, use_proximal, return_list, sde_noise, seed, fixed_mask,
-                                 fixed_mode, return_trajectory, guide)
+        gkw, snr = _sampling_refusals(self.hparams.sample_cfg, self.schedule, batch, use_proximal, return_list, sde_noise, seed,
+                                      fixed_mask, fixed_mode, return_trajectory, guide, corrector)
         ctx = self._context(batch)
         init, sde_noise, pin = self._initial_angles(ctx, batch, sde_noise, seed, fixed_mask, fixed_chi, fixed_mode)
-        out = self._run_sampler(ctx, init, sde_noise, seed, pin, return_trajectory, gkw)
+        out = self._run_sampler(ctx, init, sde_noise, seed, pin, return_trajectory, gkw, snr)
         if return_trajectory:
             return out
         return self._proximal_tail(batch, out, use_proximal, return_list)
@@ -386,9 +408,12 @@ class TDiffusionModule:
                                                   for _ in range(2)]) for _ in range(len(self.schedule) - 1)])
         return init, sde_noise, None
 
-    def _run_sampler(self, ctx, init, sde_noise, seed, pin, return_trajectory, gkw):
-        """The reverse diffusion on the context: guided, pinned, seeded or from the caller's noise tensor, each through its export."""
+    def _run_sampler(self, ctx, init, sde_noise, seed, pin, return_trajectory, gkw, snr=None):
+        """The reverse diffusion on the context: corrected, guided, pinned, seeded or from the caller's noise tensor, each through
+        its export."""
         mode = self.hparams.sample_cfg.mode
+        if snr is not None:
+            return self._corrected(ctx, init, seed, snr, return_trajectory, gkw, **(pin or {}))
         if gkw is not None:
             return self._guided(ctx, init, seed, return_trajectory, **(pin or {}), **gkw)
         if pin is not None:
@@ -424,8 +449,24 @@ class TDiffusionModule:
             return out
         return out[0] if keep else out
 
+    def _corrected(self, ctx, init, seed, snr, return_trajectory, gkw, **pin):
+        """``Context.sample_corrected`` for ``sampling``: the sample; with ``return_trajectory`` (sample, trajectory, the clash trace
+        of a guided run, corrector trace).  ``keep_guide_trace`` / ``keep_corrector_trace`` append to ``guide_traces`` /
+        ``corrector_traces`` as ``_guided`` does (the command lines write guide.csv and corrector.csv from them)."""
+        keep_g, keep_c = self.keep_guide_trace and gkw is not None, self.keep_corrector_trace
+        want_g, want_c = gkw is not None and (return_trajectory or keep_g), return_trajectory or keep_c
+        out = ctx.sample_corrected(init, self.schedule, self.hparams.sample_cfg.mode, seed, snr, trajectory=return_trajectory,
+                                   want_trace=want_g, want_corr=want_c, **pin, **(gkw or {}))
+        if keep_c:
+            self.corrector_traces.append((snr, out[-1]))
+        if keep_g:
+            self.guide_traces.append((gkw["eta"], out[-2 if want_c else -1]))
+        if return_trajectory:
+            return out
+        return out[0] if isinstance(out, tuple) else out
+
     def repack(self, batch, fixed_mask=None, *, seed, fixed_chi=None, fixed_mode="renoise", use_proximal: bool = False,
-               return_list: bool = False, norm_rows=None, guide=None):
+               return_list: bool = False, norm_rows=None, guide=None, corrector=None):
         """Partial repacking in one call (DESIGN.md sections 13 and 14): ``sampling(batch, seed=seed, fixed_mask=...)`` -- the rows
         of ``fixed_mask`` (default ``batch.fixed_mask``) keep ``fixed_chi`` (default ``batch.SC_D``), the others are sampled around
         them -- and then, with ``use_proximal``, the PINNED proximal stage (pp_proximal_pinned): the clash mask of every complex, its
@@ -434,7 +475,7 @@ class TDiffusionModule:
         the padded sizes).  Kept rows of the result are ``fixed_chi`` bit for bit with or without the proximal stage.  On a batch with
         obstacle atoms the clash of the pinned stage -- mask, loss, gradient -- includes them.
         ``return_list`` (B = 1, with ``use_proximal``): (sample, per-step angles, losses) as ``sampling`` returns them.
-        ``guide``: as in ``sampling`` (clash-guided sampling of the free rows); None = today's path."""
+        ``guide``: as in ``sampling`` (clash-guided sampling of the free rows); None = today's path.  ``corrector``: as in ``sampling``."""
         if fixed_mask is None:
             fixed_mask = _get(batch, "fixed_mask")
         if fixed_mask is None:
@@ -444,7 +485,7 @@ class TDiffusionModule:
             raise ValueError("return_list=True needs use_proximal=True and a B = 1 batch; for a packed batch use "
                              "functional.proximal_optimizer_packed (per-complex losses [n_complexes, num_steps])")
         cfg = self.hparams.sample_cfg
-        SC_D_sample = self.sampling(batch, seed=seed, fixed_mask=fixed_mask, fixed_chi=fixed_chi, fixed_mode=fixed_mode, guide=guide)
+        SC_D_sample = self.sampling(batch, seed=seed, fixed_mask=fixed_mask, fixed_chi=fixed_chi, fixed_mode=fixed_mode, guide=guide, corrector=corrector)
         if not use_proximal:
             return SC_D_sample
         traj, _, accepted, losses = proximal_optimizer_packed(batch, SC_D_sample, cfg.violation_tolerance_factor,
@@ -490,7 +531,7 @@ class TDiffusionModule:
                     confidence=res.resultant, keys=list(packed.complex_keys), **extra)
 
     def sample_ensemble(self, batch, n_decoys, *, seed=None, use_proximal: bool = False, select="clash", return_all: bool = False,
-                        recombine: bool = False, recombine_sweeps: int = 64, sasa: bool = False, guide=None):
+                        recombine: bool = False, recombine_sweeps: int = 64, sasa: bool = False, guide=None, corrector=None):
         """``n_decoys`` seeded samples of every complex in ONE packed pass, reduced on the device.  On
         complexes with obstacle atoms the decoys of a group share the group's obstacles, and the clash that
         ranks them, the proximal stage and the recombination include the overlap with them.  ``batch``: a
@@ -517,7 +558,8 @@ class TDiffusionModule:
         between its chains (``Context.sasa`` at the decoy's angles, ``seg_area[1] - seg_area[2]``).  Nothing else changes.
 
         ``guide``: every decoy is sampled with clash guidance, as ``sampling(guide=...)`` samples the complex
-        alone under the decoy's key; None = today's path."""
+        alone under the decoy's key; None = today's path.  ``corrector``: likewise -- every decoy is a segment and gets
+        its own corrector step size, the bits of ``sampling(seed=, corrector=)`` of that complex alone under ``decoy_key``."""
         from .batch import replicate, replicate_many
         if seed is None:
             raise ValueError("sample_ensemble needs seed: unseeded noise is laid out over the rows of the whole batch, so a decoy would "
@@ -531,12 +573,12 @@ class TDiffusionModule:
             packed = replicate(batch, n_decoys)
         if _get(packed, "fixed_mask") is not None:
             raise ValueError("ensembles under a fixed_mask are not supported: sample_ensemble samples every row")
-        chi = self.sampling(packed, use_proximal=use_proximal, seed=seed, guide=guide)
+        chi = self.sampling(packed, use_proximal=use_proximal, seed=seed, guide=guide, corrector=corrector)
         return self._reduce_ensemble(packed, chi, select, return_all, recombine, recombine_sweeps, sasa)
 
     def repack_ensemble(self, batch, fixed_mask=None, *, n_decoys, seed, fixed_chi=None, fixed_mode="renoise",
                         use_proximal: bool = False, select="clash", return_all: bool = False, recombine: bool = False,
-                        recombine_sweeps: int = 64, sasa: bool = False, guide=None):
+                        recombine_sweeps: int = 64, sasa: bool = False, guide=None, corrector=None):
         """``sample_ensemble`` under a pin: ``n_decoys`` seeded partial repackings of every complex in ONE packed
         pass, reduced on the device.  ``batch``: a B = 1 batch, or a list of complexes (per-complex data or B = 1 batches).  Every
         complex carries its ``fixed_mask`` (1 = keep; [1, L] on a B = 1 batch, [L] on per-complex data), or ``fixed_mask`` gives it:
@@ -549,7 +591,7 @@ class TDiffusionModule:
         with and without ``use_proximal``.  pp_ensemble_reduce is used unchanged: kept rows are identical in every decoy, so their
         ``resultant`` is 1 to rounding and they add (to rounding) nothing to ``dev``; they enter the per-decoy means of ``dev`` and
         ``clash`` with the same weight in all decoys of a group, so they dilute both equally and do not change the ranking.
-        Returns what ``sample_ensemble`` returns (``sasa``: the ``bsa`` key as there).  ``guide``: as in ``sampling``."""
+        Returns what ``sample_ensemble`` returns (``sasa``: the ``bsa`` key as there).  ``guide``, ``corrector``: as in ``sampling``."""
         from .batch import Batch, replicate_many
         self._check_select(select)
         single = not isinstance(batch, (list, tuple))
@@ -584,12 +626,12 @@ class TDiffusionModule:
                              .reshape(-1, 4)[:offs[g * D + 1] - offs[g * D]]
                              for g, (c, r) in enumerate(zip(complexes, refs)) for _ in range(D)]).unsqueeze(0)
         chi = self.repack(packed, seed=seed, fixed_chi=ref, fixed_mode=fixed_mode, use_proximal=use_proximal,
-                          norm_rows=[n for n in sizes for _ in range(D)] if use_proximal else None, guide=guide)
+                          norm_rows=[n for n in sizes for _ in range(D)] if use_proximal else None, guide=guide, corrector=corrector)
         return self._reduce_ensemble(packed, chi, select, return_all, recombine, recombine_sweeps, sasa)
 
     def mutate(self, proteins_and_mutations, *, seed, radius=10.0, shell="ca", n_decoys=1, use_proximal: bool = False,
                select="clash", fixed_mode="renoise", max_rows=200_000, log=print, recombine: bool = False,
-               recombine_sweeps: int = 64, sasa: bool = False, guide=None):
+               recombine_sweeps: int = 64, sasa: bool = False, guide=None, corrector=None):
         """Mutant modelling: put each mutation set into its complex, repack what it touches, return the mutant.
         ``proteins_and_mutations``: a list of ``(protein dict, mutations)`` pairs, ``mutations`` a string ("RA47A,EA48A") or dicts as
         ``featurize.parse_mutstr`` returns them; several sets of one protein are repeated pairs.  Set i of the call gets the noise
@@ -619,7 +661,8 @@ class TDiffusionModule:
         ``sasa``: every dict gains ``bsa`` fp64 [n_decoys], the surface each decoy buries between its chains.
 
         ``guide``: the shell is sampled with clash guidance, as in ``sampling``; rows outside the shell are
-        fixed rows, which are never nudged."""
+        fixed rows, which are never nudged.  ``corrector``: as in ``sampling``; the rows outside the shell
+        are never moved and never counted."""
         from .batch import as_single, group_rows, pack, pad_rows, unpack
         from .featurize import mutant_model_data, parse_mutstr
         from .functional import _ctx_for
@@ -654,7 +697,7 @@ class TDiffusionModule:
                 pinned.append(p)
             out = self.repack_ensemble(pinned, n_decoys=n_decoys, seed=seed, fixed_mode=fixed_mode, use_proximal=use_proximal,
                                        select=select, return_all=True, recombine=recombine, recombine_sweeps=recombine_sweeps,
-                                       sasa=sasa, guide=guide)
+                                       sasa=sasa, guide=guide, corrector=corrector)
             final = out["recombined"] if recombine else out["selected"]
             pos = gctx.atom14(final)
             picks = unpack(pb, out["pick"].reshape(1, -1)) if recombine else [None] * len(members)

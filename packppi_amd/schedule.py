@@ -104,3 +104,86 @@ def resolve_guide(guide, schedule):
     if not cap > 0:
         raise ValueError(f"guide cap must be positive (inf = no clamp), got {cfg['cap']!r}")
     return guide_eta(schedule, scale, cfg["kind"], cfg["t_on"]), cap
+
+
+# ---- predictor-corrector sampling -------------------------------------------------------------------------
+# snr 0.16 is the constant of the reference's SO2VESchedule.step_correct (schedule.py:238), NOT tuned against a trained checkpoint.
+CORRECTOR_DEFAULTS = dict(snr=0.16, t_on=1.0, last=False)
+
+
+def _snr_array(snr, n):
+    arr = np.asarray(torch.as_tensor(snr, dtype=torch.float32).cpu().numpy(), dtype=np.float32).reshape(-1)
+    if arr.size != n:
+        raise ValueError(f"snr has {arr.size} entries for the {n} reverse steps of a schedule of {n + 1} times")
+    if not np.isfinite(arr).all() or (arr < 0).any():
+        raise ValueError("snr entries must be finite and not negative")
+    return np.ascontiguousarray(arr, dtype=np.float32)
+
+
+def corrector_snr(schedule, snr=0.16, t_on=1.0, last=False) -> np.ndarray:
+    """The corrector points of ``Context.sample_corrected``: float32 [n_schedule - 1], entry j the signal-to-noise ratio of the
+    Langevin corrector behind reverse step j, which runs at time ``schedule[j + 1]``; 0 = none.  The entry is ``snr`` where
+    ``schedule[j + 1] <= t_on``; the one behind the last reverse step is 0 unless ``last`` (a corrector there adds noise to the
+    final sample).  ``ValueError``: ``snr`` negative or not finite, ``t_on`` not finite, a schedule of fewer than 2 times."""
+    sched = np.asarray(torch.as_tensor(schedule, dtype=torch.float32).cpu().numpy(), dtype=np.float32).reshape(-1)
+    if sched.size < 2:
+        raise ValueError("schedule needs at least 2 times")
+    snr = float(snr)
+    if not np.isfinite(snr) or snr < 0:
+        raise ValueError(f"snr must be finite and not negative, got {snr!r}")
+    if not np.isfinite(float(t_on)):
+        raise ValueError(f"t_on must be finite, got {t_on!r}")
+    out = np.where(sched[1:] <= np.float32(t_on), np.float32(snr), np.float32(0)).astype(np.float32)
+    if not last:
+        out[-1] = 0
+    return np.ascontiguousarray(out, dtype=np.float32)
+
+
+def resolve_corrector(corrector, schedule) -> np.ndarray:
+    """``corrector`` as ``TDiffusionModule.sampling`` takes it -> snr float32 [n_schedule - 1]: a number is the ``snr`` of the
+    default preset, a dict holds any of ``snr``, ``t_on``, ``last`` (``snr`` may be an explicit sequence), anything else is an
+    explicit sequence of n_schedule - 1 values, passed through after validation."""
+    cfg = dict(CORRECTOR_DEFAULTS)
+    if isinstance(corrector, dict):
+        unknown = sorted(set(corrector) - set(cfg))
+        if unknown:
+            raise ValueError(f"corrector has unknown keys {unknown}; known: {sorted(cfg)}")
+        cfg.update(corrector)
+        snr = cfg["snr"]
+    elif isinstance(corrector, bool):
+        raise ValueError("corrector must be an snr, a dict or an snr sequence, not a bool")
+    else:
+        snr = corrector
+    if not np.isscalar(snr) and not (isinstance(snr, (torch.Tensor, np.ndarray)) and np.ndim(snr) == 0):
+        n = int(torch.as_tensor(schedule).numel()) - 1
+        if n < 1:
+            raise ValueError("schedule needs at least 2 times")
+        return _snr_array(snr, n)
+    return corrector_snr(schedule, snr, cfg["t_on"], cfg["last"])
+
+
+@torch.no_grad()
+def step_correct(x, x_score, x_batch, x_mask=None, snr=0.16, noise=None):
+    """The reference's ``SO2VESchedule.step_correct`` (schedule.py:238-273) restated in torch, for users of its surface: x, x_score
+    [num_res, 4]; x_batch the complex of every ENTRY (anything that reshapes to [num_res, 4], as the reference passes it); x_mask
+    bool [num_res, 4] or None = every entry; ``noise`` [num_res, 4] replaces the ``torch.randn_like`` draw (tests).  The norms of
+    score and noise are taken per complex over the masked entries and AVERAGED OVER THE COMPLEXES OF THE BATCH into one step size
+    ``2 (snr |z| / |s|)^2``: a complex's result depends on what it is batched with.  The device path (``Context.sample_corrected``)
+    gives every complex its own step size and is packing-invariant; this function is not, and it does not wrap the angles either,
+    as the reference does not."""
+    x_batch = x_batch.reshape(-1, 4).long()
+    mask = torch.ones_like(x_score, dtype=torch.bool) if x_mask is None else x_mask.bool()
+    if noise is None:
+        noise = torch.randn_like(x_score)
+    idx = x_batch[mask]
+    n_seg = int(idx.max()) + 1 if idx.numel() else 0
+
+    def seg_norm(v):
+        return torch.sqrt(torch.zeros(n_seg, dtype=v.dtype, device=v.device).index_add_(0, idx, (v ** 2)[mask])).mean()
+
+    step_size = (snr * seg_norm(noise) / seg_norm(x_score)) ** 2 * 2
+    x_prev = x.clone()
+    x_prev += step_size * x_score
+    x_prev += ((step_size * 2) ** 0.5) * noise
+    x_prev[~mask] = x[~mask]
+    return x_prev
