@@ -136,6 +136,124 @@ def make_complex(n_res: int, seed: int, n_chains: int = 2) -> Dict:
                 b_factors=np.zeros((n_res, 14)))
 
 
+# ---- incomplete structures: what a deposited file looks like, on synthetic input --------------------------------------------
+DAMAGE_KINDS = ("tail", "cb_only", "backbone_only", "hole_cb", "hole_inner")
+_MIN_ATOMS = {"tail": 7, "cb_only": 6, "backbone_only": 5, "hole_cb": 6, "hole_inner": 7}   # atom14 count a kind needs
+_ARG, _LYS = 1, 11
+
+
+def damage_kinds(protein: Dict) -> List:
+    """Per row, what is missing, read off ``atom_mask`` and the residue type's atom14 table alone: None (complete), "masked" (a
+    backbone atom is missing: featurisation masks the whole row), one of ``DAMAGE_KINDS``, or "other"."""
+    aatype = np.asarray(protein["aaindex"])
+    have = np.asarray(protein["atom_mask"]) > 0
+    out = []
+    for t, h in zip(aatype, have):
+        table = rc.atom14_mask[t] > 0
+        n = int(table.sum())
+        gone = np.flatnonzero(table & ~h)
+        if len(gone) == 0:
+            out.append(None)
+        elif gone[0] < 4:
+            out.append("masked")
+        elif np.array_equal(gone, np.arange(gone[0], n)):                      # everything from slot c on
+            out.append("backbone_only" if gone[0] == 4 else "cb_only" if gone[0] == 5 else "tail")
+        elif len(gone) == 1 and gone[0] == 4:
+            out.append("hole_cb")
+        elif len(gone) == 1 and 5 <= gone[0] < n - 1:
+            out.append("hole_inner")
+        else:
+            out.append("other")
+    return out
+
+
+def drop_atoms(protein: Dict, seed: int) -> Dict:
+    """A copy of ``protein`` with side-chain atoms removed from about a quarter of its rows, the way deposited structures lack them:
+    a missing atom has ``atom_mask`` 0 and a NaN position, as ``pdb_io`` writes it.  Deterministic in ``seed``.
+
+    Every kind of ``DAMAGE_KINDS`` is dealt at least twice -- tail (slots c.. gone, 6 <= c < n_atoms), cb_only (slots 5..), backbone_only
+    (slots 4.., on a non-GLY row), hole_cb (slot 4 alone), hole_inner (one slot a, 5 <= a < n_atoms - 1) -- the first hole_cb on an ARG
+    or LYS where the complex has one (chi4 then survives chi1..3: a chi mask that is no prefix of the type's).  Besides: one row in
+    the interior of a chain loses a backbone atom (its whole row is masked) and the two rows after it are damaged; one damaged row is
+    a chain terminus; and the residue numbers of one chain jump by 4 at one place (rows i, i + 1 numbered n, n + 5) while the atoms
+    stay where they are.  Rows that already lack atoms are left as they are.  ValueError if the complex cannot carry all of that."""
+    rng = np.random.default_rng(seed)
+    aatype = np.asarray(protein["aaindex"])
+    L = len(aatype)
+    xyz = np.array(protein["atom_positions"], dtype=np.float64, copy=True)
+    mask = np.array(protein["atom_mask"], dtype=np.float64, copy=True)
+    ridx = np.array(protein["residue_index"], dtype=np.int64, copy=True)
+    chain = np.asarray(protein["chain_id"])
+    n_atoms = rc.atom14_mask[aatype].sum(-1).astype(int)
+    complete = (aatype < 20) & ((mask > 0) == (rc.atom14_mask[aatype] > 0)).all(-1)
+    usable = complete & (n_atoms >= 5)
+    same_next = np.append(chain[1:] == chain[:-1], False)                      # row i and row i + 1 are in one chain
+    same_prev = np.append(False, chain[1:] == chain[:-1])
+
+    # the row that loses a backbone atom, in the interior of a chain, and the adjacent damaged pair right after it
+    cand = [r for r in range(1, L - 3) if complete[r] and same_prev[r] and same_next[r] and same_next[r + 1] and same_next[r + 2]
+            and usable[r + 1] and usable[r + 2]]
+    if not cand:
+        raise ValueError("drop_atoms: no interior row followed by two complete non-GLY rows of its chain")
+    lost = int(rng.choice(cand))
+    # a chain terminus
+    ends = [r for r in range(L) if usable[r] and not (same_prev[r] and same_next[r]) and abs(r - lost) > 2]
+    if not ends:
+        raise ValueError("drop_atoms: no complete non-GLY chain terminus")
+    forced = [lost + 1, lost + 2, int(rng.choice(ends))]
+    rest = [int(r) for r in rng.permutation(L) if usable[r] and r != lost and r not in forced]
+    pool = forced + rest
+
+    kinds = {}
+
+    def deal(kind, rows_ok=None):
+        for r in pool:
+            if r not in kinds and n_atoms[r] >= _MIN_ATOMS[kind] and (rows_ok is None or rows_ok[r]):
+                kinds[r] = kind
+                return True
+        return False
+
+    if not deal("hole_cb", np.isin(aatype, (_ARG, _LYS))):
+        deal("hole_cb")
+    for kind in ("hole_cb", "hole_inner", "hole_inner", "tail", "tail", "cb_only", "cb_only", "backbone_only", "backbone_only"):
+        if not deal(kind):
+            raise ValueError(f"drop_atoms: no row left for a second {kind}")
+    want = max(len(kinds), int(round(0.25 * L)) - 1)                          # a quarter of the rows, the masked one among them
+    for r in pool:                                                             # the forced rows come first
+        if r in kinds:
+            continue
+        if r not in forced and len(kinds) >= want:
+            break
+        ok = [k for k in DAMAGE_KINDS if n_atoms[r] >= _MIN_ATOMS[k]]
+        kinds[r] = ok[int(rng.integers(len(ok)))]
+
+    for r, kind in kinds.items():
+        n = n_atoms[r]
+        if kind == "tail":
+            gone = range(int(rng.integers(6, n)), n)
+        elif kind == "cb_only":
+            gone = range(5, n)
+        elif kind == "backbone_only":
+            gone = range(4, n)
+        elif kind == "hole_cb":
+            gone = (4,)
+        else:
+            gone = (int(rng.integers(5, n - 1)),)
+        mask[r, list(gone)] = 0.0
+    mask[lost, int(rng.integers(0, 4))] = 0.0
+    xyz[mask == 0] = np.nan
+
+    # the numbering gap: inside a chain, away from the masked row (whose neighbours' backbone dihedrals are gone already)
+    gaps = [i for i in range(1, L) if same_prev[i] and ridx[i] == ridx[i - 1] + 1 and abs(i - lost) > 3]
+    if not gaps:
+        raise ValueError("drop_atoms: no place for a numbering gap")
+    at = int(rng.choice(gaps))
+    ridx[(np.arange(L) >= at) & (chain == chain[at])] += 4
+    out = dict(protein)
+    out.update(atom_positions=xyz, atom_mask=mask, residue_index=ridx)
+    return out
+
+
 def c5_lengths(n_complexes: int = 256) -> List[int]:
     """Residue counts of benchmark config C5: L_i ~ U{270..330}, default_rng(256)."""
     return [int(x) for x in np.random.default_rng(256).integers(270, 331, size=n_complexes)]

@@ -48,6 +48,19 @@ def _pack3():
     return pack([H.make(97, 267), H.make(65, 9), H.make(97, 267)])
 
 
+def _damaged64():
+    """A complex with incomplete side chains (synth.drop_atoms): missing atoms have radius 0 and a zeroed coordinate in X, one row has
+    no atom at all (a backbone atom is missing), others only their backbone."""
+    from packppi_amd import synth
+    from packppi_amd.featurize import protein_to_batch
+    return protein_to_batch(synth.drop_atoms(synth.make_complex(64, 11), 64))
+
+
+def _pack3_damaged():
+    from packppi_amd.batch import pack
+    return pack([H.make(97, 267), _damaged64(), H.make(97, 267)])
+
+
 def _padded():
     from packppi_amd import synth
     from packppi_amd.batch import collate
@@ -61,7 +74,9 @@ CASES = {
     "c24_row_off": lambda: H.make(24, 5, zero_row=7), "c64_row_off": lambda: H.make(64, 11, zero_row=0),
     "c97_row_off": lambda: H.make(97, 267, zero_row=96), "three_chains_row_off": lambda: H.make(45, 3, n_chains=3, zero_row=20),
     "c65": lambda: H.make(65, 9), "pack3": _pack3, "padded": _padded,
+    "damaged64": _damaged64, "pack3_damaged": _pack3_damaged,
 }
+PACKS = {"pack3": ("c97", "c65", "c97"), "pack3_damaged": ("c97", "damaged64", "c97")}
 
 
 @functools.lru_cache(maxsize=None)
@@ -78,11 +93,11 @@ def reference(name, P=96, probe=1.4, fp64=True):
 @functools.lru_cache(maxsize=None)
 def _reference(name, P, probe, fp64):
     b, (X, radius, chain), offs = case(name)
-    if name == "pack3":
+    if name in PACKS:
         # the restatement works segment by segment: on the same rows it is the references of the three complexes, back to back
-        parts = ("c97", "c65", "c97")
+        parts = PACKS[name]
         assert all(np.array_equal(np.concatenate([case(p)[1][k] for p in parts]), (X, radius, chain)[k], equal_nan=(k == 0)) for k in range(3))
-        assert offs == [0, 97, 162, 259]
+        assert offs == {"pack3": [0, 97, 162, 259], "pack3_damaged": [0, 97, 161, 258]}[name]
         return tuple(np.concatenate([reference(p, P, probe, fp64)[k] for p in parts]) for k in range(3))
     c32 = H.restate(X, radius, chain, offs, points(P), probe)
     c64, amb = H.restate(X, radius, chain, offs, points(P), probe, dtype=np.float64, want_ambiguous=True) if fp64 else (None, None)
@@ -114,8 +129,15 @@ def test_counts_and_areas_against_the_restatement(name):
     # a row without atoms gives zeros
     empty = ~(radius > 0).any(1)
     assert (got[empty] == 0).all() and (area[empty] == 0).all()
-    if name.endswith("row_off"):
+    if name.endswith("row_off") or "damaged" in name:
         assert empty.any()
+    if "damaged" in name:
+        # a missing atom sits at the origin of X with radius 0: it has no points and buries nobody's
+        am = b["atom_mask"].reshape(-1, 14).numpy()
+        table = H.rc.atom14_mask[b["residue_type"].reshape(-1).numpy()]
+        gone = (table > 0) & (am == 0)
+        assert gone.sum() >= 20 and (X[gone] == 0).all() and (got[gone] == 0).all()
+        assert ((am[:, 4:].sum(1) == 0) & (am[:, :4].sum(1) == 4) & (table[:, 4] > 0)).sum() >= 2       # backbone-only rows
     # the derived quantities are what they say
     per_row = torch.from_numpy(got.sum(1))
     assert torch.equal(res.interface.reshape(-1).cpu(), per_row[:, 1] - per_row[:, 2] > 0)
