@@ -279,8 +279,13 @@ def to_pdb(prot: Dict, keep_chains: Optional[list] = None) -> str:
             if m < 0.5:
                 continue
             shown = aname if len(aname) == 4 else f" {aname}"
+            coords = f"{p[0]:>8.3f}{p[1]:>8.3f}{p[2]:>8.3f}"
+            if len(coords) != 24:
+                # -1000 and below, 10000 and above: nine characters would push every column behind them one to the right
+                raise ValueError(f"to_pdb: coordinate {tuple(float(v) for v in p)} of {rname} {chain[i]}{ridx[i]} {aname} does not fit "
+                                 "the 8.3f columns of an ATOM record (-999.999 .. 9999.999); move the structure nearer the origin")
             out.append(f"{'ATOM':<6}{serial:>5} {shown:<4}{'':>1}{rname:>3} {chain[i]:>1}"
-                       f"{ridx[i]:>4}{'':>1}   {p[0]:>8.3f}{p[1]:>8.3f}{p[2]:>8.3f}"
+                       f"{ridx[i]:>4}{'':>1}   {coords}"
                        f"{1.0:>6.2f}{b:>6.2f}          {aname[0]:>2}{'':>2}")
             serial += 1
     out.append(_ter(serial, rc.resnames[aa[-1]], chain[-1], ridx[-1]))

@@ -254,6 +254,38 @@ def drop_atoms(protein: Dict, seed: int) -> Dict:
     return out
 
 
+# ---- structures away from the origin: where a deposited file puts them, on synthetic input ----------------------------------------
+def rotation_matrix(rot_seed) -> np.ndarray:
+    """[3, 3] float64 proper rotation from the unit quaternion ``default_rng(rot_seed).normal(size=4)``; ``None``: the identity."""
+    if rot_seed is None:
+        return np.eye(3)
+    w, x, y, z = (lambda q: q / np.linalg.norm(q))(np.random.default_rng(rot_seed).normal(size=4))
+    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
+                     [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
+                     [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
+
+
+def rigid_motion(protein: Dict, rot_seed, shift) -> Dict:
+    """A copy of ``protein`` with ``atom_positions`` rotated (``rotation_matrix(rot_seed)``, about the origin) and then translated by
+    ``shift`` [3].  The arithmetic is float64 and the result is rounded through float32, as ``make_complex`` rounds its own; NaN slots
+    (missing atoms) stay NaN.  With ``rot_seed=None`` and a zero shift the coordinates come back bit for bit."""
+    xyz = np.asarray(protein["atom_positions"], dtype=np.float64)
+    moved = xyz @ rotation_matrix(rot_seed).T + np.asarray(shift, dtype=np.float64)
+    out = dict(protein)
+    out["atom_positions"] = moved.astype(np.float32).astype(np.float64)
+    return out
+
+
+def snap_to_grid(protein: Dict, bits: int = 9) -> Dict:
+    """A copy of ``protein`` with every coordinate rounded to the nearest multiple of 2^-bits A (NaN slots stay NaN).  Such
+    coordinates, and their differences, stay exact in float32 under a translation by grid multiples while every magnitude involved
+    is below 2^(24 - bits) A: 32768 A for the default 9 bits (a grid of 0.002 A)."""
+    scale = float(1 << bits)
+    out = dict(protein)
+    out["atom_positions"] = np.round(np.asarray(protein["atom_positions"], dtype=np.float64) * scale) / scale
+    return out
+
+
 def c5_lengths(n_complexes: int = 256) -> List[int]:
     """Residue counts of benchmark config C5: L_i ~ U{270..330}, default_rng(256)."""
     return [int(x) for x in np.random.default_rng(256).integers(270, 331, size=n_complexes)]
