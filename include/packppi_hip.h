@@ -587,6 +587,38 @@ pp_status pp_sasa(pp_ctx *ctx, const float *xyz /* DEVICE [N,14,3] or NULL = the
                   int32_t *counts /* DEVICE [N][14][4] or NULL */, float *area /* DEVICE [N][4] */,
                   double *seg_area /* DEVICE [n_seg][4] or NULL */, void *stream);
 
+/* ---- Disulfide bridges (no reference kernel; csrc/pp_disulfide.hip holds the arithmetic) ------------------
+ * Finds the cysteine pairs of every segment whose sulfurs can meet -- from the backbone alone -- and closes them by choosing the
+ * two chi1 next to the caller's angles.  Per segment of the ctx's segment table; pairs never cross segments.
+ *   eligible row   residue_type == PP_RESTYPE_CYS, residue_mask != 0, atom_mask slots 0, 1, 2, 5 (N, CA, C, SG) != 0
+ *   grid           theta_k = (float)(-pi + 2 pi k / 72), k = 0 .. 71, for both chi1 of a pair a < b
+ *   E(p, q)        ((|A-B| - 2.04) / 0.10)^2 + ((ang(CB_a,A,B) - 104) / 10)^2 + ((ang(CB_b,B,A) - 104) / 10)^2
+ *                  + ((|dih(CB_a,A,B,CB_b)| - 90) / 30)^2, A = SG(a, theta_p), B = SG(b, theta_q), the ideal CB and SG of pp_atom14
+ *                  built relative to the row's CA; angles in degrees.  Emin = the minimum over the 72 x 72 points.
+ *   candidates     both rows eligible, |CB_a - CB_b| <= cb_max, Emin <= max_energy
+ *   bonded set     greedy in ascending (Emin, a, b): a pair is taken iff neither row is bonded yet
+ *   closure        a row with fixed[n] != 0 keeps its chi1: its table is its SG at chi[n][0], 72 times.  Emin_r = the minimum of E
+ *                  over that grid, thr = max(Emin_r, min(max_energy, Emin_r + 4)), F = {E <= thr}; the pick is the argmin over F of
+ *                  J = E + (wrap(theta_p - chi[a][0])^2 + wrap(theta_q - chi[b][0])^2) / sigma_chi^2 (a fixed row's term is 0; chi
+ *                  NULL: J = E), ties to the lowest 72 p + q.  Detection never reads fixed.
+ *   pairs          DEVICE int32 [n_pairs][2] of rows, or NULL.  A list replaces detection: no cb_max, no max_energy.  An entry
+ *                  with a row out of range or not eligible, or rows of two segments, is dropped.
+ * Outputs, all on the device, every word with one writer; the call never waits for the stream:
+ *   partner[n]     the bonded partner's row, or -1
+ *   report[n]      (Emin, E at the pick, SG-SG distance at the pick, signed chi3 in radians) on both rows of a bonded pair, else 0
+ *   count[s]       bonded pairs of segment s; -1 in EVERY segment when more pairs lie within cb_max than the candidate list holds
+ *                  (min(N (N - 1) / 2, 64 N)): then nothing is bonded and chi_out = chi
+ *   chi_out        chi bit for bit, except chi_out[a][0] = theta_p and chi_out[b][0] = theta_q of bonded rows that are not fixed.
+ *                  May be chi itself; NULL = detection only.
+ * The first call on a ctx allocates the workspace (sized from N), pp_ctx_destroy frees it.
+ * PP_ERR_INVALID: a null ctx, partner, report or count; chi_out or fixed without chi; n_pairs beyond the list; cb_max or sigma_chi
+ * not finite and positive; a batch without X, atom_mask, residue_type or residue_mask. */
+#define PP_RESTYPE_CYS 4       /* constants.restype_order['C'] */
+pp_status pp_disulfide_close(pp_ctx *ctx, const float *chi /* DEVICE [N,4] or NULL */, const uint8_t *fixed /* DEVICE [N] or NULL */,
+                             const int32_t *pairs /* DEVICE [n_pairs][2] or NULL */, int n_pairs, float cb_max, float max_energy,
+                             float sigma_chi, float *chi_out /* DEVICE [N,4] or NULL */, int32_t *partner /* DEVICE [N] */,
+                             float *report /* DEVICE [N][4] */, int32_t *count /* DEVICE [n_seg] */, void *stream);
+
 /* Measurement aid, no reference counterpart: average duration (ms) of one launch of a hot kernel
  * (which: 0 = node-message kernel, 1 = edge-update kernel), timed with HIP events on `stream`
  * around `iters` launches.  Synchronises the stream. */

@@ -43,6 +43,11 @@ sampling -- behind every reverse step but the last, from time T of the schedule 
 evaluation and a Langevin step of signal-to-noise ratio SNR with a step size per complex.  0.16 is the reference's constant
 (step_correct); nothing here is tuned against a trained checkpoint.  Needs --seed; combines with --repack, --n_decoys, --guide and
 --use_proximal.  Writes corrector.csv (step, t, complex or decoy, s2, n2, eps, amp; empty where no corrector ran).
+--disulfides auto|SPEC (without --disulfides every output byte as before): behind the sampler the chi1 of every
+bonded cysteine pair are set so that the two sulfurs meet -- auto finds the pairs from the backbone, SPEC names them
+('A:5-A:55,A:14-A:38').  With --use_proximal the proximal stage then keeps the bonded residues; with --repack a kept residue keeps its
+chi1.  Not with --n_decoys.  Writes disulfides.csv (chain, number, partner chain, partner number, Emin, E, SG-SG distance, chi3, chi1
+before, chi1 after; angles in degrees) and SSBOND records at the head of structure.pdb.
 """
 import argparse
 import os
@@ -177,6 +182,61 @@ def write_corrector_csv(model, outdir):
         fh.write("\n".join(rows) + "\n")
 
 
+def add_disulfide_arguments(p):
+    """--disulfides.  Its default is SUPPRESSed, like the guide's: without the flag the namespace is what it was before it."""
+    p.add_argument("--disulfides", type=str, default=argparse.SUPPRESS, metavar="auto|SPEC", help="Close disulfide bridges behind the "
+                   "sampler (DESIGN.md section 26): auto detects the cysteine pairs from the backbone, SPEC names them, e.g. "
+                   "'A:5-A:55,A:14-A:38' (chain and PDB residue number). With --use_proximal the proximal stage keeps the bonded "
+                   "residues. Writes disulfides.csv and SSBOND records at the head of structure.pdb.")
+
+
+def disulfides_from_args(args, p=None, protein=None):
+    """The ``disulfides`` value of ``TDiffusionModule.sampling`` from the command line, None without --disulfides: "auto", or (with
+    the parsed input) the row pairs of the residues named."""
+    if not hasattr(args, "disulfides"):
+        return None
+    if p is not None and args.n_decoys is not None:
+        p.error("--disulfides together with --n_decoys is not supported: the ensemble calls do not close bridges")
+    spec = args.disulfides.strip()
+    if spec == "auto" or protein is None:
+        return spec
+    from ..selection import parse_disulfides
+    return parse_disulfides(spec, protein)
+
+
+def disulfides_csv(protein, partner, report, chi_before, chi_after):
+    """The text of disulfides.csv and the bonded row pairs: one line per bonded residue -- chain, number, partner chain, partner
+    number, Emin, E, SG-SG distance (A), chi3, chi1 before, chi1 after (degrees) -- from host lists of ``Context.disulfides``."""
+    deg = 180.0 / np.pi
+    lines = ["chain,number,partner_chain,partner_number,emin,energy,sg_sg_distance,chi3,chi1_before,chi1_after\n"]
+    pairs = []
+    for a, b in enumerate(partner):
+        if b < 0:
+            continue
+        if b > a:
+            pairs.append((a, b))
+        r = report[a]
+        lines.append(f"{protein['chain_id'][a]},{int(protein['residue_index'][a])},{protein['chain_id'][b]},{int(protein['residue_index'][b])},"
+                     f"{r[0]:.4f},{r[1]:.4f},{r[2]:.4f},{r[3] * deg:.2f},{chi_before[a] * deg:.2f},{chi_after[a] * deg:.2f}\n")
+    return "".join(lines), pairs
+
+
+def write_disulfides(model, protein, outdir):
+    """disulfides.csv from the report the run left in ``model.disulfide_reports``; returns the SSBOND text of the written structure."""
+    from ..pdb_io import ssbond_records
+    rep = model.disulfide_reports[-1]
+    if bool((rep["count"] < 0).any()):
+        from ..lib import DISULFIDE_OVERFLOW
+        raise RuntimeError(DISULFIDE_OVERFLOW)
+    partner, report = rep["partner"].reshape(-1).cpu().tolist(), rep["report"].reshape(-1, 4).cpu().tolist()
+    before, after = rep["chi_before"].reshape(-1, 4)[:, 0].cpu().tolist(), rep["chi_after"].reshape(-1, 4)[:, 0].cpu().tolist()
+    text, pairs = disulfides_csv(protein, partner, report, before, after)
+    with open(os.path.join(outdir, "disulfides.csv"), "w") as fh:
+        fh.write(text)
+    print(f"----- disulfides: {len(pairs)} bridges closed -----")
+    return ssbond_records(protein, pairs, [report[a][2] for a, _ in pairs])
+
+
 def write_ensemble(model, batch, protein, args, analysis):
     """--n_decoys: sample, write every decoy, the two tables and the selected decoy; returns the selected angles [1, L, 4]."""
     from .. import constants as rc
@@ -308,6 +368,12 @@ def evaluate_model(model, args):
     if corrector is not None:
         args.guide_kw["corrector"] = corrector
     model.keep_corrector_trace = corrector is not None
+    disulfides = disulfides_from_args(args, protein=protein)
+    if disulfides is not None:
+        from ..selection import residue_names
+        args.guide_kw["disulfides"] = disulfides
+        batch["residue_names"] = residue_names(protein)        # so that a refusal names the residue, not the row
+    model.keep_disulfide_report = disulfides is not None
     fixed = None
     if args.repack is not None:
         from ..selection import device_selector, interface_selection, parse_selection, sasa_selection
@@ -329,6 +395,7 @@ def evaluate_model(model, args):
         write_guide_csv(model, args.outdir)
     if corrector is not None:
         write_corrector_csv(model, args.outdir)
+    ssbond = write_disulfides(model, protein, args.outdir) if disulfides is not None else ""
     if model.saturated() & 4:
         print("----- WARNING: NaN / infinity in the input coordinates or angles: the reference would return NaN here -----")
     if model.saturated() & 3:
@@ -339,7 +406,7 @@ def evaluate_model(model, args):
         xyz = get_atom14_coords(batch.X, batch.residue_type, batch.BB_D, SC_D_sample)
         protein["atom_positions"] = xyz.cpu().squeeze(0).numpy()
         with open(analysis.tmp_pdb, "w") as fh:
-            fh.writelines(insert_obstacle_lines(to_pdb(protein), args.obstacle_lines))
+            fh.writelines(ssbond + insert_obstacle_lines(to_pdb(protein), args.obstacle_lines))
     if obstacles is not None:
         write_obstacles_csv(model, batch, protein, args, SC_D_sample)
     if args.sasa:
@@ -388,6 +455,7 @@ def build_parser():
                    "(residues whose surface the obstacle atoms bury; needs --obstacles).")
     add_guide_arguments(p)
     add_corrector_arguments(p)
+    add_disulfide_arguments(p)
     return p
 
 
@@ -414,6 +482,7 @@ def parse_args(argv=None):
         p.error("--recombine_sweeps must not be negative")
     guide_from_args(args, p)
     corrector_from_args(args, p)
+    disulfides_from_args(args, p)
     return args
 
 

@@ -22,7 +22,8 @@ SYMBOLS = ("pp_version", "pp_last_error", "pp_build_id", "pp_plan_set_knn_ties",
            "pp_score_rows", "pp_so2_set_grids", "pp_so2_score", "pp_dsm_loss",
            "pp_ctx_set_rng_keys", "pp_noise_seeded", "pp_add_noise_seeded", "pp_sample_seeded",
            "pp_sample_partial", "pp_proximal_pinned", "pp_ctx_live_rows", "pp_ensemble_reduce", "pp_ctx_shell",
-           "pp_ensemble_recombine", "pp_ctx_set_obstacles", "pp_sasa", "pp_sample_guided", "pp_sample_corrected")
+           "pp_ensemble_recombine", "pp_ctx_set_obstacles", "pp_sasa", "pp_sample_guided", "pp_sample_corrected",
+           "pp_disulfide_close")
 
 
 FIX_MODES = {"hold": 0, "renoise": 1}         # PP_FIX_HOLD, PP_FIX_RENOISE
@@ -40,6 +41,24 @@ class EnsembleResult(dict):
             return self[k]
         except KeyError as e:
             raise AttributeError(k) from e
+
+
+DISULFIDE_OVERFLOW = ("disulfides: more cysteine pairs lie within cb_max than the candidate list of this context holds "
+                      "(min(N (N - 1) / 2, 64 N)); nothing was bonded -- lower cb_max or name the pairs")
+
+
+class DisulfideResult(EnsembleResult):
+    """What ``Context.disulfides`` returns, all on the device: ``partner`` int32 [N] (the bonded partner's row or -1), ``report``
+    fp32 [N, 4] (Emin, E at the pick, SG-SG distance, signed chi3 in radians; 0 on unbonded rows), ``count`` int32 [n_segments],
+    ``chi`` [B, L, 4] (None for a detection without angles).  ``bonds()`` reads the pairs back."""
+
+    def bonds(self):
+        """[(a, b), ...] with a < b, ascending: the bonded row pairs, on the host (waits for the stream).  ``RuntimeError`` if the
+        call overflowed its candidate list (count -1): it bonded nothing."""
+        if bool((self["count"] < 0).any()):
+            raise RuntimeError(DISULFIDE_OVERFLOW)
+        p = self["partner"].reshape(-1).tolist()
+        return [(a, b) for a, b in enumerate(p) if b > a]
 
 
 class PPTables(C.Structure):
@@ -142,6 +161,7 @@ def load():
     lib.pp_ensemble_recombine.argtypes = [vp, vp, i, vp, i, vp, vp, vp, vp, vp, vp, vp]
     lib.pp_ctx_set_obstacles.argtypes = [vp, vp, vp, i, vp]
     lib.pp_sasa.argtypes = [vp, vp, vp, vp, i, f, vp, vp, vp, vp]
+    lib.pp_disulfide_close.argtypes = [vp, vp, vp, vp, i, f, f, f, vp, vp, vp, vp, vp]
     lib.pp_sample_guided.argtypes = [vp, vp, vp, vp, i, vp, i, i, C.c_uint64, vp, f, vp, vp, vp]
     lib.pp_sample_corrected.argtypes = [vp, vp, vp, vp, i, vp, i, i, C.c_uint64, vp, vp, f, vp, vp, vp, vp]
     _lib = lib
@@ -827,6 +847,70 @@ class Context:
         return EnsembleResult(area=area, seg_area=seg_area, counts=counts if want_counts else None, bsa=area[..., 1] - area[..., 2],
                               interface=per_row[..., 1] - per_row[..., 2] > 0, pocket=per_row[..., 2] - per_row[..., 3] > 0,
                               exposure=torch.where(a0 > 0, area[..., 3] / a0, torch.zeros_like(a0)))
+
+    def disulfide_eligible(self):
+        """bool [N] on the device: the rows ``disulfides`` can bond -- cysteines with residue_mask and the atom_mask of N, CA, C and
+        SG set (the rule of csrc/pp_disulfide.hip, restated with torch)."""
+        for k in ("atom_mask", "residue_mask"):
+            if self._t.get(k) is None:
+                raise RuntimeError(f"disulfides needs a batch with {k}")
+        am = self._t["atom_mask"].reshape(-1, 14)
+        return ((self._t["residue_type"].reshape(-1) == rc.restype_order["C"]) & (self._t["residue_mask"].reshape(-1) != 0)
+                & (am[:, 0] != 0) & (am[:, 1] != 0) & (am[:, 2] != 0) & (am[:, 5] != 0))
+
+    def check_disulfide_pairs(self, pairs, names=None):
+        """Refuse a list of row pairs ``disulfides`` cannot take, naming the offender (``names``: row -> text, default the row
+        number): a row outside the context, a row that is not an eligible cysteine, a pair across two segments, a row named twice.
+        Reads the eligibility back.  Returns the pairs as [(a, b)] with a < b."""
+        from bisect import bisect_right
+        name = (lambda r: str(names[r])) if names is not None else (lambda r: f"row {r}")
+        elig = self.disulfide_eligible().tolist()
+        offs, seen, out = self.seg_offsets_host, {}, []
+        for a, b in pairs:
+            a, b = int(a), int(b)
+            for r in (a, b):
+                if not 0 <= r < self.n_rows:
+                    raise ValueError(f"disulfides: row {r} is outside the {self.n_rows} rows of this context")
+                if not elig[r]:
+                    raise ValueError(f"disulfides: {name(r)} is not a cysteine with N, CA, C and SG present")
+            if bisect_right(offs, a) != bisect_right(offs, b):
+                raise ValueError(f"disulfides: {name(a)} and {name(b)} lie in two segments")
+            for r in (a, b):
+                if r in seen or a == b:
+                    raise ValueError(f"disulfides: {name(r)} is named twice")
+                seen[r] = True
+            out.append((min(a, b), max(a, b)))
+        return out
+
+    def disulfides(self, chi=None, fixed=None, pairs=None, cb_max=5.0, max_energy=10.0, sigma_chi=np.deg2rad(20.0), names=None):
+        """Detect the disulfide bridges of every segment from the backbone and close them (pp_disulfide_close, DESIGN.md section
+        24).  ``chi`` [B, L, 4]: the angles to close from -- the result's ``chi`` equals them bit for bit except the chi1 of the
+        bonded rows; None: detection only.  ``fixed`` [N] mask: rows whose chi1 must not change (needs ``chi``).  ``pairs``: a list
+        of row pairs that replaces detection (no ``cb_max``, no ``max_energy``); it is checked first (``check_disulfide_pairs``).
+        ``cb_max`` in A between ideal CB atoms, ``max_energy`` the largest grid minimum of the bridge energy that still is a bridge,
+        ``sigma_chi`` (radians) what leaving the given chi1 by that much costs next to one unit of bridge energy.  Returns a
+        ``DisulfideResult``; the call itself does not wait for the device (validating ``pairs`` does)."""
+        dev = self.plan.device
+        for k in ("atom_mask", "residue_mask"):
+            if self._t.get(k) is None:
+                raise RuntimeError(f"disulfides needs a batch with {k}")
+        if fixed is not None and chi is None:
+            raise ValueError("disulfides: fixed needs chi")
+        chi_in = self._chi(chi) if chi is not None else None
+        fx = self._mask(fixed, "fixed") if fixed is not None else None
+        pr, n_pairs = None, 0
+        if pairs is not None:
+            rows = self.check_disulfide_pairs(pairs, names)
+            n_pairs = len(rows)
+            pr = torch.tensor(rows if rows else [[0, 0]], dtype=torch.int32).reshape(-1, 2).to(dev).contiguous()
+        out = torch.empty_like(chi_in) if chi_in is not None else None
+        partner = self._new(self.n_rows, dtype=torch.int32)
+        report = self._new(self.n_rows, 4)
+        count = self._new(self.n_segments, dtype=torch.int32)
+        _check(load().pp_disulfide_close(self.handle, _ptr(chi_in), _ptr(fx), _ptr(pr), n_pairs, float(cb_max), float(max_energy),
+                                         float(sigma_chi), _ptr(out), _ptr(partner), _ptr(report), _ptr(count), _stream(dev)),
+               "pp_disulfide_close")
+        return DisulfideResult(partner=partner, report=report, count=count, chi=out)
 
     def saturated(self) -> int:
         """Sticky flag word of this context: 0 = clean; bit 0 / bit 1 = a hidden activation was clamped at 65504 in an edge-level /

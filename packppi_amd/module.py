@@ -132,6 +132,33 @@ def _sampling_refusals(cfg, schedule, batch, use_proximal, return_list, sde_nois
     return gkw, None if corrector is None else _corrector_refusals(corrector, schedule, sde_noise, seed)
 
 
+def _disulfide_refusals(batch, disulfides, return_trajectory, return_list):
+    """The refusals of ``sampling(disulfides=)``, behind every other one.  Returns the row pairs of an explicit request, None for
+    "auto" (``Context.disulfides`` checks the rows themselves where the batch is)."""
+    if _get(batch, "seg_offsets") is None and int(batch.num_proteins) != 1:
+        raise ValueError("disulfides needs a B = 1 batch or a packed one (batch.pack), not a padded B > 1 batch")
+    if return_trajectory:
+        raise ValueError("return_trajectory with disulfides returns the sampler's trajectory: close the bridges separately "
+                         "(Context.disulfides)")
+    if return_list:
+        raise ValueError("return_list with disulfides is not supported: the pinned proximal stage returns the accepted angles")
+    if isinstance(disulfides, str) and disulfides.strip() == "auto":
+        return None
+    if not isinstance(disulfides, str):
+        try:
+            pairs = list(disulfides)
+        except TypeError:
+            raise ValueError('disulfides must be None, "auto", a selection string or a list of residue pairs') from None
+        if all(isinstance(a, (int, np.integer)) and isinstance(b, (int, np.integer)) for a, b in pairs):
+            return [(int(a), int(b)) for a, b in pairs]                   # rows of the batch
+    names = _get(batch, "residue_names")
+    if names is None:
+        raise ValueError("disulfides by chain and residue number needs batch.residue_names (selection.residue_names(protein)); "
+                         "row pairs need nothing")
+    from .selection import parse_disulfides
+    return parse_disulfides(disulfides, dict(chain_id=[n[0] for n in names], residue_index=[n[1] for n in names]))
+
+
 class TDiffusionModule:
     NUM_CHI_ANGLES = 4
     eps = 1e-6
@@ -163,6 +190,8 @@ class TDiffusionModule:
         self.guide_traces = []
         self.keep_corrector_trace = False     # True: corrected runs append (snr, (s2, n2, eps, amp) on the device) to corrector_traces (section 23)
         self.corrector_traces = []
+        self.keep_disulfide_report = False    # True: runs with disulfides= append what Context.disulfides returned (plus chi_before) to disulfide_reports (section 26)
+        self.disulfide_reports = []
         self.to(device)
 
     # ---- construction ----------------------------------------------------------------------
@@ -335,7 +364,8 @@ class TDiffusionModule:
         self._val_loss, self._test_loss = (0.0, 0), (0.0, 0)
 
     def sampling(self, batch, use_proximal: bool = False, return_list: bool = False, sde_noise=None, seed=None,
-                 fixed_mask=None, fixed_chi=None, fixed_mode="renoise", return_trajectory: bool = False, guide=None, corrector=None):
+                 fixed_mask=None, fixed_chi=None, fixed_mode="renoise", return_trajectory: bool = False, guide=None, corrector=None,
+                 disulfides=None):
         """``seed`` (an int, None = the reference's behaviour): the initial noising and the sde noise come from the counter-based
         generator on the device (csrc/pp_rng.h) instead of torch's global one.  The noise of a complex is then a function of
         (seed, its key, its rows, the step) alone: the same complex gets the same angles alone, anywhere in a packed batch and
@@ -370,17 +400,46 @@ class TDiffusionModule:
         constant, not a tuned one), a dict holds any of ``snr``, ``t_on``, ``last``, anything else is an explicit sequence of
         n_schedule - 1 values.  Needs ``seed``; excludes ``sde_noise``; works with ``fixed_mask`` (fixed rows are never moved and
         never counted) and with ``guide``.  With ``return_trajectory`` the tuple ends with (s2, n2, eps, amp) per complex and step,
-        fp64 [n_complexes, n_steps, 4], NaN where no corrector ran; the trajectory holds the angles IN FRONT OF each corrector."""
+        fp64 [n_complexes, n_steps, 4], NaN where no corrector ran; the trajectory holds the angles IN FRONT OF each corrector.
+
+        ``disulfides`` (None = today's code path, untouched): close disulfide bridges behind the sampler (and
+        behind guide and corrector) -- ``Context.disulfides`` sets the chi1 of every bonded cysteine pair next to the sample.  "auto":
+        detect the pairs from the backbone; a list of row pairs ``(a, b)``; or pairs by name, a list of ``((chain, number), (chain,
+        number))`` or a string ``A:5-A:55,...`` (needs ``batch.residue_names``, from ``selection.residue_names(protein)``).  With
+        ``use_proximal`` the bridges are closed first and the proximal stage then runs PINNED on the bonded rows
+        (``proximal_optimizer_packed(..., fixed_mask=)``), so that its accept rule cannot reopen one.  Rows of ``fixed_mask`` keep
+        their chi1.  A packed or B = 1 batch; excludes ``return_trajectory`` and ``return_list``.  ``keep_disulfide_report`` appends
+        every run's result to ``disulfide_reports``."""
         if fixed_mask is None:
             fixed_mask = _get(batch, "fixed_mask")
         gkw, snr = _sampling_refusals(self.hparams.sample_cfg, self.schedule, batch, use_proximal, return_list, sde_noise, seed,
                                       fixed_mask, fixed_mode, return_trajectory, guide, corrector)
+        pairs = _disulfide_refusals(batch, disulfides, return_trajectory, return_list) if disulfides is not None else None
         ctx = self._context(batch)
         init, sde_noise, pin = self._initial_angles(ctx, batch, sde_noise, seed, fixed_mask, fixed_chi, fixed_mode)
         out = self._run_sampler(ctx, init, sde_noise, seed, pin, return_trajectory, gkw, snr)
         if return_trajectory:
             return out
+        if disulfides is not None:
+            return self._disulfide_tail(batch, ctx, out, pairs, fixed_mask, use_proximal)
         return self._proximal_tail(batch, out, use_proximal, return_list)
+
+    def _disulfide_tail(self, batch, ctx, chi, pairs, fixed_mask, use_proximal, norm_rows=None):
+        """Behind the sampler of a run with ``disulfides``: close the bridges (``pairs`` None: detect them), then, with
+        ``use_proximal``, the pinned proximal stage on the bonded rows plus the caller's fixed rows."""
+        names = _get(batch, "residue_names")
+        res = ctx.disulfides(chi=chi, fixed=fixed_mask, pairs=pairs, names=None if names is None else [f"{c}:{n}" for c, n in names])
+        if self.keep_disulfide_report:
+            self.disulfide_reports.append(dict(partner=res.partner, report=res.report, count=res.count, chi_before=chi,
+                                               chi_after=res.chi))
+        if not use_proximal:
+            return res.chi
+        pinned = (res.partner >= 0).reshape(1, -1)
+        if fixed_mask is not None:
+            pinned = pinned | (torch.as_tensor(fixed_mask).to(pinned.device) != 0).reshape(1, -1)
+        cfg = self.hparams.sample_cfg
+        return proximal_optimizer_packed(batch, res.chi, cfg.violation_tolerance_factor, cfg.clash_overlap_tolerance, cfg.lamda,
+                                         cfg.num_steps, norm_rows=norm_rows, fixed_mask=pinned)[2]
 
     def _initial_angles(self, ctx, batch, sde_noise, seed, fixed_mask, fixed_chi, fixed_mode):
         """(the angles noised to t = 1, the sde noise tensor of an unseeded run or None, the pin's keywords or None).  Seeded: the
@@ -466,7 +525,7 @@ class TDiffusionModule:
         return out[0] if isinstance(out, tuple) else out
 
     def repack(self, batch, fixed_mask=None, *, seed, fixed_chi=None, fixed_mode="renoise", use_proximal: bool = False,
-               return_list: bool = False, norm_rows=None, guide=None, corrector=None):
+               return_list: bool = False, norm_rows=None, guide=None, corrector=None, disulfides=None):
         """Partial repacking in one call (DESIGN.md sections 13 and 14): ``sampling(batch, seed=seed, fixed_mask=...)`` -- the rows
         of ``fixed_mask`` (default ``batch.fixed_mask``) keep ``fixed_chi`` (default ``batch.SC_D``), the others are sampled around
         them -- and then, with ``use_proximal``, the PINNED proximal stage (pp_proximal_pinned): the clash mask of every complex, its
@@ -475,7 +534,9 @@ class TDiffusionModule:
         the padded sizes).  Kept rows of the result are ``fixed_chi`` bit for bit with or without the proximal stage.  On a batch with
         obstacle atoms the clash of the pinned stage -- mask, loss, gradient -- includes them.
         ``return_list`` (B = 1, with ``use_proximal``): (sample, per-step angles, losses) as ``sampling`` returns them.
-        ``guide``: as in ``sampling`` (clash-guided sampling of the free rows); None = today's path.  ``corrector``: as in ``sampling``."""
+        ``guide``: as in ``sampling`` (clash-guided sampling of the free rows); None = today's path.  ``corrector``: as in ``sampling``.
+        ``disulfides``: as in ``sampling`` -- a kept row never changes its chi1, a bridge between two kept rows
+        is only reported; the pinned stage then also keeps the bonded rows."""
         if fixed_mask is None:
             fixed_mask = _get(batch, "fixed_mask")
         if fixed_mask is None:
@@ -485,6 +546,11 @@ class TDiffusionModule:
             raise ValueError("return_list=True needs use_proximal=True and a B = 1 batch; for a packed batch use "
                              "functional.proximal_optimizer_packed (per-complex losses [n_complexes, num_steps])")
         cfg = self.hparams.sample_cfg
+        if disulfides is not None:
+            pairs = _disulfide_refusals(batch, disulfides, False, return_list)
+            SC_D_sample = self.sampling(batch, seed=seed, fixed_mask=fixed_mask, fixed_chi=fixed_chi, fixed_mode=fixed_mode, guide=guide,
+                                        corrector=corrector)
+            return self._disulfide_tail(batch, self._context(batch), SC_D_sample, pairs, fixed_mask, use_proximal, norm_rows)
         SC_D_sample = self.sampling(batch, seed=seed, fixed_mask=fixed_mask, fixed_chi=fixed_chi, fixed_mode=fixed_mode, guide=guide, corrector=corrector)
         if not use_proximal:
             return SC_D_sample

@@ -241,6 +241,20 @@ def insert_obstacle_lines(pdb_text: str, lines: List[str]) -> str:
     return "\n".join(out[:at] + list(lines) + out[at:])
 
 
+def ssbond_records(prot: Dict, pairs, lengths=None) -> str:
+    """The SSBOND records of the row pairs ``pairs`` of ``prot`` (80 columns each, serial numbers from 1, symmetry 1555, the bond
+    length from ``lengths`` if given): the text that goes in front of ``to_pdb(prot)``."""
+    out = []
+    for k, (a, b) in enumerate(pairs):
+        ends = "".join(f"CYS {str(prot['chain_id'][r])[:1]} {int(prot['residue_index'][r]):>4d}" + ("    " if i == 0 else "")
+                       for i, r in enumerate((a, b)))
+        ln = f"SSBOND {k + 1:>3d} {ends}".ljust(59) + f"{1555:>6d} {1555:>6d}"
+        if lengths is not None:
+            ln += f" {float(lengths[k]):5.2f}"
+        out.append(ln.ljust(80) + "\n")
+    return "".join(out)
+
+
 def contains_sidechains(pdb_file) -> bool:
     """eval_diffusion.py:43-50."""
     with open(pdb_file, "r") as fh:

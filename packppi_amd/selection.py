@@ -44,6 +44,50 @@ def parse_selection(spec: str, protein: Dict) -> np.ndarray:
     return mask
 
 
+def residue_names(protein: Dict):
+    """[(chain ID, PDB residue number)] per row of ``protein``: what ``batch.residue_names`` holds for
+    ``TDiffusionModule.sampling(disulfides=SPEC)``."""
+    return [(str(c), int(n)) for c, n in zip(protein["chain_id"], protein["residue_index"])]
+
+
+def parse_disulfides(spec, protein: Dict):
+    """Row pairs [(a, b)] of the residue pairs named by ``spec``: a string of comma-separated terms ``CHAIN:N-CHAIN:M`` (chain ID and
+    PDB residue number, negative numbers as in ``A:-3-A:12``) or a list of ``((chain, number), (chain, number))``.  ``ValueError``
+    for a malformed term, a residue that does not exist (unknown chain or number) and a number that several rows carry (insertion
+    codes are not part of the protein dict).  Whether the rows are cysteines that can bond is checked where the batch is
+    (``lib.Context.check_disulfide_pairs``)."""
+    import re
+    chain_id = np.asarray(protein["chain_id"])
+    number = np.asarray(protein["residue_index"]).astype(np.int64)
+    if isinstance(spec, str):
+        terms = [t.strip() for t in spec.split(",") if t.strip()]
+        if not terms:
+            raise ValueError("empty disulfide list")
+        named = []
+        for term in terms:
+            m = re.fullmatch(r"([^:\s]+):(-?\d+)-([^:\s]+):(-?\d+)", term)
+            if m is None:
+                raise ValueError(f"disulfides '{term}': expected CHAIN:N-CHAIN:M")
+            named.append(((m.group(1), int(m.group(2))), (m.group(3), int(m.group(4)))))
+    else:
+        try:
+            named = [((str(a[0]), int(a[1])), (str(b[0]), int(b[1]))) for a, b in spec]
+        except (TypeError, ValueError, IndexError):
+            raise ValueError("disulfides: expected a list of ((chain, number), (chain, number))") from None
+    pairs = []
+    for ends in named:
+        rows = []
+        for chain, num in ends:
+            hit = np.nonzero((chain_id == chain) & (number == num))[0]
+            if len(hit) == 0:
+                raise ValueError(f"disulfides: no residue {chain}:{num}")
+            if len(hit) > 1:
+                raise ValueError(f"disulfides: {len(hit)} rows carry {chain}:{num}")
+            rows.append(int(hit[0]))
+        pairs.append((rows[0], rows[1]))
+    return pairs
+
+
 DEVICE_SELECTORS = {"interface:sasa": "interface", "pocket": "pocket"}       # --repack words answered by Context.sasa
 
 
