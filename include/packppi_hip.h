@@ -619,6 +619,42 @@ pp_status pp_disulfide_close(pp_ctx *ctx, const float *chi /* DEVICE [N,4] or NU
                              float sigma_chi, float *chi_out /* DEVICE [N,4] or NULL */, int32_t *partner /* DEVICE [N] */,
                              float *report /* DEVICE [N][4] */, int32_t *count /* DEVICE [n_seg] */, void *stream);
 
+/* ---- Polar contacts (no reference kernel; csrc/pp_polar.hip holds the arithmetic) ------------------------
+ * Hydrogen bonds, salt bridges and polar obstacle contacts between the heavy atoms of every segment of the ctx's segment table (the
+ * complexes of a packed ctx, the decoys of a group, the B rows of a padded batch).  No pair crosses segments.  Chemistry is caller data:
+ *   cls   DEVICE uint8 [N][14]: bit 0 donor, bit 1 acceptor, bit 2 cation, bit 3 anion; 0 = not polar or absent
+ *   ante  DEVICE int8 [N][14][2]: the slots of the same row the atom is bonded to, -1 = none.  An entry outside -1 .. 13 is found on
+ *         the device: the atom is treated as not polar and bit 2 of pp_ctx_saturated is set
+ *   obst_polar  DEVICE uint8 [M] or NULL: != 0 marks a polar atom of the ctx's obstacle set (pp_ctx_set_obstacles)
+ * Arithmetic (fp32, fp contract off, every operation rounded on its own).  Atom x at p with antecedents at a1 (and a2): base point
+ * b = a1, or (a1 + a2) * 0.5f per component; u = b - p (0 without an antecedent: no direction test).  Pair (x at p, y at q):
+ * d = q - p, d2 = ((dx dx) + (dy dy)) + (dz dz), sx = ((ux dx) + (uy dy)) + (uz dz); e = p - q, sy the same sum of u_y and e.
+ *   hydrogen bond  x and y in different rows of one segment, (x donor and y acceptor) or (x acceptor and y donor),
+ *                  d2 <= hb_max * hb_max (rounded once on the host), sx <= 0 and sy <= 0: both angles antecedent-atom...partner are at
+ *                  least 90 degrees.  Symmetric by construction; a NaN makes a comparison false and gives no bond.
+ *                  Skipped: both atoms in backbone slots 0 or 3 of adjacent rows (|n - j| = 1) with equal chain_indices.
+ *   salt bridge    rows n != j of one segment: a cation atom of one and an anion atom of the other with d2 <= sb_max * sb_max
+ *   obstacle       an atom o of the segment's obstacle range with obst_polar[o] != 0 and d2 <= hb_max * hb_max (no direction test)
+ * Outputs, all on the device, integers; every word has one writer, except seg (integer atomics).  Does not wait for the stream,
+ * except that the first call on a ctx allocates the workspace, which may wait for the device.
+ *   n_partners[n][a]   (hydrogen-bond partners of the atom, polar obstacle atoms within reach): the true counts
+ *   partners[n][a]     the lowest min(count, PP_POLAR_CAP) partner codes, ascending, then -1; code = (row - first row of the
+ *                      segment) * 14 + slot: a segment gets the same words alone, packed behind others, or as a decoy
+ *   res[n][0..7]       sums over the row's atoms: partners of side-chain atoms (slot >= 4) in rows of the same chain (0) / another
+ *                      chain (1); of backbone atoms (slots 0 and 3) same chain (2) / another (3); salt-bridge partner rows same chain
+ *                      (4) / another (5); obstacle partners (6); atoms with cls != 0 and neither kind of partner (7)
+ *   seg[s][0..7]       bonds counted once (0), between chains (1), with a side-chain atom (2), both (3); salt-bridged row pairs (4),
+ *                      between chains (5); bonds to obstacle atoms (6); unsatisfied polar atoms (7)
+ * The row pre-filter (spheres around slot 1 that hold the row's polar atoms) changes no output word.  The first call on a ctx
+ * allocates the workspace (sized from N), pp_ctx_destroy frees it.  Works on a geometry-only plan.
+ * PP_ERR_INVALID: a null ctx, cls, ante, n_partners, res or seg; hb_max or sb_max not finite or not positive; a batch without
+ * chain_indices; no coordinates (xyz NULL and no X); obst_polar on a ctx without obstacles. */
+#define PP_POLAR_CAP 4
+pp_status pp_polar(pp_ctx *ctx, const float *xyz /* DEVICE [N,14,3] or NULL = the batch's X */, const uint8_t *cls /* DEVICE [N][14] */,
+                   const int8_t *ante /* DEVICE [N][14][2] */, const uint8_t *obst_polar /* DEVICE [M] or NULL */, float hb_max,
+                   float sb_max, int32_t *partners /* DEVICE [N][14][PP_POLAR_CAP] or NULL */, int32_t *n_partners /* DEVICE [N][14][2] */,
+                   int32_t *res /* DEVICE [N][8] */, int32_t *seg /* DEVICE [n_seg][8] */, void *stream);
+
 /* Measurement aid, no reference counterpart: average duration (ms) of one launch of a hot kernel
  * (which: 0 = node-message kernel, 1 = edge-update kernel), timed with HIP events on `stream`
  * around `iters` launches.  Synchronises the stream. */

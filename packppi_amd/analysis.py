@@ -106,6 +106,75 @@ def write_sasa_csv(path, protein, res, row=0):
           f"{seg[2] - seg[3]:.1f} A^2 buried by obstacle atoms; {int(res.interface[row].sum())} interface residues -----")
 
 
+POLAR_CSV_HEADER = ("chain,number,name,hb_side_same,hb_side_other,hb_back_same,hb_back_other,salt_same,salt_other,"
+                    "obstacle_partners,unsatisfied")
+HBONDS_CSV_HEADER = "chain_a,number_a,name_a,atom_a,chain_b,number_b,name_b,atom_b,distance,status"
+
+
+def obstacle_polar(obstacles):
+    """uint8 [M]: 1 for the atoms of ``pdb_io.obstacle_atoms`` output whose element is N or O (``constants.obstacle_polar_elements``),
+    what ``Context.polar(obst_polar=...)`` takes; None for None."""
+    from . import constants as rc
+    if obstacles is None:
+        return None
+    return np.array([1 if str(e).upper() in rc.obstacle_polar_elements else 0 for e in obstacles["element"]], dtype=np.uint8)
+
+
+def polar_csv_text(protein, res, buns=None):
+    """The text of ``polar.csv``: one line per residue of ``protein`` -- chain, residue number, residue name and the eight ``res``
+    columns of ``Context.polar`` ([n, 8]); with ``buns`` ([n, 14] bool, or [n] counts) one more column, the buried unsatisfied polar
+    atoms of the residue.  Rows of ``protein`` beyond n get zeros."""
+    from . import constants as rc
+    res = np.asarray(res, dtype=np.int64).reshape(-1, 8)
+    if buns is not None:
+        buns = np.asarray(buns)
+        buns = buns.reshape(len(buns), -1).astype(np.int64).sum(1)
+    lines = [POLAR_CSV_HEADER + (",buns" if buns is not None else "")]
+    for r, (cid, num, aa) in enumerate(zip(protein["chain_id"], protein["residue_index"], protein["aaindex"])):
+        v = res[r] if r < len(res) else np.zeros(8, np.int64)
+        tail = "" if buns is None else f",{int(buns[r]) if r < len(buns) else 0}"
+        lines.append(f"{cid},{int(num)},{rc.resnames[int(aa)]}," + ",".join(str(int(x)) for x in v) + tail)
+    return "\n".join(lines) + "\n"
+
+
+def polar_bonds(partners):
+    """The hydrogen bonds behind the ``partners`` array of ONE segment ([n, 14, 4] integers, on the host) as a sorted list of
+    ((row, slot), (row, slot)) with the lower code first: a bond is listed when either atom lists the other."""
+    p = np.asarray(partners).reshape(-1, 14, np.asarray(partners).shape[-1])
+    out = set()
+    for r, s, k in zip(*np.nonzero(p >= 0)):
+        a, b = int(r) * 14 + int(s), int(p[r, s, k])
+        out.add((min(a, b), max(a, b)))
+    return [(divmod(a, 14), divmod(b, 14)) for a, b in sorted(out)]
+
+
+def hbonds_csv_text(protein, xyz, partners, native_partners=None):
+    """The text of ``hbonds.csv`` for ONE complex: one line per hydrogen bond between chains or with a side-chain atom (slot >= 4) --
+    chain, number, residue name and atom name on both sides, the distance in A at ``xyz`` [n, 14, 3] and, against
+    ``native_partners`` (the bonds of the input's own side chains), ``kept`` (in both), ``gained`` (only here) or ``lost`` (only
+    there; the distance is then that at ``xyz`` too); without ``native_partners`` the status is empty."""
+    from . import constants as rc
+    xyz = np.asarray(xyz, dtype=np.float64).reshape(-1, 14, 3)
+    chain, num, aa = list(protein["chain_id"]), list(protein["residue_index"]), list(protein["aaindex"])
+
+    def wanted(bond):
+        (ra, sa), (rb, sb) = bond
+        return chain[ra] != chain[rb] or sa >= 4 or sb >= 4
+
+    here = [b for b in polar_bonds(partners) if wanted(b)]
+    rows = [(b, "") for b in here]
+    if native_partners is not None:
+        there = set(b for b in polar_bonds(native_partners) if wanted(b))
+        rows = [(b, "kept" if b in there else "gained") for b in here] + [(b, "lost") for b in sorted(there - set(here))]
+        rows.sort(key=lambda t: t[0])
+    lines = [HBONDS_CSV_HEADER]
+    for ((ra, sa), (rb, sb)), status in rows:
+        d = float(np.linalg.norm(xyz[ra, sa] - xyz[rb, sb]))
+        side = lambda r, s: f"{chain[r]},{int(num[r])},{rc.resnames[int(aa[r])]},{rc.atom14_names[int(aa[r])][s]}"
+        lines.append(f"{side(ra, sa)},{side(rb, sb)},{d:.3f},{status}")
+    return "\n".join(lines) + "\n"
+
+
 class ProteinAnalysis:
     def __init__(self, molprobity_clash_loc, tmp_dir, device="cuda"):
         self.molprobity_clash_loc = molprobity_clash_loc

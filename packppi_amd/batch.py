@@ -39,7 +39,9 @@ ROW_KEYS = ("fixed_mask",)
 # (x, y, z, radius) and ``obstacle_offsets`` int32 [n + 1] -- complex (or, in a batch of decoys, group) k owns the atoms
 # obstacle_offsets[k] .. obstacle_offsets[k + 1] - 1 --, with ``obstacle_offsets_host``, the same as a list.  Not per-residue
 # tensors: nothing gives them a batch axis, pads or slices them.  A batch without obstacles has none of the keys.
-OBSTACLE_KEYS = ("obstacle_xyzr", "obstacle_offsets", "obstacle_offsets_host")
+# ``obstacle_polar`` uint8 [M] (1 = a polar atom, N or O: what ``Context.polar`` counts as a partner) rides
+# along where the obstacles came with their elements (``pdb_io.obstacle_atoms``); a batch whose obstacles have none lacks the key.
+OBSTACLE_KEYS = ("obstacle_xyzr", "obstacle_offsets", "obstacle_offsets_host", "obstacle_polar")
 
 
 def has_obstacles(b) -> bool:
@@ -57,8 +59,22 @@ def _obstacles_of(c):
     return x[offs[0]:offs[1]], offs[1] - offs[0]
 
 
-def _set_obstacles(out, parts, like):
-    """Store the obstacle keys of a batch whose complexes (groups) own the atom blocks ``parts`` ([M_k, 4] or None), in order."""
+def _obstacle_polar_of(c):
+    """uint8 [M] of one complex: its ``obstacle_polar`` cut to its range, or None (no obstacles, or obstacles without the key)."""
+    if not has_obstacles(c) or c.get("obstacle_polar") is None:
+        return None
+    offs = c.get("obstacle_offsets_host") or [int(x) for x in c["obstacle_offsets"].tolist()]
+    return c["obstacle_polar"].reshape(-1)[offs[0]:offs[1]]
+
+
+def _set_obstacles(out, parts, like, polar=None):
+    """Store the obstacle keys of a batch whose complexes (groups) own the atom blocks ``parts`` ([M_k, 4] or None), in order.
+    ``polar``: the complexes' ``obstacle_polar`` blocks (or None each); if any complex has one the batch gets the key, with zeros
+    for the atoms of a complex that has none."""
+    if polar is not None and any(q is not None for q in polar):
+        blocks = [(q.to(device=like.device, dtype=torch.uint8) if q is not None else
+                   torch.zeros(int(p.shape[0]), dtype=torch.uint8, device=like.device)) for p, q in zip(parts, polar) if p is not None]
+        out["obstacle_polar"] = torch.cat(blocks, 0) if blocks else torch.zeros(0, dtype=torch.uint8, device=like.device)
     offs = [0]
     for p in parts:
         offs.append(offs[-1] + (0 if p is None else int(p.shape[0])))
@@ -212,7 +228,7 @@ def pack(complexes: Iterable[Batch], trim: bool = True) -> Batch:
     out["seg_offsets"] = torch.tensor(offs, dtype=torch.int32).to(out["X"].device, non_blocking=True)
     out["seg_offsets_host"] = offs
     if any(has_obstacles(c) for c in complexes):
-        _set_obstacles(out, [_obstacles_of(c)[0] for c in complexes], out["X"])
+        _set_obstacles(out, [_obstacles_of(c)[0] for c in complexes], out["X"], [_obstacle_polar_of(c) for c in complexes])
     return out
 
 
@@ -325,7 +341,7 @@ def replicate_many(complexes: Iterable[Batch], n_decoys: int, keys=None) -> Batc
     # obstacles belong to the group: one range per complex, which its n_decoys segments share (lib.Context maps segment s to
     # range s // n_decoys)
     if any(has_obstacles(c) for c in complexes):
-        _set_obstacles(out, [_obstacles_of(c)[0] for c in complexes], out["X"])
+        _set_obstacles(out, [_obstacles_of(c)[0] for c in complexes], out["X"], [_obstacle_polar_of(c) for c in complexes])
     out["complex_keys"] = all_keys
     out["n_decoys"] = n_decoys
     out["n_groups"] = len(complexes)

@@ -242,7 +242,8 @@ def write_ensemble(model, batch, protein, args, analysis):
     from .. import constants as rc
     kw = dict(recombine=True, recombine_sweeps=args.recombine_sweeps) if args.recombine else {}
     out = model.sample_ensemble(batch, args.n_decoys, seed=args.seed, use_proximal=args.use_proximal, select=args.select,
-                                return_all=True, **kw, **(dict(sasa=True) if args.sasa else {}), **args.guide_kw)
+                                return_all=True, **kw, **(dict(sasa=True) if args.sasa else {}),
+                                **(dict(polar=True) if getattr(args, "polar", False) else {}), **args.guide_kw)
     chi, packed = out["decoys"]
     best = int(out["best"][0])
     dev, clash = out["dev"].cpu().tolist(), out["clash"].cpu().tolist()
@@ -262,9 +263,12 @@ def write_ensemble(model, batch, protein, args, analysis):
         fh.write(final)
     with open(os.path.join(args.outdir, "ensemble.csv"), "w") as fh:
         bsa = out["bsa"].cpu().tolist() if args.sasa else None
-        fh.write("decoy,key,dev,clash,selected" + (",bsa" if args.sasa else "") + "\n")
+        pcols = [k for k in POLAR_ENSEMBLE_COLUMNS if k in out] if getattr(args, "polar", False) else []
+        pvals = [out[k].cpu().tolist() for k in pcols]
+        fh.write("decoy,key,dev,clash,selected" + (",bsa" if args.sasa else "") + "".join("," + k for k in pcols) + "\n")
         for d, key in enumerate(out["keys"]):
-            fh.write(f"{d},{key},{dev[d]!r},{clash[d]!r},{int(d == best)}" + (f",{bsa[d]!r}" if args.sasa else "") + "\n")
+            fh.write(f"{d},{key},{dev[d]!r},{clash[d]!r},{int(d == best)}" + (f",{bsa[d]!r}" if args.sasa else "")
+                     + "".join(f",{int(v[d])}" for v in pvals) + "\n")
     conf = out["confidence"][0].cpu().tolist()
     conf += [[0.0] * 4] * (len(protein["aaindex"]) - len(conf))
     with open(os.path.join(args.outdir, "confidence.csv"), "w") as fh:
@@ -320,7 +324,7 @@ def obstacle_share(model, batch, chi):
     with_set = ctx.clash(chi, **kw)
     ctx.set_obstacles(None)
     without = ctx.clash(chi, **kw)
-    ctx.set_obstacles(batch.obstacle_xyzr, ctx._obstacle_ranges(batch))
+    ctx.set_obstacles(batch.obstacle_xyzr, ctx._obstacle_ranges(batch), polar=batch.get("obstacle_polar"))
     return (with_set - without)[0].cpu().tolist()
 
 
@@ -344,6 +348,37 @@ def write_sasa(batch, protein, outdir, chi, name="sasa.csv"):
     if chi.shape[1] != batch.SC_D.shape[1]:
         chi = torch.cat([chi, batch.SC_D[:, chi.shape[1]:]], 1)
     write_sasa_csv(os.path.join(outdir, name), protein, solvent_accessibility(batch, chi))
+
+
+POLAR_ENSEMBLE_COLUMNS = ("hbonds", "hbonds_interface", "salt_interface", "buns_interface")
+
+
+def write_polar(batch, protein, outdir, chi, sasa=False, native=False, names=("polar.csv", "hbonds.csv")):
+    """--polar: polar.csv and hbonds.csv of the B = 1 ``batch`` at the angles ``chi`` [1, n, 4] (n < L: as in ``write_sasa``), and
+    the summary line.  ``sasa``: polar.csv gains the column buns.  ``native``: the input has side chains of its own -- hbonds.csv
+    marks every bond kept, gained or lost against them and the summary gives the recovery.  The polar obstacle atoms are the
+    batch's (``obstacle_polar``), as in the ensemble columns.  ``names``: the two file names."""
+    from ..analysis import hbonds_csv_text, polar_csv_text
+    from ..functional import _ctx_for, polar_contacts, polar_recovery
+    chi = chi.to(batch.SC_D.device)
+    if chi.shape[1] != batch.SC_D.shape[1]:
+        chi = torch.cat([chi, batch.SC_D[:, chi.shape[1]:]], 1)
+    res = polar_contacts(batch, chi, sasa=sasa)
+    ref = polar_contacts(batch) if native else None
+    xyz = _ctx_for(batch).atom14(chi)[0].cpu().numpy()
+    with open(os.path.join(outdir, names[0]), "w") as fh:
+        fh.write(polar_csv_text(protein, res.res[0].cpu().numpy(), res.buns[0].cpu().numpy() if sasa else None))
+    with open(os.path.join(outdir, names[1]), "w") as fh:
+        fh.write(hbonds_csv_text(protein, xyz, res.partners[0].cpu().numpy(), ref.partners[0].cpu().numpy() if native else None))
+    seg = res.seg[0].cpu().tolist()
+    line = (f"----- polar: {seg[0]} hydrogen bonds, {seg[1]} between chains, {seg[5]} salt bridges between chains, "
+            f"{seg[7]} polar atoms without a partner")
+    if sasa:
+        line += f", {int(res.buns.sum())} of them buried ({int(res.buns_interface.sum())} by the interface)"
+    if native:
+        n, k = polar_recovery(ref, res)
+        line += f"; recovered {int(k[0])} of {int(n[0])} native side-chain hydrogen bonds"
+    print(line + " -----")
 
 
 def evaluate_model(model, args):
@@ -411,6 +446,8 @@ def evaluate_model(model, args):
         write_obstacles_csv(model, batch, protein, args, SC_D_sample)
     if args.sasa:
         write_sasa(batch, protein, args.outdir, SC_D_sample)
+    if getattr(args, "polar", False):
+        write_polar(batch, protein, args.outdir, SC_D_sample, sasa=args.sasa, native=contains_sidechains(args.input))
     if contains_sidechains(args.input):
         metric = analysis.get_metric(true_pdb=args.input, pred_pdb=analysis.tmp_pdb)
         print(f"----- Metric: ----- {metric}")
@@ -453,6 +490,12 @@ def build_parser():
                    "atoms, the buried interface area and the exposure; with --n_decoys ensemble.csv gains the column bsa. "
                    "--repack also takes interface:sasa (the delta-SASA interface of the input, made on the device) and pocket "
                    "(residues whose surface the obstacle atoms bury; needs --obstacles).")
+    p.add_argument("--polar", action="store_true", default=argparse.SUPPRESS, help="Write polar.csv (per residue: hydrogen-bond "
+                   "partners of side-chain and backbone atoms within and between chains, salt-bridge partner residues, polar "
+                   "obstacle contacts, polar atoms without a partner; with --sasa the buried ones, buns) and hbonds.csv (every "
+                   "hydrogen bond between chains or with a side-chain atom, kept | gained | lost against the input's own side "
+                   "chains) for the written structure (DESIGN.md section 27); with --n_decoys ensemble.csv gains the columns "
+                   "hbonds, hbonds_interface, salt_interface and, with --sasa, buns_interface.")
     add_guide_arguments(p)
     add_corrector_arguments(p)
     add_disulfide_arguments(p)

@@ -21,6 +21,10 @@ clash against them at the wild type's angles (new side chains at chi = 0) and at
 that structure (per residue the solvent-accessible area at four nested levels, the buried interface area and the exposure; the file
 ``eval_diffusion --sasa`` writes as sasa.csv), and ``mutants.csv`` gains the column ``bsa``, the interface area the selected decoy
 buries.
+--polar (without it every output byte as before): next to every ``mutant_<tag>.pdb`` a ``polar_<tag>.csv`` and a
+``hbonds_<tag>.csv`` of that structure (the files ``eval_diffusion --polar`` writes as polar.csv and hbonds.csv, without the
+comparison against the input: the mutant has other side chains), and ``mutants.csv`` gains the columns ``hbonds``,
+``hbonds_interface``, ``salt_interface`` and, with --sasa, ``buns_interface`` of the selected decoy.
 --guide SCALE ... (without it every output byte as before): the shell is sampled with clash guidance, as
 ``eval_diffusion --guide``; ``guide.csv`` has one block of lines per decoy of every set.
 --corrector SNR [--corrector_from T] (without it every output byte as before): the shell is sampled with a
@@ -71,10 +75,13 @@ def evaluate_model(model, args):
     model.keep_guide_trace = guide is not None
     corrector = corrector_from_args(args)
     model.keep_corrector_trace = corrector is not None
+    polar = getattr(args, "polar", False)
+    pcols = ("hbonds", "hbonds_interface", "salt_interface") + (("buns_interface",) if args.sasa else ()) if polar else ()
     results = model.mutate([(protein, s) for s in sets], seed=args.seed, radius=args.radius, shell=args.shell,
                            n_decoys=args.n_decoys, use_proximal=args.use_proximal, select=args.select, fixed_mode=args.fixed_mode,
                            **(dict(recombine=True, recombine_sweeps=args.recombine_sweeps) if args.recombine else {}),
-                           **(dict(sasa=True) if args.sasa else {}), **(dict(guide=guide) if guide is not None else {}),
+                           **(dict(sasa=True) if args.sasa else {}), **(dict(polar=True) if polar else {}),
+                           **(dict(guide=guide) if guide is not None else {}),
                            **(dict(corrector=corrector) if corrector is not None else {}))
     if guide is not None:
         write_guide_csv(model, args.outdir)
@@ -82,7 +89,7 @@ def evaluate_model(model, args):
         write_corrector_csv(model, args.outdir)
     ddg = predict_ddg(protein, sets, args) if args.ap_ckpt else None
     rows = ["tag,shell_rows,selected_decoy,clash,dev" + (",clash_recombined,rows_recombined" if args.recombine else "")
-            + (",ddg,ddg_inv" if ddg else "") + (",bsa" if args.sasa else "")]
+            + (",ddg,ddg_inv" if ddg else "") + (",bsa" if args.sasa else "") + "".join("," + k for k in pcols)]
     for i, (s, r) in enumerate(zip(sets, results)):
         tag = (r["tag"] or s).replace(",", "_")
         b = r["batch"]
@@ -106,6 +113,11 @@ def evaluate_model(model, args):
             from .eval_diffusion import write_sasa
             line += f",{float(r['bsa'][best])!r}"
             write_sasa(b, mutant, args.outdir, r["SC_D"], name=f"sasa_{tag}.csv")
+        if polar:
+            from .eval_diffusion import write_polar
+            line += "".join(f",{int(r[k][best])}" for k in pcols)
+            write_polar(b, mutant, args.outdir, r["SC_D"], sasa=args.sasa,
+                        names=(f"polar_{tag}.csv", f"hbonds_{tag}.csv"))
         rows.append(line)
         print(f"----- {tag}: {int(r['shell'].sum())} residues repacked, decoy {best} of {args.n_decoys} selected"
               + (f", {int(r['rows_recombined'])} residues recombined from other decoys" if args.recombine else "") + " -----")
@@ -160,6 +172,9 @@ def build_parser():
     p.add_argument("--sasa", action="store_true", help="Write sasa_<tag>.csv next to every mutant (DESIGN.md section 20): per residue "
                    "the solvent-accessible area at four nested levels, the buried interface area and the exposure; mutants.csv gains "
                    "the column bsa.")
+    p.add_argument("--polar", action="store_true", default=argparse.SUPPRESS, help="Write polar_<tag>.csv and hbonds_<tag>.csv next "
+                   "to every mutant (DESIGN.md section 27): hydrogen bonds, salt bridges and polar atoms without a partner; "
+                   "mutants.csv gains the columns hbonds, hbonds_interface, salt_interface and, with --sasa, buns_interface.")
     add_guide_arguments(p)
     add_corrector_arguments(p)
     return p

@@ -92,7 +92,7 @@ def main(argv=None):
             with_set = ctx.clash(chi, **kw)
             ctx.set_obstacles(None)
             shares.append((with_set - ctx.clash(chi, **kw))[0].cpu().tolist())
-            ctx.set_obstacles(batch.obstacle_xyzr, ctx._obstacle_ranges(batch))
+            ctx.set_obstacles(batch.obstacle_xyzr, ctx._obstacle_ranges(batch), polar=batch.get("obstacle_polar"))
         with open(os.path.join(args.outdir, "obstacles.csv"), "w") as fh:
             fh.write("residue,chain,clash_obstacles_before,clash_obstacles_after\n")
             for num, cid, b, a in zip(protein["residue_index"], protein["chain_id"], *shares):

@@ -41,6 +41,50 @@ van_der_waals_radius = {"C": 1.7, "N": 1.55, "O": 1.52, "S": 1.8}
 # 2.0-2.3 A, which is not a clash.
 obstacle_radius = dict(van_der_waals_radius, P=1.80, F=1.47, CL=1.75, BR=1.85, I=1.98, SE=1.90)
 
+# Polar atoms (pp_polar), written out by atom name.  Class bits: 1 donor, 2 acceptor, 4 cation, 8 anion.  The
+# backbone N (except proline's) donates, the backbone O accepts; the side-chain atoms are listed per residue.  An antecedent is a
+# heavy atom covalently bonded to the polar atom within the residue: one or two per atom, also named here.
+POLAR_DONOR, POLAR_ACCEPTOR, POLAR_CATION, POLAR_ANION = 1, 2, 4, 8
+polar_donors = {"ARG": ("NE", "NH1", "NH2"), "ASN": ("ND2",), "GLN": ("NE2",), "HIS": ("ND1", "NE2"), "LYS": ("NZ",), "SER": ("OG",),
+                "THR": ("OG1",), "TYR": ("OH",), "TRP": ("NE1",)}
+polar_acceptors = {"ASP": ("OD1", "OD2"), "GLU": ("OE1", "OE2"), "ASN": ("OD1",), "GLN": ("OE1",), "HIS": ("ND1", "NE2"),
+                   "SER": ("OG",), "THR": ("OG1",), "TYR": ("OH",)}
+polar_cations = {"LYS": ("NZ",), "ARG": ("NE", "NH1", "NH2")}
+polar_anions = {"ASP": ("OD1", "OD2"), "GLU": ("OE1", "OE2")}
+polar_antecedent_names = {
+    "ARG": {"NE": ("CD", "CZ"), "NH1": ("CZ",), "NH2": ("CZ",)}, "ASN": {"OD1": ("CG",), "ND2": ("CG",)},
+    "ASP": {"OD1": ("CG",), "OD2": ("CG",)}, "GLN": {"OE1": ("CD",), "NE2": ("CD",)}, "GLU": {"OE1": ("CD",), "OE2": ("CD",)},
+    "HIS": {"ND1": ("CG", "CE1"), "NE2": ("CD2", "CE1")}, "LYS": {"NZ": ("CE",)}, "SER": {"OG": ("CB",)}, "THR": {"OG1": ("CB",)},
+    "TRP": {"NE1": ("CD1", "CE2")}, "TYR": {"OH": ("CZ",)}}
+obstacle_polar_elements = ("N", "O")          # the obstacle atoms pp_polar counts as partners
+
+
+def _polar_tables():
+    cls = np.zeros((21, 14), np.uint8)
+    ante = -np.ones((21, 14, 2), np.int8)
+    for t in range(20):
+        names, rn = atom14_names[t], resnames[t]
+        for s, nm in enumerate(names):
+            if not nm:
+                continue
+            c, an = 0, ()
+            if nm == "N" and rn != "PRO":
+                c, an = POLAR_DONOR, ("CA",)
+            elif nm == "O":
+                c, an = POLAR_ACCEPTOR, ("C",)
+            else:
+                c = ((POLAR_DONOR if nm in polar_donors.get(rn, ()) else 0) | (POLAR_ACCEPTOR if nm in polar_acceptors.get(rn, ()) else 0)
+                     | (POLAR_CATION if nm in polar_cations.get(rn, ()) else 0) | (POLAR_ANION if nm in polar_anions.get(rn, ()) else 0))
+                if c:
+                    an = polar_antecedent_names[rn][nm]
+            cls[t, s] = c
+            for k, a in enumerate(an):
+                ante[t, s, k] = names.index(a)
+    return cls, ante
+
+
+polar_class, polar_antecedent = _polar_tables()   # [21,14] u8 class bits, [21,14,2] i8 antecedent slots (-1 = none)
+
 
 @lru_cache(maxsize=16)
 def make_atom14_dists_bounds(overlap_tolerance: float = 1.5,

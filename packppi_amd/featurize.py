@@ -73,7 +73,9 @@ def chain_numbers_and_offset_index(protein: Dict):
 
 def _add_obstacles(data: Batch, obstacles) -> Batch:
     """Store obstacle atoms (``pdb_io.obstacle_atoms`` output, or any dict with ``xyz`` [M, 3] and ``radius`` [M]; None = none) in
-    per-complex data as ``obstacle_xyzr`` [M, 4] float32 and ``obstacle_offsets`` [2] (batch.OBSTACLE_KEYS)."""
+    per-complex data as ``obstacle_xyzr`` [M, 4] float32 and ``obstacle_offsets`` [2] (batch.OBSTACLE_KEYS).  Obstacles that come
+    with their ``element`` list also give ``obstacle_polar`` uint8 [M] (``analysis.obstacle_polar``: 1 for N and O), the atoms
+    ``Context.polar`` counts as partners; nothing else reads it."""
     if obstacles is None:
         return data
     xyz = torch.as_tensor(np.asarray(obstacles["xyz"], np.float32)).reshape(-1, 3)
@@ -86,6 +88,12 @@ def _add_obstacles(data: Batch, obstacles) -> Batch:
     data["obstacle_xyzr"] = torch.cat((xyz, rad[:, None]), 1).contiguous()
     data["obstacle_offsets"] = torch.tensor([0, M], dtype=torch.int32)
     data["obstacle_offsets_host"] = [0, M]
+    if obstacles.get("element") is not None:
+        from .analysis import obstacle_polar
+        polar = torch.from_numpy(obstacle_polar(obstacles)).reshape(-1)
+        if polar.shape[0] != M:
+            raise ValueError(f"obstacles: {M} positions, {polar.shape[0]} elements")
+        data["obstacle_polar"] = polar
     return data
 
 

@@ -91,6 +91,65 @@ def solvent_accessibility(batch, SC_D=None, n_points=96, probe=1.4, radius=None,
     return _ctx_for(batch).sasa(chi=SC_D, n_points=n_points, probe=probe, radius=radius, want_counts=want_counts)
 
 
+def polar_contacts(batch, chi=None, hb_max=3.5, sb_max=4.0, want_partners=True, sasa=False, bury_points=0, n_points=96, probe=1.4,
+                   obst_polar=None):
+    """Hydrogen bonds, salt bridges and unsatisfied polar atoms of every complex (``lib.Context.polar``, pp_polar; DESIGN.md section
+    27), on the geometry plan: at the angles ``chi`` (through atom14), else at the batch's X.  Padded, packed and decoy batches alike.
+    ``sasa=True`` also runs ``Context.sasa`` at the same coordinates (``n_points``, ``probe``) and fills ``buns`` and
+    ``buns_interface``.  ``obst_polar`` [M]: which obstacle atoms are polar, in place of the batch's ``obstacle_polar``."""
+    ctx = _ctx_for(batch)
+    xyz = ctx.atom14(chi) if chi is not None else None
+    sa = ctx.sasa(xyz=xyz, n_points=n_points, probe=probe, want_counts=True) if sasa else None
+    return ctx.polar(xyz=xyz, hb_max=hb_max, sb_max=sb_max, want_partners=want_partners, sasa=sa, bury_points=bury_points,
+                     obst_polar=obst_polar)
+
+
+def polar_bond_keys(partners, seg_offsets=None):
+    """The hydrogen bonds behind a ``partners`` array of ``Context.polar`` ([B, L, 14, 4], packed [1, N, 14, 4]) as sorted unique int64
+    keys ``(segment * M + low code) * M + high code`` with ``M = 14 * rows`` of the array's second axis, on the device.  A bond is in
+    the set when either of its atoms lists the other, so an atom with more partners than the list holds loses a bond only if the
+    partner's list is full as well.  ``seg_offsets``: the segment table of a packed batch (a list); None: every [L] row of the array
+    is a segment.  Returns (keys, M, number of segments).  The values stay on the device, but the number of keys depends on the data
+    (a boolean selection and ``torch.unique``): the call waits for the stream."""
+    p = partners.reshape(-1, 14, partners.shape[-1]).long()
+    n, L = p.shape[0], int(partners.shape[-3])
+    dev = p.device
+    row = torch.arange(n, device=dev)
+    if seg_offsets is None:
+        n_seg = n // L
+        seg, first = row // L, (row // L) * L
+    else:
+        offs = torch.as_tensor([int(x) for x in seg_offsets], device=dev)
+        n_seg = offs.numel() - 1
+        seg = torch.bucketize(row, offs[1:], right=True).clamp(max=n_seg - 1)
+        first = offs[seg]
+    M = 14 * L
+    own = ((row - first) * 14)[:, None, None] + torch.arange(14, device=dev)[None, :, None]
+    own = own.expand_as(p)
+    lo, hi = torch.minimum(own, p), torch.maximum(own, p)
+    key = (seg[:, None, None] * M + lo) * M + hi
+    return torch.unique(key[p >= 0]), M, n_seg
+
+
+def polar_recovery(native, sampled, seg_offsets=None):
+    """How many of the native hydrogen bonds with at least one side-chain atom (slot >= 4) a sample has: ``native`` and ``sampled``
+    are two ``partners`` arrays of ``Context.polar`` over the same rows (or the results themselves), ``seg_offsets`` the segment
+    table of a packed batch.  Returns (native int64 [n_segments], recovered int64 [n_segments]) on the device, computed with
+    torch from the bonds either atom lists (``polar_bond_keys``): atoms at the cap of their list are included.  Nothing is copied
+    to the host, but the call waits for the stream (the bond sets have data-dependent sizes)."""
+    a = native["partners"] if isinstance(native, dict) else native
+    b = sampled["partners"] if isinstance(sampled, dict) else sampled
+    if a is None or b is None or tuple(a.shape) != tuple(b.shape):
+        raise ValueError("polar_recovery: needs two partners arrays of the same shape")
+    ka, M, n_seg = polar_bond_keys(a, seg_offsets)
+    kb, _, _ = polar_bond_keys(b, seg_offsets)
+    side = ((ka % M) % 14 >= 4) | (((ka // M) % M) % 14 >= 4)
+    ka = ka[side]
+    kept = torch.isin(ka, kb)
+    s = ka // (M * M)
+    return torch.bincount(s, minlength=n_seg), torch.bincount(s[kept], minlength=n_seg)
+
+
 def proximal_optimizer_packed(packed_batch, SC_D, violation_tolerance_factor, clash_overlap_tolerance, lamda, num_steps=50,
                               norm_rows=None, want_traj=False, fixed_mask=None, return_moved=False):
     """``proximal_optimizer`` for every complex of a packed batch (``batch.pack``; a B = 1 batch counts as one complex) in the same

@@ -23,7 +23,7 @@ SYMBOLS = ("pp_version", "pp_last_error", "pp_build_id", "pp_plan_set_knn_ties",
            "pp_ctx_set_rng_keys", "pp_noise_seeded", "pp_add_noise_seeded", "pp_sample_seeded",
            "pp_sample_partial", "pp_proximal_pinned", "pp_ctx_live_rows", "pp_ensemble_reduce", "pp_ctx_shell",
            "pp_ensemble_recombine", "pp_ctx_set_obstacles", "pp_sasa", "pp_sample_guided", "pp_sample_corrected",
-           "pp_disulfide_close")
+           "pp_disulfide_close", "pp_polar")
 
 
 FIX_MODES = {"hold": 0, "renoise": 1}         # PP_FIX_HOLD, PP_FIX_RENOISE
@@ -162,6 +162,7 @@ def load():
     lib.pp_ctx_set_obstacles.argtypes = [vp, vp, vp, i, vp]
     lib.pp_sasa.argtypes = [vp, vp, vp, vp, i, f, vp, vp, vp, vp]
     lib.pp_disulfide_close.argtypes = [vp, vp, vp, vp, i, f, f, f, vp, vp, vp, vp, vp]
+    lib.pp_polar.argtypes = [vp, vp, vp, vp, vp, f, f, vp, vp, vp, vp, vp]
     lib.pp_sample_guided.argtypes = [vp, vp, vp, vp, i, vp, i, i, C.c_uint64, vp, f, vp, vp, vp]
     lib.pp_sample_corrected.argtypes = [vp, vp, vp, vp, i, vp, i, i, C.c_uint64, vp, vp, f, vp, vp, vp, vp]
     _lib = lib
@@ -313,7 +314,7 @@ class BatchKey:
     them on every call (encoder.py:198-246).  A tensor the context had to copy (dtype / layout) is covered the same way: the
     key watches the caller's tensor, not the copy."""
 
-    KEYS = tuple(k for k, _ in _BATCH_SPEC) + ("seg_offsets", "obstacle_xyzr", "obstacle_offsets")
+    KEYS = tuple(k for k, _ in _BATCH_SPEC) + ("seg_offsets", "obstacle_xyzr", "obstacle_offsets", "obstacle_polar")
 
     def __init__(self, batch):
         self.tensors = [t if isinstance(t, torch.Tensor) else None for t in (_get(batch, k) for k in self.KEYS)]
@@ -388,7 +389,7 @@ class Context:
         self.n_obstacles = 0
         ox = _get(batch, "obstacle_xyzr")
         if ox is not None:
-            self.set_obstacles(ox, self._obstacle_ranges(batch))
+            self.set_obstacles(ox, self._obstacle_ranges(batch), polar=_get(batch, "obstacle_polar"))
 
     def _obstacle_ranges(self, batch):
         """(first, count) per segment from the batch's ``obstacle_offsets``: one range per segment, or, in a batch of decoys
@@ -403,14 +404,17 @@ class Context:
             raise RuntimeError(f"obstacle_offsets describes {n_rng} ranges, the batch has {n_seg} segments (n_decoys {D})")
         return [(offs[s // D], offs[s // D + 1] - offs[s // D]) for s in range(n_seg)]
 
-    def set_obstacles(self, xyzr=None, seg_range=None):
+    def set_obstacles(self, xyzr=None, seg_range=None, polar=None):
         """Install fixed obstacle atoms (pp_ctx_set_obstacles): ``xyzr`` [M, 4] (x, y, z, radius),
         ``seg_range`` one (first, count) per segment (default: every segment owns all M).  ``clash``, the ``proximal*`` calls and
         ``ensemble_recombine`` then count the overlap of every side-chain atom with the obstacles of its segment.  ``xyzr`` None or
         empty clears the set: every call then gives the bits of a context that never had one.  The context keeps its own copy.
         ``ValueError``: a range outside the atoms; non-finite coordinates or radii or a negative radius in a host tensor (in a device
-        tensor they are found on the device and set bit 2 of ``saturated()``: no read-back here)."""
+        tensor they are found on the device and set bit 2 of ``saturated()``: no read-back here).  ``polar`` [M] (non-zero = a polar
+        atom; the batch's ``obstacle_polar``): what ``polar()`` counts as obstacle partners unless it is told otherwise; None:
+        none of them.  Only ``polar()`` reads it."""
         dev = self.plan.device
+        self._obst_polar = None
         if xyzr is None or xyzr.numel() == 0:
             _check(load().pp_ctx_set_obstacles(self.handle, None, None, 0, _stream(dev)), "pp_ctx_set_obstacles")
             self.n_obstacles = 0
@@ -429,6 +433,11 @@ class Context:
             raise ValueError(f"seg_range reaches outside the {M} obstacle atoms")
         _check(load().pp_ctx_set_obstacles(self.handle, _ptr(x), C.c_void_p(rng.ctypes.data), M, _stream(dev)), "pp_ctx_set_obstacles")
         self.n_obstacles = M
+        if polar is not None:
+            pol = (torch.as_tensor(polar).to(device=dev) != 0).to(torch.uint8).reshape(-1).contiguous()
+            if pol.numel() != M:
+                raise ValueError(f"polar has {pol.numel()} entries for {M} obstacle atoms")
+            self._obst_polar = pol
 
     def _new(self, *shape, dtype=torch.float32):
         return torch.empty(*shape, dtype=dtype, device=self.plan.device)
@@ -911,6 +920,87 @@ class Context:
                                          float(sigma_chi), _ptr(out), _ptr(partner), _ptr(report), _ptr(count), _stream(dev)),
                "pp_disulfide_close")
         return DisulfideResult(partner=partner, report=report, count=count, chi=out)
+
+    def polar_tables(self):
+        """(cls uint8 [N, 14], ante int8 [N, 14, 2]) on the device, what ``polar`` hands to pp_polar by default:
+        ``constants.polar_class`` / ``polar_antecedent`` gathered by residue_type, with the class zeroed where atom_mask is 0 for the
+        atom or for any of its antecedents.  Made once per context."""
+        if getattr(self, "_polar_tabs", None) is None:
+            dev = self.plan.device
+            if self._t.get("atom_mask") is None:
+                raise RuntimeError("polar needs a batch with atom_mask (or cls and ante)")
+            rt = self._t["residue_type"].reshape(-1)
+            am = self._t["atom_mask"].reshape(-1, 14) != 0
+            cls = torch.from_numpy(np.asarray(rc.polar_class, dtype=np.uint8)).to(dev)[rt]
+            ante = torch.from_numpy(np.asarray(rc.polar_antecedent, dtype=np.int8)).to(dev)[rt]
+            ok = am
+            for k in range(2):
+                a = ante[..., k].long()
+                ok = ok & ((a < 0) | torch.gather(am, 1, a.clamp(min=0)))
+            self._polar_tabs = ((cls * ok.to(torch.uint8)).contiguous(), ante.contiguous())
+        return self._polar_tabs
+
+    def polar(self, chi=None, xyz=None, hb_max=3.5, sb_max=4.0, want_partners=True, sasa=None, bury_points=0, obst_polar=None,
+              cls=None, ante=None):
+        """Hydrogen bonds, salt bridges and polar obstacle contacts per segment, on the device (pp_polar).
+        Coordinates as in ``sasa``: ``atom14(chi)`` if ``chi`` is given, else ``xyz`` [B, L, 14, 3], else the batch's X.  ``hb_max``
+        and ``sb_max`` in A between heavy atoms.  ``obst_polar`` [M] (non-zero = polar), one entry per atom of the context's obstacle
+        set; None: the batch's ``obstacle_polar`` (``protein_to_batch(..., obstacles=...)`` makes it from the elements
+        ``pdb_io.obstacle_atoms`` returns: N and O; ``set_obstacles(polar=)``), or no polar obstacle atom if there is none.  ``cls`` [B, L,
+        14] / ``ante`` [B, L, 14, 2]: class bits and antecedent slots other than ``polar_tables()``.  Returns an ``EnsembleResult``:
+        ``n_partners`` int32 [B, L, 14, 2] (hydrogen-bond partners, polar obstacle atoms in reach), ``partners`` int32 [B, L, 14, 4]
+        (the lowest partner codes (row - first row of the segment) * 14 + slot, ascending, then -1; None without
+        ``want_partners``), ``res`` int32 [B, L, 8], ``seg`` int32 [n_segments, 8] (include/packppi_hip.h lists the columns), and,
+        derived here with torch: ``polar`` bool [B, L, 14] (the class is not 0), ``unsat`` = polar without a partner of either
+        kind, and with ``sasa`` (a ``sasa(..., want_counts=True)`` result at the same coordinates) ``buns`` = unsat and
+        counts[..., 3] <= bury_points (buried with everything around it) and ``buns_interface`` = buns whose counts[..., 1] >
+        bury_points (exposed in the isolated chain: buried by the partner).  No host synchronisation."""
+        import math
+        dev = self.plan.device
+        if self._t.get("chain_indices") is None:
+            raise RuntimeError("polar needs a batch with chain_indices")
+        for name, v in (("hb_max", hb_max), ("sb_max", sb_max)):
+            if not (math.isfinite(float(v)) and float(v) > 0):
+                raise ValueError(f"polar: {name} must be finite and positive")
+        if int(bury_points) < 0:
+            raise ValueError("polar: bury_points must not be negative")
+        if sasa is not None and _get(sasa, "counts") is None:
+            raise ValueError("polar: sasa must be a Context.sasa(..., want_counts=True) result")
+        if (cls is None) != (ante is None):
+            raise ValueError("polar: cls and ante go together")
+        if cls is None:
+            cls, ante = self.polar_tables()
+        else:
+            cls = torch.as_tensor(cls).to(device=dev, dtype=torch.uint8).contiguous()
+            ante = torch.as_tensor(ante).to(device=dev, dtype=torch.int8).contiguous()
+            if cls.numel() != self.n_rows * 14 or ante.numel() != self.n_rows * 28:
+                raise ValueError(f"polar: cls / ante have {cls.numel()} / {ante.numel()} elements, this context has {self.n_rows} rows")
+        op = getattr(self, "_obst_polar", None) if self.n_obstacles else None
+        if obst_polar is not None:
+            if self.n_obstacles == 0:
+                raise ValueError("polar: obst_polar on a context without obstacle atoms")
+            op = (torch.as_tensor(obst_polar).to(device=dev) != 0).to(torch.uint8).reshape(-1).contiguous()
+            if op.numel() != self.n_obstacles:
+                raise ValueError(f"polar: obst_polar has {op.numel()} entries, the context holds {self.n_obstacles} obstacle atoms")
+        if chi is not None:
+            xyz = self.atom14(chi)
+        elif xyz is not None:
+            xyz = self._xyz(xyz)
+        partners = self._new(self.B, self.L, 14, 4, dtype=torch.int32) if want_partners else None
+        n_partners = self._new(self.B, self.L, 14, 2, dtype=torch.int32)
+        res = self._new(self.B, self.L, 8, dtype=torch.int32)
+        seg = self._new(self.n_segments, 8, dtype=torch.int32)
+        _check(load().pp_polar(self.handle, _ptr(xyz), _ptr(cls), _ptr(ante), _ptr(op), float(hb_max), float(sb_max), _ptr(partners),
+                               _ptr(n_partners), _ptr(res), _ptr(seg), _stream(dev)), "pp_polar")
+        polar = cls.reshape(self.B, self.L, 14) != 0
+        unsat = polar & (n_partners.sum(-1) == 0)
+        out = EnsembleResult(n_partners=n_partners, partners=partners, res=res, seg=seg, polar=polar, unsat=unsat, buns=None,
+                             buns_interface=None)
+        if sasa is not None:
+            counts = _get(sasa, "counts").reshape(self.B, self.L, 14, 4)
+            out["buns"] = unsat & (counts[..., 3] <= int(bury_points))
+            out["buns_interface"] = out["buns"] & (counts[..., 1] > int(bury_points))
+        return out
 
     def saturated(self) -> int:
         """Sticky flag word of this context: 0 = clean; bit 0 / bit 1 = a hidden activation was clamped at 65504 in an edge-level /

@@ -581,15 +581,37 @@ class TDiffusionModule:
         if select not in SELECT:
             raise ValueError(f"select must be one of 'clash', 'medoid' or None, got {select!r}")
 
-    def _reduce_ensemble(self, packed, chi, select, return_all, recombine, recombine_sweeps, sasa):
+    @staticmethod
+    def _decoy_polar(ctx, packed, chi, sasa):
+        """The polar contacts of every segment (decoy) at ``chi``, ONE pp_polar over the packed decoys: int32
+        [n_segments] ``hbonds``, ``hbonds_interface`` and ``salt_interface`` (columns 0, 1 and 5 of ``Context.polar().seg``) and, with
+        ``sasa``, ``buns_interface`` int64 [n_segments] (buried unsatisfied polar atoms that the isolated chain exposes) and ``bsa``.
+        The polar obstacle atoms are those the packed batch carries (``obstacle_polar``, per group like the obstacles)."""
+        xyz = ctx.atom14(chi)
+        sa = ctx.sasa(xyz=xyz, want_counts=True) if sasa else None
+        pol = ctx.polar(xyz=xyz, want_partners=False, sasa=sa)
+        out = dict(hbonds=pol.seg[:, 0], hbonds_interface=pol.seg[:, 1], salt_interface=pol.seg[:, 5])
+        if sasa:
+            offs = packed.seg_offsets_host
+            lens = torch.tensor([b - a for a, b in zip(offs[:-1], offs[1:])], device=xyz.device)
+            seg_of_row = torch.repeat_interleave(torch.arange(len(offs) - 1, device=xyz.device), lens, output_size=offs[-1])
+            per_row = pol.buns_interface.reshape(-1, 14).sum(1)
+            out["buns_interface"] = torch.zeros(len(offs) - 1, dtype=torch.int64, device=xyz.device).index_add_(0, seg_of_row, per_row)
+            out["bsa"] = sa.seg_area[:, 1] - sa.seg_area[:, 2]
+        return out
+
+    def _reduce_ensemble(self, packed, chi, select, return_all, recombine, recombine_sweeps, sasa, polar=False):
         """What the two ensemble calls do with the decoys' angles: the per-residue clash, ``Context.ensemble_reduce``, the
-        recombination and the buried surface if asked for; the selected (or recombined) angles, or the ``return_all`` dict."""
+        recombination, the buried surface and the polar contacts if asked for; the selected (or recombined) angles, or the
+        ``return_all`` dict."""
         cfg = self.hparams.sample_cfg
         ctx, D = self._context(packed), int(packed.n_decoys)
         per_res = ctx.clash(chi, cfg.violation_tolerance_factor, cfg.clash_overlap_tolerance)
         res = ctx.ensemble_reduce(chi, D, per_res=per_res, select=select)
         rec, extra = self._recombine(ctx, chi, D, res, recombine_sweeps) if recombine else (None, {})
-        if sasa and return_all:
+        if polar and return_all:
+            extra = dict(extra, **self._decoy_polar(ctx, packed, chi, sasa))
+        elif sasa and return_all:
             extra = dict(extra, bsa=self._decoy_bsa(ctx, chi))
         if not return_all:
             return rec.chi if recombine else res.chi_best
@@ -597,7 +619,8 @@ class TDiffusionModule:
                     confidence=res.resultant, keys=list(packed.complex_keys), **extra)
 
     def sample_ensemble(self, batch, n_decoys, *, seed=None, use_proximal: bool = False, select="clash", return_all: bool = False,
-                        recombine: bool = False, recombine_sweeps: int = 64, sasa: bool = False, guide=None, corrector=None):
+                        recombine: bool = False, recombine_sweeps: int = 64, sasa: bool = False, guide=None, corrector=None,
+                        polar: bool = False):
         """``n_decoys`` seeded samples of every complex in ONE packed pass, reduced on the device.  On
         complexes with obstacle atoms the decoys of a group share the group's obstacles, and the clash that
         ranks them, the proximal stage and the recombination include the overlap with them.  ``batch``: a
@@ -623,6 +646,11 @@ class TDiffusionModule:
         ``sasa``: ``return_all`` gains ``bsa``, fp64 [n_complexes * n_decoys]: the surface every decoy buries
         between its chains (``Context.sasa`` at the decoy's angles, ``seg_area[1] - seg_area[2]``).  Nothing else changes.
 
+        ``polar``: ``return_all`` gains ``hbonds``, ``hbonds_interface`` and ``salt_interface``, int32
+        [n_complexes * n_decoys] -- every decoy's hydrogen bonds, those between chains and its salt bridges between chains, from ONE
+        ``Context.polar`` over the packed decoys -- and, with ``sasa`` too, ``buns_interface`` (buried unsatisfied polar atoms that
+        the isolated chain exposes).  They rank nothing: ``select`` has no mode for them.
+
         ``guide``: every decoy is sampled with clash guidance, as ``sampling(guide=...)`` samples the complex
         alone under the decoy's key; None = today's path.  ``corrector``: likewise -- every decoy is a segment and gets
         its own corrector step size, the bits of ``sampling(seed=, corrector=)`` of that complex alone under ``decoy_key``."""
@@ -640,11 +668,11 @@ class TDiffusionModule:
         if _get(packed, "fixed_mask") is not None:
             raise ValueError("ensembles under a fixed_mask are not supported: sample_ensemble samples every row")
         chi = self.sampling(packed, use_proximal=use_proximal, seed=seed, guide=guide, corrector=corrector)
-        return self._reduce_ensemble(packed, chi, select, return_all, recombine, recombine_sweeps, sasa)
+        return self._reduce_ensemble(packed, chi, select, return_all, recombine, recombine_sweeps, sasa, polar)
 
     def repack_ensemble(self, batch, fixed_mask=None, *, n_decoys, seed, fixed_chi=None, fixed_mode="renoise",
                         use_proximal: bool = False, select="clash", return_all: bool = False, recombine: bool = False,
-                        recombine_sweeps: int = 64, sasa: bool = False, guide=None, corrector=None):
+                        recombine_sweeps: int = 64, sasa: bool = False, guide=None, corrector=None, polar: bool = False):
         """``sample_ensemble`` under a pin: ``n_decoys`` seeded partial repackings of every complex in ONE packed
         pass, reduced on the device.  ``batch``: a B = 1 batch, or a list of complexes (per-complex data or B = 1 batches).  Every
         complex carries its ``fixed_mask`` (1 = keep; [1, L] on a B = 1 batch, [L] on per-complex data), or ``fixed_mask`` gives it:
@@ -657,7 +685,8 @@ class TDiffusionModule:
         with and without ``use_proximal``.  pp_ensemble_reduce is used unchanged: kept rows are identical in every decoy, so their
         ``resultant`` is 1 to rounding and they add (to rounding) nothing to ``dev``; they enter the per-decoy means of ``dev`` and
         ``clash`` with the same weight in all decoys of a group, so they dilute both equally and do not change the ranking.
-        Returns what ``sample_ensemble`` returns (``sasa``: the ``bsa`` key as there).  ``guide``, ``corrector``: as in ``sampling``."""
+        Returns what ``sample_ensemble`` returns (``sasa``: the ``bsa`` key as there; ``polar``: its keys as there).  ``guide``,
+        ``corrector``: as in ``sampling``."""
         from .batch import Batch, replicate_many
         self._check_select(select)
         single = not isinstance(batch, (list, tuple))
@@ -693,11 +722,11 @@ class TDiffusionModule:
                              for g, (c, r) in enumerate(zip(complexes, refs)) for _ in range(D)]).unsqueeze(0)
         chi = self.repack(packed, seed=seed, fixed_chi=ref, fixed_mode=fixed_mode, use_proximal=use_proximal,
                           norm_rows=[n for n in sizes for _ in range(D)] if use_proximal else None, guide=guide, corrector=corrector)
-        return self._reduce_ensemble(packed, chi, select, return_all, recombine, recombine_sweeps, sasa)
+        return self._reduce_ensemble(packed, chi, select, return_all, recombine, recombine_sweeps, sasa, polar)
 
     def mutate(self, proteins_and_mutations, *, seed, radius=10.0, shell="ca", n_decoys=1, use_proximal: bool = False,
                select="clash", fixed_mode="renoise", max_rows=200_000, log=print, recombine: bool = False,
-               recombine_sweeps: int = 64, sasa: bool = False, guide=None, corrector=None):
+               recombine_sweeps: int = 64, sasa: bool = False, guide=None, corrector=None, polar: bool = False):
         """Mutant modelling: put each mutation set into its complex, repack what it touches, return the mutant.
         ``proteins_and_mutations``: a list of ``(protein dict, mutations)`` pairs, ``mutations`` a string ("RA47A,EA48A") or dicts as
         ``featurize.parse_mutstr`` returns them; several sets of one protein are repeated pairs.  Set i of the call gets the noise
@@ -725,6 +754,9 @@ class TDiffusionModule:
         the overlap with them.  The network and the shell rule do not see them.
 
         ``sasa``: every dict gains ``bsa`` fp64 [n_decoys], the surface each decoy buries between its chains.
+
+        ``polar``: every dict gains ``hbonds``, ``hbonds_interface`` and ``salt_interface`` int32 [n_decoys]
+        and, with ``sasa`` too, ``buns_interface`` [n_decoys], as ``sample_ensemble`` describes them.
 
         ``guide``: the shell is sampled with clash guidance, as in ``sampling``; rows outside the shell are
         fixed rows, which are never nudged.  ``corrector``: as in ``sampling``; the rows outside the shell
@@ -763,7 +795,7 @@ class TDiffusionModule:
                 pinned.append(p)
             out = self.repack_ensemble(pinned, n_decoys=n_decoys, seed=seed, fixed_mode=fixed_mode, use_proximal=use_proximal,
                                        select=select, return_all=True, recombine=recombine, recombine_sweeps=recombine_sweeps,
-                                       sasa=sasa, guide=guide, corrector=corrector)
+                                       sasa=sasa, guide=guide, corrector=corrector, polar=polar)
             final = out["recombined"] if recombine else out["selected"]
             pos = gctx.atom14(final)
             picks = unpack(pb, out["pick"].reshape(1, -1)) if recombine else [None] * len(members)
@@ -780,6 +812,9 @@ class TDiffusionModule:
                     results[i].update(pick=pad_rows(pk, n, out["best"][g].expand(1, n)), clash_recombined=out["clash_trace"][g, -1], rows_recombined=moved)
                 if sasa:
                     results[i]["bsa"] = out["bsa"][g * n_decoys:(g + 1) * n_decoys]
+                for k in ("hbonds", "hbonds_interface", "salt_interface", "buns_interface") if polar else ():
+                    if k in out:
+                        results[i][k] = out[k][g * n_decoys:(g + 1) * n_decoys]
         return results
 
     def sample_from(self, batch, SC_D_init, sde_noise=None):
