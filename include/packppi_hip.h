@@ -13,7 +13,11 @@
  *     library never synchronises the device, except where stated;
  *   - no exceptions cross the ABI: calls return pp_status, pp_last_error() gives the message
  *     of the calling thread's most recent failure;
- *   - a pp_ctx is not thread-safe; different ctxs may be driven from different threads.
+ *   - a pp_ctx is not thread-safe; different ctxs may be driven from different threads;
+ *   - a pp_ctx may be driven on one stream now and on another later, but the library orders nothing between two streams: a call
+ *     on stream B sees what an earlier call on stream A left in the ctx only if the caller has ordered B behind A (an event
+ *     wait, a synchronisation).  The one ordering the library does itself is the workspace hand-over of pp_ctx_destroy.
+ *     tests/test_streams_gpu.py runs every stream-taking entry on a busy non-default stream.
  */
 #ifndef PACKPPI_HIP_H
 #define PACKPPI_HIP_H
@@ -166,7 +170,8 @@ void pp_ctx_destroy(pp_ctx *ctx);
 pp_status pp_complex_prepare_packed(pp_plan *plan, const pp_batch *batch, const int32_t *seg_offsets, int n_seg,
                                     int min_len, int max_len, void *stream, pp_ctx **ctx);
 
-/* Inspection (tests): copy out E_idx [B,L,K] and the embedded edges h_E0 [B,L,K,128]; K = min(32,L). */
+/* Inspection (tests): copy out E_idx [B,L,K] and the embedded edges h_E0 [B,L,K,128]; K = min(32,L).  The copies are enqueued on
+ * `stream`; the call does not wait for them. */
 pp_status pp_ctx_get_graph(pp_ctx *ctx, int64_t *E_idx, float *hE0, void *stream);
 
 /* Replace the ctx's neighbour lists by the caller's E_idx [B,L,K] (per-complex numbering, as

@@ -490,6 +490,7 @@ __global__ void k_widen_idx(const int32_t *__restrict__ src, int64_t *__restrict
 }
 
 extern "C" pp_status pp_ctx_get_graph(pp_ctx *c, int64_t *E_idx, float *hE0, void *stream) {
+    if (c) c->last_stream = static_cast<hipStream_t>(stream);      // the copies below read the arena on `stream`
     if (!c) FAIL(PP_ERR_INVALID, "pp_ctx_get_graph: null ctx");
     if (!c->plan->has_network) FAIL(PP_ERR_INVALID, "pp_ctx_get_graph: plan was created without network weights");
     hipStream_t s = static_cast<hipStream_t>(stream);

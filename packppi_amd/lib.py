@@ -345,6 +345,8 @@ class Context:
         B, L = batch["residue_type"].shape
         self.B, self.L, self.K = int(B), int(L), min(32, int(L))
         self._t = {}
+        # tensors this context made and hands to the kernels by raw pointer, and the streams it has run on (``_stream``)
+        self._owned, self._streams = [], {}
         for key, dt in _BATCH_SPEC:
             t = _get(batch, key)
             if t is None:
@@ -354,7 +356,7 @@ class Context:
                 continue
             if t.device.type != "cuda" or (t.device.index is not None and t.device.index != dev.index):
                 raise RuntimeError(f"batch.{key} is on {t.device}, expected {dev} (call batch.to(device) first)")
-            self._t[key] = t.to(dt).contiguous()
+            self._t[key] = self._own(t.to(dt).contiguous(), t)
         pb = PPBatch(self.B, self.L, *[(self._t[k].data_ptr() if self._t[k] is not None else None)
                                        for k, _ in _BATCH_SPEC])
         h = C.c_void_p()
@@ -364,7 +366,7 @@ class Context:
         self.packed = seg is not None
         if not self.packed:
             self.seg_offsets_host = [s * self.L for s in range(self.B + 1)]
-            _check(lib.pp_complex_prepare(plan.handle, C.byref(pb), _stream(dev), C.byref(h)), "pp_complex_prepare")
+            _check(lib.pp_complex_prepare(plan.handle, C.byref(pb), self._stream(), C.byref(h)), "pp_complex_prepare")
         else:
             # ragged batch without padding rows (batch.pack): [1, sum of lengths, ...] + the complexes' first rows; the host
             # copy of the table that pack() carries along saves the read-back
@@ -379,11 +381,11 @@ class Context:
             lens = [b - a for a, b in zip(offs[:-1], offs[1:])]
             if self.B != 1 or len(offs) < 2 or offs[-1] != self.L or offs[0] != 0 or min(lens) < 1:
                 raise RuntimeError("seg_offsets does not describe this batch")
-            self._t["seg_offsets"] = seg.to(device=dev, dtype=torch.int32).contiguous()
+            self._t["seg_offsets"] = self._own(seg.to(device=dev, dtype=torch.int32).contiguous(), seg)
             self.seg_offsets_host = offs
             self.K = min(32, min(lens))
             _check(lib.pp_complex_prepare_packed(plan.handle, C.byref(pb), self._t["seg_offsets"].data_ptr(), len(lens),
-                                                 min(lens), max(lens), _stream(dev), C.byref(h)),
+                                                 min(lens), max(lens), self._stream(), C.byref(h)),
                    "pp_complex_prepare_packed")
         self.handle = h
         self.n_obstacles = 0
@@ -416,7 +418,7 @@ class Context:
         dev = self.plan.device
         self._obst_polar = None
         if xyzr is None or xyzr.numel() == 0:
-            _check(load().pp_ctx_set_obstacles(self.handle, None, None, 0, _stream(dev)), "pp_ctx_set_obstacles")
+            _check(load().pp_ctx_set_obstacles(self.handle, None, None, 0, self._stream()), "pp_ctx_set_obstacles")
             self.n_obstacles = 0
             return
         src = torch.as_tensor(xyzr)
@@ -431,13 +433,35 @@ class Context:
             raise ValueError(f"seg_range has {rng.shape[0]} entries for {self.n_segments} segments")
         if (rng < 0).any() or (rng.sum(1) > M).any():
             raise ValueError(f"seg_range reaches outside the {M} obstacle atoms")
-        _check(load().pp_ctx_set_obstacles(self.handle, _ptr(x), C.c_void_p(rng.ctypes.data), M, _stream(dev)), "pp_ctx_set_obstacles")
+        _check(load().pp_ctx_set_obstacles(self.handle, _ptr(x), C.c_void_p(rng.ctypes.data), M, self._stream()), "pp_ctx_set_obstacles")
         self.n_obstacles = M
         if polar is not None:
             pol = (torch.as_tensor(polar).to(device=dev) != 0).to(torch.uint8).reshape(-1).contiguous()
             if pol.numel() != M:
                 raise ValueError(f"polar has {pol.numel()} entries for {M} obstacle atoms")
-            self._obst_polar = pol
+            self._obst_polar = self._own(pol)
+
+    def _own(self, t, src=None):
+        """Register a tensor the context keeps and passes to the kernels by raw pointer (a converted copy of a batch tensor, a
+        cached table).  torch's caching allocator ties its memory to the stream that was current when it was made and knows
+        nothing of the kernels that read it through ``data_ptr()``: every other stream the context runs on is recorded on it
+        (``Tensor.record_stream``), so that dropping the context cannot hand the memory out while such a stream still reads it.
+        ``src``: the caller's tensor -- if the conversion was no copy the memory is the caller's, and so is that duty."""
+        if t is not src:
+            self._owned.append(t)
+            for s in self._streams.values():
+                t.record_stream(s)
+        return t
+
+    def _stream(self):
+        """The current stream as the exports take it.  The first call under a stream records it on the context's own tensors
+        (``_own``): host bookkeeping of the allocator, once per (context, stream), no device call."""
+        s = torch.cuda.current_stream(self.plan.device)
+        if s.cuda_stream not in self._streams:
+            self._streams[s.cuda_stream] = s
+            for t in self._owned:
+                t.record_stream(s)
+        return C.c_void_p(s.cuda_stream)
 
     def _new(self, *shape, dtype=torch.float32):
         return torch.empty(*shape, dtype=dtype, device=self.plan.device)
@@ -448,13 +472,13 @@ class Context:
     def graph(self):
         E = self._new(self.B, self.L, self.K, dtype=torch.int64)
         hE = self._new(self.B, self.L, self.K, 128)
-        _check(load().pp_ctx_get_graph(self.handle, _ptr(E), _ptr(hE), _stream(self.plan.device)), "pp_ctx_get_graph")
+        _check(load().pp_ctx_get_graph(self.handle, _ptr(E), _ptr(hE), self._stream()), "pp_ctx_get_graph")
         return E, hE
 
     def set_graph(self, E_idx):
         """Use the caller's neighbour lists [B, L, K] (per-complex numbering) instead of the built-in search."""
         E = E_idx.to(device=self.plan.device, dtype=torch.int64).reshape(self.B, self.L, self.K).contiguous()
-        _check(load().pp_ctx_set_graph(self.handle, _ptr(E), _stream(self.plan.device)), "pp_ctx_set_graph")
+        _check(load().pp_ctx_set_graph(self.handle, _ptr(E), self._stream()), "pp_ctx_set_graph")
 
     def score(self, chi, t):
         """``t``: a number, or a tensor; one with mixed values ([B*L], packed: [N]) goes to ``score_rows``."""
@@ -464,7 +488,7 @@ class Context:
             t = t.reshape(-1)[0]
         chi = self._chi(chi)
         score, hV = self._new(self.B, self.L, 4), self._new(self.B, self.L, 128)
-        _check(load().pp_score(self.handle, _ptr(chi), float(t), _ptr(score), _ptr(hV), _stream(self.plan.device)),
+        _check(load().pp_score(self.handle, _ptr(chi), float(t), _ptr(score), _ptr(hV), self._stream()),
                "pp_score")
         return score, hV
 
@@ -500,7 +524,7 @@ class Context:
         """``score`` with a time per row ([B*L], packed: [N]): pp_score_rows.  ``t_rows`` is not modified."""
         chi, t_rows = self._chi(chi), self._rows(t_rows, "t")
         score, hV = self._new(self.B, self.L, 4), self._new(self.B, self.L, 128)
-        _check(load().pp_score_rows(self.handle, _ptr(chi), _ptr(t_rows), _ptr(score), _ptr(hV), _stream(self.plan.device)),
+        _check(load().pp_score_rows(self.handle, _ptr(chi), _ptr(t_rows), _ptr(score), _ptr(hV), self._stream()),
                "pp_score_rows")
         return score, hV
 
@@ -512,7 +536,7 @@ class Context:
             raise ValueError(f"score_norm must be a float64 [2, {SO2_GRID}] tensor on {self.plan.device}")
         num, den = self._new(self.n_segments, dtype=torch.float64), self._new(self.n_segments, dtype=torch.float64)
         _check(load().pp_dsm_loss(self.handle, _ptr(pred), _ptr(tgt), _ptr(t_rows), _ptr(score_norm.contiguous()), _ptr(num), _ptr(den),
-                                  _stream(self.plan.device)), "pp_dsm_loss")
+                                  self._stream()), "pp_dsm_loss")
         return num, den
 
     # ---- seeded sampling noise, generated on the device (csrc/pp_rng.h) ----------------------------
@@ -527,7 +551,7 @@ class Context:
             if arr.size != self.n_segments:
                 raise ValueError(f"{arr.size} complex keys for {self.n_segments} complexes")
         _check(load().pp_ctx_set_rng_keys(self.handle, C.c_void_p(arr.ctypes.data) if arr is not None else C.c_void_p(0),
-                                          _stream(self.plan.device)), "pp_ctx_set_rng_keys")
+                                          self._stream()), "pp_ctx_set_rng_keys")
 
     def noise(self, seed, step, want_words=False):
         """What the seeded sampler draws at ``step`` (-1: the initial noising): [2, N, 4] fp32, the 1pi draw then the 2pi draw --
@@ -535,7 +559,7 @@ class Context:
         unsigned 32-bit patterns."""
         nz = self._new(2, self.n_rows, 4)
         words = self._new(self.n_rows, 4, 4, dtype=torch.int32) if want_words else None
-        _check(load().pp_noise_seeded(self.handle, _seed64(seed), int(step), _ptr(nz), _ptr(words), _stream(self.plan.device)),
+        _check(load().pp_noise_seeded(self.handle, _seed64(seed), int(step), _ptr(nz), _ptr(words), self._stream()),
                "pp_noise_seeded")
         return (nz, words) if want_words else nz
 
@@ -543,7 +567,7 @@ class Context:
         """``add_sc_noise`` at one shared time ``t`` with the step = -1 draws of ``seed``: [B, L, 4]."""
         chi = self._chi(chi)
         out = torch.empty_like(chi)
-        _check(load().pp_add_noise_seeded(self.handle, _ptr(chi), float(t), _seed64(seed), _ptr(out), _stream(self.plan.device)),
+        _check(load().pp_add_noise_seeded(self.handle, _ptr(chi), float(t), _seed64(seed), _ptr(out), self._stream()),
                "pp_add_noise_seeded")
         return out
 
@@ -557,7 +581,7 @@ class Context:
             if sde_noise is not None:
                 raise ValueError("seed and sde_noise exclude each other: the seeded sampler draws its own noise")
             _check(load().pp_sample_seeded(self.handle, _ptr(chi), sched.ctypes.data, int(len(sched)), md, _seed64(seed),
-                                           _stream(self.plan.device)), "pp_sample_seeded")
+                                           self._stream()), "pp_sample_seeded")
             return chi
         nz = None
         if mode == "sde":
@@ -565,7 +589,7 @@ class Context:
                 raise RuntimeError("sde sampling needs the per-step noise tensor")
             nz = sde_noise.to(device=self.plan.device, dtype=torch.float32).contiguous()
             assert nz.numel() == (len(sched) - 1) * 2 * self.B * self.L * 4
-        _check(load().pp_sample(self.handle, _ptr(chi), sched.ctypes.data, int(len(sched)), md, _ptr(nz), _stream(self.plan.device)),
+        _check(load().pp_sample(self.handle, _ptr(chi), sched.ctypes.data, int(len(sched)), md, _ptr(nz), self._stream()),
                "pp_sample")
         return chi
 
@@ -584,7 +608,7 @@ class Context:
         sched = _host_f32(schedule)
         traj = self._new(max(len(sched) - 1, 0), self.B, self.L, 4) if trajectory else None
         _check(load().pp_sample_partial(self.handle, _ptr(chi), _ptr(ref), _ptr(fx), FIX_MODES[fix_mode], sched.ctypes.data,
-                                        int(len(sched)), md, _seed64(seed), _ptr(traj), _stream(self.plan.device)), "pp_sample_partial")
+                                        int(len(sched)), md, _seed64(seed), _ptr(traj), self._stream()), "pp_sample_partial")
         return (chi, traj) if trajectory else chi
 
     def sample_guided(self, chi, schedule, mode, seed, eta, cap=0.1, chi_ref=None, fixed=None, fix_mode="renoise",
@@ -615,7 +639,7 @@ class Context:
         trace = self._new(self.n_segments, len(sched), dtype=torch.float64) if want_trace else None
         _check(load().pp_sample_guided(self.handle, _ptr(chi), _ptr(ref), _ptr(fx), FIX_MODES.get(fix_mode, 1), sched.ctypes.data,
                                        int(len(sched)), md, _seed64(seed if seed is not None else 0),
-                                       et.ctypes.data, float(cap), _ptr(traj), _ptr(trace), _stream(self.plan.device)),
+                                       et.ctypes.data, float(cap), _ptr(traj), _ptr(trace), self._stream()),
                "pp_sample_guided")
         out = (chi,) + ((traj,) if trajectory else ()) + ((trace,) if want_trace else ())
         return out if len(out) > 1 else chi
@@ -660,14 +684,14 @@ class Context:
         _check(load().pp_sample_corrected(self.handle, _ptr(chi), _ptr(ref), _ptr(fx), FIX_MODES.get(fix_mode, 1), sched.ctypes.data,
                                           int(len(sched)), md, _seed64(seed), sn.ctypes.data,
                                           et.ctypes.data if et is not None else None, float(cap), _ptr(traj), _ptr(trace), _ptr(corr),
-                                          _stream(self.plan.device)), "pp_sample_corrected")
+                                          self._stream()), "pp_sample_corrected")
         out = (chi,) + ((traj,) if trajectory else ()) + ((trace,) if want_trace else ()) + ((corr,) if want_corr else ())
         return out if len(out) > 1 else chi
 
     def atom14(self, chi):
         chi = self._chi(chi)
         xyz = self._new(self.B, self.L, 14, 3)
-        _check(load().pp_atom14(self.handle, _ptr(chi), _ptr(xyz), _stream(self.plan.device)), "pp_atom14")
+        _check(load().pp_atom14(self.handle, _ptr(chi), _ptr(xyz), self._stream()), "pp_atom14")
         return xyz
 
     def clash(self, chi, vtf=12.0, tol=0.5, need_grad=False):
@@ -676,7 +700,7 @@ class Context:
         chi = self._chi(chi)
         per_res = self._new(self.B, self.L)
         dchi = self._new(self.B, self.L, 4) if need_grad else None
-        _check(load().pp_clash(self.handle, _ptr(chi), _ptr(per_res), _ptr(dchi), _stream(self.plan.device)), "pp_clash")
+        _check(load().pp_clash(self.handle, _ptr(chi), _ptr(per_res), _ptr(dchi), self._stream()), "pp_clash")
         return (per_res, dchi) if need_grad else per_res
 
     def proximal(self, chi, vtf, tol, lamda, num_steps, want_traj=True):
@@ -688,7 +712,7 @@ class Context:
         last = self._new(self.B, self.L, 4)
         losses = self._new(num_steps)
         _check(load().pp_proximal(self.handle, _ptr(chi), float(lamda), int(num_steps), _ptr(traj), _ptr(last),
-                                  _ptr(losses), _stream(self.plan.device)), "pp_proximal")
+                                  _ptr(losses), self._stream()), "pp_proximal")
         return traj, last, losses
 
     def proximal_packed(self, chi, vtf, tol, lamda, num_steps, norm_rows=None, want_traj=False, fixed=None, return_moved=False):
@@ -723,12 +747,12 @@ class Context:
         nrp = C.c_void_p(nr.ctypes.data) if nr is not None else C.c_void_p(0)
         if fixed is None:
             _check(load().pp_proximal_packed(self.handle, _ptr(chi), float(lamda), int(num_steps), nrp, _ptr(traj), _ptr(last),
-                                             _ptr(accepted), _ptr(losses), _stream(self.plan.device)), "pp_proximal_packed")
+                                             _ptr(accepted), _ptr(losses), self._stream()), "pp_proximal_packed")
             return traj, last, accepted, losses
         fx = self._mask(fixed, "fixed")
         moved = self._new(self.B, self.L, dtype=torch.uint8) if return_moved else None
         _check(load().pp_proximal_pinned(self.handle, _ptr(chi), _ptr(fx), float(lamda), int(num_steps), nrp, _ptr(traj), _ptr(last),
-                                         _ptr(accepted), _ptr(losses), _ptr(moved), _stream(self.plan.device)), "pp_proximal_pinned")
+                                         _ptr(accepted), _ptr(losses), _ptr(moved), self._stream()), "pp_proximal_pinned")
         return (traj, last, accepted, losses, moved.bool()) if return_moved else (traj, last, accepted, losses)
 
     def ensemble_reduce(self, chi, n_decoys, per_res=None, select=None, want_best=True):
@@ -758,7 +782,7 @@ class Context:
         best = self._new(n_seg // D, dtype=torch.int32)
         chi_best = self._new(1, n_cons, 4) if want_best else None
         _check(load().pp_ensemble_reduce(self.handle, _ptr(chi), D, _ptr(pr), int(sel), _ptr(mean), _ptr(resultant), _ptr(dev),
-                                         _ptr(clash), _ptr(best), _ptr(chi_best), _stream(self.plan.device)), "pp_ensemble_reduce")
+                                         _ptr(clash), _ptr(best), _ptr(chi_best), self._stream()), "pp_ensemble_reduce")
         return EnsembleResult(mean=mean, resultant=resultant, dev=dev, clash=clash, best=best, chi_best=chi_best)
 
     def ensemble_recombine(self, chi, n_decoys, start=None, max_sweeps=64, want_energy=False, vtf=12.0, tol=0.5):
@@ -792,7 +816,7 @@ class Context:
         sweeps, conv = self._new(n_grp, dtype=torch.int32), self._new(n_grp, dtype=torch.int32)
         energy = self._new(n_cons, D) if want_energy else None
         _check(load().pp_ensemble_recombine(self.handle, _ptr(chi), D, _ptr(st), K, _ptr(pick), _ptr(out), _ptr(trace), _ptr(sweeps),
-                                            _ptr(conv), _ptr(energy), _stream(self.plan.device)), "pp_ensemble_recombine")
+                                            _ptr(conv), _ptr(energy), self._stream()), "pp_ensemble_recombine")
         return EnsembleResult(pick=pick, chi=out, clash_trace=trace, sweeps=sweeps, converged=conv, energy=energy)
 
     def shell(self, seeds, radius=10.0, mode="ca", other_chain=False, xyz=None, want_count=False):
@@ -811,7 +835,7 @@ class Context:
         out = self._new(self.B, self.L, dtype=torch.uint8)
         count = self._new(self.n_segments, dtype=torch.int32) if want_count else None
         _check(load().pp_ctx_shell(self.handle, _ptr(sd), SHELL_MODES[mode], float(radius), SHELL_OTHER_CHAIN if other_chain else 0,
-                                   _ptr(xyz), _ptr(out), _ptr(count), _stream(self.plan.device)), "pp_ctx_shell")
+                                   _ptr(xyz), _ptr(out), _ptr(count), self._stream()), "pp_ctx_shell")
         return (out.bool(), count) if want_count else out.bool()
 
     def sasa(self, chi=None, xyz=None, n_points=96, probe=1.4, radius=None, want_counts=False):
@@ -838,19 +862,19 @@ class Context:
                 if self._t.get("atom_mask") is None:
                     raise RuntimeError("sasa needs a batch with atom_mask (or radius)")
                 table = torch.from_numpy(np.asarray(rc.slot_radius, dtype=np.float32)).to(dev)
-                self._sasa_radius = (table[self._t["residue_type"]] * (self._t["atom_mask"] != 0)).contiguous()
+                self._sasa_radius = self._own((table[self._t["residue_type"]] * (self._t["atom_mask"] != 0)).contiguous())
             radius = self._sasa_radius
         else:
             radius = self._rows(torch.as_tensor(radius), "radius", 14)
         P = int(n_points)
         cache = self.__dict__.setdefault("_sasa_points", {})
         if P not in cache:
-            cache[P] = torch.from_numpy(sphere_points(P)).to(dev) if 1 <= P <= 256 else torch.zeros(1, 3, device=dev)
+            cache[P] = self._own(torch.from_numpy(sphere_points(P)).to(dev) if 1 <= P <= 256 else torch.zeros(1, 3, device=dev))
         counts = self._new(self.B, self.L, 14, 4, dtype=torch.int32)
         area = self._new(self.B, self.L, 4)
         seg_area = self._new(self.n_segments, 4, dtype=torch.float64)
         _check(load().pp_sasa(self.handle, _ptr(xyz), _ptr(radius), _ptr(cache[P]), P, float(probe), _ptr(counts), _ptr(area),
-                              _ptr(seg_area), _stream(dev)), "pp_sasa")
+                              _ptr(seg_area), self._stream()), "pp_sasa")
         per_row = counts.sum(2)
         a0 = area[..., 0]
         return EnsembleResult(area=area, seg_area=seg_area, counts=counts if want_counts else None, bsa=area[..., 1] - area[..., 2],
@@ -917,7 +941,7 @@ class Context:
         report = self._new(self.n_rows, 4)
         count = self._new(self.n_segments, dtype=torch.int32)
         _check(load().pp_disulfide_close(self.handle, _ptr(chi_in), _ptr(fx), _ptr(pr), n_pairs, float(cb_max), float(max_energy),
-                                         float(sigma_chi), _ptr(out), _ptr(partner), _ptr(report), _ptr(count), _stream(dev)),
+                                         float(sigma_chi), _ptr(out), _ptr(partner), _ptr(report), _ptr(count), self._stream()),
                "pp_disulfide_close")
         return DisulfideResult(partner=partner, report=report, count=count, chi=out)
 
@@ -937,7 +961,7 @@ class Context:
             for k in range(2):
                 a = ante[..., k].long()
                 ok = ok & ((a < 0) | torch.gather(am, 1, a.clamp(min=0)))
-            self._polar_tabs = ((cls * ok.to(torch.uint8)).contiguous(), ante.contiguous())
+            self._polar_tabs = (self._own((cls * ok.to(torch.uint8)).contiguous()), self._own(ante.contiguous()))
         return self._polar_tabs
 
     def polar(self, chi=None, xyz=None, hb_max=3.5, sb_max=4.0, want_partners=True, sasa=None, bury_points=0, obst_polar=None,
@@ -991,7 +1015,7 @@ class Context:
         res = self._new(self.B, self.L, 8, dtype=torch.int32)
         seg = self._new(self.n_segments, 8, dtype=torch.int32)
         _check(load().pp_polar(self.handle, _ptr(xyz), _ptr(cls), _ptr(ante), _ptr(op), float(hb_max), float(sb_max), _ptr(partners),
-                               _ptr(n_partners), _ptr(res), _ptr(seg), _stream(dev)), "pp_polar")
+                               _ptr(n_partners), _ptr(res), _ptr(seg), self._stream()), "pp_polar")
         polar = cls.reshape(self.B, self.L, 14) != 0
         unsat = polar & (n_partners.sum(-1) == 0)
         out = EnsembleResult(n_partners=n_partners, partners=partners, res=res, seg=seg, polar=polar, unsat=unsat, buns=None,
@@ -1007,20 +1031,20 @@ class Context:
         node-level kernel; bit 2 (value 4) = a NaN or infinity entered with the caller's tensors (the reference would return NaN, the
         kernels' clamps return finite numbers that mean nothing).  Waits for the stream."""
         v = C.c_int(0)
-        _check(load().pp_ctx_saturated(self.handle, C.byref(v), _stream(self.plan.device)), "pp_ctx_saturated")
+        _check(load().pp_ctx_saturated(self.handle, C.byref(v), self._stream()), "pp_ctx_saturated")
         return int(v.value)
 
     def live_rows(self):
         """The rows a sampling run can move (residue_mask != 0 and a non-zero SC_D_mask entry), ascending: int32 [count] on the
         device.  The layer-1 edge update of ``sample`` runs on these rows only (pp_ctx_live_rows).  Waits for the stream."""
         rows, n = self._new(self.n_rows, dtype=torch.int32), C.c_int(0)
-        _check(load().pp_ctx_live_rows(self.handle, _ptr(rows), C.byref(n), _stream(self.plan.device)), "pp_ctx_live_rows")
+        _check(load().pp_ctx_live_rows(self.handle, _ptr(rows), C.byref(n), self._stream()), "pp_ctx_live_rows")
         return rows[:int(n.value)]
 
     def time_kernel(self, which: int, iters: int = 20) -> float:
         """Average ms per launch of the node-message (0) / edge-update (1) kernel, HIP events on the current stream."""
         ms = C.c_float(0.0)
-        _check(load().pp_time_kernel(self.handle, int(which), int(iters), C.byref(ms), _stream(self.plan.device)),
+        _check(load().pp_time_kernel(self.handle, int(which), int(iters), C.byref(ms), self._stream()),
                "pp_time_kernel")
         return float(ms.value)
 
@@ -1114,7 +1138,7 @@ class AffinityHead:
             raise RuntimeError("pp_affinity_encode: tensors do not match the context's rows")
         hV = torch.empty(hp.shape, dtype=torch.float32, device=dev)
         _check(load().pp_affinity_encode(self.handle, ctx.handle, _ptr(rt), _ptr(sc), _ptr(mm), _ptr(hp), _ptr(hV),
-                                         _stream(dev)), "pp_affinity_encode")
+                                         ctx._stream()), "pp_affinity_encode")
         return hV
 
     def predict(self, h_wt, h_mt, seg_offsets):
