@@ -660,6 +660,69 @@ pp_status pp_polar(pp_ctx *ctx, const float *xyz /* DEVICE [N,14,3] or NULL = th
                    float sb_max, int32_t *partners /* DEVICE [N][14][PP_POLAR_CAP] or NULL */, int32_t *n_partners /* DEVICE [N][14][2] */,
                    int32_t *res /* DEVICE [N][8] */, int32_t *seg /* DEVICE [n_seg][8] */, void *stream);
 
+/* ---- Explicit hydrogens (no reference kernel; csrc/pp_hydrogens.hip holds the arithmetic) -------------------
+ * Places the hydrogens of every row from its heavy atoms.  An all-atom row has PP_AA_SLOTS slots: 0 .. 13 atom14, 14 + k the k-th
+ * hydrogen of the residue type (k < PP_H_MAX).  Per segment of the ctx's segment table; nothing crosses segments.  Chemistry is
+ * caller data (packppi_amd/constants.py derives it from the covalent bonds):
+ *   place  DEVICE int8 [21][13][5]: (kind, parent slot, n1, n2, n3) per residue type and hydrogen.  kind & 15: 0 none, 1 SUM (away
+ *          from the parent's neighbours n1 .. n3; -1 = none, 14 = the C of the previous row), 2 T2 (two neighbours n1 < n2, one of
+ *          the two tetrahedral positions), 3 NERF (n1 = a, the parent's one neighbour, n2 = b, a neighbour of a: bond angle and
+ *          dihedral); kind & 16: dropped on a row with link[n] >= 0
+ *   param  DEVICE float [21][13][5]: (bond length L, c1, s1, c2, s2): T2 cos alpha and +-sin alpha; NERF cos / sin of the angle
+ *          H-parent-a and of the dihedral H-parent-a-b
+ *   link   DEVICE int32 [N] or NULL: what pp_disulfide_close writes as partner
+ * Arithmetic: fp32, fp contract off, every vector a difference to the parent, in the order csrc/pp_hydrogens.hip states.
+ *   link_prev[n]  1 iff row n - 1 is in the same segment with the same chain_indices, atom_mask of its C and of this row's N are
+ *                 not 0 and |C - N|^2 <= 4.0: the rows are joined by a peptide bond
+ *   hmask[n][k]   1 iff the hydrogen exists: atom_mask != 0 for the parent and every atom read, link_prev[n] if it reads the
+ *                 previous C, not dropped for link, all three coordinates finite (atoms exactly in line: dropped)
+ *   hxyz[n][k]    its position, 0 where hmask is 0
+ * A table entry outside its range, or a residue_type outside 0 .. 20, is found on the device: the hydrogen is dropped and bit 3
+ * (value 8) of pp_ctx_saturated is set; it is never used as an index.  Works on a geometry-only plan, never waits for the stream,
+ * one writer per word.
+ * PP_ERR_INVALID: a null ctx, place, param, hxyz, hmask or link_prev; a batch without chain_indices, residue_type or atom_mask; no
+ * coordinates (xyz NULL and no X). */
+#define PP_AA_SLOTS 27
+#define PP_H_MAX 13
+pp_status pp_hydrogens(pp_ctx *ctx, const float *xyz /* DEVICE [N,14,3] or NULL = the batch's X */,
+                       const int8_t *place /* DEVICE [21][13][5] */, const float *param /* DEVICE [21][13][5] */,
+                       const int32_t *link /* DEVICE [N] or NULL */, float *hxyz /* DEVICE [N][13][3] */,
+                       uint8_t *hmask /* DEVICE [N][13] */, uint8_t *link_prev /* DEVICE [N] */, void *stream);
+
+/* ---- All-atom clashscore (no reference kernel; csrc/pp_hydrogens.hip holds the arithmetic) ----------------
+ * Serious overlaps between all atoms, hydrogens included, of every segment of the ctx's segment table.  NOT MolProbity: no Reduce
+ * flips, no optimisation of rotatable hydrogens, and the numbers belong to the radii given.  Caller data:
+ *   hxyz, hmask, link_prev   what pp_hydrogens wrote at the same xyz
+ *   radius  DEVICE float [N][27]: atom (n, a) is counted iff radius > 0 (and, for a >= 14, hmask != 0)
+ *   acls    DEVICE uint8 [N][27]: bit 0 polar hydrogen, bit 1 acceptor, bit 2 hydrogen, bit 3 backbone
+ *   aa_sep  DEVICE uint8 [21][27][27]: bond separation inside a residue of each type, hydrogens included
+ *   link, obst_polar   as for pp_hydrogens / pp_polar, or NULL
+ * Pair (x at p, y at q) of counted atoms of one segment, fp32, fp contract off: d = q - p, d2 = ((dx dx) + (dy dy)) + (dz dz);
+ * t = (rx + ry) - cut; one a polar hydrogen and the other an acceptor: t = t - hb_allow; SERIOUS OVERLAP iff t > 0 and d2 <= t t (a
+ * NaN gives none).  Excluded: bond separation <= 3, or <= 4 when either atom is a hydrogen -- same row: aa_sep[type][x][y]; rows i, i +
+ * 1 with link_prev[i + 1]: sep(x, slot 2) + 1 + sep(y, slot 0); rows with link[i] == j and link[j] == i: sep(x, slot 5) + 1 + sep(y,
+ * slot 5).  An obstacle atom o (r_o > 0) of the segment's range counts against every counted atom: t = (rx + r_o) - cut, minus
+ * hb_allow iff x is a polar hydrogen and obst_polar[o] != 0; no exclusions.
+ * Outputs, int32 on the device, every word with one writer except seg (integer atomics); no read-back:
+ *   n_clash[n][a]   (partner atoms, obstacle atoms): the true counts
+ *   partners[n][a]  the lowest min(count, PP_CLASH_CAP) partner codes (row - first row of the segment) * 27 + slot, ascending, then -1
+ *   res[n][0..3]    pairs inside the row (each once) plus pairs with other rows of the same chain_indices (0); pairs with rows of
+ *                   another chain (1); pairs with obstacle atoms (2); atoms counted (3)
+ *   seg[s][0..7]    atoms counted (0); pairs, each once (1); between chains (2); with a hydrogen (3); with an atom that is not
+ *                   backbone (4); within a row (5); with obstacle atoms (6); both atoms backbone (7)
+ * clashscore = 1000 seg[1] / max(seg[0], 1), for the host to compute.  The row pre-filter changes no output word.  The first call on a
+ * ctx allocates the workspace (sized from N), which may wait for the device; pp_ctx_destroy frees it.  Geometry-only plans work.
+ * PP_ERR_INVALID: a null ctx, hxyz, hmask, radius, acls, aa_sep, link_prev, n_clash, res or seg; cut not finite; hb_allow not finite
+ * or negative; a batch without chain_indices or residue_type; no coordinates; obst_polar on a ctx without obstacles. */
+#define PP_CLASH_CAP 4
+pp_status pp_clashscore(pp_ctx *ctx, const float *xyz /* DEVICE [N,14,3] or NULL = the batch's X */, const float *hxyz /* DEVICE [N][13][3] */,
+                        const uint8_t *hmask /* DEVICE [N][13] */, const float *radius /* DEVICE [N][27] */,
+                        const uint8_t *acls /* DEVICE [N][27] */, const uint8_t *aa_sep /* DEVICE [21][27][27] */,
+                        const uint8_t *link_prev /* DEVICE [N] */, const int32_t *link /* DEVICE [N] or NULL */,
+                        const uint8_t *obst_polar /* DEVICE [M] or NULL */, float cut, float hb_allow,
+                        int32_t *partners /* DEVICE [N][27][PP_CLASH_CAP] or NULL */, int32_t *n_clash /* DEVICE [N][27][2] */,
+                        int32_t *res /* DEVICE [N][4] */, int32_t *seg /* DEVICE [n_seg][8] */, void *stream);
+
 /* Measurement aid, no reference counterpart: average duration (ms) of one launch of a hot kernel
  * (which: 0 = node-message kernel, 1 = edge-update kernel), timed with HIP events on `stream`
  * around `iters` launches.  Synchronises the stream. */
@@ -703,7 +766,8 @@ pp_status pp_range_check_parts(unsigned long long *edge_events, unsigned long lo
  * pp_complex_prepare, an angle at pp_score / pp_sample).  The reference propagates it to its output (layers.py:22-33 has no
  * clamp); these kernels' clamps turn it into finite numbers that mean nothing -- the flag is how a caller learns of it.
  * Inside a sampling run the last node update of an evaluation reports bit 1 only for rows whose angles can move (the live rows
- * below, without the fixed rows of pp_sample_partial): what it computes for the others is returned to nobody. */
+ * below, without the fixed rows of pp_sample_partial): what it computes for the others is returned to nobody.
+ * Bit 3 (value 8): pp_hydrogens / pp_clashscore met a table entry or a residue_type outside its range and dropped the atom. */
 pp_status pp_ctx_saturated(pp_ctx *ctx, int *flags, void *stream);
 
 /* Live rows (no reference counterpart): the rows of the context whose angles a sampling run can move --

@@ -175,9 +175,89 @@ def hbonds_csv_text(protein, xyz, partners, native_partners=None):
     return "\n".join(lines) + "\n"
 
 
+CLASHES_CSV_HEADER = "chain_a,number_a,name_a,atom_a,chain_b,number_b,name_b,atom_b,distance,overlap,status"
+
+
+def clash_pairs(partners):
+    """The serious overlaps behind the ``partners`` array of ONE segment of ``Context.clashscore`` ([n, 27, 4] integers, on the host)
+    as a sorted list of ((row, slot), (row, slot)), lower code first: a pair is listed when either atom lists the other (an atom
+    with more than four partners lists its lowest four)."""
+    p = np.asarray(partners)
+    p = p.reshape(-1, 27, p.shape[-1])
+    out = set()
+    for r, s, k in zip(*np.nonzero(p >= 0)):
+        a, b = int(r) * 27 + int(s), int(p[r, s, k])
+        out.add((min(a, b), max(a, b)))
+    return [(divmod(a, 27), divmod(b, 27)) for a, b in sorted(out)]
+
+
+def clashes_csv_text(protein, xyz, hxyz, partners, radius, hb_allow=0.6, native_partners=None):
+    """The text of ``clashes.csv`` for ONE complex: one line per serious overlap of ``Context.clashscore`` --
+    chain, number, residue name and atom name on both sides (hydrogens by their PDB v3 names), the distance in A and the overlap
+    (rx + ry - d, less ``hb_allow`` between a polar hydrogen and an acceptor; ``radius`` [n, 27] as the call counted them), computed
+    here in float64, and, against ``native_partners`` (the overlaps of the input's own side chains), ``kept``, ``gained`` or
+    ``lost`` (distance and overlap are then those at ``xyz`` too); without ``native_partners`` the status is empty."""
+    from . import constants as rc
+    pos = np.concatenate([np.asarray(xyz, dtype=np.float64).reshape(-1, 14, 3), np.asarray(hxyz, dtype=np.float64).reshape(-1, 13, 3)], 1)
+    radius = np.asarray(radius, dtype=np.float64).reshape(-1, 27)
+    chain, num, aa = list(protein["chain_id"]), list(protein["residue_index"]), list(protein["aaindex"])
+    here = clash_pairs(partners)
+    rows = [(b, "") for b in here]
+    if native_partners is not None:
+        there = set(clash_pairs(native_partners))
+        rows = [(b, "kept" if b in there else "gained") for b in here] + [(b, "lost") for b in sorted(there - set(here))]
+        rows.sort(key=lambda t: t[0])
+    lines = [CLASHES_CSV_HEADER]
+    for ((ra, sa), (rb, sb)), status in rows:
+        d = float(np.linalg.norm(pos[ra, sa] - pos[rb, sb]))
+        ca, cb = int(rc.allatom_class[int(aa[ra]), sa]), int(rc.allatom_class[int(aa[rb]), sb])
+        pair = ((ca & rc.AA_POLAR_H) and (cb & rc.AA_ACCEPTOR)) or ((ca & rc.AA_ACCEPTOR) and (cb & rc.AA_POLAR_H))
+        ov = radius[ra, sa] + radius[rb, sb] - (float(hb_allow) if pair else 0.0) - d
+        side = lambda r, s: f"{chain[r]},{int(num[r])},{rc.resnames[int(aa[r])]},{rc.allatom_names[int(aa[r])][s]}"
+        lines.append(f"{side(ra, sa)},{side(rb, sb)},{d:.3f},{ov:.3f},{status}")
+    return "\n".join(lines) + "\n"
+
+
+def clashscore_summary(res, row=0, native=None):
+    """The summary line of the command lines for segment ``row`` of a ``Context.clashscore`` result (``native``: that of the input's
+    own side chains, reported beside it)."""
+    seg = res.seg[row].cpu().tolist()
+    line = (f"----- clashscore (all atoms, placed hydrogens; not MolProbity): {float(res.clashscore[row]):.2f}, {seg[1]} serious overlaps, "
+            f"{seg[2]} between chains, {seg[7]} backbone only")
+    if native is not None:
+        line += f"; the input's own side chains: {float(native.clashscore[row]):.2f}"
+    return line + " -----"
+
+
+def write_clashes(path, protein, res, row=0, native=None, hb_allow=0.6):
+    """``clashes.csv`` at ``path`` from what ``Context.clashscore`` returned for a B = 1 batch of ``protein``; prints the summary."""
+    n = len(protein["aaindex"])
+    cut = lambda t, *shape: t[row].reshape(-1, *shape)[:n].cpu().numpy()
+    with open(path, "w") as fh:
+        fh.write(clashes_csv_text(protein, cut(res.xyz, 14, 3), cut(res.hxyz, 13, 3), cut(res.partners, 27, 4),
+                                  res.radius.reshape(res.hmask.shape[0], -1, 27)[row][:n].cpu().numpy(), hb_allow,
+                                  cut(native.partners, 27, 4) if native is not None else None))
+    print(clashscore_summary(res, row, native))
+
+
+def write_structure_h(path, protein, h, row=0, head="", obstacle_lines=()):
+    """``structure_H.pdb`` at ``path``: ``pdb_io.to_pdb_hydrogens`` of ``protein`` with the hydrogens ``Context.hydrogens`` (or
+    ``clashscore``) placed for a B = 1 batch of it; ``head``: records that go in front (SSBOND); ``obstacle_lines``: the obstacle
+    records, kept as in structure.pdb."""
+    from .pdb_io import insert_obstacle_lines, to_pdb_hydrogens
+    n = len(protein["aaindex"])
+    text = to_pdb_hydrogens(protein, h.hxyz[row].reshape(-1, 13, 3)[:n].cpu().numpy(), h.hmask[row].reshape(-1, 13)[:n].cpu().numpy())
+    with open(path, "w") as fh:
+        fh.write(head + insert_obstacle_lines(text, list(obstacle_lines)))
+
+
 class ProteinAnalysis:
-    def __init__(self, molprobity_clash_loc, tmp_dir, device="cuda"):
+    def __init__(self, molprobity_clash_loc, tmp_dir, device="cuda", device_clashscore=False):
+        """``device_clashscore``: ``get_metric`` also returns ``clashscore_device``, the all-atom clashscore of the predicted structure
+        with hydrogens placed on the device (``functional.clashscore``; not MolProbity's number).  Off by
+        default: the dict and its ``clashscore`` entry are then exactly what they were."""
         self.molprobity_clash_loc = molprobity_clash_loc
+        self.device_clashscore = bool(device_clashscore)
         self.device = device
         self.tmp_dir = tmp_dir
         os.makedirs(self.tmp_dir, exist_ok=True)
@@ -254,4 +334,7 @@ class ProteinAnalysis:
         metric["total_acc"] = total_acc / 4
         metric["interface_acc"] = interface_acc / 4
         metric["clashscore"] = clashscore
+        if self.device_clashscore:
+            from .functional import clashscore as device_clashscore
+            metric["clashscore_device"] = float(device_clashscore(pred_data.to(d), want_partners=False).clashscore[0])
         return metric

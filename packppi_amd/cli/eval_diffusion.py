@@ -43,6 +43,12 @@ sampling -- behind every reverse step but the last, from time T of the schedule 
 evaluation and a Langevin step of signal-to-noise ratio SNR with a step size per complex.  0.16 is the reference's constant
 (step_correct); nothing here is tuned against a trained checkpoint.  Needs --seed; combines with --repack, --n_decoys, --guide and
 --use_proximal.  Writes corrector.csv (step, t, complex or decoy, s2, n2, eps, amp; empty where no corrector ran).
+--clashscore / --hydrogens (without them every output byte as before): --clashscore writes clashes.csv for the
+written structure -- one line per serious all-atom overlap with placed hydrogens (atoms named as in hbonds.csv, distance, overlap in
+A, kept | gained | lost against the input's own side chains) -- and prints the clashscore (with the input's own beside it);
+--hydrogens writes structure_H.pdb, structure.pdb plus the placed hydrogens.  With --n_decoys ensemble.csv gains the columns clashscore
+and clashes_interface.  --disulfides hands its bridges on: a bonded cysteine has no HG and the bridge is not an overlap.  The score
+is NOT MolProbity's: no flips, no optimisation of rotatable hydrogens, this package's radius table.
 --disulfides auto|SPEC (without --disulfides every output byte as before): behind the sampler the chi1 of every
 bonded cysteine pair are set so that the two sulfurs meet -- auto finds the pairs from the backbone, SPEC names them
 ('A:5-A:55,A:14-A:38').  With --use_proximal the proximal stage then keeps the bonded residues; with --repack a kept residue keeps its
@@ -243,7 +249,8 @@ def write_ensemble(model, batch, protein, args, analysis):
     kw = dict(recombine=True, recombine_sweeps=args.recombine_sweeps) if args.recombine else {}
     out = model.sample_ensemble(batch, args.n_decoys, seed=args.seed, use_proximal=args.use_proximal, select=args.select,
                                 return_all=True, **kw, **(dict(sasa=True) if args.sasa else {}),
-                                **(dict(polar=True) if getattr(args, "polar", False) else {}), **args.guide_kw)
+                                **(dict(polar=True) if getattr(args, "polar", False) else {}),
+                                **(dict(clashscore=True) if getattr(args, "clashscore", False) else {}), **args.guide_kw)
     chi, packed = out["decoys"]
     best = int(out["best"][0])
     dev, clash = out["dev"].cpu().tolist(), out["clash"].cpu().tolist()
@@ -265,10 +272,13 @@ def write_ensemble(model, batch, protein, args, analysis):
         bsa = out["bsa"].cpu().tolist() if args.sasa else None
         pcols = [k for k in POLAR_ENSEMBLE_COLUMNS if k in out] if getattr(args, "polar", False) else []
         pvals = [out[k].cpu().tolist() for k in pcols]
-        fh.write("decoy,key,dev,clash,selected" + (",bsa" if args.sasa else "") + "".join("," + k for k in pcols) + "\n")
+        aa = getattr(args, "clashscore", False)
+        score, face = (out["clashscore"].cpu().tolist(), out["clashes_interface"].cpu().tolist()) if aa else (None, None)
+        fh.write("decoy,key,dev,clash,selected" + (",bsa" if args.sasa else "") + "".join("," + k for k in pcols)
+                 + (",clashscore,clashes_interface" if aa else "") + "\n")
         for d, key in enumerate(out["keys"]):
             fh.write(f"{d},{key},{dev[d]!r},{clash[d]!r},{int(d == best)}" + (f",{bsa[d]!r}" if args.sasa else "")
-                     + "".join(f",{int(v[d])}" for v in pvals) + "\n")
+                     + "".join(f",{int(v[d])}" for v in pvals) + (f",{score[d]!r},{int(face[d])}" if aa else "") + "\n")
     conf = out["confidence"][0].cpu().tolist()
     conf += [[0.0] * 4] * (len(protein["aaindex"]) - len(conf))
     with open(os.path.join(args.outdir, "confidence.csv"), "w") as fh:
@@ -381,6 +391,40 @@ def write_polar(batch, protein, outdir, chi, sasa=False, native=False, names=("p
     print(line + " -----")
 
 
+def add_allatom_arguments(p):
+    """--clashscore and --hydrogens.  Their defaults are SUPPRESSed: without the flags the namespace is what it was before them."""
+    p.add_argument("--clashscore", action="store_true", default=argparse.SUPPRESS, help="Write clashes.csv for the written structure "
+                   "(DESIGN.md section 29): every serious all-atom overlap with hydrogens placed on the device, and print the "
+                   "clashscore (overlaps per 1000 atoms; NOT MolProbity's number: no flips, no optimisation of rotatable hydrogens, "
+                   "this package's radii); with --n_decoys ensemble.csv gains the columns clashscore and clashes_interface.")
+    p.add_argument("--hydrogens", action="store_true", default=argparse.SUPPRESS, help="Write structure_H.pdb: the records of the "
+                   "written structure plus the hydrogens placed on the device behind each residue's heavy atoms (DESIGN.md section 29; "
+                   "hydroxyl, thiol and lysine NH3+ hydrogens at a conventional position, not an optimised one).")
+
+
+def write_allatom(batch, protein, outdir, chi, clashscore=False, hydrogens=False, native=False, link=None, head="", obstacle_lines=(),
+                  names=("clashes.csv", "structure_H.pdb")):
+    """--clashscore / --hydrogens: clashes.csv and structure_H.pdb of the B = 1 ``batch`` at the angles ``chi`` [1, n, 4] (n < L: as in
+    ``write_sasa``), and the summary line.  ``native``: the input has side chains of its own -- clashes.csv marks every overlap kept,
+    gained or lost against them and the summary gives the input's own score.  ``link``: the partner array of the run's disulfide
+    closure.  ``head`` / ``obstacle_lines``: what the written structure carries around its ATOM records."""
+    from ..analysis import write_clashes, write_structure_h
+    from ..functional import _ctx_for
+    chi = chi.to(batch.SC_D.device)
+    if chi.shape[1] != batch.SC_D.shape[1]:
+        chi = torch.cat([chi, batch.SC_D[:, chi.shape[1]:]], 1)
+    ctx = _ctx_for(batch)
+    if clashscore:
+        h = ctx.clashscore(chi=chi, link=link)
+        write_clashes(os.path.join(outdir, names[0]), protein, h, 0, ctx.clashscore(link=link) if native else None)
+    else:
+        h = ctx.hydrogens(chi=chi, link=link)
+    if hydrogens:
+        n = len(protein["aaindex"])
+        placed = dict(protein, atom_positions=h.xyz[0].reshape(-1, 14, 3)[:n].cpu().numpy())
+        write_structure_h(os.path.join(outdir, names[1]), placed, h, 0, head, obstacle_lines)
+
+
 def evaluate_model(model, args):
     print("----- Starting evaluation! -----")
     analysis = ProteinAnalysis(args.molprobity_clash_loc, args.outdir, args.device)
@@ -448,6 +492,10 @@ def evaluate_model(model, args):
         write_sasa(batch, protein, args.outdir, SC_D_sample)
     if getattr(args, "polar", False):
         write_polar(batch, protein, args.outdir, SC_D_sample, sasa=args.sasa, native=contains_sidechains(args.input))
+    if getattr(args, "clashscore", False) or getattr(args, "hydrogens", False):
+        link = model.disulfide_reports[-1]["partner"] if disulfides is not None else None
+        write_allatom(batch, protein, args.outdir, SC_D_sample, getattr(args, "clashscore", False), getattr(args, "hydrogens", False),
+                      native=contains_sidechains(args.input), link=link, head=ssbond, obstacle_lines=args.obstacle_lines)
     if contains_sidechains(args.input):
         metric = analysis.get_metric(true_pdb=args.input, pred_pdb=analysis.tmp_pdb)
         print(f"----- Metric: ----- {metric}")
@@ -499,6 +547,7 @@ def build_parser():
     add_guide_arguments(p)
     add_corrector_arguments(p)
     add_disulfide_arguments(p)
+    add_allatom_arguments(p)
     return p
 
 

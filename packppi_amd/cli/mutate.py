@@ -21,6 +21,9 @@ clash against them at the wild type's angles (new side chains at chi = 0) and at
 that structure (per residue the solvent-accessible area at four nested levels, the buried interface area and the exposure; the file
 ``eval_diffusion --sasa`` writes as sasa.csv), and ``mutants.csv`` gains the column ``bsa``, the interface area the selected decoy
 buries.
+--clashscore / --hydrogens (without them every output byte as before): next to every ``mutant_<tag>.pdb`` a
+``clashes_<tag>.csv`` (every serious all-atom overlap with placed hydrogens; mutants.csv gains the columns clashscore and
+clashes_interface of the selected decoy) and a ``mutant_<tag>_H.pdb`` (the mutant plus the placed hydrogens).  Not MolProbity's score.
 --polar (without it every output byte as before): next to every ``mutant_<tag>.pdb`` a ``polar_<tag>.csv`` and a
 ``hbonds_<tag>.csv`` of that structure (the files ``eval_diffusion --polar`` writes as polar.csv and hbonds.csv, without the
 comparison against the input: the mutant has other side chains), and ``mutants.csv`` gains the columns ``hbonds``,
@@ -77,10 +80,11 @@ def evaluate_model(model, args):
     model.keep_corrector_trace = corrector is not None
     polar = getattr(args, "polar", False)
     pcols = ("hbonds", "hbonds_interface", "salt_interface") + (("buns_interface",) if args.sasa else ()) if polar else ()
+    allatom, with_h = getattr(args, "clashscore", False), getattr(args, "hydrogens", False)
     results = model.mutate([(protein, s) for s in sets], seed=args.seed, radius=args.radius, shell=args.shell,
                            n_decoys=args.n_decoys, use_proximal=args.use_proximal, select=args.select, fixed_mode=args.fixed_mode,
                            **(dict(recombine=True, recombine_sweeps=args.recombine_sweeps) if args.recombine else {}),
-                           **(dict(sasa=True) if args.sasa else {}), **(dict(polar=True) if polar else {}),
+                           **(dict(sasa=True) if args.sasa else {}), **(dict(polar=True) if polar else {}), **(dict(clashscore=True) if allatom else {}),
                            **(dict(guide=guide) if guide is not None else {}),
                            **(dict(corrector=corrector) if corrector is not None else {}))
     if guide is not None:
@@ -89,7 +93,8 @@ def evaluate_model(model, args):
         write_corrector_csv(model, args.outdir)
     ddg = predict_ddg(protein, sets, args) if args.ap_ckpt else None
     rows = ["tag,shell_rows,selected_decoy,clash,dev" + (",clash_recombined,rows_recombined" if args.recombine else "")
-            + (",ddg,ddg_inv" if ddg else "") + (",bsa" if args.sasa else "") + "".join("," + k for k in pcols)]
+            + (",ddg,ddg_inv" if ddg else "") + (",bsa" if args.sasa else "") + "".join("," + k for k in pcols)
+            + (",clashscore,clashes_interface" if allatom else "")]
     for i, (s, r) in enumerate(zip(sets, results)):
         tag = (r["tag"] or s).replace(",", "_")
         b = r["batch"]
@@ -118,6 +123,12 @@ def evaluate_model(model, args):
             line += "".join(f",{int(r[k][best])}" for k in pcols)
             write_polar(b, mutant, args.outdir, r["SC_D"], sasa=args.sasa,
                         names=(f"polar_{tag}.csv", f"hbonds_{tag}.csv"))
+        if allatom or with_h:
+            from .eval_diffusion import write_allatom
+            if allatom:
+                line += f",{float(r['clashscore'][best])!r},{int(r['clashes_interface'][best])}"
+            write_allatom(b, mutant, args.outdir, r["SC_D"], allatom, with_h, obstacle_lines=obstacles["lines"] if obstacles else [],
+                          names=(f"clashes_{tag}.csv", f"mutant_{tag}_H.pdb"))
         rows.append(line)
         print(f"----- {tag}: {int(r['shell'].sum())} residues repacked, decoy {best} of {args.n_decoys} selected"
               + (f", {int(r['rows_recombined'])} residues recombined from other decoys" if args.recombine else "") + " -----")
@@ -177,6 +188,8 @@ def build_parser():
                    "mutants.csv gains the columns hbonds, hbonds_interface, salt_interface and, with --sasa, buns_interface.")
     add_guide_arguments(p)
     add_corrector_arguments(p)
+    from .eval_diffusion import add_allatom_arguments
+    add_allatom_arguments(p)
     return p
 
 

@@ -9,6 +9,9 @@ residue's clash against them before and after.
 --sasa (without it every output byte as before) writes sasa.csv for the optimised structure, as eval_diffusion
 does; --repack also takes interface:sasa (the delta-SASA interface of the input, made on the device) and pocket (residues whose
 surface the obstacle atoms bury; needs --obstacles other than none).
+--clashscore / --hydrogens (without them every output byte as before): clashes.csv (every serious all-atom
+overlap of the optimised structure with placed hydrogens, kept | gained | lost against the input, and the clashscore of both) and
+structure_H.pdb, as eval_diffusion writes them.  Not MolProbity's score.
 """
 import argparse
 from pathlib import Path
@@ -37,6 +40,8 @@ def build_parser():
     p.add_argument("--sasa", action="store_true", help="Write sasa.csv for the optimised structure (DESIGN.md section 20): per "
                    "residue the solvent-accessible area at four nested levels, the buried interface area and the exposure. --repack "
                    "also takes interface:sasa and pocket (needs --obstacles).")
+    from .eval_diffusion import add_allatom_arguments
+    add_allatom_arguments(p)
     return p
 
 
@@ -100,6 +105,10 @@ def main(argv=None):
     if args.sasa:
         from .eval_diffusion import write_sasa
         write_sasa(batch, protein, args.outdir, SC_D)
+    if getattr(args, "clashscore", False) or getattr(args, "hydrogens", False):
+        from .eval_diffusion import write_allatom
+        write_allatom(batch, protein, args.outdir, SC_D, getattr(args, "clashscore", False), getattr(args, "hydrogens", False),
+                      native=True, obstacle_lines=obstacles["lines"] if obstacles else [])
     print(f"----- The optimized structure clashscore is {analysis.get_clashscore(analysis.tmp_pdb)} -----")
     print("----- Finishing optimize! -----")
 

@@ -86,6 +86,140 @@ def _polar_tables():
 polar_class, polar_antecedent = _polar_tables()   # [21,14] u8 class bits, [21,14,2] i8 antecedent slots (-1 = none)
 
 
+# Explicit hydrogens and the all-atom clashscore (pp_hydrogens / pp_clashscore).  The table is DERIVED from the
+# covalent bonds of bond_rows (entries below 1.9 A, as for polar_antecedent) and the atom names; only the hybridisation of the carbons
+# and the protonation of the side-chain nitrogens are written out.  Slots of an all-atom row: 0 .. 13 atom14, 14 + k the k-th hydrogen.
+PP_AA_SLOTS, PP_H_MAX = 27, 13
+H_NONE, H_SUM, H_T2, H_NERF = 0, 1, 2, 3      # how pp_hydrogens places a hydrogen (kind & 15); H_DROP_LINKED: not on a row in `link`
+H_DROP_LINKED = 16
+H_PREV_C = 14                                 # neighbour code: the C of the previous row (the backbone N's second neighbour)
+H_POLAR, H_ROTATABLE, H_AROMATIC = 1, 2, 4    # hydrogen_flags bits
+AA_POLAR_H, AA_ACCEPTOR, AA_HYDROGEN, AA_BACKBONE = 1, 2, 4, 8   # allatom_class bits
+hydrogen_bond_length = {"C": 1.09, "N": 1.01, "O": 0.96, "S": 1.34}      # nuclear positions, A
+sp2_carbons = {"ARG": ("CZ",), "ASN": ("CG",), "ASP": ("CG",), "GLN": ("CD",), "GLU": ("CD",), "HIS": ("CG", "CD2", "CE1"),
+               "PHE": ("CG", "CD1", "CD2", "CE1", "CE2", "CZ"), "TYR": ("CG", "CD1", "CD2", "CE1", "CE2", "CZ"),
+               "TRP": ("CG", "CD1", "CD2", "CE2", "CE3", "CZ2", "CZ3", "CH2")}
+# side-chain nitrogens: (class, hydrogens); HIS is neutral with the hydrogen on NE2, ND1 is bare
+nitrogen_hydrogens = {"ARG": {"NE": ("P1", 1), "NH1": ("P2", 2), "NH2": ("P2", 2)}, "ASN": {"ND2": ("P2", 2)}, "GLN": {"NE2": ("P2", 2)},
+                      "HIS": {"NE2": ("P1", 1)}, "TRP": {"NE1": ("P1", 1)}, "LYS": {"NZ": ("T3", 3)}}
+# the explicit-hydrogen radii as we recall Probe's set; its source is not at hand, so absolute scores belong to THIS table
+allatom_radius = {"C": 1.75, "C_carbonyl": 1.65, "N": 1.55, "O": 1.40, "S": 1.80, "H": 1.17, "H_aromatic": 1.00, "H_polar": 1.00}
+carbonyl_carbons = {"ASP": ("CG",), "GLU": ("CD",), "ASN": ("CG",), "GLN": ("CD",)}      # next to the backbone C of every residue
+T2_ALPHA_DEG, TETRAHEDRAL_DEG = 54.75, 109.5
+
+
+def _bonded(t):
+    """The heavy-atom neighbours of every atom14 slot of residue type t, ascending: bond_rows entries below 1.9 A."""
+    nb = [set() for _ in range(14)]
+    for rt, a, b, length, _ in bond_rows:
+        if int(rt) == t and length < 1.9:
+            nb[int(a)].add(int(b))
+            nb[int(b)].add(int(a))
+    return [sorted(s) for s in nb]
+
+
+def _hydrogen_tables():
+    f32 = np.float32
+    cs = lambda deg: (f32(np.cos(np.deg2rad(deg))), f32(np.sin(np.deg2rad(deg))))     # rounded to float once, here
+    names = [[] for _ in range(21)]
+    parent = -np.ones((21, PP_H_MAX), np.int8)
+    place = np.zeros((21, PP_H_MAX, 5), np.int8)
+    place[:, :, 1:] = -1
+    par = np.zeros((21, PP_H_MAX, 5), np.float32)
+    flags = np.zeros((21, PP_H_MAX), np.uint8)
+    for t in range(20):
+        rn, an, nb = resnames[t], atom14_names[t], _bonded(t)
+        k = 0
+        for p, nm in enumerate(an):
+            if not nm or nm in ("C", "O"):
+                continue
+            el, stem, heavy = nm[0], "H" + nm[1:], nb[p]
+            aromatic = False
+            if nm == "N":
+                cls, n_h = ("P1bb", 1) if rn != "PRO" else (None, 0)
+            elif el == "C":
+                aromatic = nm in sp2_carbons.get(rn, ())
+                if aromatic:
+                    cls, n_h = ("P1", 1) if len(heavy) == 2 else (None, 0)
+                else:
+                    cls, n_h = {3: ("T1", 1), 2: ("T2", 2), 1: ("T3", 3)}[len(heavy)]
+            elif el == "N":
+                cls, n_h = nitrogen_hydrogens.get(rn, {}).get(nm, (None, 0))
+            else:
+                cls, n_h = ("R1", 1) if (rn, nm) in (("SER", "OG"), ("THR", "OG1"), ("TYR", "OH"), ("CYS", "SG")) else (None, 0)
+            if not n_h:
+                continue
+            L = hydrogen_bond_length[el]
+            suffix = {1: ("",), 2: ("1", "2") if cls == "P2" else ("2", "3"), 3: ("1", "2", "3")}[n_h]
+            for q in range(n_h):
+                names[t].append(stem + suffix[q])
+                parent[t, k] = p
+                flags[t, k] = ((H_POLAR if el in "NOS" else 0) | (H_ROTATABLE if cls == "R1" or (rn, nm) == ("LYS", "NZ") else 0)
+                               | (H_AROMATIC if aromatic else 0))
+                if cls in ("T1", "P1", "P1bb"):
+                    n = heavy + ([H_PREV_C] if cls == "P1bb" else [])
+                    place[t, k] = [H_SUM, p] + n + [-1] * (3 - len(n))
+                    par[t, k, 0] = L
+                elif cls == "T2":
+                    c, s = cs(T2_ALPHA_DEG)
+                    place[t, k] = [H_T2, p, heavy[0], heavy[1], -1]
+                    par[t, k, :3] = [L, c, s if q == 0 else -s]
+                else:
+                    a = heavy[0]
+                    b = [x for x in nb[a] if x != p][0]
+                    theta = 120.0 if cls == "P2" else TETRAHEDRAL_DEG
+                    phi = {"T3": (60.0, 180.0, 300.0), "P2": (0.0, 180.0), "R1": (180.0,)}[cls][q]
+                    place[t, k] = [H_NERF | (H_DROP_LINKED if (rn, nm) == ("CYS", "SG") else 0), p, a, b, -1]
+                    par[t, k] = [L, *cs(theta), *cs(phi)]
+                k += 1
+    return names, parent, place, par, flags
+
+
+hydrogen_names, hydrogen_parent, hydrogen_place, hydrogen_param, hydrogen_flags = _hydrogen_tables()
+# [21] name lists; [21,13] i8 parent slot (-1 = none); [21,13,5] i8 (kind, parent, three neighbour slots or -1; H_NERF: a, b, -1);
+# [21,13,5] f32 (L, then cos/sin of alpha with the sign of the side (H_T2) or cos/sin theta, cos/sin phi (H_NERF)); [21,13] u8 flags
+hydrogen_count = np.array([len(n) for n in hydrogen_names], np.int32)
+allatom_names = [list(atom14_names[t]) + hydrogen_names[t] + [""] * (PP_H_MAX - len(hydrogen_names[t])) for t in range(21)]
+
+
+def _allatom_tables():
+    sep = np.full((21, PP_AA_SLOTS, PP_AA_SLOTS), 9, np.uint8)
+    radius = np.zeros((21, PP_AA_SLOTS), np.float32)
+    cls = np.zeros((21, PP_AA_SLOTS), np.uint8)
+    for t in range(21):
+        nb = [list(x) for x in _bonded(t)] + [[] for _ in range(PP_H_MAX)]
+        for k in range(int(hydrogen_count[t])):
+            p = int(hydrogen_parent[t, k])
+            nb[14 + k].append(p)
+            nb[p].append(14 + k)
+        for s in range(PP_AA_SLOTS):                       # breadth first over the bond graph, hydrogens included
+            sep[t, s, s] = 0
+            seen, front, d = {s}, [s], 0
+            while front and d < 9:
+                d += 1
+                front = [y for x in front for y in nb[x] if y not in seen and not seen.add(y)]
+                for y in front:
+                    sep[t, s, y] = min(d, 9)
+        rn = resnames[t]
+        for s, nm in enumerate(allatom_names[t]):
+            if not nm:
+                continue
+            if s < 14:
+                carbonyl = nm == "C" or nm in carbonyl_carbons.get(rn, ())
+                radius[t, s] = allatom_radius["C_carbonyl" if carbonyl else nm[0]]
+                cls[t, s] = (AA_ACCEPTOR if polar_class[t, s] & POLAR_ACCEPTOR else 0) | (AA_BACKBONE if s < 4 else 0)
+            else:
+                f, p = int(hydrogen_flags[t, s - 14]), int(hydrogen_parent[t, s - 14])
+                radius[t, s] = allatom_radius["H_polar" if f & H_POLAR else "H_aromatic" if f & H_AROMATIC else "H"]
+                cls[t, s] = AA_HYDROGEN | (AA_POLAR_H if f & H_POLAR else 0) | (AA_BACKBONE if p < 2 else 0)
+    return sep, radius, cls
+
+
+aa_sep, allatom_default_radius, allatom_class = _allatom_tables()
+# [21,27,27] u8 bond-graph separation inside a residue, hydrogens included, clamped at 9 (also: not connected, empty slot);
+# [21,27] f32 default radius (0 = empty slot); [21,27] u8 class bits AA_*
+
+
 @lru_cache(maxsize=16)
 def make_atom14_dists_bounds(overlap_tolerance: float = 1.5,
                              bond_length_tolerance_factor: float = 15.0):

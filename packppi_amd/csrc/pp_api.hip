@@ -342,6 +342,7 @@ extern "C" void pp_ctx_destroy(pp_ctx *c) {
     if (c->obst) (void)hipFree(c->obst);              // waits for the device: only a context that ever held obstacles pays it
     if (c->ds_ws) (void)hipFree(c->ds_ws);            // likewise: only a context that ever ran pp_disulfide_close
     if (c->po_ws) (void)hipFree(c->po_ws);            // likewise: only a context that ever ran pp_polar
+    if (c->aa_ws) (void)hipFree(c->aa_ws);            // likewise: only a context that ever ran pp_clashscore
     delete c;
 }
 

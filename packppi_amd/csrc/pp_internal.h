@@ -199,6 +199,8 @@ struct pp_ctx {
     size_t ds_bytes = 0;      // outside the arena, made by the first call, freed with the ctx (no other call pays for it)
     void *po_ws = nullptr;    // pp_polar: its workspace ([N][14] position + class, [N][14] direction, [N] row sphere), sized from N; ONE
     size_t po_bytes = 0;      // allocation outside the arena, made by the first call, freed with the ctx
+    void *aa_ws = nullptr;    // pp_clashscore: its workspace ([N][27] position + radius, [N] row sphere, [N][27] class + separations), sized
+    size_t aa_bytes = 0;      // from N; ONE allocation outside the arena, made by the first call, freed with the ctx
     // seeded sampling noise (pp_rng.h): the per-row table of the seeded kernels and the complexes' keys
     pp_rng_row *rng_tab;      // [N] (row within the complex, key of the complex); filled by pp_launch_rng_table
     uint64_t *rng_keys;       // [B] the caller's keys (pp_ctx_set_rng_keys), staged for the table kernel

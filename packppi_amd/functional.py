@@ -104,6 +104,21 @@ def polar_contacts(batch, chi=None, hb_max=3.5, sb_max=4.0, want_partners=True, 
                      obst_polar=obst_polar)
 
 
+def add_hydrogens(batch, SC_D=None, link=None):
+    """The hydrogens of every row, placed on the device (``lib.Context.hydrogens``, pp_hydrogens), on the geometry
+    plan: at the angles ``SC_D`` (through atom14), else at the batch's X.  ``link``: the ``partner`` array of ``Context.disulfides``
+    (a bonded cysteine has no HG).  Returns ``hxyz`` [B, L, 13, 3], ``hmask`` [B, L, 13], ``link_prev`` [B, L] and ``xyz``."""
+    return _ctx_for(batch).hydrogens(chi=SC_D, link=link)
+
+
+def clashscore(batch, SC_D=None, link=None, rotatable="skip", cut=0.4, hb_allow=0.6, radius=None, want_partners=True):
+    """All-atom clashscore of every complex with placed hydrogens (``lib.Context.clashscore``, pp_clashscore), on
+    the geometry plan: at the angles ``SC_D`` (through atom14), else at the batch's X.  Padded, packed and decoy batches alike.  Not
+    MolProbity's number: no flips, no optimisation of rotatable hydrogens, this package's radius table."""
+    return _ctx_for(batch).clashscore(chi=SC_D, link=link, rotatable=rotatable, cut=cut, hb_allow=hb_allow, radius=radius,
+                                      want_partners=want_partners)
+
+
 def polar_bond_keys(partners, seg_offsets=None):
     """The hydrogen bonds behind a ``partners`` array of ``Context.polar`` ([B, L, 14, 4], packed [1, N, 14, 4]) as sorted unique int64
     keys ``(segment * M + low code) * M + high code`` with ``M = 14 * rows`` of the array's second axis, on the device.  A bond is in

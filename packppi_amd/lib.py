@@ -23,7 +23,7 @@ SYMBOLS = ("pp_version", "pp_last_error", "pp_build_id", "pp_plan_set_knn_ties",
            "pp_ctx_set_rng_keys", "pp_noise_seeded", "pp_add_noise_seeded", "pp_sample_seeded",
            "pp_sample_partial", "pp_proximal_pinned", "pp_ctx_live_rows", "pp_ensemble_reduce", "pp_ctx_shell",
            "pp_ensemble_recombine", "pp_ctx_set_obstacles", "pp_sasa", "pp_sample_guided", "pp_sample_corrected",
-           "pp_disulfide_close", "pp_polar")
+           "pp_disulfide_close", "pp_polar", "pp_hydrogens", "pp_clashscore")
 
 
 FIX_MODES = {"hold": 0, "renoise": 1}         # PP_FIX_HOLD, PP_FIX_RENOISE
@@ -163,6 +163,8 @@ def load():
     lib.pp_sasa.argtypes = [vp, vp, vp, vp, i, f, vp, vp, vp, vp]
     lib.pp_disulfide_close.argtypes = [vp, vp, vp, vp, i, f, f, f, vp, vp, vp, vp, vp]
     lib.pp_polar.argtypes = [vp, vp, vp, vp, vp, f, f, vp, vp, vp, vp, vp]
+    lib.pp_hydrogens.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.pp_clashscore.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, f, f, vp, vp, vp, vp, vp]
     lib.pp_sample_guided.argtypes = [vp, vp, vp, vp, i, vp, i, i, C.c_uint64, vp, f, vp, vp, vp]
     lib.pp_sample_corrected.argtypes = [vp, vp, vp, vp, i, vp, i, i, C.c_uint64, vp, vp, f, vp, vp, vp, vp]
     _lib = lib
@@ -1025,6 +1027,125 @@ class Context:
             out["buns"] = unsat & (counts[..., 3] <= int(bury_points))
             out["buns_interface"] = out["buns"] & (counts[..., 1] > int(bury_points))
         return out
+
+    def _link(self, link):
+        """A ``link`` argument (the ``partner`` of ``disulfides``, a ``DisulfideResult``, or None) as int32 [N] on the device."""
+        if link is None:
+            return None
+        if isinstance(link, dict):
+            link = link["partner"]
+        link = torch.as_tensor(link).to(device=self.plan.device, dtype=torch.int32).reshape(-1).contiguous()
+        if link.numel() != self.n_rows:
+            raise ValueError(f"link has {link.numel()} entries, this context has {self.n_rows} rows")
+        return link
+
+    def allatom_tables(self):
+        """The tables of ``hydrogens`` / ``clashscore`` on the device, made once per context from ``constants``: ``place`` int8
+        [21, 13, 5], ``param`` fp32 [21, 13, 5], ``aa_sep`` uint8 [21, 27, 27], and gathered by residue_type ``radius`` fp32 [N, 27]
+        (the default radii, 0 for the heavy atoms whose atom_mask is 0), ``acls`` uint8 [N, 27] and ``rotatable`` bool [N, 27]."""
+        if getattr(self, "_aa_tabs", None) is None:
+            dev = self.plan.device
+            if self._t.get("atom_mask") is None:
+                raise RuntimeError("hydrogens / clashscore need a batch with atom_mask")
+            rt = self._t["residue_type"].reshape(-1)
+            up = lambda a, dt: self._own(torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev))
+            present = torch.cat([self._t["atom_mask"].reshape(-1, 14) != 0,
+                                 torch.ones(self.n_rows, rc.PP_H_MAX, dtype=torch.bool, device=dev)], 1)
+            radius = torch.from_numpy(rc.allatom_default_radius).to(dev)[rt] * present
+            rot = np.zeros((21, rc.PP_AA_SLOTS), bool)
+            rot[:, 14:] = (rc.hydrogen_flags & rc.H_ROTATABLE) != 0
+            self._aa_tabs = EnsembleResult(
+                place=up(rc.hydrogen_place, np.int8), param=up(rc.hydrogen_param, np.float32), aa_sep=up(rc.aa_sep, np.uint8),
+                radius=self._own(radius.contiguous()), acls=self._own(torch.from_numpy(rc.allatom_class).to(dev)[rt].contiguous()),
+                rotatable=self._own(torch.from_numpy(rot).to(dev)[rt].contiguous()))
+        return self._aa_tabs
+
+    def hydrogens(self, chi=None, xyz=None, link=None, place=None, param=None):
+        """Place the hydrogens of every row on the device (pp_hydrogens).  Coordinates as in ``sasa``:
+        ``atom14(chi)`` if ``chi`` is given, else ``xyz`` [B, L, 14, 3], else the batch's X.  ``link`` int32 [N]: the ``partner`` of
+        ``disulfides`` (or its result) -- a bonded cysteine has no HG.  ``place`` / ``param``: tables other than ``constants``'.
+        Returns an ``EnsembleResult``: ``hxyz`` fp32 [B, L, 13, 3] (0 where there is none), ``hmask`` uint8 [B, L, 13], ``link_prev``
+        uint8 [B, L] (the row is peptide-bonded to the row before it) and ``xyz`` (the heavy atoms used).  The k-th hydrogen of a row
+        is ``constants.hydrogen_names[type][k]``.  Rotatable hydrogens (OH, SH, NH3+) sit at a conventional position, not an
+        optimised one.  No host synchronisation."""
+        dev = self.plan.device
+        for k in ("chain_indices", "atom_mask"):
+            if self._t.get(k) is None:
+                raise RuntimeError(f"hydrogens needs a batch with {k}")
+        if (place is None) != (param is None):
+            raise ValueError("hydrogens: place and param go together")
+        if place is None:
+            tabs = self.allatom_tables()
+            place, param = tabs.place, tabs.param
+        else:
+            place = torch.as_tensor(place).to(device=dev, dtype=torch.int8).contiguous()
+            param = torch.as_tensor(param).to(device=dev, dtype=torch.float32).contiguous()
+            if place.numel() != 21 * 13 * 5 or param.numel() != 21 * 13 * 5:
+                raise ValueError("hydrogens: place and param are [21, 13, 5] tables")
+        link = self._link(link)
+        if chi is not None:
+            xyz = self.atom14(chi)
+        elif xyz is not None:
+            xyz = self._xyz(xyz)
+        hxyz = self._new(self.B, self.L, rc.PP_H_MAX, 3)
+        hmask = self._new(self.B, self.L, rc.PP_H_MAX, dtype=torch.uint8)
+        link_prev = self._new(self.B, self.L, dtype=torch.uint8)
+        _check(load().pp_hydrogens(self.handle, _ptr(xyz), _ptr(place), _ptr(param), _ptr(link), _ptr(hxyz), _ptr(hmask),
+                                   _ptr(link_prev), self._stream()), "pp_hydrogens")
+        return EnsembleResult(hxyz=hxyz, hmask=hmask, link_prev=link_prev, xyz=xyz if xyz is not None else self._t.get("X"))
+
+    def clashscore(self, chi=None, xyz=None, link=None, rotatable="skip", cut=0.4, hb_allow=0.6, radius=None, want_partners=True,
+                   obst_polar=None, hydrogens=None):
+        """All-atom clashscore per segment on the device (pp_hydrogens + pp_clashscore): serious overlaps
+        (more than ``cut`` A of van der Waals overlap, ``hb_allow`` A more between a polar hydrogen and an acceptor) between all atoms,
+        placed hydrogens included, per 1000 atoms.  NOT MolProbity's number: no Reduce flips, no optimisation of rotatable
+        hydrogens, and the radii are ``constants.allatom_radius``.  Coordinates and ``link`` as in ``hydrogens`` (``hydrogens``: a
+        result of it at the same coordinates, else it is called here).  ``rotatable`` "skip" (default): hydroxyl, thiol and lysine
+        NH3+ hydrogens are not counted (radius 0); "keep": they are.  ``radius`` [B, L, 27]: radii other than the default (an atom is
+        counted iff its radius is > 0).  ``obst_polar`` as in ``polar``.  Returns an ``EnsembleResult``: ``n_clash`` int32 [B, L, 27,
+        2], ``partners`` int32 [B, L, 27, 4] (None without ``want_partners``), ``res`` int32 [B, L, 4], ``seg`` int32 [n_segments, 8]
+        (include/packppi_hip.h lists the columns), ``clashscore`` = 1000 seg[:, 1] / max(seg[:, 0], 1) and ``clashscore_obstacles``
+        (with seg[:, 6] added) fp64 [n_segments], and ``hxyz`` / ``hmask`` / ``link_prev`` / ``xyz``.  No host synchronisation."""
+        import math
+        dev = self.plan.device
+        if rotatable not in ("skip", "keep"):
+            raise ValueError('clashscore: rotatable must be "skip" or "keep"')
+        if not math.isfinite(float(cut)):
+            raise ValueError("clashscore: cut must be finite")
+        if not (math.isfinite(float(hb_allow)) and float(hb_allow) >= 0):
+            raise ValueError("clashscore: hb_allow must be finite and not negative")
+        tabs = self.allatom_tables()
+        if radius is None:
+            cache = self.__dict__.setdefault("_aa_radius", {})
+            if rotatable not in cache:
+                cache[rotatable] = tabs.radius if rotatable == "keep" else self._own((tabs.radius * ~tabs.rotatable).contiguous())
+            radius = cache[rotatable]
+        else:
+            radius = self._rows(torch.as_tensor(radius), "radius", rc.PP_AA_SLOTS)
+            if rotatable == "skip":
+                radius = (radius.reshape(-1, rc.PP_AA_SLOTS) * ~tabs.rotatable).contiguous()
+        op = getattr(self, "_obst_polar", None) if self.n_obstacles else None
+        if obst_polar is not None:
+            if self.n_obstacles == 0:
+                raise ValueError("clashscore: obst_polar on a context without obstacle atoms")
+            op = (torch.as_tensor(obst_polar).to(device=dev) != 0).to(torch.uint8).reshape(-1).contiguous()
+            if op.numel() != self.n_obstacles:
+                raise ValueError(f"clashscore: obst_polar has {op.numel()} entries, the context holds {self.n_obstacles} obstacle atoms")
+        link = self._link(link)
+        h = hydrogens if hydrogens is not None else self.hydrogens(chi=chi, xyz=xyz, link=link)
+        xyz = h["xyz"]
+        S = rc.PP_AA_SLOTS
+        partners = self._new(self.B, self.L, S, 4, dtype=torch.int32) if want_partners else None
+        n_clash = self._new(self.B, self.L, S, 2, dtype=torch.int32)
+        res = self._new(self.B, self.L, 4, dtype=torch.int32)
+        seg = self._new(self.n_segments, 8, dtype=torch.int32)
+        _check(load().pp_clashscore(self.handle, _ptr(xyz), _ptr(h["hxyz"]), _ptr(h["hmask"]), _ptr(radius), _ptr(tabs.acls),
+                                    _ptr(tabs.aa_sep), _ptr(h["link_prev"]), _ptr(link), _ptr(op), float(cut), float(hb_allow),
+                                    _ptr(partners), _ptr(n_clash), _ptr(res), _ptr(seg), self._stream()), "pp_clashscore")
+        atoms = seg[:, 0].clamp(min=1).double()
+        return EnsembleResult(n_clash=n_clash, partners=partners, res=res, seg=seg, clashscore=1000.0 * seg[:, 1].double() / atoms,
+                              clashscore_obstacles=1000.0 * (seg[:, 1] + seg[:, 6]).double() / atoms, hxyz=h["hxyz"], hmask=h["hmask"],
+                              link_prev=h["link_prev"], xyz=xyz, radius=radius)
 
     def saturated(self) -> int:
         """Sticky flag word of this context: 0 = clean; bit 0 / bit 1 = a hidden activation was clamped at 65504 in an edge-level /

@@ -305,3 +305,50 @@ def to_pdb(prot: Dict, keep_chains: Optional[list] = None) -> str:
     out.append(_ter(serial, rc.resnames[aa[-1]], chain[-1], ridx[-1]))
     out += ["ENDMDL", "END"]
     return "\n".join(ln.ljust(80) for ln in out) + "\n"
+
+
+def to_pdb_hydrogens(prot: Dict, hxyz, hmask) -> str:
+    """``to_pdb(prot)`` with the placed hydrogens (``Context.hydrogens``: ``hxyz`` [n, 13, 3], ``hmask`` [n, 13])
+    behind each residue's heavy atoms: the same records, the hydrogens named as in PDB v3 (``constants.hydrogen_names``) with
+    element H and the B factor of their parent, serial numbers renumbered.  A hydrogen of an absent parent is not written."""
+    amask, aa = np.asarray(prot["atom_mask"]), np.asarray(prot["aaindex"])
+    xyz, ridx = np.asarray(prot["atom_positions"]), np.asarray(prot["residue_index"])
+    chain, bfac = np.asarray(prot["chain_id"]), np.asarray(prot["b_factors"])
+    hxyz, hmask = np.asarray(hxyz, dtype=np.float64).reshape(-1, rc.PP_H_MAX, 3), np.asarray(hmask).reshape(-1, rc.PP_H_MAX)
+    if np.any(aa > 20):
+        raise ValueError("Invalid aaindexs.")
+    if len(hxyz) < len(aa):
+        raise ValueError(f"to_pdb_hydrogens: hydrogens of {len(hxyz)} rows for {len(aa)} residues")
+
+    def record(serial, aname, rname, i, p, b, element):
+        shown = aname if len(aname) == 4 else f" {aname}"
+        coords = f"{p[0]:>8.3f}{p[1]:>8.3f}{p[2]:>8.3f}"
+        if len(coords) != 24:
+            raise ValueError(f"to_pdb_hydrogens: coordinate {tuple(float(v) for v in p)} of {rname} {chain[i]}{ridx[i]} {aname} does not "
+                             "fit the 8.3f columns of an ATOM record (-999.999 .. 9999.999); move the structure nearer the origin")
+        return (f"{'ATOM':<6}{serial:>5} {shown:<4}{'':>1}{rname:>3} {chain[i]:>1}{ridx[i]:>4}{'':>1}   {coords}"
+                f"{1.0:>6.2f}{b:>6.2f}          {element:>2}{'':>2}")
+
+    out = ["MODEL     1"]
+    serial = 1
+    prev_chain = chain[0]
+    for i in range(aa.shape[0]):
+        if chain[i] != prev_chain:
+            out.append(_ter(serial, rc.resnames[aa[i - 1]], chain[i - 1], ridx[i - 1]))
+            prev_chain = chain[i]
+            serial += 1
+        rname = rc.resnames[aa[i]]
+        for aname, p, m, b in zip(rc.atom14_names[aa[i]], xyz[i], amask[i], bfac[i]):
+            if m < 0.5:
+                continue
+            out.append(record(serial, aname, rname, i, p, b, aname[0]))
+            serial += 1
+        for k, hname in enumerate(rc.hydrogen_names[aa[i]]):
+            parent = int(rc.hydrogen_parent[aa[i], k])
+            if hmask[i, k] == 0 or amask[i, parent] < 0.5:
+                continue
+            out.append(record(serial, hname, rname, i, hxyz[i, k], bfac[i, parent], "H"))
+            serial += 1
+    out.append(_ter(serial, rc.resnames[aa[-1]], chain[-1], ridx[-1]))
+    out += ["ENDMDL", "END"]
+    return "\n".join(ln.ljust(80) for ln in out) + "\n"
