@@ -723,6 +723,65 @@ pp_status pp_clashscore(pp_ctx *ctx, const float *xyz /* DEVICE [N,14,3] or NULL
                         int32_t *partners /* DEVICE [N][27][PP_CLASH_CAP] or NULL */, int32_t *n_clash /* DEVICE [N][27][2] */,
                         int32_t *res /* DEVICE [N][4] */, int32_t *seg /* DEVICE [n_seg][8] */, void *stream);
 
+/* ---- Hydrogen-bond network optimisation (no reference kernel; csrc/pp_hnet.hip holds the arithmetic) ---------
+ * Chooses, per segment of the ctx's segment table, a state for every MOVER -- a rotor (hydroxyl, thiol, lysine NH3+: the hydrogens
+ * turn about the bond to their parent) or a flip (Asn / Gln / His: the group behind one chi turned by pi) -- by a monotone descent on
+ * an integer energy: 64 per serious overlap of pp_clashscore minus 2 per good, 1 per weak explicit-hydrogen bond.  Integer counts,
+ * NOT Reduce's dot scores; no exhaustive search of cliques; the numbers belong to the radii given.  Caller data:
+ *   xyz0, hxyz0, hmask0   state 0: the heavy atoms and what pp_hydrogens wrote at them
+ *   xyz1, hxyz1, hmask1   the same at chi + pi on the flip rows (pp_atom14 and pp_hydrogens made them), or all NULL: no row flips
+ *   chi0, chi1, chi_out   DEVICE [N][4]: the angles behind the two sets and the selection, or all NULL
+ *   place, param          pp_hydrogens' tables
+ *   mover   DEVICE int32 [21][4]: (kind, states, bit mask over the 27 slots of the atoms that move, 0) per residue type; kind 0 none,
+ *           1 rotor (1 .. PP_HNET_STATES states, at most PP_HNET_ROT_H moved slots, all hydrogens placed by NERF), 2 flip (2 states,
+ *           at most PP_HNET_MOVED moved slots)
+ *   rot     DEVICE float [21][12][3][2]: cos / sin of the dihedral of a rotor's j-th moved hydrogen in state c, used in place of
+ *           param's in pp_hydrogens' NERF arithmetic; state 0 holds param's own values
+ *   ext     DEVICE float [21]: no moved atom of the type is farther from CA than this, in any state
+ *   radius, acls, aa_sep, link_prev, link, obst_polar, cut, hb_allow   as for pp_clashscore (rotatable hydrogens kept)
+ *   hb_weak, hb_weak2, hb_good2   the bond lengths: hb_weak in A, and the squares of the weak and the good limit rounded on the host
+ *   reach   max(2 largest radius - cut, hb_weak): two movers are PARTNERS iff d2(CA, CA') <= ((ext + ext') + reach)^2
+ * A row is a mover iff its type has one and a moved slot is a counted atom in state 0.  State 0 is the input; every mover proposes
+ * its best state given the others, and a proposal is accepted iff its gain is positive and beats that of every partner (ties: the
+ * lower row); accepted movers share no term, so the total energy F drops by exactly the sum of the accepted gains.  max_sweeps
+ * sweeps are enqueued (0 .. PP_HNET_MAX_SWEEPS); a segment without a positive gain is converged and its later launches return at
+ * once.  Outputs on the device, no read-back:
+ *   state[n]      the chosen state, -1 for a row that is no mover
+ *   xyz_out, hxyz_out, hmask_out, chi_out   row n of set 1 or of set 0, bit for bit; a rotor's moved hydrogens at the chosen state
+ *   e[n]          E of the row at the start and at the end (0 for a row that is no mover)
+ *   hb[n]         DEVICE int32 [N][2] or NULL: the explicit-hydrogen bonds (weak or good) of the row's moved atoms at the start and
+ *                 at the end, a bond between two movers counted in the higher row only: a segment's sum counts every bond once
+ *   trace[s][k]   F after k sweeps, k = 0 .. max_sweeps
+ *   sweeps[s], converged[s]   sweeps that moved a row; 1 iff the segment has no positive gain left
+ *   cand          DEVICE float [N][12][3][3] or NULL: every rotor candidate position (state, hydrogen), 0 where there is none
+ *   energy        DEVICE int32 [N][12] or NULL: E of the row in every state, the others at state 0
+ * A mover entry outside its range, or a residue_type outside 0 .. 20, is found on the device: the row is no mover and bit 3 (value 8)
+ * of pp_ctx_saturated is set; it is never used as an index.  The first call on a ctx allocates the workspace (sized from N and the
+ * segment count), which may wait for the device; pp_ctx_destroy frees it.  Geometry-only plans work.  Never waits for the stream.
+ * PP_ERR_INVALID: a null ctx, table, input of set 0 or output other than cand / energy / chi_out; half of set 1 or of the chi
+ * triple; chi without set 1; cut, hb_allow as pp_clashscore; a bond length that is not finite and positive, hb_good2 > hb_weak2;
+ * reach not finite or below hb_weak; max_sweeps outside 0 .. PP_HNET_MAX_SWEEPS; a batch without chain_indices or residue_type;
+ * obst_polar on a ctx without obstacles. */
+#define PP_HNET_STATES 12
+#define PP_HNET_ROT_H 3
+#define PP_HNET_MOVED 7
+#define PP_HNET_PCAP 16
+#define PP_HNET_MAX_SWEEPS 256
+pp_status pp_hnet_optimize(pp_ctx *ctx, const float *xyz0 /* DEVICE [N,14,3] */, const float *hxyz0 /* DEVICE [N][13][3] */,
+                           const uint8_t *hmask0 /* DEVICE [N][13] */, const float *xyz1, const float *hxyz1, const uint8_t *hmask1,
+                           const float *chi0 /* DEVICE [N][4] or NULL */, const float *chi1, const int8_t *place /* DEVICE [21][13][5] */,
+                           const float *param /* DEVICE [21][13][5] */, const int32_t *mover /* DEVICE [21][4] */,
+                           const float *rot /* DEVICE [21][12][3][2] */, const float *ext /* DEVICE [21] */,
+                           const float *radius /* DEVICE [N][27] */, const uint8_t *acls /* DEVICE [N][27] */,
+                           const uint8_t *aa_sep /* DEVICE [21][27][27] */, const uint8_t *link_prev /* DEVICE [N] */,
+                           const int32_t *link /* DEVICE [N] or NULL */, const uint8_t *obst_polar /* DEVICE [M] or NULL */, float cut,
+                           float hb_allow, float hb_weak, float hb_weak2, float hb_good2, float reach, int max_sweeps,
+                           int32_t *state /* DEVICE [N] */, float *xyz_out /* DEVICE [N,14,3] */, float *hxyz_out /* DEVICE [N][13][3] */,
+                           uint8_t *hmask_out /* DEVICE [N][13] */, float *chi_out /* DEVICE [N][4] or NULL */, int32_t *e /* DEVICE [N][2] */,
+                           int32_t *hb /* DEVICE [N][2] or NULL */, int32_t *trace /* DEVICE [n_seg][max_sweeps + 1] */, int32_t *sweeps /* DEVICE [n_seg] */,
+                           int32_t *converged /* DEVICE [n_seg] */, float *cand /* DEVICE [N][12][3][3] or NULL */,
+                           int32_t *energy /* DEVICE [N][12] or NULL */, void *stream);
+
 /* Measurement aid, no reference counterpart: average duration (ms) of one launch of a hot kernel
  * (which: 0 = node-message kernel, 1 = edge-update kernel), timed with HIP events on `stream`
  * around `iters` launches.  Synchronises the stream. */
@@ -767,7 +826,8 @@ pp_status pp_range_check_parts(unsigned long long *edge_events, unsigned long lo
  * clamp); these kernels' clamps turn it into finite numbers that mean nothing -- the flag is how a caller learns of it.
  * Inside a sampling run the last node update of an evaluation reports bit 1 only for rows whose angles can move (the live rows
  * below, without the fixed rows of pp_sample_partial): what it computes for the others is returned to nobody.
- * Bit 3 (value 8): pp_hydrogens / pp_clashscore met a table entry or a residue_type outside its range and dropped the atom. */
+ * Bit 3 (value 8): pp_hydrogens / pp_clashscore met a table entry or a residue_type outside its range and dropped the atom;
+ * pp_hnet_optimize met such a mover entry and left the row alone. */
 pp_status pp_ctx_saturated(pp_ctx *ctx, int *flags, void *stream);
 
 /* Live rows (no reference counterpart): the rows of the context whose angles a sampling run can move --

@@ -240,6 +240,42 @@ def write_clashes(path, protein, res, row=0, native=None, hb_allow=0.6):
     print(clashscore_summary(res, row, native))
 
 
+HNET_CSV_HEADER = "chain,residue,name,kind,state,angle,e_before,e_after"
+
+
+def hnet_csv(residue_type, state, e, chain, residue_index):
+    """The text of ``hnet.csv``: one line per mover (``state`` >= 0) of what ``Context.hbond_optimize`` returned -- chain, residue
+    number, residue name, kind (rotor / flip), the chosen state, its angle in degrees (the dihedral of a rotor's first hydrogen; 0 or
+    180 for a flip) and the row's energy before and after.  All arguments per row, lists or arrays; ``e`` [n, 2]."""
+    from . import constants as rc
+    e = np.asarray(e, dtype=np.int64).reshape(-1, 2)
+    lines = [HNET_CSV_HEADER]
+    for r, (aa, st) in enumerate(zip(residue_type, state)):
+        if int(st) < 0:
+            continue
+        kind = {rc.MOVER_ROTOR: "rotor", rc.MOVER_FLIP: "flip"}[int(rc.mover_table[int(aa), 0])]
+        lines.append(f"{chain[r]},{int(residue_index[r])},{rc.resnames[int(aa)]},{kind},{int(st)},{rc.mover_state_angle(int(aa), int(st)):.1f},"
+                     f"{int(e[r, 0])},{int(e[r, 1])}")
+    return "\n".join(lines) + "\n"
+
+
+def hnet_summary(res, row=0):
+    """The summary line of the command lines for segment ``row`` of a ``Context.hbond_optimize`` result."""
+    st = res.state.reshape(-1)
+    tr = res.trace[row].cpu().tolist()
+    return (f"----- hydrogen-bond network: {int(res.n_movers[row])} movers, energy {tr[0]} -> {tr[-1]} in {int(res.sweeps[row])} sweeps"
+            f"{'' if int(res.converged[row]) else ' (not converged)'} -----")
+
+
+def write_hnet(path, protein, res, row=0):
+    """``hnet.csv`` at ``path`` from what ``Context.hbond_optimize`` returned for a B = 1 batch of ``protein``; prints the summary."""
+    n = len(protein["aaindex"])
+    with open(path, "w") as fh:
+        fh.write(hnet_csv(protein["aaindex"], res.state[row].reshape(-1)[:n].cpu().numpy(), res.e[row].reshape(-1, 2)[:n].cpu().numpy(),
+                          protein["chain_id"], protein["residue_index"]))
+    print(hnet_summary(res, row))
+
+
 def write_structure_h(path, protein, h, row=0, head="", obstacle_lines=()):
     """``structure_H.pdb`` at ``path``: ``pdb_io.to_pdb_hydrogens`` of ``protein`` with the hydrogens ``Context.hydrogens`` (or
     ``clashscore``) placed for a B = 1 batch of it; ``head``: records that go in front (SSBOND); ``obstacle_lines``: the obstacle

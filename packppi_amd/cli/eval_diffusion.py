@@ -46,9 +46,10 @@ evaluation and a Langevin step of signal-to-noise ratio SNR with a step size per
 --clashscore / --hydrogens (without them every output byte as before): --clashscore writes clashes.csv for the
 written structure -- one line per serious all-atom overlap with placed hydrogens (atoms named as in hbonds.csv, distance, overlap in
 A, kept | gained | lost against the input's own side chains) -- and prints the clashscore (with the input's own beside it);
---hydrogens writes structure_H.pdb, structure.pdb plus the placed hydrogens.  With --n_decoys ensemble.csv gains the columns clashscore
+--hydrogens writes structure_H.pdb, structure.pdb plus the placed hydrogens.  --hnet optimises flips and
+rotatable hydrogens first: structure.pdb takes the flipped angles, structure_H.pdb the optimised hydrogens, hnet.csv lists the movers.  With --n_decoys ensemble.csv gains the columns clashscore
 and clashes_interface.  --disulfides hands its bridges on: a bonded cysteine has no HG and the bridge is not an overlap.  The score
-is NOT MolProbity's: no flips, no optimisation of rotatable hydrogens, this package's radius table.
+is NOT MolProbity's: this package's radius table, and flips and rotatable hydrogens only with --hnet.
 --disulfides auto|SPEC (without --disulfides every output byte as before): behind the sampler the chi1 of every
 bonded cysteine pair are set so that the two sulfurs meet -- auto finds the pairs from the backbone, SPEC names them
 ('A:5-A:55,A:14-A:38').  With --use_proximal the proximal stage then keeps the bonded residues; with --repack a kept residue keeps its
@@ -250,7 +251,8 @@ def write_ensemble(model, batch, protein, args, analysis):
     out = model.sample_ensemble(batch, args.n_decoys, seed=args.seed, use_proximal=args.use_proximal, select=args.select,
                                 return_all=True, **kw, **(dict(sasa=True) if args.sasa else {}),
                                 **(dict(polar=True) if getattr(args, "polar", False) else {}),
-                                **(dict(clashscore=True) if getattr(args, "clashscore", False) else {}), **args.guide_kw)
+                                **(dict(clashscore=True) if getattr(args, "clashscore", False) else {}),
+                                **(dict(hbond_optimize=True) if getattr(args, "hnet", False) else {}), **args.guide_kw)
     chi, packed = out["decoys"]
     best = int(out["best"][0])
     dev, clash = out["dev"].cpu().tolist(), out["clash"].cpu().tolist()
@@ -274,11 +276,14 @@ def write_ensemble(model, batch, protein, args, analysis):
         pvals = [out[k].cpu().tolist() for k in pcols]
         aa = getattr(args, "clashscore", False)
         score, face = (out["clashscore"].cpu().tolist(), out["clashes_interface"].cpu().tolist()) if aa else (None, None)
+        hcols = [k for k in ("hnet_bonds", "hnet_flips", "clashscore_hnet") if k in out] if getattr(args, "hnet", False) else []
+        hvals = [out[k].cpu().tolist() for k in hcols]
         fh.write("decoy,key,dev,clash,selected" + (",bsa" if args.sasa else "") + "".join("," + k for k in pcols)
-                 + (",clashscore,clashes_interface" if aa else "") + "\n")
+                 + (",clashscore,clashes_interface" if aa else "") + "".join("," + k for k in hcols) + "\n")
         for d, key in enumerate(out["keys"]):
             fh.write(f"{d},{key},{dev[d]!r},{clash[d]!r},{int(d == best)}" + (f",{bsa[d]!r}" if args.sasa else "")
-                     + "".join(f",{int(v[d])}" for v in pvals) + (f",{score[d]!r},{int(face[d])}" if aa else "") + "\n")
+                     + "".join(f",{int(v[d])}" for v in pvals) + (f",{score[d]!r},{int(face[d])}" if aa else "")
+                     + "".join(f",{v[d]!r}" if isinstance(v[d], float) else f",{int(v[d])}" for v in hvals) + "\n")
     conf = out["confidence"][0].cpu().tolist()
     conf += [[0.0] * 4] * (len(protein["aaindex"]) - len(conf))
     with open(os.path.join(args.outdir, "confidence.csv"), "w") as fh:
@@ -395,19 +400,39 @@ def add_allatom_arguments(p):
     """--clashscore and --hydrogens.  Their defaults are SUPPRESSed: without the flags the namespace is what it was before them."""
     p.add_argument("--clashscore", action="store_true", default=argparse.SUPPRESS, help="Write clashes.csv for the written structure "
                    "(DESIGN.md section 29): every serious all-atom overlap with hydrogens placed on the device, and print the "
-                   "clashscore (overlaps per 1000 atoms; NOT MolProbity's number: no flips, no optimisation of rotatable hydrogens, "
+                   "clashscore (overlaps per 1000 atoms; NOT MolProbity's number: flips and rotatable hydrogens only with --hnet, "
                    "this package's radii); with --n_decoys ensemble.csv gains the columns clashscore and clashes_interface.")
     p.add_argument("--hydrogens", action="store_true", default=argparse.SUPPRESS, help="Write structure_H.pdb: the records of the "
                    "written structure plus the hydrogens placed on the device behind each residue's heavy atoms (DESIGN.md section 29; "
-                   "hydroxyl, thiol and lysine NH3+ hydrogens at a conventional position, not an optimised one).")
+                   "hydroxyl, thiol and lysine NH3+ hydrogens at a conventional position, not an optimised one; --hnet optimises them).")
+    p.add_argument("--hnet", action="store_true", default=argparse.SUPPRESS, help="Optimise the hydrogen-bond network of the written "
+                   "structure on the device (DESIGN.md section 30): Asn / Gln / His flips and the rotatable hydrogens of Ser, Thr, Tyr, "
+                   "Cys and Lys.  structure.pdb takes the flipped angles, structure_H.pdb (--hydrogens) the optimised hydrogens, hnet.csv "
+                   "holds one line per mover, and the --clashscore summary gains the score with the rotatable hydrogens counted, before "
+                   "and after.  Integer counts of overlaps and bonds, not Reduce's dot scores.")
+
+
+def optimise_hnet(batch, protein, outdir, chi, link=None, name="hnet.csv"):
+    """--hnet: ``Context.hbond_optimize`` of the B = 1 ``batch`` at the angles ``chi`` [1, n, 4] (n < L: as in ``write_sasa``), hnet.csv and
+    the summary line.  Returns the result; its ``chi`` [1, L, 4] holds the flips."""
+    from ..analysis import write_hnet
+    from ..functional import _ctx_for
+    chi = chi.to(batch.SC_D.device)
+    if chi.shape[1] != batch.SC_D.shape[1]:
+        chi = torch.cat([chi, batch.SC_D[:, chi.shape[1]:]], 1)
+    res = _ctx_for(batch).hbond_optimize(chi=chi, link=link)
+    write_hnet(os.path.join(outdir, name), protein, res, 0)
+    return res
 
 
 def write_allatom(batch, protein, outdir, chi, clashscore=False, hydrogens=False, native=False, link=None, head="", obstacle_lines=(),
-                  names=("clashes.csv", "structure_H.pdb")):
+                  names=("clashes.csv", "structure_H.pdb"), hnet=None):
     """--clashscore / --hydrogens: clashes.csv and structure_H.pdb of the B = 1 ``batch`` at the angles ``chi`` [1, n, 4] (n < L: as in
     ``write_sasa``), and the summary line.  ``native``: the input has side chains of its own -- clashes.csv marks every overlap kept,
     gained or lost against them and the summary gives the input's own score.  ``link``: the partner array of the run's disulfide
-    closure.  ``head`` / ``obstacle_lines``: what the written structure carries around its ATOM records."""
+    closure.  ``head`` / ``obstacle_lines``: what the written structure carries around its ATOM records.  ``hnet``: what
+    ``optimise_hnet`` returned for ``chi`` before its flips went into it -- structure_H.pdb then takes the optimised hydrogens, and the
+    summary gains the score with the rotatable hydrogens counted, conventional and optimised."""
     from ..analysis import write_clashes, write_structure_h
     from ..functional import _ctx_for
     chi = chi.to(batch.SC_D.device)
@@ -417,8 +442,15 @@ def write_allatom(batch, protein, outdir, chi, clashscore=False, hydrogens=False
     if clashscore:
         h = ctx.clashscore(chi=chi, link=link)
         write_clashes(os.path.join(outdir, names[0]), protein, h, 0, ctx.clashscore(link=link) if native else None)
+        if hnet is not None:
+            conv = ctx.clashscore(chi=hnet.chi0, link=link, rotatable="keep", want_partners=False)
+            opt = ctx.clashscore(chi=hnet.chi, link=link, hydrogens=hnet, rotatable="keep", want_partners=False)
+            print(f"----- clashscore with the rotatable hydrogens counted: {float(conv.clashscore[0]):.2f} as placed, "
+                  f"{float(opt.clashscore[0]):.2f} with the hydrogen-bond network optimised (--hnet) -----")
     else:
         h = ctx.hydrogens(chi=chi, link=link)
+    if hnet is not None:
+        h = hnet
     if hydrogens:
         n = len(protein["aaindex"])
         placed = dict(protein, atom_positions=h.xyz[0].reshape(-1, 14, 3)[:n].cpu().numpy())
@@ -481,6 +513,13 @@ def evaluate_model(model, args):
         # a hidden activation reached the f16 maximum in the split-f16 dense layers: not the reference's arithmetic any more
         print("----- WARNING: f16 saturation in the score network (flag %d); run `python -m packppi_amd.rangecheck` on this "
               "checkpoint -----" % model.saturated())
+    hnet = None
+    if getattr(args, "hnet", False):
+        # with --n_decoys structure.pdb stays the selected decoy's file; hnet.csv and structure_H.pdb describe its optimised network
+        link = model.disulfide_reports[-1]["partner"] if disulfides is not None else None
+        hnet = optimise_hnet(batch, protein, args.outdir, SC_D_sample, link)
+        if args.n_decoys is None:
+            SC_D_sample = hnet.chi[:, :SC_D_sample.shape[1]].to(SC_D_sample.device)
     if args.n_decoys is None:           # --n_decoys wrote structure.pdb itself: byte for byte the selected decoy's file
         xyz = get_atom14_coords(batch.X, batch.residue_type, batch.BB_D, SC_D_sample)
         protein["atom_positions"] = xyz.cpu().squeeze(0).numpy()
@@ -495,7 +534,8 @@ def evaluate_model(model, args):
     if getattr(args, "clashscore", False) or getattr(args, "hydrogens", False):
         link = model.disulfide_reports[-1]["partner"] if disulfides is not None else None
         write_allatom(batch, protein, args.outdir, SC_D_sample, getattr(args, "clashscore", False), getattr(args, "hydrogens", False),
-                      native=contains_sidechains(args.input), link=link, head=ssbond, obstacle_lines=args.obstacle_lines)
+                      native=contains_sidechains(args.input), link=link, head=ssbond, obstacle_lines=args.obstacle_lines,
+                      **(dict(hnet=hnet) if hnet is not None else {}))
     if contains_sidechains(args.input):
         metric = analysis.get_metric(true_pdb=args.input, pred_pdb=analysis.tmp_pdb)
         print(f"----- Metric: ----- {metric}")

@@ -9,6 +9,8 @@ residue's clash against them before and after.
 --sasa (without it every output byte as before) writes sasa.csv for the optimised structure, as eval_diffusion
 does; --repack also takes interface:sasa (the delta-SASA interface of the input, made on the device) and pocket (residues whose
 surface the obstacle atoms bury; needs --obstacles other than none).
+--hnet (without it every output byte as before): the hydrogen-bond network of the optimised structure is
+optimised on the device -- structure.pdb takes the flips, structure_H.pdb the optimised hydrogens, hnet.csv lists the movers.
 --clashscore / --hydrogens (without them every output byte as before): clashes.csv (every serious all-atom
 overlap of the optimised structure with placed hydrogens, kept | gained | lost against the input, and the clashscore of both) and
 structure_H.pdb, as eval_diffusion writes them.  Not MolProbity's score.
@@ -105,10 +107,19 @@ def main(argv=None):
     if args.sasa:
         from .eval_diffusion import write_sasa
         write_sasa(batch, protein, args.outdir, SC_D)
+    hnet = None
+    if getattr(args, "hnet", False):
+        # structure.pdb takes the flips: written again at the angles of the optimised network
+        from .eval_diffusion import optimise_hnet
+        hnet = optimise_hnet(batch, protein, args.outdir, SC_D)
+        SC_D = hnet.chi[:, :SC_D.shape[1]].to(SC_D.device)
+        flipped = dict(protein, atom_positions=get_atom14_coords(batch.X, batch.residue_type, batch.BB_D, SC_D).cpu().squeeze(0).numpy())
+        with open(analysis.tmp_pdb, "w") as fh:
+            fh.writelines(insert_obstacle_lines(to_pdb(flipped), obstacles["lines"] if obstacles else []))
     if getattr(args, "clashscore", False) or getattr(args, "hydrogens", False):
         from .eval_diffusion import write_allatom
         write_allatom(batch, protein, args.outdir, SC_D, getattr(args, "clashscore", False), getattr(args, "hydrogens", False),
-                      native=True, obstacle_lines=obstacles["lines"] if obstacles else [])
+                      native=True, obstacle_lines=obstacles["lines"] if obstacles else [], **(dict(hnet=hnet) if hnet is not None else {}))
     print(f"----- The optimized structure clashscore is {analysis.get_clashscore(analysis.tmp_pdb)} -----")
     print("----- Finishing optimize! -----")
 

@@ -220,6 +220,78 @@ aa_sep, allatom_default_radius, allatom_class = _allatom_tables()
 # [21,27] f32 default radius (0 = empty slot); [21,27] u8 class bits AA_*
 
 
+# Hydrogen-bond network optimisation (pp_hnet_optimize).  A residue type has at most one MOVER: a rotor (the
+# rotatable hydrogens above turn about the bond to their parent) or a flip (the rigid group of one chi turned by pi, hydrogens with
+# it).  Only the flipped chi of each flip type and the rotor states are written out; the moved atoms are derived.
+MOVER_NONE, MOVER_ROTOR, MOVER_FLIP = 0, 1, 2
+PP_HNET_STATES, PP_HNET_ROT_H, PP_HNET_MOVED = 12, 3, 7
+mover_flip_chi = {"ASN": 1, "GLN": 2, "HIS": 1}          # index of the flipped chi: chi2, chi3, chi2
+# dihedral of the rotor's first hydrogen in state c, degrees; a lysine's HZ2 / HZ3 follow at + 120 / + 240
+mover_rotor_states = {"SER": [180.0 + 30.0 * c for c in range(12)], "THR": [180.0 + 30.0 * c for c in range(12)],
+                      "CYS": [180.0 + 30.0 * c for c in range(12)], "TYR": [180.0, 0.0], "LYS": [60.0 + 30.0 * c for c in range(4)]}
+
+
+def _mover_tables():
+    f32 = np.float32
+    table = np.zeros((21, 4), np.int32)                    # (kind, states, bit mask of the moved slots, 0)
+    rot = np.zeros((21, PP_HNET_STATES, PP_HNET_ROT_H, 2), np.float32)
+    ext = np.zeros(21, np.float32)
+    for t in range(20):
+        rn = resnames[t]
+        hyd = [k for k in range(int(hydrogen_count[t])) if hydrogen_flags[t, k] & H_ROTATABLE]
+        moved = []
+        if rn in mover_flip_chi:
+            heavy = [s for s in range(14) if atom14_names[t][s] and int(atom14_to_group[t, s]) == 4 + mover_flip_chi[rn]]
+            moved = heavy + [14 + k for k in range(int(hydrogen_count[t])) if int(hydrogen_parent[t, k]) in heavy]
+            table[t, :2] = MOVER_FLIP, 2
+        elif hyd:
+            states = mover_rotor_states[rn]
+            moved = [14 + k for k in hyd]
+            table[t, :2] = MOVER_ROTOR, len(states)
+            for c, deg in enumerate(states):
+                for j, k in enumerate(hyd):
+                    if c == 0:
+                        rot[t, 0, j] = hydrogen_param[t, k, 3:5]           # the very values pp_hydrogens uses
+                    else:
+                        a = np.deg2rad(deg + 120.0 * j)
+                        rot[t, c, j] = f32(np.cos(a)), f32(np.sin(a))
+        if not moved:
+            continue
+        assert len(moved) <= PP_HNET_MOVED and len(hyd) <= PP_HNET_ROT_H
+        table[t, 2] = sum(1 << s for s in moved)
+        # the longest way along the bonds from CA to a moved atom, ideal lengths: no moved atom is ever farther from CA than this
+        dist = {1: 0.0}
+        edges = [(int(a), int(b), float(length)) for rt, a, b, length, _ in bond_rows if int(rt) == t and length < 1.9]
+        edges += [(int(hydrogen_parent[t, k]), 14 + k, hydrogen_bond_length[atom14_names[t][int(hydrogen_parent[t, k])][0]])
+                  for k in range(int(hydrogen_count[t]))]
+        for _ in range(PP_AA_SLOTS):
+            for a, b, length in edges:
+                for u, v in ((a, b), (b, a)):
+                    if u in dist and dist[u] + length < dist.get(v, 1e9):
+                        dist[v] = dist[u] + length
+        ext[t] = f32(max(dist[s] for s in moved))
+    return table, rot, ext
+
+
+mover_table, mover_rotor_cs, mover_extent = _mover_tables()
+# [21,4] i32 (kind MOVER_*, number of states, bit mask over the 27 all-atom slots of the atoms that move, 0); [21,12,3,2] f32 cos / sin
+# of the dihedral of the rotor's j-th hydrogen in state c (state 0: hydrogen_param's); [21] f32 sum of ideal bond lengths from CA to
+# the farthest moved atom
+
+
+def mover_moved_names(t):
+    """Names of the moved atoms of residue type t, in slot order."""
+    return [allatom_names[t][s] for s in range(PP_AA_SLOTS) if int(mover_table[t, 2]) >> s & 1]
+
+
+def mover_state_angle(t, state):
+    """What ``hnet.csv`` prints as the angle of a mover of type t in `state`: the dihedral of a rotor's first hydrogen in degrees
+    (wrapped to [0, 360)), 0 / 180 for a flip."""
+    if int(mover_table[t, 0]) == MOVER_ROTOR:
+        return float(mover_rotor_states[resnames[t]][int(state)] % 360.0)
+    return 180.0 * int(state)
+
+
 @lru_cache(maxsize=16)
 def make_atom14_dists_bounds(overlap_tolerance: float = 1.5,
                              bond_length_tolerance_factor: float = 15.0):

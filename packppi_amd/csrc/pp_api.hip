@@ -343,6 +343,7 @@ extern "C" void pp_ctx_destroy(pp_ctx *c) {
     if (c->ds_ws) (void)hipFree(c->ds_ws);            // likewise: only a context that ever ran pp_disulfide_close
     if (c->po_ws) (void)hipFree(c->po_ws);            // likewise: only a context that ever ran pp_polar
     if (c->aa_ws) (void)hipFree(c->aa_ws);            // likewise: only a context that ever ran pp_clashscore
+    if (c->hn_ws) (void)hipFree(c->hn_ws);            // likewise: only a context that ever ran pp_hnet_optimize
     delete c;
 }
 

@@ -201,6 +201,8 @@ struct pp_ctx {
     size_t po_bytes = 0;      // allocation outside the arena, made by the first call, freed with the ctx
     void *aa_ws = nullptr;    // pp_clashscore: its workspace ([N][27] position + radius, [N] row sphere, [N][27] class + separations), sized
     size_t aa_bytes = 0;      // from N; ONE allocation outside the arena, made by the first call, freed with the ctx
+    void *hn_ws = nullptr;    // pp_hnet_optimize: its workspace (current atoms, rotor candidates, mover and partner lists, per-sweep counters),
+    size_t hn_bytes = 0;      // sized from N and the segment count; ONE allocation outside the arena, made by the first call, freed with the ctx
     // seeded sampling noise (pp_rng.h): the per-row table of the seeded kernels and the complexes' keys
     pp_rng_row *rng_tab;      // [N] (row within the complex, key of the complex); filled by pp_launch_rng_table
     uint64_t *rng_keys;       // [B] the caller's keys (pp_ctx_set_rng_keys), staged for the table kernel

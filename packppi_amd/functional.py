@@ -114,9 +114,19 @@ def add_hydrogens(batch, SC_D=None, link=None):
 def clashscore(batch, SC_D=None, link=None, rotatable="skip", cut=0.4, hb_allow=0.6, radius=None, want_partners=True):
     """All-atom clashscore of every complex with placed hydrogens (``lib.Context.clashscore``, pp_clashscore), on
     the geometry plan: at the angles ``SC_D`` (through atom14), else at the batch's X.  Padded, packed and decoy batches alike.  Not
-    MolProbity's number: no flips, no optimisation of rotatable hydrogens, this package's radius table."""
+    MolProbity's number: this package's radius table; flips and rotatable hydrogens are optimised by ``optimize_hydrogens``, not here."""
     return _ctx_for(batch).clashscore(chi=SC_D, link=link, rotatable=rotatable, cut=cut, hb_allow=hb_allow, radius=radius,
                                       want_partners=want_partners)
+
+
+def optimize_hydrogens(batch, SC_D=None, link=None, max_sweeps=32, hb_weak=2.5, hb_good=2.2, cut=0.4, hb_allow=0.6, radius=None,
+                       obst_polar=None, want_candidates=False):
+    """Asn / Gln / His flips and rotatable hydrogens chosen on the device (``lib.Context.hbond_optimize``, pp_hnet_optimize; DESIGN.md
+    section 30), on the geometry plan: at the angles ``SC_D`` (flips and rotors), else at the batch's X (rotors alone).  Padded,
+    packed and decoy batches alike.  The result goes to ``Context.clashscore(chi=res.chi, hydrogens=res, rotatable="keep")`` as it
+    is.  Integer counts of overlaps and explicit-hydrogen bonds, not Reduce's dot scores."""
+    return _ctx_for(batch).hbond_optimize(chi=SC_D, link=link, max_sweeps=max_sweeps, hb_weak=hb_weak, hb_good=hb_good, cut=cut,
+                                          hb_allow=hb_allow, radius=radius, obst_polar=obst_polar, want_candidates=want_candidates)
 
 
 def polar_bond_keys(partners, seg_offsets=None):

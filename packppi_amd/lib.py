@@ -23,7 +23,7 @@ SYMBOLS = ("pp_version", "pp_last_error", "pp_build_id", "pp_plan_set_knn_ties",
            "pp_ctx_set_rng_keys", "pp_noise_seeded", "pp_add_noise_seeded", "pp_sample_seeded",
            "pp_sample_partial", "pp_proximal_pinned", "pp_ctx_live_rows", "pp_ensemble_reduce", "pp_ctx_shell",
            "pp_ensemble_recombine", "pp_ctx_set_obstacles", "pp_sasa", "pp_sample_guided", "pp_sample_corrected",
-           "pp_disulfide_close", "pp_polar", "pp_hydrogens", "pp_clashscore")
+           "pp_disulfide_close", "pp_polar", "pp_hydrogens", "pp_clashscore", "pp_hnet_optimize")
 
 
 FIX_MODES = {"hold": 0, "renoise": 1}         # PP_FIX_HOLD, PP_FIX_RENOISE
@@ -165,6 +165,7 @@ def load():
     lib.pp_polar.argtypes = [vp, vp, vp, vp, vp, f, f, vp, vp, vp, vp, vp]
     lib.pp_hydrogens.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.pp_clashscore.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, f, f, vp, vp, vp, vp, vp]
+    lib.pp_hnet_optimize.argtypes = [vp] * 20 + [f] * 6 + [C.c_int] + [vp] * 13
     lib.pp_sample_guided.argtypes = [vp, vp, vp, vp, i, vp, i, i, C.c_uint64, vp, f, vp, vp, vp]
     lib.pp_sample_corrected.argtypes = [vp, vp, vp, vp, i, vp, i, i, C.c_uint64, vp, vp, f, vp, vp, vp, vp]
     _lib = lib
@@ -1066,7 +1067,7 @@ class Context:
         ``disulfides`` (or its result) -- a bonded cysteine has no HG.  ``place`` / ``param``: tables other than ``constants``'.
         Returns an ``EnsembleResult``: ``hxyz`` fp32 [B, L, 13, 3] (0 where there is none), ``hmask`` uint8 [B, L, 13], ``link_prev``
         uint8 [B, L] (the row is peptide-bonded to the row before it) and ``xyz`` (the heavy atoms used).  The k-th hydrogen of a row
-        is ``constants.hydrogen_names[type][k]``.  Rotatable hydrogens (OH, SH, NH3+) sit at a conventional position, not an
+        is ``constants.hydrogen_names[type][k]``.  Rotatable hydrogens (OH, SH, NH3+) sit at a conventional position (``hbond_optimize`` chooses them), not an
         optimised one.  No host synchronisation."""
         dev = self.plan.device
         for k in ("chain_indices", "atom_mask"):
@@ -1146,6 +1147,111 @@ class Context:
         return EnsembleResult(n_clash=n_clash, partners=partners, res=res, seg=seg, clashscore=1000.0 * seg[:, 1].double() / atoms,
                               clashscore_obstacles=1000.0 * (seg[:, 1] + seg[:, 6]).double() / atoms, hxyz=h["hxyz"], hmask=h["hmask"],
                               link_prev=h["link_prev"], xyz=xyz, radius=radius)
+
+    def hnet_tables(self):
+        """The mover tables of ``hbond_optimize`` on the device, made once per context from ``constants``: ``mover`` int32 [21, 4],
+        ``rot`` fp32 [21, 12, 3, 2], ``ext`` fp32 [21], ``flip_chi`` int64 [N] (the index of the chi a flip row turns, -1 on
+        every other row) and ``seg_of_row`` int64 [N]."""
+        if getattr(self, "_hn_tabs", None) is None:
+            dev = self.plan.device
+            up = lambda a, dt: self._own(torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev))
+            fc = -np.ones(21, np.int64)
+            for rn, k in rc.mover_flip_chi.items():
+                fc[rc.resname_to_idx[rn]] = k
+            rt = self._t["residue_type"].reshape(-1)
+            self._hn_tabs = EnsembleResult(mover=up(rc.mover_table, np.int32), rot=up(rc.mover_rotor_cs, np.float32),
+                                           ext=up(rc.mover_extent, np.float32),
+                                           seg_of_row=up(np.repeat(np.arange(self.n_segments), np.diff(self.seg_offsets_host)), np.int64),
+                                           flip_chi=self._own(torch.from_numpy(fc).to(dev)[rt.clamp(0, 20)].contiguous()))
+        return self._hn_tabs
+
+    def hbond_optimize(self, chi=None, xyz=None, link=None, max_sweeps=32, hb_weak=2.5, hb_good=2.2, cut=0.4, hb_allow=0.6, radius=None,
+                       obst_polar=None, want_candidates=False, mover=None):
+        """Optimise the hydrogen-bond network of every segment on the device (pp_hnet_optimize): Asn / Gln / His
+        flips and the rotatable hydrogens (Ser / Thr / Tyr OH, Cys SH, Lys NH3+), by a monotone descent on an integer energy -- 64 per
+        serious overlap of ``clashscore`` minus 2 per good and 1 per weak explicit-hydrogen bond (H ... acceptor within ``hb_good`` A
+        at an angle of at least 120 degrees / within ``hb_weak`` A at 90).  Integer counts, not Reduce's dot scores, no exhaustive
+        clique search, this package's radii.  Coordinates and ``link`` as in ``hydrogens``; flips need ``chi`` (they are chi + pi),
+        with ``xyz`` or the batch's X only rotors are optimised.  ``radius`` [B, L, 27] as in ``clashscore`` (rotatable hydrogens are
+        always kept; radii of the caller's cost one read-back); ``mover``: a table other than ``constants.mover_table``.  Returns
+        an ``EnsembleResult``: ``state`` int32 [B, L] (-1: no mover), ``xyz`` [B, L, 14, 3], ``hxyz`` / ``hmask`` / ``link_prev`` (what ``clashscore(hydrogens=...)`` takes),
+        ``chi`` [B, L, 4] (None without ``chi``), ``e`` int32 [B, L, 2] (the row's energy at the start and at the end), ``hb`` int32
+        [B, L, 2] (its explicit-hydrogen bonds, each bond in one row), ``n_bonds`` / ``n_flips`` int64 [n_segments], ``trace`` int32
+        [n_segments, max_sweeps + 1] (the total energy after each sweep), ``sweeps`` / ``converged`` int32 [n_segments], ``n_movers``
+        int64 [n_segments], and with ``want_candidates`` ``cand`` fp32 [B, L, 12, 3, 3] and ``energy`` int32 [B, L, 12].  No host
+        synchronisation."""
+        import math
+        dev = self.plan.device
+        for name, v in (("cut", cut), ("hb_allow", hb_allow), ("hb_weak", hb_weak), ("hb_good", hb_good)):
+            if not math.isfinite(float(v)):
+                raise ValueError(f"hbond_optimize: {name} must be finite")
+        if float(hb_allow) < 0 or not (0 < float(hb_good) <= float(hb_weak)):
+            raise ValueError("hbond_optimize: hb_allow must not be negative, and 0 < hb_good <= hb_weak")
+        if not (0 <= int(max_sweeps) <= 256):
+            raise ValueError("hbond_optimize: max_sweeps must lie in 0 .. 256")
+        tabs, ht = self.allatom_tables(), self.hnet_tables()
+        if radius is None:
+            radius, r_max = tabs.radius, float(rc.allatom_default_radius.max())
+        else:
+            radius = self._rows(torch.as_tensor(radius), "radius", rc.PP_AA_SLOTS)
+            r_max = float(radius.max())                    # the one read-back, only with radii of the caller's
+        op = getattr(self, "_obst_polar", None) if self.n_obstacles else None
+        if obst_polar is not None:
+            if self.n_obstacles == 0:
+                raise ValueError("hbond_optimize: obst_polar on a context without obstacle atoms")
+            op = (torch.as_tensor(obst_polar).to(device=dev) != 0).to(torch.uint8).reshape(-1).contiguous()
+            if op.numel() != self.n_obstacles:
+                raise ValueError(f"hbond_optimize: obst_polar has {op.numel()} entries, the context holds {self.n_obstacles} obstacle atoms")
+        mv = ht.mover
+        if mover is not None:
+            mv = torch.as_tensor(mover).to(device=dev, dtype=torch.int32).contiguous()
+            if mv.numel() != 21 * 4:
+                raise ValueError("hbond_optimize: mover is a [21, 4] table")
+        link = self._link(link)
+        chi0 = chi1 = chi_out = h1 = None
+        if chi is not None:
+            chi0 = self._chi(chi)
+            fc = ht.flip_chi.reshape(self.B, self.L)
+            turn = torch.nn.functional.one_hot(fc.clamp(min=0), 4).bool() & (fc >= 0)[..., None]
+            flipped = torch.remainder(chi0 + 2.0 * math.pi, 2.0 * math.pi) - math.pi          # chi + pi wrapped into [-pi, pi)
+            chi1 = torch.where(turn, flipped, chi0).contiguous()
+            h0 = self.hydrogens(chi=chi0, link=link)
+            h1 = self.hydrogens(chi=chi1, link=link)
+            chi_out = self._new(self.B, self.L, 4)
+        else:
+            h0 = self.hydrogens(xyz=xyz, link=link)
+        f32 = np.float32
+        reach = max(f32(f32(2.0) * f32(r_max) - f32(cut)), f32(hb_weak))
+        S = rc.PP_AA_SLOTS
+        state = self._new(self.B, self.L, dtype=torch.int32)
+        xyz_out = self._new(self.B, self.L, 14, 3)
+        hxyz_out = self._new(self.B, self.L, rc.PP_H_MAX, 3)
+        hmask_out = self._new(self.B, self.L, rc.PP_H_MAX, dtype=torch.uint8)
+        e = self._new(self.B, self.L, 2, dtype=torch.int32)
+        hb = self._new(self.B, self.L, 2, dtype=torch.int32)
+        trace = self._new(self.n_segments, int(max_sweeps) + 1, dtype=torch.int32)
+        sweeps = self._new(self.n_segments, dtype=torch.int32)
+        converged = self._new(self.n_segments, dtype=torch.int32)
+        cand = self._new(self.B, self.L, 12, 3, 3) if want_candidates else None
+        energy = self._new(self.B, self.L, 12, dtype=torch.int32) if want_candidates else None
+        g = lambda h, k: _ptr(h[k]) if h is not None else None
+        _check(load().pp_hnet_optimize(
+            self.handle, _ptr(h0["xyz"]), _ptr(h0["hxyz"]), _ptr(h0["hmask"]), g(h1, "xyz"), g(h1, "hxyz"), g(h1, "hmask"), _ptr(chi0),
+            _ptr(chi1), _ptr(tabs.place), _ptr(tabs.param), _ptr(mv), _ptr(ht.rot), _ptr(ht.ext), _ptr(radius), _ptr(tabs.acls),
+            _ptr(tabs.aa_sep), _ptr(h0["link_prev"]), _ptr(link), _ptr(op), float(cut), float(hb_allow), float(hb_weak),
+            float(f32(hb_weak) * f32(hb_weak)), float(f32(hb_good) * f32(hb_good)), float(reach), int(max_sweeps), _ptr(state),
+            _ptr(xyz_out), _ptr(hxyz_out), _ptr(hmask_out), _ptr(chi_out), _ptr(e), _ptr(hb), _ptr(trace), _ptr(sweeps), _ptr(converged),
+            _ptr(cand), _ptr(energy), self._stream()), "pp_hnet_optimize")
+        per_seg = lambda rows: torch.zeros(self.n_segments, dtype=torch.int64, device=dev).index_add_(0, ht.seg_of_row, rows.to(torch.int64))
+        n_movers = per_seg(state.reshape(-1) >= 0)
+        flip_row = (ht.flip_chi >= 0) & (state.reshape(-1) == 1)
+        return EnsembleResult(state=state, xyz=xyz_out, hxyz=hxyz_out, hmask=hmask_out, link_prev=h0["link_prev"], chi=chi_out, e=e, hb=hb,
+                              n_bonds=per_seg(hb.reshape(-1, 2)[:, 1]), n_flips=per_seg(flip_row), trace=trace, sweeps=sweeps,
+                              converged=converged, n_movers=n_movers, cand=cand, energy=energy, radius=radius,
+                              # the inputs of the call, for whoever holds the result against them
+                              xyz0=h0["xyz"], hxyz0=h0["hxyz"], hmask0=h0["hmask"], xyz1=h1["xyz"] if h1 is not None else None,
+                              hxyz1=h1["hxyz"] if h1 is not None else None, hmask1=h1["hmask"] if h1 is not None else None,
+                              chi0=chi0, chi1=chi1)
 
     def saturated(self) -> int:
         """Sticky flag word of this context: 0 = clean; bit 0 / bit 1 = a hidden activation was clamped at 65504 in an edge-level /

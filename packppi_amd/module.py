@@ -607,7 +607,20 @@ class TDiffusionModule:
         res = ctx.clashscore(chi=chi, want_partners=False)
         return dict(clashscore=res.clashscore, clashes_interface=res.seg[:, 2])
 
-    def _reduce_ensemble(self, packed, chi, select, return_all, recombine, recombine_sweeps, sasa, polar=False, clashscore=False):
+    @staticmethod
+    def _decoy_hnet(ctx, chi, clashscore):
+        """The hydrogen-bond networks of every segment (decoy) at ``chi`` optimised, ONE ``Context.hbond_optimize``
+        over the packed decoys: ``hnet_bonds`` and ``hnet_flips`` int64 [n_segments] (explicit-hydrogen bonds of the movers, rows
+        flipped) and, with ``clashscore``, ``clashscore_hnet`` fp64 [n_segments]: the score of the optimised structure with the
+        rotatable hydrogens counted."""
+        res = ctx.hbond_optimize(chi=chi)
+        out = dict(hnet_bonds=res.n_bonds, hnet_flips=res.n_flips)
+        if clashscore:
+            out["clashscore_hnet"] = ctx.clashscore(chi=res.chi, hydrogens=res, rotatable="keep", want_partners=False).clashscore
+        return out
+
+    def _reduce_ensemble(self, packed, chi, select, return_all, recombine, recombine_sweeps, sasa, polar=False, clashscore=False,
+                         hbond_optimize=False):
         """What the two ensemble calls do with the decoys' angles: the per-residue clash, ``Context.ensemble_reduce``, the
         recombination, the buried surface and the polar contacts if asked for; the selected (or recombined) angles, or the
         ``return_all`` dict."""
@@ -622,6 +635,8 @@ class TDiffusionModule:
             extra = dict(extra, bsa=self._decoy_bsa(ctx, chi))
         if clashscore and return_all:
             extra = dict(extra, **self._decoy_clashscore(ctx, chi))
+        if hbond_optimize and return_all:
+            extra = dict(extra, **self._decoy_hnet(ctx, chi, clashscore))
         if not return_all:
             return rec.chi if recombine else res.chi_best
         return dict(decoys=(chi, packed), selected=res.chi_best, best=res.best, dev=res.dev, clash=res.clash, consensus=res.mean,
@@ -629,7 +644,7 @@ class TDiffusionModule:
 
     def sample_ensemble(self, batch, n_decoys, *, seed=None, use_proximal: bool = False, select="clash", return_all: bool = False,
                         recombine: bool = False, recombine_sweeps: int = 64, sasa: bool = False, guide=None, corrector=None,
-                        polar: bool = False, clashscore: bool = False):
+                        polar: bool = False, clashscore: bool = False, hbond_optimize: bool = False):
         """``n_decoys`` seeded samples of every complex in ONE packed pass, reduced on the device.  On
         complexes with obstacle atoms the decoys of a group share the group's obstacles, and the clash that
         ranks them, the proximal stage and the recombination include the overlap with them.  ``batch``: a
@@ -665,6 +680,12 @@ class TDiffusionModule:
         chains, from ONE ``Context.clashscore`` over the packed decoys.  Not MolProbity's number; ranking by it is untuned, so
         ``select`` has no mode for it.
 
+        ``hbond_optimize``: ``return_all`` gains ``hnet_bonds`` and ``hnet_flips`` int64
+        [n_complexes * n_decoys] -- the explicit-hydrogen bonds every decoy's movers make once its flips and rotatable hydrogens
+        are optimised, and the rows flipped, from ONE ``Context.hbond_optimize`` over the packed decoys -- and, with ``clashscore``
+        too, ``clashscore_hnet``: the score of the optimised structure with the rotatable hydrogens counted, beside the
+        conventional one.  The decoys' angles are returned as sampled; nothing is ranked by these.
+
         ``guide``: every decoy is sampled with clash guidance, as ``sampling(guide=...)`` samples the complex
         alone under the decoy's key; None = today's path.  ``corrector``: likewise -- every decoy is a segment and gets
         its own corrector step size, the bits of ``sampling(seed=, corrector=)`` of that complex alone under ``decoy_key``."""
@@ -682,12 +703,12 @@ class TDiffusionModule:
         if _get(packed, "fixed_mask") is not None:
             raise ValueError("ensembles under a fixed_mask are not supported: sample_ensemble samples every row")
         chi = self.sampling(packed, use_proximal=use_proximal, seed=seed, guide=guide, corrector=corrector)
-        return self._reduce_ensemble(packed, chi, select, return_all, recombine, recombine_sweeps, sasa, polar, clashscore)
+        return self._reduce_ensemble(packed, chi, select, return_all, recombine, recombine_sweeps, sasa, polar, clashscore, hbond_optimize)
 
     def repack_ensemble(self, batch, fixed_mask=None, *, n_decoys, seed, fixed_chi=None, fixed_mode="renoise",
                         use_proximal: bool = False, select="clash", return_all: bool = False, recombine: bool = False,
                         recombine_sweeps: int = 64, sasa: bool = False, guide=None, corrector=None, polar: bool = False,
-                        clashscore: bool = False):
+                        clashscore: bool = False, hbond_optimize: bool = False):
         """``sample_ensemble`` under a pin: ``n_decoys`` seeded partial repackings of every complex in ONE packed
         pass, reduced on the device.  ``batch``: a B = 1 batch, or a list of complexes (per-complex data or B = 1 batches).  Every
         complex carries its ``fixed_mask`` (1 = keep; [1, L] on a B = 1 batch, [L] on per-complex data), or ``fixed_mask`` gives it:
@@ -700,7 +721,7 @@ class TDiffusionModule:
         with and without ``use_proximal``.  pp_ensemble_reduce is used unchanged: kept rows are identical in every decoy, so their
         ``resultant`` is 1 to rounding and they add (to rounding) nothing to ``dev``; they enter the per-decoy means of ``dev`` and
         ``clash`` with the same weight in all decoys of a group, so they dilute both equally and do not change the ranking.
-        Returns what ``sample_ensemble`` returns (``sasa``: the ``bsa`` key as there; ``polar``, ``clashscore``: their keys as there).  ``guide``,
+        Returns what ``sample_ensemble`` returns (``sasa``: the ``bsa`` key as there; ``polar``, ``clashscore``, ``hbond_optimize``: their keys as there).  ``guide``,
         ``corrector``: as in ``sampling``."""
         from .batch import Batch, replicate_many
         self._check_select(select)
@@ -737,12 +758,12 @@ class TDiffusionModule:
                              for g, (c, r) in enumerate(zip(complexes, refs)) for _ in range(D)]).unsqueeze(0)
         chi = self.repack(packed, seed=seed, fixed_chi=ref, fixed_mode=fixed_mode, use_proximal=use_proximal,
                           norm_rows=[n for n in sizes for _ in range(D)] if use_proximal else None, guide=guide, corrector=corrector)
-        return self._reduce_ensemble(packed, chi, select, return_all, recombine, recombine_sweeps, sasa, polar, clashscore)
+        return self._reduce_ensemble(packed, chi, select, return_all, recombine, recombine_sweeps, sasa, polar, clashscore, hbond_optimize)
 
     def mutate(self, proteins_and_mutations, *, seed, radius=10.0, shell="ca", n_decoys=1, use_proximal: bool = False,
                select="clash", fixed_mode="renoise", max_rows=200_000, log=print, recombine: bool = False,
                recombine_sweeps: int = 64, sasa: bool = False, guide=None, corrector=None, polar: bool = False,
-               clashscore: bool = False):
+               clashscore: bool = False, hbond_optimize: bool = False):
         """Mutant modelling: put each mutation set into its complex, repack what it touches, return the mutant.
         ``proteins_and_mutations``: a list of ``(protein dict, mutations)`` pairs, ``mutations`` a string ("RA47A,EA48A") or dicts as
         ``featurize.parse_mutstr`` returns them; several sets of one protein are repeated pairs.  Set i of the call gets the noise
@@ -776,6 +797,9 @@ class TDiffusionModule:
 
         ``clashscore``: every dict gains ``clashscore`` fp64 and ``clashes_interface`` int32 [n_decoys], as
         ``sample_ensemble`` describes them.
+
+        ``hbond_optimize``: every dict gains ``hnet_bonds`` and ``hnet_flips`` int64 [n_decoys] and, with
+        ``clashscore`` too, ``clashscore_hnet`` fp64 [n_decoys], as ``sample_ensemble`` describes them.
 
         ``guide``: the shell is sampled with clash guidance, as in ``sampling``; rows outside the shell are
         fixed rows, which are never nudged.  ``corrector``: as in ``sampling``; the rows outside the shell
@@ -814,7 +838,8 @@ class TDiffusionModule:
                 pinned.append(p)
             out = self.repack_ensemble(pinned, n_decoys=n_decoys, seed=seed, fixed_mode=fixed_mode, use_proximal=use_proximal,
                                        select=select, return_all=True, recombine=recombine, recombine_sweeps=recombine_sweeps,
-                                       sasa=sasa, guide=guide, corrector=corrector, polar=polar, clashscore=clashscore)
+                                       sasa=sasa, guide=guide, corrector=corrector, polar=polar, clashscore=clashscore,
+                                       hbond_optimize=hbond_optimize)
             final = out["recombined"] if recombine else out["selected"]
             pos = gctx.atom14(final)
             picks = unpack(pb, out["pick"].reshape(1, -1)) if recombine else [None] * len(members)
@@ -836,6 +861,9 @@ class TDiffusionModule:
                         results[i][k] = out[k][g * n_decoys:(g + 1) * n_decoys]
                 for k in ("clashscore", "clashes_interface") if clashscore else ():
                     results[i][k] = out[k][g * n_decoys:(g + 1) * n_decoys]
+                for k in ("hnet_bonds", "hnet_flips", "clashscore_hnet") if hbond_optimize else ():
+                    if k in out:
+                        results[i][k] = out[k][g * n_decoys:(g + 1) * n_decoys]
         return results
 
     def sample_from(self, batch, SC_D_init, sde_noise=None):
