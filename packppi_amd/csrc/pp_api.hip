@@ -340,10 +340,7 @@ extern "C" void pp_ctx_destroy(pp_ctx *c) {
     }
     for (hipEvent_t e : c->prof_ev) (void)hipEventDestroy(e);
     if (c->obst) (void)hipFree(c->obst);              // waits for the device: only a context that ever held obstacles pays it
-    if (c->ds_ws) (void)hipFree(c->ds_ws);            // likewise: only a context that ever ran pp_disulfide_close
-    if (c->po_ws) (void)hipFree(c->po_ws);            // likewise: only a context that ever ran pp_polar
-    if (c->aa_ws) (void)hipFree(c->aa_ws);            // likewise: only a context that ever ran pp_clashscore
-    if (c->hn_ws) (void)hipFree(c->hn_ws);            // likewise: only a context that ever ran pp_hnet_optimize
+    pp_ctx_free_workspaces(c);                        // likewise: only a context that ever ran one of their entries
     delete c;
 }
 

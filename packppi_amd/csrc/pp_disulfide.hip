@@ -38,6 +38,7 @@
 // call that finds more sets count[s] = -1 for EVERY segment and bonds nothing (partner -1, report 0, chi_out = chi): the call has no
 // read-back, so that is how it fails; packppi_amd.lib raises on it.  Never a silent cut.
 #include "pp_internal.h"
+#include "pp_vec.h"
 #include <algorithm>
 #pragma clang fp contract(off)
 
@@ -51,7 +52,8 @@
 
 __host__ __device__ __forceinline__ float ds_theta(int k) { return (float)(-PP_PI_D + 2.0 * PP_PI_D * (double)k / 72.0); }
 
-__device__ __forceinline__ float ds_dot(const float *a, const float *b) { return ((a[0] * b[0]) + (a[1] * b[1])) + (a[2] * b[2]); }
+__device__ __forceinline__ float ds_dot(const float *a, const float *b) { return pp_dot3(a[0], a[1], a[2], b[0], b[1], b[2]); }
+// pp_cross's operations on arrays: converting to pp_v3 and back at every call would be longer than these three lines
 __device__ __forceinline__ void ds_cross(const float *a, const float *b, float *o) {
     o[0] = (a[1] * b[2]) - (a[2] * b[1]);
     o[1] = (a[2] * b[0]) - (a[0] * b[2]);
@@ -413,11 +415,10 @@ extern "C" pp_status pp_disulfide_close(pp_ctx *c, const float *chi, const uint8
     const size_t o_eidx = 0, o_erow = o_eidx + ds_align(N * 4), o_head = o_erow + ds_align(N * 4), o_tab = o_head + 256,
                  o_ci = o_tab + ds_align(N * DS_TAB * sizeof(float4)), o_ce = o_ci + ds_align((size_t)cap * sizeof(int4)),
                  total = o_ce + ds_align((size_t)cap * sizeof(float2));
-    if (!c->ds_ws) {
-        PP_HIP_CHECK(hipMalloc(&c->ds_ws, total));
-        c->ds_bytes = total;
-    }
-    char *ws = static_cast<char *>(c->ds_ws);
+    // total is a function of N alone (cap is), and N of a context never changes: the helper's size check never fires here
+    void *wsp;
+    if (pp_status rc = pp_ctx_workspace(c, PP_WS_DISULFIDE, total, &wsp)) return rc;
+    char *ws = static_cast<char *>(wsp);
     int32_t *eidx = reinterpret_cast<int32_t *>(ws + o_eidx), *erow = reinterpret_cast<int32_t *>(ws + o_erow),
             *head = reinterpret_cast<int32_t *>(ws + o_head);
     float4 *tab = reinterpret_cast<float4 *>(ws + o_tab);

@@ -1,11 +1,12 @@
 // Hydrogen-bond network optimisation: Asn / Gln / His flips and rotatable hydrogens (no reference kernel).
 // One entry, pp_hnet_optimize, per segment of the context's segment table; nothing crosses segments.  Chemistry is caller data, as
-// for pp_hydrogens / pp_clashscore (csrc/pp_hydrogens.hip, whose slots, class bits, separations and overlap test are used unchanged).
+// for pp_hydrogens / pp_clashscore, whose slots, class bits, separations and NERF are pp_allatom.h's here as there; the overlap test
+// is written out in hn_term as k_clashscore writes it.
 //
 // MOVERS.  mover int32 [21][4] per residue type: (kind, states, bit mask over the 27 all-atom slots of the atoms that move, 0).
 //   kind 1 ROTOR: 1 .. 12 states, at most 3 moved slots, all hydrogens with a NERF entry in `place`.  The j-th moved hydrogen in state c
-//                 is pp_hydrogens' NERF with (c2, s2) = rot [21][12][3][2] at (type, c, j) in place of param's: same operation order,
-//                 fp32, contract off.  State 0 holds param's own values, so it reproduces pp_hydrogens' bits.
+//                 is pp_hydrogens' NERF (the same pp_nerf) with (c2, s2) = rot [21][12][3][2] at (type, c, j) in place of param's.
+//                 State 0 holds param's own values, so it reproduces pp_hydrogens' bits.
 //   kind 2 FLIP:  2 states, at most 7 moved slots.  State c takes the moved slots from (xyz_c, hxyz_c, hmask_c): the caller's two
 //                 coordinate sets, the second at chi + pi.  Without a second set no flip row is a mover.
 // An entry outside these ranges, or a residue_type outside 0 .. 20, is found on the device: the row is no mover and bit 3 of the
@@ -15,8 +16,8 @@
 //
 // ENERGY (int32).  A pair term exists for a moved atom x of mover r at its state against any other counted atom y of the segment that
 // is not a moved atom of r, and against every obstacle atom (r_o > 0) of the segment's range.  fp32, contract off:
-//   excluded  step 5 of pp_clashscore (never for an obstacle)
-//   overlap   steps 1 - 4 (6 for an obstacle) of pp_clashscore, and not excluded
+//   excluded  step 5 of the pair rules of pp_allatom.h (never for an obstacle)
+//   overlap   their steps 1 - 4 (6 for an obstacle), and not excluded
 //   bond      not excluded, x and y in different rows, one a polar hydrogen h (class bit 0) with its parent D (place[..][1]; of a
 //             moved hydrogen: the parent at the same state), the other an acceptor A (class bit 1; an obstacle: obst_polar != 0):
 //             v = A - h, w = D - h, d2 = ((vx vx) + (vy vy)) + (vz vz), s = ((vx wx) + (vy wy)) + (vz wz), ww the same sum of w and w;
@@ -49,33 +50,12 @@
 // in P.  k_hn_finish writes the selection.  Launches: prep, compact, partners, propose x (max_sweeps + 1), apply x max_sweeps, finish;
 // no read-back, no persistent kernel, no spin-wait, no float atomics.
 #include "pp_internal.h"
+#include "pp_allatom.h"
 
 #define HN_T 64
-#define HN_S PP_AA_SLOTS
-#define HN_SAT 8u                      // sticky bit 3, as pp_hydrogens
 #define HN_NP (PP_HNET_MAX_SWEEPS + 1)
 #define HN_CAND (PP_HNET_STATES * PP_HNET_ROT_H)
 
-__device__ __forceinline__ float hn_dot(float ax, float ay, float az, float bx, float by, float bz) {
-#pragma clang fp contract(off)
-    return ((ax * bx) + (ay * by)) + (az * bz);
-}
-struct hn_v3 { float x, y, z; };
-__device__ __forceinline__ hn_v3 hn_unit(hn_v3 v) {
-#pragma clang fp contract(off)
-    const float n = sqrtf(hn_dot(v.x, v.y, v.z, v.x, v.y, v.z));
-    return {v.x / n, v.y / n, v.z / n};
-}
-__device__ __forceinline__ hn_v3 hn_cross(hn_v3 a, hn_v3 b) {
-#pragma clang fp contract(off)
-    return {(a.y * b.z) - (a.z * b.y), (a.z * b.x) - (a.x * b.z), (a.x * b.y) - (a.y * b.x)};
-}
-__device__ __forceinline__ hn_v3 hn_sub(const float *q, hn_v3 p) {
-#pragma clang fp contract(off)
-    return {q[0] - p.x, q[1] - p.y, q[2] - p.z};
-}
-// the larger of two; a NaN sticks
-__device__ __forceinline__ float hn_max(float m, float o) { return (m != m) ? m : ((o != o || o > m) ? o : m); }
 // slot of the j-th set bit of mask (j below its bit count)
 __device__ __forceinline__ int hn_nth_bit(unsigned mask, int j) {
     for (int q = 0; q < j; q++) mask &= mask - 1u;
@@ -89,10 +69,7 @@ struct HnSets {                        // the caller's two coordinate sets; set 
 
 // position and radius-or-0 of moved slot `slot` of flip row n in state c
 __device__ __forceinline__ float4 hn_flip_atom(const HnSets &S, const float *radius, int n, int slot, int c) {
-    const float *src = slot < 14 ? S.xyz[c] + (size_t)n * 42 + 3 * slot : S.hxyz[c] + ((size_t)n * PP_H_MAX + (slot - 14)) * 3;
-    float r = radius[(size_t)n * HN_S + slot];
-    if (!(r > 0.f) || (slot >= 14 && S.hmask[c][(size_t)n * PP_H_MAX + (slot - 14)] == 0)) r = 0.f;
-    return make_float4(src[0], src[1], src[2], r);
+    return pp_aa_atom(S.xyz[c], S.hxyz[c], S.hmask[c], radius, n, slot);
 }
 
 __global__ void __launch_bounds__(256)
@@ -113,7 +90,7 @@ k_hn_prep(int N, HnSets S, const float *__restrict__ radius, const uint8_t *__re
         const int32_t *mt = mover + (size_t)ty * 4;
         kind = mt[0]; ns = mt[1]; mask = (unsigned)mt[2];
         if (kind != 0) {
-            bool bad = kind < 0 || kind > 2 || (mask >> HN_S) != 0u || mask == 0u;
+            bool bad = kind < 0 || kind > 2 || (mask >> AA_S) != 0u || mask == 0u;
             if (kind == 1) bad = bad || ns < 1 || ns > PP_HNET_STATES || (mask & 0x3fffu) != 0u || __popc(mask) > PP_HNET_ROT_H;
             if (kind == 2) bad = bad || ns != 2 || __popc(mask) > PP_HNET_MOVED;
             if (!bad && kind == 1) {
@@ -124,7 +101,7 @@ k_hn_prep(int N, HnSets S, const float *__restrict__ radius, const uint8_t *__re
                 }
             }
             if (bad) {
-                if (a == 0) atomicOr(sat, HN_SAT);
+                if (a == 0) atomicOr(sat, AA_SAT);
                 kind = 0;
             }
         }
@@ -132,45 +109,33 @@ k_hn_prep(int N, HnSets S, const float *__restrict__ radius, const uint8_t *__re
         if (kind == 0) { ns = 0; mask = 0u; }
     }
     const float *ca = S.xyz[0] + (size_t)(rowok ? n : 0) * 42 + 3;
-    float m = -1.f, r = 0.f, px = 0.f, py = 0.f, pz = 0.f;
+    float m = -1.f;
+    float4 at = make_float4(0.f, 0.f, 0.f, 0.f);                // the lane's atom at state 0
     bool any = false;
     int word = 0;
-    const bool live = rowok && a < HN_S;
+    const bool live = rowok && a < AA_S;
     const bool mine = live && ((mask >> a) & 1u) != 0u;        // a moved slot of the row's type
     if (live) {
-        const float *src = a < 14 ? S.xyz[0] + (size_t)n * 42 + 3 * a : S.hxyz[0] + ((size_t)n * PP_H_MAX + (a - 14)) * 3;
-        px = src[0]; py = src[1]; pz = src[2];
-        r = radius[(size_t)n * HN_S + a];
-        if (!(r > 0.f) || (a >= 14 && S.hmask[0][(size_t)n * PP_H_MAX + (a - 14)] == 0)) r = 0.f;
-        if (!tyok) {
-            if (r > 0.f) atomicOr(sat, HN_SAT);
-            r = 0.f;
-        } else {
-            const uint8_t *sp = aa_sep + ((size_t)ty * HN_S + a) * HN_S;
-            const int s0 = sp[0] > 15 ? 15 : sp[0], s2 = sp[2] > 15 ? 15 : sp[2], s5 = sp[5] > 15 ? 15 : sp[5];
-            int par = 0;
-            if (a >= 14) {
-                par = place[((size_t)ty * PP_H_MAX + (a - 14)) * 5 + 1];
-                par = (par < 0 || par > 13) ? 0 : par;          // such a hydrogen was dropped by pp_hydrogens: it is not counted
-            }
-            word = (acls[(size_t)n * HN_S + a] & 15) | (s0 << 4) | (s2 << 8) | (s5 << 12) | (par << 16);
+        at = hn_flip_atom(S, radius, n, a, 0);
+        word = pp_aa_word(at, acls, aa_sep, ty, n, a, sat);
+        if (tyok && a >= 14) {
+            const int par = place[((size_t)ty * PP_H_MAX + (a - 14)) * 5 + 1];
+            word |= ((par < 0 || par > 13) ? 0 : par) << 16;    // such a hydrogen was dropped by pp_hydrogens: it is not counted
         }
-        if (r > 0.f) {
+        if (at.w > 0.f) {
             any = true;
-            const float dx = px - ca[0], dy = py - ca[1], dz = pz - ca[2];
-            m = sqrtf(hn_dot(dx, dy, dz, dx, dy, dz)) + r;
+            m = pp_aa_extent(at, ca);
         }
     }
     // a mover iff a moved slot is counted in state 0
-    int mv = (mine && r > 0.f) ? 1 : 0;
+    int mv = (mine && at.w > 0.f) ? 1 : 0;
     for (int w = 16; w > 0; w >>= 1) mv |= __shfl_xor(mv, w, 32);
     const bool is_mover = mv != 0;
     if (is_mover && kind == 2 && mine) {                        // the other state of a flip
         const float4 q = hn_flip_atom(S, radius, n, a, 1);
         if (q.w > 0.f) {
             any = true;
-            const float dx = q.x - ca[0], dy = q.y - ca[1], dz = q.z - ca[2];
-            m = hn_max(m, sqrtf(hn_dot(dx, dy, dz, dx, dy, dz)) + q.w);
+            m = pp_nanmax(m, pp_aa_extent(q, ca));
         }
     }
     if (is_mover && kind == 1) {                                // every state of a rotor: candidate (c, j) at c * 3 + j
@@ -185,38 +150,23 @@ k_hn_prep(int N, HnSets S, const float *__restrict__ radius, const uint8_t *__re
             const float *cs = rot + (((size_t)ty * PP_HNET_STATES + c) * PP_HNET_ROT_H + j) * 2;
             const float *pr = S.xyz[0] + (size_t)n * 42;
             const int p = pl[1], n1 = pl[2], n2 = pl[3];
-            const hn_v3 Pp = {pr[3 * p], pr[3 * p + 1], pr[3 * p + 2]};
-            const float L = pa[0];
-            const hn_v3 qa = hn_sub(pr + 3 * n1, Pp), qb = hn_sub(pr + 3 * n2, Pp);
-            const hn_v3 e = hn_unit({-qa.x, -qa.y, -qa.z});
-            const hn_v3 nn = hn_unit(hn_cross({qa.x - qb.x, qa.y - qb.y, qa.z - qb.z}, e));
-            const hn_v3 mm = hn_cross(nn, e);
-            const float k0 = -(L * pa[1]), k1 = (L * pa[2]) * cs[0], k2 = (L * pa[2]) * cs[1];
-            const hn_v3 d = {((k0 * e.x) + (k1 * mm.x)) + (k2 * nn.x), ((k0 * e.y) + (k1 * mm.y)) + (k2 * nn.y),
-                             ((k0 * e.z) + (k1 * mm.z)) + (k2 * nn.z)};
+            const pp_v3 Pp = {pr[3 * p], pr[3 * p + 1], pr[3 * p + 2]};
+            const pp_v3 d = pp_nerf(Pp, pr + 3 * n1, pr + 3 * n2, pa[0], pa[1], pa[2], cs[0], cs[1]);
             const float hx = Pp.x + d.x, hy = Pp.y + d.y, hz = Pp.z + d.z;
             candb[(size_t)n * HN_CAND + q] = make_float4(hx, hy, hz, 0.f);
             if (cand_out) {
                 float *o = cand_out + ((size_t)n * HN_CAND + q) * 3;
                 o[0] = hx; o[1] = hy; o[2] = hz;
             }
-            const float rr = radius[(size_t)n * HN_S + 14 + k];
-            if (rr > 0.f) {
-                const float dx = hx - ca[0], dy = hy - ca[1], dz = hz - ca[2];
-                m = hn_max(m, sqrtf(hn_dot(dx, dy, dz, dx, dy, dz)) + rr);
-            }
+            const float rr = radius[(size_t)n * AA_S + 14 + k];
+            if (rr > 0.f) m = pp_nanmax(m, pp_aa_extent(make_float4(hx, hy, hz, rr), ca));
         }
     }
     if (live) {
-        P[(size_t)n * HN_S + a] = make_float4(px, py, pz, r);
-        I[(size_t)n * HN_S + a] = word | ((is_mover && mine) ? (1 << 20) : 0);
+        P[(size_t)n * AA_S + a] = at;
+        I[(size_t)n * AA_S + a] = word | ((is_mover && mine) ? (1 << 20) : 0);
     }
-    for (int w = 16; w > 0; w >>= 1) {
-        const float o = __shfl_xor(m, w, 32);
-        const int oa = __shfl_xor(any ? 1 : 0, w, 32);
-        m = hn_max(m, o);
-        any = any || oa != 0;
-    }
+    pp_aa_row_sphere(m, any);
     if (rowok && a == 0) {
         row[n] = make_float4(ca[0], ca[1], ca[2], any ? m : -1.f);
         meta[n] = is_mover ? (kind | (ns << 4)) : 0;
@@ -254,7 +204,7 @@ __device__ __forceinline__ bool hn_partner(const float4 ci, const float4 cj, flo
 #pragma clang fp contract(off)
     const float b = (ei + ej) + reach;
     const float dx = cj.x - ci.x, dy = cj.y - ci.y, dz = cj.z - ci.z;
-    return hn_dot(dx, dy, dz, dx, dy, dz) <= b * b;
+    return pp_dot3(dx, dy, dz, dx, dy, dz) <= b * b;
 }
 
 __global__ void __launch_bounds__(HN_T)
@@ -295,8 +245,8 @@ __device__ __forceinline__ int hn_term(const float4 p, int xi, const float4 dp, 
                                        bool far, const HnPhys &ph) {
 #pragma clang fp contract(off)
     const float dx = q.x - p.x, dy = q.y - p.y, dz = q.z - p.z;
-    const float d2 = hn_dot(dx, dy, dz, dx, dy, dz);
-    float t = (p.w + q.w) - ph.cut;
+    const float d2 = pp_dot3(dx, dy, dz, dx, dy, dz);
+    float t = (p.w + q.w) - ph.cut;                           // steps 2 - 4 as k_clashscore (pp_hydrogens.hip) writes them
     const bool xh = (xi & 1) && (yi & 2), yh = (xi & 2) && (yi & 1);
     if (xh || yh) t = t - ph.hb_allow;
     int v = (ok && t > 0.f && d2 <= t * t) ? 64 : 0;
@@ -304,7 +254,7 @@ __device__ __forceinline__ int hn_term(const float4 p, int xi, const float4 dp, 
         // v = A - h, w = D - h
         const float vx = xh ? dx : -dx, vy = xh ? dy : -dy, vz = xh ? dz : -dz;
         const float wx = xh ? dp.x - p.x : dq.x - q.x, wy = xh ? dp.y - p.y : dq.y - q.y, wz = xh ? dp.z - p.z : dq.z - q.z;
-        const float s = hn_dot(vx, vy, vz, wx, wy, wz), ww = hn_dot(wx, wy, wz, wx, wy, wz);
+        const float s = pp_dot3(vx, vy, vz, wx, wy, wz), ww = pp_dot3(wx, wy, wz, wx, wy, wz);
         const bool weak = d2 <= ph.hb_weak2 && s <= 0.f;
         const bool good = weak && d2 <= ph.hb_good2 && (s * s) >= 0.25f * (ww * d2);
         v -= good ? 2 : (weak ? 1 : 0);
@@ -326,7 +276,7 @@ k_hn_propose(int N, int n_seg, const int32_t *__restrict__ seg_off, int sweep, c
     __shared__ float4 l_own[PP_HNET_STATES * PP_HNET_MOVED];   // [state][moved atom]: position, radius of a counted atom or 0
     __shared__ float4 l_par[PP_HNET_STATES * PP_HNET_MOVED];   // its parent at that state (hydrogens)
     __shared__ int l_slot[8], l_xi[8];
-    __shared__ uint8_t l_sep[HN_S * HN_S + 7];
+    __shared__ uint8_t l_sep[AA_S * AA_S + 7];
     __shared__ int l_rows[HN_T];
     const int lane = threadIdx.x;
     if ((int)blockIdx.x >= n_movers[0]) return;
@@ -341,12 +291,12 @@ k_hn_propose(int N, int n_seg, const int32_t *__restrict__ seg_off, int sweep, c
     const int nx = __popc(mask);
     {
         const long long ty = rtype[i];                         // a mover: in range
-        for (int q = lane; q < HN_S * HN_S; q += HN_T) l_sep[q] = aa_sep[(size_t)ty * HN_S * HN_S + q];
+        for (int q = lane; q < AA_S * AA_S; q += HN_T) l_sep[q] = aa_sep[(size_t)ty * AA_S * AA_S + q];
     }
     if (lane < nx) {
         const int slot = hn_nth_bit(mask, lane);
         l_slot[lane] = slot;
-        l_xi[lane] = I[(size_t)i * HN_S + slot];
+        l_xi[lane] = I[(size_t)i * AA_S + slot];
     }
     __syncthreads();
     if (lane < ns * nx) {
@@ -355,14 +305,14 @@ k_hn_propose(int N, int n_seg, const int32_t *__restrict__ seg_off, int sweep, c
         const int par = (l_xi[xk] >> 16) & 15;
         if (kind == 1) {
             p = candb[(size_t)i * HN_CAND + c * PP_HNET_ROT_H + xk];
-            const float r = radius[(size_t)i * HN_S + slot];
+            const float r = radius[(size_t)i * AA_S + slot];
             const bool have = S.hmask[0][(size_t)i * PP_H_MAX + (slot - 14)] != 0;
             p.w = (r > 0.f && have) ? r : 0.f;
             if (!have) p = make_float4(0.f, 0.f, 0.f, 0.f);
-            d = P[(size_t)i * HN_S + par];
+            d = P[(size_t)i * AA_S + par];
         } else {
             p = hn_flip_atom(S, radius, i, slot, c);
-            if (slot >= 14) d = ((mask >> par) & 1u) ? hn_flip_atom(S, radius, i, par, c) : P[(size_t)i * HN_S + par];
+            if (slot >= 14) d = ((mask >> par) & 1u) ? hn_flip_atom(S, radius, i, par, c) : P[(size_t)i * AA_S + par];
         }
         l_own[c * PP_HNET_MOVED + xk] = p;
         l_par[c * PP_HNET_MOVED + xk] = d;
@@ -389,7 +339,7 @@ k_hn_propose(int N, int n_seg, const int32_t *__restrict__ seg_off, int sweep, c
             } else if (!(rj.w < 0.f)) {
                 const float bound = (((ri.w + rj.w) + g) * 1.001f) + 0.01f;
                 const float dx = rj.x - ri.x, dy = rj.y - ri.y, dz = rj.z - ri.z;
-                keep = !(hn_dot(dx, dy, dz, dx, dy, dz) > bound * bound);
+                keep = !(pp_dot3(dx, dy, dz, dx, dy, dz) > bound * bound);
             }
         }
         const unsigned long long kept = __ballot(keep);
@@ -399,14 +349,14 @@ k_hn_propose(int N, int n_seg, const int32_t *__restrict__ seg_off, int sweep, c
         const int nr = __popcll(kept);
         for (int r0 = 0; r0 < nr; r0 += 2) {
             const int r = r0 + (lane >> 5), a = lane & 31;
-            const bool valid = r < nr && a < HN_S;
+            const bool valid = r < nr && a < AA_S;
             int jj = i, yi = 0;
             float4 q = make_float4(0.f, 0.f, 0.f, 0.f), dq = q;
             bool rel_next = false, rel_prev = false, rel_ss = false;
             if (valid) {
                 jj = l_rows[r];
-                q = P[(size_t)jj * HN_S + a];
-                yi = I[(size_t)jj * HN_S + a];
+                q = P[(size_t)jj * AA_S + a];
+                yi = I[(size_t)jj * AA_S + a];
                 rel_next = jj == i + 1 && link_prev[jj] != 0;
                 rel_prev = jj == i - 1 && lpi != 0;
                 rel_ss = jj != i && lki == jj && link[jj] == i;       // lki >= 0 only with link
@@ -414,7 +364,7 @@ k_hn_propose(int N, int n_seg, const int32_t *__restrict__ seg_off, int sweep, c
             const bool own = jj == i;
             const bool yok = valid && q.w > 0.f && !(own && ((mask >> a) & 1u));
             if (__ballot(yok) == 0ull) continue;
-            if (yok && (yi & 1)) dq = P[(size_t)jj * HN_S + ((yi >> 16) & 15)];
+            if (yok && (yi & 1)) dq = P[(size_t)jj * AA_S + ((yi >> 16) & 15)];
             const bool lower = ((yi >> 20) & 1) && jj < i;
             const int y0 = (yi >> 4) & 15, y2 = (yi >> 8) & 15, y5 = (yi >> 12) & 15;
             const bool yhyd = (yi & 4) != 0;
@@ -427,12 +377,8 @@ k_hn_propose(int N, int n_seg, const int32_t *__restrict__ seg_off, int sweep, c
                         const float4 p = l_own[c * PP_HNET_MOVED + xk];
                         if (!(p.w > 0.f)) continue;           // the same in every lane
                         const int xi = l_xi[xk], x = l_slot[xk];
-                        int sep = 99;
-                        if (own) sep = l_sep[x * HN_S + (valid ? a : 0)];
-                        if (rel_next) sep = min(sep, ((xi >> 8) & 15) + 1 + y0);
-                        if (rel_prev) sep = min(sep, ((xi >> 4) & 15) + 1 + y2);
-                        if (rel_ss) sep = min(sep, ((xi >> 12) & 15) + 1 + y5);
-                        const bool ok = yok && sep > (((xi & 4) || yhyd) ? 4 : 3);
+                        const int sep = pp_aa_sep(own, rel_next, rel_prev, rel_ss, xi, y0, y2, y5, &l_sep[x * AA_S + (valid ? a : 0)]);
+                        const bool ok = yok && sep > pp_aa_excl((xi & 4) || yhyd);
                         const int v = hn_term(p, xi, l_par[c * PP_HNET_MOVED + xk], q, yi, dq, ok, !own, ph);
                         acc += v;
                         if (c == cur && !lower && (v > 32 ? 64 - v : -v) > 0) nb++;       // v is 64 [overlap] - bond
@@ -546,18 +492,18 @@ k_hn_apply(int N, int n_seg, const int32_t *__restrict__ seg_off, int sweep, con
     if (__ballot(blocked) != 0ull) return;
     const unsigned mask = (unsigned)mmask[i];
     const int kind = meta[i] & 15, c = prop[i];
-    if (lane < HN_S && ((mask >> lane) & 1u)) {
+    if (lane < AA_S && ((mask >> lane) & 1u)) {
         float4 p;
         if (kind == 1) {
             const int j = __popc(mask & ((1u << lane) - 1u));
-            const float r = radius[(size_t)i * HN_S + lane];
+            const float r = radius[(size_t)i * AA_S + lane];
             const bool have = S.hmask[0][(size_t)i * PP_H_MAX + (lane - 14)] != 0;
             p = have ? candb[(size_t)i * HN_CAND + c * PP_HNET_ROT_H + j] : make_float4(0.f, 0.f, 0.f, 0.f);
             p.w = (r > 0.f && have) ? r : 0.f;
         } else {
             p = hn_flip_atom(S, radius, i, lane, c);
         }
-        P[(size_t)i * HN_S + lane] = p;
+        P[(size_t)i * AA_S + lane] = p;
     }
     if (lane == 0) st[i] = c;
 }
@@ -638,23 +584,15 @@ extern "C" pp_status pp_hnet_optimize(pp_ctx *c, const float *xyz0, const float 
     PP_HIP_CHECK(hipSetDevice(c->plan->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (c->N < 1) return PP_OK;
-    const size_t N = (size_t)c->N, n_atoms = N * HN_S;
+    const size_t N = (size_t)c->N, n_atoms = N * AA_S;
     // float4: P [N][27], row [N], candb [N][36];  int32: I [N][27], then [N] each of meta, mmask, st, prop, gain, movers, pcount,
     // plist [N][PCAP], npos [n_seg][HN_NP], n_movers [4]
     const size_t n_f4 = n_atoms + N + N * HN_CAND;
     const size_t n_i32 = n_atoms + 7 * N + N * PP_HNET_PCAP + (size_t)c->B * HN_NP + 4;
     const size_t total = n_f4 * sizeof(float4) + n_i32 * sizeof(int32_t);
-    // as pp_clashscore: N and the segment count of a context never change, so the first call's allocation fits every later one
-    if (c->hn_ws && c->hn_bytes != total) {
-        PP_HIP_CHECK(hipFree(c->hn_ws));
-        c->hn_ws = nullptr;
-        c->hn_bytes = 0;
-    }
-    if (!c->hn_ws) {
-        PP_HIP_CHECK(hipMalloc(&c->hn_ws, total));
-        c->hn_bytes = total;
-    }
-    float4 *P = static_cast<float4 *>(c->hn_ws), *row = P + n_atoms, *candb = row + N;
+    void *ws;
+    if (pp_status rc = pp_ctx_workspace(c, PP_WS_HNET, total, &ws)) return rc;
+    float4 *P = static_cast<float4 *>(ws), *row = P + n_atoms, *candb = row + N;
     int32_t *I = reinterpret_cast<int32_t *>(candb + N * HN_CAND);
     int32_t *meta = I + n_atoms, *mmask = meta + N, *cur = mmask + N, *prop = cur + N, *gain = prop + N, *movers = gain + N;
     int32_t *pcount = movers + N, *plist = pcount + N, *npos = plist + N * PP_HNET_PCAP, *n_movers = npos + (size_t)c->B * HN_NP;

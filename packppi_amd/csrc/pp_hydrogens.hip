@@ -20,24 +20,14 @@
 //   SUM    u_i = unit(q_i - p) for the neighbours in table order;  s = unit((u_1 + u_2) + u_3) (absent ones left out);
 //          H = p - (L s)
 //   T2     u_1, u_2 as above;  b = -unit(u_1 + u_2);  n = unit(u_1 x u_2);  H = p + L ((c1 b) + (s1 n))
-//   NERF   qa = a - p, qb = b - p;  e = unit(-qa);  n = unit((qa - qb) x e);  m = n x e;
-//          H = p + (((k0 e) + (k1 m)) + (k2 n)),  k0 = -(L c1), k1 = (L s1) c2, k2 = (L s1) s2
-//   cross products: (a x b)_x = (ay bz) - (az by), cyclic
+//   NERF   H = p + pp_nerf(...) (pp_allatom.h: the definition, shared with the rotor states of pp_hnet.hip)
+//   dot and cross products, unit: pp_vec.h
 // A hydrogen EXISTS iff atom_mask is not 0 for its parent and for every atom it reads, link_prev[n] holds if it reads the previous
 // C, it is not dropped for link, and all three results are finite (atoms exactly in line give 0 / 0: the hydrogen is dropped).
 // hmask says so; hxyz of a hydrogen that does not exist is 0.
 //
-// pp_clashscore.  Atom (row n, slot a) is COUNTED iff radius[n][a] > 0 and, for a >= 14, hmask[n][a - 14] != 0.  acls bits:
-// 0 polar hydrogen, 1 acceptor, 2 hydrogen, 3 backbone.  Pair (x at p, y at q) of counted atoms of one segment:
-//   1  d = q - p;  d2 = ((dx dx) + (dy dy)) + (dz dz)
-//   2  t = (rx + ry) - cut
-//   3  one a polar hydrogen and the other an acceptor:  t = t - hb_allow
-//   4  SERIOUS OVERLAP iff t > 0 and d2 <= t t   (no root; a NaN makes a comparison false: none)
-//   5  EXCLUDED iff the bond separation is <= 3, or <= 4 when either atom is a hydrogen.  Same row: aa_sep[type][x][y].  Rows i and
-//      i + 1 with link_prev[i + 1]: sep(x, slot 2) + 1 + sep(y, slot 0).  Rows with link[i] == j and link[j] == i: sep(x, slot 5) + 1 +
-//      sep(y, slot 5).  The smallest of those that apply; any other pair of rows is never excluded.
-//   6  OBSTACLE atom o (r_o > 0) of the segment's range against every counted atom: t = (rx + r_o) - cut, minus hb_allow iff x is a
-//      polar hydrogen and obst_polar[o] != 0; no exclusions
+// pp_clashscore.  Which atoms are COUNTED, the acls bits and the pair rules, steps 1 - 6 (serious overlap, excluded pairs, obstacle
+// atoms): pp_allatom.h.  A pair is a hit iff it overlaps (steps 1 - 4) and is not excluded (step 5); obstacle atoms by step 6.
 // Every test is an integer statement about fp32 numbers: a NumPy float32 restatement gives the same words (tests/allatom_oracle.py).
 //
 // OUTPUTS (int32): n_clash [N][27][2] (partner atoms, obstacle atoms: true counts), partners [N][27][PP_CLASH_CAP] (the lowest codes
@@ -57,30 +47,9 @@
 // below the lane.  Per-atom counts live in the lane of the atom's slot, row and segment counts in wave-uniform registers.  The
 // segment sums are integer atomics on a zeroed array; a pair is counted from its lower (row, slot).  No float atomics anywhere.
 #include "pp_internal.h"
+#include "pp_allatom.h"
 
 #define AA_T 64                        // one wave per row
-#define AA_S PP_AA_SLOTS
-#define AA_SAT 8u                      // sticky bit 3: a table entry or residue type out of range
-
-__device__ __forceinline__ float aa_dot(float ax, float ay, float az, float bx, float by, float bz) {
-#pragma clang fp contract(off)
-    return ((ax * bx) + (ay * by)) + (az * bz);
-}
-struct aa_v3 { float x, y, z; };
-__device__ __forceinline__ aa_v3 aa_unit(aa_v3 v) {
-#pragma clang fp contract(off)
-    const float n = sqrtf(aa_dot(v.x, v.y, v.z, v.x, v.y, v.z));
-    return {v.x / n, v.y / n, v.z / n};
-}
-__device__ __forceinline__ aa_v3 aa_cross(aa_v3 a, aa_v3 b) {
-#pragma clang fp contract(off)
-    return {(a.y * b.z) - (a.z * b.y), (a.z * b.x) - (a.x * b.z), (a.x * b.y) - (a.y * b.x)};
-}
-__device__ __forceinline__ aa_v3 aa_sub(const float *q, aa_v3 p) {
-#pragma clang fp contract(off)
-    return {q[0] - p.x, q[1] - p.y, q[2] - p.z};
-}
-__device__ __forceinline__ bool aa_finite(float v) { return __builtin_fabsf(v) <= 3.402823466e38f; }
 
 // 16 lanes per row: lane k < 13 places hydrogen k, lane 13 writes link_prev
 __global__ void __launch_bounds__(256)
@@ -101,7 +70,7 @@ k_hydrogens(int N, int n_seg, const int32_t *__restrict__ seg_off, const float *
     if (n > lo && n < hi && chain[n] == chain[n - 1] && amask[(size_t)(n - 1) * 14 + 2] != 0.f && am[0] != 0.f) {
         const float *pc = pr - 42 + 6;
         const float dx = pc[0] - pr[0], dy = pc[1] - pr[1], dz = pc[2] - pr[2];
-        lp = aa_dot(dx, dy, dz, dx, dy, dz) <= 4.0f;
+        lp = pp_dot3(dx, dy, dz, dx, dy, dz) <= 4.0f;
     }
     if (k == PP_H_MAX) {
         link_prev[n] = lp ? 1 : 0;
@@ -125,11 +94,11 @@ k_hydrogens(int N, int n_seg, const int32_t *__restrict__ seg_off, const float *
                 atomicOr(sat, AA_SAT);
             } else {
                 ok = am[p] != 0.f && !((kind & 16) && link && link[n] >= 0);
-                const aa_v3 P = {pr[3 * p], pr[3 * p + 1], pr[3 * p + 2]};
+                const pp_v3 P = {pr[3 * p], pr[3 * p + 1], pr[3 * p + 2]};
                 const float L = pa[0];
-                aa_v3 d = {0.f, 0.f, 0.f};
+                pp_v3 d = {0.f, 0.f, 0.f};
                 if (how == 1) {
-                    aa_v3 sum = {0.f, 0.f, 0.f};
+                    pp_v3 sum = {0.f, 0.f, 0.f};
                     bool first = true;
                     const int nb[3] = {n1, n2, n3};
 #pragma unroll
@@ -143,33 +112,27 @@ k_hydrogens(int N, int n_seg, const int32_t *__restrict__ seg_off, const float *
                         } else {
                             ok = ok && am[a] != 0.f;
                         }
-                        const aa_v3 u = aa_unit(aa_sub(src, P));
+                        const pp_v3 u = pp_unit(pp_sub(src, P));
                         if (first) sum = u;
                         else sum = {sum.x + u.x, sum.y + u.y, sum.z + u.z};
                         first = false;
                     }
                     ok = ok && !first;
-                    const aa_v3 sdir = aa_unit(sum);
+                    const pp_v3 sdir = pp_unit(sum);
                     d = {-(L * sdir.x), -(L * sdir.y), -(L * sdir.z)};
                 } else if (how == 2) {
                     ok = ok && am[n1] != 0.f && am[n2] != 0.f;
-                    const aa_v3 u1 = aa_unit(aa_sub(pr + 3 * n1, P)), u2 = aa_unit(aa_sub(pr + 3 * n2, P));
-                    const aa_v3 b = aa_unit({u1.x + u2.x, u1.y + u2.y, u1.z + u2.z});
-                    const aa_v3 nn = aa_unit(aa_cross(u1, u2));
+                    const pp_v3 u1 = pp_unit(pp_sub(pr + 3 * n1, P)), u2 = pp_unit(pp_sub(pr + 3 * n2, P));
+                    const pp_v3 b = pp_unit({u1.x + u2.x, u1.y + u2.y, u1.z + u2.z});
+                    const pp_v3 nn = pp_unit(pp_cross(u1, u2));
                     const float c1 = pa[1], s1 = pa[2];
                     d = {L * ((c1 * -b.x) + (s1 * nn.x)), L * ((c1 * -b.y) + (s1 * nn.y)), L * ((c1 * -b.z) + (s1 * nn.z))};
                 } else {
                     ok = ok && am[n1] != 0.f && am[n2] != 0.f;
-                    const aa_v3 qa = aa_sub(pr + 3 * n1, P), qb = aa_sub(pr + 3 * n2, P);
-                    const aa_v3 e = aa_unit({-qa.x, -qa.y, -qa.z});
-                    const aa_v3 nn = aa_unit(aa_cross({qa.x - qb.x, qa.y - qb.y, qa.z - qb.z}, e));
-                    const aa_v3 m = aa_cross(nn, e);
-                    const float k0 = -(L * pa[1]), k1 = (L * pa[2]) * pa[3], k2 = (L * pa[2]) * pa[4];
-                    d = {((k0 * e.x) + (k1 * m.x)) + (k2 * nn.x), ((k0 * e.y) + (k1 * m.y)) + (k2 * nn.y),
-                         ((k0 * e.z) + (k1 * m.z)) + (k2 * nn.z)};
+                    d = pp_nerf(P, pr + 3 * n1, pr + 3 * n2, L, pa[1], pa[2], pa[3], pa[4]);
                 }
                 hx = P.x + d.x; hy = P.y + d.y; hz = P.z + d.z;
-                ok = ok && aa_finite(hx) && aa_finite(hy) && aa_finite(hz);
+                ok = ok && pp_finite(hx) && pp_finite(hy) && pp_finite(hz);
             }
         }
     }
@@ -211,36 +174,15 @@ k_aa_prep(int N, const float *__restrict__ xyz, const float *__restrict__ hxyz, 
     float m = -1.f;
     bool any = false;
     if (live) {
-        const float *src = a < 14 ? xyz + (size_t)n * 42 + 3 * a : hxyz + ((size_t)n * PP_H_MAX + (a - 14)) * 3;
-        const float px = src[0], py = src[1], pz = src[2];
-        float r = radius[(size_t)n * AA_S + a];
-        const long long ty = rtype[n];
-        int word = 0;
-        if (!(r > 0.f) || (a >= 14 && hmask[(size_t)n * PP_H_MAX + (a - 14)] == 0)) r = 0.f;
-        if (ty < 0 || ty > 20) {
-            if (r > 0.f) atomicOr(sat, AA_SAT);
-            r = 0.f;
-        } else {
-            const uint8_t *sp = aa_sep + ((size_t)ty * AA_S + a) * AA_S;
-            const int s0 = sp[0] > 15 ? 15 : sp[0], s2 = sp[2] > 15 ? 15 : sp[2], s5 = sp[5] > 15 ? 15 : sp[5];
-            word = (acls[(size_t)n * AA_S + a] & 15) | (s0 << 4) | (s2 << 8) | (s5 << 12);
-        }
-        P[(size_t)n * AA_S + a] = make_float4(px, py, pz, r);
-        I[(size_t)n * AA_S + a] = word;
-        if (r > 0.f) {
+        float4 p = pp_aa_atom(xyz, hxyz, hmask, radius, n, a);
+        I[(size_t)n * AA_S + a] = pp_aa_word(p, acls, aa_sep, rtype[n], n, a, sat);
+        P[(size_t)n * AA_S + a] = p;
+        if (p.w > 0.f) {
             any = true;
-            const float *ca = xyz + (size_t)n * 42 + 3;
-            const float dx = px - ca[0], dy = py - ca[1], dz = pz - ca[2];
-            m = sqrtf(aa_dot(dx, dy, dz, dx, dy, dz)) + r;
+            m = pp_aa_extent(p, xyz + (size_t)n * 42 + 3);
         }
     }
-    // the largest over the row's 32 lanes; a NaN sticks
-    for (int w = 16; w > 0; w >>= 1) {
-        const float o = __shfl_xor(m, w, 32);
-        const int oa = __shfl_xor(any ? 1 : 0, w, 32);
-        m = (m != m) ? m : ((o != o || o > m) ? o : m);
-        any = any || oa != 0;
-    }
+    pp_aa_row_sphere(m, any);
     if (n < N && a == 0) {
         const float *ca = xyz + (size_t)n * 42 + 3;
         row[n] = make_float4(ca[0], ca[1], ca[2], any ? m : -1.f);
@@ -301,7 +243,7 @@ k_clashscore(int N, int n_seg, const int32_t *__restrict__ seg_off, const float4
                 } else if (!(rj.w < 0.f)) {
                     const float bound = (((ri.w + rj.w) - cut) * 1.001f) + 0.01f;
                     const float dx = rj.x - ri.x, dy = rj.y - ri.y, dz = rj.z - ri.z;
-                    keep = !(aa_dot(dx, dy, dz, dx, dy, dz) > bound * bound);
+                    keep = !(pp_dot3(dx, dy, dz, dx, dy, dz) > bound * bound);
                 }
             }
             const unsigned long long kept = __ballot(keep);
@@ -335,16 +277,12 @@ k_clashscore(int N, int n_seg, const int32_t *__restrict__ seg_off, const float4
                     if (!(p.w > 0.f)) continue;               // the same in every lane
                     const int xi = l_i[x];
                     const float dx = q.x - p.x, dy = q.y - p.y, dz = q.z - p.z;
-                    const float d2 = aa_dot(dx, dy, dz, dx, dy, dz);
-                    float t = (p.w + q.w) - cut;
+                    const float d2 = pp_dot3(dx, dy, dz, dx, dy, dz);
+                    float t = (p.w + q.w) - cut;                  // steps 2 - 4; hn_term (pp_hnet.hip) is the other copy
                     if (((xi & 1) && (yi & 2)) || ((xi & 2) && (yi & 1))) t = t - hb_allow;
-                    int sep = 99;
-                    if (own) sep = l_sep[x * AA_S + (valid ? a : 0)];
-                    if (rel_next) sep = min(sep, ((xi >> 8) & 15) + 1 + y0);
-                    if (rel_prev) sep = min(sep, ((xi >> 4) & 15) + 1 + y2);
-                    if (rel_ss) sep = min(sep, ((xi >> 12) & 15) + 1 + y5);
+                    const int sep = pp_aa_sep(own, rel_next, rel_prev, rel_ss, xi, y0, y2, y5, &l_sep[x * AA_S + (valid ? a : 0)]);
                     const bool hyd = ((xi | yi) & 4) != 0;
-                    const bool hit = yok && !(own && a == x) && sep > (hyd ? 4 : 3) && t > 0.f && d2 <= t * t;
+                    const bool hit = yok && !(own && a == x) && sep > pp_aa_excl(hyd) && t > 0.f && d2 <= t * t;
                     const unsigned long long m = __ballot(hit);
                     if (m != 0ull) {
                         const bool up = jj > i || (own && a > x);
@@ -386,7 +324,7 @@ k_clashscore(int N, int n_seg, const int32_t *__restrict__ seg_off, const float4
                     const float4 p = l_p[x];
                     if (!(p.w > 0.f)) continue;
                     const float dx = o.x - p.x, dy = o.y - p.y, dz = o.z - p.z;
-                    const float d2 = aa_dot(dx, dy, dz, dx, dy, dz);
+                    const float d2 = pp_dot3(dx, dy, dz, dx, dy, dz);
                     float t = (p.w + o.w) - cut;
                     if ((l_i[x] & 1) && pol) t = t - hb_allow;
                     const int cnt = __popcll(__ballot(ook && t > 0.f && d2 <= t * t));
@@ -433,17 +371,9 @@ extern "C" pp_status pp_clashscore(pp_ctx *c, const float *xyz, const float *hxy
     if (c->N < 1) return PP_OK;
     const size_t n_atoms = (size_t)c->N * AA_S;
     const size_t total = n_atoms * (sizeof(float4) + sizeof(int32_t)) + (size_t)c->N * sizeof(float4);
-    // as pp_polar: N of a context never changes, so the first call's allocation fits every later one
-    if (c->aa_ws && c->aa_bytes != total) {
-        PP_HIP_CHECK(hipFree(c->aa_ws));
-        c->aa_ws = nullptr;
-        c->aa_bytes = 0;
-    }
-    if (!c->aa_ws) {
-        PP_HIP_CHECK(hipMalloc(&c->aa_ws, total));
-        c->aa_bytes = total;
-    }
-    float4 *P = static_cast<float4 *>(c->aa_ws), *row = P + n_atoms;
+    void *ws;
+    if (pp_status rc = pp_ctx_workspace(c, PP_WS_ALLATOM, total, &ws)) return rc;
+    float4 *P = static_cast<float4 *>(ws), *row = P + n_atoms;
     int32_t *I = reinterpret_cast<int32_t *>(row + c->N);
     const bool obst = c->obst_M > 0;
     PP_HIP_CHECK(hipMemsetAsync(seg, 0, (size_t)c->B * 8 * sizeof(int32_t), st));

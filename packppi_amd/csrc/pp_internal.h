@@ -137,6 +137,21 @@ struct StepParams {
     float pad[12];
 };
 
+// Lazy workspaces: ONE allocation each outside the arena, made by the first call of its entry on a context (hipMalloc may wait for
+// the device: no other call pays for it), kept for the later ones, freed with the context.  Each is sized from N (pp_hnet_optimize:
+// and the segment count), which never change on a context, so the first call's allocation fits every later one.
+enum {
+    PP_WS_DISULFIDE,          // pp_disulfide_close: tables of the eligible rows, candidate list
+    PP_WS_POLAR,              // pp_polar: [N][14] position + class, [N][14] direction, [N] row sphere
+    PP_WS_ALLATOM,            // pp_clashscore: [N][27] position + radius, [N] row sphere, [N][27] class + separations
+    PP_WS_HNET,               // pp_hnet_optimize: current atoms, rotor candidates, mover and partner lists, per-sweep counters
+    PP_WS_COUNT
+};
+struct pp_workspace {
+    void *p = nullptr;
+    size_t bytes = 0;
+};
+
 struct pp_ctx {
     pp_plan *plan;
     pp_batch b;               // caller-owned device pointers
@@ -195,14 +210,7 @@ struct pp_ctx {
     int32_t *obst_cand;       // [N][PP_OB_CAP] proximal: static obstacle candidates of every residue, ascending (k_obst_cand)
     int32_t *obst_cnt;        // [N] their number, -1 = more than PP_OB_CAP (the residue scans its segment's range)
     float *sasa_row;          // [N][8] pp_sasa: slot 1 (3), bounding radius of the present atoms around it, largest R (k_sasa_rows)
-    void *ds_ws = nullptr;    // pp_disulfide_close: its workspace (tables of the eligible rows, candidate list), sized from N; ONE allocation
-    size_t ds_bytes = 0;      // outside the arena, made by the first call, freed with the ctx (no other call pays for it)
-    void *po_ws = nullptr;    // pp_polar: its workspace ([N][14] position + class, [N][14] direction, [N] row sphere), sized from N; ONE
-    size_t po_bytes = 0;      // allocation outside the arena, made by the first call, freed with the ctx
-    void *aa_ws = nullptr;    // pp_clashscore: its workspace ([N][27] position + radius, [N] row sphere, [N][27] class + separations), sized
-    size_t aa_bytes = 0;      // from N; ONE allocation outside the arena, made by the first call, freed with the ctx
-    void *hn_ws = nullptr;    // pp_hnet_optimize: its workspace (current atoms, rotor candidates, mover and partner lists, per-sweep counters),
-    size_t hn_bytes = 0;      // sized from N and the segment count; ONE allocation outside the arena, made by the first call, freed with the ctx
+    pp_workspace ws[PP_WS_COUNT];   // the lazy workspaces of the analysis entries (pp_ctx_workspace)
     // seeded sampling noise (pp_rng.h): the per-row table of the seeded kernels and the complexes' keys
     pp_rng_row *rng_tab;      // [N] (row within the complex, key of the complex); filled by pp_launch_rng_table
     uint64_t *rng_keys;       // [B] the caller's keys (pp_ctx_set_rng_keys), staged for the table kernel
@@ -237,6 +245,29 @@ void pp_set_error(const std::string &msg);
         pp_set_error(msg);       \
         return code;             \
     } while (0)
+// workspace `which` (PP_WS_*) of the context at exactly `bytes`: the existing allocation if its size matches; one of another size (it
+// cannot arise today) is replaced, not trusted.  Here, not in pp_api.hip, so that tests/native/workspace_sanitize.cpp can compile the
+// two functions against stand-ins for hipMalloc / hipFree
+inline pp_status pp_ctx_workspace(pp_ctx *c, int which, size_t bytes, void **out) {
+    pp_workspace &w = c->ws[which];
+    if (w.p && w.bytes != bytes) {
+        PP_HIP_CHECK(hipFree(w.p));
+        w = {};
+    }
+    if (!w.p) {
+        PP_HIP_CHECK(hipMalloc(&w.p, bytes));
+        w.bytes = bytes;
+    }
+    *out = w.p;
+    return PP_OK;
+}
+// pp_ctx_destroy: hipFree waits for the device, so only a context that ever ran one of these entries pays it
+inline void pp_ctx_free_workspaces(pp_ctx *c) {
+    for (pp_workspace &w : c->ws) {
+        if (w.p) (void)hipFree(w.p);
+        w = {};
+    }
+}
 // what the ensemble calls (`who`: pp_ensemble_reduce, pp_ensemble_recombine) ask of the context: packed or B = 1, and its segments
 // and rows groups of n_decoys (pp_ensemble.hip)
 pp_status pp_check_decoy_groups(const pp_ctx *c, int n_decoys, const char *who);

@@ -34,13 +34,9 @@
 // below the lane, so the lowest PP_POLAR_CAP codes come out ascending without a sort.  All counters are wave-uniform registers.  The
 // segment sums are integer atomics on a zeroed array; each pair is counted from its lower row.  No float atomics anywhere.
 #include "pp_internal.h"
+#include "pp_vec.h"
 
 #define PO_T 64                        // one wave per row
-
-__device__ __forceinline__ float po_dot(float ax, float ay, float az, float bx, float by, float bz) {
-#pragma clang fp contract(off)
-    return ((ax * bx) + (ay * by)) + (az * bz);
-}
 
 // P[n][a] = (x, y, z, class bits), U[n][a] = (u, 0), row[n] = (slot 1, radius of the polar atoms around it or -1)
 __global__ void __launch_bounds__(256)
@@ -80,14 +76,14 @@ k_polar_prep(int N, const float *__restrict__ xyz, const uint8_t *__restrict__ c
         if (c != 0) {
             any = true;
             const float dx = px - pr[3], dy = py - pr[4], dz = pz - pr[5];
-            m2 = po_dot(dx, dy, dz, dx, dy, dz);
+            m2 = pp_dot3(dx, dy, dz, dx, dy, dz);
         }
     }
     // the largest over the row's 16 lanes; a NaN sticks
     for (int w = 8; w > 0; w >>= 1) {
         const float o = __shfl_xor(m2, w, 16);
         const int oa = __shfl_xor(any ? 1 : 0, w, 16);
-        m2 = (m2 != m2) ? m2 : ((o != o || o > m2) ? o : m2);
+        m2 = pp_nanmax(m2, o);
         any = any || oa != 0;
     }
     if (n < N && a == 0) {
@@ -138,7 +134,7 @@ k_polar(int N, int n_seg, const int32_t *__restrict__ seg_off, const float4 *__r
                 if (!(rj.w < 0.f)) {
                     const float bound = (((ri.w + rj.w) + reach) * 1.001f) + 0.01f;
                     const float dx = rj.x - ri.x, dy = rj.y - ri.y, dz = rj.z - ri.z;
-                    keep = !(po_dot(dx, dy, dz, dx, dy, dz) > bound * bound);
+                    keep = !(pp_dot3(dx, dy, dz, dx, dy, dz) > bound * bound);
                 }
             }
             const unsigned long long kept = __ballot(keep);
@@ -171,10 +167,10 @@ k_polar(int N, int n_seg, const int32_t *__restrict__ seg_off, const float4 *__r
                     if (xc == 0) continue;                    // the same in every lane
                     const float4 u = l_u[x];
                     const float dx = q.x - p.x, dy = q.y - p.y, dz = q.z - p.z;
-                    const float d2 = po_dot(dx, dy, dz, dx, dy, dz);
-                    const float sx = po_dot(u.x, u.y, u.z, dx, dy, dz);
+                    const float d2 = pp_dot3(dx, dy, dz, dx, dy, dz);
+                    const float sx = pp_dot3(u.x, u.y, u.z, dx, dy, dz);
                     const float ex = p.x - q.x, ey = p.y - q.y, ez = p.z - q.z;
-                    const float sy = po_dot(uq.x, uq.y, uq.z, ex, ey, ez);
+                    const float sy = pp_dot3(uq.x, uq.y, uq.z, ex, ey, ez);
                     const bool da = ((xc & 1) && (yc & 2)) || ((xc & 2) && (yc & 1));
                     const bool skip = adj && (x == 0 || x == 3);
                     const bool hb = da && !skip && d2 <= hb2 && sx <= 0.f && sy <= 0.f;
@@ -229,7 +225,7 @@ k_polar(int N, int n_seg, const int32_t *__restrict__ seg_off, const float4 *__r
                     const float4 p = l_p[x];
                     if (__float_as_int(p.w) == 0) continue;
                     const float dx = o.x - p.x, dy = o.y - p.y, dz = o.z - p.z;
-                    n_ob[x] += __popcll(__ballot(pol && po_dot(dx, dy, dz, dx, dy, dz) <= hb2));
+                    n_ob[x] += __popcll(__ballot(pol && pp_dot3(dx, dy, dz, dx, dy, dz) <= hb2));
                 }
             }
         }
@@ -279,18 +275,9 @@ extern "C" pp_status pp_polar(pp_ctx *c, const float *xyz, const uint8_t *cls, c
     if (c->N < 1) return PP_OK;
     const size_t n_atoms = (size_t)c->N * 14;
     const size_t total = (2 * n_atoms + (size_t)c->N) * sizeof(float4);
-    // N of a context never changes, so the first call's allocation fits every later one; a workspace of another size (it cannot
-    // arise today) is replaced, not trusted.  hipMalloc may wait for the device: only the first call on a context pays that
-    if (c->po_ws && c->po_bytes != total) {
-        PP_HIP_CHECK(hipFree(c->po_ws));
-        c->po_ws = nullptr;
-        c->po_bytes = 0;
-    }
-    if (!c->po_ws) {
-        PP_HIP_CHECK(hipMalloc(&c->po_ws, total));
-        c->po_bytes = total;
-    }
-    float4 *P = static_cast<float4 *>(c->po_ws), *U = P + n_atoms, *row = U + n_atoms;
+    void *ws;
+    if (pp_status rc = pp_ctx_workspace(c, PP_WS_POLAR, total, &ws)) return rc;
+    float4 *P = static_cast<float4 *>(ws), *U = P + n_atoms, *row = U + n_atoms;
     const float hb2 = hb_max * hb_max, sb2 = sb_max * sb_max;
     const float reach = hb_max > sb_max ? hb_max : sb_max;
     const bool obst = obst_polar != nullptr;

@@ -32,15 +32,10 @@
 // k_sasa_seg (one workgroup per segment): the fp64 sums of area over the segment's rows in the fixed binary tree of
 // k_ens_per_decoy.  No float atomics anywhere.
 #include "pp_internal.h"
+#include "pp_vec.h"
 
 #define SA_T 256                       // threads of a workgroup
 #define SA_STEP 16                     // kept rows whose atoms one append step takes: 16 lanes per row, 14 of them with an atom
-
-__device__ __forceinline__ float sa_d2(float px, float py, float pz, float qx, float qy, float qz) {
-#pragma clang fp contract(off)
-    const float dx = px - qx, dy = py - qy, dz = pz - qz;
-    return ((dx * dx) + (dy * dy)) + (dz * dz);
-}
 
 // row[8 n + 0..2] = slot 1, [3] = bounding radius of the present atoms around it (-1: none present), [4] = the largest R
 __global__ void __launch_bounds__(SA_T)
@@ -55,8 +50,9 @@ k_sasa_rows(int N, const float *__restrict__ xyz, const float *__restrict__ radi
         const float r = radius[(size_t)n * 14 + a];
         if (r > 0.f) {
             any = true;
-            const float d2 = sa_d2(p[3 * a], p[3 * a + 1], p[3 * a + 2], p[3], p[4], p[5]);
-            m2 = (d2 > m2 || d2 != d2) ? d2 : m2;           // a NaN sticks: the row is then never pruned
+            const float d2 = pp_d2(p[3 * a], p[3 * a + 1], p[3 * a + 2], p[3], p[4], p[5]);
+            // a NaN sticks: the row is then never pruned.  Not pp_nanmax: that tests the old value first, other instructions for the same value
+            m2 = (d2 > m2 || d2 != d2) ? d2 : m2;
             const float R = r + probe;
             rmax = R > rmax ? R : rmax;
         }
@@ -127,7 +123,7 @@ k_sasa(int N, int n_seg, const int32_t *__restrict__ seg_off, const float *__res
                 int mm = 4;
                 for (int b = 0; b < 14; b++) {
                     const float Rb = l_own[b][3];
-                    if (b != a && Rb > 0.f && sa_d2(x, y, z, l_own[b][0], l_own[b][1], l_own[b][2]) < Rb * Rb) mm = 0;
+                    if (b != a && Rb > 0.f && pp_d2(x, y, z, l_own[b][0], l_own[b][1], l_own[b][2]) < Rb * Rb) mm = 0;
                 }
                 m[u] = mm;
                 if (mm) { qx[u] = x; qy[u] = y; qz[u] = z; }     // a point at class 0 cannot sink further: it rides along as NaN
@@ -143,7 +139,7 @@ k_sasa(int N, int n_seg, const int32_t *__restrict__ seg_off, const float *__res
             const int c = l_cls[e];
 #pragma unroll
             for (int u = 0; u < NU; u++) {
-                const bool hit = sa_d2(qx[u], qy[u], qz[u], o.x, o.y, o.z) < o.w;
+                const bool hit = pp_d2(qx[u], qy[u], qz[u], o.x, o.y, o.z) < o.w;
                 m[u] = (hit && c < m[u]) ? c : m[u];
             }
         }
@@ -163,7 +159,7 @@ k_sasa(int N, int n_seg, const int32_t *__restrict__ seg_off, const float *__res
             const float rad_j = rj[3];
             if (!(rad_j < 0.f)) {
                 const float bound = (((rad_i + rad_j) + (rmax_i + rj[4])) * 1.001f) + 0.01f;
-                keep = !(sa_d2(cx, cy, cz, rj[0], rj[1], rj[2]) > bound * bound);
+                keep = !(pp_d2(cx, cy, cz, rj[0], rj[1], rj[2]) > bound * bound);
             }
         }
         if (keep) l_rows[atomicAdd(&l_nrows, 1)] = j;
@@ -198,7 +194,7 @@ k_sasa(int N, int n_seg, const int32_t *__restrict__ seg_off, const float *__res
                 if (o.w > 0.f) {
                     const float Ro = o.w + probe;
                     const float bound = (((rad_i + rmax_i) + Ro) * 1.001f) + 0.01f;
-                    if (!(sa_d2(cx, cy, cz, o.x, o.y, o.z) > bound * bound)) {
+                    if (!(pp_d2(cx, cy, cz, o.x, o.y, o.z) > bound * bound)) {
                         will = true;
                         const int e = atomicAdd(&l_n, 1);
                         l_atom[e] = make_float4(o.x, o.y, o.z, Ro * Ro);

@@ -32,14 +32,9 @@
 // with a computed d2 < r2: not one output byte changes.  A NaN or infinite radius or CA makes the comparison false and the pair is
 // tested in full.  A row without a present atom is in no ATOM shell and seeds none; it is dropped where the list is made.
 #include "pp_internal.h"
+#include "pp_vec.h"
 
 #define SH_T 256        // threads of a workgroup = rows it decides = seed candidates it looks at per pass
-
-__device__ __forceinline__ float sh_d2(float px, float py, float pz, float qx, float qy, float qz) {
-#pragma clang fp contract(off)
-    const float dx = px - qx, dy = py - qy, dz = pz - qz;
-    return ((dx * dx) + (dy * dy)) + (dz * dz);
-}
 
 // present-atom bits of a row and its bounding radius around slot 1 (-1: no atom present)
 __device__ __forceinline__ unsigned sh_row_atoms(const float *__restrict__ xyz, const float *__restrict__ amask, int n, float &rad) {
@@ -49,7 +44,7 @@ __device__ __forceinline__ unsigned sh_row_atoms(const float *__restrict__ xyz, 
     for (int a = 0; a < 14; a++)
         if (amask[(size_t)n * 14 + a] != 0.f) {
             bits |= 1u << a;
-            const float d2 = sh_d2(p[3 * a], p[3 * a + 1], p[3 * a + 2], p[3], p[4], p[5]);
+            const float d2 = pp_d2(p[3 * a], p[3 * a + 1], p[3 * a + 2], p[3], p[4], p[5]);
             m2 = (d2 > m2 || d2 != d2) ? d2 : m2;           // a NaN sticks: the pair is then never pruned
         }
     rad = bits ? sqrtf(m2) : -1.f;
@@ -127,7 +122,7 @@ k_shell(int N, int n_seg, const int32_t *__restrict__ seg_off, const uint8_t *__
             for (int e = 0; e < cnt; e++) {
                 if (l_seg[e] != my_seg) continue;
                 if (chain && l_chain[e] == my_chain) continue;
-                const float dca2 = sh_d2(cx, cy, cz, l_ca[e][0], l_ca[e][1], l_ca[e][2]);
+                const float dca2 = pp_d2(cx, cy, cz, l_ca[e][0], l_ca[e][1], l_ca[e][2]);
                 if (!ATOM) {
                     if (dca2 < r2) { hit = true; break; }
                     continue;
@@ -141,7 +136,7 @@ k_shell(int N, int n_seg, const int32_t *__restrict__ seg_off, const uint8_t *__
                     const float qx = q[3 * b2], qy = q[3 * b2 + 1], qz = q[3 * b2 + 2];
 #pragma unroll
                     for (int a2 = 0; a2 < (ATOM ? 14 : 1); a2++)
-                        if (((my_bits >> a2) & 1u) && sh_d2(ax[a2][0], ax[a2][1], ax[a2][2], qx, qy, qz) < r2) hit = true;
+                        if (((my_bits >> a2) & 1u) && pp_d2(ax[a2][0], ax[a2][1], ax[a2][2], qx, qy, qz) < r2) hit = true;
                 }
                 if (hit) break;
             }

@@ -208,6 +208,18 @@ def test_few_sweeps(max_sweeps):
         st = host(res.state, -1)
         assert ((st == 0) | (st == -1)).all()
         assert torch.equal(res.hxyz.reshape(-1), res.hxyz0.reshape(-1)) and torch.equal(res.chi, res.chi0)
+        # rotor state 0 and pp_hydrogens call one pp_nerf: the same words for every rotor hydrogen, and c64 is the smallest fixture
+        # with a Ser, a Tyr and a Lys that have theirs
+        n, rt = st.size, arrays(b)[2]
+        cand, h0 = host(res.cand, n, 12, 3, 3).view(np.int32), host(res.hxyz0, n, 13, 3).view(np.int32)
+        hm, seen = host(res.hmask0, n, 13), set()
+        for r in range(n):
+            kind, _, moved = H.mover_of_type(int(rt[r]))
+            for j, s in enumerate(moved if kind == 1 else ()):
+                if hm[r, s - 14]:
+                    assert np.array_equal(cand[r, 0, j], h0[r, s - 14]), (r, s)
+                    seen.add(rc.resnames[int(rt[r])])
+        assert {"SER", "TYR", "LYS"} <= seen, seen
 
 
 # ---- hand-built cases: obstacle atoms can be put anywhere --------------------------------------------------------------------------------

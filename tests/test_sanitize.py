@@ -2,7 +2,8 @@
 
 What can be compiled without HIP is exactly the host-side logic that handles caller-sized inputs: the restated libstdc++
 selection (csrc/pp_topk_aten.h: pp_topk_aten_host, the kNN tie path) and the checkpoint rewrites (csrc/pp_rebalance.h:
-pp_rebalance_weights_host, pp_plan_create), plus the std:: comparison harness of tests/test_topk_aten.py."""
+pp_rebalance_weights_host, pp_plan_create), plus the std:: comparison harness of tests/test_topk_aten.py.  The lazy workspaces of a
+context (csrc/pp_internal.h) need the HIP headers: hipcc's host pass compiles them, against stand-ins for hipMalloc / hipFree."""
 import ctypes
 import os
 import shutil
@@ -27,6 +28,19 @@ def gxx():
 def test_host_code_under_asan_ubsan(gxx, tmp_path):
     exe = str(tmp_path / "host_sanitize")
     subprocess.run([gxx, *SAN, "-o", exe, os.path.join(ROOT, "tests", "native", "host_sanitize.cpp")], check=True)
+    r = subprocess.run([exe], env=ENV, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0 and r.stdout.startswith("ok:"), r.stdout[-500:] + r.stderr[-3000:]
+    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-3000:]
+
+
+def test_context_workspaces_under_asan_ubsan(tmp_path):
+    """tests/native/workspace_sanitize.cpp: pp_ctx_workspace and the free path of pp_ctx_destroy over stand-ins for hipMalloc /
+    hipFree.  csrc/pp_internal.h needs the HIP headers, so the host compiler is hipcc's (host pass only: no device code, no device)."""
+    from packppi_amd.build import _hipcc
+    exe = str(tmp_path / "workspace_sanitize")
+    san = [a for f in SAN[3:5] for a in ("-Xarch_host", f)]
+    subprocess.run([_hipcc(), "-x", "hip", "--cuda-host-only", *SAN[:3], *san, SAN[5], "-w", "-o", exe,
+                    os.path.join(ROOT, "tests", "native", "workspace_sanitize.cpp")], check=True)
     r = subprocess.run([exe], env=ENV, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and r.stdout.startswith("ok:"), r.stdout[-500:] + r.stderr[-3000:]
     assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-3000:]
