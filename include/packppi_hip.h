@@ -853,6 +853,10 @@ pp_status pp_debug_set_hE(pp_ctx *ctx, const float *src, size_t n);
 pp_status pp_debug_buffer(pp_ctx *ctx, int which, float *dst, size_t n);
 /* the first n_launches launches of pp_score's schedule (embed, NM0, NU0, EU0, NU1, EU1, NU2) */
 pp_status pp_debug_score_prefix(pp_ctx *ctx, const float *chi, float t, int n_launches, void *stream);
+/* out = {R, mixed, n_pairs, cl, multi}: the kernel instances a network evaluation of this context launches -- residues per edge /
+ * node-message workgroup, the mixed pair + single launch and its pair count, workgroups per tile of a middle-layer node update,
+ * the node update's instance for more tiles than CUs.  Asked of the launchers' own predicates (tests/test_launch_boundaries.py). */
+pp_status pp_debug_launch_plan(pp_ctx *ctx, int32_t out[5]);
 void pp_debug_set_dbg(float *p);          /* stamp buffer of the -DPP_LAB -DPP_X_TS builds */
 void pp_debug_set_lds_pad(int bytes);     /* occupancy experiments */
 void pp_debug_set_edge_R(int R);          /* residues per edge workgroup: 1, 2, 0 = automatic */

@@ -335,18 +335,20 @@ def reverse_step(x, score, time, dt, mask, mode="ode", noise=None):
 
 
 def sampling(sd, batch, init_chi, schedule=None, mode="ode", sde_noise=None, hoist=True,
-             zero_self_dihedral=False, trajectory=False):
+             zero_self_dihedral=False, trajectory=False, static=None):
     """Reverse diffusion from ``init_chi`` (TorsionalDiffusion.py:254-280).
 
     ``hoist=True`` evaluates the timestep-invariant graph/edge embedding once (identical
     values, it is a pure function of the backbone); ``hoist=False`` recomputes it every
-    step the way the reference does, which is what the CPU baseline times.
+    step the way the reference does, which is what the CPU baseline times.  ``static``: an
+    ``encode_static`` result of this batch that the caller already holds (several runs on one backbone).
     """
     if schedule is None:
         schedule = torch.linspace(1, 0, 31)
     B, L = batch["residue_type"].shape
     x = init_chi.clone()
-    static = encode_static(sd, batch, zero_self_dihedral) if hoist else None
+    if static is None and hoist:
+        static = encode_static(sd, batch, zero_self_dihedral)
     m1 = batch["chi_1pi_periodic_mask"].reshape(-1, 4)
     m2 = batch["chi_2pi_periodic_mask"].reshape(-1, 4)
     traj = []

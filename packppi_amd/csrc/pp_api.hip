@@ -1138,6 +1138,23 @@ extern "C" pp_status pp_debug_score_prefix(pp_ctx *c, const float *chi, float t,
     }
     return st;
 }
+// Which kernel instances the launches of a network evaluation run for this context's row count, from the launchers' own
+// predicates: out = {R, mixed, n_pairs, cl, multi} -- residues per edge / node-message workgroup, the mixed pair + single launch and
+// its pair count (0 when not mixed), workgroups per tile of a middle-layer node update, the node update's more-tiles-than-CUs instance.
+extern "C" pp_status pp_debug_launch_plan(pp_ctx *c, int32_t out[5]) {
+    if (!c || !out) FAIL(PP_ERR_INVALID, "pp_debug_launch_plan: null");
+#ifdef PP_EDGE_F16
+    PP_HIP_CHECK(hipSetDevice(c->plan->device));
+    int R = 0, mixed = 0, n_pairs = 0, cl = 0, multi = 0;
+    pp_status st = pp_edge_launch_plan(c->N, &R, &mixed, &n_pairs);
+    if (st == PP_OK) st = pp_node_launch_plan(c->N, &cl, &multi);
+    if (st != PP_OK) return st;
+    out[0] = R; out[1] = mixed; out[2] = n_pairs; out[3] = cl; out[4] = multi;
+    return PP_OK;
+#else
+    FAIL(PP_ERR_UNSUPPORTED, "pp_debug_launch_plan: the split-f16 edge kernels only");
+#endif
+}
 #endif
 
 // Measurement aid (bench.py): in-situ duration of one hot kernel.  After pp_profile_kernel(ctx, which) every launch of

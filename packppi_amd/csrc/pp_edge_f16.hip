@@ -1336,6 +1336,8 @@ static bool use_mix(int N) {
     if (g_forced_R >= 1 || !g_mix) return false;
     return N > 2 * g_num_cu && N <= 3 * g_num_cu;
 }
+// its two-residue workgroups: residues (2 b, 2 b + 1) for b < mix_pairs(N), the remaining N - 2 mix_pairs(N) get one workgroup each
+static int mix_pairs(int N) { return (N + 2) / 3; }
 
 // resident workgroups per CU the runtime predicts for the two kernels (measurement aid)
 void pp_edge_occupancy(int *node_msg, int *edge_upd) {
@@ -1369,7 +1371,7 @@ pp_status pp_launch_node_message(pp_ctx *c, int layer, hipStream_t s) {
     static const char *nmix_env = PP_GETENV("PP_NM_MIX");
     static const bool nmix = !(nmix_env && atoi(nmix_env) == 0);
     if (nmix && !(nm_R >= 1 && nm_R <= PP_RMAX) && use_mix(c->N)) {
-        A.n_pairs = (c->N + 2) / 3;
+        A.n_pairs = mix_pairs(c->N);
         const int singles = c->N - 2 * A.n_pairs > 0 ? c->N - 2 * A.n_pairs : 0;
         PP_LAUNCH(c, (layer == 0 ? k_node_message_mix<true> : k_node_message_mix<false>), dim3(A.n_pairs + singles), dim3(ET),
                   nm_smem(2), s, A);
@@ -1380,6 +1382,17 @@ pp_status pp_launch_node_message(pp_ctx *c, int layer, hipStream_t s) {
     PP_HIP_CHECK(hipGetLastError());
     return PP_OK;
 }
+
+#ifdef PP_DIAG
+// pp_debug_launch_plan: what the edge update and the node message of N rows would launch
+pp_status pp_edge_launch_plan(int N, int *R, int *mixed, int *n_pairs) {
+    EDGE_ATTR_CHECK()
+    *mixed = use_mix(N) ? 1 : 0;
+    *R = pick_R(N);
+    *n_pairs = *mixed ? mix_pairs(N) : 0;
+    return PP_OK;
+}
+#endif
 
 // true when k_edge_update also computes the next layer's node message
 extern "C" int pp_edge_variant(void) { return 1; }
@@ -1404,7 +1417,7 @@ pp_status pp_launch_edge_update(pp_ctx *c, int layer, bool keep_hE, hipStream_t 
     if (lns && !PP_FUSED) { pp_set_error("pp_launch_edge_update: a plan with LayerNorm operand scales needs the fused build"); return PP_ERR_UNSUPPORTED; }
     if (mixed) {
         // three residues per CU as one two-residue and one one-residue workgroup
-        A.n_pairs = (c->N + 2) / 3;
+        A.n_pairs = mix_pairs(c->N);
         A.mix_mode = g_mix;
         const int singles = c->N - 2 * A.n_pairs > 0 ? c->N - 2 * A.n_pairs : 0;
         // live rows: the table deals M <= N <= 3 C rows out to (M + 2) / 3 pair and M - 2 pairs one-row workgroups (k_live_rows),

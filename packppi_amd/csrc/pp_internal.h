@@ -464,6 +464,11 @@ pp_status pp_launch_correct(pp_ctx *c, float *chi, const uint8_t *fixed, float s
                             double *trace, hipStream_t s);
 
 void pp_edge_occupancy(int *node_msg, int *edge_upd);
+#if defined(PP_DIAG) && defined(PP_EDGE_F16)
+// pp_debug_launch_plan: the launchers' own choices for a context of N rows (pp_edge_f16.hip pick_R / use_mix / mix_pairs, pp_node.hip nu_shape)
+pp_status pp_edge_launch_plan(int N, int *R, int *mixed, int *n_pairs);
+pp_status pp_node_launch_plan(int N, int *cl, int *multi);
+#endif
 
 // last_mode values for pp_launch_node_update
 #define PP_NU_MID 0        // layers 0,1: update + edge-message inputs + next layer's node-message inputs

@@ -1395,6 +1395,27 @@ static pp_status node_attrs() {
     return PP_OK;
 }
 
+// The launch shape of a node update over `tiles` 16-row tiles (after node_attrs()).  multi: more tiles than CUs, the shallow-ring
+// instance.  cl: middle layers of a launch that leaves most CUs idle run 4 (or 2) workgroups per tile, which share out the projections.
+struct NuShape { int cl; bool multi; };
+static NuShape nu_shape(int tiles, int last_mode) {
+    static const char *split_env = PP_GETENV("PP_NU_SPLIT");
+    static const int split_max = split_env ? atoi(split_env) : 4;     // measurement aid: 1 = never
+    const int cl = last_mode != PP_NU_MID ? 1 : (split_max >= 4 && 4 * tiles <= g_nu_cus) ? 4 : (split_max >= 2 && 2 * tiles <= g_nu_cus) ? 2 : 1;
+    return {cl, tiles > g_nu_cus};
+}
+#ifdef PP_DIAG
+// pp_debug_launch_plan: what a middle-layer node update of N rows would launch
+pp_status pp_node_launch_plan(int N, int *cl, int *multi) {
+    pp_status st = node_attrs();
+    if (st != PP_OK) return st;
+    const NuShape shape = nu_shape((N + 15) / 16, PP_NU_MID);
+    *cl = shape.cl;
+    *multi = shape.multi ? 1 : 0;
+    return PP_OK;
+}
+#endif
+
 pp_status pp_launch_node_embed(pp_ctx *c, const float *chi, const StepParams &sp, hipStream_t s) {
     pp_status st = node_attrs();
     if (st != PP_OK) return st;
@@ -1494,12 +1515,10 @@ pp_status pp_launch_node_update(pp_ctx *c, int layer, int last_mode, const NodeE
         }
     }
 #endif
-    const bool multi = (int)grid.x > g_nu_cus;
-    // middle layers of a launch that leaves most CUs idle: 4 (or 2) workgroups per tile share out the projections
-    static const char *split_env = PP_GETENV("PP_NU_SPLIT");
-    static const int split_max = split_env ? atoi(split_env) : 4;     // measurement aid: 1 = never
     const int tiles = (int)grid.x;
-    const int cl = last_mode != PP_NU_MID ? 1 : (split_max >= 4 && 4 * tiles <= g_nu_cus) ? 4 : (split_max >= 2 && 2 * tiles <= g_nu_cus) ? 2 : 1;
+    const NuShape shape = nu_shape(tiles, last_mode);
+    const bool multi = shape.multi;
+    const int cl = shape.cl;
     if (cl > 1) {
         // the tile's workgroups all read the old h_V and one of them writes the new one: into the other buffer, so that a
         // workgroup that starts late (a shared GPU, a busy chip) still reads what it must; the context's pointers swap

@@ -90,7 +90,8 @@ def test_per_layer_states(name, weights):
 
 
 def test_diag_library_runs_the_layer_tests():
-    """One child run of this file (and of the tests that force launch shapes) on libpackppi_hip.dbg.so."""
+    """One child run of this file (and of the tests that force launch shapes, ask for the launch plan or read per-layer tensors at the
+    launch-regime boundaries: test_launch_boundaries.py) on libpackppi_hip.dbg.so."""
     from packppi_amd.build import diag_variant_path
     if os.environ.get("PACKPPI_LIB"):
         pytest.skip("already a child run")
@@ -99,9 +100,11 @@ def test_diag_library_runs_the_layer_tests():
         pytest.skip("libpackppi_hip.dbg.so not built (__graft_entry__.build() builds it)")
     env = dict(os.environ, PACKPPI_LIB=lib, PACKPPI_EXPECT_VARIANT="1")
     r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_hip_layers.py"),
-                        os.path.join(ROOT, "tests", "test_hip_parity.py"), "-q", "-x", "-m", "gpu", "-p", "no:cacheprovider", "-k",
+                        os.path.join(ROOT, "tests", "test_hip_parity.py"), os.path.join(ROOT, "tests", "test_launch_boundaries.py"),
+                        "-q", "-x", "-m", "gpu", "-p", "no:cacheprovider", "-k",
                         "test_node_embedding_at_three_times or test_per_layer_states or test_residues_per_workgroup_agree or "
-                        "test_library_variant_is_the_requested_one"],
+                        "test_library_variant_is_the_requested_one or test_launch_plan_names_the_regimes or "
+                        "test_per_layer_states_at_boundaries"],
                        env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-1000:]
     assert " passed" in r.stdout and "skipped" not in r.stdout.splitlines()[-1], r.stdout[-500:]

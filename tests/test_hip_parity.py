@@ -988,8 +988,11 @@ def test_fp32_variant_library():
     env = dict(os.environ, PACKPPI_LIB=lib, PACKPPI_EXPECT_VARIANT="0" if lib.endswith(".f32.so") else "1")
     sel = ("test_library_variant_is_the_requested_one or test_graph or test_network or test_sampling_ode or test_sampling_sde "
            "or test_T1124_100_steps or test_S1500_100_steps or test_sampling_is_bit_reproducible or test_packed_batch or test_knn_ties "
-           "or test_checkpoint_outside_the_f16_range or test_weight_range_envelope_T1124")
-    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(root, "tests", "test_hip_parity.py"), "-q", "-x", "-m", "gpu",
+           "or test_checkpoint_outside_the_f16_range or test_weight_range_envelope_T1124 "
+           # test_launch_boundaries.py: every test that runs on the default library
+           "or test_boundary_network_and_sampling or test_boundary_sde or test_small_ends or test_masked_rows or test_arccos_edges")
+    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(root, "tests", "test_hip_parity.py"),
+                        os.path.join(root, "tests", "test_launch_boundaries.py"), "-q", "-x", "-m", "gpu",
                         "-k", sel, "-p", "no:cacheprovider"], env=env, cwd=root, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-1000:]
     assert " passed" in r.stdout
