@@ -782,6 +782,59 @@ pp_status pp_hnet_optimize(pp_ctx *ctx, const float *xyz0 /* DEVICE [N,14,3] */,
                            int32_t *converged /* DEVICE [n_seg] */, float *cand /* DEVICE [N][12][3][3] or NULL */,
                            int32_t *energy /* DEVICE [N][12] or NULL */, void *stream);
 
+/* ---- All-atom chi refinement (no reference kernel; csrc/pp_refine.hip holds the arithmetic) -------------------
+ * Lowers, per segment of the ctx's segment table, the explicit-hydrogen overlap energy by small steps in chi space: a monotone
+ * descent on an integer energy, 64 per LEVEL of overlap (level >= 1 is pp_clashscore's serious overlap; each further `band` A of
+ * depth is one more level, up to `bands`) minus pp_hnet_optimize's 2 / 1 per good / weak explicit-hydrogen bond.  A residue without
+ * a serious overlap is never moved.  Caller data:
+ *   chi0    DEVICE [N][4]: the angles to start from
+ *   fixed   DEVICE uint8 [N] or NULL: rows that do not move (the caller ORs bridged cysteines into it)
+ *   place, param, radius, acls, aa_sep, link, obst_polar, cut, hb_allow   as for pp_hydrogens / pp_clashscore (a rotatable hydrogen
+ *           the caller does not want counted has radius 0)
+ *   ext     DEVICE float [21]: no side-chain atom behind CB or hydrogen on it is farther from CA than this, at any angles
+ *   delta, max_steps   the step in radians; a state is steps int8 [4] with |steps[j]| <= max_steps (1 .. PP_REFINE_MAX_STEPS,
+ *           max_steps delta < pi) and angle j = chi0[j] for steps[j] == 0, else chi0[j] + steps[j] delta wrapped into [-pi, pi)
+ *   bands, band   1 .. PP_REFINE_MAX_BANDS levels, `band` A apart
+ *   hb_weak, hb_weak2, hb_good2, reach   as for pp_hnet_optimize
+ * A row is a MOVER iff residue_mask != 0, an SC_D_mask entry != 0, it is not fixed and its residue_type lies in 0 .. 20.  Per sweep a
+ * mover with a term of level >= 1 proposes the best of its current state and one step up or down on each chi it has (at most
+ * PP_REFINE_CAND candidates; coordinates by pp_atom14 and pp_hydrogens themselves, bit for bit); accept rule, partners, trace and
+ * convergence as for pp_hnet_optimize: the total energy F drops by exactly the sum of the accepted gains.  max_sweeps sweeps are
+ * enqueued (0 .. PP_REFINE_MAX_SWEEPS).  Outputs on the device, no read-back:
+ *   chi_out, steps   the angles and the state of every row; a row that did not move keeps the caller's bits, steps 0
+ *   xyz_out, hxyz_out, hmask_out, link_prev   pp_atom14 and pp_hydrogens at chi_out
+ *   e[n]             E of the row at the start and at the end (0 for a row that is no mover)
+ *   trace[s][k], sweeps[s], converged[s]   as for pp_hnet_optimize
+ *   cand_xyz [9][N][14][3], cand_hxyz [9][N][13][3], cand_hmask [9][N][13], cand_mask int32 [N]   all NULL or none: the candidates
+ *                    of the first sweep (candidate 0 the input, 1 + 2j / 2 + 2j one step up / down on chi j; one that does not exist
+ *                    repeats candidate 0) and the bit mask of those that exist (0 for a row that is no mover)
+ *   energy           DEVICE int32 [N][9] or NULL: E of the row at every candidate of the first sweep (0 where there is none)
+ * Table entries out of range are handled as by pp_hydrogens (bit 3 of pp_ctx_saturated).  The first call on a ctx allocates the
+ * workspace (sized from N and the segment count), which may wait for the device; pp_ctx_destroy frees it.  Geometry-only plans work.
+ * Never waits for the stream.
+ * PP_ERR_INVALID: a null ctx, table, chi0 or output other than cand_* / energy; part of the cand_* group; delta not finite and
+ * positive, max_steps outside 1 .. PP_REFINE_MAX_STEPS or max_steps delta >= pi; bands outside 1 .. PP_REFINE_MAX_BANDS, band not
+ * finite and positive; cut, hb_allow, the bond lengths and reach as pp_hnet_optimize; max_sweeps outside 0 .. PP_REFINE_MAX_SWEEPS;
+ * a batch without X, BB_D, chain_indices, residue_type, atom_mask, residue_mask or SC_D_mask; obst_polar on a ctx without obstacles. */
+#define PP_REFINE_CAND 9
+#define PP_REFINE_MOVED 22
+#define PP_REFINE_PCAP 16
+#define PP_REFINE_MAX_SWEEPS 256
+#define PP_REFINE_MAX_STEPS 16
+#define PP_REFINE_MAX_BANDS 8
+pp_status pp_chi_refine(pp_ctx *ctx, const float *chi0 /* DEVICE [N][4] */, const uint8_t *fixed /* DEVICE [N] or NULL */,
+                        const int8_t *place /* DEVICE [21][13][5] */, const float *param /* DEVICE [21][13][5] */,
+                        const float *ext /* DEVICE [21] */, const float *radius /* DEVICE [N][27] */,
+                        const uint8_t *acls /* DEVICE [N][27] */, const uint8_t *aa_sep /* DEVICE [21][27][27] */,
+                        const int32_t *link /* DEVICE [N] or NULL */, const uint8_t *obst_polar /* DEVICE [M] or NULL */, float delta,
+                        int max_steps, int bands, float band, float cut, float hb_allow, float hb_weak, float hb_weak2, float hb_good2,
+                        float reach, int max_sweeps, float *chi_out /* DEVICE [N][4] */, int8_t *steps /* DEVICE [N][4] */,
+                        float *xyz_out /* DEVICE [N,14,3] */, float *hxyz_out /* DEVICE [N][13][3] */,
+                        uint8_t *hmask_out /* DEVICE [N][13] */, uint8_t *link_prev /* DEVICE [N] */, int32_t *e /* DEVICE [N][2] */,
+                        int32_t *trace /* DEVICE [n_seg][max_sweeps + 1] */, int32_t *sweeps /* DEVICE [n_seg] */,
+                        int32_t *converged /* DEVICE [n_seg] */, float *cand_xyz, float *cand_hxyz, uint8_t *cand_hmask,
+                        int32_t *cand_mask, int32_t *energy /* DEVICE [N][9] or NULL */, void *stream);
+
 /* Measurement aid, no reference counterpart: average duration (ms) of one launch of a hot kernel
  * (which: 0 = node-message kernel, 1 = edge-update kernel), timed with HIP events on `stream`
  * around `iters` launches.  Synchronises the stream. */

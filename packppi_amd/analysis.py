@@ -259,6 +259,48 @@ def hnet_csv(residue_type, state, e, chain, residue_index):
     return "\n".join(lines) + "\n"
 
 
+REFINE_CSV_HEADER = "chain,residue,name,steps_chi1,steps_chi2,steps_chi3,steps_chi4,rotation_deg,e_before,e_after"
+
+
+def refine_csv(residue_type, steps, deltas_deg, e, chain, residue_index):
+    """The text of ``refine.csv``: one line per residue ``Context.refine_allatom`` moved -- chain, residue number, residue name, the
+    steps taken on each chi as ``round1/round2/...`` (a step of round r is ``deltas_deg[r]`` degrees), the total rotation in degrees
+    (the sum of |steps| x delta over rounds and angles) and the row's energy before and after.  ``steps`` [rounds, n, 4], ``e`` [n, 2]."""
+    from . import constants as rc
+    steps = np.asarray(steps, dtype=np.int64).reshape(len(deltas_deg), -1, 4)
+    e = np.asarray(e, dtype=np.int64).reshape(-1, 2)
+    lines = [REFINE_CSV_HEADER]
+    for r, aa in enumerate(residue_type):
+        if r >= steps.shape[1] or not steps[:, r].any():
+            continue
+        cols = ["/".join(str(int(v)) for v in steps[:, r, j]) for j in range(4)]
+        rot = sum(abs(int(v)) * float(d) for d, row in zip(deltas_deg, steps[:, r]) for v in row)
+        lines.append(f"{chain[r]},{int(residue_index[r])},{rc.resnames[int(aa)]},{','.join(cols)},{rot:.1f},{int(e[r, 0])},{int(e[r, 1])}")
+    return "\n".join(lines) + "\n"
+
+
+def refine_summary(res, row=0):
+    """The summary line of the command lines for segment ``row`` of a ``Context.refine_allatom`` result."""
+    lo_hi = res.F[row].cpu().tolist()
+    return (f"----- all-atom refinement: energy {lo_hi[0]} -> {lo_hi[1]}, sweeps per round {res.sweeps[:, row].cpu().tolist()}"
+            f"{'' if bool(res.converged[:, row].all()) else ' (not converged)'} -----")
+
+
+def write_refine(path, protein, res, seg=0, first_row=0):
+    """``refine.csv`` at ``path`` from what ``Context.refine_allatom`` returned: the rows of ``protein`` are rows ``first_row`` ... of the
+    result (0 for a B = 1 batch; a decoy's first row in a packed one) and ``seg`` is their segment; prints the summary."""
+    n = len(protein["aaindex"])
+    R = res.steps.shape[0]
+    steps = res.steps.reshape(R, -1, 4)[:, first_row:first_row + n].cpu().numpy()
+    steps = np.concatenate([steps, np.zeros((R, n - steps.shape[1], 4), steps.dtype)], 1)     # trailing rows a packed batch dropped
+    e = res.e.reshape(-1, 2)[first_row:first_row + n].cpu().numpy()
+    e = np.concatenate([e, np.zeros((n - e.shape[0], 2), e.dtype)], 0)
+    with open(path, "w") as fh:
+        fh.write(refine_csv(protein["aaindex"], steps, [float(np.rad2deg(d)) for d in res.deltas], e, protein["chain_id"],
+                            protein["residue_index"]))
+    print(refine_summary(res, seg))
+
+
 def hnet_summary(res, row=0):
     """The summary line of the command lines for segment ``row`` of a ``Context.hbond_optimize`` result."""
     st = res.state.reshape(-1)

@@ -43,6 +43,9 @@ sampling -- behind every reverse step but the last, from time T of the schedule 
 evaluation and a Langevin step of signal-to-noise ratio SNR with a step size per complex.  0.16 is the reference's constant
 (step_correct); nothing here is tuned against a trained checkpoint.  Needs --seed; combines with --repack, --n_decoys, --guide and
 --use_proximal.  Writes corrector.csv (step, t, complex or decoy, s2, n2, eps, amp; empty where no corrector ran).
+--refine_allatom (without it every output byte as before): the side chains are refined in chi space against
+the explicit-hydrogen overlaps, behind the proximal stage and the disulfide closure and in front of --hnet; refine.csv lists the moved
+residues, with --n_decoys every decoy is refined and ensemble.csv gains refine_moved, refine_F_before and refine_F_after.
 --clashscore / --hydrogens (without them every output byte as before): --clashscore writes clashes.csv for the
 written structure -- one line per serious all-atom overlap with placed hydrogens (atoms named as in hbonds.csv, distance, overlap in
 A, kept | gained | lost against the input's own side chains) -- and prints the clashscore (with the input's own beside it);
@@ -255,6 +258,7 @@ def write_ensemble(model, batch, protein, args, analysis):
                                 **(dict(hbond_optimize=True) if getattr(args, "hnet", False) else {}), **args.guide_kw)
     chi, packed = out["decoys"]
     best = int(out["best"][0])
+    args.refine_rows = (packed.seg_offsets_host[best], best)       # --refine_allatom: the selected decoy's first row and segment
     dev, clash = out["dev"].cpu().tolist(), out["clash"].cpu().tolist()
     print(f"----- {args.n_decoys} decoys in one packed pass; selected decoy {best} ({args.select}) -----")
     xyz = get_atom14_coords(packed.X, packed.residue_type, packed.BB_D, chi).cpu().squeeze(0).numpy()
@@ -278,6 +282,9 @@ def write_ensemble(model, batch, protein, args, analysis):
         score, face = (out["clashscore"].cpu().tolist(), out["clashes_interface"].cpu().tolist()) if aa else (None, None)
         hcols = [k for k in ("hnet_bonds", "hnet_flips", "clashscore_hnet") if k in out] if getattr(args, "hnet", False) else []
         hvals = [out[k].cpu().tolist() for k in hcols]
+        if "refine_moved" in out:
+            hcols += ["refine_moved", "refine_F_before", "refine_F_after"]
+            hvals += [out["refine_moved"].cpu().tolist(), out["refine_F"][:, 0].cpu().tolist(), out["refine_F"][:, 1].cpu().tolist()]
         fh.write("decoy,key,dev,clash,selected" + (",bsa" if args.sasa else "") + "".join("," + k for k in pcols)
                  + (",clashscore,clashes_interface" if aa else "") + "".join("," + k for k in hcols) + "\n")
         for d, key in enumerate(out["keys"]):
@@ -410,6 +417,13 @@ def add_allatom_arguments(p):
                    "Cys and Lys.  structure.pdb takes the flipped angles, structure_H.pdb (--hydrogens) the optimised hydrogens, hnet.csv "
                    "holds one line per mover, and the --clashscore summary gains the score with the rotatable hydrogens counted, before "
                    "and after.  Integer counts of overlaps and bonds, not Reduce's dot scores.")
+    p.add_argument("--refine_allatom", action="store_true", default=argparse.SUPPRESS, help="Refine the side chains in chi space against "
+                   "the explicit-hydrogen overlaps --clashscore counts, on the device (DESIGN.md section 32), behind the proximal stage and "
+                   "the disulfide closure and in front of --hnet: small steps on one chi at a time, a residue without a serious overlap "
+                   "keeps its angles.  structure.pdb takes the refined angles, refine.csv holds one line per moved residue, the "
+                   "--clashscore summary gains the score before and after, and with --n_decoys ensemble.csv gains refine_moved, "
+                   "refine_F_before and refine_F_after.  Kept rows (--repack) and bonded cysteines stay.  Step sizes and bands are "
+                   "starting values, not tuned ones.")
 
 
 def optimise_hnet(batch, protein, outdir, chi, link=None, name="hnet.csv"):
@@ -426,13 +440,14 @@ def optimise_hnet(batch, protein, outdir, chi, link=None, name="hnet.csv"):
 
 
 def write_allatom(batch, protein, outdir, chi, clashscore=False, hydrogens=False, native=False, link=None, head="", obstacle_lines=(),
-                  names=("clashes.csv", "structure_H.pdb"), hnet=None):
+                  names=("clashes.csv", "structure_H.pdb"), hnet=None, unrefined=None):
     """--clashscore / --hydrogens: clashes.csv and structure_H.pdb of the B = 1 ``batch`` at the angles ``chi`` [1, n, 4] (n < L: as in
     ``write_sasa``), and the summary line.  ``native``: the input has side chains of its own -- clashes.csv marks every overlap kept,
     gained or lost against them and the summary gives the input's own score.  ``link``: the partner array of the run's disulfide
     closure.  ``head`` / ``obstacle_lines``: what the written structure carries around its ATOM records.  ``hnet``: what
     ``optimise_hnet`` returned for ``chi`` before its flips went into it -- structure_H.pdb then takes the optimised hydrogens, and the
-    summary gains the score with the rotatable hydrogens counted, conventional and optimised."""
+    summary gains the score with the rotatable hydrogens counted, conventional and optimised.  ``unrefined``: the angles [1, n, 4]
+    --refine_allatom started from -- the summary gains the score before and after it."""
     from ..analysis import write_clashes, write_structure_h
     from ..functional import _ctx_for
     chi = chi.to(batch.SC_D.device)
@@ -442,6 +457,14 @@ def write_allatom(batch, protein, outdir, chi, clashscore=False, hydrogens=False
     if clashscore:
         h = ctx.clashscore(chi=chi, link=link)
         write_clashes(os.path.join(outdir, names[0]), protein, h, 0, ctx.clashscore(link=link) if native else None)
+        if unrefined is not None:
+            was = unrefined.to(batch.SC_D.device)
+            if was.shape[1] != batch.SC_D.shape[1]:
+                was = torch.cat([was, batch.SC_D[:, was.shape[1]:]], 1)
+            before = ctx.clashscore(chi=was, link=link, want_partners=False)
+            after = h if hnet is None else ctx.clashscore(chi=hnet.chi0, link=link, want_partners=False)
+            print(f"----- clashscore {float(before.clashscore[0]):.2f} before, {float(after.clashscore[0]):.2f} after the all-atom "
+                  f"refinement (--refine_allatom) -----")
         if hnet is not None:
             conv = ctx.clashscore(chi=hnet.chi0, link=link, rotatable="keep", want_partners=False)
             opt = ctx.clashscore(chi=hnet.chi, link=link, hydrogens=hnet, rotatable="keep", want_partners=False)
@@ -485,6 +508,10 @@ def evaluate_model(model, args):
         args.guide_kw["disulfides"] = disulfides
         batch["residue_names"] = residue_names(protein)        # so that a refusal names the residue, not the row
     model.keep_disulfide_report = disulfides is not None
+    refine_on = getattr(args, "refine_allatom", False)
+    if refine_on:
+        args.guide_kw["refine_allatom"] = True
+        model.keep_refine_report, model.refine_reports = True, []
     fixed = None
     if args.repack is not None:
         from ..selection import device_selector, interface_selection, parse_selection, sasa_selection
@@ -513,6 +540,13 @@ def evaluate_model(model, args):
         # a hidden activation reached the f16 maximum in the split-f16 dense layers: not the reference's arithmetic any more
         print("----- WARNING: f16 saturation in the score network (flag %d); run `python -m packppi_amd.rangecheck` on this "
               "checkpoint -----" % model.saturated())
+    unrefined = None
+    if refine_on:
+        from ..analysis import write_refine
+        rep = model.refine_reports[-1]
+        first = args.refine_rows[0] if args.n_decoys is not None else 0
+        unrefined = rep.chi0.reshape(1, -1, 4)[:, first:first + SC_D_sample.shape[1]]
+        write_refine(os.path.join(args.outdir, "refine.csv"), protein, rep, args.refine_rows[1] if args.n_decoys is not None else 0, first)
     hnet = None
     if getattr(args, "hnet", False):
         # with --n_decoys structure.pdb stays the selected decoy's file; hnet.csv and structure_H.pdb describe its optimised network
@@ -535,7 +569,7 @@ def evaluate_model(model, args):
         link = model.disulfide_reports[-1]["partner"] if disulfides is not None else None
         write_allatom(batch, protein, args.outdir, SC_D_sample, getattr(args, "clashscore", False), getattr(args, "hydrogens", False),
                       native=contains_sidechains(args.input), link=link, head=ssbond, obstacle_lines=args.obstacle_lines,
-                      **(dict(hnet=hnet) if hnet is not None else {}))
+                      **(dict(hnet=hnet) if hnet is not None else {}), **(dict(unrefined=unrefined) if unrefined is not None else {}))
     if contains_sidechains(args.input):
         metric = analysis.get_metric(true_pdb=args.input, pred_pdb=analysis.tmp_pdb)
         print(f"----- Metric: ----- {metric}")

@@ -24,6 +24,10 @@ buries.
 --hnet (without it every output byte as before): every mutant's hydrogen-bond network is optimised on the
 device -- ``mutant_<tag>.pdb`` takes the flips, ``mutant_<tag>_H.pdb`` the optimised hydrogens, ``hnet_<tag>.csv`` lists the movers and
 mutants.csv gains hnet_bonds and hnet_flips (with --clashscore also clashscore_hnet) of the selected decoy.
+--refine_allatom (without it every output byte as before): the shell rows of every decoy are refined in chi
+space against the explicit-hydrogen overlaps behind the pinned stage; mutants.csv gains refine_moved, refine_F_before and
+refine_F_after of the selected decoy, ``refine_<tag>.csv`` lists the residues its refinement moved, and the --clashscore summary
+gains the score before and after.
 --clashscore / --hydrogens (without them every output byte as before): next to every ``mutant_<tag>.pdb`` a
 ``clashes_<tag>.csv`` (every serious all-atom overlap with placed hydrogens; mutants.csv gains the columns clashscore and
 clashes_interface of the selected decoy) and a ``mutant_<tag>_H.pdb`` (the mutant plus the placed hydrogens).  Not MolProbity's score.
@@ -85,11 +89,13 @@ def evaluate_model(model, args):
     pcols = ("hbonds", "hbonds_interface", "salt_interface") + (("buns_interface",) if args.sasa else ()) if polar else ()
     allatom, with_h, hnet_on = getattr(args, "clashscore", False), getattr(args, "hydrogens", False), getattr(args, "hnet", False)
     hcols = (("hnet_bonds", "hnet_flips") + (("clashscore_hnet",) if allatom else ())) if hnet_on else ()
+    refine_on = getattr(args, "refine_allatom", False)
     results = model.mutate([(protein, s) for s in sets], seed=args.seed, radius=args.radius, shell=args.shell,
                            n_decoys=args.n_decoys, use_proximal=args.use_proximal, select=args.select, fixed_mode=args.fixed_mode,
                            **(dict(recombine=True, recombine_sweeps=args.recombine_sweeps) if args.recombine else {}),
                            **(dict(sasa=True) if args.sasa else {}), **(dict(polar=True) if polar else {}), **(dict(clashscore=True) if allatom else {}),
-                           **(dict(hbond_optimize=True) if hnet_on else {}), **(dict(guide=guide) if guide is not None else {}),
+                           **(dict(hbond_optimize=True) if hnet_on else {}), **(dict(refine_allatom=True) if refine_on else {}),
+                           **(dict(guide=guide) if guide is not None else {}),
                            **(dict(corrector=corrector) if corrector is not None else {}))
     if guide is not None:
         write_guide_csv(model, args.outdir)
@@ -98,13 +104,21 @@ def evaluate_model(model, args):
     ddg = predict_ddg(protein, sets, args) if args.ap_ckpt else None
     rows = ["tag,shell_rows,selected_decoy,clash,dev" + (",clash_recombined,rows_recombined" if args.recombine else "")
             + (",ddg,ddg_inv" if ddg else "") + (",bsa" if args.sasa else "") + "".join("," + k for k in pcols)
-            + (",clashscore,clashes_interface" if allatom else "") + "".join("," + k for k in hcols)]
+            + (",clashscore,clashes_interface" if allatom else "") + "".join("," + k for k in hcols)
+            + (",refine_moved,refine_F_before,refine_F_after" if refine_on else "")]
     for i, (s, r) in enumerate(zip(sets, results)):
         tag = (r["tag"] or s).replace(",", "_")
         b = r["batch"]
         mutant = dict(protein, atom_positions=r["X"][0].cpu().numpy(), atom_mask=b["atom_mask"][0].cpu().numpy(),
                       aaindex=np.where(b["residue_mask"][0].cpu().numpy() > 0, b["residue_type"][0].cpu().numpy(),
                                        np.asarray(protein["aaindex"])))
+        unrefined = None
+        if refine_on:                            # what the selected decoy's refinement did, row by row
+            from ..analysis import refine_csv
+            unrefined = r["refine_chi0"]
+            with open(os.path.join(args.outdir, f"refine_{tag}.csv"), "w") as fh:
+                fh.write(refine_csv(mutant["aaindex"], r["refine_steps"][:, 0].cpu().numpy(), [float(np.rad2deg(d)) for d in r["refine_deltas"]],
+                                    r["refine_e"][0].cpu().numpy(), protein["chain_id"], protein["residue_index"]))
         hnet = None
         if hnet_on:                              # the mutant's file takes the flips of its optimised network
             from .eval_diffusion import optimise_hnet
@@ -138,9 +152,12 @@ def evaluate_model(model, args):
             if allatom:
                 line += f",{float(r['clashscore'][best])!r},{int(r['clashes_interface'][best])}"
             write_allatom(b, mutant, args.outdir, r["SC_D"], allatom, with_h, obstacle_lines=obstacles["lines"] if obstacles else [],
-                          names=(f"clashes_{tag}.csv", f"mutant_{tag}_H.pdb"), **(dict(hnet=hnet) if hnet is not None else {}))
+                          names=(f"clashes_{tag}.csv", f"mutant_{tag}_H.pdb"), **(dict(hnet=hnet) if hnet is not None else {}),
+                          **(dict(unrefined=unrefined) if unrefined is not None else {}))
         for k in hcols:
             line += f",{float(r[k][best])!r}" if k == "clashscore_hnet" else f",{int(r[k][best])}"
+        if refine_on:
+            line += f",{int(r['refine_moved'][best])},{int(r['refine_F'][best, 0])},{int(r['refine_F'][best, 1])}"
         rows.append(line)
         print(f"----- {tag}: {int(r['shell'].sum())} residues repacked, decoy {best} of {args.n_decoys} selected"
               + (f", {int(r['rows_recombined'])} residues recombined from other decoys" if args.recombine else "") + " -----")

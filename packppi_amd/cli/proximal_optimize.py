@@ -11,6 +11,9 @@ does; --repack also takes interface:sasa (the delta-SASA interface of the input,
 surface the obstacle atoms bury; needs --obstacles other than none).
 --hnet (without it every output byte as before): the hydrogen-bond network of the optimised structure is
 optimised on the device -- structure.pdb takes the flips, structure_H.pdb the optimised hydrogens, hnet.csv lists the movers.
+--refine_allatom (without it every output byte as before): behind the proximal stage the side chains are
+refined in chi space against the explicit-hydrogen overlaps (kept rows stay) -- structure.pdb takes the refined angles, refine.csv
+lists the moved residues, the --clashscore summary gains the score before and after.
 --clashscore / --hydrogens (without them every output byte as before): clashes.csv (every serious all-atom
 overlap of the optimised structure with placed hydrogens, kept | gained | lost against the input, and the clashscore of both) and
 structure_H.pdb, as eval_diffusion writes them.  Not MolProbity's score.
@@ -107,6 +110,19 @@ def main(argv=None):
     if args.sasa:
         from .eval_diffusion import write_sasa
         write_sasa(batch, protein, args.outdir, SC_D)
+    unrefined = None
+    if getattr(args, "refine_allatom", False):
+        # structure.pdb takes the refined angles; kept rows (--repack) stay
+        import os
+        from ..analysis import write_refine
+        from ..functional import _ctx_for
+        unrefined = SC_D
+        res = _ctx_for(batch).refine_allatom(SC_D, fixed=fixed)
+        write_refine(os.path.join(args.outdir, "refine.csv"), protein, res)
+        SC_D = res.chi[:, :SC_D.shape[1]].to(SC_D.device)
+        refined = dict(protein, atom_positions=get_atom14_coords(batch.X, batch.residue_type, batch.BB_D, SC_D).cpu().squeeze(0).numpy())
+        with open(analysis.tmp_pdb, "w") as fh:
+            fh.writelines(insert_obstacle_lines(to_pdb(refined), obstacles["lines"] if obstacles else []))
     hnet = None
     if getattr(args, "hnet", False):
         # structure.pdb takes the flips: written again at the angles of the optimised network
@@ -119,7 +135,8 @@ def main(argv=None):
     if getattr(args, "clashscore", False) or getattr(args, "hydrogens", False):
         from .eval_diffusion import write_allatom
         write_allatom(batch, protein, args.outdir, SC_D, getattr(args, "clashscore", False), getattr(args, "hydrogens", False),
-                      native=True, obstacle_lines=obstacles["lines"] if obstacles else [], **(dict(hnet=hnet) if hnet is not None else {}))
+                      native=True, obstacle_lines=obstacles["lines"] if obstacles else [], **(dict(hnet=hnet) if hnet is not None else {}),
+                      **(dict(unrefined=unrefined) if unrefined is not None else {}))
     print(f"----- The optimized structure clashscore is {analysis.get_clashscore(analysis.tmp_pdb)} -----")
     print("----- Finishing optimize! -----")
 

@@ -292,6 +292,38 @@ def mover_state_angle(t, state):
     return 180.0 * int(state)
 
 
+# All-atom chi refinement (pp_chi_refine).  The atoms a chi step can move are the atom14 slots 5 .. 13 and
+# every hydrogen whose parent, or one of the atoms it is built from, is such a slot (the hydrogens on CB are built from CG); the
+# kernel derives them from ``hydrogen_place``.  Here only how far from CA they can get.
+
+
+def _refine_extent():
+    ext = np.zeros(21, np.float32)
+    for t in range(20):
+        if not chi_angles_mask[t].any():
+            continue
+        moved = [s for s in range(5, 14) if atom14_names[t][s]]
+        moved += [14 + k for k in range(int(hydrogen_count[t])) if any(5 <= int(v) <= 13 for v in hydrogen_place[t, k, 1:])]
+        # as mover_extent: the way along the bonds from CA to the farthest moved atom, ideal lengths -- without proline's N-CD bond,
+        # which the reconstruction at arbitrary angles does not close
+        dist = {1: 0.0}
+        edges = [(int(a), int(b), float(length)) for rt, a, b, length, _ in bond_rows
+                 if int(rt) == t and length < 1.9 and not (min(int(a), int(b)) == 0 and max(int(a), int(b)) >= 5)]
+        edges += [(int(hydrogen_parent[t, k]), 14 + k, hydrogen_bond_length[atom14_names[t][int(hydrogen_parent[t, k])][0]])
+                  for k in range(int(hydrogen_count[t]))]
+        for _ in range(PP_AA_SLOTS):
+            for a, b, length in edges:
+                for u, v in ((a, b), (b, a)):
+                    if u in dist and dist[u] + length < dist.get(v, 1e9):
+                        dist[v] = dist[u] + length
+        ext[t] = np.float32(max(dist[s] for s in moved))
+    return ext
+
+
+refine_extent = _refine_extent()
+# [21] f32 sum of ideal bond lengths from CA to the farthest atom a chi step can move (0: the type has no chi)
+
+
 @lru_cache(maxsize=16)
 def make_atom14_dists_bounds(overlap_tolerance: float = 1.5,
                              bond_length_tolerance_factor: float = 15.0):

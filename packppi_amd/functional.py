@@ -129,6 +129,17 @@ def optimize_hydrogens(batch, SC_D=None, link=None, max_sweeps=32, hb_weak=2.5, 
                                           hb_allow=hb_allow, radius=radius, obst_polar=obst_polar, want_candidates=want_candidates)
 
 
+def refine_allatom(batch, SC_D, fixed=None, link=None, deltas_deg=(16, 8, 4), max_steps=3, max_sweeps=32, bands=4, band=0.15, cut=0.4,
+                   hb_allow=0.6, hb_weak=2.5, hb_good=2.2, radius=None, obst_polar=None, want_candidates=False):
+    """Side chains refined in chi space against the explicit-hydrogen overlaps ``clashscore`` counts, on the device
+    (``lib.Context.refine_allatom``, pp_chi_refine), on the geometry plan.  Padded, packed and decoy batches
+    alike.  A residue without a serious overlap keeps its angles bit for bit; the defaults are starting values, not tuned against
+    anything.  ``res.chi`` goes to ``clashscore`` / ``optimize_hydrogens`` as it is."""
+    return _ctx_for(batch).refine_allatom(SC_D, fixed=fixed, link=link, deltas_deg=deltas_deg, max_steps=max_steps, max_sweeps=max_sweeps,
+                                          bands=bands, band=band, cut=cut, hb_allow=hb_allow, hb_weak=hb_weak, hb_good=hb_good,
+                                          radius=radius, obst_polar=obst_polar, want_candidates=want_candidates)
+
+
 def polar_bond_keys(partners, seg_offsets=None):
     """The hydrogen bonds behind a ``partners`` array of ``Context.polar`` ([B, L, 14, 4], packed [1, N, 14, 4]) as sorted unique int64
     keys ``(segment * M + low code) * M + high code`` with ``M = 14 * rows`` of the array's second axis, on the device.  A bond is in

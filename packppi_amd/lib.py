@@ -23,7 +23,7 @@ SYMBOLS = ("pp_version", "pp_last_error", "pp_build_id", "pp_plan_set_knn_ties",
            "pp_ctx_set_rng_keys", "pp_noise_seeded", "pp_add_noise_seeded", "pp_sample_seeded",
            "pp_sample_partial", "pp_proximal_pinned", "pp_ctx_live_rows", "pp_ensemble_reduce", "pp_ctx_shell",
            "pp_ensemble_recombine", "pp_ctx_set_obstacles", "pp_sasa", "pp_sample_guided", "pp_sample_corrected",
-           "pp_disulfide_close", "pp_polar", "pp_hydrogens", "pp_clashscore", "pp_hnet_optimize")
+           "pp_disulfide_close", "pp_polar", "pp_hydrogens", "pp_clashscore", "pp_hnet_optimize", "pp_chi_refine")
 
 
 FIX_MODES = {"hold": 0, "renoise": 1}         # PP_FIX_HOLD, PP_FIX_RENOISE
@@ -166,6 +166,7 @@ def load():
     lib.pp_hydrogens.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.pp_clashscore.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, f, f, vp, vp, vp, vp, vp]
     lib.pp_hnet_optimize.argtypes = [vp] * 20 + [f] * 6 + [C.c_int] + [vp] * 13
+    lib.pp_chi_refine.argtypes = [vp] * 11 + [f, i, i] + [f] * 7 + [i] + [vp] * 16
     lib.pp_sample_guided.argtypes = [vp, vp, vp, vp, i, vp, i, i, C.c_uint64, vp, f, vp, vp, vp]
     lib.pp_sample_corrected.argtypes = [vp, vp, vp, vp, i, vp, i, i, C.c_uint64, vp, vp, f, vp, vp, vp, vp]
     _lib = lib
@@ -1252,6 +1253,102 @@ class Context:
                               xyz0=h0["xyz"], hxyz0=h0["hxyz"], hmask0=h0["hmask"], xyz1=h1["xyz"] if h1 is not None else None,
                               hxyz1=h1["hxyz"] if h1 is not None else None, hmask1=h1["hmask"] if h1 is not None else None,
                               chi0=chi0, chi1=chi1)
+
+    def refine_allatom(self, chi, fixed=None, link=None, deltas_deg=(16, 8, 4), max_steps=3, max_sweeps=32, bands=4, band=0.15, cut=0.4,
+                       hb_allow=0.6, hb_weak=2.5, hb_good=2.2, radius=None, obst_polar=None, want_candidates=False):
+        """Refine the side chains of every segment in chi space against the explicit-hydrogen overlaps ``clashscore`` counts, on the
+        device (pp_chi_refine): a monotone descent on an integer energy -- 64 per level of overlap (level 1 is
+        a serious overlap of ``clashscore``, every further ``band`` A of depth one more, up to ``bands``) minus ``hbond_optimize``'s 2
+        / 1 per good / weak explicit-hydrogen bond --, by single steps of +-delta on one chi, at most ``max_steps`` steps from the
+        start on each chi.  A residue without a serious overlap is never moved and keeps its angles bit for bit.  One device call
+        per entry of ``deltas_deg`` (degrees), each starting from the angles of the one before; no angle is read back.  The
+        defaults are starting values, not tuned against anything.  ``fixed`` [B, L]: rows that stay; the bridged cysteines of
+        ``link`` (as in ``hydrogens``) stay too.  Rotatable hydrogens are not counted (``clashscore``'s ``rotatable="skip"``);
+        ``radius`` [B, L, 27] other radii (one read-back), ``obst_polar`` as in ``clashscore``.  Returns an ``EnsembleResult`` that
+        ``clashscore(hydrogens=res)`` and ``clashscore(chi=res.chi)`` / ``hbond_optimize(chi=res.chi)`` take: ``chi`` [B, L, 4],
+        ``xyz`` / ``hxyz`` / ``hmask`` / ``link_prev`` at ``chi``, ``moved`` bool [B, L], ``rotation`` [B, L, 4] (radians, the sum of
+        the steps taken), ``e`` int32 [B, L, 2] (the row's energy at the very start and end), ``F`` int64 [n_segments, 2], and per
+        round (leading dimension ``len(deltas_deg)``) ``steps`` int8 [R, B, L, 4], ``trace`` int32 [R, n_segments, max_sweeps + 1],
+        ``sweeps`` / ``converged`` int32 [R, n_segments], ``e_round`` int32 [R, B, L, 2]; with ``want_candidates`` also ``cand_xyz``
+        [R, 9, B, L, 14, 3], ``cand_hxyz`` [R, 9, B, L, 13, 3], ``cand_hmask`` [R, 9, B, L, 13], ``cand_mask`` int32 [R, B, L],
+        ``cand_chi`` [R, B, L, 4] (the angles each round started from) and ``energy`` int32 [R, B, L, 9]."""
+        import math
+        dev = self.plan.device
+        for name, v in (("cut", cut), ("hb_allow", hb_allow), ("hb_weak", hb_weak), ("hb_good", hb_good), ("band", band)):
+            if not math.isfinite(float(v)):
+                raise ValueError(f"refine_allatom: {name} must be finite")
+        if float(hb_allow) < 0 or not (0 < float(hb_good) <= float(hb_weak)):
+            raise ValueError("refine_allatom: hb_allow must not be negative, and 0 < hb_good <= hb_weak")
+        if not (0 <= int(max_sweeps) <= 256):
+            raise ValueError("refine_allatom: max_sweeps must lie in 0 .. 256")
+        if not (1 <= int(bands) <= 8) or not float(band) > 0:
+            raise ValueError("refine_allatom: bands must lie in 1 .. 8 and band must be positive")
+        deltas = [float(np.float32(np.deg2rad(float(d)))) for d in deltas_deg]
+        if not deltas or not (1 <= int(max_steps) <= 16) or any(not (math.isfinite(d) and d > 0 and int(max_steps) * d < 3.1415) for d in deltas):
+            raise ValueError("refine_allatom: deltas_deg must be positive, max_steps in 1 .. 16 and max_steps * delta below 180 degrees")
+        for k in ("X", "BB_D", "chain_indices", "atom_mask", "residue_mask", "SC_D_mask"):
+            if self._t.get(k) is None:
+                raise RuntimeError(f"refine_allatom needs a batch with {k}")
+        tabs = self.allatom_tables()
+        if getattr(self, "_rf_ext", None) is None:
+            self._rf_ext = self._own(torch.from_numpy(np.ascontiguousarray(rc.refine_extent, dtype=np.float32)).to(dev))
+        if radius is None:
+            cache = self.__dict__.setdefault("_aa_radius", {})
+            if "skip" not in cache:
+                cache["skip"] = self._own((tabs.radius * ~tabs.rotatable).contiguous())
+            radius, r_max = cache["skip"], float(rc.allatom_default_radius.max())
+        else:
+            radius = self._rows(torch.as_tensor(radius), "radius", rc.PP_AA_SLOTS)
+            radius = (radius.reshape(-1, rc.PP_AA_SLOTS) * ~tabs.rotatable).contiguous()
+            r_max = float(radius.max())                    # the one read-back, only with radii of the caller's
+        op = getattr(self, "_obst_polar", None) if self.n_obstacles else None
+        if obst_polar is not None:
+            if self.n_obstacles == 0:
+                raise ValueError("refine_allatom: obst_polar on a context without obstacle atoms")
+            op = (torch.as_tensor(obst_polar).to(device=dev) != 0).to(torch.uint8).reshape(-1).contiguous()
+            if op.numel() != self.n_obstacles:
+                raise ValueError(f"refine_allatom: obst_polar has {op.numel()} entries, the context holds {self.n_obstacles} obstacle atoms")
+        link = self._link(link)
+        fx = self._mask(fixed, "fixed") if fixed is not None else None
+        if link is not None:
+            bridged = (link >= 0).to(torch.uint8)
+            fx = bridged if fx is None else (fx | bridged)
+        f32 = np.float32
+        reach = max(f32(f32(2.0) * f32(r_max) - f32(cut)), f32(hb_weak))
+        R, nseg, ms = len(deltas), self.n_segments, int(max_sweeps)
+        cur = self._chi(chi)
+        chi_in = cur
+        steps = self._new(R, self.B, self.L, 4, dtype=torch.int8)
+        e_round = self._new(R, self.B, self.L, 2, dtype=torch.int32)
+        trace = self._new(R, nseg, ms + 1, dtype=torch.int32)
+        sweeps, converged = self._new(R, nseg, dtype=torch.int32), self._new(R, nseg, dtype=torch.int32)
+        xyz, hxyz = self._new(self.B, self.L, 14, 3), self._new(self.B, self.L, rc.PP_H_MAX, 3)
+        hmask = self._new(self.B, self.L, rc.PP_H_MAX, dtype=torch.uint8)
+        link_prev = self._new(self.B, self.L, dtype=torch.uint8)
+        cx = ch = cm = ck = en = cc = None
+        if want_candidates:
+            cx, ch = self._new(R, 9, self.B, self.L, 14, 3), self._new(R, 9, self.B, self.L, rc.PP_H_MAX, 3)
+            cm = self._new(R, 9, self.B, self.L, rc.PP_H_MAX, dtype=torch.uint8)
+            ck, en = self._new(R, self.B, self.L, dtype=torch.int32), self._new(R, self.B, self.L, 9, dtype=torch.int32)
+            cc = self._new(R, self.B, self.L, 4)
+        at = lambda t, r: _ptr(t[r]) if t is not None else None
+        for r, delta in enumerate(deltas):
+            out = self._new(self.B, self.L, 4)
+            if cc is not None:
+                cc[r].copy_(cur)
+            _check(load().pp_chi_refine(
+                self.handle, _ptr(cur), _ptr(fx), _ptr(tabs.place), _ptr(tabs.param), _ptr(self._rf_ext), _ptr(radius), _ptr(tabs.acls),
+                _ptr(tabs.aa_sep), _ptr(link), _ptr(op), delta, int(max_steps), int(bands), float(band), float(cut), float(hb_allow),
+                float(hb_weak), float(f32(hb_weak) * f32(hb_weak)), float(f32(hb_good) * f32(hb_good)), float(reach), ms, _ptr(out),
+                _ptr(steps[r]), _ptr(xyz), _ptr(hxyz), _ptr(hmask), _ptr(link_prev), _ptr(e_round[r]), _ptr(trace[r]), _ptr(sweeps[r]),
+                _ptr(converged[r]), at(cx, r), at(ch, r), at(cm, r), at(ck, r), at(en, r), self._stream()), "pp_chi_refine")
+            cur = out
+        rotation = sum(steps[r].float() * deltas[r] for r in range(R))          # python scalars: no host table to copy
+        return EnsembleResult(chi=cur, chi0=chi_in, xyz=xyz, hxyz=hxyz, hmask=hmask, link_prev=link_prev, steps=steps,
+                              moved=(steps != 0).any(-1).any(0), rotation=rotation, e=torch.stack([e_round[0, ..., 0], e_round[-1, ..., 1]], -1),
+                              e_round=e_round, F=torch.stack([trace[0, :, 0], trace[-1, :, -1]], -1).to(torch.int64), trace=trace,
+                              sweeps=sweeps, converged=converged, deltas=deltas, radius=radius, fixed=fx, cand_xyz=cx, cand_hxyz=ch,
+                              cand_hmask=cm, cand_mask=ck, cand_chi=cc, energy=en)
 
     def saturated(self) -> int:
         """Sticky flag word of this context: 0 = clean; bit 0 / bit 1 = a hidden activation was clamped at 65504 in an edge-level /

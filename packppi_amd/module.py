@@ -365,7 +365,7 @@ class TDiffusionModule:
 
     def sampling(self, batch, use_proximal: bool = False, return_list: bool = False, sde_noise=None, seed=None,
                  fixed_mask=None, fixed_chi=None, fixed_mode="renoise", return_trajectory: bool = False, guide=None, corrector=None,
-                 disulfides=None):
+                 disulfides=None, refine_allatom: bool = False):
         """``seed`` (an int, None = the reference's behaviour): the initial noising and the sde noise come from the counter-based
         generator on the device (csrc/pp_rng.h) instead of torch's global one.  The noise of a complex is then a function of
         (seed, its key, its rows, the step) alone: the same complex gets the same angles alone, anywhere in a packed batch and
@@ -409,9 +409,16 @@ class TDiffusionModule:
         ``use_proximal`` the bridges are closed first and the proximal stage then runs PINNED on the bonded rows
         (``proximal_optimizer_packed(..., fixed_mask=)``), so that its accept rule cannot reopen one.  Rows of ``fixed_mask`` keep
         their chi1.  A packed or B = 1 batch; excludes ``return_trajectory`` and ``return_list``.  ``keep_disulfide_report`` appends
-        every run's result to ``disulfide_reports``."""
+        every run's result to ``disulfide_reports``.
+
+        ``refine_allatom`` (False = today's code path, untouched): behind the proximal stage and the disulfide
+        closure, ONE ``Context.refine_allatom`` over the rows of the batch lowers the explicit-hydrogen overlaps in chi space.  Rows
+        of ``fixed_mask`` and bonded cysteines stay; a residue without a serious overlap keeps its angles bit for bit.  Excludes
+        ``return_trajectory`` and ``return_list``.  ``keep_refine_report`` appends every run's result to ``refine_reports``."""
         if fixed_mask is None:
             fixed_mask = _get(batch, "fixed_mask")
+        if refine_allatom and (return_trajectory or return_list):
+            raise ValueError("refine_allatom returns the refined angles alone: it excludes return_trajectory and return_list")
         gkw, snr = _sampling_refusals(self.hparams.sample_cfg, self.schedule, batch, use_proximal, return_list, sde_noise, seed,
                                       fixed_mask, fixed_mode, return_trajectory, guide, corrector)
         pairs = _disulfide_refusals(batch, disulfides, return_trajectory, return_list) if disulfides is not None else None
@@ -420,26 +427,47 @@ class TDiffusionModule:
         out = self._run_sampler(ctx, init, sde_noise, seed, pin, return_trajectory, gkw, snr)
         if return_trajectory:
             return out
+        link = None
         if disulfides is not None:
-            return self._disulfide_tail(batch, ctx, out, pairs, fixed_mask, use_proximal)
-        return self._proximal_tail(batch, out, use_proximal, return_list)
+            out, link = self._disulfide_tail(batch, ctx, out, pairs, fixed_mask, use_proximal, want_link=True)
+        else:
+            out = self._proximal_tail(batch, out, use_proximal, return_list)
+        return self._refine_tail(batch, out, fixed_mask, link)[0] if refine_allatom else out
 
-    def _disulfide_tail(self, batch, ctx, chi, pairs, fixed_mask, use_proximal, norm_rows=None):
+    def _refine_tail(self, batch, chi, fixed_mask=None, link=None):
+        """Behind everything else that moves a side chain: ONE ``Context.refine_allatom`` over the rows of ``batch`` (DESIGN.md section
+        32), the rows of ``fixed_mask`` and the bonded cysteines of ``link`` held.  Returns (the refined angles, the result)."""
+        res = self._context(batch).refine_allatom(chi, fixed=fixed_mask, link=link)
+        if getattr(self, "keep_refine_report", False):
+            self.__dict__.setdefault("refine_reports", []).append(res)
+        return res.chi, res
+
+    @staticmethod
+    def _refine_columns(ctx, res):
+        """What ``return_all`` gains from a refinement: ``refine_moved`` int64 [n_segments] (rows moved) and ``refine_F`` int64
+        [n_segments, 2] (the all-atom overlap energy before and after)."""
+        seg_of_row = ctx.hnet_tables().seg_of_row
+        moved = torch.zeros(ctx.n_segments, dtype=torch.int64, device=seg_of_row.device).index_add_(0, seg_of_row, res.moved.reshape(-1).to(torch.int64))
+        return dict(refine_moved=moved, refine_F=res.F)
+
+    def _disulfide_tail(self, batch, ctx, chi, pairs, fixed_mask, use_proximal, norm_rows=None, want_link=False):
         """Behind the sampler of a run with ``disulfides``: close the bridges (``pairs`` None: detect them), then, with
-        ``use_proximal``, the pinned proximal stage on the bonded rows plus the caller's fixed rows."""
+        ``use_proximal``, the pinned proximal stage on the bonded rows plus the caller's fixed rows.  ``want_link``: (angles, the
+        partner array of the closure)."""
         names = _get(batch, "residue_names")
         res = ctx.disulfides(chi=chi, fixed=fixed_mask, pairs=pairs, names=None if names is None else [f"{c}:{n}" for c, n in names])
         if self.keep_disulfide_report:
             self.disulfide_reports.append(dict(partner=res.partner, report=res.report, count=res.count, chi_before=chi,
                                                chi_after=res.chi))
         if not use_proximal:
-            return res.chi
+            return (res.chi, res.partner) if want_link else res.chi
         pinned = (res.partner >= 0).reshape(1, -1)
         if fixed_mask is not None:
             pinned = pinned | (torch.as_tensor(fixed_mask).to(pinned.device) != 0).reshape(1, -1)
         cfg = self.hparams.sample_cfg
-        return proximal_optimizer_packed(batch, res.chi, cfg.violation_tolerance_factor, cfg.clash_overlap_tolerance, cfg.lamda,
-                                         cfg.num_steps, norm_rows=norm_rows, fixed_mask=pinned)[2]
+        out = proximal_optimizer_packed(batch, res.chi, cfg.violation_tolerance_factor, cfg.clash_overlap_tolerance, cfg.lamda,
+                                        cfg.num_steps, norm_rows=norm_rows, fixed_mask=pinned)[2]
+        return (out, res.partner) if want_link else out
 
     def _initial_angles(self, ctx, batch, sde_noise, seed, fixed_mask, fixed_chi, fixed_mode):
         """(the angles noised to t = 1, the sde noise tensor of an unseeded run or None, the pin's keywords or None).  Seeded: the
@@ -525,7 +553,7 @@ class TDiffusionModule:
         return out[0] if isinstance(out, tuple) else out
 
     def repack(self, batch, fixed_mask=None, *, seed, fixed_chi=None, fixed_mode="renoise", use_proximal: bool = False,
-               return_list: bool = False, norm_rows=None, guide=None, corrector=None, disulfides=None):
+               return_list: bool = False, norm_rows=None, guide=None, corrector=None, disulfides=None, refine_allatom: bool = False):
         """Partial repacking in one call (DESIGN.md sections 13 and 14): ``sampling(batch, seed=seed, fixed_mask=...)`` -- the rows
         of ``fixed_mask`` (default ``batch.fixed_mask``) keep ``fixed_chi`` (default ``batch.SC_D``), the others are sampled around
         them -- and then, with ``use_proximal``, the PINNED proximal stage (pp_proximal_pinned): the clash mask of every complex, its
@@ -536,9 +564,12 @@ class TDiffusionModule:
         ``return_list`` (B = 1, with ``use_proximal``): (sample, per-step angles, losses) as ``sampling`` returns them.
         ``guide``: as in ``sampling`` (clash-guided sampling of the free rows); None = today's path.  ``corrector``: as in ``sampling``.
         ``disulfides``: as in ``sampling`` -- a kept row never changes its chi1, a bridge between two kept rows
-        is only reported; the pinned stage then also keeps the bonded rows."""
+        is only reported; the pinned stage then also keeps the bonded rows.
+        ``refine_allatom``: as in ``sampling``, behind the pinned stage; kept rows stay kept."""
         if fixed_mask is None:
             fixed_mask = _get(batch, "fixed_mask")
+        if refine_allatom and return_list:
+            raise ValueError("refine_allatom returns the refined angles alone: it excludes return_list")
         if fixed_mask is None:
             raise ValueError("repack needs fixed_mask (or a batch that carries one); sampling() samples every row")
         packed = _get(batch, "seg_offsets") is not None
@@ -550,16 +581,17 @@ class TDiffusionModule:
             pairs = _disulfide_refusals(batch, disulfides, False, return_list)
             SC_D_sample = self.sampling(batch, seed=seed, fixed_mask=fixed_mask, fixed_chi=fixed_chi, fixed_mode=fixed_mode, guide=guide,
                                         corrector=corrector)
-            return self._disulfide_tail(batch, self._context(batch), SC_D_sample, pairs, fixed_mask, use_proximal, norm_rows)
+            out, link = self._disulfide_tail(batch, self._context(batch), SC_D_sample, pairs, fixed_mask, use_proximal, norm_rows, want_link=True)
+            return self._refine_tail(batch, out, fixed_mask, link)[0] if refine_allatom else out
         SC_D_sample = self.sampling(batch, seed=seed, fixed_mask=fixed_mask, fixed_chi=fixed_chi, fixed_mode=fixed_mode, guide=guide, corrector=corrector)
         if not use_proximal:
-            return SC_D_sample
+            return self._refine_tail(batch, SC_D_sample, fixed_mask)[0] if refine_allatom else SC_D_sample
         traj, _, accepted, losses = proximal_optimizer_packed(batch, SC_D_sample, cfg.violation_tolerance_factor,
                                                               cfg.clash_overlap_tolerance, cfg.lamda, cfg.num_steps,
                                                               norm_rows=norm_rows, want_traj=return_list, fixed_mask=fixed_mask)
         if return_list:
             return SC_D_sample, [traj[i] for i in range(cfg.num_steps)], [float(v) for v in losses[0].cpu()]
-        return accepted
+        return self._refine_tail(batch, accepted, fixed_mask)[0] if refine_allatom else accepted
 
     def _recombine(self, ctx, chi, n_decoys, res, recombine_sweeps):
         """``Context.ensemble_recombine`` from the decoy ``ensemble_reduce`` selected (``res.best``, taken on the device) with the
@@ -620,7 +652,7 @@ class TDiffusionModule:
         return out
 
     def _reduce_ensemble(self, packed, chi, select, return_all, recombine, recombine_sweeps, sasa, polar=False, clashscore=False,
-                         hbond_optimize=False):
+                         hbond_optimize=False, refine=None):
         """What the two ensemble calls do with the decoys' angles: the per-residue clash, ``Context.ensemble_reduce``, the
         recombination, the buried surface and the polar contacts if asked for; the selected (or recombined) angles, or the
         ``return_all`` dict."""
@@ -635,6 +667,8 @@ class TDiffusionModule:
             extra = dict(extra, bsa=self._decoy_bsa(ctx, chi))
         if clashscore and return_all:
             extra = dict(extra, **self._decoy_clashscore(ctx, chi))
+        if refine is not None and return_all:
+            extra = dict(extra, **self._refine_columns(ctx, refine))
         if hbond_optimize and return_all:
             extra = dict(extra, **self._decoy_hnet(ctx, chi, clashscore))
         if not return_all:
@@ -644,7 +678,7 @@ class TDiffusionModule:
 
     def sample_ensemble(self, batch, n_decoys, *, seed=None, use_proximal: bool = False, select="clash", return_all: bool = False,
                         recombine: bool = False, recombine_sweeps: int = 64, sasa: bool = False, guide=None, corrector=None,
-                        polar: bool = False, clashscore: bool = False, hbond_optimize: bool = False):
+                        polar: bool = False, clashscore: bool = False, hbond_optimize: bool = False, refine_allatom: bool = False):
         """``n_decoys`` seeded samples of every complex in ONE packed pass, reduced on the device.  On
         complexes with obstacle atoms the decoys of a group share the group's obstacles, and the clash that
         ranks them, the proximal stage and the recombination include the overlap with them.  ``batch``: a
@@ -686,6 +720,11 @@ class TDiffusionModule:
         too, ``clashscore_hnet``: the score of the optimised structure with the rotatable hydrogens counted, beside the
         conventional one.  The decoys' angles are returned as sampled; nothing is ranked by these.
 
+        ``refine_allatom``: behind the proximal stage, ONE ``Context.refine_allatom`` over the packed decoys
+        lowers every decoy's explicit-hydrogen overlaps in chi space; everything after it (the ranking, the keys above) sees the
+        refined angles, and ``return_all`` gains ``refine_moved`` int64 [n_complexes * n_decoys] (rows moved) and ``refine_F`` int64
+        [n_complexes * n_decoys, 2] (the overlap energy before and after).  Nothing is ranked by them.
+
         ``guide``: every decoy is sampled with clash guidance, as ``sampling(guide=...)`` samples the complex
         alone under the decoy's key; None = today's path.  ``corrector``: likewise -- every decoy is a segment and gets
         its own corrector step size, the bits of ``sampling(seed=, corrector=)`` of that complex alone under ``decoy_key``."""
@@ -703,12 +742,16 @@ class TDiffusionModule:
         if _get(packed, "fixed_mask") is not None:
             raise ValueError("ensembles under a fixed_mask are not supported: sample_ensemble samples every row")
         chi = self.sampling(packed, use_proximal=use_proximal, seed=seed, guide=guide, corrector=corrector)
-        return self._reduce_ensemble(packed, chi, select, return_all, recombine, recombine_sweeps, sasa, polar, clashscore, hbond_optimize)
+        refine = None
+        if refine_allatom:
+            chi, refine = self._refine_tail(packed, chi)
+        return self._reduce_ensemble(packed, chi, select, return_all, recombine, recombine_sweeps, sasa, polar, clashscore, hbond_optimize,
+                                     refine)
 
     def repack_ensemble(self, batch, fixed_mask=None, *, n_decoys, seed, fixed_chi=None, fixed_mode="renoise",
                         use_proximal: bool = False, select="clash", return_all: bool = False, recombine: bool = False,
                         recombine_sweeps: int = 64, sasa: bool = False, guide=None, corrector=None, polar: bool = False,
-                        clashscore: bool = False, hbond_optimize: bool = False):
+                        clashscore: bool = False, hbond_optimize: bool = False, refine_allatom: bool = False):
         """``sample_ensemble`` under a pin: ``n_decoys`` seeded partial repackings of every complex in ONE packed
         pass, reduced on the device.  ``batch``: a B = 1 batch, or a list of complexes (per-complex data or B = 1 batches).  Every
         complex carries its ``fixed_mask`` (1 = keep; [1, L] on a B = 1 batch, [L] on per-complex data), or ``fixed_mask`` gives it:
@@ -721,7 +764,7 @@ class TDiffusionModule:
         with and without ``use_proximal``.  pp_ensemble_reduce is used unchanged: kept rows are identical in every decoy, so their
         ``resultant`` is 1 to rounding and they add (to rounding) nothing to ``dev``; they enter the per-decoy means of ``dev`` and
         ``clash`` with the same weight in all decoys of a group, so they dilute both equally and do not change the ranking.
-        Returns what ``sample_ensemble`` returns (``sasa``: the ``bsa`` key as there; ``polar``, ``clashscore``, ``hbond_optimize``: their keys as there).  ``guide``,
+        Returns what ``sample_ensemble`` returns (``sasa``: the ``bsa`` key as there; ``polar``, ``clashscore``, ``hbond_optimize``, ``refine_allatom``: their keys as there; kept rows are not refined).  ``guide``,
         ``corrector``: as in ``sampling``."""
         from .batch import Batch, replicate_many
         self._check_select(select)
@@ -758,12 +801,16 @@ class TDiffusionModule:
                              for g, (c, r) in enumerate(zip(complexes, refs)) for _ in range(D)]).unsqueeze(0)
         chi = self.repack(packed, seed=seed, fixed_chi=ref, fixed_mode=fixed_mode, use_proximal=use_proximal,
                           norm_rows=[n for n in sizes for _ in range(D)] if use_proximal else None, guide=guide, corrector=corrector)
-        return self._reduce_ensemble(packed, chi, select, return_all, recombine, recombine_sweeps, sasa, polar, clashscore, hbond_optimize)
+        refine = None
+        if refine_allatom:
+            chi, refine = self._refine_tail(packed, chi, packed.fixed_mask)
+        return self._reduce_ensemble(packed, chi, select, return_all, recombine, recombine_sweeps, sasa, polar, clashscore, hbond_optimize,
+                                     refine)
 
     def mutate(self, proteins_and_mutations, *, seed, radius=10.0, shell="ca", n_decoys=1, use_proximal: bool = False,
                select="clash", fixed_mode="renoise", max_rows=200_000, log=print, recombine: bool = False,
                recombine_sweeps: int = 64, sasa: bool = False, guide=None, corrector=None, polar: bool = False,
-               clashscore: bool = False, hbond_optimize: bool = False):
+               clashscore: bool = False, hbond_optimize: bool = False, refine_allatom: bool = False):
         """Mutant modelling: put each mutation set into its complex, repack what it touches, return the mutant.
         ``proteins_and_mutations``: a list of ``(protein dict, mutations)`` pairs, ``mutations`` a string ("RA47A,EA48A") or dicts as
         ``featurize.parse_mutstr`` returns them; several sets of one protein are repeated pairs.  Set i of the call gets the noise
@@ -801,6 +848,12 @@ class TDiffusionModule:
         ``hbond_optimize``: every dict gains ``hnet_bonds`` and ``hnet_flips`` int64 [n_decoys] and, with
         ``clashscore`` too, ``clashscore_hnet`` fp64 [n_decoys], as ``sample_ensemble`` describes them.
 
+        ``refine_allatom``: the shell rows of every decoy are refined against the explicit-hydrogen overlaps
+        behind the pinned stage (rows outside the shell stay the wild type's, bit for bit); every dict gains ``refine_moved`` int64
+        [n_decoys] and ``refine_F`` int64 [n_decoys, 2], and of the SELECTED decoy ``refine_steps`` int8 [rounds, 1, L, 4],
+        ``refine_e`` int32 [1, L, 2], ``refine_chi0`` [1, L, 4] (its angles in front of the refinement) and ``refine_deltas`` (the
+        step sizes in radians), gathered on the device.
+
         ``guide``: the shell is sampled with clash guidance, as in ``sampling``; rows outside the shell are
         fixed rows, which are never nudged.  ``corrector``: as in ``sampling``; the rows outside the shell
         are never moved and never counted."""
@@ -836,10 +889,16 @@ class TDiffusionModule:
                 p = type(b)(b)
                 p["fixed_mask"] = pad_rows(part, int(b["max_size"]), True)      # trailing rows pack() dropped keep their (zero) angles
                 pinned.append(p)
+            keep, self.keep_refine_report = getattr(self, "keep_refine_report", False), refine_allatom or getattr(self, "keep_refine_report", False)
             out = self.repack_ensemble(pinned, n_decoys=n_decoys, seed=seed, fixed_mode=fixed_mode, use_proximal=use_proximal,
                                        select=select, return_all=True, recombine=recombine, recombine_sweeps=recombine_sweeps,
                                        sasa=sasa, guide=guide, corrector=corrector, polar=polar, clashscore=clashscore,
-                                       hbond_optimize=hbond_optimize)
+                                       hbond_optimize=hbond_optimize, refine_allatom=refine_allatom)
+            self.keep_refine_report = keep
+            rep = None
+            if refine_allatom:
+                rep = self.refine_reports[-1] if keep else self.refine_reports.pop()
+                seg_first = torch.tensor(out["decoys"][1].seg_offsets_host[:-1], device=self.device)
             final = out["recombined"] if recombine else out["selected"]
             pos = gctx.atom14(final)
             picks = unpack(pb, out["pick"].reshape(1, -1)) if recombine else [None] * len(members)
@@ -864,6 +923,17 @@ class TDiffusionModule:
                 for k in ("hnet_bonds", "hnet_flips", "clashscore_hnet") if hbond_optimize else ():
                     if k in out:
                         results[i][k] = out[k][g * n_decoys:(g + 1) * n_decoys]
+                for k in ("refine_moved", "refine_F") if refine_allatom else ():
+                    results[i][k] = out[k][g * n_decoys:(g + 1) * n_decoys]
+                if rep is not None:
+                    # the rows of the selected decoy in the packed call, taken on the device; rows pack() dropped took no step
+                    offs = out["decoys"][1].seg_offsets_host
+                    ln = offs[g * n_decoys + 1] - offs[g * n_decoys]
+                    rows = seg_first[g * n_decoys + out["best"][g].long()] + torch.arange(ln, device=self.device)
+                    R = rep.steps.shape[0]
+                    st, en = rep.steps.reshape(R, 1, -1, 4)[:, :, rows], rep.e.reshape(1, -1, 2)[:, rows]
+                    results[i].update(refine_steps=torch.cat([st, st.new_zeros(R, 1, n - ln, 4)], 2), refine_e=torch.cat([en, en.new_zeros(1, n - ln, 2)], 1),
+                                      refine_chi0=pad_rows(rep.chi0.reshape(1, -1, 4)[:, rows], n, b["SC_D"]), refine_deltas=rep.deltas)
         return results
 
     def sample_from(self, batch, SC_D_init, sde_noise=None):
