@@ -163,7 +163,8 @@ void pp_ctx_destroy(pp_ctx *ctx);
  * row of every complex and the total, min_len / max_len their shortest and longest length.  Neighbour
  * search, clash partners and E_idx numbering stay inside each complex; every other stage is per row or per
  * edge.  Results equal those of each complex prepared on its own (K = min(32, length): complexes shorter
- * than 32 residues cannot be mixed with longer ones -> PP_ERR_UNSUPPORTED).  pp_proximal needs one complex
+ * than 32 residues cannot be mixed with longer ones -> PP_ERR_UNSUPPORTED; a plan without network weights builds
+ * no graph, has no K and takes segments of any lengths).  pp_proximal needs one complex
  * per ctx; pp_proximal_packed optimises every complex of a packed ctx at once.  CONTRACT: the device table must describe the batch (seg_offsets[0] = 0, seg_offsets[n_seg] = the number of rows,
  * every length within [min_len, max_len]): the library sizes its launches from min_len / max_len and cannot read the table
  * back without stalling the stream; a table that disagrees is clamped where that is cheap, but the behaviour is undefined. */

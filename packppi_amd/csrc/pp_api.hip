@@ -370,8 +370,9 @@ static pp_status prepare_impl(pp_plan *plan, const pp_batch *b, const int32_t *s
         if (n_seg < 1 || min_len < 1 || max_len < min_len || (long long)n_seg * min_len > b->L || (long long)n_seg * max_len < b->L)
             FAIL(PP_ERR_INVALID, "pp_complex_prepare_packed: segment count / lengths do not fit the batch");
         // K = min(32, L) is a per-batch constant of the reference (encoder.py:115): complexes shorter than 32 residues
-        // cannot share a context with longer ones
-        if (min_len < PP_TOP_K && min_len != max_len)
+        // cannot share a context with longer ones.  A plan without network weights builds no graph and has no K: its structure
+        // stages (shell, SASA, disulfides, polar, hydrogens, clashscore, hnet, refine) take segments of any lengths
+        if (plan->has_network && min_len < PP_TOP_K && min_len != max_len)
             FAIL(PP_ERR_UNSUPPORTED, "pp_complex_prepare_packed: complexes shorter than 32 residues must be prepared on their own");
     }
     if (!b->X || !b->residue_type || !b->BB_D)
