@@ -891,6 +891,17 @@ pp_status pp_ctx_saturated(pp_ctx *ctx, int *flags, void *stream);
  * (same results).  rows is a DEVICE array [B*L] (packed ctx: [N]); the entries behind *count are -1.  Waits for `stream`. */
 pp_status pp_ctx_live_rows(pp_ctx *ctx, int32_t *rows, int *count, void *stream);
 
+/* The work table of the context's mixed live-row launch, read-only.  At the context sizes where a CU gets
+ * three rows in one round, or a full round of two-row workgroups has a tail, the layer-1 edge update of a sampling run is one launch
+ * of one- and two-row workgroups; a table made on the device next to the live-row list says which rows workgroup b takes.  mix is a
+ * HOST array [N][2]: (r, s) two rows, (r, -1) one row, (-1, -1) no work; two-row entries come first.  *workgroups is the size of
+ * that launch -- every live row sits in front of it -- or 0 for a context of another size (mix is then left alone).  A read-back
+ * for tests and tools: it takes no stream and waits for the whole device.
+ * pp_live_mix_host fills the same table on the host, without a device, for num_cu compute units: rows [N + 2] holds M rows and then
+ * -1, mix is a HOST array [N][2].  Both run the same rule (the launch shape of M rows) and the same entry function. */
+pp_status pp_ctx_live_mix(pp_ctx *ctx, int32_t *mix, int *workgroups);
+pp_status pp_live_mix_host(const int32_t *rows, int M, int N, int num_cu, int32_t *mix, int *workgroups);
+
 /* Diagnostics -- ONLY in libpackppi_hip.dbg.so (built with -DPP_DIAG; same kernels and results as the default library):
  * single launches, internal-buffer copies and a prefix of one network evaluation, for tools/debug/ and the per-layer parity
  * test (tests/test_hip_layers.py).  Not part of the drop-in boundary; the default, .f32 and .chk libraries do not export them

@@ -117,6 +117,36 @@ extern "C" pp_status pp_ctx_live_rows(pp_ctx *c, int32_t *rows, int *count, void
     return PP_OK;
 }
 
+// The work table of the context's mixed live-row launch, read-only: mix is a HOST array [N][2], entry b the
+// one or two rows of workgroup b in dispatch order ((r, -1): one row; (-1, -1): none).  *workgroups is the launch's grid -- every live
+// row must sit in front of it -- or 0 for a context whose size does not take the mixed launch (mix is left alone).  Takes no stream:
+// a read-back for tests and tools, it waits for the whole device (whatever stream prepared the context, the table is complete).
+extern "C" pp_status pp_ctx_live_mix(pp_ctx *c, int32_t *mix, int *workgroups) {
+    if (!c || !mix || !workgroups) FAIL(PP_ERR_INVALID, "pp_ctx_live_mix: null argument");
+    if (!c->plan->has_network) FAIL(PP_ERR_INVALID, "pp_ctx_live_mix: plan was created without network weights");
+    PP_HIP_CHECK(hipSetDevice(c->plan->device));
+    *workgroups = 0;
+    if (!c->live_mix_set[0]) return PP_OK;
+    PP_HIP_CHECK(hipDeviceSynchronize());
+    PP_HIP_CHECK(hipMemcpy(mix, c->live_mix[0], (size_t)c->N * sizeof(int2), hipMemcpyDeviceToHost));
+    *workgroups = pp_live_mix_grid(c->N, c->plan->num_cu, PP_WGS2);
+    return PP_OK;
+}
+
+// The same table on the HOST, for a device of num_cu compute units (no device call; the rule and the entries are the functions
+// k_live_rows calls, pp_internal.h): rows [N + 2] holds M rows and then -1, mix is [N][2].  *workgroups as above.
+extern "C" pp_status pp_live_mix_host(const int32_t *rows, int M, int N, int num_cu, int32_t *mix, int *workgroups) {
+    if (!rows || !mix || !workgroups || M < 0 || M > N || num_cu < 1) FAIL(PP_ERR_INVALID, "pp_live_mix_host: null argument, M outside 0 .. N or no compute unit");
+    const PPEdgeShape sh = pp_edge_shape(M, num_cu, PP_WGS2);
+    for (int b = 0; b < N; b++) {
+        const int2 e = pp_live_mix_entry(rows, sh, b);
+        mix[2 * b] = e.x;
+        mix[2 * b + 1] = e.y;
+    }
+    *workgroups = pp_live_mix_size(N, num_cu, PP_WGS2) ? pp_live_mix_grid(N, num_cu, PP_WGS2) : 0;
+    return PP_OK;
+}
+
 // How far a side-chain atom can get from its CA whatever the chi angles are, per residue type: the atom sits at chain(lit) in the
 // backbone frame (origin CA), the chain composes default frames and rotations about x, a rotation keeps the norm and a frame adds at
 // most the length of its translation: |atom - CA| <= |lit| + sum of |t_k| over the frames of its chain (features.py:95-194).

@@ -163,9 +163,7 @@ enum { P_BMID = 0, P_BOUT = 128, P_FOB = 256, P_G2 = 384, P_BE2 = 512, P_FIB = 6
 #else
 #define TSF(k)
 #endif
-#ifndef PP_WGS2
-#define PP_WGS2 2          // same for the two-residue instances
-#endif
+// (PP_WGS2, the same for the two-residue instances: pp_internal.h, next to the launch-shape rule that counts in it)
 #ifndef PP_WGS
 #define PP_WGS 3           // register budget = 512 / PP_WGS per lane: three workgroups per CU (the kernels need ~140 VGPRs, 38.4 KB of LDS)
 #endif
@@ -979,8 +977,13 @@ k_node_message_mix(EdgeArgs A) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int b = blockIdx.x;
     const int ns = gridDim.x - A.n_pairs;
-    if (b < ns) node_message_body<1, ST0>(A, 2 * A.n_pairs + b, smem);       // the one-residue workgroups first, as in k_edge_update_mix
-    else node_message_body<2, ST0>(A, 2 * (b - ns), smem);
+    if (A.mix_mode == 3) {               // the one-residue workgroups first in dispatch order
+        if (b < ns) node_message_body<1, ST0>(A, 2 * A.n_pairs + b, smem);
+        else node_message_body<2, ST0>(A, 2 * (b - ns), smem);
+    } else {                             // the pairs first, as in k_edge_update_mix
+        if (b < A.n_pairs) node_message_body<2, ST0>(A, 2 * b, smem);
+        else node_message_body<1, ST0>(A, 2 * A.n_pairs + (b - A.n_pairs), smem);
+    }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1331,13 +1334,22 @@ static int g_mix = -1;
 static bool use_mix(int N) {
     if (g_mix < 0) {
         const char *e = PP_GETENV("PP_EDGE_MIX");
-        g_mix = e ? atoi(e) : 3;       // 3: the one-residue workgroups first in dispatch order (they are the longer ones now: +0.5-1 %)
+        // 1: the pairs first in dispatch order, in the edge update and in the node message (re-measured behind the live rows: 1.3 % of
+        // a T1124 pass over 3, the one-residue workgroups first, which round 4 had found better by 0.5-1 %)
+        g_mix = e ? atoi(e) : 1;
     }
     if (g_forced_R >= 1 || !g_mix) return false;
     return N > 2 * g_num_cu && N <= 3 * g_num_cu;
 }
 // its two-residue workgroups: residues (2 b, 2 b + 1) for b < mix_pairs(N), the remaining N - 2 mix_pairs(N) get one workgroup each
-static int mix_pairs(int N) { return (N + 2) / 3; }
+// (the launch-shape rule's count for this regime, pp_internal.h pp_edge_shape: (N + 2) / 3)
+static int mix_pairs(int N) { return pp_edge_shape(N, g_num_cu, PP_WGS2).pairs; }
+// the live-row launch is the mixed one in both mixed regimes of the rule: the one above and 2 slots < N <= 3 slots rows, where the
+// all-rows launches stay two-row launches
+static bool use_live_mix(int N) {
+    (void)use_mix(N);      // (reads PP_EDGE_MIX once)
+    return g_forced_R < 1 && g_mix && pp_live_mix_size(N, g_num_cu, PP_WGS2);
+}
 
 // resident workgroups per CU the runtime predicts for the two kernels (measurement aid)
 void pp_edge_occupancy(int *node_msg, int *edge_upd) {
@@ -1372,6 +1384,7 @@ pp_status pp_launch_node_message(pp_ctx *c, int layer, hipStream_t s) {
     static const bool nmix = !(nmix_env && atoi(nmix_env) == 0);
     if (nmix && !(nm_R >= 1 && nm_R <= PP_RMAX) && use_mix(c->N)) {
         A.n_pairs = mix_pairs(c->N);
+        A.mix_mode = g_mix;
         const int singles = c->N - 2 * A.n_pairs > 0 ? c->N - 2 * A.n_pairs : 0;
         PP_LAUNCH(c, (layer == 0 ? k_node_message_mix<true> : k_node_message_mix<false>), dim3(A.n_pairs + singles), dim3(ET),
                   nm_smem(2), s, A);
@@ -1406,7 +1419,7 @@ pp_status pp_launch_edge_update(pp_ctx *c, int layer, bool keep_hE, hipStream_t 
     if (live && (layer != 1 || keep_hE || !PP_FUSED)) { pp_set_error("pp_launch_edge_update: the live-row launch is layer 1's, without write-back"); return PP_ERR_INVALID; }
     EdgeArgs A = edge_args(c, layer, true);
     const int R = pick_R(c->N);
-    const bool mixed = use_mix(c->N);
+    const bool mixed = live ? use_live_mix(c->N) : use_mix(c->N);
     if (live) {                     // (the slot of rmask)
         // the table is filled by pp_launch_live_rows for the sizes it expects the mixed launch at: never launch on one it did not fill
         if (mixed && !live->mix) { pp_set_error("pp_launch_edge_update: the mixed launch has no live-row work table for this context"); return PP_ERR_INVALID; }
@@ -1417,12 +1430,12 @@ pp_status pp_launch_edge_update(pp_ctx *c, int layer, bool keep_hE, hipStream_t 
     if (lns && !PP_FUSED) { pp_set_error("pp_launch_edge_update: a plan with LayerNorm operand scales needs the fused build"); return PP_ERR_UNSUPPORTED; }
     if (mixed) {
         // three residues per CU as one two-residue and one one-residue workgroup
-        A.n_pairs = mix_pairs(c->N);
+        A.n_pairs = live ? 0 : mix_pairs(c->N);      // (the live instances read the table, not n_pairs)
         A.mix_mode = g_mix;
         const int singles = c->N - 2 * A.n_pairs > 0 ? c->N - 2 * A.n_pairs : 0;
-        // live rows: the table deals M <= N <= 3 C rows out to (M + 2) / 3 pair and M - 2 pairs one-row workgroups (k_live_rows),
-        // no more than 2 M / 3 + 1 <= 2 C in all
-        const int wgs = live ? (c->N < 2 * g_num_cu ? c->N : 2 * g_num_cu) : A.n_pairs + singles;
+        // live rows: the table deals the M <= N live rows out by the launch-shape rule (k_live_rows); the grid is the rule's worst
+        // case over M, the surplus workgroups read (-1, -1) and leave
+        const int wgs = live ? pp_live_mix_grid(c->N, g_num_cu, PP_WGS2) : A.n_pairs + singles;
         PP_LAUNCH(c, mix_kernel(layer == 0, lns, keep_hE, live != nullptr), dim3(wgs), dim3(ET), eu_smem(2) > eu_smem(1) ? eu_smem(2) : eu_smem(1), s, A);
         PP_HIP_CHECK(hipGetLastError());
         return PP_OK;

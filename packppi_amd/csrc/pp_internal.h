@@ -400,6 +400,55 @@ struct PPLive {
     const int2 *mix;
 };
 
+// ---- the shape of an edge-level launch over M rows ------------------------------------------------------
+// ONE rule for the host's launchers (M = the context's rows) and for k_live_rows (M = the live rows, known only on the device).  A CU
+// hosts `slots` (PP_WGS2) workgroups of the two-row instances, S = slots * CUs in one round, and every workgroup streams the layer's
+// whole weight set:
+//   M <= S            one row per workgroup: one round, no CU streams the weights more than `slots` times
+//   S < M <= 3 S / 2  three rows on a CU in one round as one pair and one one-row workgroup: (M + 2) / 3 pairs (section 4.8)
+//   3 S / 2 < M <= 2 S  pairs: one round of co-resident pairs
+//   2 S < M <= 3 S    a full round of S pairs, then the other M - 2 S rows as one-row workgroups: the tail of a second round of
+//                     pairs lasts as long as a pair running alone, a one-row workgroup is done sooner (section 4.9)
+//   3 S < M           pairs: the length follows the number of weight passes
+// Pairs are dispatched first, in the table of k_live_rows and in the all-rows mixed launches (pp_edge_f16.hip use_mix; the
+// diagnostics library's PP_EDGE_MIX=3 restores their earlier order).  An odd M leaves the last pair with one row: one_row is never
+// negative.
+#ifndef PP_WGS2
+#define PP_WGS2 2          // workgroups per CU of the two-row edge instances (pp_edge_f16.hip)
+#endif
+struct PPEdgeShape {
+    int pairs, one_row;
+    bool pairs_first;
+};
+__host__ __device__ inline PPEdgeShape pp_edge_shape(int M, int num_cu, int slots) {
+    const int S = slots * num_cu;
+    PPEdgeShape sh = {(M + 1) / 2, 0, true};
+    if (M <= S) sh.pairs = 0;
+    else if (2 * M <= 3 * S) sh.pairs = (M + 2) / 3;
+    else if (M > 2 * S && M <= 3 * S) sh.pairs = S;
+    sh.one_row = M > 2 * sh.pairs ? M - 2 * sh.pairs : 0;
+    return sh;
+}
+// entry b of the work table of a mixed launch (pp_ctx::live_mix) with this shape: rows [>= M + 1] holds the M rows, then -1
+__host__ __device__ inline int2 pp_live_mix_entry(const int32_t *rows, const PPEdgeShape &sh, int b) {
+    int2 e = make_int2(-1, -1);
+    const int p = sh.pairs_first ? b : b - sh.one_row, q = sh.pairs_first ? b - sh.pairs : b;      // index among the pairs / the one-row
+    if (p >= 0 && p < sh.pairs) e = make_int2(rows[2 * p], rows[2 * p + 1]);
+    else if (q >= 0 && q < sh.one_row) e.x = rows[2 * sh.pairs + q];
+    return e;
+}
+// the context sizes whose live-row launch is the mixed one and takes its rows from the work table (both mixed regimes above)
+inline bool pp_live_mix_size(int N, int num_cu, int slots) {
+    const int S = slots * num_cu;
+    return (N > S && 2 * N <= 3 * S) || (N > 2 * S && N <= 3 * S);
+}
+// its workgroups for the worst case over M <= N live rows (the host never learns M; surplus workgroups read (-1, -1) and leave):
+// no shape of M <= 3 S / 2 rows has more than S workgroups, one of 2 S < M rows has M - S
+inline int pp_live_mix_grid(int N, int num_cu, int slots) {
+    const int S = slots * num_cu;
+    return N > 2 * S ? N - S : S;
+}
+
 // ---- launchers implemented in the kernel translation units ----------------------------------
 // live-row set `set` of the context (0: every row with an angle to move; 1: those that are not `fixed` either), on the stream
 pp_status pp_launch_live_rows(pp_ctx *c, int set, const uint8_t *fixed, hipStream_t s);

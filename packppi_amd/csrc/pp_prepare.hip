@@ -408,15 +408,15 @@ pp_status pp_launch_prepare(pp_ctx *c, hipStream_t s, const int64_t *E_idx) {
 // counts a contiguous slice of the rows, the 1024 counts are scanned in LDS, every thread writes its slice's rows behind its offset.
 //   rows [N + 2]  the live rows, ascending, then -1: workgroup b of a one- / two-row launch reads rows[R b .. R b + R - 1], so a
 //                 launch sized for N rows needs no count -- the surplus workgroups read -1 and leave;
-//   mix  [N]      (or null) the work table of the mixed launch k_edge_update_mix in dispatch order: with M live rows (M + 2) / 3
-//                 pair workgroups -- the rule of the all-rows launch -- FIRST, then the M - 2 pairs one-row workgroups, then
-//                 (-1, -1).  The other rule (M - 2 CUs pairs: as few CUs with three rows as M allows) and the other order were
-//                 measured at T1124 and were slower (profiles/r17_live_rows.json t1124_split);
+//   mix  [N]      (or null) the work table of the mixed launch k_edge_update_mix in dispatch order: the pair and one-row workgroups
+//                 that the launch-shape rule gives M live rows (pp_internal.h pp_edge_shape: the shape the launchers give a
+//                 context of M rows), pairs FIRST, then (-1, -1).  Other counts of pairs and the other order were measured and
+//                 were slower or no faster (DESIGN.md sections 4.8 and 4.9, profiles/r17_live_rows.json, r20_edge_shape.json);
 //   cnt  [1]      M.
 #define LIVE_THREADS 1024
 __global__ void __launch_bounds__(LIVE_THREADS)
 k_live_rows(const float *__restrict__ rmask, const float *__restrict__ scm, const uint8_t *__restrict__ fixed, int N,
-            int32_t *__restrict__ rows, int2 *__restrict__ mix, int32_t *__restrict__ cnt) {
+            int32_t *__restrict__ rows, int2 *__restrict__ mix, int32_t *__restrict__ cnt, int num_cu, int slots) {
     __shared__ int part[LIVE_THREADS];
     const int t = threadIdx.x;
     const int per = (N + LIVE_THREADS - 1) / LIVE_THREADS;
@@ -441,24 +441,19 @@ k_live_rows(const float *__restrict__ rmask, const float *__restrict__ scm, cons
         if (is_live(i)) rows[o++] = i;
     for (int i = M + t; i < N + 2; i += LIVE_THREADS) rows[i] = -1;
     if (mix) {
-        const int np = (M + 2) / 3, ns = max(M - 2 * np, 0);      // (M = 1: one pair workgroup whose second row is -1)
+        const PPEdgeShape sh = pp_edge_shape(M, num_cu, slots);
         __syncthreads();                                // the workgroup's own writes to rows[] are visible to all of it
-        for (int b = t; b < N; b += LIVE_THREADS) {
-            int2 e = make_int2(-1, -1);
-            if (b < np) e = make_int2(rows[2 * b], rows[2 * b + 1]);
-            else if (b - np < ns) e.x = rows[2 * np + b - np];
-            mix[b] = e;
-        }
+        for (int b = t; b < N; b += LIVE_THREADS) mix[b] = pp_live_mix_entry(rows, sh, b);      // (an odd M in pairs: (row, -1))
     }
     if (t == 0) cnt[0] = M;
 }
 
 pp_status pp_launch_live_rows(pp_ctx *c, int set, const uint8_t *fixed, hipStream_t s) {
     const int num_cu = c->plan->num_cu;
-    // the mixed launch serves 2 C < N <= 3 C rows (pp_edge_f16.hip use_mix); other sizes never read the table
-    const bool want_mix = c->N > 2 * num_cu && c->N <= 3 * num_cu;
+    // the live-row launch is the mixed one at these sizes (pp_edge_f16.hip use_live_mix); other sizes never read the table
+    const bool want_mix = pp_live_mix_size(c->N, num_cu, PP_WGS2);
     hipLaunchKernelGGL(k_live_rows, dim3(1), dim3(LIVE_THREADS), 0, s, c->b.residue_mask, c->b.SC_D_mask, fixed, c->N,
-                       c->live_rows[set], want_mix ? c->live_mix[set] : nullptr, c->live_cnt[set]);
+                       c->live_rows[set], want_mix ? c->live_mix[set] : nullptr, c->live_cnt[set], num_cu, PP_WGS2);
     c->live_mix_set[set] = want_mix;      // what the sampling loop hands to the mixed launch, or null (pp_api.hip sample_impl)
     PP_HIP_CHECK(hipGetLastError());
     return PP_OK;

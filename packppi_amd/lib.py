@@ -21,7 +21,7 @@ SYMBOLS = ("pp_version", "pp_last_error", "pp_build_id", "pp_plan_set_knn_ties",
            "pp_affinity_create", "pp_affinity_destroy", "pp_affinity_encode", "pp_affinity_predict",
            "pp_score_rows", "pp_so2_set_grids", "pp_so2_score", "pp_dsm_loss",
            "pp_ctx_set_rng_keys", "pp_noise_seeded", "pp_add_noise_seeded", "pp_sample_seeded",
-           "pp_sample_partial", "pp_proximal_pinned", "pp_ctx_live_rows", "pp_ensemble_reduce", "pp_ctx_shell",
+           "pp_sample_partial", "pp_proximal_pinned", "pp_ctx_live_rows", "pp_ctx_live_mix", "pp_live_mix_host", "pp_ensemble_reduce", "pp_ctx_shell",
            "pp_ensemble_recombine", "pp_ctx_set_obstacles", "pp_sasa", "pp_sample_guided", "pp_sample_corrected",
            "pp_disulfide_close", "pp_polar", "pp_hydrogens", "pp_clashscore", "pp_hnet_optimize", "pp_chi_refine")
 
@@ -156,6 +156,8 @@ def load():
     lib.pp_sample_partial.argtypes = [vp, vp, vp, vp, i, vp, i, i, C.c_uint64, vp, vp]
     lib.pp_proximal_pinned.argtypes = [vp, vp, vp, f, i, vp, vp, vp, vp, vp, vp, vp]
     lib.pp_ctx_live_rows.argtypes = [vp, vp, C.POINTER(C.c_int), vp]
+    lib.pp_ctx_live_mix.argtypes = [vp, vp, C.POINTER(C.c_int)]
+    lib.pp_live_mix_host.argtypes = [vp, i, i, i, vp, C.POINTER(C.c_int)]
     lib.pp_ensemble_reduce.argtypes = [vp, vp, i, vp, i, vp, vp, vp, vp, vp, vp, vp]
     lib.pp_ctx_shell.argtypes = [vp, vp, i, f, i, vp, vp, vp, vp]
     lib.pp_ensemble_recombine.argtypes = [vp, vp, i, vp, i, vp, vp, vp, vp, vp, vp, vp]
@@ -1364,6 +1366,14 @@ class Context:
         rows, n = self._new(self.n_rows, dtype=torch.int32), C.c_int(0)
         _check(load().pp_ctx_live_rows(self.handle, _ptr(rows), C.byref(n), self._stream()), "pp_ctx_live_rows")
         return rows[:int(n.value)]
+
+    def live_mix(self):
+        """The work table of the context's mixed live-row launch (pp_ctx_live_mix): ``(table, workgroups)`` -- int32 [N, 2] on the
+        HOST, entry b the one or two rows of workgroup b ((r, -1): one row, (-1, -1): none), and the size of that launch; ``(None, 0)``
+        for a context whose size does not take the mixed launch.  A read-back for tests and tools: waits for the whole device."""
+        mix, n = torch.empty(self.n_rows, 2, dtype=torch.int32), C.c_int(0)
+        _check(load().pp_ctx_live_mix(self.handle, _ptr(mix), C.byref(n)), "pp_ctx_live_mix")
+        return (mix, int(n.value)) if n.value else (None, 0)
 
     def time_kernel(self, which: int, iters: int = 20) -> float:
         """Average ms per launch of the node-message (0) / edge-update (1) kernel, HIP events on the current stream."""
