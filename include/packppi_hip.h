@@ -625,6 +625,59 @@ pp_status pp_disulfide_close(pp_ctx *ctx, const float *chi /* DEVICE [N,4] or NU
                              float sigma_chi, float *chi_out /* DEVICE [N,4] or NULL */, int32_t *partner /* DEVICE [N] */,
                              float *report /* DEVICE [N][4] */, int32_t *count /* DEVICE [n_seg] */, void *stream);
 
+/* ---- Anchors: metal sites and covalent links (no reference kernel; csrc/pp_anchor.hip holds the arithmetic) --
+ * An anchor is a distance restraint, optionally with an angle term, between a side-chain atom and a fixed point: a metal ion, or the
+ * atom of a ligand the residue is covalently linked to.  The call closes anchors next to the caller's angles; the caller then pins
+ * the closed rows, as it does with the rows of a disulfide bridge.
+ * Arithmetic is fp32 with fp contract off.  Each row's result is a function of that row's data and its anchors only.
+ *   anchor i       has: row, the row it belongs to; slot, the donor atom14 slot, 5..13; ante, the slot of the same row the donor is
+ *                  bonded to, 0..13; target, xyz in the batch's coordinates; d0 and sigma_d in A; theta0 and sigma_theta in degrees.
+ *                  sigma_theta <= 0 means no angle term.  A row may carry at most PP_ANCHOR_PER_ROW = 4 anchors.  They are taken in
+ *                  list order.
+ *   valid          means all of: row is in range and residue_mask != 0; atom_mask of N, CA, C, slot and ante is non-zero; the rigid
+ *                  group of slot (a2g) is a chi group, 4..7 (CB never moves); ante != slot; target, d0, sigma_d > 0, theta0 and
+ *                  sigma_theta are finite.  An invalid entry, or a fifth anchor on a row, is dropped on the device and the row's
+ *                  status becomes -2.  The Python layer refuses it by name before the call.  (A residue_type outside 0..20 makes
+ *                  the entry invalid too; an entry whose row is out of range marks no row; "fifth" counts the valid entries of the
+ *                  row in list order.)
+ *   geometry       The row's atoms are built as pp_atom14 builds them: backbone frame, default frames of the rigid groups, rotation
+ *                  about x by chi, literature positions.  They are built relative to the row's CA, and the target is taken as
+ *                  target - CA once (pp_shell's and pp_disulfide's habit, so a structure far from the origin loses nothing).
+ *   grid           n = the largest (group - 3) over the row's valid anchors: the number of chi the row's donors depend on, 1..4.
+ *                  g(n) = 72, 72, 36, 24.  theta_k = (float)(-pi + 2 pi k / g).  A point is (k1..kn) with flat index
+ *                  ((k1 g + k2) g + k3) g + k4, truncated to n digits.  Chi beyond n keep the caller's value (0 without chi).
+ *   energy         Sum over the row's valid anchors in list order of
+ *                      ((|A - q| - d0) / sigma_d)^2 + ((ang(P, A, q) - theta0) / sigma_theta)^2
+ *                  where A is the donor, P its antecedent and q the target.  ang is pp_disulfide_close's, in degrees.  A NaN never
+ *                  wins a minimum.
+ *   closure        Emin = the minimum over the grid.  If Emin > max_energy, the row is open: status -1 and chi_out row = chi row bit
+ *                  for bit.  Otherwise thr = max(Emin, min(max_energy, Emin + 4)) and F = {E <= thr}.
+ *                  J = E + (sum over k <= n, left to right, of wrap(theta - chi[row][k])^2) / sigma_chi^2.  chi NULL means J = E.
+ *                  The pick is the argmin of J over F, ties to the lowest flat index.  chi_out = chi bit for bit except the first n
+ *                  chi of closed rows.  A fixed row is kept: status 2.  Its E, distance and angle at its own angles are reported and
+ *                  nothing is written.
+ * Outputs, on the device, one writer per word, no read-back, the call never waits for the stream:
+ *   status[n]          0 none, 1 closed, 2 kept, -1 open, -2 an entry of this row was dropped (its other anchors close it, keep it or
+ *                      leave it open all the same: chi_out and the reports say which)
+ *   report[n]          (Emin, E at the pick, the first anchor's distance, the first anchor's angle); an open row has Emin alone, a
+ *                      kept row its E twice; 0 on rows without a valid anchor
+ *   anchor_report[i]   distance and angle of every anchor at its row's pick; 0 for a dropped entry or an open row
+ *   count[s]           rows of status 1 per segment of the ctx's segment table
+ *   chi_out            may be chi itself; NULL = reports only
+ * Capacity: A <= 8 N.  The first call on a ctx allocates the workspace (sized from N), pp_ctx_destroy frees it.  Works on a
+ * geometry-only plan.
+ * PP_ERR_INVALID: a null ctx, status, report or count; A > 0 without the three anchor arrays or anchor_report; A negative or beyond
+ * 8 N; chi_out or fixed without chi; max_energy NaN; with chi, sigma_chi not finite and positive; a batch without X, atom_mask,
+ * residue_type or residue_mask. */
+#define PP_ANCHOR_PER_ROW 4
+pp_status pp_anchor_close(pp_ctx *ctx, const float *chi /* DEVICE [N,4] or NULL */, const uint8_t *fixed /* DEVICE [N] or NULL */,
+                          const int32_t *anchors_i /* DEVICE [A][4] (row, slot, ante, 0) */,
+                          const float *anchors_target /* DEVICE [A][4] (x, y, z, 0) */,
+                          const float *anchors_param /* DEVICE [A][4] (d0, sigma_d, theta0, sigma_theta) */, int A, float max_energy,
+                          float sigma_chi, float *chi_out /* DEVICE [N,4] or NULL */, int32_t *status /* DEVICE [N] */,
+                          float *report /* DEVICE [N][4] */, float *anchor_report /* DEVICE [A][2] */,
+                          int32_t *count /* DEVICE [n_seg] */, void *stream);
+
 /* ---- Polar contacts (no reference kernel; csrc/pp_polar.hip holds the arithmetic) ------------------------
  * Hydrogen bonds, salt bridges and polar obstacle contacts between the heavy atoms of every segment of the ctx's segment table (the
  * complexes of a packed ctx, the decoys of a group, the B rows of a padded batch).  No pair crosses segments.  Chemistry is caller data:

@@ -17,7 +17,7 @@ def sources_for(edge_f16):
     """The translation units of a library, in link order, by edge-kernel variant: THE list (tools/debug/isa_digest.sh reads it too)."""
     return ["pp_api.hip", "pp_prepare.hip", "pp_node.hip", "pp_edge_f16.hip" if edge_f16 else "pp_edge.hip", "pp_clash.hip",
             "pp_affinity.hip", "pp_dsm.hip", "pp_ensemble.hip", "pp_shell.hip", "pp_recombine.hip", "pp_sasa.hip", "pp_correct.hip",
-            "pp_disulfide.hip", "pp_polar.hip", "pp_hydrogens.hip", "pp_hnet.hip", "pp_refine.hip"]
+            "pp_disulfide.hip", "pp_polar.hip", "pp_hydrogens.hip", "pp_hnet.hip", "pp_refine.hip", "pp_anchor.hip"]
 
 
 SOURCES = sources_for(EDGE_F16)

@@ -53,6 +53,11 @@ A, kept | gained | lost against the input's own side chains) -- and prints the c
 rotatable hydrogens first: structure.pdb takes the flipped angles, structure_H.pdb the optimised hydrogens, hnet.csv lists the movers.  With --n_decoys ensemble.csv gains the columns clashscore
 and clashes_interface.  --disulfides hands its bridges on: a bonded cysteine has no HG and the bridge is not an overlap.  The score
 is NOT MolProbity's: this package's radius table, and flips and rotatable hydrogens only with --hnet.
+--anchors auto|geometry|SPEC (without --anchors every output byte as before): behind the sampler and the
+disulfide closure the side chains that coordinate a metal or are covalently linked to a ligand are closed onto it (``Context.anchors``)
+and, with --use_proximal, held by the proximal stage.  Not with --n_decoys.  Writes anchors.csv (one line per anchor: residue, atom,
+target, kind, d0, distance before and after, angle, E, status) and, when the hetero lines are written (--obstacles), LINK records at
+the head of structure.pdb.
 --disulfides auto|SPEC (without --disulfides every output byte as before): behind the sampler the chi1 of every
 bonded cysteine pair are set so that the two sulfurs meet -- auto finds the pairs from the backbone, SPEC names them
 ('A:5-A:55,A:14-A:38').  With --use_proximal the proximal stage then keeps the bonded residues; with --repack a kept residue keeps its
@@ -245,6 +250,69 @@ def write_disulfides(model, protein, outdir):
         fh.write(text)
     print(f"----- disulfides: {len(pairs)} bridges closed -----")
     return ssbond_records(protein, pairs, [report[a][2] for a, _ in pairs])
+
+
+def add_anchor_arguments(p):
+    """--anchors.  Its default is SUPPRESSed, like --disulfides: without the flag the namespace is what it was before it."""
+    p.add_argument("--anchors", type=str, default=argparse.SUPPRESS, metavar="auto|geometry|SPEC", help="Close metal sites and "
+                   "covalent links behind the sampler (DESIGN.md section 34): auto takes the input's LINK records between a side-chain "
+                   "atom and a HETATM or non-standard-residue atom, geometry the donor atoms within reach of a metal in the input's "
+                   "own coordinates (they decide which atoms coordinate, never where they go), SPEC names them, e.g. "
+                   "'A:94:NE2=A:301:ZN' (chain, PDB residue number, atom). With --use_proximal the proximal stage keeps the closed "
+                   "residues. Writes anchors.csv and, with --obstacles, LINK records at the head of structure.pdb.")
+
+
+def anchors_from_args(args, p=None, protein=None):
+    """The ``anchors`` value of ``TDiffusionModule.sampling`` from the command line, None without --anchors: "auto" (the module reads
+    the LINK records of ``batch.pdb_path``), or (with the parsed input) the ``AnchorSet`` of "geometry" or of the atoms named."""
+    if not hasattr(args, "anchors"):
+        return None
+    if p is not None and getattr(args, "n_decoys", None) is not None:
+        p.error("--anchors together with --n_decoys is not supported: the ensemble calls do not close anchors")
+    spec = args.anchors.strip()
+    if spec == "auto" or protein is None:
+        return spec
+    from ..pdb_io import anchor_sites, hetero_atoms
+    from ..selection import parse_anchors
+    return anchor_sites(args.input, protein, "geometry", log=print) if spec == "geometry" else parse_anchors(spec, protein, hetero_atoms(args.input))
+
+
+ANCHOR_STATUS = {0: "none", 1: "closed", 2: "kept", -1: "open", -2: "dropped"}
+
+
+def anchors_csv(protein, anchors, status, report, anchor_report, before):
+    """The text of anchors.csv: one line per anchor -- chain, number, atom, target, kind, d0, the distance before and after (A), the
+    angle (degrees), the row's E at the pick and its status -- from host lists of ``Context.anchors`` (``before``: the anchors'
+    reports at the angles the closure started from)."""
+    from .. import constants as rc
+    lines = ["chain,number,atom,target,kind,d0,distance_before,distance_after,angle,energy,status\n"]
+    for i in range(len(anchors)):
+        r = int(anchors.rows[i])
+        atom = rc.atom14_names[int(protein["aaindex"][r])][int(anchors.slots[i])]
+        target = anchors.labels[i].partition("=")[2] or "/".join(f"{v:.3f}" for v in anchors.targets[i])
+        lines.append(f"{protein['chain_id'][r]},{int(protein['residue_index'][r])},{atom},{target},{anchors.kinds[i]},{anchors.params[i][0]:.3f},"
+                     f"{before[i][0]:.4f},{anchor_report[i][0]:.4f},{anchor_report[i][1]:.2f},{report[r][1]:.4f},{ANCHOR_STATUS[status[r]]}\n")
+    return "".join(lines)
+
+
+def write_anchors(rep, ctx, protein, outdir, pdb_file, with_links):
+    """anchors.csv from a report of the shape ``model.anchor_reports`` holds; returns the LINK text of the closed and kept anchors
+    (``with_links``: the hetero lines are written too, so the records have both ends), else ""."""
+    from ..pdb_io import hetero_atoms, link_lines
+    a = rep["anchors"]
+    status, report = rep["status"].reshape(-1).cpu().tolist(), rep["report"].reshape(-1, 4).cpu().tolist()
+    arep = rep["anchor_report"].cpu().tolist()
+    if -2 in status:
+        raise RuntimeError("anchors: the device dropped an entry the host check let through")
+    # the distances the closure started from: the same anchors with every row kept, at chi_before
+    before = ctx.anchors(rep["chi_before"], a, fixed=np.ones(ctx.n_rows, np.uint8), check=False).anchor_report.cpu().tolist() if len(a) else []
+    with open(os.path.join(outdir, "anchors.csv"), "w") as fh:
+        fh.write(anchors_csv(protein, a, status, report, arep, before))
+    done = [i for i in range(len(a)) if status[int(a.rows[i])] in (1, 2)]
+    print(f"----- anchors: {sum(1 for v in status if v == 1)} residues closed, {sum(1 for v in status if v == -1)} left open -----")
+    if not with_links or not done:
+        return ""
+    return link_lines(protein, a, hetero_atoms(pdb_file), [arep[i][0] for i in done], keep=done)
 
 
 def write_ensemble(model, batch, protein, args, analysis):
@@ -508,6 +576,12 @@ def evaluate_model(model, args):
         args.guide_kw["disulfides"] = disulfides
         batch["residue_names"] = residue_names(protein)        # so that a refusal names the residue, not the row
     model.keep_disulfide_report = disulfides is not None
+    anchors = anchors_from_args(args, protein=protein)
+    if anchors is not None:
+        from ..selection import residue_names
+        args.guide_kw["anchors"] = anchors
+        batch["residue_names"], batch["pdb_path"] = residue_names(protein), args.input
+        model.keep_anchor_report, model.anchor_reports = True, []
     refine_on = getattr(args, "refine_allatom", False)
     if refine_on:
         args.guide_kw["refine_allatom"] = True
@@ -534,6 +608,8 @@ def evaluate_model(model, args):
     if corrector is not None:
         write_corrector_csv(model, args.outdir)
     ssbond = write_disulfides(model, protein, args.outdir) if disulfides is not None else ""
+    if anchors is not None:            # LINK records behind the SSBOND records, as in a deposited file
+        ssbond += write_anchors(model.anchor_reports[-1], model._context(batch), protein, args.outdir, args.input, bool(args.obstacle_lines))
     if model.saturated() & 4:
         print("----- WARNING: NaN / infinity in the input coordinates or angles: the reference would return NaN here -----")
     if model.saturated() & 3:
@@ -621,6 +697,7 @@ def build_parser():
     add_guide_arguments(p)
     add_corrector_arguments(p)
     add_disulfide_arguments(p)
+    add_anchor_arguments(p)
     add_allatom_arguments(p)
     return p
 
@@ -649,6 +726,7 @@ def parse_args(argv=None):
     guide_from_args(args, p)
     corrector_from_args(args, p)
     disulfides_from_args(args, p)
+    anchors_from_args(args, p)
     return args
 
 

@@ -14,6 +14,9 @@ optimised on the device -- structure.pdb takes the flips, structure_H.pdb the op
 --refine_allatom (without it every output byte as before): behind the proximal stage the side chains are
 refined in chi space against the explicit-hydrogen overlaps (kept rows stay) -- structure.pdb takes the refined angles, refine.csv
 lists the moved residues, the --clashscore summary gains the score before and after.
+--anchors auto|geometry|SPEC (without it every output byte as before): in front of the optimiser the side chains
+that coordinate a metal or are covalently linked to a ligand are closed onto it from the input's angles; the optimiser then keeps
+them.  Writes anchors.csv and, with --obstacles, LINK records at the head of structure.pdb, as eval_diffusion does.
 --clashscore / --hydrogens (without them every output byte as before): clashes.csv (every serious all-atom
 overlap of the optimised structure with placed hydrogens, kept | gained | lost against the input, and the clashscore of both) and
 structure_H.pdb, as eval_diffusion writes them.  Not MolProbity's score.
@@ -45,8 +48,9 @@ def build_parser():
     p.add_argument("--sasa", action="store_true", help="Write sasa.csv for the optimised structure (DESIGN.md section 20): per "
                    "residue the solvent-accessible area at four nested levels, the buried interface area and the exposure. --repack "
                    "also takes interface:sasa and pocket (needs --obstacles).")
-    from .eval_diffusion import add_allatom_arguments
+    from .eval_diffusion import add_allatom_arguments, add_anchor_arguments
     add_allatom_arguments(p)
+    add_anchor_arguments(p)
     return p
 
 
@@ -86,13 +90,27 @@ def main(argv=None):
             sel = interface_selection(protein, args.input) if args.repack == "interface" else parse_selection(args.repack, protein)
         print(f"----- Optimising {int(sel.sum())} of {len(sel)} residues; the others keep the input's angles -----")
         fixed = torch.from_numpy(~sel).unsqueeze(0)
-    chis, losses = proximal_optimizer(batch, batch.SC_D, args.violation_tolerance_factor,
+    start, links = batch.SC_D, ""
+    if hasattr(args, "anchors"):
+        # closed from the input's angles, then held: the optimiser's accept rule compares the closed structure with the optimised one
+        from ..functional import _ctx_for
+        from ..pdb_io import anchor_sites
+        from .eval_diffusion import anchors_from_args, write_anchors
+        a = anchors_from_args(args, protein=protein)
+        a = anchor_sites(args.input, protein, "link", log=print) if isinstance(a, str) else a
+        ctx = _ctx_for(batch)
+        res = ctx.anchors(batch.SC_D, a.shifted(0, 0), fixed=fixed, names=[f"{c}:{int(n)}" for c, n in zip(protein["chain_id"], protein["residue_index"])])
+        links = write_anchors(dict(res, anchors=a, chi_before=batch.SC_D), ctx, protein, args.outdir, args.input, obstacles is not None)
+        start = res.chi
+        held = res.pinned().reshape(1, -1)
+        fixed = held if fixed is None else held | (fixed.to(held.device) != 0)
+    chis, losses = proximal_optimizer(batch, start, args.violation_tolerance_factor,
                                       args.clash_overlap_tolerance, args.lamda, args.num_steps, fixed_mask=fixed)
-    SC_D = chis[-1] if losses[-1] < losses[0] else batch.SC_D
+    SC_D = chis[-1] if losses[-1] < losses[0] else start
     xyz = get_atom14_coords(batch.X, batch.residue_type, batch.BB_D, SC_D)
     protein["atom_positions"] = xyz.cpu().squeeze(0).numpy()
     with open(analysis.tmp_pdb, "w") as fh:
-        fh.writelines(insert_obstacle_lines(to_pdb(protein), obstacles["lines"] if obstacles else []))
+        fh.writelines(links + insert_obstacle_lines(to_pdb(protein), obstacles["lines"] if obstacles else []))
     if obstacles is not None:
         import os
         from ..functional import _ctx_for
@@ -122,7 +140,7 @@ def main(argv=None):
         SC_D = res.chi[:, :SC_D.shape[1]].to(SC_D.device)
         refined = dict(protein, atom_positions=get_atom14_coords(batch.X, batch.residue_type, batch.BB_D, SC_D).cpu().squeeze(0).numpy())
         with open(analysis.tmp_pdb, "w") as fh:
-            fh.writelines(insert_obstacle_lines(to_pdb(refined), obstacles["lines"] if obstacles else []))
+            fh.writelines(links + insert_obstacle_lines(to_pdb(refined), obstacles["lines"] if obstacles else []))
     hnet = None
     if getattr(args, "hnet", False):
         # structure.pdb takes the flips: written again at the angles of the optimised network
@@ -131,7 +149,7 @@ def main(argv=None):
         SC_D = hnet.chi[:, :SC_D.shape[1]].to(SC_D.device)
         flipped = dict(protein, atom_positions=get_atom14_coords(batch.X, batch.residue_type, batch.BB_D, SC_D).cpu().squeeze(0).numpy())
         with open(analysis.tmp_pdb, "w") as fh:
-            fh.writelines(insert_obstacle_lines(to_pdb(flipped), obstacles["lines"] if obstacles else []))
+            fh.writelines(links + insert_obstacle_lines(to_pdb(flipped), obstacles["lines"] if obstacles else []))
     if getattr(args, "clashscore", False) or getattr(args, "hydrogens", False):
         from .eval_diffusion import write_allatom
         write_allatom(batch, protein, args.outdir, SC_D, getattr(args, "clashscore", False), getattr(args, "hydrogens", False),

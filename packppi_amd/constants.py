@@ -86,6 +86,43 @@ def _polar_tables():
 polar_class, polar_antecedent = _polar_tables()   # [21,14] u8 class bits, [21,14,2] i8 antecedent slots (-1 = none)
 
 
+# Anchors: metal sites and covalent links (pp_anchor_close).  Starting values from textbook coordination
+# geometry, not tuned against anything and not taken from a library: ideal donor-metal distances by donor element with the few
+# metal-specific exceptions every inorganic text lists, single-bond covalent radii (Cordero et al., Dalton Trans. 2008, rounded), and
+# the angle antecedent-donor-target with its tolerance per donor atom.
+metal_elements = ("LI", "NA", "MG", "K", "CA", "MN", "FE", "CO", "NI", "CU", "ZN", "MO", "CD", "HG")
+metal_donor_default = {"N": 2.1, "O": 2.1, "S": 2.3}                      # A, by donor element
+metal_donor_distance = {("CA", "O"): 2.4, ("NA", "O"): 2.4, ("K", "O"): 2.8}   # (metal, donor element) where it differs
+covalent_radius = {"C": 0.76, "N": 0.71, "O": 0.66, "S": 1.05, "P": 1.07, "F": 0.57, "CL": 1.02, "BR": 1.20, "I": 1.39, "SE": 1.20,
+                   "B": 0.84, "SI": 1.11}
+anchor_angle = {"HIS": {"ND1": (126.0, 15.0), "NE2": (126.0, 15.0)}, "ASP": {"OD1": (120.0, 20.0), "OD2": (120.0, 20.0)},
+                "GLU": {"OE1": (120.0, 20.0), "OE2": (120.0, 20.0)}, "CYS": {"SG": (105.0, 12.0)}, "MET": {"SD": (110.0, 15.0)},
+                "SER": {"OG": (115.0, 15.0)}, "THR": {"OG1": (115.0, 15.0)}, "TYR": {"OH": (115.0, 15.0)}, "LYS": {"NZ": (112.0, 12.0)},
+                "ASN": {"OD1": (130.0, 20.0)}, "GLN": {"OE1": (130.0, 20.0)}}      # (theta0, sigma_theta) in degrees
+ANCHOR_SIGMA_D_METAL, ANCHOR_SIGMA_D_COVALENT = 0.15, 0.10                # A
+PP_ANCHOR_PER_ROW = 4
+
+
+def metal_distance(metal: str, donor_element: str) -> float:
+    """Ideal donor-metal distance in A: ``metal_donor_distance`` where it names the pair, else the default of the donor element."""
+    key = (str(metal).upper(), str(donor_element).upper())
+    if key in metal_donor_distance:
+        return metal_donor_distance[key]
+    if key[1] not in metal_donor_default:
+        raise ValueError(f"no metal-donor distance for donor element {donor_element}")
+    return metal_donor_default[key[1]]
+
+
+def anchor_antecedent(restype: int, slot: int) -> int:
+    """The slot the donor in ``slot`` is bonded to, as the angle term reads it: the lowest slot among its covalent neighbours in
+    ``bond_rows`` (entries below 1.9 A) -- the neighbour towards the backbone."""
+    nb = sorted({int(b) if int(a) == slot else int(a) for rt, a, b, length, _ in bond_rows
+                 if int(rt) == restype and length < 1.9 and slot in (int(a), int(b))})
+    if not nb:
+        raise ValueError(f"{resnames[restype]} slot {slot} has no bonded neighbour")
+    return nb[0]
+
+
 # Explicit hydrogens and the all-atom clashscore (pp_hydrogens / pp_clashscore; DESIGN.md section 29).  The table is DERIVED from the
 # covalent bonds of bond_rows (entries below 1.9 A, as for polar_antecedent) and the atom names; only the hybridisation of the carbons
 # and the protonation of the side-chain nitrogens are written out.  Slots of an all-atom row: 0 .. 13 atom14, 14 + k the k-th hydrogen.

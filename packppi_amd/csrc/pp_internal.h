@@ -146,6 +146,7 @@ enum {
     PP_WS_ALLATOM,            // pp_clashscore: [N][27] position + radius, [N] row sphere, [N][27] class + separations
     PP_WS_HNET,               // pp_hnet_optimize: current atoms, rotor candidates, mover and partner lists, per-sweep counters
     PP_WS_REFINE,             // pp_chi_refine: the candidate angle and coordinate sets, current atoms, mover and partner lists, counters
+    PP_WS_ANCHOR,             // pp_anchor_close: the rows' anchor lists, marks, the list of anchored rows, validity of the entries
     PP_WS_COUNT
 };
 struct pp_workspace {

@@ -140,6 +140,15 @@ def refine_allatom(batch, SC_D, fixed=None, link=None, deltas_deg=(16, 8, 4), ma
                                           radius=radius, obst_polar=obst_polar, want_candidates=want_candidates)
 
 
+def close_anchors(batch, SC_D, anchor_set, fixed=None, max_energy=10.0, sigma_chi=0.3490658503988659, names=None):
+    """Metal sites and covalent links closed on the device (``lib.Context.anchors``, pp_anchor_close), on the
+    geometry plan: every anchor of ``anchor_set`` (``selection.AnchorSet``, rows of the batch) -- a distance restraint, optionally
+    with an angle term, between a side-chain atom and a fixed point -- is closed next to the angles ``SC_D`` by a grid search over
+    the chi angles its donor depends on.  Padded, packed and decoy batches alike.  ``res.chi`` equals ``SC_D`` bit for bit outside
+    the closed rows; ``res.pinned()`` is the mask of rows a later stage must keep.  ``sigma_chi`` is 20 degrees in radians."""
+    return _ctx_for(batch).anchors(SC_D, anchor_set, fixed=fixed, max_energy=max_energy, sigma_chi=sigma_chi, names=names)
+
+
 def polar_bond_keys(partners, seg_offsets=None):
     """The hydrogen bonds behind a ``partners`` array of ``Context.polar`` ([B, L, 14, 4], packed [1, N, 14, 4]) as sorted unique int64
     keys ``(segment * M + low code) * M + high code`` with ``M = 14 * rows`` of the array's second axis, on the device.  A bond is in

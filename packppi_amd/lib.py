@@ -23,7 +23,7 @@ SYMBOLS = ("pp_version", "pp_last_error", "pp_build_id", "pp_plan_set_knn_ties",
            "pp_ctx_set_rng_keys", "pp_noise_seeded", "pp_add_noise_seeded", "pp_sample_seeded",
            "pp_sample_partial", "pp_proximal_pinned", "pp_ctx_live_rows", "pp_ctx_live_mix", "pp_live_mix_host", "pp_ensemble_reduce", "pp_ctx_shell",
            "pp_ensemble_recombine", "pp_ctx_set_obstacles", "pp_sasa", "pp_sample_guided", "pp_sample_corrected",
-           "pp_disulfide_close", "pp_polar", "pp_hydrogens", "pp_clashscore", "pp_hnet_optimize", "pp_chi_refine")
+           "pp_disulfide_close", "pp_polar", "pp_hydrogens", "pp_clashscore", "pp_hnet_optimize", "pp_chi_refine", "pp_anchor_close")
 
 
 FIX_MODES = {"hold": 0, "renoise": 1}         # PP_FIX_HOLD, PP_FIX_RENOISE
@@ -59,6 +59,33 @@ class DisulfideResult(EnsembleResult):
             raise RuntimeError(DISULFIDE_OVERFLOW)
         p = self["partner"].reshape(-1).tolist()
         return [(a, b) for a, b in enumerate(p) if b > a]
+
+
+class AnchorResult(EnsembleResult):
+    """What ``Context.anchors`` returns, all on the device: ``status`` int32 [N] (0 none, 1 closed, 2 kept, -1 open, -2 an entry of
+    the row was dropped), ``report`` fp32 [N, 4] (Emin, E at the pick, the first anchor's distance and angle), ``anchor_report`` fp32
+    [A, 2] (distance and angle of every anchor at its row's pick), ``count`` int32 [n_segments] (closed rows), ``chi`` [B, L, 4]
+    (None for a call without angles).  ``closed()`` and ``pinned()`` read the status back."""
+
+    def _status(self):
+        st = self["status"].reshape(-1).tolist()
+        bad = [r for r, v in enumerate(st) if v == -2]
+        if bad:
+            raise RuntimeError(f"anchors: an entry of row {bad[0]} was dropped on the device (invalid, or a fifth anchor of the row); "
+                               f"{len(bad)} such row(s) -- Context.check_anchors names the entry")
+        return st
+
+    def closed(self):
+        """The closed rows, ascending, on the host (waits for the stream).  ``RuntimeError`` if the device dropped an entry
+        (status -2)."""
+        return [r for r, v in enumerate(self._status()) if v == 1]
+
+    def pinned(self):
+        """bool [N] on the device: the rows a later stage must not move -- closed or kept, and every row of status -2: its other
+        anchors may have closed it (``chi`` then holds the grid angles), and a row whose angles were written is held whatever its
+        status says.  No read-back."""
+        st = self["status"].reshape(-1)
+        return (st == 1) | (st == 2) | (st == -2)
 
 
 class PPTables(C.Structure):
@@ -164,6 +191,7 @@ def load():
     lib.pp_ctx_set_obstacles.argtypes = [vp, vp, vp, i, vp]
     lib.pp_sasa.argtypes = [vp, vp, vp, vp, i, f, vp, vp, vp, vp]
     lib.pp_disulfide_close.argtypes = [vp, vp, vp, vp, i, f, f, f, vp, vp, vp, vp, vp]
+    lib.pp_anchor_close.argtypes = [vp, vp, vp, vp, vp, vp, i, f, f, vp, vp, vp, vp, vp, vp]
     lib.pp_polar.argtypes = [vp, vp, vp, vp, vp, f, f, vp, vp, vp, vp, vp]
     lib.pp_hydrogens.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.pp_clashscore.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, f, f, vp, vp, vp, vp, vp]
@@ -950,6 +978,57 @@ class Context:
                                          float(sigma_chi), _ptr(out), _ptr(partner), _ptr(report), _ptr(count), self._stream()),
                "pp_disulfide_close")
         return DisulfideResult(partner=partner, report=report, count=count, chi=out)
+
+    def check_anchors(self, anchor_set, names=None):
+        """Refuse an ``AnchorSet`` (``selection.AnchorSet``; rows are rows of this context) that ``anchors`` cannot take, naming the
+        offender by the set's label (and ``names``: row -> text): an invalid entry -- a row outside the context or masked out, N, CA,
+        C, the donor or its antecedent missing, a donor that is no side-chain atom moved by a chi angle, an antecedent equal to the
+        donor, a value that is not finite or a ``sigma_d`` that is not positive --, a fifth anchor on a row, and an anchor on a row
+        of another segment than the set claims (``anchor_set.segment``; None claims nothing).  The rules are those of
+        csrc/pp_anchor.hip, restated on the host; reads the masks back."""
+        from .selection import check_anchor_set
+        for k in ("atom_mask", "residue_mask"):
+            if self._t.get(k) is None:
+                raise RuntimeError(f"anchors needs a batch with {k}")
+        if len(anchor_set):
+            check_anchor_set(anchor_set, self._t["residue_type"].reshape(-1).cpu().numpy(), self._t["residue_mask"].reshape(-1).cpu().numpy(),
+                             self._t["atom_mask"].reshape(-1, 14).cpu().numpy(), self.seg_offsets_host, names)
+        return anchor_set
+
+    def anchors(self, chi, anchor_set, fixed=None, max_energy=10.0, sigma_chi=np.deg2rad(20.0), names=None, check=True):
+        """Close the anchors of ``anchor_set`` (``selection.AnchorSet``, rows of this context; a list of sets is concatenated) next
+        to the angles ``chi`` [B, L, 4] (pp_anchor_close): a distance restraint, optionally with an angle
+        term, between a side-chain atom and a fixed point -- a metal ion, the atom of a covalently linked ligand.  The result's
+        ``chi`` equals ``chi`` bit for bit except the first n chi of the closed rows; None: reports only (J = E).  ``fixed`` [N]
+        mask: rows that keep their angles and are only reported (needs ``chi``).  ``max_energy``: the largest grid minimum that still
+        closes; ``sigma_chi`` (radians): what leaving the given angles by that much costs next to one unit of anchor energy.  The
+        set is checked first (``check_anchors``, which reads masks back; ``check=False`` leaves the entries to the device, which
+        drops what it cannot take and sets status -2); the call itself does not wait for the device.  Returns an ``AnchorResult``."""
+        from .selection import AnchorSet
+        dev = self.plan.device
+        if isinstance(anchor_set, (list, tuple)):
+            anchor_set = AnchorSet.concat([self.check_anchors(a, names) if check else a for a in anchor_set if a is not None])
+        if check:
+            self.check_anchors(anchor_set, names)
+        if fixed is not None and chi is None:
+            raise ValueError("anchors: fixed needs chi")
+        chi_in = self._chi(chi) if chi is not None else None
+        fx = self._mask(fixed, "fixed") if fixed is not None else None
+        return self._anchor_close(chi_in, fx, *anchor_set.device_arrays(dev), len(anchor_set), max_energy, sigma_chi)
+
+    def _anchor_close(self, chi_in, fx, ai, at, ap, A, max_energy, sigma_chi, out=None):
+        """pp_anchor_close on device arrays as they are (int32 [A, 4], fp32 [A, 4], fp32 [A, 4]): no check, no read-back.  ``out``:
+        where chi_out goes (``chi_in`` itself: in place), default a new tensor."""
+        if out is None:
+            out = torch.empty_like(chi_in) if chi_in is not None else None
+        status = self._new(self.n_rows, dtype=torch.int32)
+        report = self._new(self.n_rows, 4)
+        arep = self._new(max(A, 1), 2)
+        count = self._new(self.n_segments, dtype=torch.int32)
+        _check(load().pp_anchor_close(self.handle, _ptr(chi_in), _ptr(fx), _ptr(ai), _ptr(at), _ptr(ap), int(A), float(max_energy),
+                                      float(sigma_chi), _ptr(out), _ptr(status), _ptr(report), _ptr(arep), _ptr(count),
+                                      self._stream()), "pp_anchor_close")
+        return AnchorResult(status=status, report=report, anchor_report=arep[:A], count=count, chi=out)
 
     def polar_tables(self):
         """(cls uint8 [N, 14], ante int8 [N, 14, 2]) on the device, what ``polar`` hands to pp_polar by default:

@@ -159,6 +159,57 @@ def _disulfide_refusals(batch, disulfides, return_trajectory, return_list):
     return parse_disulfides(disulfides, dict(chain_id=[n[0] for n in names], residue_index=[n[1] for n in names]))
 
 
+def _anchor_refusals(batch, anchors, return_trajectory, return_list):
+    """The refusals of ``sampling(anchors=)``, behind every other one, as ``_disulfide_refusals``.  Returns (the ``AnchorSet`` of
+    every complex with rows of the batch and the segment it claims, or None entries; whether the request was "auto")."""
+    from .selection import AnchorSet, parse_anchors
+    seg = _get(batch, "seg_offsets")
+    if seg is None and int(batch.num_proteins) != 1:
+        raise ValueError("anchors needs a B = 1 batch or a packed one (batch.pack), not a padded B > 1 batch")
+    if return_trajectory:
+        raise ValueError("return_trajectory with anchors returns the sampler's trajectory: close the anchors separately "
+                         "(Context.anchors)")
+    if return_list:
+        raise ValueError("return_list with anchors is not supported: the pinned proximal stage returns the accepted angles")
+    host = _get(batch, "seg_offsets_host")
+    offs = [int(x) for x in (host if host is not None else (seg.tolist() if seg is not None else [0, int(batch.max_size)]))]
+    n_seg = len(offs) - 1
+    auto = isinstance(anchors, str) and anchors.strip() == "auto"
+    if isinstance(anchors, AnchorSet):
+        sets = [anchors]
+    elif isinstance(anchors, (list, tuple)):
+        sets = list(anchors)
+        if not all(s is None or isinstance(s, AnchorSet) for s in sets):
+            raise ValueError('anchors must be None, an AnchorSet, a list of them (None entries allowed), "auto" or a spec string')
+    elif isinstance(anchors, str):
+        paths = _get(batch, "pdb_path")
+        if paths is None:
+            raise ValueError(f"anchors={anchors.strip()!r} needs batch.pdb_path: the targets are atoms of the PDB file "
+                             "(an AnchorSet needs nothing)")
+        names = _get(batch, "residue_names")
+        if names is None:
+            raise ValueError("anchors from a PDB file needs batch.residue_names (selection.residue_names(protein)): LINK records and "
+                             "spec strings name residues by chain and number")
+        paths = [paths] if isinstance(paths, (str, bytes)) or hasattr(paths, "__fspath__") else list(paths)
+        if len(paths) != n_seg:
+            raise ValueError(f"batch.pdb_path names {len(paths)} files, the batch holds {n_seg} complexes")
+        if not auto and n_seg != 1:
+            raise ValueError("an anchors spec string names the residues of ONE complex: give a packed batch a list of AnchorSets")
+        from .pdb_io import anchor_sites, hetero_atoms
+        rt = batch["residue_type"].reshape(-1).cpu().numpy()
+        sets = []
+        for i, path in enumerate(paths):
+            lo, hi = offs[i], offs[i + 1]
+            prot = dict(chain_id=np.asarray([n[0] for n in names[lo:hi]]), residue_index=np.asarray([n[1] for n in names[lo:hi]]),
+                        aaindex=rt[lo:hi])
+            sets.append(anchor_sites(path, prot, "link") if auto else parse_anchors(anchors, prot, hetero_atoms(path)))
+    else:
+        raise ValueError('anchors must be None, an AnchorSet, a list of them (None entries allowed), "auto" or a spec string')
+    if len(sets) != n_seg:
+        raise ValueError(f"anchors holds {len(sets)} sets, the batch holds {n_seg} complexes (one set per complex, None for none)")
+    return [None if s is None else s.shifted(offs[i], i) for i, s in enumerate(sets)], auto
+
+
 class TDiffusionModule:
     NUM_CHI_ANGLES = 4
     eps = 1e-6
@@ -192,6 +243,8 @@ class TDiffusionModule:
         self.corrector_traces = []
         self.keep_disulfide_report = False    # True: runs with disulfides= append what Context.disulfides returned (plus chi_before) to disulfide_reports (section 26)
         self.disulfide_reports = []
+        self.keep_anchor_report = False       # True: runs with anchors= append what Context.anchors returned (plus the set and chi_before) to anchor_reports (section 34)
+        self.anchor_reports = []
         self.to(device)
 
     # ---- construction ----------------------------------------------------------------------
@@ -365,7 +418,7 @@ class TDiffusionModule:
 
     def sampling(self, batch, use_proximal: bool = False, return_list: bool = False, sde_noise=None, seed=None,
                  fixed_mask=None, fixed_chi=None, fixed_mode="renoise", return_trajectory: bool = False, guide=None, corrector=None,
-                 disulfides=None, refine_allatom: bool = False):
+                 disulfides=None, refine_allatom: bool = False, anchors=None):
         """``seed`` (an int, None = the reference's behaviour): the initial noising and the sde noise come from the counter-based
         generator on the device (csrc/pp_rng.h) instead of torch's global one.  The noise of a complex is then a function of
         (seed, its key, its rows, the step) alone: the same complex gets the same angles alone, anywhere in a packed batch and
@@ -414,7 +467,17 @@ class TDiffusionModule:
         ``refine_allatom`` (False = today's code path, untouched): behind the proximal stage and the disulfide
         closure, ONE ``Context.refine_allatom`` over the rows of the batch lowers the explicit-hydrogen overlaps in chi space.  Rows
         of ``fixed_mask`` and bonded cysteines stay; a residue without a serious overlap keeps its angles bit for bit.  Excludes
-        ``return_trajectory`` and ``return_list``.  ``keep_refine_report`` appends every run's result to ``refine_reports``."""
+        ``return_trajectory`` and ``return_list``.  ``keep_refine_report`` appends every run's result to ``refine_reports``.
+
+        ``anchors`` (None = today's code path, untouched): close metal sites and covalent links behind the
+        sampler and behind the disulfide closure -- ``Context.anchors`` sets the chi angles each anchored donor depends on next to the
+        sample.  An ``AnchorSet`` (``selection.AnchorSet``; rows of its complex), a list of them with one per complex of a packed
+        batch (None entries allowed), "auto" (the LINK records of ``batch.pdb_path``; needs ``batch.residue_names``) or a spec string
+        ``A:94:NE2=A:301:ZN,...`` (one complex; needs both too).  With ``use_proximal`` the proximal stage runs PINNED on the bonded,
+        closed and kept rows and those of ``fixed_mask``; ``refine_allatom`` holds the same rows.  Rows of ``fixed_mask`` keep their
+        angles (status 2).  An anchor on a row a bridge has bonded is refused when it was given explicitly, skipped with a warning
+        under "auto".  A packed or B = 1 batch; excludes ``return_trajectory`` and ``return_list``.  ``keep_anchor_report`` appends
+        every run's result to ``anchor_reports``."""
         if fixed_mask is None:
             fixed_mask = _get(batch, "fixed_mask")
         if refine_allatom and (return_trajectory or return_list):
@@ -422,11 +485,15 @@ class TDiffusionModule:
         gkw, snr = _sampling_refusals(self.hparams.sample_cfg, self.schedule, batch, use_proximal, return_list, sde_noise, seed,
                                       fixed_mask, fixed_mode, return_trajectory, guide, corrector)
         pairs = _disulfide_refusals(batch, disulfides, return_trajectory, return_list) if disulfides is not None else None
+        sets = _anchor_refusals(batch, anchors, return_trajectory, return_list) if anchors is not None else None
         ctx = self._context(batch)
         init, sde_noise, pin = self._initial_angles(ctx, batch, sde_noise, seed, fixed_mask, fixed_chi, fixed_mode)
         out = self._run_sampler(ctx, init, sde_noise, seed, pin, return_trajectory, gkw, snr)
         if return_trajectory:
             return out
+        if anchors is not None:
+            out, link, held = self._anchor_tail(batch, ctx, out, sets, disulfides, pairs, fixed_mask, use_proximal)
+            return self._refine_tail(batch, out, held, link)[0] if refine_allatom else out
         link = None
         if disulfides is not None:
             out, link = self._disulfide_tail(batch, ctx, out, pairs, fixed_mask, use_proximal, want_link=True)
@@ -468,6 +535,53 @@ class TDiffusionModule:
         out = proximal_optimizer_packed(batch, res.chi, cfg.violation_tolerance_factor, cfg.clash_overlap_tolerance, cfg.lamda,
                                         cfg.num_steps, norm_rows=norm_rows, fixed_mask=pinned)[2]
         return (out, res.partner) if want_link else out
+
+    def _anchor_tail(self, batch, ctx, chi, sets, disulfides, pairs, fixed_mask, use_proximal, norm_rows=None):
+        """Behind the sampler of a run with ``anchors``: the disulfide closure if ``disulfides`` asks for one, then the anchor
+        closure, then, with ``use_proximal``, the pinned proximal stage with the bonded, closed and kept rows and the caller's fixed
+        rows held.  ``sets``: what ``_anchor_refusals`` returned.  Returns (angles, the partner array of the bridges or None, the held
+        rows as a bool [1, N] mask on the device)."""
+        sets, auto = sets
+        names = _get(batch, "residue_names")
+        nm = None if names is None else [f"{c}:{n}" for c, n in names]
+        link, held = None, None
+        if disulfides is not None:
+            res = ctx.disulfides(chi=chi, fixed=fixed_mask, pairs=pairs, names=nm)
+            if self.keep_disulfide_report:
+                self.disulfide_reports.append(dict(partner=res.partner, report=res.report, count=res.count, chi_before=chi,
+                                                   chi_after=res.chi))
+            chi, link, held = res.chi, res.partner, (res.partner >= 0).reshape(1, -1)
+            bonded = set(held.reshape(-1).nonzero().reshape(-1).tolist())
+            kept_sets = []
+            for s in sets:
+                hit = [] if s is None else [i for i, r in enumerate(s.rows.tolist()) if r in bonded]
+                if hit and not auto:
+                    r = int(s.rows[hit[0]])
+                    raise ValueError(f"anchors: anchor {s.labels[hit[0]] or hit[0]}: {nm[r] if nm is not None else f'row {r}'} is bonded "
+                                     "in a disulfide bridge; a row takes one or the other")
+                if hit:
+                    import warnings
+                    warnings.warn(f"anchors: {len(hit)} LINK anchor(s) on cysteines a disulfide bridge has bonded are skipped "
+                                  f"({', '.join(s.labels[i] for i in hit)})")
+                    s = s.subset([i for i in range(len(s)) if i not in hit])
+                kept_sets.append(s)
+            sets = kept_sets
+        ares = ctx.anchors(chi, sets, fixed=fixed_mask, names=nm)
+        if self.keep_anchor_report:
+            from .selection import AnchorSet
+            self.anchor_reports.append(dict(status=ares.status, report=ares.report, anchor_report=ares.anchor_report, count=ares.count,
+                                            chi_before=chi, chi_after=ares.chi, anchors=AnchorSet.concat([s for s in sets if s is not None])))
+        pinned = ares.pinned().reshape(1, -1)
+        if held is not None:
+            pinned = pinned | held
+        if fixed_mask is not None:
+            pinned = pinned | (torch.as_tensor(fixed_mask).to(pinned.device) != 0).reshape(1, -1)
+        out = ares.chi
+        if use_proximal:
+            cfg = self.hparams.sample_cfg
+            out = proximal_optimizer_packed(batch, out, cfg.violation_tolerance_factor, cfg.clash_overlap_tolerance, cfg.lamda,
+                                            cfg.num_steps, norm_rows=norm_rows, fixed_mask=pinned)[2]
+        return out, link, pinned
 
     def _initial_angles(self, ctx, batch, sde_noise, seed, fixed_mask, fixed_chi, fixed_mode):
         """(the angles noised to t = 1, the sde noise tensor of an unseeded run or None, the pin's keywords or None).  Seeded: the
@@ -553,7 +667,8 @@ class TDiffusionModule:
         return out[0] if isinstance(out, tuple) else out
 
     def repack(self, batch, fixed_mask=None, *, seed, fixed_chi=None, fixed_mode="renoise", use_proximal: bool = False,
-               return_list: bool = False, norm_rows=None, guide=None, corrector=None, disulfides=None, refine_allatom: bool = False):
+               return_list: bool = False, norm_rows=None, guide=None, corrector=None, disulfides=None, refine_allatom: bool = False,
+               anchors=None):
         """Partial repacking in one call (DESIGN.md sections 13 and 14): ``sampling(batch, seed=seed, fixed_mask=...)`` -- the rows
         of ``fixed_mask`` (default ``batch.fixed_mask``) keep ``fixed_chi`` (default ``batch.SC_D``), the others are sampled around
         them -- and then, with ``use_proximal``, the PINNED proximal stage (pp_proximal_pinned): the clash mask of every complex, its
@@ -565,7 +680,9 @@ class TDiffusionModule:
         ``guide``: as in ``sampling`` (clash-guided sampling of the free rows); None = today's path.  ``corrector``: as in ``sampling``.
         ``disulfides``: as in ``sampling`` -- a kept row never changes its chi1, a bridge between two kept rows
         is only reported; the pinned stage then also keeps the bonded rows.
-        ``refine_allatom``: as in ``sampling``, behind the pinned stage; kept rows stay kept."""
+        ``refine_allatom``: as in ``sampling``, behind the pinned stage; kept rows stay kept.
+        ``anchors``: as in ``sampling`` -- an anchor on a kept row is only reported (status 2); the pinned stage
+        then also keeps the closed rows."""
         if fixed_mask is None:
             fixed_mask = _get(batch, "fixed_mask")
         if refine_allatom and return_list:
@@ -577,6 +694,14 @@ class TDiffusionModule:
             raise ValueError("return_list=True needs use_proximal=True and a B = 1 batch; for a packed batch use "
                              "functional.proximal_optimizer_packed (per-complex losses [n_complexes, num_steps])")
         cfg = self.hparams.sample_cfg
+        if anchors is not None:
+            pairs = _disulfide_refusals(batch, disulfides, False, return_list) if disulfides is not None else None
+            sets = _anchor_refusals(batch, anchors, False, return_list)
+            SC_D_sample = self.sampling(batch, seed=seed, fixed_mask=fixed_mask, fixed_chi=fixed_chi, fixed_mode=fixed_mode, guide=guide,
+                                        corrector=corrector)
+            out, link, held = self._anchor_tail(batch, self._context(batch), SC_D_sample, sets, disulfides, pairs, fixed_mask, use_proximal,
+                                                norm_rows)
+            return self._refine_tail(batch, out, held, link)[0] if refine_allatom else out
         if disulfides is not None:
             pairs = _disulfide_refusals(batch, disulfides, False, return_list)
             SC_D_sample = self.sampling(batch, seed=seed, fixed_mask=fixed_mask, fixed_chi=fixed_chi, fixed_mode=fixed_mode, guide=guide,

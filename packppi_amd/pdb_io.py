@@ -255,6 +255,187 @@ def ssbond_records(prot: Dict, pairs, lengths=None) -> str:
     return "".join(out)
 
 
+def hetero_atoms(pdb_file, mse_to_met: bool = True) -> List[Dict]:
+    """Every atom of a PDB file that the protein dict does not hold and that an anchor can point at: the
+    ``HETATM`` records and the ``ATOM`` records of non-standard residues, metals included, without waters and hydrogens; the first
+    record of an atom wins.  One dict per atom: ``chain``, ``resseq``, ``icode``, ``resname``, ``name``, ``element``, ``xyz``."""
+    out, seen = [], set()
+    for raw in _raw_lines(Path(pdb_file)):
+        het = raw.startswith("HETATM")
+        if not het and not raw.startswith("ATOM"):
+            continue
+        ln = raw.rstrip("\r\n").ljust(80)
+        resname = ln[17:20].strip()
+        if not het and rc.resname_to_idx.get("MET" if (mse_to_met and resname == "MSE") else resname, 20) != 20:
+            continue
+        el = _element(ln)
+        if resname in _WATERS or el in ("H", "D"):
+            continue
+        try:
+            resseq = int(ln[22:26].split()[0])
+            xyz = np.float32((float(ln[30:38]), float(ln[38:46]), float(ln[46:54])))
+        except (ValueError, IndexError):
+            continue
+        key = (ln[21], resseq, ln[26], resname, ln[12:16].strip())
+        if key in seen:
+            continue
+        seen.add(key)
+        out.append(dict(chain=ln[21], resseq=resseq, icode=ln[26], resname=resname, name=ln[12:16].strip(), element=el, xyz=xyz))
+    return out
+
+
+def link_records(pdb_file) -> List[Dict]:
+    """The LINK records of a PDB file by their fixed columns: one dict per record with ``name1``, ``altloc1``, ``resname1``,
+    ``chain1``, ``resseq1``, ``icode1``, the same with 2, ``sym1``, ``sym2`` (text, "" if blank) and ``length`` (float or None).  A
+    record whose residue numbers do not parse is left out."""
+    out = []
+    for raw in _raw_lines(Path(pdb_file)):
+        if not raw.startswith("LINK  "):
+            continue
+        ln = raw.rstrip("\r\n").ljust(80)
+        try:
+            seq1, seq2 = int(ln[22:26]), int(ln[52:56])
+        except ValueError:
+            continue
+        try:
+            length = float(ln[73:78])
+        except ValueError:
+            length = None
+        out.append(dict(name1=ln[12:16].strip(), altloc1=ln[16].strip(), resname1=ln[17:20].strip(), chain1=ln[21], resseq1=seq1,
+                        icode1=ln[26].strip(), name2=ln[42:46].strip(), altloc2=ln[46].strip(), resname2=ln[47:50].strip(),
+                        chain2=ln[51], resseq2=seq2, icode2=ln[56].strip(), sym1=ln[59:65].strip(), sym2=ln[66:72].strip(),
+                        length=length))
+    return out
+
+
+ANCHOR_MODES = ("link", "geometry")
+
+
+def anchor_sites(pdb_file, protein: Dict, mode: str = "link", log=None):
+    """The ``selection.AnchorSet`` of a PDB file's metal sites and covalent links.
+
+    ``"link"``: every LINK record between a side-chain atom (atom14 slot >= 5) of a standard residue of ``protein`` and a HETATM or
+    non-standard-residue atom present in the file, with an identity (1555) or blank symmetry operator on both sides.  The target is
+    that atom's coordinates.  A metal target takes ``constants.metal_distance``; for a covalent link d0 is the record's distance
+    column when it lies in 1.2 to 2.0 A, else the sum of the covalent radii.  Protein-protein LINKs and symmetry mates are skipped with
+    one warning each (``log``, default ``warnings.warn``).
+
+    ``"geometry"``: metals only.  A donor atom (N, O or S of the residues in ``constants.anchor_angle``) within d0 + 0.5 A of a metal
+    IN THE DEPOSITED COORDINATES of ``protein`` becomes an anchor.  The input's side chains decide WHICH atoms coordinate, never where
+    they go: the anchor holds the metal's position and the ideal distance and angle, not the deposited donor position.  A structure
+    without side chains has no donors to find; nothing detects anchors from the backbone alone.  A residue that finds more than four
+    contacts (a carboxylate next to a metal cluster) keeps the four nearest their ideal distance; the others are named in one warning."""
+    from .selection import anchor_entry, anchor_set_of
+    if mode not in ANCHOR_MODES:
+        raise ValueError(f"anchors: mode must be one of {ANCHOR_MODES}")
+
+    def warn(msg):
+        if log is not None:
+            log(msg)
+        else:
+            import warnings
+            warnings.warn(msg)
+
+    het = hetero_atoms(pdb_file)
+    chain_id = np.asarray(protein["chain_id"])
+    number = np.asarray(protein["residue_index"]).astype(np.int64)
+    aa = np.asarray(protein["aaindex"])
+    entries = []
+    if mode == "geometry":
+        xyz, amask = np.asarray(protein["atom_positions"], np.float64), np.asarray(protein["atom_mask"])
+        for h in het:
+            if h["element"] not in rc.metal_elements:
+                continue
+            for r in range(len(aa)):
+                table = rc.anchor_angle.get(rc.resnames[int(aa[r])], {})
+                for atom in table:
+                    slot = rc.atom14_names[int(aa[r])].index(atom)
+                    d0 = rc.metal_distance(h["element"], atom[0])
+                    dist = np.linalg.norm(xyz[r, slot] - np.asarray(h["xyz"], np.float64))
+                    if amask[r, slot] != 0 and dist <= d0 + 0.5:
+                        entries.append((dist - d0, anchor_entry(protein, r, atom, h["xyz"], kind="metal", metal=h["element"],
+                                                                label=f"{chain_id[r]}:{int(number[r])}:{atom}={h['chain']}:{h['resseq']}:{h['name']}")))
+        # a row carries at most four anchors (a carboxylate next to a metal cluster can find more): the four nearest their ideal
+        # distance stay, in the order they were found, and the others are named in one warning
+        keep = set()
+        for r in {e[0] for _, e in entries}:
+            mine = sorted((i for i, (_, e) in enumerate(entries) if e[0] == r), key=lambda i: (abs(entries[i][0]), i))
+            keep.update(mine[:rc.PP_ANCHOR_PER_ROW])
+        dropped = [e[5] for i, (_, e) in enumerate(entries) if i not in keep]
+        if dropped:
+            warn(f"anchor_sites: geometry finds more than {rc.PP_ANCHOR_PER_ROW} donor-metal contacts on a residue of {pdb_file}; "
+                 f"the four nearest their ideal distance are kept, dropped: {', '.join(dropped)}")
+        return anchor_set_of([e for i, (_, e) in enumerate(entries) if i in keep])
+    skipped_pp = skipped_sym = 0
+    for rec in link_records(pdb_file):
+        ends = []
+        for k in ("1", "2"):
+            rows = np.nonzero((chain_id == rec["chain" + k]) & (number == rec["resseq" + k]))[0]
+            std = rc.resname_to_idx.get("MET" if rec["resname" + k] == "MSE" else rec["resname" + k], 20) != 20
+            ends.append((k, rows, std))
+        prot = [e for e in ends if e[2] and len(e[1]) == 1]
+        if len(prot) == 2:
+            skipped_pp += 1
+            continue
+        if len(prot) != 1:
+            continue
+        if any(rec["sym" + k] not in ("", "1555") for k in ("1", "2")):
+            skipped_sym += 1
+            continue
+        k, rows, _ = prot[0]
+        o = "2" if k == "1" else "1"
+        row, atom = int(rows[0]), rec["name" + k]
+        if rec["resname" + k] == "MSE" and atom == "SE":
+            atom = "SD"
+        names = rc.atom14_names[int(aa[row])]
+        if atom not in names or names.index(atom) < 5:
+            continue                                       # a backbone atom or CB: no chi angle moves it
+        tg = [h for h in het if h["chain"] == rec["chain" + o] and h["resseq"] == rec["resseq" + o] and h["name"] == rec["name" + o]
+              and h["resname"] == rec["resname" + o]]
+        if not tg:
+            continue                                       # the partner is not in the file (a water, a hydrogen, a missing atom)
+        el = tg[0]["element"]
+        label = f"{chain_id[row]}:{int(number[row])}:{atom}={tg[0]['chain']}:{tg[0]['resseq']}:{tg[0]['name']}"
+        if el in rc.metal_elements:
+            entries.append(anchor_entry(protein, row, atom, tg[0]["xyz"], kind="metal", metal=el, label=label))
+        elif el in rc.covalent_radius and atom[0] in rc.covalent_radius:
+            d0 = rec["length"] if rec["length"] is not None and 1.2 <= rec["length"] <= 2.0 else rc.covalent_radius[el] + rc.covalent_radius[atom[0]]
+            entries.append(anchor_entry(protein, row, atom, tg[0]["xyz"], d0=d0, kind="link", label=label))
+    if skipped_pp:
+        warn(f"anchor_sites: {skipped_pp} LINK record(s) between two protein residues in {pdb_file} skipped: anchors hold a fixed target")
+    if skipped_sym:
+        warn(f"anchor_sites: {skipped_sym} LINK record(s) to a symmetry mate in {pdb_file} skipped")
+    return anchor_set_of(entries)
+
+
+def link_lines(prot: Dict, anchor_set, hetero, lengths=None, keep=None) -> str:
+    """The LINK records of the anchors of ``anchor_set`` (rows of ``prot``; ``keep``: the indices to write, default all) to the
+    atoms of ``hetero`` (``hetero_atoms``) their targets are, 80 columns each, symmetry 1555 on both sides, the distance from
+    ``lengths`` if given: the text that goes in front of ``to_pdb(prot)``, as ``ssbond_records`` does."""
+    out = []
+    for n, i in enumerate(range(len(anchor_set)) if keep is None else keep):
+        row, slot = int(anchor_set.rows[i]), int(anchor_set.slots[i])
+        tg = [h for h in hetero if np.allclose(h["xyz"], anchor_set.targets[i], atol=1e-3)]
+        if not tg:
+            raise ValueError(f"link_lines: no hetero atom at the target of anchor {anchor_set.labels[i] or i}")
+        h = tg[0]
+        rt = int(np.asarray(prot["aaindex"])[row])
+
+        def name4(a):
+            return a if len(a) == 4 else f" {a}".ljust(4)
+
+        ln = (f"LINK        {name4(rc.atom14_names[rt][slot])} {rc.resnames[rt]:>3} {str(prot['chain_id'][row])[:1]}"
+              f"{int(prot['residue_index'][row]):>4d} ").ljust(42)
+        hn = h["name"]
+        hname = hn.ljust(4) if (len(hn) == 4 or len(h["element"]) == 2) else f" {hn}".ljust(4)
+        ln += f"{hname} {h['resname']:>3} {h['chain']}{h['resseq']:>4d}{h['icode']}".ljust(17)
+        ln += f"{1555:>6d} {1555:>6d}"
+        if lengths is not None:
+            ln += f" {float(lengths[n]):5.2f}"
+        out.append(ln.ljust(80) + "\n")
+    return "".join(out)
+
+
 def contains_sidechains(pdb_file) -> bool:
     """eval_diffusion.py:43-50."""
     with open(pdb_file, "r") as fh:
